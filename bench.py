@@ -1,10 +1,23 @@
 """bench.py -- the gDCA hot path on MI355X, BASELINE.json's headline configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C|B|D|E] [--score frob|DI]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C|B|D|E] [--score frob|DI] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (src/GaussDCA.jl:28-42 of the reference: reweighting ->
 Pi/Pij -> covariance -> SPD inverse -> FN/DI -> APC) over one batch of synthetic input whose
 int8 alignments are already resident in HBM; the N x N score matrices are left in HBM.
+
+A plain run sets up, warms up, times the K steps, writes the outputs if --dump-outputs is given and prints the
+result line.  --full adds everything else the benchmark measures, each with runs of its own: the end-to-end
+gDCA(filename) time, the other configurations of BASELINE.json (default run only, see --no-other-configs), the
+probe for a Julia reference and the CPU baseline (see --no-cpu-baseline).
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed, as a caller of the path receives it:
+DIR/scores_fam<id>.npy, the N x N float64 score matrix of each family whose result is still held in a score buffer
+(for config C, the one family), and DIR/family_stats.npy, one float64 row (N, M, theta, Meff, thresh) per family
+of that step.  At most 64 MB in all; a matrix beyond that is written as a fixed seeded sample
+(scores_fam<id>_sample.npy with its flat column-major indices in scores_fam<id>_sample_index.npy).  With several
+ranks every rank writes its own families, family_stats_rank<r>.npy for the table.
 
   --config C (default)  one family N=500, M=50k per rank per step          (BASELINE.json configs[2], the headline)
   --config B / D        one family N=128, M=10k (theta=0.2) / N=1000, M=100k per rank per step
@@ -367,9 +380,14 @@ def main():
     ap.add_argument("--M", type=int, default=0)
     ap.add_argument("--q", type=int, default=21)
     ap.add_argument("--families", type=int, default=256, help="--config E: families in the batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the end-to-end gDCA(filename) time, the other configurations (`other_configs`), "
+                         "the Julia probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (config C, :frob): skip the lines of :DI, B, D and the E prefix (`other_configs`)")
+                    help="with --full, default run (config C, :frob): skip the lines of :DI, B, D and the E prefix (`other_configs`)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: every rank derives its shard, the ranks meet at the (gloo) barrier and rank 0 prints "
                          "the JSON line with the shards instead of timings (used by the CPU tests of the N > 1 path)")
@@ -457,6 +475,8 @@ def main():
 
     meas = measure(args, args.config, args.score, args.steps, args.warmup, rank, world, local, dev, dist)
     out = summarize(args, meas, world, dist, comm_fallback)  # (every rank: it holds the reductions)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, meas, rank, world)
     if args.dump_families and rank == 0:
         keys = ("N", "M", "n", "ms_total", "ms_theta", "ms_weights", "ms_covariance", "ms_inverse", "ms_score", "inverse_batch")
         with open(args.dump_families, "w") as f:
@@ -467,12 +487,13 @@ def main():
     else:
         cfg = CONFIGS[args.config]
         N0, M0 = meas["fams"][0][1], meas["fams"][0][2]
-        if world == 1 and args.config != "E":
+        if args.full and world == 1 and args.config != "E":
             out["end_to_end_gdca_sec"] = end_to_end(meas["Zh"][0], q, args.score, meas["pc"], meas["ctxs"][0])
         release(meas)
         # every other single-GPU configuration of BASELINE.json in the same run: :DI at the headline size, B
         # (alone and eight at a time through the merged sweep), D and a 32-family prefix of the batch E
-        if world == 1 and args.config == "C" and args.score == "frob" and not args.no_other_configs and not (args.N or args.M):
+        if (args.full and world == 1 and args.config == "C" and args.score == "frob" and not args.no_other_configs
+                and not (args.N or args.M)):
             others = {}
             plan = (("C_DI", "C", "DI", 20, 3, 1, False, 256), ("B", "B", "frob", 40, 5, 1, False, 256),
                     ("B_merged8", "B", "frob", 80, 8, 8, True, 256), ("D", "D", "frob", 5, 1, 1, False, 256),
@@ -501,7 +522,7 @@ def main():
                 except Exception as e:  # noqa: BLE001
                     others[key] = {"error": "%s: %s" % (type(e).__name__, e)}
             out["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline and args.config != "E":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config != "E":
             out["reference_julia"] = probe_reference_julia()
             try:
                 out["cpu_baseline"] = cpu_baseline(N0, M0, q, meas["pc"], cfg["theta"], args.score, meas["fams"][0][3])
@@ -519,9 +540,42 @@ def release(meas):
         c.close()
     meas["ctxs"], meas["ctxs2"] = [], []
     meas["Zd"] = meas["Sd"] = meas["Sd2"] = None
+    meas["last_outputs"] = {}
     import torch
 
     torch.cuda.empty_cache()
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all (over the ranks)
+DUMP_SAMPLE = 1 << 16  # entries of the seeded sample of a score matrix that does not fit any more
+
+
+def dump_outputs(path, meas, rank, world):
+    """--dump-outputs: the score matrices of the last timed step that the buffers still hold (column-major N x N on the
+    device, written as (i, j) arrays) and the per-family results of that step, as float64 .npy files (module docstring)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // max(1, world)
+    F = len(meas["fams"])
+    rows = sorted((float(s["N"]), float(s["M"]), float(s["theta"]), float(s["Meff"]), float(s["thresh"]))
+                  for s in meas["stats"][-F:])
+    table = np.array(rows, dtype=np.float64).reshape(-1, 5)
+    np.save(os.path.join(path, "family_stats.npy" if world == 1 else "family_stats_rank%d.npy" % rank), table)
+    budget -= table.nbytes
+    for fi in sorted(meas["last_outputs"]):
+        fid, N = meas["fams"][fi][0], meas["fams"][fi][1]
+        flat = meas["last_outputs"][fi].reshape(-1)[:N * N]
+        if 8 * N * N <= budget - 2 * 8 * DUMP_SAMPLE:
+            S = flat.cpu().numpy().reshape((N, N), order="F")
+            np.save(os.path.join(path, "scores_fam%03d.npy" % fid), np.ascontiguousarray(S, dtype=np.float64))
+            budget -= 8 * N * N
+        elif 2 * 8 * DUMP_SAMPLE <= budget:
+            idx = np.sort(np.random.default_rng(fid).choice(N * N, size=min(DUMP_SAMPLE, N * N), replace=False))
+            vals = flat.cpu().numpy()[idx]
+            np.save(os.path.join(path, "scores_fam%03d_sample.npy" % fid), vals.astype(np.float64))
+            np.save(os.path.join(path, "scores_fam%03d_sample_index.npy" % fid), idx.astype(np.float64))
+            budget -= 2 * 8 * idx.size
 
 
 def measure(args, config, score_name, steps, warmup, rank, world, local, dev, dist):
@@ -563,10 +617,10 @@ def measure(args, config, score_name, steps, warmup, rank, world, local, dev, di
         ctxs2 = [ctxs[0].peer() for _ in range(P)]
         Sd2 = [torch.empty((nmax, nmax), dtype=torch.float64, device=dev) for _ in range(P)]
 
-    def run_steps_phased(count, sink):
+    def run_steps_phased(count, sink, owners):
         """`count` steps, the rank's families taken P at a time and batched by phase (gdca_run_dev_phased).  Two sets of P
         contexts alternate: the next batch is enqueued (on the other set's stream) before the previous one is collected, so
-        the GPU never waits for the host to enqueue a batch."""
+        the GPU never waits for the host to enqueue a batch.  owners: score buffer -> (step, family index) of its last run."""
         work = [fi for _ in range(count) for fi in range(len(fams))]
         pending = None
         for b, a in enumerate(range(0, len(work), P)):
@@ -580,25 +634,28 @@ def measure(args, config, score_name, steps, warmup, rank, world, local, dev, di
             g.run_dev_phased(cset, [Zd[fi].data_ptr() for fi in grp], [fams[fi][1] for fi in grp],
                              [fams[fi][2] for fi in grp], [q] * len(grp), pc, cfg["theta"], score,
                              [x.data_ptr() for x in sset])
+            for k, fi in enumerate(grp):
+                owners[("Sd2" if alt else "Sd", k)] = ((a + k) // len(fams), fi)
             if pending is not None:
                 sink.extend(c.collect() for c in pending)
             pending = cset
         if pending is not None:
             sink.extend(c.collect() for c in pending)
 
-    def run_steps(count, sink):
+    def run_steps(count, sink, owners):
         """`count` steps; inside a step the rank's families go round-robin over the P contexts; a context's previous
         pass is collected (stream sync + stats) right before it is given the next one."""
         if phased:
-            return run_steps_phased(count, sink)
+            return run_steps_phased(count, sink, owners)
         t = 0
-        for _ in range(count):
+        for s in range(count):
             for fi, (_, N, M, _) in enumerate(fams):
                 c = t % P
                 t += 1
                 if busy[c]:
                     sink.append(ctxs[c].collect())
                 ctxs[c].run_dev_async(Zd[fi].data_ptr(), N, M, q, pc, cfg["theta"], score, Sd[c].data_ptr())
+                owners[("Sd", c)] = (s, fi)
                 busy[c] = True
         for c in range(P):
             if busy[c]:
@@ -614,15 +671,19 @@ def measure(args, config, score_name, steps, warmup, rank, world, local, dev, di
 
     # every context is warmed (workspace allocation: hipMalloc synchronises the device) before the clock starts
     warm = max(warmup, 1, -(-(2 * P if phased else P) // max(1, len(fams))))
-    run_steps(warm, [])
+    run_steps(warm, [], {})
     barrier()
     t0 = time.perf_counter()
     stats = []
-    run_steps(steps, stats)
+    owners = {}
+    run_steps(steps, stats, owners)
     barrier()
     dt = time.perf_counter() - t0
+    # the score buffers that hold a family of the last timed step, by family index
+    bufs = {"Sd": Sd, "Sd2": Sd2}
+    last = {fi: bufs[key][k] for (key, k), (s, fi) in sorted(owners.items()) if s == steps - 1}
     return dict(config=config, score_name=score_name, pc=pc, fams=fams, Zh=Zh, Zd=Zd, Sd=Sd, Sd2=Sd2, ctxs=ctxs, ctxs2=ctxs2,
-                stats=stats, dt=dt, steps=steps, warm=warm, P=P, phased=phased)
+                stats=stats, dt=dt, steps=steps, warm=warm, P=P, phased=phased, last_outputs=last)
 
 
 def pmc_kernel_traffic(N, M, score, prefix):
