@@ -45,6 +45,20 @@ class Params(C.Structure):
     _fields_ = [("pseudocount", C.c_double), ("theta", C.c_double), ("score", C.c_int32), ("apc", C.c_int32)]
 
 
+MULTI_MAX = 16  # GDCA_MULTI_MAX: settings one gdca_run_multi call takes
+
+
+def _multi_params(settings, theta: float, apc: bool):
+    """settings: (pseudocount, score) or (pseudocount, score, apc) per member, score SCORE_FROB | SCORE_DI -> a Params[K] array"""
+    K = len(settings)
+    prm = (Params * max(K, 1))()
+    for k, s in enumerate(settings):
+        pc, score = s[0], s[1]
+        a = s[2] if len(s) > 2 else apc
+        prm[k] = Params(float(pc), float(theta), int(score), 1 if a else 0)
+    return prm, K
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("theta", C.c_double), ("Meff", C.c_double), ("pair_identity_sum", C.c_uint64),
@@ -136,6 +150,10 @@ SYMBOLS = {
     "gdca_run_ranked_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdca_run_ranked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdca_run_multi": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdca_run_multi_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdca_run_ranked_multi": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -270,6 +288,64 @@ class Context:
                                       _p(sc), C.byref(st))
         self.check(rc, st.info)
         return ii, jj, sc, st.as_dict()
+
+    # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
+    def _check_multi(self, rc: int, sts, results):
+        """Raise as check() does for the first failing member (its info); the exception carries every member's result in
+        `.results` (a failing member's arrays are unspecified) and the members' statuses in `.statuses`."""
+        if rc == GDCA_OK:
+            return
+        info = 0
+        statuses = []
+        for st in sts:
+            statuses.append(GDCA_OK if st.info == 0 else (GDCA_ENOTPD if st.info > 0 else GDCA_ENOCONV))
+        for st, s in zip(sts, statuses):
+            if s == rc:
+                info = st.info
+                break
+        try:
+            self.check(rc, info)
+        except Exception as e:
+            e.results = results
+            e.statuses = statuses
+            raise
+
+    def run_multi(self, Zf: np.ndarray, q: int, settings, theta: float, apc: bool = True):
+        """gdca_run_multi.  Zf: int8 (N, M), Fortran-contiguous; settings: (pseudocount, score[, apc]) per member (score
+        SCORE_FROB | SCORE_DI), one theta for all.  Returns [(S[N,N], stats dict)] in the order of settings, each bit for bit
+        what run() gives for that setting."""
+        N, M = Zf.shape
+        prm, K = _multi_params(settings, theta, apc)
+        S = np.empty((max(K, 1), N, N), dtype=np.float64)  # block k = S[k] read as column-major: S[k].T
+        sts = (Stats * max(K, 1))()
+        rc = self.lib.gdca_run_multi(self.h, _p(Zf), N, M, int(q), prm, K, _p(S), sts)
+        results = [(np.asfortranarray(S[k].T), sts[k].as_dict()) for k in range(K)]
+        self._check_multi(rc, sts[:K], results)
+        return results
+
+    def run_multi_dev(self, Z_ptr: int, N: int, M: int, q: int, settings, theta: float, S_ptr: int, apc: bool = True):
+        """Device-pointer form: S_ptr holds K consecutive N x N column-major matrices.  Returns the stats dicts."""
+        prm, K = _multi_params(settings, theta, apc)
+        sts = (Stats * max(K, 1))()
+        rc = self.lib.gdca_run_multi_dev(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), prm, K, C.c_void_p(S_ptr), sts)
+        results = [sts[k].as_dict() for k in range(K)]
+        self._check_multi(rc, sts[:K], results)
+        return results
+
+    def run_ranked_multi_ptr(self, Z_ptr: int, N: int, M: int, q: int, settings, theta: float, min_separation: int, apc: bool = True):
+        """gdca_run_ranked_multi on a HOST matrix given by address.  Returns [(i, j, score, stats)] in the order of settings, each
+        what run_ranked_ptr() gives for that setting."""
+        prm, K = _multi_params(settings, theta, apc)
+        n = max(int(self.lib.gdca_ranking_length(int(N), int(min_separation))), 0)
+        ii = np.empty((max(K, 1), n), dtype=np.int32)
+        jj = np.empty((max(K, 1), n), dtype=np.int32)
+        sc = np.empty((max(K, 1), n), dtype=np.float64)
+        sts = (Stats * max(K, 1))()
+        rc = self.lib.gdca_run_ranked_multi(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), prm, K, int(min_separation), _p(ii), _p(jj),
+                                            _p(sc), sts)
+        results = [(ii[k], jj[k], sc[k], sts[k].as_dict()) for k in range(K)]
+        self._check_multi(rc, sts[:K], results)
+        return results
 
     def run_ranked_async_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, score: int, min_separation: int,
                              apc: bool = True):

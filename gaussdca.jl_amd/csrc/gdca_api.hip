@@ -48,6 +48,8 @@ struct gdca_ctx {
     gdca_buf hcand;               // reweighting, bound forms: the list of candidate pairs
     gdca_buf himg;                // reweighting, fp4 form: the image of the three low bit planes as E2M1 nibbles
     gdca_buf rankws;              // device ranking: keys, values, histograms, the three output arrays
+    gdca_buf Pij;                 // gdca_run_multi: Pij_true of the alignment (n x n, ld = n), the covariance of every pseudocount is built from it
+    gdca_buf sc_front;            // gdca_run_multi: the scalars as the front end left them (every pseudocount group starts from them)
     // an enqueued ranked run (gdca_run_ranked_async): where its ranking will be, and whether enqueueing it worked
     bool rank_pending = false;
     long long rank_len = 0;
@@ -77,6 +79,7 @@ struct gdca_ctx {
     int pend_N, pend_M, pend_q, pend_n, pend_npad, pend_nupd;
     int pend_batch;            // families that shared this run's SPD-inverse launch (1: a launch of its own)
     const int8_t *pend_Z;      // what a refinement at collect time needs to build C again and to score again
+    const double *pend_pij;    // ... or, a pseudocount group of gdca_run_multi, the stored Pij_true C is built again from (nullptr: the tallies)
     double *pend_S;
     gdca_params pend_p;
     int pend_refined;
@@ -491,7 +494,8 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
     if (ctx->own_stream || ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     gdca_buf *bufs[] = {&ctx->Zt, &ctx->Zp, &ctx->hist, &ctx->Zb, &ctx->hcnt, &ctx->nk, &ctx->W, &ctx->Wfix, &ctx->Pifix,
                         &ctx->Pipc, &ctx->A, &ctx->G, &ctx->H, &ctx->P, &ctx->Sg, &ctx->Dblk, &ctx->Ld,
-                        &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg};
+                        &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg,
+                        &ctx->Pij, &ctx->sc_front};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < N_SCRATCH; ++i)
@@ -644,6 +648,14 @@ static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, 
     return check_launch(ctx, "weights");
 }
 
+// true where the pseudocount alone bounds cond(C) below the refinement threshold whatever the alignment (pi_max <= (1 - pc) + pc / q):
+// then the first build of a covariance (tally_stage, gdca_run_multi) does not even launch k_cov_norm1
+static bool norm1_settled(const gdca_ctx *ctx, int N, int q, double pc)
+{
+    const double pi_cap = (1.0 - pc) + pc / (double)q;
+    return pc > 0.0 && 2.0 * (double)N * pi_cap * (double)q * (double)q / pc <= ctx->tune.refine_cond && ctx->tune.refine != 1;
+}
+
 // stage 3: Pi, pair tallies.  mode 0 -> Pij_true (ld) ; mode 1 -> covariance (ld)
 // want_norm1 (mode 1): the fused path's first build -- sc->pi_max, and sc->mat_norm1 = ||C||_1 where the screen needs it (k_cov_norm1)
 static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, int q, const double *Meff_dev, double pc,
@@ -672,9 +684,7 @@ static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, in
     if (tm) CHK(mark(ctx, 10));
     // ||C||_1 for the refinement screen, where the bound that costs nothing (2 N pi_max) does not settle it (k_cov_norm1)
     // (not even launched where the answer is known on the host: pi_max <= (1 - pc) + pc / q whatever the alignment)
-    const double pi_cap = (1.0 - pc) + pc / (double)q;
-    const bool settled = pc > 0.0 && 2.0 * (double)N * pi_cap * (double)q * (double)q / pc <= ctx->tune.refine_cond && ctx->tune.refine != 1;
-    if (want_norm1 && !settled)
+    if (want_norm1 && !norm1_settled(ctx, N, q, pc))
         gdca_launch_cov_norm1(s, out, ld, N, q, pc, ctx->tune.refine_cond, (gdca_dev_scalars *)ctx->sc.p, ctx->tune.refine == 1);
     return check_launch(ctx, "tally");
 }
@@ -867,6 +877,31 @@ static gdca_status cholesky_stage(gdca_ctx *ctx, int n, int n_pad)
     return check_launch(ctx, "cholesky_inverse");
 }
 
+// gdca_run_multi: the covariance of pseudocount pc into dst (ld = n_pad; the padding is the caller's) from the stored Pij_true and the
+// kept single-site tallies Pifix -- Pi' of pc (k_pi_finalize), then k_cov_from_pij: bit for bit what tally_stage's mode 1 writes for
+// pc.  want_norm1: a group's first build -- sc->pi_max and, where the screen needs it, sc->mat_norm1, as the fused path's first build
+static gdca_status cov_from_pij_stage(gdca_ctx *ctx, int N, int M, int q, double pc, double *dst, size_t ld, bool want_norm1)
+{
+    hipStream_t s = ctx->stream;
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    gdca_launch_pi_finalize(s, (const unsigned long long *)ctx->Pifix.p, N, q, gdca_fix_shift(M), &sc->Meff, pc, nullptr, (double *)ctx->Pipc.p,
+                            want_norm1 ? &sc->pi_max : nullptr);
+    gdca_launch_cov_from_pij(s, (const double *)ctx->Pij.p, (const double *)ctx->Pipc.p, N, q, pc, dst, ld);
+    if (want_norm1 && !norm1_settled(ctx, N, q, pc))
+        gdca_launch_cov_norm1(s, dst, ld, N, q, pc, ctx->tune.refine_cond, sc, ctx->tune.refine == 1);
+    return check_launch(ctx, "covariance from Pij_true");
+}
+
+// The covariance of the enqueued run once more into dst (ld = n_pad), for the collect's second attempt, refinement and Cholesky
+// fallback (the sweep worked in place): from the tallies -- or, a pseudocount group of gdca_run_multi, from the stored Pij_true
+static gdca_status rebuild_covariance(gdca_ctx *ctx, double *dst)
+{
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    const int N = ctx->pend_N, M = ctx->pend_M, q = ctx->pend_q;
+    if (ctx->pend_pij) return cov_from_pij_stage(ctx, N, M, q, ctx->pend_p.pseudocount, dst, (size_t)ctx->pend_npad, false);
+    return tally_stage(ctx, ctx->pend_Z, N, M, q, &sc->Meff, ctx->pend_p.pseudocount, 1, nullptr, dst, (size_t)ctx->pend_npad);
+}
+
 static gdca_status begin(gdca_ctx *ctx)
 {
     CHK(not_pending(ctx));
@@ -902,9 +937,9 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
         // once more from the tallies -- the sweep works in place --, the inverse again as a launch of its own behind the pipeline's
         // gate, the scores again.  A launch that fails option SWEEP_RETRIES times in a row (default 2) is reported as GDCA_EHIP.
         gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-        const int N = ctx->pend_N, M = ctx->pend_M, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
+        const int N = ctx->pend_N, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
         ++ctx->pend_attempt;
-        CHK(tally_stage(ctx, ctx->pend_Z, N, M, q, &sc->Meff, ctx->pend_p.pseudocount, 1, nullptr, (double *)ctx->A.p, (size_t)n_pad));
+        CHK(rebuild_covariance(ctx, (double *)ctx->A.p));
         gdca_launch_pad_identity(ctx->stream, (double *)ctx->A.p, n, n_pad);
         HIPCHK(hipMemsetAsync(&sc->info, 0, sizeof(int), ctx->stream));
         HIPCHK(hipMemsetAsync(&sc->di_noconv, 0, sizeof(int), ctx->stream));
@@ -925,12 +960,12 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
         // scores are computed again from the refined inverse.  Synchronous and several times the cost of the run itself: a path
         // for rare inputs (pseudocounts far below the 0.2 .. 0.8 gDCA is used with), taken here so that the enqueue side stays lean.
         gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-        const int N = ctx->pend_N, M = ctx->pend_M, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
+        const int N = ctx->pend_N, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
         const size_t mat = (size_t)n_pad * n_pad * sizeof(double);
         CHK(ensure(ctx, ctx->C2, mat));
         CHK(ensure(ctx, ctx->B0, mat));
         CHK(ensure(ctx, ctx->Rt, mat));
-        CHK(tally_stage(ctx, ctx->pend_Z, N, M, q, &sc->Meff, ctx->pend_p.pseudocount, 1, nullptr, (double *)ctx->C2.p, (size_t)n_pad));
+        CHK(rebuild_covariance(ctx, (double *)ctx->C2.p));
         gdca_launch_pad_identity(ctx->stream, (double *)ctx->C2.p, n, n_pad);
         gdca_launch_newton_schulz(ctx->stream, (double *)ctx->A.p, (const double *)ctx->C2.p, (double *)ctx->B0.p, (double *)ctx->Rt.p, n_pad,
                                   &sc->ns_resid);
@@ -947,9 +982,9 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
         // reference's way -- the covariance from the tallies again, blocked dpotrf + dpotri, the scores from that inverse.  Its
         // verdict on positive definiteness is LAPACK's.
         gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-        const int N = ctx->pend_N, M = ctx->pend_M, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
+        const int N = ctx->pend_N, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
         CHK(ensure(ctx, ctx->C2, (size_t)n_pad * n_pad * sizeof(double)));
-        CHK(tally_stage(ctx, ctx->pend_Z, N, M, q, &sc->Meff, ctx->pend_p.pseudocount, 1, nullptr, (double *)ctx->C2.p, (size_t)n_pad));
+        CHK(rebuild_covariance(ctx, (double *)ctx->C2.p));
         gdca_launch_pad_identity(ctx->stream, (double *)ctx->C2.p, n, n_pad);
         CHK(cholesky_stage(ctx, n, n_pad));
         CHK(inverse_norm_stage(ctx, n, n_pad));
@@ -1076,6 +1111,7 @@ static gdca_status run_front(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int3
     ctx->pend_tally_timed = timed && ctx->tune.refine != 0;
     ctx->pend_fn_timed = false;
     ctx->pend_Z = Z_dev;
+    ctx->pend_pij = nullptr;
     ctx->pend_p = *p;
     ctx->pend_refined = 0;
     ctx->pend_N = N;
@@ -1642,6 +1678,228 @@ gdca_status gdca_run_ranked(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int3
     if (ctx && gdca_ranking_length(N, min_separation) > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     CHK(gdca_run_ranked_async(ctx, Z_host, N, M, q, p, min_separation));
     return gdca_run_ranked_collect(ctx, i_out, j_out, score_out, st);
+}
+
+}  // extern "C"
+
+// ---- several pseudocount / score settings of one alignment (gdca_run_multi, include/gdca.h) -------------------------------------
+// Only the pseudocount and what follows it depend on the setting: theta, the reweighting, Pi and the pair tallies run ONCE, the pair
+// tallies in their Pij_true form (k_pair_tally mode 0) into ctx->Pij.  Then for every distinct pseudocount, in order of first
+// appearance (a "group"): the covariance from Pij_true (k_cov_from_pij: bit for bit the fused build of that pseudocount), the DI
+// diagonal blocks if a member asks for DI, the inverse -- collected for the group's first member exactly like a single run (second
+// attempt, refinement, Cholesky fallback: each builds C again from Pij_true, rebuild_covariance) -- and every further member scored
+// from the inverse the collect left.  A single run of any member would compute the same C, the same inverse and the same scores.
+struct multi_rank {
+    int sep;
+    long long len;
+    int32_t *i_out, *j_out;
+    double *score_out;
+};
+
+// every member as run_check_args checks a single run, and one theta setting (equal, or all negative: :auto) -- before anything is enqueued
+static gdca_status multi_check_args(gdca_ctx *ctx, const void *Z, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K, double *S)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (K < 1 || K > GDCA_MULTI_MAX) return fail(ctx, GDCA_EINVAL, "number of settings must be between 1 and GDCA_MULTI_MAX%s%s", "", "");
+    if (!p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    for (int k = 0; k < K; ++k) {
+        CHK(run_check_args(ctx, (const int8_t *)Z, N, M, q, &p[k], S));
+        if (!(p[k].theta == p[0].theta || (p[k].theta < 0.0 && p[0].theta < 0.0)))
+            return fail(ctx, GDCA_EINVAL, "every setting of one call must have the same theta%s%s", "", "");
+    }
+    return not_pending(ctx);
+}
+
+static gdca_status multi_rank_member(gdca_ctx *ctx, const multi_rank *rk, int k, const double *S_dev)
+{
+    if (rk->len == 0) return GDCA_OK;
+    int32_t *ii, *jj;
+    double *sv;
+    CHK(ranking_stage(ctx, S_dev, ctx->pend_N, rk->sep, rk->len, &ii, &jj, &sv));
+    const size_t at = (size_t)k * (size_t)rk->len;
+    return ranking_to_host(ctx, rk->len, ii, jj, sv, rk->i_out + at, rk->j_out + at, rk->score_out + at);
+}
+
+// K >= 2 members, arguments checked.  Member k's scores go to S_dev + k S_stride (S_stride 0: one matrix, ranked before the next
+// member overwrites it); st: K entries
+static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int q, const gdca_params *p, int K, double *S_dev, size_t S_stride,
+                             gdca_stats *st, const multi_rank *rk)
+{
+    hipStream_t s = ctx->stream;
+    const int sdim = q - 1, n = N * sdim, n_pad = round_up(n, GDCA_TILE);
+    gdca_status mst[GDCA_MULTI_MAX];
+    bool done[GDCA_MULTI_MAX];
+    for (int k = 0; k < K; ++k) {
+        memset(&st[k], 0, sizeof(st[k]));
+        mst[k] = GDCA_OK;
+        done[k] = false;
+    }
+    // ---- the front end, once: theta, reweighting, Pi, Pij_true (ld = n) ----
+    CHK(begin(ctx));
+    const bool timed = ctx->timing;
+    if (timed) CHK(need_events(ctx, 18));
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    if (timed) CHK(mark(ctx, 0));
+    CHK(weights_stage(ctx, Z_dev, N, M, q, p[0].theta, -1, false, timed ? 1 : -1));
+    if (timed) CHK(mark(ctx, 2));
+    CHK(ensure(ctx, ctx->Pij, (size_t)n * n * sizeof(double)));
+    CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
+    CHK(ensure(ctx, ctx->sc_front, sizeof(gdca_dev_scalars)));
+    CHK(tally_stage(ctx, Z_dev, N, M, q, &sc->Meff, p[0].pseudocount, 0, nullptr, (double *)ctx->Pij.p, (size_t)n));
+    HIPCHK(hipMemcpyAsync(ctx->sc_front.p, sc, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
+    ctx->pend_timed = timed;
+    ctx->pend_stamped = ctx->stamped;
+    ctx->pend_front_batch = 1;
+    ctx->pend_score_batch = 1;
+    ctx->pend_tally_timed = false;
+    ctx->pend_Z = Z_dev;
+    ctx->pend_pij = (const double *)ctx->Pij.p;
+    ctx->pend_N = N;
+    ctx->pend_M = M;
+    ctx->pend_q = q;
+    ctx->pend_n = n;
+    ctx->pend_npad = n_pad;
+    double ms_theta = 0.0, ms_weights = 0.0;
+    bool first = true;
+    for (int k0 = 0; k0 < K; ++k0) {
+        if (done[k0]) continue;
+        // ---- the group of p[k0].pseudocount: covariance, DI blocks, inverse; its first member collected like a single run ----
+        const double pc = p[k0].pseudocount;
+        bool di = false;
+        for (int k = k0; k < K; ++k) di = di || (p[k].pseudocount == pc && p[k].score == GDCA_SCORE_DI);
+        if (!first) {
+            // (every group starts from the scalars the front end left: theta, Meff, ...; its own -- pi_max, norms, info -- zero)
+            HIPCHK(hipMemcpyAsync(sc, ctx->sc_front.p, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
+            ctx->pend_attempt = 0;
+            ctx->pend_rescored = false;
+            if (timed) CHK(mark(ctx, 2));
+        }
+        ctx->pend_p = p[k0];
+        ctx->pend_refined = 0;
+        ctx->pend_fn_timed = false;
+        CHK(cov_from_pij_stage(ctx, N, M, q, pc, (double *)ctx->A.p, (size_t)n_pad, ctx->tune.refine != 0));
+        gdca_launch_pad_identity(s, (double *)ctx->A.p, n, n_pad);
+        if (di) {
+            CHK(ensure(ctx, ctx->Dblk, (size_t)N * sdim * sdim * sizeof(double)));
+            CHK(ensure(ctx, ctx->Ld, (size_t)N * sdim * sdim * sizeof(double)));
+            gdca_launch_save_diag_blocks(s, (const double *)ctx->A.p, (size_t)n_pad, N, sdim, (double *)ctx->Dblk.p);
+            gdca_launch_diag_chol(s, (const double *)ctx->Dblk.p, N, sdim, (double *)ctx->Ld.p);
+        }
+        CHK(check_launch(ctx, "covariance"));
+        if (timed) CHK(mark(ctx, 3));
+        CHK(run_inverse(ctx));
+        double *S0 = S_dev + (size_t)k0 * S_stride;
+        CHK(run_score(ctx, &p[k0], S0));
+        const gdca_status gs = gdca_run_collect(ctx, &st[k0]);
+        if (gs == GDCA_EHIP || gs == GDCA_ENOMEM || gs == GDCA_EINVAL) return gs;  // (EINVAL here: a symbol outside 1..q)
+        mst[k0] = gs;
+        done[k0] = true;
+        if (first) {
+            ms_theta = st[k0].ms_theta;
+            ms_weights = st[k0].ms_weights;
+            first = false;
+        } else {
+            st[k0].ms_theta = ms_theta;
+            st[k0].ms_weights = ms_weights;
+        }
+        if (gs == GDCA_OK && rk) CHK(multi_rank_member(ctx, rk, k0, S0));
+        // ---- the group's further members: scored from the inverse the collect left in ctx->A ----
+        const int ginfo = ctx->sc_host->info;  // the group's: 0, or the leading minor that is not positive definite
+        for (int k = k0 + 1; k < K; ++k) {
+            if (done[k] || p[k].pseudocount != pc) continue;
+            done[k] = true;
+            st[k] = st[k0];
+            st[k].info = ginfo;
+            st[k].ms_fn = 0.0;
+            st[k].ms_score = 0.0;
+            if (ginfo != 0) {
+                mst[k] = GDCA_ENOTPD;
+                continue;
+            }
+            double *Sk = S_dev + (size_t)k * S_stride;
+            ctx->pend_fn_timed = false;
+            HIPCHK(hipMemsetAsync(&sc->di_noconv, 0, sizeof(int), s));
+            if (timed) CHK(mark(ctx, 11));
+            CHK(score_stage(ctx, N, sdim, n_pad, p[k].score, p[k].apc, Sk, timed));
+            if (timed) CHK(mark(ctx, 5));
+            CHK(fetch_scalars(ctx));
+            if (timed) {
+                float ms = 0.f;
+                HIPCHK(hipEventElapsedTime(&ms, ctx->ev[11], ctx->ev[5]));
+                st[k].ms_score = ms;
+                HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[5]));
+                st[k].ms_total = ms;
+                if (ctx->pend_fn_timed && ctx->pend_refined == 0) {
+                    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[8]));
+                    st[k].ms_fn = ms;
+                }
+            }
+            if (ctx->sc_host->di_noconv != 0) {
+                st[k].info = -ctx->sc_host->di_noconv;
+                mst[k] = fail(ctx, GDCA_ENOCONV, "eigenvalue iteration of a DI block did not converge%s%s", "", "");
+                continue;
+            }
+            if (rk) CHK(multi_rank_member(ctx, rk, k, Sk));
+        }
+    }
+    for (int k = 0; k < K; ++k)
+        if (mst[k] != GDCA_OK) {
+            char msg[sizeof(ctx->err)];
+            snprintf(msg, sizeof(msg), "setting %d: %s", k, mst[k] == GDCA_ENOTPD ? "covariance matrix is not positive definite"
+                                                                               : "eigenvalue iteration of a DI block did not converge");
+            memcpy(ctx->err, msg, sizeof(msg));
+            return mst[k];
+        }
+    return GDCA_OK;
+}
+
+extern "C" {
+
+gdca_status gdca_run_multi_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K,
+                               double *S_dev, gdca_stats *st)
+{
+    CHK(multi_check_args(ctx, Z_dev, N, M, q, p, K, S_dev));
+    if (K == 1) return gdca_run_dev(ctx, Z_dev, N, M, q, p, S_dev, st);
+    gdca_stats own[GDCA_MULTI_MAX];
+    return run_multi(ctx, Z_dev, N, M, q, p, K, S_dev, (size_t)N * N, st ? st : own, nullptr);
+}
+
+gdca_status gdca_run_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K,
+                           double *S_host, gdca_stats *st)
+{
+    CHK(multi_check_args(ctx, Z_host, N, M, q, p, K, S_host));
+    if (K == 1) return gdca_run(ctx, Z_host, N, M, q, p, S_host, st);
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t mat = (size_t)N * N;
+    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
+    CHK(ensure(ctx, ctx->scratch[1], (size_t)K * mat * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
+    gdca_stats own[GDCA_MULTI_MAX];
+    const gdca_status rs = run_multi(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, K, (double *)ctx->scratch[1].p, mat, st ? st : own, nullptr);
+    if (rs != GDCA_OK && rs != GDCA_ENOTPD && rs != GDCA_ENOCONV) return rs;
+    // (the members that did not fail are results: all K blocks come back)
+    HIPCHK(hipMemcpyAsync(S_host, ctx->scratch[1].p, (size_t)K * mat * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return rs;
+}
+
+gdca_status gdca_run_ranked_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K,
+                                  int32_t min_separation, int32_t *i_out, int32_t *j_out, double *score_out, gdca_stats *st)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (min_separation < 1) return fail(ctx, GDCA_EINVAL, "min_separation < 1%s%s", "", "");
+    double placeholder = 0.0;  // (no score matrix crosses this ABI: the one the members share is the context's)
+    CHK(multi_check_args(ctx, Z_host, N, M, q, p, K, &placeholder));
+    const long long len = gdca_ranking_length(N, min_separation);
+    if (len > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (K == 1) return gdca_run_ranked(ctx, Z_host, N, M, q, p, min_separation, i_out, j_out, score_out, st);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
+    CHK(ensure(ctx, ctx->scratch[1], (size_t)N * N * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
+    const multi_rank rk{min_separation, len, i_out, j_out, score_out};
+    gdca_stats own[GDCA_MULTI_MAX];
+    return run_multi(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, K, (double *)ctx->scratch[1].p, 0, st ? st : own, &rk);
 }
 
 // ---- caller-visible device buffers ----------------------------------------------------------------------

@@ -130,6 +130,9 @@ void gdca_launch_colblock(hipStream_t s, const int8_t *Z, int8_t *Zc, int N, int
 void gdca_launch_pair_tally(hipStream_t s, const int8_t *Zc, const int8_t *Zt, const unsigned long long *Wfix,
                             int N, int M, int q, int fix_shift, const double *Meff_dev, double pc,
                             const double *Pi_pc, int mode, double *out, size_t ld, int TJ);
+// out (ld) = the covariance of pseudocount pc built from stored tallies: Pij (n x n, ld = n, mode 0's output) and that pc's Pi_pc --
+// bit for bit what mode 1 writes for pc (both triangles; the padding is the caller's: gdca_launch_pad_identity)
+void gdca_launch_cov_from_pij(hipStream_t s, const double *Pij, const double *Pi_pc, int N, int q, double pc, double *out, size_t ld);
 
 // ---- k_elementwise.hip ---------------------------------------------------------------------
 void gdca_launch_add_pseudocount(hipStream_t s, const double *Pi_true, const double *Pij_true, int N, int q,

@@ -464,3 +464,69 @@ void gdca_launch_pair_tally(hipStream_t st, const int8_t *Zc, const int8_t *Zt, 
         (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16>, k_pair_tally<GDCA_MAXB, 16>>(dim3((N + 15) / 16, N), dim3(TALLY_THREADS), tally_lds_bytes(s, 16), st, k_pair_tally_mk(Zc, Zt, Wfix, N, M, q, fix_shift, Meff_dev, pc, Pi_pc, mode, out, ld)));
     }
 }
+
+// ---- the covariance of one pseudocount from stored tallies (gdca_run_multi) ---------------------------------------------------------
+// Pij_true (n x n, full symmetric, ld = n: what k_pair_tally's mode 0 wrote) and Pi' of this pseudocount (k_pi_finalize) -> C in the
+// inverse's buffer (ld = n_pad), both triangles.  Every element is k_pair_tally's epilogue expression (pass 1) copied verbatim, with
+// the same operands -- Pij_true there is this very f64 value before it is stored -- so under -ffp-contract=off the two builds agree
+// bit for bit.  (A shared inline helper was tried: it moves k_pair_tally's register allocation, so the epilogue is left as it was.)
+// HBM-bound: 8 n^2 bytes read, 8 n^2 written.  A workgroup owns one column and ROWS_PER_THREAD x 256 rows of it: lanes walk the rows, so
+// the reads of Pij_true and Pi' and the writes of C are all contiguous along a column.
+#define COV_ROWS_PER_THREAD 4
+struct k_cov_from_pij_args {
+    const double *Pij;
+    const double *Pi_pc;
+    int n;
+    int q;
+    double pc;
+    double *out;
+    size_t ld;
+};
+static inline k_cov_from_pij_args k_cov_from_pij_mk(const double *Pij, const double *Pi_pc, int n, int q, double pc, double *out, size_t ld)
+{
+    return k_cov_from_pij_args{Pij, Pi_pc, n, q, pc, out, ld};
+}
+template <int CAP>
+__global__ __launch_bounds__(256) void k_cov_from_pij(const BatchArgs<k_cov_from_pij_args, CAP> B_)
+{
+    GDCA_MEMBER(B_);
+    const double *__restrict__ Pij = a_.Pij;
+    const double *__restrict__ Pi_pc = a_.Pi_pc;
+    int n = a_.n;
+    int q = a_.q;
+    double pc = a_.pc;
+    double *__restrict__ out = a_.out;
+    size_t ld = a_.ld;
+    const int s = q - 1;
+    const int c = blockIdx.y;
+    const int ic = c / s;
+    const double pcq = pc / (double)q;
+    const double off_add = pcq / (double)q;
+    const double pi_c = Pi_pc[c];
+    const double *__restrict__ src = Pij + (size_t)c * n;
+    double *__restrict__ dst = out + (size_t)c * ld;
+    const int r0 = blockIdx.x * (256 * COV_ROWS_PER_THREAD) + threadIdx.x;
+    double pt[COV_ROWS_PER_THREAD], pr[COV_ROWS_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < COV_ROWS_PER_THREAD; ++u) {  // all loads first: COV_ROWS_PER_THREAD of each in flight
+        const int r = r0 + u * 256;
+        pt[u] = r < n ? src[r] : 0.0;
+        pr[u] = r < n ? Pi_pc[r] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < COV_ROWS_PER_THREAD; ++u) {
+        const int r = r0 + u * 256;
+        if (r >= n) continue;
+        const int jj = r / s, i = ic;  // row site, column site: the names of k_pair_tally's pass 1
+        const bool ab = r == c;        // (a == b) inside the diagonal block
+        const double pij = (jj != i) ? ((1.0 - pc) * pt[u] + off_add) : ((1.0 - pc) * pt[u] + (ab ? pcq : 0.0));
+        dst[r] = pij - pi_c * pr[u];
+    }
+}
+
+void gdca_launch_cov_from_pij(hipStream_t s, const double *Pij, const double *Pi_pc, int N, int q, double pc, double *out, size_t ld)
+{
+    const int n = N * (q - 1);
+    const int rows = 256 * COV_ROWS_PER_THREAD;
+    (gdca_launch<k_cov_from_pij_args, k_cov_from_pij<1>, k_cov_from_pij<GDCA_MAXB>>(dim3((n + rows - 1) / rows, n), dim3(256), 0, s, k_cov_from_pij_mk(Pij, Pi_pc, n, q, pc, out, ld)));
+}

@@ -15,6 +15,7 @@ from ._lib import ArgumentError, default_context
 from .dcautils import (FastaAlignment, Ranking, _theta_arg, read_fasta_alignment, remove_duplicate_sequences)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
+last_multi_stats = None  # gDCA_multi: one stats dict per setting of its most recent call, in the order of the settings
 
 
 def _score_arg(score) -> int:
@@ -81,3 +82,67 @@ def gDCA(filename: str, pseudocount: float = 0.8, theta=":auto", max_gap_fractio
                       f"(||inv(C)||_1 = {last_stats['inverse_norm1']:.3g}; pseudocount {pseudocount}): scores are unreliable",
                       RuntimeWarning, stacklevel=2)
     return Ranking(ii, jj, sc)
+
+
+def _setting(s):
+    """(pseudocount, score) or {"pseudocount": .., "score": ..} -> (pseudocount, score)"""
+    if isinstance(s, dict):
+        unknown = set(s) - {"pseudocount", "score"}
+        if unknown:
+            raise ArgumentError(f"invalid setting keys: {sorted(unknown)} (a setting has a pseudocount and a score)")
+        return s.get("pseudocount", 0.8), s.get("score", ":frob")
+    try:
+        pc, score = s
+    except (TypeError, ValueError):
+        raise ArgumentError(f"invalid setting: {s!r} (must be a (pseudocount, score) pair)") from None
+    return pc, score
+
+
+def gDCA_multi(filename: str, settings, theta=":auto", max_gap_fraction: float = 0.9, min_separation: int = 5,
+               remove_dups: bool = False, ctx=None, **kw) -> List[Ranking]:
+    """gDCA of one alignment under several (pseudocount, score) settings in one pass: [Ranking], one per setting, in order.
+
+    ``settings``: a sequence of ``(pseudocount, score)`` pairs or of dicts with those keys, e.g. the reference's two standard
+    rankings ``[(0.8, ":frob"), (0.2, ":DI")]`` or a scan of the pseudocount.  Every ranking is the one ``gDCA`` returns for that
+    setting with the other arguments given here; the alignment is read, reweighted and tallied once (gdca_run_ranked_multi), and
+    settings with the same pseudocount share one inverse.  At most 16 settings a call.  Keyword ``θ`` is an alias of ``theta``.
+    Per-setting stats go to ``last_multi_stats``."""
+    global last_multi_stats
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_multi() got unexpected keyword arguments {sorted(kw)}")
+    try:
+        settings = [_setting(s) for s in settings]
+    except TypeError:
+        raise ArgumentError(f"invalid settings: {settings!r} (must be a sequence of (pseudocount, score) pairs)") from None
+    if not 1 <= len(settings) <= _lib.MULTI_MAX:
+        raise ArgumentError(f"invalid number of settings: {len(settings)} (must be between 1 and {_lib.MULTI_MAX})")
+    for pc, score in settings:
+        check_arguments(filename, pc, theta, max_gap_fraction, score, min_separation)
+    prm = [(float(pc), _score_arg(score)) for pc, score in settings]
+
+    ctx = ctx or default_context()
+    if remove_dups:
+        Z = read_fasta_alignment(filename, max_gap_fraction)
+        Z, _ = remove_duplicate_sequences(Z)
+        q = int(Z.max())
+        if q >= 32:
+            raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+        Zf = np.asfortranarray(Z, dtype=np.int8)
+        out = ctx.run_ranked_multi_ptr(Zf.ctypes.data, Zf.shape[0], Zf.shape[1], q, prm, _theta_arg(theta), int(min_separation), apc=True)
+    else:
+        with FastaAlignment(filename, max_gap_fraction) as fa:
+            q = fa.q
+            if q >= 32:
+                raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+            out = ctx.run_ranked_multi_ptr(fa.ptr, fa.N, fa.M, q, prm, _theta_arg(theta), int(min_separation), apc=True)
+    last_multi_stats = [st for _, _, _, st in out]
+    for (pc, _), st in zip(settings, last_multi_stats):
+        if st.get("refined", 0) < 0:
+            import warnings
+
+            warnings.warn("gDCA: the covariance is too ill-conditioned for the block sweep even with its refinement step "
+                          f"(||inv(C)||_1 = {st['inverse_norm1']:.3g}; pseudocount {pc}): scores are unreliable",
+                          RuntimeWarning, stacklevel=2)
+    return [Ranking(ii, jj, sc) for ii, jj, sc, _ in out]

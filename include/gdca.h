@@ -188,6 +188,35 @@ gdca_status gdca_run(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, 
 gdca_status gdca_run_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q,
                          const gdca_params *p, double *S_dev, gdca_stats *st);
 
+/* ---- several settings of ONE alignment in one call ----------------------------------------------------------------------
+ * The reference's two standard rankings (FN at pseudocount 0.8, DI at 0.2) or a scan of the pseudocount over one family.  p and st
+ * have K entries, 1 <= K <= GDCA_MULTI_MAX; every p[k].theta must be the same setting (equal, or all negative = :auto) and every
+ * p[k] valid as for gdca_run, else GDCA_EINVAL with nothing run.  Outputs are K consecutive blocks in the order of p: S_* holds K
+ * column-major N x N matrices, i_out / j_out / score_out K blocks of gdca_ranking_length(N, min_separation) entries.
+ * What does not depend on the setting runs ONCE: theta, the reweighting, Pi and the pair tallies, kept as Pij_true in a grow-only
+ * context buffer of n x n f64 (one buffer whatever K: 0.8 GB at n = 10 000, 28.8 GB at GDCA_MAX_N, on top of the covariance).  Then,
+ * for every distinct pseudocount in order of first appearance (a "group"), the covariance is built from Pij_true, the DI diagonal
+ * blocks where a member asks for DI, and the SPD inverse; each member of the group gets its score, APC and ranking from that
+ * inverse.  Every member's output is bit for bit that of gdca_run / gdca_run_ranked with p[k] (K = 1 is that very call).
+ * Conditioning is per group: the refinement screen, the Newton-Schulz step, the Cholesky fallback and the sweep's second attempt
+ * are those a single run of the group's pseudocount takes (each rebuilds C from Pij_true).  A member that fails (GDCA_ENOTPD, e.g.
+ * pc = 0 with a constant column; GDCA_ENOCONV) leaves the others computed: the call returns the status of the first failing member
+ * in the order of p, every st[k].info is what a single run would report, and a failing member's outputs are unspecified.
+ * GDCA_EHIP, GDCA_ENOMEM and an alignment with a symbol outside 1..q end the whole call.  Synchronous.
+ * Stats: theta, Meff, pair_identity_sum, thresh, ms_theta and ms_weights are the shared front end's, the same in every entry.
+ * ms_covariance is the pair tally + build for the first group and only the build from Pij_true for the others; refined, info (but
+ * a DI member's ENOCONV count), cond_bound, matrix_norm1, inverse_norm1, sweep_retries, sweep_ghz and the ms_inverse* are the
+ * group's; ms_score and ms_fn the member's own; ms_total runs from the start of the call to the end of the member's score stage;
+ * ms_pair_tally is 0. */
+#define GDCA_MULTI_MAX 16
+gdca_status gdca_run_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K,
+                           double *S_host, gdca_stats *st);
+gdca_status gdca_run_multi_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K,
+                               double *S_dev, gdca_stats *st);
+/* The same with the device ranking of every member (gdca_run_ranked): Z (host) in, K rankings out; no score matrix crosses PCIe. */
+gdca_status gdca_run_ranked_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K,
+                                  int32_t min_separation, int32_t *i_out, int32_t *j_out, double *score_out, gdca_stats *st);
+
 /* Split form for pipelining independent families over several contexts on one GPU: _async only
  * enqueues (no host synchronisation); gdca_run_collect waits for that run, fills *st and returns the run's
  * status.  One run may be outstanding per ctx (a second _async before the collect is GDCA_EINVAL); the Z and S
