@@ -48,6 +48,7 @@ struct gdca_ctx {
     gdca_buf hcand;               // reweighting, bound forms: the list of candidate pairs
     gdca_buf himg;                // reweighting, fp4 form: the image of the three low bit planes as E2M1 nibbles
     gdca_buf rankws;              // device ranking: keys, values, histograms, the three output arrays
+    gdca_buf keep;                // pair tally, TALLY_SKIP: the sequences each column's tally visits, their counts and sigma (k_tally_keep)
     gdca_buf Pij;                 // gdca_run_multi: Pij_true of the alignment (n x n, ld = n), the covariance of every pseudocount is built from it
     gdca_buf sc_front;            // gdca_run_multi: the scalars as the front end left them (every pseudocount group starts from them)
     // an enqueued ranked run (gdca_run_ranked_async): where its ranking will be, and whether enqueueing it worked
@@ -240,7 +241,7 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         {"GROUP", &t->group, -1, 4},        {"RAMP", &t->ramp, 0, 1},          {"RAGGED", &t->ragged, 0, 1},
         {"REM_TAIL", &t->rem_tail, -1, 1 << 20}, {"PANEL_HALVES", &t->panel_halves, -1, 1}, {"SLAB", &t->slab, 0, 1},
         {"RING", &t->ring, 2, 8},           {"MCUS", &t->mcus, -1, 32},        {"MCU_SOLO", &t->mcu_solo, -1, 1},       {"SWEEP_DEBUG", &t->sweep_debug, 0, 63}, {"SWEEP_RETRIES", &t->sweep_retries, 0, 5},
-        {"TALLY_TJ", &t->tally_tj, 0, 32},  {"MERGE", &t->merge, 1, 8},        {"MERGE_BLOCKS", &t->merge_blocks, 1, 64},
+        {"TALLY_TJ", &t->tally_tj, 0, 32},  {"TALLY_SKIP", &t->tally_skip, 0, 1}, {"MERGE", &t->merge, 1, 8},        {"MERGE_BLOCKS", &t->merge_blocks, 1, 64},
         {"MERGE_MCUS", &t->merge_mcus, -1, 16},  {"MERGE_GROUP", &t->merge_group, -1, 4}, {"MERGE_TILES", &t->merge_tiles, 1, 1 << 20},
         {"CHOLESKY", &t->cholesky, 0, 2},  {"PHASED_FRONTS", &t->phased_fronts, 0, 1}, {"PHASED_GRIDS", &t->phased_grids, -1, 8}, {"PHASED_STREAMS", &t->phased_streams, 1, 64},
     };
@@ -286,6 +287,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     t->mcus = -1;
     t->mcu_solo = -1;
     t->sweep_retries = 2;
+    t->tally_skip = 1;
     t->hamming_mode = -1;
     t->merge = 8;
     t->merge_blocks = 57;
@@ -299,7 +301,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     t->refine_cond = 1e6;
     t->cholesky = 1;
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
-                                        "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ",
+                                        "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
                                         "GDCA_HAMMING_MODE", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
                                         "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO"};
     for (const char *nm : names)
@@ -495,7 +497,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
     gdca_buf *bufs[] = {&ctx->Zt, &ctx->Zp, &ctx->hist, &ctx->Zb, &ctx->hcnt, &ctx->nk, &ctx->W, &ctx->Wfix, &ctx->Pifix,
                         &ctx->Pipc, &ctx->A, &ctx->G, &ctx->H, &ctx->P, &ctx->Sg, &ctx->Dblk, &ctx->Ld,
                         &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg,
-                        &ctx->Pij, &ctx->sc_front};
+                        &ctx->Pij, &ctx->sc_front, &ctx->keep};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < N_SCRATCH; ++i)
@@ -665,6 +667,9 @@ static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, in
     const int sdim = q - 1, n = N * sdim;
     const int shift = gdca_fix_shift(M);
     const int TJ = gdca_tally_tj(q, ctx->tune.tally_tj);
+    const bool skip = gdca_tally_skip(q, TJ, ctx->tune.tally_skip, M);
+    const size_t keep_list = (size_t)N * M * sizeof(uint32_t);  // then keep_n (N int), sigma (N bytes)
+    if (skip) CHK(ensure(ctx, ctx->keep, keep_list + (size_t)N * sizeof(int) + N));
     CHK(ensure(ctx, ctx->Zt, (size_t)N * M));
     CHK(ensure(ctx, ctx->Zp, (size_t)round_up(N, 64) * M + 64));
     CHK(ensure(ctx, ctx->Pifix, (size_t)N * 32 * sizeof(unsigned long long)));
@@ -678,9 +683,15 @@ static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, in
                             (double *)ctx->Pipc.p, want_norm1 ? &((gdca_dev_scalars *)ctx->sc.p)->pi_max : nullptr);
     const bool tm = want_norm1 && ctx->timing && ctx->n_ev >= 18;  // (the fused path's first build: its own device time, gdca_stats.ms_pair_tally)
     if (tm) CHK(mark(ctx, 9));
+    uint32_t *keep = skip ? (uint32_t *)ctx->keep.p : nullptr;
+    int *keep_n = skip ? (int *)((char *)ctx->keep.p + keep_list) : nullptr;
+    uint8_t *sigma = skip ? (uint8_t *)(keep_n + N) : nullptr;
+    if (skip)  // (inside events 9 / 10: gdca_stats.ms_pair_tally is the whole tally)
+        gdca_launch_tally_keep(s, (const int8_t *)ctx->Zt.p, (const unsigned long long *)ctx->Pifix.p, keep, keep_n, sigma, N, M, q);
     gdca_launch_pair_tally(s, (const int8_t *)ctx->Zp.p, (const int8_t *)ctx->Zt.p,
                            (const unsigned long long *)ctx->Wfix.p, N, M, q, shift, Meff_dev, pc,
-                           (const double *)ctx->Pipc.p, mode, out, ld, TJ);
+                           (const double *)ctx->Pipc.p, mode, out, ld, TJ, keep, keep_n, sigma,
+                           (const unsigned long long *)ctx->Pifix.p);
     if (tm) CHK(mark(ctx, 10));
     // ||C||_1 for the refinement screen, where the bound that costs nothing (2 N pi_max) does not settle it (k_cov_norm1)
     // (not even launched where the answer is known on the host: pi_max <= (1 - pc) + pc / q whatever the alignment)

@@ -55,6 +55,7 @@ struct gdca_tuning {
     long sweep_timeout_ms;  // GDCA_SWEEP_TIMEOUT_MS: bound of one dependency wait; 0 = scaled with the problem (>= 4 s)
     int sweep_retries;      // GDCA_SWEEP_RETRIES: attempts an inverse gets after its launch was ended by the watchdog (default 2; 0 = none: GDCA_EHIP at once)
     int tally_tj;           // GDCA_TALLY_TJ: 32 = the wide pair-tally form
+    int tally_skip;         // GDCA_TALLY_SKIP: 1 = the pair tally skips each column's most frequent symbol and recovers its row (default), 0 = the full loop
     int hamming_mode;       // GDCA_HAMMING_MODE: -1 = probe, 0 = full (exact five-plane distances), 1 = bound (three planes + refinement), 2 = mfma (bit counts on the fp4 matrix pipe + refinement)
     int force_fallback;     // GDCA_FORCE_FALLBACK: 1 = the independent byte-compare Hamming kernel
     int merge;              // GDCA_MERGE: families one merged sweep launch may carry in gdca_run_dev_phased (1 = never merge)
@@ -127,9 +128,17 @@ void gdca_launch_cov_norm1(hipStream_t s, const double *C, size_t ld, int N, int
 // Zc: the alignment regrouped as [ceil(N/TJ)][M][TJ] (gdca_launch_colblock), TJ = gdca_tally_tj(q).
 int gdca_tally_tj(int q, int tj_wanted);
 void gdca_launch_colblock(hipStream_t s, const int8_t *Z, int8_t *Zc, int N, int M, int TJ);
+// TALLY_SKIP where the [q][q][TJ] histograms fit as many workgroups per CU as the full loop's (and M <= 2^27)
+bool gdca_tally_skip(int q, int TJ, int skip_wanted, int M);
+// keep: uint32 [N][M] (per column i: keep_n[i] entries (k << 5) | Z[i,k], ascending k, every sequence whose Z[i,k] is a legal
+// symbol other than sigma[i] = the argmax of Pifix[i][1..q], ties to the smallest); Zt: Z transposed (N rows of M)
+void gdca_launch_tally_keep(hipStream_t s, const int8_t *Zt, const unsigned long long *Pifix, uint32_t *keep, int *keep_n,
+                            uint8_t *sigma, int N, int M, int q);
+// keep == nullptr: the full loop over all M sequences; else keep / keep_n / sigma of gdca_launch_tally_keep and Pifix (the SKIP form)
 void gdca_launch_pair_tally(hipStream_t s, const int8_t *Zc, const int8_t *Zt, const unsigned long long *Wfix,
                             int N, int M, int q, int fix_shift, const double *Meff_dev, double pc,
-                            const double *Pi_pc, int mode, double *out, size_t ld, int TJ);
+                            const double *Pi_pc, int mode, double *out, size_t ld, int TJ, const uint32_t *keep = nullptr,
+                            const int *keep_n = nullptr, const uint8_t *sigma = nullptr, const unsigned long long *Pifix = nullptr);
 // out (ld) = the covariance of pseudocount pc built from stored tallies: Pij (n x n, ld = n, mode 0's output) and that pc's Pi_pc --
 // bit for bit what mode 1 writes for pc (both triangles; the padding is the caller's: gdca_launch_pad_identity)
 void gdca_launch_cov_from_pij(hipStream_t s, const double *Pij, const double *Pi_pc, int N, int q, double pc, double *out, size_t ld);

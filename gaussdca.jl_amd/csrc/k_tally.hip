@@ -266,6 +266,93 @@ void gdca_launch_colblock(hipStream_t s, const int8_t *Z, int8_t *Zc, int N, int
     (gdca_launch<k_colblock_args, k_colblock<1>, k_colblock<GDCA_MAXB>>(grid, dim3(256), 0, s, k_colblock_mk(Z, Zc, N, M, TJ)));
 }
 
+// ---- the sequences the pair tally of column i has to visit (TALLY_SKIP) ----
+// sigma(i) = the symbol of column i with the largest single-site sum Pifix[i][.] (1..q, ties to the smallest).  Only the sequences
+// whose Z[i,k] is a legal symbol other than sigma(i) are tallied; row sigma(i) of every histogram is recovered afterwards from the
+// column sums  sum_a H[a][b] = Pifix[j][b]  in u64 (exact: wrap-around cancels, the true value is < 2^63).  This kernel writes, per
+// column i, those sequences in ascending order as  (k << 5) | Z[i,k]  into keep[i][0 .. keep_n[i]-1], and sigma[i].
+// One workgroup per column, 256 threads x KEEP_SLABS sequences per step: a wave ballot gives each kept sequence its place.
+#define KEEP_THREADS 256
+#define KEEP_SLABS 16
+struct k_tally_keep_args {
+    const int8_t *Zt;
+    const u64 *Pifix;
+    uint32_t *keep;
+    int *keep_n;
+    uint8_t *sigma;
+    int N;
+    int M;
+    int q;
+};
+static inline k_tally_keep_args k_tally_keep_mk(const int8_t *Zt, const u64 *Pifix, uint32_t *keep, int *keep_n, uint8_t *sigma, int N, int M, int q)
+{
+    return k_tally_keep_args{Zt, Pifix, keep, keep_n, sigma, N, M, q};
+}
+template <int CAP>
+__global__ __launch_bounds__(KEEP_THREADS) void k_tally_keep(const BatchArgs<k_tally_keep_args, CAP> B_)
+{
+    GDCA_MEMBER(B_);
+    const int8_t *__restrict__ Zt = a_.Zt;
+    const u64 *__restrict__ Pifix = a_.Pifix;
+    uint32_t *__restrict__ keep = a_.keep;
+    int M = a_.M;
+    int q = a_.q;
+    constexpr int NW = KEEP_THREADS / 64;
+    __shared__ unsigned wcnt[KEEP_SLABS * NW], woff[KEEP_SLABS * NW];  // kept sequences per (slab, wave), slab-major = ascending k
+    const int i = blockIdx.x;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const u64 *P = Pifix + (size_t)i * 32;
+    unsigned sig = 1;
+    u64 best = P[1];
+    for (int a = 2; a <= q; ++a) {
+        const u64 v = P[a];
+        if (v > best) {
+            best = v;
+            sig = (unsigned)a;
+        }
+    }
+    const int8_t *zi = Zt + (size_t)i * M;
+    uint32_t *out = keep + (size_t)i * M;
+    const u64 lt = (1ull << lane) - 1ull;
+    unsigned base = 0;
+    for (int kc = 0; kc < M; kc += KEEP_THREADS * KEEP_SLABS) {
+        unsigned raw[KEEP_SLABS], pos[KEEP_SLABS];
+#pragma unroll
+        for (int u = 0; u < KEEP_SLABS; ++u) {
+            const int k = kc + u * KEEP_THREADS + t;
+            raw[u] = k < M ? (unsigned)(uint8_t)zi[k] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < KEEP_SLABS; ++u) {
+            const bool kp = (raw[u] - 1u) < (unsigned)q && raw[u] != sig;
+            const u64 bal = __ballot(kp);
+            pos[u] = kp ? (unsigned)__popcll(bal & lt) : ~0u;
+            if (lane == 0) wcnt[u * NW + wv] = (unsigned)__popcll(bal);
+        }
+        __syncthreads();
+        if (t < KEEP_SLABS * NW) {
+            unsigned o = base;
+            for (int e = 0; e < t; ++e) o += wcnt[e];
+            woff[t] = o;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KEEP_SLABS; ++u)
+            if (pos[u] != ~0u) out[woff[u * NW + wv] + pos[u]] = ((unsigned)(kc + u * KEEP_THREADS + t) << 5) | raw[u];
+        base = woff[KEEP_SLABS * NW - 1] + wcnt[KEEP_SLABS * NW - 1];
+        __syncthreads();  // wcnt / woff are rewritten by the next step
+    }
+    if (t == 0) {
+        a_.keep_n[i] = (int)base;
+        a_.sigma[i] = (uint8_t)sig;
+    }
+}
+
+void gdca_launch_tally_keep(hipStream_t s, const int8_t *Zt, const u64 *Pifix, uint32_t *keep, int *keep_n, uint8_t *sigma, int N, int M, int q)
+{
+    (gdca_launch<k_tally_keep_args, k_tally_keep<1>, k_tally_keep<GDCA_MAXB>>(dim3(N), dim3(KEEP_THREADS), 0, s, k_tally_keep_mk(Zt, Pifix, keep, keep_n, sigma, N, M, q)));
+}
+
 // Workgroup = (column i) x (block of TJ columns j >= i's block), 1024 threads = 16 waves (the
 // histograms take most of the LDS, so one workgroup per CU: the waves have to come from here).
 // Per pass of 1024 sequences the block's TJ bytes of every sequence and a packed
@@ -277,6 +364,13 @@ void gdca_launch_colblock(hipStream_t s, const int8_t *Z, int8_t *Zc, int N, int
 // The histogram has s+2 columns per row (b = 0 and b = q are junk columns for padding / gaps) so
 // the inner loop needs no validity test at all: an invalid Z[i,k] is staged as weight 0, lanes left
 // of the diagonal tally into columns the epilogue never reads.
+//
+// SKIP (TALLY_SKIP, the default where it fits): the staged sequences of column i are k_tally_keep's list -- every sequence but
+// those with Z[i,k] = sigma(i) or an illegal byte -- so at config C a pass of 1024 staged sequences is 1024 useful ones out of
+// ~2400.  The histogram then has a row AND a column per symbol, [q][q][TJ] indexed by symbol - 1 (the gap's row takes the gap
+// sequences, which the recovery needs; the gap's column also takes the zero padding and any illegal byte), and row sigma(i) is
+// rebuilt in u64 after the last barrier: H[sigma][b] = Pifix[j][b] - sum_{a != sigma} H[a][b].  The integer tallies, and so
+// every f64 value of the epilogue, are those of the full loop bit for bit.
 struct k_pair_tally_args {
     const int8_t *Zc;
     const int8_t *Zt;
@@ -291,12 +385,17 @@ struct k_pair_tally_args {
     int mode;
     double *out;
     size_t ld;
+    const uint32_t *keep;   // SKIP: k_tally_keep's lists, keep_n, sigma; Pifix for the recovery
+    const int *keep_n;
+    const uint8_t *sigma;
+    const u64 *Pifix;
 };
-static inline k_pair_tally_args k_pair_tally_mk(const int8_t *Zc, const int8_t *Zt, const u64 *Wfix, int N, int M, int q, int fix_shift, const double *Meff_dev, double pc, const double *Pi_pc, int mode, double *out, size_t ld)
+static inline k_pair_tally_args k_pair_tally_mk(const int8_t *Zc, const int8_t *Zt, const u64 *Wfix, int N, int M, int q, int fix_shift, const double *Meff_dev, double pc, const double *Pi_pc, int mode, double *out, size_t ld,
+                                                const uint32_t *keep, const int *keep_n, const uint8_t *sigma, const u64 *Pifix)
 {
-    return k_pair_tally_args{Zc, Zt, Wfix, N, M, q, fix_shift, Meff_dev, pc, Pi_pc, mode, out, ld};
+    return k_pair_tally_args{Zc, Zt, Wfix, N, M, q, fix_shift, Meff_dev, pc, Pi_pc, mode, out, ld, keep, keep_n, sigma, Pifix};
 }
-template <int CAP, int TJ>
+template <int CAP, int TJ, bool SKIP>
 __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_pair_tally_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
@@ -324,9 +423,11 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
     const int j0 = jblk * TJ;
     if (j0 + TJ - 1 < i) return;  // block entirely left of the diagonal: its mirror does the work
 
-    const int RS = (s + 2) * TJ;                                                  // u64 per histogram row a
-    u64 *hist = reinterpret_cast<u64 *>(smem);                                    // [s][s+2][TJ]
-    u64 *meta_s = hist + (size_t)s * RS;                                          // [TALLY_CHUNK]
+    const int NROW = SKIP ? q : s;                                                // histogram rows
+    const int CB = SKIP ? 0 : 1;                                                  // histogram column of state b (0..s-1): b + CB
+    const int RS = (SKIP ? q : s + 2) * TJ;                                       // u64 per histogram row a
+    u64 *hist = reinterpret_cast<u64 *>(smem);                                    // [s][s+2][TJ]  (SKIP: [q][q][TJ])
+    u64 *meta_s = hist + (size_t)NROW * RS;                                       // [TALLY_CHUNK]
     uint8_t *zs = reinterpret_cast<uint8_t *>(meta_s + TALLY_CHUNK);              // [TALLY_CHUNK][TJ]
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -337,9 +438,11 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
     static_assert(TALLY_CHUNK == TALLY_THREADS, "one staged sequence per thread");
     const int jl = lane % TJ, sub = lane / TJ;
     const u64 wmask = (1ull << 59) - 1;
-    const unsigned qclamp = (unsigned)(s + 1);
+    const unsigned qclamp = (unsigned)(SKIP ? q - 1 : s + 1);
+    const int nk = SKIP ? a_.keep_n[i] : M;  // sequences to stage
+    const uint32_t *__restrict__ keep_i = a_.keep + (size_t)i * M;
 
-    for (int e = tid; e < s * RS; e += TALLY_THREADS) hist[e] = 0;
+    for (int e = tid; e < NROW * RS; e += TALLY_THREADS) hist[e] = 0;
 
     // prefetch registers for one pass: this thread's sequence kc + tid.  The raw loads stay
     // untouched in registers until the LDS write of the NEXT pass, so a whole pass of tallies
@@ -351,25 +454,30 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
 #define TALLY_FETCH(KC)                                                                       \
     do {                                                                                      \
         int k_ = (KC) + tid;                                                                  \
-        k_ = k_ < M ? k_ : M - 1; /* clamp: the tail is staged with weight 0 */               \
+        k_ = k_ < nk ? k_ : nk - 1; /* clamp: the tail is staged with weight 0 */             \
+        if (SKIP) {                                                                           \
+            const uint32_t e_ = keep_i[k_];                                                   \
+            av = (int8_t)(e_ & 31u);                                                          \
+            k_ = (int)(e_ >> 5);                                                              \
+        }                                                                                     \
         const uint4 *src_ = reinterpret_cast<const uint4 *>(Zblk + (size_t)k_ * TJ);          \
         z0 = src_[0];                                                                         \
         if (NV > 1) z1 = src_[1];                                                             \
-        av = Zt[(size_t)i * M + k_];                                                          \
+        if (!SKIP) av = Zt[(size_t)i * M + k_];                                               \
         wf = Wfix[k_];                                                                        \
     } while (0)
-    TALLY_FETCH(0);
-    for (int kc = 0; kc < M; kc += TALLY_CHUNK) {
+    if (nk > 0) TALLY_FETCH(0);  // (SKIP: an empty list stages nothing)
+    for (int kc = 0; kc < nk; kc += TALLY_CHUNK) {
         __syncthreads();  // previous pass fully consumed (and hist zeroed, first time)
         {
             reinterpret_cast<uint4 *>(zs + (size_t)tid * TJ)[0] = z0;
             if (NV > 1) reinterpret_cast<uint4 *>(zs + (size_t)tid * TJ)[1] = z1;
-            const unsigned a = (unsigned)(uint8_t)av - 1u;  // row index 0..s-1 when valid
-            const bool valid = (a < (unsigned)s) && (kc + tid < M);
+            const unsigned a = (unsigned)(uint8_t)av - 1u;  // row index 0..s-1 when valid (SKIP: 0..q-1, the list holds legal symbols only)
+            const bool valid = (SKIP || a < (unsigned)s) && (kc + tid < nk);
             meta_s[tid] = valid ? (((u64)a << 59) | (wf & wmask)) : 0ull;
         }
         __syncthreads();
-        if (kc + TALLY_CHUNK < M) TALLY_FETCH(kc + TALLY_CHUNK);
+        if (kc + TALLY_CHUNK < nk) TALLY_FETCH(kc + TALLY_CHUNK);
         const int kw = wv * SEQ_PER_WAVE;
 #pragma unroll 2
         for (int it = 0; it < SEQ_PER_WAVE / SPI; it += 4) {
@@ -384,13 +492,31 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const unsigned a = (unsigned)(m4[u] >> 59);
-                const unsigned b = min(b4[u], qclamp);
+                const unsigned b = min(b4[u] - (unsigned)(1 - CB), qclamp);  // (SKIP: symbol 0 wraps and lands in the gap's column)
                 const unsigned idx = __umul24(a, (unsigned)RS) + __umul24(b, (unsigned)TJ) + (unsigned)jl;
                 atomicAdd(&hist[idx], m4[u] & wmask);
             }
         }
     }
     __syncthreads();
+#undef TALLY_FETCH
+
+    // ---- SKIP: row sigma(i) from the column sums (the gap's row is never read: nothing to do where sigma(i) = q) ----
+    if (SKIP) {
+        const int sg = (int)a_.sigma[i] - 1;
+        const u64 *__restrict__ Pifix = a_.Pifix;
+        if (sg < s) {
+            for (int e = tid; e < s * TJ; e += TALLY_THREADS) {
+                const int b = e / TJ, l = e - b * TJ;
+                const int jj = j0 + l;
+                if (jj >= N || jj < i) continue;
+                u64 v = Pifix[(size_t)jj * 32 + b + 1];
+                for (int a = 0; a < q; ++a)
+                    if (a != sg) v -= hist[(size_t)a * RS + b * TJ + l];
+                hist[(size_t)sg * RS + b * TJ + l] = v;
+            }
+        }
+    }
 
     // ---- epilogue: histograms -> Pij_true (mode 0) or covariance C (mode 1) ----
     // Pi' of column i and of the TJ columns of the block are staged in LDS first (the staging
@@ -415,7 +541,7 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
         const int l = rem / s, b = rem - l * s;
         const int jj = j0 + l;
         if (jj >= N || jj < i) continue;
-        const double pt = ldexp((double)hist[(size_t)a * RS + (b + 1) * TJ + l], -fix_shift) / Meff;
+        const double pt = ldexp((double)hist[(size_t)a * RS + (b + CB) * TJ + l], -fix_shift) / Meff;
         double v = pt;
         if (mode == 1) {
             const double pij = (jj != i) ? ((1.0 - pc) * pt + off_add) : ((1.0 - pc) * pt + ((a == b) ? pcq : 0.0));
@@ -429,7 +555,7 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
         const int b = rem / s, a = rem - b * s;
         const int jj = j0 + l;
         if (jj >= N || jj <= i) continue;  // the diagonal block was written in full by pass 1
-        const double pt = ldexp((double)hist[(size_t)a * RS + (b + 1) * TJ + l], -fix_shift) / Meff;
+        const double pt = ldexp((double)hist[(size_t)a * RS + (b + CB) * TJ + l], -fix_shift) / Meff;
         double v = pt;
         if (mode == 1) {
             const double pij = (1.0 - pc) * pt + off_add;
@@ -439,9 +565,10 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
     }
 }
 
-static size_t tally_lds_bytes(int s, int TJ)
+static size_t tally_lds_bytes(int s, int TJ, bool skip = false)
 {
-    return (size_t)s * (s + 2) * TJ * 8 + (size_t)TALLY_CHUNK * 8 + (size_t)TALLY_CHUNK * TJ;
+    const size_t hist = skip ? (size_t)(s + 1) * (s + 1) * TJ * 8 : (size_t)s * (s + 2) * TJ * 8;
+    return hist + (size_t)TALLY_CHUNK * 8 + (size_t)TALLY_CHUNK * TJ;
 }
 
 int gdca_tally_tj(int q, int tj_wanted)
@@ -453,15 +580,33 @@ int gdca_tally_tj(int q, int tj_wanted)
     return 16;
 }
 
+bool gdca_tally_skip(int q, int TJ, int skip_wanted, int M)
+{
+    // the [q][q][TJ] histograms must leave as many workgroups per CU as the full loop's [s][s+2][TJ] (q = 21, TJ = 16: 81 024 B
+    // against 80 896, two per CU either way); the list entries hold k in 27 bits
+    const size_t lds = 160 * 1024, full = tally_lds_bytes(q - 1, TJ), skip = tally_lds_bytes(q - 1, TJ, true);
+    return skip_wanted && M <= (1 << 27) && skip <= lds && lds / skip >= lds / full;
+}
+
 void gdca_launch_pair_tally(hipStream_t st, const int8_t *Zc, const int8_t *Zt, const u64 *Wfix, int N, int M, int q,
                             int fix_shift, const double *Meff_dev, double pc, const double *Pi_pc, int mode,
-                            double *out, size_t ld, int TJ)
+                            double *out, size_t ld, int TJ, const uint32_t *keep, const int *keep_n, const uint8_t *sigma,
+                            const u64 *Pifix)
 {
     const int s = q - 1;
+    const bool skip = keep != nullptr;
+    const k_pair_tally_args a = k_pair_tally_mk(Zc, Zt, Wfix, N, M, q, fix_shift, Meff_dev, pc, Pi_pc, mode, out, ld, keep, keep_n, sigma, Pifix);
+    const size_t lds = tally_lds_bytes(s, TJ, skip);
     if (TJ == 32) {
-        (gdca_launch<k_pair_tally_args, k_pair_tally<1, 32>, k_pair_tally<GDCA_MAXB, 32>>(dim3((N + 31) / 32, N), dim3(TALLY_THREADS), tally_lds_bytes(s, 32), st, k_pair_tally_mk(Zc, Zt, Wfix, N, M, q, fix_shift, Meff_dev, pc, Pi_pc, mode, out, ld)));
+        if (skip)
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 32, true>, k_pair_tally<GDCA_MAXB, 32, true>>(dim3((N + 31) / 32, N), dim3(TALLY_THREADS), lds, st, a));
+        else
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 32, false>, k_pair_tally<GDCA_MAXB, 32, false>>(dim3((N + 31) / 32, N), dim3(TALLY_THREADS), lds, st, a));
     } else {
-        (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16>, k_pair_tally<GDCA_MAXB, 16>>(dim3((N + 15) / 16, N), dim3(TALLY_THREADS), tally_lds_bytes(s, 16), st, k_pair_tally_mk(Zc, Zt, Wfix, N, M, q, fix_shift, Meff_dev, pc, Pi_pc, mode, out, ld)));
+        if (skip)
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16, true>, k_pair_tally<GDCA_MAXB, 16, true>>(dim3((N + 15) / 16, N), dim3(TALLY_THREADS), lds, st, a));
+        else
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16, false>, k_pair_tally<GDCA_MAXB, 16, false>>(dim3((N + 15) / 16, N), dim3(TALLY_THREADS), lds, st, a));
     }
 }
 
