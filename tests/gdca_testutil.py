@@ -96,3 +96,19 @@ def random_msa(rng, M, N, q=21, gap_runs=True, clusters=None):
                 a = rng.integers(0, N)
                 Z[k, a:a + rng.integers(1, max(2, N // 10) + 1)] = q
     return np.ascontiguousarray(Z.astype(np.int8))
+
+
+def edge_family(M, N, q, seed):
+    """(N, M) Fortran int8: a random family plus the columns the tally's skip form treats specially (N >= 5).  For q < 5 the
+    symbols of the special columns are clipped to q - 1, so the family stays inside 1..q."""
+    c = (lambda x: x) if q >= 5 else (lambda x: min(x, q - 1))
+    rng = np.random.default_rng(seed)
+    Z = random_msa(rng, M, N, q=q)                      # (M, N)
+    Z[:, 0] = c(3)                                      # one symbol everywhere: column 0's kept list is empty
+    Z[:, 1] = q                                         # the gap everywhere
+    Z[:, 2] = np.where(rng.random(M) < 0.7, q, Z[:, 2])  # the gap is the most frequent symbol
+    Z[:, 3] = np.where(np.arange(M) % 2 == 0, c(2), c(5))  # two symbols, equal counts: a tie (with equal weights)
+    if M % 2:
+        Z[-1, 3] = 1
+    Z[:, 4] = np.where(np.arange(M) % 3 == 0, c(4), Z[:, 4])
+    return np.asfortranarray(Z.T.astype(np.int8))

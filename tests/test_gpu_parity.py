@@ -529,8 +529,8 @@ def test_headline_config_properties(g, ctx):
 
 @pytest.mark.parametrize("n", [6000, 9100])
 def test_large_spd_inverse_residual(g, ctx, n):
-    """n = 6000 (47 pivot blocks: single pivots) and n = 9100 (72 blocks: groups of three, K = 384 trailing updates):
-    A X v == v on random probes."""
+    """n = 6000 (47 pivot blocks: groups of two -- single pivots end at 44 blocks, pairs at 52) and n = 9100 (72 blocks: groups of
+    three, K = 384 trailing updates): A X v == v on random probes."""
     rng = np.random.default_rng(4)
     B = rng.standard_normal((n, 64))
     d = 0.5 + rng.random(n)

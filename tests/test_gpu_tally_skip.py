@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from gdca_testutil import random_msa
+from gdca_testutil import edge_family as _edge_family
 
 pytestmark = pytest.mark.gpu
 
@@ -30,20 +30,6 @@ def ctx(g):
     c = g.Context(0)
     yield c
     c.close()
-
-
-def _edge_family(M, N, q, seed):
-    """(N, M) Fortran int8: a random family plus the columns the skip form treats specially."""
-    rng = np.random.default_rng(seed)
-    Z = random_msa(rng, M, N, q=q)                      # (M, N)
-    Z[:, 0] = 3                                         # one symbol everywhere: column 0's kept list is empty
-    Z[:, 1] = q                                         # the gap everywhere
-    Z[:, 2] = np.where(rng.random(M) < 0.7, q, Z[:, 2])  # the gap is the most frequent symbol
-    Z[:, 3] = np.where(np.arange(M) % 2 == 0, 2, 5)     # two symbols, equal counts: a tie (with equal weights)
-    if M % 2:
-        Z[-1, 3] = 1
-    Z[:, 4] = np.where(np.arange(M) % 3 == 0, 4, Z[:, 4])
-    return np.asfortranarray(Z.T.astype(np.int8))
 
 
 def _frequencies(g, ctx, Zf, q, W):
