@@ -154,6 +154,12 @@ SYMBOLS = {
     "gdca_run_multi_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "gdca_run_ranked_multi": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdca_energies_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdca_energies": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdca_run_energies_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_energies": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.POINTER(Stats)]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -288,6 +294,34 @@ class Context:
                                       _p(sc), C.byref(st))
         self.check(rc, st.info)
         return ii, jj, sc, st.as_dict()
+
+    # ---- energies of sequences under the fitted model (gdca_run_energies) ----
+    def run_energies_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None, K: int = 0):
+        """gdca_run_energies on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run() fits
+        it, then E(x) = 1/2 (x - Pi)' mJ (x - Pi) of the K sequences X (N x K, same layout; None: Z's own M sequences).
+        Returns (E float64[K], stats)."""
+        Ke = int(K) if X_ptr is not None else int(M)
+        E = np.empty(max(Ke, 0), dtype=np.float64)
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rc = self.lib.gdca_run_energies(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
+                                        C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), _p(E), C.byref(st))
+        self.check(rc, st.info)
+        return E, st.as_dict()
+
+    def run_energies_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int, E_ptr: int):
+        """Device-pointer form (Z, X and E resident in HBM).  Returns the stats dict."""
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rc = self.lib.gdca_run_energies_dev(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
+                                            C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), C.c_void_p(E_ptr), C.byref(st))
+        self.check(rc, st.info)
+        return st.as_dict()
+
+    def energies_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int, K: int, E_ptr: int) -> None:
+        """gdca_energies_dev: mJ (n x n), Pi (n), X (N x K int8) and E (K) are device pointers."""
+        self.check(self.lib.gdca_energies_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), C.c_void_p(X_ptr), int(K),
+                                              C.c_void_p(E_ptr)))
 
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):

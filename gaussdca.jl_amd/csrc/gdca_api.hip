@@ -51,6 +51,12 @@ struct gdca_ctx {
     gdca_buf keep;                // pair tally, TALLY_SKIP: the sequences each column's tally visits, their counts and sigma (k_tally_keep)
     gdca_buf Pij;                 // gdca_run_multi: Pij_true of the alignment (n x n, ld = n), the covariance of every pseudocount is built from it
     gdca_buf sc_front;            // gdca_run_multi: the scalars as the front end left them (every pseudocount group starts from them)
+    gdca_buf Xg, Epart, gpart, gvec;  // energies (k_energy.hip): the packed sequences, the per-site-block partial energies, the partials of g = mJ Pi, g and c0
+    // gdca_run_energies: the enqueued run's score stage is the energy stage (a second attempt, refinement or fallback at collect time scores X again)
+    bool pend_energy = false;
+    const int8_t *pend_X = nullptr;
+    int pend_K = 0;
+    double *pend_E = nullptr;
     // an enqueued ranked run (gdca_run_ranked_async): where its ranking will be, and whether enqueueing it worked
     bool rank_pending = false;
     long long rank_len = 0;
@@ -244,6 +250,7 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         {"TALLY_TJ", &t->tally_tj, 0, 32},  {"TALLY_SKIP", &t->tally_skip, 0, 1}, {"MERGE", &t->merge, 1, 8},        {"MERGE_BLOCKS", &t->merge_blocks, 1, 64},
         {"MERGE_MCUS", &t->merge_mcus, -1, 16},  {"MERGE_GROUP", &t->merge_group, -1, 4}, {"MERGE_TILES", &t->merge_tiles, 1, 1 << 20},
         {"CHOLESKY", &t->cholesky, 0, 2},  {"PHASED_FRONTS", &t->phased_fronts, 0, 1}, {"PHASED_GRIDS", &t->phased_grids, -1, 8}, {"PHASED_STREAMS", &t->phased_streams, 1, 64},
+        {"ENERGY_CHUNK", &t->energy_chunk, 0, 1 << 30},
     };
     for (auto &e : ints)
         if (!strcmp(k, e.name)) {
@@ -303,7 +310,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
                                         "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
                                         "GDCA_HAMMING_MODE", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
-                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO"};
+                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK"};
     for (const char *nm : names)
         if (const char *v = getenv(nm)) (void)gdca_tuning_set(t, nm, v);  // an unusable value leaves the default
 }
@@ -497,7 +504,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
     gdca_buf *bufs[] = {&ctx->Zt, &ctx->Zp, &ctx->hist, &ctx->Zb, &ctx->hcnt, &ctx->nk, &ctx->W, &ctx->Wfix, &ctx->Pifix,
                         &ctx->Pipc, &ctx->A, &ctx->G, &ctx->H, &ctx->P, &ctx->Sg, &ctx->Dblk, &ctx->Ld,
                         &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg,
-                        &ctx->Pij, &ctx->sc_front, &ctx->keep};
+                        &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < N_SCRATCH; ++i)
@@ -782,9 +789,33 @@ static gdca_status inverse_stage(gdca_ctx *ctx, int n, int n_pad, bool timed, in
     return check_launch(ctx, "spd_inverse");
 }
 
+// E[K] = 1/2 (x - Pi)' mJ (x - Pi) of the K sequences X (N x K) from the element-wise lower triangle of A (ld): mJ itself (sign +1: the
+// operator-level entry) or -mJ where the sweep left it (sign -1: ctx->A of the fused path).  Illegal bytes of X: sc->bad_symbol bit 2.
+static gdca_status energy_stage(gdca_ctx *ctx, const double *A, size_t ld, double sign, const double *Pi, int N, int q, const int8_t *X_dev,
+                                int K, double *E_dev)
+{
+    hipStream_t s = ctx->stream;
+    const int sdim = q - 1, n = N * sdim;
+    const int nI = gdca_energy_blocks(N), nb = gdca_energy_gblocks(n), Kc = gdca_energy_chunk(N, K, ctx->tune.energy_chunk);
+    CHK(ensure(ctx, ctx->Xg, (size_t)nI * K * sizeof(uint32_t)));
+    CHK(ensure(ctx, ctx->Epart, (size_t)nI * Kc * sizeof(double)));
+    CHK(ensure(ctx, ctx->gpart, (size_t)nb * nb * 64 * sizeof(double)));
+    CHK(ensure(ctx, ctx->gvec, ((size_t)n + 1) * sizeof(double)));
+    double *g = (double *)ctx->gvec.p, *c0 = g + n;
+    gdca_launch_energy_pack(s, X_dev, (uint32_t *)ctx->Xg.p, N, K, q, (gdca_dev_scalars *)ctx->sc.p);
+    gdca_launch_energy_g(s, A, ld, sign, n, Pi, (double *)ctx->gpart.p, g, c0);
+    for (int k0 = 0; k0 < K; k0 += Kc)
+        gdca_launch_energy_rows(s, A, ld, sign, g, c0, (const uint32_t *)ctx->Xg.p, N, sdim, K, k0, std::min(Kc, K - k0), (double *)ctx->Epart.p,
+                                E_dev, ctx->ncu);
+    return check_launch(ctx, "energies");
+}
+
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, int score, int apc, double *S_dev, bool time_fn = false)
 {
     hipStream_t s = ctx->stream;
+    if (ctx->pend_energy)  // gdca_run_energies: the model is scored on X instead of being turned into a contact score
+        return energy_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, ctx->pend_X, ctx->pend_K,
+                            ctx->pend_E);
     if (score == GDCA_SCORE_DI) {
         CHK(ensure(ctx, ctx->Tws, gdca_di_ws_bytes(N, sdim)));
         gdca_launch_di(s, (const double *)ctx->A.p, (size_t)n_pad, (const double *)ctx->Ld.p, N, sdim, S_dev,
@@ -921,6 +952,7 @@ static gdca_status begin(gdca_ctx *ctx)
     gdca_fill_async(ctx->stream, ctx->sc.p, 0, sizeof(gdca_dev_scalars));
     ctx->pend_attempt = 0;
     ctx->pend_rescored = false;
+    ctx->pend_energy = false;
     return GDCA_OK;
 }
 
@@ -1063,6 +1095,7 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
             if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
         }
     }
+    if (h.bad_symbol & 4) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
     if (h.bad_symbol) return fail(ctx, GDCA_EINVAL, "alignment holds a symbol outside 1..q%s%s", "", "");
     if (h.info == INT32_MIN)  // the sweep kernel's watchdog (k_inverse.hip, spin_until): a dependency wait ran out of time
         return fail(ctx, GDCA_EHIP, "SPD inverse aborted: a dependency wait inside the sweep kernel timed out%s%s", "", "");
@@ -2263,6 +2296,50 @@ gdca_status gdca_di_dev(gdca_ctx *ctx, const double *mJ_dev, const double *C_dev
     return GDCA_OK;
 }
 
+gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev, int32_t K,
+                              double *E_dev)
+{
+    CHK(validate(ctx, N, K, q));
+    if (!mJ_dev || !Pi_dev || !X_dev || !E_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(begin(ctx));
+    CHK(energy_stage(ctx, mJ_dev, (size_t)N * (q - 1), 1.0, Pi_dev, N, q, X_dev, K, E_dev));
+    CHK(fetch_scalars(ctx));
+    if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
+    return GDCA_OK;
+}
+
+// the fused form: gdca_run's front end and inverse, then the energy stage in the place of the score stage (score_stage, pend_energy)
+static gdca_status run_energies(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, const int8_t *X_dev,
+                                int32_t K, double *E_dev, gdca_stats *st)
+{
+    CHK(run_front(ctx, Z_dev, N, M, q, p));
+    ctx->pend_energy = true;
+    ctx->pend_X = X_dev;
+    ctx->pend_K = K;
+    ctx->pend_E = E_dev;
+    CHK(run_inverse(ctx));
+    CHK(run_score(ctx, p, nullptr));
+    return gdca_run_collect(ctx, st);
+}
+
+gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                  const int8_t *X_dev, int32_t K, double *E_dev, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (X_dev && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0))
+        return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)%s%s", "", "");
+    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value%s%s", "", "");
+    CHK(not_pending(ctx));
+    gdca_params pp = *p;  // (score and apc are ignored: no contact score is computed)
+    pp.score = GDCA_SCORE_FROB;
+    pp.apc = 0;
+    const gdca_status rs = run_energies(ctx, Z_dev, N, M, q, &pp, X_dev ? X_dev : Z_dev, X_dev ? K : M, E_dev, st);
+    ctx->pend_energy = false;
+    return rs;
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -2422,6 +2499,37 @@ gdca_status gdca_apc(gdca_ctx *ctx, double *S, int32_t N)
     CHK(to_dev(ctx, ctx->scratch[2], S, (size_t)N * N * sizeof(double)));
     CHK(gdca_apc_dev(ctx, (double *)ctx->scratch[2].p, N));
     return to_host(ctx, S, ctx->scratch[2], (size_t)N * N * sizeof(double));
+}
+
+gdca_status gdca_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K, double *E)
+{
+    CHK(validate(ctx, N, K, q));
+    if (!mJ || !Pi || !X || !E) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)N * (q - 1);
+    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
+    CHK(to_dev(ctx, ctx->scratch[2], Pi, n * sizeof(double)));
+    CHK(to_dev(ctx, ctx->scratch[0], X, (size_t)N * K));
+    CHK(ensure(ctx, ctx->scratch[3], (size_t)K * sizeof(double)));
+    CHK(gdca_energies_dev(ctx, (const double *)ctx->scratch[1].p, (const double *)ctx->scratch[2].p, N, q, (const int8_t *)ctx->scratch[0].p, K,
+                          (double *)ctx->scratch[3].p));
+    return to_host(ctx, E, ctx->scratch[3], (size_t)K * sizeof(double));
+}
+
+gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, const int8_t *X_host,
+                              int32_t K, double *E_host, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    if (!Z_host || !E_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (X_host && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int Ke = X_host ? K : M;
+    CHK(to_dev(ctx, ctx->scratch[0], Z_host, (size_t)N * M));
+    if (X_host) CHK(to_dev(ctx, ctx->scratch[3], X_host, (size_t)N * K));
+    CHK(ensure(ctx, ctx->scratch[5], (size_t)Ke * sizeof(double)));
+    CHK(gdca_run_energies_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, X_host ? (const int8_t *)ctx->scratch[3].p : nullptr, K,
+                              (double *)ctx->scratch[5].p, st));
+    return to_host(ctx, E_host, ctx->scratch[5], (size_t)Ke * sizeof(double));
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

@@ -69,6 +69,7 @@ struct gdca_tuning {
     int refine;             // GDCA_REFINE: -1 = one Newton-Schulz step where the inverse looks ill-conditioned (auto), 0 = never, 1 = always
     double refine_cond;     // GDCA_REFINE_COND: the threshold of auto: the a-priori bound of cond_2(C) first, beyond it kappa_1 = ||C||_1 ||X||_1
     int cholesky;           // GDCA_CHOLESKY: the blocked dpotrf + dpotri fallback: 0 = never, 1 = where the sweep gave up (default), 2 = always
+    int energy_chunk;       // GDCA_ENERGY_CHUNK: sequences one launch of the energy gather kernel takes; 0 = as many as keep its partials within ~256 MB
     char sweep_trace[256];  // GDCA_SWEEP_TRACE: file the in-kernel trace of the next inverse is written to ("" = off)
 };
 void gdca_tuning_from_env(gdca_tuning *t);
@@ -226,3 +227,17 @@ size_t gdca_di_ws_bytes(int N, int sdim);
 void gdca_launch_di(hipStream_t s, const double *A, size_t ld, const double *Ld, int N, int sdim, double *S,
                     double *Tws, gdca_dev_scalars *sc);
 void gdca_launch_apc(hipStream_t s, double *S, int N, double *rowsum_ws);
+
+// ---- k_energy.hip: E(x) = 1/2 (x - Pi)' mJ (x - Pi) of K sequences ---------------------------------------------------------------
+int gdca_energy_blocks(int N);        // site blocks (of four sites) of the gather kernel
+int gdca_energy_gblocks(int n);       // 64-blocks of the g pass
+int gdca_energy_chunk(int N, int K, int wanted);  // sequences one launch of the gather kernel takes (wanted > 0: that many)
+// Xg: uint32 [gdca_energy_blocks(N)][K]; bytes of X outside 1..q set bit 2 of sc->bad_symbol (and count as gaps)
+void gdca_launch_energy_pack(hipStream_t s, const int8_t *X, uint32_t *Xg, int N, int K, int q, gdca_dev_scalars *sc);
+// g = mJ Pi (n entries) and c0 = Pi' g from the element-wise lower triangle of A (ld; sign -1: A holds -mJ, the sweep's storage);
+// part: nb x (nb * 64) doubles, nb = gdca_energy_gblocks(n)
+void gdca_launch_energy_g(hipStream_t s, const double *A, size_t ld, double sign, int n, const double *Pi, double *part, double *g,
+                          double *c0);
+// E[k0 .. k0 + Kc - 1]; part: gdca_energy_blocks(N) x Kc doubles
+void gdca_launch_energy_rows(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const double *c0, const uint32_t *Xg,
+                             int N, int sdim, int K, int k0, int Kc, double *part, double *E, int ncu);

@@ -309,6 +309,35 @@ def correct_APC(S, ctx=None) -> np.ndarray:
     return A
 
 
+def sequence_energies(mJ, Pi, X, q: int = 21, ctx=None) -> np.ndarray:
+    """E[k] = 1/2 (x_k - Pi)' mJ (x_k - Pi) for the K columns of X (shape (N, K) like Z, symbols 1..q, q = the gap): minus the
+    log-likelihood of each sequence under the Gaussian model with precision mJ = inv(cholesky(C)) (src/GaussDCA.jl:34) and mean
+    Pi (add_pseudocount's Pi, :30), up to the model's constant 1/2 log det(2 pi C), which is not included.  Lower = fits better.
+    mJ must be symmetric (its lower triangle is read)."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    Xa = np.asarray(X)
+    if Xa.dtype != np.int8 and Xa.ndim == 2:  # (a wider type is not cast blindly: 261 would wrap to the legal symbol 5)
+        if not np.issubdtype(Xa.dtype, np.integer) or (Xa.size and (Xa.min() < 1 or Xa.max() > 31)):
+            raise ArgumentError("X must hold integer symbols between 1 and q")
+    Xf = _zf(Xa)
+    N, K = Xf.shape
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = N * (int(q) - 1)
+    if mJ.shape != (n, n) or Pi.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: X has N = {N} sites, q = {q}, so mJ must be {n} x {n} and Pi have {n} entries "
+                            f"(got {mJ.shape} and {Pi.shape})")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    ctx = ctx or default_context()
+    E = np.empty(K, dtype=np.float64)
+    ctx.check(ctx.lib.gdca_energies(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xf), K, _lib._p(E)))
+    return E
+
+
 def printrank(io, R: Sequence[Tuple[int, int, float]] = None):
     """printrank(io, R) / printrank(filename, R): one "%i %i %e" line per entry
     (src/GaussDCA.jl:67-74).  printrank(R) alone writes to stdout (the reference's one-argument

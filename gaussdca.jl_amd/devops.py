@@ -82,6 +82,14 @@ def correct_APC_dev(ctx: Context, dS, N: int):
     return dS
 
 
+def sequence_energies_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, dE=None):
+    """E[k] = 1/2 (x_k - Pi)' mJ (x_k - Pi) of the K sequences X (N x K int8) with every array in HBM (gdca_energies_dev):
+    mJ from inv_cholesky_dev, Pi from add_pseudocount_dev"""
+    dE = dE or DeviceBuffer(ctx, 8 * K)
+    ctx.energies_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), _ptr(dX).value, int(K), _ptr(dE).value)
+    return dE
+
+
 def scores_stepwise(Z, q: int, pseudocount: float = 0.8, theta=":auto", score: str = "frob", ctx: Context = None
                     ) -> Tuple[np.ndarray, dict]:
     """The six statements of src/GaussDCA.jl:28-42 one by one, arrays resident in HBM.  Z: (N, M) int8.

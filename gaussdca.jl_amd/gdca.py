@@ -84,6 +84,65 @@ def gDCA(filename: str, pseudocount: float = 0.8, theta=":auto", max_gap_fractio
     return Ranking(ii, jj, sc)
 
 
+def gDCA_energies(filename: str, sequences=None, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+                  remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
+    """Energies of sequences under the Gaussian model gDCA fits to the alignment in ``filename`` (same reading, reweighting,
+    pseudocount, covariance and inverse; same validation and messages): E(x) = 1/2 (x - Pi)' mJ (x - Pi), minus the log-likelihood
+    up to the model's constant.  Lower = fits the family better.
+
+    ``sequences``: ``None`` scores the alignment's own sequences (after the gap filter and the optional deduplication); an
+    ``(N, K)`` int8 array (symbols 1..q like ``Z``) scores its columns; a string names a second FASTA file, read with the same reader
+    and ``max_gap_fraction = 1.0`` -- every record is kept, so the energies line up with the records.  Stats go to ``last_stats``."""
+    global last_stats
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_energies() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    if isinstance(sequences, (str, bytes, os.PathLike)):
+        if not os.path.isfile(sequences):
+            raise ArgumentError(f"cannot open file {sequences}")
+        X = read_fasta_alignment(os.fspath(sequences) if not isinstance(sequences, bytes) else sequences.decode(), 1.0)
+    elif sequences is not None:
+        X = np.asarray(sequences)
+        if X.ndim != 2:
+            raise ArgumentError("sequences must be an N x K matrix")
+        if X.dtype != np.int8:  # (a wider type is not cast blindly: 261 would wrap to the legal symbol 5)
+            if not np.issubdtype(X.dtype, np.integer) or (X.size and (X.min() < 1 or X.max() > 31)):
+                raise ArgumentError("sequences must hold integer symbols between 1 and q")
+        X = np.asfortranarray(X, dtype=np.int8)
+    else:
+        X = None
+
+    def _run(ptr, N, M, q):
+        if q >= 32:
+            raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+        if X is not None and X.shape[0] != N:
+            raise ArgumentError(f"sequences have {X.shape[0]} sites, the alignment has {N}")
+        if X is not None and X.shape[1] < 1:
+            raise ArgumentError("sequences holds no sequence")
+        c = ctx or default_context()
+        if X is None:
+            return c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta))
+        return c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), X.ctypes.data, X.shape[1])
+
+    if remove_dups:
+        Z = read_fasta_alignment(filename, max_gap_fraction)
+        Z, _ = remove_duplicate_sequences(Z)
+        Zf = np.asfortranarray(Z, dtype=np.int8)
+        E, last_stats = _run(Zf.ctypes.data, Zf.shape[0], Zf.shape[1], int(Z.max()))
+    else:
+        with FastaAlignment(filename, max_gap_fraction) as fa:
+            E, last_stats = _run(fa.ptr, fa.N, fa.M, fa.q)
+    if last_stats.get("refined", 0) < 0:
+        import warnings
+
+        warnings.warn("gDCA: the covariance is too ill-conditioned for the block sweep even with its refinement step "
+                      f"(||inv(C)||_1 = {last_stats['inverse_norm1']:.3g}; pseudocount {pseudocount}): energies are unreliable",
+                      RuntimeWarning, stacklevel=2)
+    return E
+
+
 def _setting(s):
     """(pseudocount, score) or {"pseudocount": .., "score": ..} -> (pseudocount, score)"""
     if isinstance(s, dict):

@@ -174,7 +174,8 @@ gdca_status gdca_ctx_set_timing(gdca_ctx *ctx, int32_t enabled);
  * 128-blocks), MERGE_TILES, MERGE_GROUP, MERGE_MCUS, PHASED_FRONTS (1: the front ends of a phase batch run side by side on the
  * members' streams, 0: one after the other), PHASED_STREAMS (how many of those streams, the first members', they are spread over: default 4), PHASED_GRIDS (the kernels of a phase batch as ONE grid per kernel kind carrying all members of a group: -1 = 1 group for small families, 4 for big ones [default], 1 .. 8 = that many groups side by side, 0 = a launch per member and kernel as PHASED_FRONTS describes); REFINE (auto | 0 | 1: one Newton-Schulz step on an inverse that looks
  * ill-conditioned / never / always) and REFINE_COND (the threshold of auto, default 1e6); CHOLESKY (0 | 1 | 2: the blocked
- * dpotrf + dpotri fallback never / where the sweep gave up [default] / for every inverse).  The schedule switches change results
+ * dpotrf + dpotri fallback never / where the sweep gave up [default] / for every inverse); ENERGY_CHUNK (sequences one launch of the energy gather
+ * kernel takes, 0 = the rule [default]: the same bits whatever it is).  The schedule switches change results
  * at rounding level at most (another summation order); REFINE improves an ill-conditioned inverse.  GDCA_EINVAL: unknown key
  * or unusable value. */
 gdca_status gdca_ctx_set_option(gdca_ctx *ctx, const char *key, const char *value);
@@ -282,6 +283,30 @@ gdca_status gdca_fn_dev(gdca_ctx *ctx, const double *mJ_dev, int32_t N, int32_t 
 gdca_status gdca_di_dev(gdca_ctx *ctx, const double *mJ_dev, const double *C_dev, int32_t N, int32_t q, double *S_dev);
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N);
 
+/* ---- energies: scoring sequences under the fitted model ------------------------------------------------------------------
+ * The other use of mJ = inv(cholesky(C)) (src/GaussDCA.jl:34): the likelihood of a sequence under the multivariate Gaussian whose
+ * covariance :32 builds (the paper's "protein-interaction partners" half: partner matching, filtering, ranking variants).  With the
+ * one-hot encoding x of a sequence (x[i*s + a - 1] = 1 for symbol a in 1..s at 0-based site i; symbol q, the gap, leaves the site's
+ * block zero) and Pi the single-site frequencies WITH pseudocount (add_pseudocount's first result, :30):
+ *     E(x) = 1/2 (x - Pi)' mJ (x - Pi)
+ * i.e. minus the log-likelihood up to the model's constant 1/2 log det(2 pi C), which is NOT included (the block sweep does not
+ * produce the Cholesky pivots; comparisons inside one model never need it).  Lower energy = better fit.
+ * X is N x K int8 column-major like Z (sequence k = the N bytes X[k*N ..]), K >= 1; E has K entries.  mJ is n x n column-major,
+ * leading dimension n, symmetric: only its lower triangle is read.  Every sum is taken in a fixed order in f64 (no floating-point
+ * atomics): a sequence's energy is the same bits from run to run, whatever other sequences share the call and wherever it stands
+ * among them.  GDCA_EINVAL: K < 1, q outside 2..31, a null pointer -- nothing is run -- or a byte of X outside 1..q (detected on the
+ * device; nothing is read out of bounds for it).  On failure E is unspecified.  Synchronous. */
+gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q,
+                              const int8_t *X_dev, int32_t K, double *E_dev);
+/* Fused: fits the model on Z exactly as gdca_run does (theta, reweighting, tallies, pseudocount, covariance, the SPD inverse with its
+ * conditioning screen, refinement, Cholesky fallback and second attempt -- the same code, so the model is bit for bit the one gdca_run
+ * scores from), then computes the energies of X under it; mJ never leaves HBM.  X == NULL scores Z itself (K is then ignored and M
+ * energies are written).  p->score and p->apc are ignored.  Status codes as gdca_run (GDCA_ENOTPD with st->info, ...).  Stats: everything
+ * up to and including the inverse as a gdca_run of the same parameters reports it; ms_score is the energy stage, ms_fn 0, ms_total runs
+ * to the end of the energy stage. */
+gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                  const int8_t *X_dev, int32_t K, double *E_dev, gdca_stats *st);
+
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* compute_theta's all-pairs identity sum (inside compute_weighted_frequencies, :28) */
 gdca_status gdca_pair_identity_sum(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, uint64_t *out);
@@ -313,6 +338,13 @@ gdca_status gdca_fn(gdca_ctx *ctx, const double *mJ, int32_t N, int32_t q, doubl
 gdca_status gdca_di(gdca_ctx *ctx, const double *mJ, const double *C, int32_t N, int32_t q, double *S);
 /* correct_APC(S) (:42, :78-86), in place */
 gdca_status gdca_apc(gdca_ctx *ctx, double *S, int32_t N);
+
+/* energies with host pointers: upload, the _dev form, download (the n x n matrix crosses PCIe: a caller who has just fitted the model
+ * uses gdca_run_energies, where only Z, X and E do) */
+gdca_status gdca_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                          double *E);
+gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                              const int8_t *X_host, int32_t K, double *E_host, gdca_stats *st);
 
 /* ---- host-side utilities around the hot path (plain C++, no GPU): the reference's callers of the path -------- */
 /* CPUs this process can really use: hardware threads capped by the cgroup CPU quota (a container may see 256 threads and be given

@@ -15,7 +15,7 @@
 module GaussDCAHip
 
 export gDCA, gDCA_stepwise, printrank, compute_weights, compute_weighted_frequencies, add_pseudocount,
-       compute_FN, compute_DI_gauss
+       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies
 
 using LinearAlgebra
 import DCAUtils                                   # host-side I/O only: read_fasta_alignment, remove_duplicate_sequences
@@ -169,6 +169,46 @@ function compute_FN(mJ::Matrix{Float64}, q::Integer = 21)
     GC.@preserve mJ S check(ccall((:gdca_fn, libgdca), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}),
                                   ctx(), mJ, N, q, S))
     return S
+end
+
+# E[k] = 1/2 (x_k - Pi)' mJ (x_k - Pi) for the K columns of X (N x K like Z): minus the log-likelihood of each sequence under the
+# fitted Gaussian model, up to the model's constant (include/gdca.h, "energies").  Lower = fits better.
+function sequence_energies(mJ::Matrix{Float64}, Pi::Vector{Float64}, X::Matrix{Int8}, q::Integer = 21)
+    N, K = size(X); n = N * (q - 1)
+    (size(mJ) == (n, n) && length(Pi) == n) || throw(ArgumentError("incompatible sizes of mJ, Pi, X and q"))
+    E = Vector{Float64}(undef, K)
+    GC.@preserve mJ Pi X E check(ccall((:gdca_energies, libgdca), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int8}, Int32, Ptr{Float64}), ctx(), mJ, Pi, N, q, X, K, E))
+    return E
+end
+
+# gDCA's fit (same keywords, minus score and min_separation), then the energies of `sequences` under it: nothing = the alignment's
+# own sequences, a Matrix{Int8} (N x K), or the name of a second FASTA file (read with max_gap_fraction = 1: every record kept)
+function gDCA_energies(filename::AbstractString; sequences = nothing, pseudocount::Real = 0.8, θ = :auto,
+                       max_gap_fraction::Real = 0.9, remove_dups::Bool = false)
+    check_arguments(filename, pseudocount, θ, max_gap_fraction, :frob, 1)
+    Z = DCAUtils.read_fasta_alignment(filename, max_gap_fraction)
+    if remove_dups
+        Z, _ = DCAUtils.remove_duplicate_sequences(Z)
+    end
+    q = Int(maximum(Z))
+    q ≥ 32 && error("parameter q=$q is too big (max 31 is allowed)")
+    X = sequences isa AbstractString ? DCAUtils.read_fasta_alignment(sequences, 1.0) : sequences
+    N, M = size(Z)
+    (X === nothing || size(X, 1) == N) || throw(ArgumentError("sequences have $(size(X, 1)) sites, the alignment has $N"))
+    K = X === nothing ? M : size(X, 2)
+    E = Vector{Float64}(undef, K)
+    p = Ref(GdcaParams(Float64(pseudocount), theta_arg(θ), 0, 0))
+    st = GdcaStats()
+    Xp = X === nothing ? Ptr{Int8}(C_NULL) : pointer(X)
+    GC.@preserve Z X E begin
+        rc = ccall((:gdca_run_energies, libgdca), Cint,
+                   (Ptr{Cvoid}, Ptr{Int8}, Int32, Int32, Int32, Ref{GdcaParams}, Ptr{Int8}, Int32, Ptr{Float64}, Ref{GdcaStats}),
+                   ctx(), Z, N, M, q, p, Xp, K, E, st)
+    end
+    check(rc, st.info)
+    st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: energies are unreliable" pseudocount
+    return E
 end
 
 function compute_DI_gauss(mJ::Matrix{Float64}, C::Matrix{Float64}, q::Integer = 21)
