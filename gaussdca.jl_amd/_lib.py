@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("GDCA_LIB") or os.path.join(_HERE, "libgdca.so")
 
 GDCA_OK, GDCA_EINVAL, GDCA_ENOTPD, GDCA_EHIP, GDCA_ENOMEM, GDCA_ENOCONV = 0, 1, 2, 3, 4, 5
 SCORE_FROB, SCORE_DI = 0, 1
+PAIR_COUPLING, PAIR_ENERGY = 0, 1  # `what` of gdca_pair_energies: the cross-term matrix R alone, or the energy of every concatenation
 ABI_VERSION = 6  # GDCA_VERSION_MAJOR * 1000 + GDCA_VERSION_MINOR of the header this binding mirrors
 
 
@@ -160,6 +161,14 @@ SYMBOLS = {
                                         C.c_void_p, C.POINTER(Stats)]),
     "gdca_run_energies": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
                                     C.c_void_p, C.POINTER(Stats)]),
+    "gdca_pair_energies_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_pair_energies": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_run_pair_energies_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_pair_energies": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -322,6 +331,43 @@ class Context:
         """gdca_energies_dev: mJ (n x n), Pi (n), X (N x K int8) and E (K) are device pointers."""
         self.check(self.lib.gdca_energies_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), C.c_void_p(X_ptr), int(K),
                                               C.c_void_p(E_ptr)))
+
+    # ---- energies of every pairing across a split alignment (gdca_run_pair_energies) ----
+    def run_pair_energies_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int,
+                              XA_ptr: int | None = None, KA: int = 0, XB_ptr: int | None = None, KB: int = 0, what: int = 1):
+        """gdca_run_pair_energies on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run()
+        fits it, then E[a, b] of the pairings of the KA sequences XA (split x KA) with the KB sequences XB ((N - split) x KB); None:
+        the halves of Z's own M sequences.  ``what``: PAIR_ENERGY or PAIR_COUPLING.  Returns (E float64 (KA, KB), stats)."""
+        ka = int(KA) if XA_ptr is not None else int(M)
+        kb = int(KB) if XB_ptr is not None else int(M)
+        E = np.empty((max(ka, 0), max(kb, 0)), dtype=np.float64, order="F")
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rc = self.lib.gdca_run_pair_energies(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm), int(split),
+                                             C.c_void_p(XA_ptr) if XA_ptr is not None else None, int(KA),
+                                             C.c_void_p(XB_ptr) if XB_ptr is not None else None, int(KB), int(what), _p(E), C.byref(st))
+        self.check(rc, st.info)
+        return E, st.as_dict()
+
+    def run_pair_energies_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int, XA_ptr: int | None,
+                              KA: int, XB_ptr: int | None, KB: int, what: int, E_ptr: int):
+        """Device-pointer form (Z, XA, XB and E resident in HBM; E column-major KA x KB).  Returns the stats dict."""
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rc = self.lib.gdca_run_pair_energies_dev(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm), int(split),
+                                                 C.c_void_p(XA_ptr) if XA_ptr is not None else None, int(KA),
+                                                 C.c_void_p(XB_ptr) if XB_ptr is not None else None, int(KB), int(what), C.c_void_p(E_ptr),
+                                                 C.byref(st))
+        self.check(rc, st.info)
+        return st.as_dict()
+
+    def pair_energies_dev(self, mJ_ptr: int, Pi_ptr: int | None, N: int, q: int, split: int, XA_ptr: int, KA: int, XB_ptr: int, KB: int,
+                          what: int, E_ptr: int) -> None:
+        """gdca_pair_energies_dev: mJ (n x n), Pi (n; None for PAIR_COUPLING), XA (split x KA int8), XB ((N - split) x KB int8) and E
+        (KA x KB, column-major) are device pointers."""
+        self.check(self.lib.gdca_pair_energies_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr) if Pi_ptr is not None else None, int(N),
+                                                   int(q), int(split), C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB), int(what),
+                                                   C.c_void_p(E_ptr)))
 
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):

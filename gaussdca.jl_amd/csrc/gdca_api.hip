@@ -57,6 +57,14 @@ struct gdca_ctx {
     const int8_t *pend_X = nullptr;
     int pend_K = 0;
     double *pend_E = nullptr;
+    // pair energies (k_pair_energy.hip): the packed symbols of the A and the B halves, the gap-padded halves and their marginal energies,
+    // the folded rows T of one chunk of A sequences
+    gdca_buf PXa, PXb, PXpad, PEab, PT;
+    // gdca_run_pair_energies: the enqueued run's score stage is the pair stage (run again at collect time like the energy stage)
+    bool pend_pair = false;
+    const int8_t *pend_XA = nullptr, *pend_XB = nullptr;
+    size_t pend_strideA = 0, pend_strideB = 0;
+    int pend_KA = 0, pend_KB = 0, pend_split = 0, pend_what = 0;
     // an enqueued ranked run (gdca_run_ranked_async): where its ranking will be, and whether enqueueing it worked
     bool rank_pending = false;
     long long rank_len = 0;
@@ -250,7 +258,7 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         {"TALLY_TJ", &t->tally_tj, 0, 32},  {"TALLY_SKIP", &t->tally_skip, 0, 1}, {"MERGE", &t->merge, 1, 8},        {"MERGE_BLOCKS", &t->merge_blocks, 1, 64},
         {"MERGE_MCUS", &t->merge_mcus, -1, 16},  {"MERGE_GROUP", &t->merge_group, -1, 4}, {"MERGE_TILES", &t->merge_tiles, 1, 1 << 20},
         {"CHOLESKY", &t->cholesky, 0, 2},  {"PHASED_FRONTS", &t->phased_fronts, 0, 1}, {"PHASED_GRIDS", &t->phased_grids, -1, 8}, {"PHASED_STREAMS", &t->phased_streams, 1, 64},
-        {"ENERGY_CHUNK", &t->energy_chunk, 0, 1 << 30},
+        {"ENERGY_CHUNK", &t->energy_chunk, 0, 1 << 30}, {"PAIR_CHUNK", &t->pair_chunk, 0, 1 << 30},
     };
     for (auto &e : ints)
         if (!strcmp(k, e.name)) {
@@ -310,7 +318,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
                                         "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
                                         "GDCA_HAMMING_MODE", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
-                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK"};
+                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK"};
     for (const char *nm : names)
         if (const char *v = getenv(nm)) (void)gdca_tuning_set(t, nm, v);  // an unusable value leaves the default
 }
@@ -504,7 +512,8 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
     gdca_buf *bufs[] = {&ctx->Zt, &ctx->Zp, &ctx->hist, &ctx->Zb, &ctx->hcnt, &ctx->nk, &ctx->W, &ctx->Wfix, &ctx->Pifix,
                         &ctx->Pipc, &ctx->A, &ctx->G, &ctx->H, &ctx->P, &ctx->Sg, &ctx->Dblk, &ctx->Ld,
                         &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg,
-                        &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec};
+                        &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
+                        &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < N_SCRATCH; ++i)
@@ -810,9 +819,44 @@ static gdca_status energy_stage(gdca_ctx *ctx, const double *A, size_t ld, doubl
     return check_launch(ctx, "energies");
 }
 
+// E[a + KA * b] of the KA x KB pairings a (+) b across the split (k_pair_energy.hip) from the element-wise lower triangle of A (ld, sign
+// as energy_stage).  XA / XB point at the first site of sequence 0's half; sequence k's starts strideA / strideB bytes on (so the
+// columns of an alignment serve as they lie).  what = GDCA_PAIR_ENERGY: the marginal energies through energy_stage on the gap-padded
+// halves (Pi needed), combined in the gather kernel's epilogue; GDCA_PAIR_COUPLING: R alone.  Illegal bytes: sc->bad_symbol bit 2.
+static gdca_status pair_stage(gdca_ctx *ctx, const double *A, size_t ld, double sign, const double *Pi, int N, int q, int split,
+                              const int8_t *XA, size_t strideA, int KA, const int8_t *XB, size_t strideB, int KB, int what, double *E_dev)
+{
+    hipStream_t s = ctx->stream;
+    const int sdim = q - 1, n = N * sdim, nB = (N - split) * sdim;
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    CHK(ensure(ctx, ctx->PXa, (size_t)gdca_pair_blocks(split) * KA * sizeof(uint32_t)));
+    CHK(ensure(ctx, ctx->PXb, (size_t)gdca_pair_blocks(N - split) * KB * sizeof(uint32_t)));
+    gdca_launch_pair_pack(s, XA, strideA, split, KA, q, (uint32_t *)ctx->PXa.p, sc);
+    gdca_launch_pair_pack(s, XB, strideB, N - split, KB, q, (uint32_t *)ctx->PXb.p, sc);
+    const double *EAB = nullptr, *c0 = nullptr;
+    if (what == GDCA_PAIR_ENERGY) {
+        CHK(ensure(ctx, ctx->PXpad, (size_t)N * ((size_t)KA + (size_t)KB)));
+        CHK(ensure(ctx, ctx->PEab, ((size_t)KA + (size_t)KB) * sizeof(double)));
+        gdca_launch_pair_pad(s, XA, strideA, XB, strideB, N, split, KA, KB, q, (int8_t *)ctx->PXpad.p);
+        CHK(energy_stage(ctx, A, ld, sign, Pi, N, q, (const int8_t *)ctx->PXpad.p, KA + KB, (double *)ctx->PEab.p));
+        EAB = (const double *)ctx->PEab.p;
+        c0 = (const double *)ctx->gvec.p + n;
+    }
+    const int Ac = gdca_pair_chunk(nB, KA, ctx->tune.pair_chunk);
+    CHK(ensure(ctx, ctx->PT, (size_t)Ac * nB * sizeof(double)));
+    for (int a0 = 0; a0 < KA; a0 += Ac)
+        gdca_launch_pair_chunk(s, A, ld, sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim, KA, KB, a0,
+                               std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev, ctx->ncu);
+    return check_launch(ctx, "pair energies");
+}
+
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, int score, int apc, double *S_dev, bool time_fn = false)
 {
     hipStream_t s = ctx->stream;
+    if (ctx->pend_pair)  // gdca_run_pair_energies: the model is scored on the pairings across the split
+        return pair_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, ctx->pend_split,
+                          ctx->pend_XA, ctx->pend_strideA, ctx->pend_KA, ctx->pend_XB, ctx->pend_strideB, ctx->pend_KB, ctx->pend_what,
+                          ctx->pend_E);
     if (ctx->pend_energy)  // gdca_run_energies: the model is scored on X instead of being turned into a contact score
         return energy_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, ctx->pend_X, ctx->pend_K,
                             ctx->pend_E);
@@ -953,6 +997,7 @@ static gdca_status begin(gdca_ctx *ctx)
     ctx->pend_attempt = 0;
     ctx->pend_rescored = false;
     ctx->pend_energy = false;
+    ctx->pend_pair = false;
     return GDCA_OK;
 }
 
@@ -2340,6 +2385,65 @@ gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N,
     return rs;
 }
 
+// the argument checks the four pair entry points share (nothing has run when one fails); KA / KB as they will be used
+static gdca_status validate_pair(gdca_ctx *ctx, int N, int q, int split, long long KA, long long KB, int what)
+{
+    CHK(validate(ctx, N, 1, q));
+    if (split < 1 || split > N - 1) return fail(ctx, GDCA_EINVAL, "invalid split (must be between 1 and N - 1)%s%s", "", "");
+    if (KA < 1 || KB < 1 || KA + KB > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (what != GDCA_PAIR_COUPLING && what != GDCA_PAIR_ENERGY) return fail(ctx, GDCA_EINVAL, "invalid value of `what`%s%s", "", "");
+    return GDCA_OK;
+}
+
+gdca_status gdca_pair_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, int32_t split,
+                                   const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what, double *E_dev)
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
+    if (!mJ_dev || !XA_dev || !XB_dev || !E_dev || (what == GDCA_PAIR_ENERGY && !Pi_dev))
+        return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(begin(ctx));
+    CHK(pair_stage(ctx, mJ_dev, (size_t)N * (q - 1), 1.0, Pi_dev, N, q, split, XA_dev, (size_t)split, KA, XB_dev, (size_t)(N - split), KB, what,
+                   E_dev));
+    CHK(fetch_scalars(ctx));
+    if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
+    return GDCA_OK;
+}
+
+gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                       const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what, double *E_dev,
+                                       gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_pair(ctx, N, q, split, XA_dev ? KA : M, XB_dev ? KB : M, what));
+    if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0))
+        return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)%s%s", "", "");
+    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value%s%s", "", "");
+    CHK(not_pending(ctx));
+    gdca_params pp = *p;  // (score and apc are ignored: no contact score is computed)
+    pp.score = GDCA_SCORE_FROB;
+    pp.apc = 0;
+    // the fused form as run_energies: the pair stage in the place of the score stage (score_stage, pend_pair)
+    gdca_status rs = run_front(ctx, Z_dev, N, M, q, &pp);
+    if (rs == GDCA_OK) {
+        ctx->pend_pair = true;
+        ctx->pend_split = split;
+        ctx->pend_what = what;
+        ctx->pend_XA = XA_dev ? XA_dev : Z_dev;  // (the A halves of Z's own sequences lie N bytes apart)
+        ctx->pend_strideA = XA_dev ? (size_t)split : (size_t)N;
+        ctx->pend_KA = XA_dev ? KA : M;
+        ctx->pend_XB = XB_dev ? XB_dev : Z_dev + split;
+        ctx->pend_strideB = XB_dev ? (size_t)(N - split) : (size_t)N;
+        ctx->pend_KB = XB_dev ? KB : M;
+        ctx->pend_E = E_dev;
+        rs = run_inverse(ctx);
+        if (rs == GDCA_OK) rs = run_score(ctx, &pp, nullptr);
+        if (rs == GDCA_OK) rs = gdca_run_collect(ctx, st);
+    }
+    ctx->pend_pair = false;
+    return rs;
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -2530,6 +2634,42 @@ gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, in
     CHK(gdca_run_energies_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, X_host ? (const int8_t *)ctx->scratch[3].p : nullptr, K,
                               (double *)ctx->scratch[5].p, st));
     return to_host(ctx, E_host, ctx->scratch[5], (size_t)Ke * sizeof(double));
+}
+
+gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split, const int8_t *XA,
+                               int32_t KA, const int8_t *XB, int32_t KB, int32_t what, double *E)
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
+    if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)N * (q - 1), ne = (size_t)KA * (size_t)KB * sizeof(double);
+    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
+    if (Pi) CHK(to_dev(ctx, ctx->scratch[2], Pi, n * sizeof(double)));
+    CHK(to_dev(ctx, ctx->scratch[0], XA, (size_t)split * KA));
+    CHK(to_dev(ctx, ctx->scratch[3], XB, (size_t)(N - split) * KB));
+    CHK(ensure(ctx, ctx->scratch[5], ne));
+    CHK(gdca_pair_energies_dev(ctx, (const double *)ctx->scratch[1].p, Pi ? (const double *)ctx->scratch[2].p : nullptr, N, q, split,
+                               (const int8_t *)ctx->scratch[0].p, KA, (const int8_t *)ctx->scratch[3].p, KB, what, (double *)ctx->scratch[5].p));
+    return to_host(ctx, E, ctx->scratch[5], ne);
+}
+
+gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                   const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, int32_t what, double *E_host,
+                                   gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_pair(ctx, N, q, split, XA_host ? KA : M, XB_host ? KB : M, what));
+    if (!Z_host || !E_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ne = (size_t)(XA_host ? KA : M) * (size_t)(XB_host ? KB : M) * sizeof(double);
+    CHK(to_dev(ctx, ctx->scratch[0], Z_host, (size_t)N * M));
+    if (XA_host) CHK(to_dev(ctx, ctx->scratch[3], XA_host, (size_t)split * KA));
+    if (XB_host) CHK(to_dev(ctx, ctx->scratch[4], XB_host, (size_t)(N - split) * KB));
+    CHK(ensure(ctx, ctx->scratch[5], ne));
+    CHK(gdca_run_pair_energies_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, split,
+                                   XA_host ? (const int8_t *)ctx->scratch[3].p : nullptr, KA, XB_host ? (const int8_t *)ctx->scratch[4].p : nullptr,
+                                   KB, what, (double *)ctx->scratch[5].p, st));
+    return to_host(ctx, E_host, ctx->scratch[5], ne);
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

@@ -70,6 +70,7 @@ struct gdca_tuning {
     double refine_cond;     // GDCA_REFINE_COND: the threshold of auto: the a-priori bound of cond_2(C) first, beyond it kappa_1 = ||C||_1 ||X||_1
     int cholesky;           // GDCA_CHOLESKY: the blocked dpotrf + dpotri fallback: 0 = never, 1 = where the sweep gave up (default), 2 = always
     int energy_chunk;       // GDCA_ENERGY_CHUNK: sequences one launch of the energy gather kernel takes; 0 = as many as keep its partials within ~256 MB
+    int pair_chunk;         // GDCA_PAIR_CHUNK: sequences of protein A one launch of the pair-energy fold / gather kernels takes; 0 = as many as keep their folded rows within ~256 MB (the rule), a smaller count is taken as given, a larger one is cut to the rule
     char sweep_trace[256];  // GDCA_SWEEP_TRACE: file the in-kernel trace of the next inverse is written to ("" = off)
 };
 void gdca_tuning_from_env(gdca_tuning *t);
@@ -241,3 +242,17 @@ void gdca_launch_energy_g(hipStream_t s, const double *A, size_t ld, double sign
 // E[k0 .. k0 + Kc - 1]; part: gdca_energy_blocks(N) x Kc doubles
 void gdca_launch_energy_rows(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const double *c0, const uint32_t *Xg,
                              int N, int sdim, int K, int k0, int Kc, double *part, double *E, int ncu);
+
+// ---- k_pair_energy.hip: E(a (+) b) of K_A x K_B pairings across a split alignment -------------------------------------------------------
+int gdca_pair_blocks(int Ns);                       // site blocks (of four sites) of a packed range of Ns sites
+int gdca_pair_chunk(int nB, int KA, int wanted);    // sequences a one launch of the fold / gather kernels takes (wanted > 0: that many)
+// out: uint32 [gdca_pair_blocks(Ns)][K] from the Ns sites X points at (sequence k: X + k * stride); bytes outside 1..q set bit 2 of
+// sc->bad_symbol (and count as gaps)
+void gdca_launch_pair_pack(hipStream_t s, const int8_t *X, size_t stride, int Ns, int K, int q, uint32_t *out, gdca_dev_scalars *sc);
+// Xp (N x (KA + KB)): a (+) gaps for the KA sequences of XA (split sites each), then gaps (+) b for the KB of XB (N - split sites each)
+void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const int8_t *XB, size_t strideB, int N, int split, int KA, int KB,
+                          int q, int8_t *Xp);
+// E[a + KA * b], a0 <= a < a0 + Ac, all b, from the block rows >= split * sdim, columns < split * sdim of A (ld; sign -1: A holds -mJ);
+// T: Ac x (N - split) * sdim doubles.  EAB (KA + KB marginal energies) and c0: the energy; EAB == nullptr: the coupling R alone
+void gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N, int split,
+                            int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E, int ncu);

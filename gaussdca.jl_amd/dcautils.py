@@ -338,6 +338,57 @@ def sequence_energies(mJ, Pi, X, q: int = 21, ctx=None) -> np.ndarray:
     return E
 
 
+def _what_arg(what) -> int:
+    w = str(what).lstrip(":")
+    if w == "energy":
+        return _lib.PAIR_ENERGY
+    if w == "coupling":
+        return _lib.PAIR_COUPLING
+    raise ArgumentError(f"invalid what value: {what} (must be either energy or coupling)")
+
+
+def _symbols(X, name: str) -> np.ndarray:
+    """(sites, K) symbols -> int8, column-major; a wider type is not cast blindly (261 would wrap to the legal symbol 5)"""
+    Xa = np.asarray(X)
+    if Xa.ndim != 2:
+        raise ArgumentError(f"{name} must be a sites x K matrix")
+    if Xa.dtype != np.int8:
+        if not np.issubdtype(Xa.dtype, np.integer) or (Xa.size and (Xa.min() < 1 or Xa.max() > 31)):
+            raise ArgumentError(f"{name} must hold integer symbols between 1 and q")
+    return np.asfortranarray(Xa, dtype=np.int8)
+
+
+def pair_energies(mJ, Pi, XA, XB, q: int = 21, what="energy", ctx=None) -> np.ndarray:
+    """E[a, b] for every pairing of the K_A columns of XA (shape (split, K_A): the sites of protein A) with the K_B columns of XB
+    (shape (N - split, K_B): protein B) under the Gaussian model (mJ, Pi) of the concatenated alignment -- what partner matching
+    ranks candidate pairings by.  ``what="energy"``: the energy ``sequence_energies`` gives the concatenation a (+) b;
+    ``what="coupling"``: only its part that depends on the pairing, R[a, b] = sum of mJ[r(j), r(i)] over the non-gap sites i of a
+    and j of b (``Pi`` may then be None), with E(a (+) b) = E(a (+) gaps) + E(gaps (+) b) - c0 / 2 + R(a, b).  Returns a
+    (K_A, K_B) array.  mJ must be symmetric (its lower triangle is read)."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    w = _what_arg(what)
+    Pi = None if (Pi is None and w == _lib.PAIR_COUPLING) else np.ascontiguousarray(Pi, dtype=np.float64)
+    XAf, XBf = _symbols(XA, "XA"), _symbols(XB, "XB")
+    split, KA = XAf.shape
+    NB, KB = XBf.shape
+    N = split + NB
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = N * (int(q) - 1)
+    if split < 1 or NB < 1 or mJ.shape != (n, n) or (Pi is not None and Pi.shape != (n,)):
+        raise ArgumentError(f"incompatible sizes: XA has {split} sites and XB {NB}, q = {q}, so mJ must be {n} x {n} and Pi have {n} "
+                            f"entries (got {mJ.shape} and {None if Pi is None else Pi.shape})")
+    if KA < 1 or KB < 1:
+        raise ArgumentError("XA or XB holds no sequence")
+    ctx = ctx or default_context()
+    E = np.empty((KA, KB), dtype=np.float64, order="F")
+    ctx.check(ctx.lib.gdca_pair_energies(ctx.h, _lib._p(mJ), _lib._p(Pi) if Pi is not None else None, N, int(q), split, _lib._p(XAf), KA,
+                                         _lib._p(XBf), KB, w, _lib._p(E)))
+    return E
+
+
 def printrank(io, R: Sequence[Tuple[int, int, float]] = None):
     """printrank(io, R) / printrank(filename, R): one "%i %i %e" line per entry
     (src/GaussDCA.jl:67-74).  printrank(R) alone writes to stdout (the reference's one-argument

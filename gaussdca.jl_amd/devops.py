@@ -90,6 +90,15 @@ def sequence_energies_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, dE
     return dE
 
 
+def pair_energies_dev(ctx: Context, dmJ, dPi, N: int, q: int, split: int, dXA, KA: int, dXB, KB: int, what: int = 1, dE=None):
+    """E[a + KA * b] of the KA x KB pairings across the split with every array in HBM (gdca_pair_energies_dev): XA split x KA,
+    XB (N - split) x KB int8; what: _lib.PAIR_ENERGY or _lib.PAIR_COUPLING (dPi may then be None)"""
+    dE = dE or DeviceBuffer(ctx, 8 * KA * KB)
+    ctx.pair_energies_dev(_ptr(dmJ).value, None if dPi is None else _ptr(dPi).value, N, int(q), int(split), _ptr(dXA).value, int(KA),
+                          _ptr(dXB).value, int(KB), int(what), _ptr(dE).value)
+    return dE
+
+
 def scores_stepwise(Z, q: int, pseudocount: float = 0.8, theta=":auto", score: str = "frob", ctx: Context = None
                     ) -> Tuple[np.ndarray, dict]:
     """The six statements of src/GaussDCA.jl:28-42 one by one, arrays resident in HBM.  Z: (N, M) int8.

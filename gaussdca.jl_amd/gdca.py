@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, default_context
-from .dcautils import (FastaAlignment, Ranking, _theta_arg, read_fasta_alignment, remove_duplicate_sequences)
+from .dcautils import (FastaAlignment, Ranking, _symbols, _theta_arg, _what_arg, read_fasta_alignment, remove_duplicate_sequences)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
 last_multi_stats = None  # gDCA_multi: one stats dict per setting of its most recent call, in the order of the settings
@@ -125,6 +125,68 @@ def gDCA_energies(filename: str, sequences=None, pseudocount: float = 0.8, theta
         if X is None:
             return c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta))
         return c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), X.ctypes.data, X.shape[1])
+
+    if remove_dups:
+        Z = read_fasta_alignment(filename, max_gap_fraction)
+        Z, _ = remove_duplicate_sequences(Z)
+        Zf = np.asfortranarray(Z, dtype=np.int8)
+        E, last_stats = _run(Zf.ctypes.data, Zf.shape[0], Zf.shape[1], int(Z.max()))
+    else:
+        with FastaAlignment(filename, max_gap_fraction) as fa:
+            E, last_stats = _run(fa.ptr, fa.N, fa.M, fa.q)
+    if last_stats.get("refined", 0) < 0:
+        import warnings
+
+        warnings.warn("gDCA: the covariance is too ill-conditioned for the block sweep even with its refinement step "
+                      f"(||inv(C)||_1 = {last_stats['inverse_norm1']:.3g}; pseudocount {pseudocount}): energies are unreliable",
+                      RuntimeWarning, stacklevel=2)
+    return E
+
+
+def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what="energy", pseudocount: float = 0.8, theta=":auto",
+                       max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
+    """Energies of every pairing across a split alignment under the Gaussian model gDCA fits to ``filename``, an alignment of
+    concatenated pairs A (+) B whose first ``split`` sites are protein A (same reading, reweighting, pseudocount, covariance and
+    inverse as gDCA; same validation and messages).  Returns the (K_A, K_B) matrix E[a, b] = the energy ``gDCA_energies`` gives the
+    concatenation of sequence a of ``seqs_a`` with sequence b of ``seqs_b`` (``what="coupling"``: only the part R[a, b] that
+    depends on the pairing).  Lower = the better pairing; row-wise minima are the matches partner matching starts from.
+
+    ``seqs_a`` / ``seqs_b``: ``None`` takes that half of the alignment's own sequences (after the gap filter and the optional
+    deduplication; both None: the diagonal holds the native pairs); a ``(split, K_A)`` / ``(N - split, K_B)`` int8 array (symbols
+    1..q); or a string naming a FASTA file of that half alone, read with ``max_gap_fraction = 1.0`` so every record is kept.
+    Stats go to ``last_stats``."""
+    global last_stats
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_pair_energies() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    w = _what_arg(what)
+
+    def _half(seqs, name):
+        if isinstance(seqs, (str, bytes, os.PathLike)):
+            if not os.path.isfile(seqs):
+                raise ArgumentError(f"cannot open file {seqs}")
+            return np.asfortranarray(read_fasta_alignment(os.fspath(seqs) if not isinstance(seqs, bytes) else seqs.decode(), 1.0), dtype=np.int8)
+        return None if seqs is None else _symbols(seqs, name)
+
+    XA, XB = _half(seqs_a, "seqs_a"), _half(seqs_b, "seqs_b")
+
+    def _run(ptr, N, M, q):
+        if q >= 32:
+            raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+        if not isinstance(split, (int, np.integer)) or not 1 <= split <= N - 1:
+            raise ArgumentError(f"invalid split value: {split} (must be between 1 and N - 1 = {N - 1})")
+        if XA is not None and XA.shape[0] != split:
+            raise ArgumentError(f"seqs_a have {XA.shape[0]} sites, protein A has {split}")
+        if XB is not None and XB.shape[0] != N - split:
+            raise ArgumentError(f"seqs_b have {XB.shape[0]} sites, protein B has {N - split}")
+        if (XA is not None and XA.shape[1] < 1) or (XB is not None and XB.shape[1] < 1):
+            raise ArgumentError("seqs_a or seqs_b holds no sequence")
+        c = ctx or default_context()
+        return c.run_pair_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split),
+                                       None if XA is None else XA.ctypes.data, 0 if XA is None else XA.shape[1],
+                                       None if XB is None else XB.ctypes.data, 0 if XB is None else XB.shape[1], w)
 
     if remove_dups:
         Z = read_fasta_alignment(filename, max_gap_fraction)

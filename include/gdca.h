@@ -175,7 +175,8 @@ gdca_status gdca_ctx_set_timing(gdca_ctx *ctx, int32_t enabled);
  * members' streams, 0: one after the other), PHASED_STREAMS (how many of those streams, the first members', they are spread over: default 4), PHASED_GRIDS (the kernels of a phase batch as ONE grid per kernel kind carrying all members of a group: -1 = 1 group for small families, 4 for big ones [default], 1 .. 8 = that many groups side by side, 0 = a launch per member and kernel as PHASED_FRONTS describes); REFINE (auto | 0 | 1: one Newton-Schulz step on an inverse that looks
  * ill-conditioned / never / always) and REFINE_COND (the threshold of auto, default 1e6); CHOLESKY (0 | 1 | 2: the blocked
  * dpotrf + dpotri fallback never / where the sweep gave up [default] / for every inverse); ENERGY_CHUNK (sequences one launch of the energy gather
- * kernel takes, 0 = the rule [default]: the same bits whatever it is).  The schedule switches change results
+ * kernel takes, 0 = the rule [default]: the same bits whatever it is); PAIR_CHUNK (sequences of protein A one launch of the pair-energy
+ * kernels takes, 0 = the rule [default: a ~256 MB buffer]; a count above the rule's is cut to it: the same bits whatever it is).  The schedule switches change results
  * at rounding level at most (another summation order); REFINE improves an ill-conditioned inverse.  GDCA_EINVAL: unknown key
  * or unusable value. */
 gdca_status gdca_ctx_set_option(gdca_ctx *ctx, const char *key, const char *value);
@@ -307,6 +308,35 @@ gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double 
 gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                   const int8_t *X_dev, int32_t K, double *E_dev, gdca_stats *st);
 
+/* ---- pair energies: every pairing across a split alignment -----------------------------------------------------------------
+ * Partner matching (the paper's second use of the model) takes an alignment of concatenated pairs A (+) B and needs, per species, the
+ * energy of EVERY candidate pairing of K_A sequences of A with K_B of B.  Sites 0 .. split - 1 (0-based) are protein A, the rest
+ * protein B, 1 <= split <= N - 1.  XA is split x K_A, XB is (N - split) x K_B, both int8 column-major with symbols 1..q like Z; E has
+ * K_A K_B entries, column-major: E[a + K_A * b] (64-bit index).
+ *     what = GDCA_PAIR_ENERGY:    E[a, b] = the energy gdca_energies gives the concatenation a (+) b,
+ *     what = GDCA_PAIR_COUPLING:  R[a, b] = sum_{i in A, j in B, neither a gap} mJ[r(j), r(i)],  r(i) = i s + a_i - 1  (Pi may be NULL),
+ * joined by the exact identity (g = mJ Pi, c0 = Pi' g; a gap leaves its site's block of the one-hot vector zero)
+ *     E(a (+) b) = E(a (+) gaps) + E(gaps (+) b) - c0 / 2 + R(a, b).
+ * The two marginal terms are K_A + K_B energies of the stage above; R reads ONE rectangular block of mJ -- rows n_A .. n - 1, columns
+ * 0 .. n_A - 1, n_A = split (q - 1), inside the lower triangle -- and nothing else of it, at about N - split gathers a pairing where
+ * the K_A K_B concatenations would cost N^2 / 2 each (and K_A K_B N bytes).  mJ as for gdca_energies: symmetric, lower triangle read.
+ * Every sum is taken in a fixed order in f64 (no floating-point atomics): the bits of E[a, b] depend only on the model, a, b, split
+ * and `what` -- not on K_A, K_B, where a and b stand in their batches, option PAIR_CHUNK (at most that many sequences of A per launch; 0 = the rule) or
+ * the kernel instance.  An all-gap a or b has R = 0.0 exactly.
+ * GDCA_EINVAL: K_A or K_B < 1, split outside 1..N-1, q outside 2..31, a null pointer that is needed, an unknown `what` -- nothing is
+ * run -- or a byte of XA / XB outside 1..q (detected on the device; nothing is read out of bounds for it).  On failure E is unspecified.
+ * Synchronous. */
+enum { GDCA_PAIR_COUPLING = 0, GDCA_PAIR_ENERGY = 1 };
+gdca_status gdca_pair_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, int32_t split,
+                                   const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what, double *E_dev);
+/* Fused: fits the model on Z exactly as gdca_run_energies does (the same code, the same conditioning screen), then the pair stage on
+ * it; mJ never leaves HBM.  XA == NULL takes the A halves of Z's own sequences (K_A is then M, KA ignored); XB == NULL likewise and
+ * independently, so both NULL gives the M x M matrix whose diagonal holds the native pairs.  p->score and p->apc are ignored.  Stats
+ * as gdca_run_energies: ms_score is the pair stage, ms_fn 0. */
+gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                       int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what,
+                                       double *E_dev, gdca_stats *st);
+
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* compute_theta's all-pairs identity sum (inside compute_weighted_frequencies, :28) */
 gdca_status gdca_pair_identity_sum(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, uint64_t *out);
@@ -345,6 +375,13 @@ gdca_status gdca_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int
                           double *E);
 gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                               const int8_t *X_host, int32_t K, double *E_host, gdca_stats *st);
+
+/* pair energies with host pointers: upload, the _dev form, download */
+gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split, const int8_t *XA,
+                               int32_t KA, const int8_t *XB, int32_t KB, int32_t what, double *E);
+gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                   int32_t split, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, int32_t what,
+                                   double *E_host, gdca_stats *st);
 
 /* ---- host-side utilities around the hot path (plain C++, no GPU): the reference's callers of the path -------- */
 /* CPUs this process can really use: hardware threads capped by the cgroup CPU quota (a container may see 256 threads and be given

@@ -15,7 +15,7 @@
 module GaussDCAHip
 
 export gDCA, gDCA_stepwise, printrank, compute_weights, compute_weighted_frequencies, add_pseudocount,
-       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies
+       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, pair_energies
 
 using LinearAlgebra
 import DCAUtils                                   # host-side I/O only: read_fasta_alignment, remove_duplicate_sequences
@@ -179,6 +179,23 @@ function sequence_energies(mJ::Matrix{Float64}, Pi::Vector{Float64}, X::Matrix{I
     E = Vector{Float64}(undef, K)
     GC.@preserve mJ Pi X E check(ccall((:gdca_energies, libgdca), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int8}, Int32, Ptr{Float64}), ctx(), mJ, Pi, N, q, X, K, E))
+    return E
+end
+
+# E[a, b] for every pairing of the columns of XA (split x K_A: protein A's sites) with the columns of XB ((N - split) x K_B) under the
+# model of the concatenated alignment (include/gdca.h, "pair energies"): what = :energy, the energy sequence_energies gives a (+) b, or
+# :coupling, only the part that depends on the pairing (Pi may then be nothing)
+function pair_energies(mJ::Matrix{Float64}, Pi::Union{Vector{Float64}, Nothing}, XA::Matrix{Int8}, XB::Matrix{Int8}, q::Integer = 21;
+                       what::Symbol = :energy)
+    what in (:energy, :coupling) || throw(ArgumentError("invalid what value: $what (must be either :energy or :coupling)"))
+    split, KA = size(XA); NB, KB = size(XB); N = split + NB; n = N * (q - 1)
+    (Pi === nothing && what == :energy) && throw(ArgumentError("what = :energy needs Pi"))
+    (size(mJ) == (n, n) && (Pi === nothing || length(Pi) == n)) || throw(ArgumentError("incompatible sizes of mJ, Pi, XA, XB and q"))
+    E = Matrix{Float64}(undef, KA, KB)
+    Pp = Pi === nothing ? Ptr{Float64}(C_NULL) : pointer(Pi)
+    GC.@preserve mJ Pi XA XB E check(ccall((:gdca_pair_energies, libgdca), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ptr{Int8}, Int32, Ptr{Int8}, Int32, Int32, Ptr{Float64}),
+        ctx(), mJ, Pp, N, q, split, XA, KA, XB, KB, what == :energy ? 1 : 0, E))
     return E
 end
 
