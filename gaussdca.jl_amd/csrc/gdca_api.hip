@@ -33,6 +33,71 @@ struct gdca_gate {
     hipStream_t batch_stream;
 };
 
+// What the score stage of a run computes, handed to score_stage by whoever calls it: the contact score (FN or DI, with or without
+// APC), or -- the fused energy entries -- the model scored on sequences X, or on the pairings across a split.  The enqueued run keeps
+// its own (gdca_pending::target): a second attempt, refinement or fallback at collect time scores the same thing again.
+struct score_target {
+    enum { CONTACT, ENERGY, PAIR } kind;
+    double *out;                       // S (N x N), E (K) or E (KA x KB)
+    int score, apc;                    // contact
+    const int8_t *X;                   // energy (k_energy.hip): N x K
+    int K;
+    const int8_t *XA, *XB;             // pair (k_pair_energy.hip): as pair_stage takes them
+    size_t strideA, strideB;
+    int KA, KB, split, what;
+};
+
+static score_target contact_target(int score, int apc, double *S_dev)
+{
+    score_target t{};
+    t.kind = score_target::CONTACT;
+    t.out = S_dev;
+    t.score = score;
+    t.apc = apc;
+    return t;
+}
+
+// The enqueued, not yet collected run (gdca_run_dev_async / gdca_run_collect): all a collect needs to know, grouped by who writes it.
+// The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev, operator_inverse_retry) borrows n, n_pad, timed and
+// at.attempt, so that it can go through run_inverses.
+struct gdca_pending {
+    // ---- the front end (pending_front) ----
+    int N, M, q, n, n_pad;
+    const int8_t *Z;           // what a refinement at collect time needs to build C again
+    const double *pij;         // ... or, a pseudocount group of gdca_run_multi, the stored Pij_true C is built again from (nullptr: the tallies)
+    gdca_params p;
+    bool timed;
+    bool stamped;              // the run marked its stages with device time stamps (gdca_ctx::stamped): its collect reads the stamps
+    int front_batch;           // members that shared this run's batched front-end grids (1: grids of its own); their stage times are the grids' divided by it
+    int score_batch;           // ... and its score grids (run_phased sets both)
+    bool tally_timed;          // events 9 / 10 around k_pair_tally were recorded by this run
+    // ---- the inverse (run_inverse, run_inverse_merged) ----
+    int n_upd;
+    int batch;                 // families that shared this run's SPD-inverse launch (1: a launch of its own)
+    bool inv_stamped;          // the inverse was a merged launch bracketed by stamps (slots 6 / 16 before, 17 / 4 behind) instead of events
+    hipEvent_t upd_ev[2];      // the two events around that launch (this context's own, also for a merged launch)
+    double upd_flops;
+    // ---- the score stage (run_score) ----
+    score_target target;
+    bool fn_timed;             // events 7 / 8 around k_fn were recorded by this run
+    bool sc_published;         // the run ends with k_publish_scalars: its collect reads sc_host after a stream synchronisation
+    // ---- progress at collect time (zero when a run begins) ----
+    struct progress {
+        int attempt;           // attempts the run's inverse has had so far (0: the first is enqueued); its watchdog may end a launch (k_inverse.hip, spin_until)
+        bool rescored;         // ... and it was run again at collect time: the scores (and a ranking) are those of the last attempt
+        int refined;
+    } at;
+    // ---- a ranked run (gdca_run_ranked_async): where its ranking will be, and whether enqueueing it worked ----
+    struct {
+        bool pending;
+        long long len;
+        int sep;
+        gdca_status status;
+        int32_t *i, *j;
+        double *s;
+    } rank;
+};
+
 struct gdca_ctx {
     int device;
     gdca_gate *gate;
@@ -52,56 +117,21 @@ struct gdca_ctx {
     gdca_buf Pij;                 // gdca_run_multi: Pij_true of the alignment (n x n, ld = n), the covariance of every pseudocount is built from it
     gdca_buf sc_front;            // gdca_run_multi: the scalars as the front end left them (every pseudocount group starts from them)
     gdca_buf Xg, Epart, gpart, gvec;  // energies (k_energy.hip): the packed sequences, the per-site-block partial energies, the partials of g = mJ Pi, g and c0
-    // gdca_run_energies: the enqueued run's score stage is the energy stage (a second attempt, refinement or fallback at collect time scores X again)
-    bool pend_energy = false;
-    const int8_t *pend_X = nullptr;
-    int pend_K = 0;
-    double *pend_E = nullptr;
     // pair energies (k_pair_energy.hip): the packed symbols of the A and the B halves, the gap-padded halves and their marginal energies,
     // the folded rows T of one chunk of A sequences
     gdca_buf PXa, PXb, PXpad, PEab, PT;
-    // gdca_run_pair_energies: the enqueued run's score stage is the pair stage (run again at collect time like the energy stage)
-    bool pend_pair = false;
-    const int8_t *pend_XA = nullptr, *pend_XB = nullptr;
-    size_t pend_strideA = 0, pend_strideB = 0;
-    int pend_KA = 0, pend_KB = 0, pend_split = 0, pend_what = 0;
-    // an enqueued ranked run (gdca_run_ranked_async): where its ranking will be, and whether enqueueing it worked
-    bool rank_pending = false;
-    long long rank_len = 0;
-    int rank_sep = 0;
-    gdca_status rank_status = GDCA_OK;
-    int32_t *rank_i = nullptr, *rank_j = nullptr;
-    double *rank_s = nullptr;
     int ncu;                   // compute units of the device
     int *item0_host;           // pinned staging of the sweep's item table
     int item0_cap;
     gdca_buf scratch[N_SCRATCH];
     gdca_dev_scalars *sc_host;  // pinned
     gdca_dev_scalars *sc_host_dev;  // ... as the device addresses it (k_publish_scalars)
-    bool sc_published;          // the enqueued run ends with k_publish_scalars: its collect reads sc_host after a stream synchronisation
     hipEvent_t ev[MAX_EV];
     int n_ev;
-    // state of an enqueued, not yet collected run (gdca_run_dev_async / gdca_run_collect)
     hipEvent_t ev_batch, ev_upload;
-    bool pending;
-    bool pend_timed;
     bool stamped;              // the run being enqueued marks its stages with device time stamps (sc->stamp) instead of HIP events: a member of a batch issued as batched grids
-    bool pend_inv_stamped;     // the enqueued run's inverse was a merged launch bracketed by stamps (slots 6 / 16 before, 17 / 4 behind) instead of events
-    bool pend_stamped;         // ... and the enqueued run did so: its collect reads the stamps
-    int pend_score_batch;      // ... and of its score grids
-    int pend_front_batch;      // members that shared this run's batched front-end / score grids (1: grids of its own); their stage times are the grids' divided by it
-    bool pend_fn_timed, pend_tally_timed;  // events 7 / 8 around k_fn, 9 / 10 around k_pair_tally were recorded by this run
-    int pend_N, pend_M, pend_q, pend_n, pend_npad, pend_nupd;
-    int pend_batch;            // families that shared this run's SPD-inverse launch (1: a launch of its own)
-    const int8_t *pend_Z;      // what a refinement at collect time needs to build C again and to score again
-    const double *pend_pij;    // ... or, a pseudocount group of gdca_run_multi, the stored Pij_true C is built again from (nullptr: the tallies)
-    double *pend_S;
-    gdca_params pend_p;
-    int pend_refined;
-    int pend_attempt;          // attempts the enqueued run's inverse has had so far (0: the first is enqueued); its watchdog may end a launch (k_inverse.hip, spin_until)
-    bool pend_rescored;        // ... and it was run again at collect time: the scores (and a ranking) are those of the last attempt
-    hipEvent_t pend_upd_ev[2]; // the two events around that launch (this context's own, also for a merged launch)
-    double pend_upd_flops;
+    bool pending;              // a run is enqueued and not yet collected ...
+    gdca_pending pend;         // ... this one
 };
 
 // ---- batched grids: the recorder of gdca_launch.h, and the two stream operations of this file in recordable form ------------------
@@ -588,6 +618,32 @@ static gdca_status mark(gdca_ctx *ctx, int slot)
     return GDCA_OK;
 }
 
+// device time between two stage boundaries of the enqueued run: HIP events of this context, or -- a run whose kernels went out as
+// batched grids -- the 100 MHz time stamps kernels of the batch wrote into its scalars (slot = the event's index)
+static double between(const gdca_ctx *ctx, int a, int b, bool *failed)
+{
+    if (ctx->pend.stamped) return (double)(long long)(ctx->sc_host->stamp[b] - ctx->sc_host->stamp[a]) * 1e-5;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->ev[a], ctx->ev[b]) != hipSuccess) *failed = true;
+    return ms;
+}
+
+// a pipeline's gate: the stream waits for the inverse that went through it last; the inverse just enqueued becomes that one
+static hipError_t gate_wait(const gdca_gate *g, hipStream_t s)
+{
+    return g->armed ? hipStreamWaitEvent(s, g->ev[g->last], 0) : hipSuccess;
+}
+
+static hipError_t gate_pass(gdca_gate *g, hipStream_t s)
+{
+    const hipError_t e = hipEventRecord(g->ev[g->next], s);
+    if (e != hipSuccess) return e;
+    g->last = g->next;
+    g->next = (g->next + 1) & 3;
+    g->armed = 1;
+    return hipSuccess;
+}
+
 // a member's failure as the LEADER's last error (the caller of a batch entry reads the leader's)
 static gdca_status member_error(gdca_ctx *lead, gdca_ctx *m, int k, gdca_status st)
 {
@@ -759,7 +815,7 @@ static gdca_status inverse_job(gdca_ctx *ctx, int n, int n_pad, gdca_inverse_job
     job->n_real = n;
     job->sc = (gdca_dev_scalars *)ctx->sc.p;
     job->tune = &ctx->tune;
-    job->doomed = (ctx->tune.sweep_debug & 32) != 0 && ctx->pend_attempt == 0;
+    job->doomed = (ctx->tune.sweep_debug & 32) != 0 && ctx->pend.at.attempt == 0;
     return GDCA_OK;
 }
 
@@ -850,17 +906,17 @@ static gdca_status pair_stage(gdca_ctx *ctx, const double *A, size_t ld, double 
     return check_launch(ctx, "pair energies");
 }
 
-static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, int score, int apc, double *S_dev, bool time_fn = false)
+// -mJ in ctx->A (ld = n_pad) -> what `t` asks for
+static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t, bool time_fn = false)
 {
     hipStream_t s = ctx->stream;
-    if (ctx->pend_pair)  // gdca_run_pair_energies: the model is scored on the pairings across the split
-        return pair_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, ctx->pend_split,
-                          ctx->pend_XA, ctx->pend_strideA, ctx->pend_KA, ctx->pend_XB, ctx->pend_strideB, ctx->pend_KB, ctx->pend_what,
-                          ctx->pend_E);
-    if (ctx->pend_energy)  // gdca_run_energies: the model is scored on X instead of being turned into a contact score
-        return energy_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, ctx->pend_X, ctx->pend_K,
-                            ctx->pend_E);
-    if (score == GDCA_SCORE_DI) {
+    if (t.kind == score_target::PAIR)  // gdca_run_pair_energies: the model is scored on the pairings across the split
+        return pair_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, t.split, t.XA, t.strideA,
+                          t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
+    if (t.kind == score_target::ENERGY)  // gdca_run_energies: the model is scored on X instead of being turned into a contact score
+        return energy_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, t.X, t.K, t.out);
+    double *S_dev = t.out;
+    if (t.score == GDCA_SCORE_DI) {
         CHK(ensure(ctx, ctx->Tws, gdca_di_ws_bytes(N, sdim)));
         gdca_launch_di(s, (const double *)ctx->A.p, (size_t)n_pad, (const double *)ctx->Ld.p, N, sdim, S_dev,
                        (double *)ctx->Tws.p, (gdca_dev_scalars *)ctx->sc.p);
@@ -869,9 +925,9 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, int sc
         if (tm) CHK(mark(ctx, 7));
         gdca_launch_fn(s, (const double *)ctx->A.p, (size_t)n_pad, N, sdim, S_dev, ctx->ncu);
         if (tm) CHK(mark(ctx, 8));
-        if (time_fn) ctx->pend_fn_timed = tm;
+        if (time_fn) ctx->pend.fn_timed = tm;
     }
-    if (apc) {
+    if (t.apc) {
         CHK(ensure(ctx, ctx->colsum, (size_t)N * sizeof(double)));
         gdca_launch_apc(s, S_dev, N, (double *)ctx->colsum.p);
     }
@@ -983,9 +1039,27 @@ static gdca_status cov_from_pij_stage(gdca_ctx *ctx, int N, int M, int q, double
 static gdca_status rebuild_covariance(gdca_ctx *ctx, double *dst)
 {
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    const int N = ctx->pend_N, M = ctx->pend_M, q = ctx->pend_q;
-    if (ctx->pend_pij) return cov_from_pij_stage(ctx, N, M, q, ctx->pend_p.pseudocount, dst, (size_t)ctx->pend_npad, false);
-    return tally_stage(ctx, ctx->pend_Z, N, M, q, &sc->Meff, ctx->pend_p.pseudocount, 1, nullptr, dst, (size_t)ctx->pend_npad);
+    const int N = ctx->pend.N, M = ctx->pend.M, q = ctx->pend.q;
+    if (ctx->pend.pij) return cov_from_pij_stage(ctx, N, M, q, ctx->pend.p.pseudocount, dst, (size_t)ctx->pend.n_pad, false);
+    return tally_stage(ctx, ctx->pend.Z, N, M, q, &sc->Meff, ctx->pend.p.pseudocount, 1, nullptr, dst, (size_t)ctx->pend.n_pad);
+}
+
+// ... with its identity padding: what every recovery branch of the collect starts from
+static gdca_status rebuild_padded(gdca_ctx *ctx, void *dst)
+{
+    CHK(rebuild_covariance(ctx, (double *)dst));
+    gdca_launch_pad_identity(ctx->stream, (double *)dst, ctx->pend.n, ctx->pend.n_pad);
+    return GDCA_OK;
+}
+
+// ... and ends with: the enqueued run's score stage again on the inverse now in ctx->A, the scalars fetched.  mark_end: a second
+// attempt of a timed run records the run's last event again
+static gdca_status rescore(gdca_ctx *ctx, bool mark_end = false)
+{
+    HIPCHK(hipMemsetAsync(&((gdca_dev_scalars *)ctx->sc.p)->di_noconv, 0, sizeof(int), ctx->stream));
+    CHK(score_stage(ctx, ctx->pend.N, ctx->pend.q - 1, ctx->pend.n_pad, ctx->pend.target));
+    if (mark_end && ctx->pend.timed && !ctx->pend.stamped) CHK(mark(ctx, 5));
+    return fetch_scalars(ctx);
 }
 
 static gdca_status begin(gdca_ctx *ctx)
@@ -994,14 +1068,12 @@ static gdca_status begin(gdca_ctx *ctx)
     HIPCHK(hipSetDevice(ctx->device));
     CHK(ensure(ctx, ctx->sc, sizeof(gdca_dev_scalars)));
     gdca_fill_async(ctx->stream, ctx->sc.p, 0, sizeof(gdca_dev_scalars));
-    ctx->pend_attempt = 0;
-    ctx->pend_rescored = false;
-    ctx->pend_energy = false;
-    ctx->pend_pair = false;
+    ctx->pend.at = gdca_pending::progress{};
     return GDCA_OK;
 }
 
 static gdca_status run_inverse(gdca_ctx *ctx);
+static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st);
 
 extern "C" {
 
@@ -1011,35 +1083,31 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
     if (!ctx->pending) return fail(ctx, GDCA_EINVAL, "no enqueued run to collect%s%s", "", "");
     HIPCHK(hipSetDevice(ctx->device));
     ctx->pending = false;
-    ctx->rank_pending = false;  // (collected through this entry, a ranked run's ranking is given up: its arrays are scratch of the next run)
-    if (ctx->sc_published) {
+    ctx->pend.rank.pending = false;  // (collected through this entry, a ranked run's ranking is given up: its arrays are scratch of the next run)
+    if (ctx->pend.sc_published) {
         // the run's last kernel wrote the scalars to sc_host: no copy of the runtime's -- a kernel -- behind another context's sweep
-        ctx->sc_published = false;
+        ctx->pend.sc_published = false;
         HIPCHK(hipStreamSynchronize(ctx->stream));
     } else {
         CHK(fetch_scalars(ctx));
     }
-    while (ctx->sc_host->info == INT32_MIN && !ctx->sc_host->bad_symbol && ctx->pend_attempt < ctx->tune.sweep_retries) {
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    const int n_pad = ctx->pend.n_pad, n = ctx->pend.n;
+    while (ctx->sc_host->info == INT32_MIN && !ctx->sc_host->bad_symbol && ctx->pend.at.attempt < ctx->tune.sweep_retries) {
         // The sweep's watchdog ended the launch (k_inverse.hip, spin_until: in practice a launch that did not get all its workgroups
         // back after the driver had taken the device's queues off the hardware).  Nothing is wrong with the matrix: the covariance
         // once more from the tallies -- the sweep works in place --, the inverse again as a launch of its own behind the pipeline's
         // gate, the scores again.  A launch that fails option SWEEP_RETRIES times in a row (default 2) is reported as GDCA_EHIP.
-        gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-        const int N = ctx->pend_N, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
-        ++ctx->pend_attempt;
-        CHK(rebuild_covariance(ctx, (double *)ctx->A.p));
-        gdca_launch_pad_identity(ctx->stream, (double *)ctx->A.p, n, n_pad);
+        ++ctx->pend.at.attempt;
+        CHK(rebuild_padded(ctx, ctx->A.p));
         HIPCHK(hipMemsetAsync(&sc->info, 0, sizeof(int), ctx->stream));
-        HIPCHK(hipMemsetAsync(&sc->di_noconv, 0, sizeof(int), ctx->stream));
         CHK(run_inverse(ctx));
-        CHK(score_stage(ctx, N, q - 1, n_pad, ctx->pend_p.score, ctx->pend_p.apc, ctx->pend_S));
-        if (ctx->pend_timed && !ctx->pend_stamped) CHK(mark(ctx, 5));
-        CHK(fetch_scalars(ctx));
-        ctx->pend_rescored = true;
+        CHK(rescore(ctx, true));
+        ctx->pend.at.rescored = true;
     }
     if (ctx->tune.refine != 0 && ctx->sc_host->info == 0 && !ctx->sc_host->bad_symbol &&
-        (ctx->tune.refine == 1 || cond_bound(*ctx->sc_host, ctx->pend_p.pseudocount, ctx->pend_q, ctx->pend_N) > ctx->tune.refine_cond)) {
-        CHK(inverse_norm_stage(ctx, ctx->pend_n, ctx->pend_npad));   // cond(C) may be beyond the threshold: ||X||_1 itself
+        (ctx->tune.refine == 1 || cond_bound(*ctx->sc_host, ctx->pend.p.pseudocount, ctx->pend.q, ctx->pend.N) > ctx->tune.refine_cond)) {
+        CHK(inverse_norm_stage(ctx, ctx->pend.n, ctx->pend.n_pad));   // cond(C) may be beyond the threshold: ||X||_1 itself
         CHK(fetch_scalars(ctx));
     }
     if (wants_refinement(ctx, *ctx->sc_host) && !ctx->sc_host->bad_symbol) {
@@ -1047,99 +1115,32 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
         // one Newton-Schulz step against the covariance -- built again from the tallies: the sweep worked in place -- and the
         // scores are computed again from the refined inverse.  Synchronous and several times the cost of the run itself: a path
         // for rare inputs (pseudocounts far below the 0.2 .. 0.8 gDCA is used with), taken here so that the enqueue side stays lean.
-        gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-        const int N = ctx->pend_N, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
         const size_t mat = (size_t)n_pad * n_pad * sizeof(double);
         CHK(ensure(ctx, ctx->C2, mat));
         CHK(ensure(ctx, ctx->B0, mat));
         CHK(ensure(ctx, ctx->Rt, mat));
-        CHK(rebuild_covariance(ctx, (double *)ctx->C2.p));
-        gdca_launch_pad_identity(ctx->stream, (double *)ctx->C2.p, n, n_pad);
+        CHK(rebuild_padded(ctx, ctx->C2.p));
         gdca_launch_newton_schulz(ctx->stream, (double *)ctx->A.p, (const double *)ctx->C2.p, (double *)ctx->B0.p, (double *)ctx->Rt.p, n_pad,
                                   &sc->ns_resid);
         CHK(check_launch(ctx, "newton_schulz"));
-        HIPCHK(hipMemsetAsync(&sc->di_noconv, 0, sizeof(int), ctx->stream));
-        CHK(score_stage(ctx, N, q - 1, n_pad, ctx->pend_p.score, ctx->pend_p.apc, ctx->pend_S));
-        CHK(fetch_scalars(ctx));
+        CHK(rescore(ctx));
         // the step squares I - X0 C: with that residual at one or beyond (cond(C) past ~1e10: the sweep's own error is of order one
         // there) it cannot have converged, and the caller is told so instead of being handed the result as if it were refined
-        ctx->pend_refined = ctx->sc_host->ns_resid < 1.0 ? 1 : -1;
+        ctx->pend.at.refined = ctx->sc_host->ns_resid < 1.0 ? 1 : -1;
     }
-    if (wants_cholesky(ctx, *ctx->sc_host, ctx->pend_refined)) {
+    if (wants_cholesky(ctx, *ctx->sc_host, ctx->pend.at.refined)) {
         // the sweep gave up on this covariance (a non-positive pivot, or a refinement that cannot converge): once more the
         // reference's way -- the covariance from the tallies again, blocked dpotrf + dpotri, the scores from that inverse.  Its
         // verdict on positive definiteness is LAPACK's.
-        gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-        const int N = ctx->pend_N, q = ctx->pend_q, n_pad = ctx->pend_npad, n = ctx->pend_n;
         CHK(ensure(ctx, ctx->C2, (size_t)n_pad * n_pad * sizeof(double)));
-        CHK(rebuild_covariance(ctx, (double *)ctx->C2.p));
-        gdca_launch_pad_identity(ctx->stream, (double *)ctx->C2.p, n, n_pad);
+        CHK(rebuild_padded(ctx, ctx->C2.p));
         CHK(cholesky_stage(ctx, n, n_pad));
         CHK(inverse_norm_stage(ctx, n, n_pad));
-        HIPCHK(hipMemsetAsync(&sc->di_noconv, 0, sizeof(int), ctx->stream));
-        CHK(score_stage(ctx, N, q - 1, n_pad, ctx->pend_p.score, ctx->pend_p.apc, ctx->pend_S));
-        CHK(fetch_scalars(ctx));
-        ctx->pend_refined = 2;
+        CHK(rescore(ctx));
+        ctx->pend.at.refined = 2;
     }
+    if (st) CHK(fill_stats(ctx, st));
     const gdca_dev_scalars &h = *ctx->sc_host;
-    hipEvent_t *ev = ctx->ev;
-    if (st) {
-        memset(st, 0, sizeof(*st));
-        st->theta = h.theta;
-        st->Meff = h.Meff;
-        st->pair_identity_sum = h.pair_sum;
-        st->thresh = h.thresh;
-        st->info = h.info;
-        st->N = ctx->pend_N;
-        st->M = ctx->pend_M;
-        st->q = ctx->pend_q;
-        st->n = ctx->pend_n;
-        st->n_pad = ctx->pend_npad;
-        st->update_launches = ctx->pend_nupd;
-        st->inverse_batch = ctx->pend_batch;
-        st->refined = ctx->pend_refined;
-        st->sweep_retries = ctx->pend_attempt;
-        st->inverse_norm1 = h.inv_norm1;
-        st->matrix_norm1 = h.mat_norm1;
-        st->cond_bound = ctx->tune.refine != 0 ? cond_bound(h, ctx->pend_p.pseudocount, ctx->pend_q, ctx->pend_N) : 0.0;
-        st->inverse_flops = inverse_flops_model((double)ctx->pend_n);
-        st->update_flops = ctx->pend_upd_flops;
-        st->sweep_ghz = h.sweep_ticks ? (double)h.sweep_cycles / (double)h.sweep_ticks * 0.1 : 0.0;
-        if (ctx->pend_timed) {
-            // device time between two stage boundaries: HIP events of this context, or -- a run whose kernels went out as batched grids --
-            // the 100 MHz time stamps kernels of the batch wrote into its scalars (slot = the event's index)
-            bool tfail = false;
-            auto between = [&](int a, int b) -> double {
-                if (ctx->pend_stamped) return (double)(long long)(h.stamp[b] - h.stamp[a]) * 1e-5;
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) tfail = true;
-                return ms;
-            };
-            // (stages issued as batched grids carry the whole batch: a member reports its share, as for a merged inverse)
-            const double fshare = 1.0 / (double)(ctx->pend_front_batch > 0 ? ctx->pend_front_batch : 1);
-            st->ms_total = between(0, 5);
-            st->ms_theta = between(0, 1) * fshare;
-            st->ms_weights = between(1, 2) * fshare;
-            st->ms_covariance = between(2, 3) * fshare;
-            // (a family whose inverse shared a merged launch with others reports its share of that launch: the launch's time
-            // divided by the families it carried -- the sum over the members is the launch)
-            const double share = 1.0 / (double)(ctx->pend_batch > 0 ? ctx->pend_batch : 1);
-            st->ms_score = between(11, 5) / (double)(ctx->pend_score_batch > 0 ? ctx->pend_score_batch : 1);
-            if (ctx->pend_inv_stamped) {
-                st->ms_inverse = (double)(long long)(h.stamp[4] - h.stamp[6]) * 1e-5 * share;
-                st->ms_inverse_update = (double)(long long)(h.stamp[17] - h.stamp[16]) * 1e-5 * share;
-            } else {
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, ev[6], ev[4]));  // from the start of its turn (after any pipeline gate)
-                st->ms_inverse = ms * share;
-                HIPCHK(hipEventElapsedTime(&ms, ctx->pend_upd_ev[0], ctx->pend_upd_ev[1]));
-                st->ms_inverse_update = ms * share;
-            }
-            if (ctx->pend_fn_timed && ctx->pend_refined == 0) st->ms_fn = between(7, 8) / (double)(ctx->pend_score_batch > 0 ? ctx->pend_score_batch : 1);
-            if (ctx->pend_tally_timed && ctx->pend_refined == 0) st->ms_pair_tally = between(9, 10) * fshare;
-            if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
-        }
-    }
     if (h.bad_symbol & 4) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
     if (h.bad_symbol) return fail(ctx, GDCA_EINVAL, "alignment holds a symbol outside 1..q%s%s", "", "");
     if (h.info == INT32_MIN)  // the sweep kernel's watchdog (k_inverse.hip, spin_until): a dependency wait ran out of time
@@ -1154,19 +1155,99 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
 
 }  // extern "C"
 
+// gdca_stats of the run just collected: the scalars in sc_host, the pending record and, for a timed run, its stage times
+static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st)
+{
+    const gdca_dev_scalars &h = *ctx->sc_host;
+    memset(st, 0, sizeof(*st));
+    st->theta = h.theta;
+    st->Meff = h.Meff;
+    st->pair_identity_sum = h.pair_sum;
+    st->thresh = h.thresh;
+    st->info = h.info;
+    st->N = ctx->pend.N;
+    st->M = ctx->pend.M;
+    st->q = ctx->pend.q;
+    st->n = ctx->pend.n;
+    st->n_pad = ctx->pend.n_pad;
+    st->update_launches = ctx->pend.n_upd;
+    st->inverse_batch = ctx->pend.batch;
+    st->refined = ctx->pend.at.refined;
+    st->sweep_retries = ctx->pend.at.attempt;
+    st->inverse_norm1 = h.inv_norm1;
+    st->matrix_norm1 = h.mat_norm1;
+    st->cond_bound = ctx->tune.refine != 0 ? cond_bound(h, ctx->pend.p.pseudocount, ctx->pend.q, ctx->pend.N) : 0.0;
+    st->inverse_flops = inverse_flops_model((double)ctx->pend.n);
+    st->update_flops = ctx->pend.upd_flops;
+    st->sweep_ghz = h.sweep_ticks ? (double)h.sweep_cycles / (double)h.sweep_ticks * 0.1 : 0.0;
+    if (!ctx->pend.timed) return GDCA_OK;
+    bool tfail = false;
+    // (stages issued as batched grids carry the whole batch: a member reports its share, as for a merged inverse)
+    const double fshare = 1.0 / (double)(ctx->pend.front_batch > 0 ? ctx->pend.front_batch : 1);
+    const double sbatch = (double)(ctx->pend.score_batch > 0 ? ctx->pend.score_batch : 1);
+    st->ms_total = between(ctx, 0, 5, &tfail);
+    st->ms_theta = between(ctx, 0, 1, &tfail) * fshare;
+    st->ms_weights = between(ctx, 1, 2, &tfail) * fshare;
+    st->ms_covariance = between(ctx, 2, 3, &tfail) * fshare;
+    // (a family whose inverse shared a merged launch with others reports its share of that launch: the launch's time
+    // divided by the families it carried -- the sum over the members is the launch)
+    const double share = 1.0 / (double)(ctx->pend.batch > 0 ? ctx->pend.batch : 1);
+    st->ms_score = between(ctx, 11, 5, &tfail) / sbatch;
+    if (ctx->pend.inv_stamped) {
+        st->ms_inverse = (double)(long long)(h.stamp[4] - h.stamp[6]) * 1e-5 * share;
+        st->ms_inverse_update = (double)(long long)(h.stamp[17] - h.stamp[16]) * 1e-5 * share;
+    } else {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[4]));  // from the start of its turn (after any pipeline gate)
+        st->ms_inverse = ms * share;
+        HIPCHK(hipEventElapsedTime(&ms, ctx->pend.upd_ev[0], ctx->pend.upd_ev[1]));
+        st->ms_inverse_update = ms * share;
+    }
+    if (ctx->pend.fn_timed && ctx->pend.at.refined == 0) st->ms_fn = between(ctx, 7, 8, &tfail) / sbatch;
+    if (ctx->pend.tally_timed && ctx->pend.at.refined == 0) st->ms_pair_tally = between(ctx, 9, 10, &tfail) * fshare;
+    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
+    return GDCA_OK;
+}
+
 // The three phases of one run, enqueued on `s` (the ctx's own stream, or the leader's when several families are batched by
 // phase): front end (theta, reweighting, tallies, covariance), SPD inverse, scores.
+static gdca_status check_params(gdca_ctx *ctx, const gdca_params *p)
+{
+    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0))
+        return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)%s%s", "", "");
+    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value%s%s", "", "");
+    return GDCA_OK;
+}
+
 static gdca_status run_check_args(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                   double *S_dev)
 {
     CHK(validate(ctx, N, M, q));
     if (!Z_dev || !S_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0))
-        return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)%s%s", "", "");
-    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value%s%s", "", "");
+    CHK(check_params(ctx, p));
     if (p->score != GDCA_SCORE_FROB && p->score != GDCA_SCORE_DI)
         return fail(ctx, GDCA_EINVAL, "invalid score value%s%s", "", "");
     return GDCA_OK;
+}
+
+// the front-end part of the pending record.  pij: the stored Pij_true of gdca_run_multi (whose tallies are not the fused build:
+// no time of their own), nullptr for a single run
+static void pending_front(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int q, const gdca_params *p, const double *pij, bool timed)
+{
+    gdca_pending &r = ctx->pend;
+    r.N = N;
+    r.M = M;
+    r.q = q;
+    r.n = N * (q - 1);
+    r.n_pad = round_up(r.n, GDCA_TILE);
+    r.Z = Z_dev;
+    r.pij = pij;
+    r.p = *p;
+    r.timed = timed;
+    r.stamped = ctx->stamped;
+    r.front_batch = r.score_batch = 1;  // (run_phased knows better)
+    r.tally_timed = timed && !pij && ctx->tune.refine != 0;
+    r.fn_timed = false;
 }
 
 static gdca_status run_front(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p)
@@ -1193,49 +1274,29 @@ static gdca_status run_front(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int3
     }
     CHK(check_launch(ctx, "covariance"));
     if (timed) CHK(mark(ctx, 3));
-    ctx->pend_timed = timed;
-    ctx->pend_stamped = ctx->stamped;
-    ctx->pend_front_batch = 1;
-    ctx->pend_score_batch = 1;
-    ctx->pend_tally_timed = timed && ctx->tune.refine != 0;
-    ctx->pend_fn_timed = false;
-    ctx->pend_Z = Z_dev;
-    ctx->pend_pij = nullptr;
-    ctx->pend_p = *p;
-    ctx->pend_refined = 0;
-    ctx->pend_N = N;
-    ctx->pend_M = M;
-    ctx->pend_q = q;
-    ctx->pend_n = n;
-    ctx->pend_npad = n_pad;
+    pending_front(ctx, Z_dev, N, M, q, p, nullptr, timed);
     return GDCA_OK;
 }
 
 static gdca_status run_inverse(gdca_ctx *ctx)
 {
     hipStream_t s = ctx->stream;
-    const bool timed = ctx->pend_timed;
+    const bool timed = ctx->pend.timed;
     hipEvent_t *ev = ctx->ev;
     int n_upd = 0;
     double upd_flops = 0.0;
-    if (ctx->gate && ctx->gate->armed) HIPCHK(hipStreamWaitEvent(s, ctx->gate->ev[ctx->gate->last], 0));
+    if (ctx->gate) HIPCHK(gate_wait(ctx->gate, s));
     if (timed) HIPCHK(hipEventRecord(ev[6], s));  // start of this family's turn on the MFMA pipe
-    CHK(inverse_stage(ctx, ctx->pend_n, ctx->pend_npad, timed, &n_upd, &upd_flops));
+    CHK(inverse_stage(ctx, ctx->pend.n, ctx->pend.n_pad, timed, &n_upd, &upd_flops));
     if (timed) HIPCHK(hipEventRecord(ev[4], s));
-    if (ctx->gate) {
-        gdca_gate *g = ctx->gate;
-        HIPCHK(hipEventRecord(g->ev[g->next], s));
-        g->last = g->next;
-        g->next = (g->next + 1) & 3;
-        g->armed = 1;
-    }
-    ctx->pend_nupd = n_upd;
-    ctx->pend_upd_flops = upd_flops;
-    ctx->pend_batch = 1;
-    ctx->pend_inv_stamped = false;
+    if (ctx->gate) HIPCHK(gate_pass(ctx->gate, s));
+    ctx->pend.n_upd = n_upd;
+    ctx->pend.upd_flops = upd_flops;
+    ctx->pend.batch = 1;
+    ctx->pend.inv_stamped = false;
     if (timed) {
-        ctx->pend_upd_ev[0] = ev[16];
-        ctx->pend_upd_ev[1] = ev[17];
+        ctx->pend.upd_ev[0] = ev[16];
+        ctx->pend.upd_ev[1] = ev[17];
     }
     return GDCA_OK;
 }
@@ -1271,20 +1332,20 @@ static gdca_status run_inverse_merged(gdca_ctx *lead, gdca_ctx *const *mem, int 
     gdca_gate *gates[8];
     int n_gates = 0;
     for (int k = 0; k < K; ++k) {
-        timed = timed && mem[k]->pend_timed;
-        stamped = stamped && mem[k]->pend_stamped;
+        timed = timed && mem[k]->pend.timed;
+        stamped = stamped && mem[k]->pend.stamped;
         gdca_gate *g = mem[k]->gate;
         bool seen = !g;
         for (int j = 0; j < n_gates && !seen; ++j) seen = gates[j] == g;
         if (!seen) {
             gates[n_gates++] = g;
-            if (g->armed) HIPCHK(hipStreamWaitEvent(s, g->ev[g->last], 0));
+            HIPCHK(gate_wait(g, s));
         }
     }
     stamped = stamped && timed;
     for (int k = 0; k < K; ++k) {
-        if (mem[k]->pend_timed && !stamped) HIPCHK(hipEventRecord(mem[k]->ev[6], s));
-        CHK(inverse_job(mem[k], mem[k]->pend_n, mem[k]->pend_npad, &jobs[k]));
+        if (mem[k]->pend.timed && !stamped) HIPCHK(hipEventRecord(mem[k]->ev[6], s));
+        CHK(inverse_job(mem[k], mem[k]->pend.n, mem[k]->pend.n_pad, &jobs[k]));
         tun[k] = mem[k]->tune;
         tun[k].merge_group = lead->tune.merge_group;
         tun[k].merge_mcus = lead->tune.merge_mcus;
@@ -1307,49 +1368,43 @@ static gdca_status run_inverse_merged(gdca_ctx *lead, gdca_ctx *const *mem, int 
         stamp_members(s, mem, K, 17, 4);
     else if (timed)
         for (int k = 0; k < K; ++k) HIPCHK(hipEventRecord(mem[k]->ev[17], s));
-    for (int j = 0; j < n_gates; ++j) {
-        gdca_gate *g = gates[j];
-        HIPCHK(hipEventRecord(g->ev[g->next], s));
-        g->last = g->next;
-        g->next = (g->next + 1) & 3;
-        g->armed = 1;
-    }
+    for (int j = 0; j < n_gates; ++j) HIPCHK(gate_pass(gates[j], s));
     for (int k = 0; k < K; ++k) {
         gdca_ctx *m = mem[k];
-        if (m->pend_timed && !stamped) HIPCHK(hipEventRecord(m->ev[4], s));
-        m->pend_nupd = k == 0 ? 1 : 0;
-        m->pend_upd_flops = flops[k];
-        m->pend_batch = K;
+        if (m->pend.timed && !stamped) HIPCHK(hipEventRecord(m->ev[4], s));
+        m->pend.n_upd = k == 0 ? 1 : 0;
+        m->pend.upd_flops = flops[k];
+        m->pend.batch = K;
         // (a member without timing of its own still gets valid events to read: the launch's, or none -- collect reads them only if timed)
-        m->pend_timed = m->pend_timed && timed;
-        m->pend_inv_stamped = stamped;
+        m->pend.timed = m->pend.timed && timed;
+        m->pend.inv_stamped = stamped;
         if (timed && !stamped) {
-            m->pend_upd_ev[0] = m->ev[16];
-            m->pend_upd_ev[1] = m->ev[17];
+            m->pend.upd_ev[0] = m->ev[16];
+            m->pend.upd_ev[1] = m->ev[17];
         }
     }
     return GDCA_OK;
 }
 
-static gdca_status run_score(gdca_ctx *ctx, const gdca_params *p, double *S_dev)
+static gdca_status run_score(gdca_ctx *ctx, const score_target &t)
 {
-    ctx->pend_S = S_dev;
+    ctx->pend.target = t;
     // (the start of THIS run's score stage: in a phase batch the members' stages follow one another behind the shared inverse)
-    if (ctx->pend_timed) CHK(mark(ctx, 11));
-    CHK(score_stage(ctx, ctx->pend_N, ctx->pend_q - 1, ctx->pend_npad, p->score, p->apc, S_dev, ctx->pend_timed));
-    if (ctx->pend_timed) CHK(mark(ctx, 5));
-    ctx->sc_published = false;
+    if (ctx->pend.timed) CHK(mark(ctx, 11));
+    CHK(score_stage(ctx, ctx->pend.N, ctx->pend.q - 1, ctx->pend.n_pad, t, ctx->pend.timed));
+    if (ctx->pend.timed) CHK(mark(ctx, 5));
+    ctx->pend.sc_published = false;
     if (ctx->sc_host_dev) {
         gdca_launch_publish_scalars(ctx->stream, (const gdca_dev_scalars *)ctx->sc.p, ctx->sc_host_dev);
         CHK(check_launch(ctx, "publish_scalars"));
-        ctx->sc_published = true;
+        ctx->pend.sc_published = true;
     }
     ctx->pending = true;
     return GDCA_OK;
 }
 
-// The inverses of the members of a batch, all enqueued on the batch's stream (every member's `stream` points there, pend_n /
-// pend_npad are set): those of the small members (up to `merge_blocks` 128-blocks: chain-bound single-block schedules that leave
+// The inverses of the members of a batch, all enqueued on the batch's stream (every member's `stream` points there, pend.n /
+// pend.n_pad are set): those of the small members (up to `merge_blocks` 128-blocks: chain-bound single-block schedules that leave
 // most of the chip idle) are carried `merge` at a time by ONE launch (options GDCA_MERGE, GDCA_MERGE_BLOCKS of the leader; bit for
 // bit the results of launches of their own), the others run back to back
 static gdca_status run_inverses(gdca_ctx *lead, gdca_ctx *const *ctxs, int K)
@@ -1359,7 +1414,7 @@ static gdca_status run_inverses(gdca_ctx *lead, gdca_ctx *const *ctxs, int K)
     gdca_status st = GDCA_OK;
     const int merge = std::min(lead->tune.merge, gdca_inverse_max_merge());
     for (int k = 0; k < K && st == GDCA_OK; ++k) {
-        if (merge > 1 && ctxs[k]->pend_npad / GDCA_TILE <= lead->tune.merge_blocks)
+        if (merge > 1 && ctxs[k]->pend.n_pad / GDCA_TILE <= lead->tune.merge_blocks)
             small[n_small++] = ctxs[k];
         else
             st = run_inverse(ctxs[k]);
@@ -1374,7 +1429,7 @@ static gdca_status run_inverses(gdca_ctx *lead, gdca_ctx *const *ctxs, int K)
         int cnt = 0;
         for (int k = 0; k < n_small; ++k) {
             if (cnt == 0) start[n_grp++] = k;
-            const long long nb = small[k]->pend_npad / GDCA_TILE;
+            const long long nb = small[k]->pend.n_pad / GDCA_TILE;
             tiles += nb * nb / 2;
             ++cnt;
             if (cnt == merge || tiles >= lead->tune.merge_tiles) {
@@ -1401,10 +1456,20 @@ gdca_status gdca_run_dev_async(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, in
     CHK(run_check_args(ctx, Z_dev, N, M, q, p, S_dev));
     CHK(run_front(ctx, Z_dev, N, M, q, p));
     CHK(run_inverse(ctx));
-    return run_score(ctx, p, S_dev);
+    return run_score(ctx, contact_target(p->score, p->apc, S_dev));
 }
 
 static gdca_status ranking_stage(gdca_ctx *ctx, const double *S_dev, int N, int sep, long long len, int32_t **ii, int32_t **jj, double **sc);
+
+// the ranking of an enqueued run behind its scores, before anybody waits: one synchronisation for the whole run
+static void enqueue_ranking(gdca_ctx *ctx, const double *S_dev, int N, int sep)
+{
+    auto &r = ctx->pend.rank;
+    r.len = gdca_ranking_length(N, sep);
+    r.sep = sep;
+    r.status = r.len > 0 ? ranking_stage(ctx, S_dev, N, sep, r.len, &r.i, &r.j, &r.s) : GDCA_OK;
+    r.pending = true;
+}
 
 static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *const *Z_dev, const int32_t *N, const int32_t *M, const int32_t *q,
                               const gdca_params *p, double *const *S_dev, int rank_sep, bool *ranked)
@@ -1420,14 +1485,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         if (ctxs[k]->device != lead->device) return fail(lead, GDCA_EINVAL, "contexts of one batch must share a device%s%s", "", "");
         gdca_status vs = not_pending(ctxs[k]);
         if (vs == GDCA_OK) vs = run_check_args(ctxs[k], Z_dev[k], N[k], M[k], q[k], p, S_dev[k]);
-        if (vs != GDCA_OK) {
-            if (k > 0) {  // the caller reads the leader's last_error
-                char msg[sizeof(lead->err)];
-                snprintf(msg, sizeof(msg), "member %d: %.400s", k, ctxs[k]->err);
-                memcpy(lead->err, msg, sizeof(msg));
-            }
-            return vs;
-        }
+        if (vs != GDCA_OK) return member_error(lead, ctxs[k], k, vs);
     }
     // Phase by phase: K front ends, K inverses back to back, K score stages.  The inverses and the score stages go to the leader's
     // stream.  The front ends (reweighting, tallies, covariance: kernels of a few dozen to a few hundred workgroups each for a small
@@ -1491,21 +1549,15 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         if (st != GDCA_OK) done_front = 0;  // (nothing of a batch that failed to enqueue is run any further; it is drained below)
         for (int k = 0; k < K; ++k) {
             ctxs[k]->stream = bs;
-            if (st == GDCA_OK) ctxs[k]->pend_front_batch = in_group[k % G];
+            if (st == GDCA_OK) ctxs[k]->pend.front_batch = in_group[k % G];
         }
         rec.begin(bs, K);
         if (st == GDCA_OK) st = run_inverses(lead, ctxs, done_front);
         for (int k = 0; k < done_front && st == GDCA_OK; ++k) {
             rec.member(k);
-            ctxs[k]->pend_score_batch = done_front;
-            st = run_score(ctxs[k], p, S_dev[k]);
-            if (st == GDCA_OK && rank_sep > 0) {
-                gdca_ctx *m = ctxs[k];
-                m->rank_len = gdca_ranking_length(N[k], rank_sep);
-                m->rank_sep = rank_sep;
-                m->rank_status = m->rank_len > 0 ? ranking_stage(m, S_dev[k], N[k], rank_sep, m->rank_len, &m->rank_i, &m->rank_j, &m->rank_s) : GDCA_OK;
-                m->rank_pending = true;
-            }
+            ctxs[k]->pend.score_batch = done_front;
+            st = run_score(ctxs[k], contact_target(p->score, p->apc, S_dev[k]));
+            if (st == GDCA_OK && rank_sep > 0) enqueue_ranking(ctxs[k], S_dev[k], N[k], rank_sep);
             if (st != GDCA_OK) failed = k;
         }
         rec.member(-1);
@@ -1523,14 +1575,9 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
             for (int k = 0; k < K; ++k) {
                 (void)hipStreamSynchronize(own[k]);  // (a group's front ends)
                 ctxs[k]->pending = false;
-                ctxs[k]->rank_pending = false;
+                ctxs[k]->pend.rank.pending = false;
             }
-            if (failed > 0 && ctxs[failed]->err[0]) {
-                char msg[sizeof(lead->err)];
-                snprintf(msg, sizeof(msg), "member %d: %.400s", failed, ctxs[failed]->err);
-                memcpy(lead->err, msg, sizeof(msg));
-            }
-            return st;
+            return failed > 0 ? member_error(lead, ctxs[failed], failed, st) : st;
         }
         if (!chained) {
             (void)hipStreamSynchronize(bs);
@@ -1572,7 +1619,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
     bool chained = true;  // every member's own stream waits for what was enqueued for it elsewhere
     for (int k = 0; k < done_front && st == GDCA_OK; ++k) {
         ctxs[k]->stream = use[k];
-        st = run_score(ctxs[k], p, S_dev[k]);
+        st = run_score(ctxs[k], contact_target(p->score, p->apc, S_dev[k]));
         // the members' collects synchronise THEIR stream: make it wait for the stream the member's work went to (one event per member)
         if (st == GDCA_OK && use[k] != own[k] &&
             (hipEventRecord(ctxs[k]->ev_batch, use[k]) != hipSuccess || hipStreamWaitEvent(own[k], ctxs[k]->ev_batch, 0) != hipSuccess))
@@ -1585,11 +1632,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         for (int k = 0; k < K; ++k) {
             (void)hipStreamSynchronize(own[k]);  // (a front end enqueued side by side)
             ctxs[k]->pending = false;
-            if (k > 0 && ctxs[k]->err[0] && k == done_front) {
-                char msg[sizeof(lead->err)];
-                snprintf(msg, sizeof(msg), "member %d: %.400s", k, ctxs[k]->err);
-                memcpy(lead->err, msg, sizeof(msg));
-            }
+            if (k == done_front) member_error(lead, ctxs[k], k, st);
         }
     }
     for (int k = 0; k < K; ++k) ctxs[k]->stream = own[k];
@@ -1600,6 +1643,17 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         return fail(lead, GDCA_EHIP, "event chain of the batch%s%s", "", "");
     }
     return st;
+}
+
+// a host alignment on its way into a fused run: Z into scratch[0] (enqueued on the context's stream), room for n_scores score
+// matrices in scratch[1]
+static gdca_status upload_alignment(gdca_ctx *ctx, const int8_t *Z_host, int N, int M, int n_scores = 1)
+{
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
+    CHK(ensure(ctx, ctx->scratch[1], (size_t)n_scores * N * N * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
+    return GDCA_OK;
 }
 
 gdca_status gdca_run_dev_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *const *Z_dev, const int32_t *N,
@@ -1620,10 +1674,7 @@ gdca_status gdca_run(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, 
 {
     CHK(validate(ctx, N, M, q));
     if (!Z_host || !S_host) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
-    CHK(ensure(ctx, ctx->scratch[1], (size_t)N * N * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
+    CHK(upload_alignment(ctx, Z_host, N, M));
     gdca_status rs = gdca_run_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, (double *)ctx->scratch[1].p, st);
     if (rs != GDCA_OK) return rs;
     HIPCHK(hipMemcpyAsync(S_host, ctx->scratch[1].p, (size_t)N * N * sizeof(double), hipMemcpyDeviceToHost,
@@ -1669,21 +1720,13 @@ gdca_status gdca_run_ranked_async(gdca_ctx *ctx, const int8_t *Z_host, int32_t N
     CHK(validate(ctx, N, M, q));
     CHK(not_pending(ctx));
     if (!Z_host || min_separation < 1) return fail(ctx, GDCA_EINVAL, "null pointer or min_separation < 1%s%s", "", "");
-    const long long len = gdca_ranking_length(N, min_separation);
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
-    CHK(ensure(ctx, ctx->scratch[1], (size_t)N * N * sizeof(double)));
     // (from pageable memory this copy holds the calling thread until the last byte is staged -- and overlaps whatever another
     // context of the same device is computing meanwhile: the pipelined batch driver's upload of the NEXT family)
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
+    CHK(upload_alignment(ctx, Z_host, N, M));
     CHK(upload_done(ctx));  // Z_host is the caller's again when this call returns (gdca.h), pinned or not
     double *S_dev = (double *)ctx->scratch[1].p;
     CHK(gdca_run_dev_async(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, S_dev));
-    // the ranking is enqueued behind the scores before anybody waits: one synchronisation for the whole run
-    ctx->rank_len = len;
-    ctx->rank_sep = min_separation;
-    ctx->rank_status = len > 0 ? ranking_stage(ctx, S_dev, N, min_separation, len, &ctx->rank_i, &ctx->rank_j, &ctx->rank_s) : GDCA_OK;
-    ctx->rank_pending = true;
+    enqueue_ranking(ctx, S_dev, N, min_separation);
     return GDCA_OK;
 }
 
@@ -1702,14 +1745,7 @@ gdca_status gdca_run_ranked_phased_async(gdca_ctx *const *ctxs, int32_t K, const
         if (!m || !Z_host[k]) return fail(lead, GDCA_EINVAL, "null context or alignment in the batch%s%s", "", "");
         gdca_status vs = validate(m, N[k], M[k], q[k]);
         if (vs == GDCA_OK) vs = not_pending(m);
-        if (vs != GDCA_OK) {
-            if (k > 0) {
-                char msg[sizeof(lead->err)];
-                snprintf(msg, sizeof(msg), "member %d: %.400s", k, m->err);
-                memcpy(lead->err, msg, sizeof(msg));
-            }
-            return vs;
-        }
+        if (vs != GDCA_OK) return member_error(lead, m, k, vs);
     }
     HIPCHK(hipSetDevice(lead->device));
     for (int k = 0; k < K; ++k) {
@@ -1733,32 +1769,25 @@ gdca_status gdca_run_ranked_phased_async(gdca_ctx *const *ctxs, int32_t K, const
     bool ranked = false;  // (issued as batched grids, the rankings are part of the batch)
     CHK(run_phased(ctxs, K, Zd, N, M, q, p, Sd, min_separation, &ranked));
     // every member's ranking behind its scores, on the member's own stream (which now waits for the batch)
-    for (int k = 0; k < K && !ranked; ++k) {
-        gdca_ctx *m = ctxs[k];
-        m->rank_len = gdca_ranking_length(N[k], min_separation);
-        m->rank_sep = min_separation;
-        m->rank_status = m->rank_len > 0 ? ranking_stage(m, Sd[k], N[k], min_separation, m->rank_len, &m->rank_i, &m->rank_j, &m->rank_s) : GDCA_OK;
-        m->rank_pending = true;
-    }
+    for (int k = 0; k < K && !ranked; ++k) enqueue_ranking(ctxs[k], Sd[k], N[k], min_separation);
     return GDCA_OK;
 }
 
 gdca_status gdca_run_ranked_collect(gdca_ctx *ctx, int32_t *i_out, int32_t *j_out, double *score_out, gdca_stats *st)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (!ctx->rank_pending) return fail(ctx, GDCA_EINVAL, "no enqueued ranked run to collect%s%s", "", "");
-    ctx->rank_pending = false;
+    auto &r = ctx->pend.rank;
+    if (!r.pending) return fail(ctx, GDCA_EINVAL, "no enqueued ranked run to collect%s%s", "", "");
+    r.pending = false;
     gdca_stats own;
-    gdca_status cs = gdca_run_collect(ctx, st ? st : &own);
-    if (cs != GDCA_OK) return cs;
-    if (ctx->rank_status != GDCA_OK) return ctx->rank_status;
-    const long long len = ctx->rank_len;
-    if (len == 0) return GDCA_OK;
+    CHK(gdca_run_collect(ctx, st ? st : &own));
+    if (r.status != GDCA_OK) return r.status;
+    if (r.len == 0) return GDCA_OK;
     if (!i_out || !j_out || !score_out) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     // (a run whose inverse was refined, recomputed or run again at collect time has new scores: rank those)
-    if (ctx->pend_refined != 0 || ctx->pend_rescored)
-        CHK(ranking_stage(ctx, ctx->pend_S, ctx->pend_N, ctx->rank_sep, len, &ctx->rank_i, &ctx->rank_j, &ctx->rank_s));
-    return ranking_to_host(ctx, len, ctx->rank_i, ctx->rank_j, ctx->rank_s, i_out, j_out, score_out);
+    if (ctx->pend.at.refined != 0 || ctx->pend.at.rescored)
+        CHK(ranking_stage(ctx, ctx->pend.target.out, ctx->pend.N, r.sep, r.len, &r.i, &r.j, &r.s));
+    return ranking_to_host(ctx, r.len, r.i, r.j, r.s, i_out, j_out, score_out);
 }
 
 gdca_status gdca_run_ranked(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t min_separation,
@@ -1804,7 +1833,7 @@ static gdca_status multi_rank_member(gdca_ctx *ctx, const multi_rank *rk, int k,
     if (rk->len == 0) return GDCA_OK;
     int32_t *ii, *jj;
     double *sv;
-    CHK(ranking_stage(ctx, S_dev, ctx->pend_N, rk->sep, rk->len, &ii, &jj, &sv));
+    CHK(ranking_stage(ctx, S_dev, ctx->pend.N, rk->sep, rk->len, &ii, &jj, &sv));
     const size_t at = (size_t)k * (size_t)rk->len;
     return ranking_to_host(ctx, rk->len, ii, jj, sv, rk->i_out + at, rk->j_out + at, rk->score_out + at);
 }
@@ -1836,18 +1865,7 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
     CHK(ensure(ctx, ctx->sc_front, sizeof(gdca_dev_scalars)));
     CHK(tally_stage(ctx, Z_dev, N, M, q, &sc->Meff, p[0].pseudocount, 0, nullptr, (double *)ctx->Pij.p, (size_t)n));
     HIPCHK(hipMemcpyAsync(ctx->sc_front.p, sc, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
-    ctx->pend_timed = timed;
-    ctx->pend_stamped = ctx->stamped;
-    ctx->pend_front_batch = 1;
-    ctx->pend_score_batch = 1;
-    ctx->pend_tally_timed = false;
-    ctx->pend_Z = Z_dev;
-    ctx->pend_pij = (const double *)ctx->Pij.p;
-    ctx->pend_N = N;
-    ctx->pend_M = M;
-    ctx->pend_q = q;
-    ctx->pend_n = n;
-    ctx->pend_npad = n_pad;
+    pending_front(ctx, Z_dev, N, M, q, &p[0], (const double *)ctx->Pij.p, timed);
     double ms_theta = 0.0, ms_weights = 0.0;
     bool first = true;
     for (int k0 = 0; k0 < K; ++k0) {
@@ -1859,13 +1877,11 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
         if (!first) {
             // (every group starts from the scalars the front end left: theta, Meff, ...; its own -- pi_max, norms, info -- zero)
             HIPCHK(hipMemcpyAsync(sc, ctx->sc_front.p, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
-            ctx->pend_attempt = 0;
-            ctx->pend_rescored = false;
+            ctx->pend.at = gdca_pending::progress{};
             if (timed) CHK(mark(ctx, 2));
         }
-        ctx->pend_p = p[k0];
-        ctx->pend_refined = 0;
-        ctx->pend_fn_timed = false;
+        ctx->pend.p = p[k0];
+        ctx->pend.fn_timed = false;
         CHK(cov_from_pij_stage(ctx, N, M, q, pc, (double *)ctx->A.p, (size_t)n_pad, ctx->tune.refine != 0));
         gdca_launch_pad_identity(s, (double *)ctx->A.p, n, n_pad);
         if (di) {
@@ -1878,7 +1894,7 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
         if (timed) CHK(mark(ctx, 3));
         CHK(run_inverse(ctx));
         double *S0 = S_dev + (size_t)k0 * S_stride;
-        CHK(run_score(ctx, &p[k0], S0));
+        CHK(run_score(ctx, contact_target(p[k0].score, p[k0].apc, S0)));
         const gdca_status gs = gdca_run_collect(ctx, &st[k0]);
         if (gs == GDCA_EHIP || gs == GDCA_ENOMEM || gs == GDCA_EINVAL) return gs;  // (EINVAL here: a symbol outside 1..q)
         mst[k0] = gs;
@@ -1906,22 +1922,18 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
                 continue;
             }
             double *Sk = S_dev + (size_t)k * S_stride;
-            ctx->pend_fn_timed = false;
+            ctx->pend.fn_timed = false;
             HIPCHK(hipMemsetAsync(&sc->di_noconv, 0, sizeof(int), s));
             if (timed) CHK(mark(ctx, 11));
-            CHK(score_stage(ctx, N, sdim, n_pad, p[k].score, p[k].apc, Sk, timed));
+            CHK(score_stage(ctx, N, sdim, n_pad, contact_target(p[k].score, p[k].apc, Sk), timed));
             if (timed) CHK(mark(ctx, 5));
             CHK(fetch_scalars(ctx));
             if (timed) {
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, ctx->ev[11], ctx->ev[5]));
-                st[k].ms_score = ms;
-                HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[5]));
-                st[k].ms_total = ms;
-                if (ctx->pend_fn_timed && ctx->pend_refined == 0) {
-                    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[8]));
-                    st[k].ms_fn = ms;
-                }
+                bool tfail = false;
+                st[k].ms_score = between(ctx, 11, 5, &tfail);
+                st[k].ms_total = between(ctx, 0, 5, &tfail);
+                if (ctx->pend.fn_timed && ctx->pend.at.refined == 0) st[k].ms_fn = between(ctx, 7, 8, &tfail);
+                if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
             }
             if (ctx->sc_host->di_noconv != 0) {
                 st[k].info = -ctx->sc_host->di_noconv;
@@ -1958,11 +1970,8 @@ gdca_status gdca_run_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32
 {
     CHK(multi_check_args(ctx, Z_host, N, M, q, p, K, S_host));
     if (K == 1) return gdca_run(ctx, Z_host, N, M, q, p, S_host, st);
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t mat = (size_t)N * N;
-    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
-    CHK(ensure(ctx, ctx->scratch[1], (size_t)K * mat * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
+    CHK(upload_alignment(ctx, Z_host, N, M, K));
     gdca_stats own[GDCA_MULTI_MAX];
     const gdca_status rs = run_multi(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, K, (double *)ctx->scratch[1].p, mat, st ? st : own, nullptr);
     if (rs != GDCA_OK && rs != GDCA_ENOTPD && rs != GDCA_ENOCONV) return rs;
@@ -1982,10 +1991,7 @@ gdca_status gdca_run_ranked_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N
     const long long len = gdca_ranking_length(N, min_separation);
     if (len > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     if (K == 1) return gdca_run_ranked(ctx, Z_host, N, M, q, p, min_separation, i_out, j_out, score_out, st);
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
-    CHK(ensure(ctx, ctx->scratch[1], (size_t)N * N * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
+    CHK(upload_alignment(ctx, Z_host, N, M));
     const multi_rank rk{min_separation, len, i_out, j_out, score_out};
     gdca_stats own[GDCA_MULTI_MAX];
     return run_multi(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, K, (double *)ctx->scratch[1].p, 0, st ? st : own, &rk);
@@ -2211,8 +2217,8 @@ static gdca_status operator_inverse_once(gdca_ctx *ctx, double *A_dev, int n, in
 // ... once more after a launch the watchdog ended (gdca_run_collect has the why), up to option SWEEP_RETRIES times
 static gdca_status operator_inverse_retry(gdca_ctx *ctx, double *A_dev, int n, int n_pad)
 {
-    while (ctx->sc_host->info == INT32_MIN && ctx->pend_attempt < ctx->tune.sweep_retries) {
-        ++ctx->pend_attempt;
+    while (ctx->sc_host->info == INT32_MIN && ctx->pend.at.attempt < ctx->tune.sweep_retries) {
+        ++ctx->pend.at.attempt;
         HIPCHK(hipMemsetAsync(&((gdca_dev_scalars *)ctx->sc.p)->info, 0, sizeof(int), ctx->stream));
         CHK(operator_inverse_once(ctx, A_dev, n, n_pad));
     }
@@ -2268,18 +2274,18 @@ gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double 
             break;
         }
         gdca_launch_copy_in(lead->stream, A_dev[k], n[k], (double *)m->A.p, n_pad);
-        m->pend_n = n[k];
-        m->pend_npad = n_pad;
-        m->pend_timed = false;
+        m->pend.n = n[k];
+        m->pend.n_pad = n_pad;
+        m->pend.timed = false;
     }
     if (st == GDCA_OK) st = run_inverses(lead, ctxs, K);
     // kappa_1 and, where it is beyond the threshold, the Newton-Schulz step: member by member, as gdca_spd_inverse_dev does (the
     // caller's matrices are still intact; each member's switches are its own context's)
-    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_norms_and_refine(ctxs[k], A_dev[k], n[k], ctxs[k]->pend_npad));
-    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_fallback(ctxs[k], A_dev[k], n[k], ctxs[k]->pend_npad));
+    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_norms_and_refine(ctxs[k], A_dev[k], n[k], ctxs[k]->pend.n_pad));
+    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_fallback(ctxs[k], A_dev[k], n[k], ctxs[k]->pend.n_pad));
     for (int k = 0; k < K && st == GDCA_OK; ++k) {
         if (ctxs[k]->sc_host->info == INT32_MIN) continue;  // (the watchdog ended this member's launch: see below)
-        gdca_launch_copy_out_neg_sym(lead->stream, (const double *)ctxs[k]->A.p, ctxs[k]->pend_npad, A_dev[k], n[k]);
+        gdca_launch_copy_out_neg_sym(lead->stream, (const double *)ctxs[k]->A.p, ctxs[k]->pend.n_pad, A_dev[k], n[k]);
         st = check_launch(lead, "copy_out");
     }
     (void)hipStreamSynchronize(lead->stream);
@@ -2287,7 +2293,7 @@ gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double 
     if (st != GDCA_OK) return st;
     // members whose launch the watchdog ended (all members of a merged launch share that fate): once more, one by one
     for (int k = 0; k < K && st == GDCA_OK; ++k)
-        if (ctxs[k]->sc_host->info == INT32_MIN) st = member_error(lead, ctxs[k], k, operator_inverse_retry(ctxs[k], A_dev[k], n[k], ctxs[k]->pend_npad));
+        if (ctxs[k]->sc_host->info == INT32_MIN) st = member_error(lead, ctxs[k], k, operator_inverse_retry(ctxs[k], A_dev[k], n[k], ctxs[k]->pend.n_pad));
     if (st != GDCA_OK) return st;
     gdca_status worst = GDCA_OK;
     for (int k = 0; k < K; ++k) {
@@ -2319,7 +2325,7 @@ gdca_status gdca_fn_dev(gdca_ctx *ctx, const double *mJ_dev, int32_t N, int32_t 
     HIPCHK(hipSetDevice(ctx->device));
     const int sdim = q - 1, n = N * sdim, n_pad = round_up(n, GDCA_TILE);
     CHK(stage_neg_mJ(ctx, mJ_dev, n, n_pad));
-    return score_stage(ctx, N, sdim, n_pad, GDCA_SCORE_FROB, 0, S_dev);
+    return score_stage(ctx, N, sdim, n_pad, contact_target(GDCA_SCORE_FROB, 0, S_dev));
 }
 
 gdca_status gdca_di_dev(gdca_ctx *ctx, const double *mJ_dev, const double *C_dev, int32_t N, int32_t q, double *S_dev)
@@ -2334,7 +2340,7 @@ gdca_status gdca_di_dev(gdca_ctx *ctx, const double *mJ_dev, const double *C_dev
     gdca_launch_save_diag_blocks(s, C_dev, (size_t)n, N, sdim, (double *)ctx->Dblk.p);
     gdca_launch_diag_chol(s, (const double *)ctx->Dblk.p, N, sdim, (double *)ctx->Ld.p);
     CHK(stage_neg_mJ(ctx, mJ_dev, n, n_pad));
-    CHK(score_stage(ctx, N, sdim, n_pad, GDCA_SCORE_DI, 0, S_dev));
+    CHK(score_stage(ctx, N, sdim, n_pad, contact_target(GDCA_SCORE_DI, 0, S_dev)));
     CHK(fetch_scalars(ctx));
     if (ctx->sc_host->di_noconv)
         return fail(ctx, GDCA_ENOCONV, "eigenvalue iteration of a DI block did not converge%s%s", "", "");
@@ -2353,17 +2359,19 @@ gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double 
     return GDCA_OK;
 }
 
-// the fused form: gdca_run's front end and inverse, then the energy stage in the place of the score stage (score_stage, pend_energy)
-static gdca_status run_energies(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, const int8_t *X_dev,
-                                int32_t K, double *E_dev, gdca_stats *st)
+// the fused form of the energy entries, their own arguments checked: gdca_run's front end and inverse, then the stage `t` names in
+// the place of the contact score, collected at once
+static gdca_status run_target(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, const score_target &t,
+                              gdca_stats *st)
 {
-    CHK(run_front(ctx, Z_dev, N, M, q, p));
-    ctx->pend_energy = true;
-    ctx->pend_X = X_dev;
-    ctx->pend_K = K;
-    ctx->pend_E = E_dev;
+    CHK(check_params(ctx, p));
+    CHK(not_pending(ctx));
+    gdca_params pp = *p;  // (score and apc are ignored: no contact score is computed)
+    pp.score = GDCA_SCORE_FROB;
+    pp.apc = 0;
+    CHK(run_front(ctx, Z_dev, N, M, q, &pp));
     CHK(run_inverse(ctx));
-    CHK(run_score(ctx, p, nullptr));
+    CHK(run_score(ctx, t));
     return gdca_run_collect(ctx, st);
 }
 
@@ -2373,16 +2381,12 @@ gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N,
     CHK(validate(ctx, N, M, q));
     if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     if (X_dev && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0))
-        return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)%s%s", "", "");
-    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value%s%s", "", "");
-    CHK(not_pending(ctx));
-    gdca_params pp = *p;  // (score and apc are ignored: no contact score is computed)
-    pp.score = GDCA_SCORE_FROB;
-    pp.apc = 0;
-    const gdca_status rs = run_energies(ctx, Z_dev, N, M, q, &pp, X_dev ? X_dev : Z_dev, X_dev ? K : M, E_dev, st);
-    ctx->pend_energy = false;
-    return rs;
+    score_target t{};
+    t.kind = score_target::ENERGY;
+    t.out = E_dev;
+    t.X = X_dev ? X_dev : Z_dev;
+    t.K = X_dev ? K : M;
+    return run_target(ctx, Z_dev, N, M, q, p, t, st);
 }
 
 // the argument checks the four pair entry points share (nothing has run when one fails); KA / KB as they will be used
@@ -2416,32 +2420,18 @@ gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
     CHK(validate(ctx, N, M, q));
     CHK(validate_pair(ctx, N, q, split, XA_dev ? KA : M, XB_dev ? KB : M, what));
     if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0))
-        return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)%s%s", "", "");
-    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value%s%s", "", "");
-    CHK(not_pending(ctx));
-    gdca_params pp = *p;  // (score and apc are ignored: no contact score is computed)
-    pp.score = GDCA_SCORE_FROB;
-    pp.apc = 0;
-    // the fused form as run_energies: the pair stage in the place of the score stage (score_stage, pend_pair)
-    gdca_status rs = run_front(ctx, Z_dev, N, M, q, &pp);
-    if (rs == GDCA_OK) {
-        ctx->pend_pair = true;
-        ctx->pend_split = split;
-        ctx->pend_what = what;
-        ctx->pend_XA = XA_dev ? XA_dev : Z_dev;  // (the A halves of Z's own sequences lie N bytes apart)
-        ctx->pend_strideA = XA_dev ? (size_t)split : (size_t)N;
-        ctx->pend_KA = XA_dev ? KA : M;
-        ctx->pend_XB = XB_dev ? XB_dev : Z_dev + split;
-        ctx->pend_strideB = XB_dev ? (size_t)(N - split) : (size_t)N;
-        ctx->pend_KB = XB_dev ? KB : M;
-        ctx->pend_E = E_dev;
-        rs = run_inverse(ctx);
-        if (rs == GDCA_OK) rs = run_score(ctx, &pp, nullptr);
-        if (rs == GDCA_OK) rs = gdca_run_collect(ctx, st);
-    }
-    ctx->pend_pair = false;
-    return rs;
+    score_target t{};
+    t.kind = score_target::PAIR;
+    t.out = E_dev;
+    t.split = split;
+    t.what = what;
+    t.XA = XA_dev ? XA_dev : Z_dev;  // (the A halves of Z's own sequences lie N bytes apart)
+    t.strideA = XA_dev ? (size_t)split : (size_t)N;
+    t.KA = XA_dev ? KA : M;
+    t.XB = XB_dev ? XB_dev : Z_dev + split;
+    t.strideB = XB_dev ? (size_t)(N - split) : (size_t)N;
+    t.KB = XB_dev ? KB : M;
+    return run_target(ctx, Z_dev, N, M, q, p, t, st);
 }
 
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)

@@ -328,6 +328,47 @@ def test_failure_modes(g, ctx, refdata):
     assert np.array_equal(g.sequence_energies(mJ, Pi, X, q, ctx=ctx), good)
 
 
+def test_a_fused_energy_run_leaves_nothing_behind_for_the_next_score_stage(g, refdata):
+    """What a score stage computes is an argument of that stage, not state an earlier run left in the context: after a
+    gdca_run_energies that fails on an illegal byte of X and a good gdca_run_pair_energies, gdca_fn_dev on a known mJ and gdca_run on
+    the same alignment give, on the same context, bit for bit what a fresh context gives."""
+    import ctypes as C
+
+    from gaussdca.jl_amd import devops
+
+    Zo, q, mJ, Pi = golden_model(refdata, "small.fasta.gz", 0.8)
+    Zf = np.asfortranarray(Zo.T)
+    N, M = Zf.shape
+    X = mixed_sequences(np.random.default_rng(21), Zo, q, 10)
+
+    def fn_and_run(c):
+        dmJ = g.DeviceBuffer.from_array(c, np.ascontiguousarray(mJ))
+        dS = devops.compute_FN_dev(c, dmJ, N, q)
+        S_fn = dS.download((N, N))
+        dmJ.free()
+        dS.free()
+        return S_fn, c.run(Zf, q, 0.8, -1.0, 0)[0]
+
+    used, fresh = g.Context(0), g.Context(0)
+    try:
+        bad = X.copy(order="F")
+        bad[7, 4] = q + 1
+        prm, st, E = g._lib.Params(0.8, -1.0, 0, 0), g._lib.Stats(), np.full(10, np.nan)
+        p = g._lib._p
+        assert used.lib.gdca_run_energies(used.h, p(Zf), N, M, q, C.byref(prm), p(bad), 10, p(E), C.byref(st)) == g._lib.GDCA_EINVAL
+        split = N // 2
+        XA, XB = np.asfortranarray(X[:split]), np.asfortranarray(X[split:])
+        Ep, _ = used.run_pair_energies_ptr(Zf.ctypes.data, N, M, q, 0.8, -1.0, split, XA.ctypes.data, 10, XB.ctypes.data, 10)
+        assert Ep.shape == (10, 10) and np.all(np.isfinite(Ep))
+        S_fn, S_run = fn_and_run(used)
+        S_fn0, S_run0 = fn_and_run(fresh)
+    finally:
+        used.close()
+        fresh.close()
+    assert S_fn.shape == (N, N) and np.array_equal(S_fn, S_fn0)
+    assert S_run.shape == (N, N) and np.array_equal(S_run, S_run0)
+
+
 # ---- 6. sanity of meaning ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", GOLD)
 def test_family_fits_better_than_random(g, ctx, refdata, name):
