@@ -10,8 +10,8 @@ from ._lib import (ArgumentError, Context, ConvergenceError, DeviceBuffer, GdcaE
                    default_context, load)
 from .dcautils import (add_pseudocount, compute_C, compute_DI_gauss, compute_FN, compute_ranking,  # noqa: F401
                        compute_theta, compute_weighted_frequencies, compute_weights, correct_APC,
-                       inv_cholesky, neighbour_counts, pair_energies, pair_identity_sum, printrank,
+                       inv_cholesky, mutation_scan, neighbour_counts, pair_energies, pair_identity_sum, printrank,
                        read_fasta_alignment, remove_duplicate_sequences, sequence_energies, Ranking)
-from .gdca import check_arguments, gDCA, gDCA_energies, gDCA_multi, gDCA_pair_energies  # noqa: F401
+from .gdca import check_arguments, gDCA, gDCA_energies, gDCA_multi, gDCA_mutation_scan, gDCA_pair_energies  # noqa: F401
 
 __all__ = ["gDCA", "printrank"]

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("GDCA_LIB") or os.path.join(_HERE, "libgdca.so")
 GDCA_OK, GDCA_EINVAL, GDCA_ENOTPD, GDCA_EHIP, GDCA_ENOMEM, GDCA_ENOCONV = 0, 1, 2, 3, 4, 5
 SCORE_FROB, SCORE_DI = 0, 1
 PAIR_COUPLING, PAIR_ENERGY = 0, 1  # `what` of gdca_pair_energies: the cross-term matrix R alone, or the energy of every concatenation
+MUT_DELTA, MUT_POTENTIAL = 0, 1  # `what` of gdca_mutation_scan: the energy change of every substitution, or the site potentials themselves
 ABI_VERSION = 6  # GDCA_VERSION_MAJOR * 1000 + GDCA_VERSION_MINOR of the header this binding mirrors
 
 
@@ -169,6 +170,12 @@ SYMBOLS = {
                                              C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
     "gdca_run_pair_energies": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
                                          C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_mutation_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_mutation_scan": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_run_mutation_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_mutation_scan": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.POINTER(Stats)]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -368,6 +375,37 @@ class Context:
         self.check(self.lib.gdca_pair_energies_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr) if Pi_ptr is not None else None, int(N),
                                                    int(q), int(split), C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB), int(what),
                                                    C.c_void_p(E_ptr)))
+
+    # ---- the energy change of every single substitution (gdca_run_mutation_scan) ----
+    def run_mutation_scan_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None,
+                              K: int = 0, what: int = 0):
+        """gdca_run_mutation_scan on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run() fits
+        it, then D[k, i, b - 1] = the energy change of setting site i of sequence k of X (N x K, same layout; None: Z's own M sequences)
+        to symbol b (``what`` = MUT_DELTA), or the site potential V (MUT_POTENTIAL).  Returns (D float64 (K, N, q), stats)."""
+        Ke = int(K) if X_ptr is not None else int(M)
+        D = np.empty((max(Ke, 0), int(N), int(q)), dtype=np.float64)
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rc = self.lib.gdca_run_mutation_scan(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
+                                             C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), int(what), _p(D), C.byref(st))
+        self.check(rc, st.info)
+        return D, st.as_dict()
+
+    def run_mutation_scan_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int,
+                              what: int, D_ptr: int):
+        """Device-pointer form (Z, X and D resident in HBM; D holds q N K doubles).  Returns the stats dict."""
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rc = self.lib.gdca_run_mutation_scan_dev(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
+                                                 C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), int(what), C.c_void_p(D_ptr),
+                                                 C.byref(st))
+        self.check(rc, st.info)
+        return st.as_dict()
+
+    def mutation_scan_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int, K: int, what: int, D_ptr: int) -> None:
+        """gdca_mutation_scan_dev: mJ (n x n), Pi (n), X (N x K int8) and D (q N K doubles, (K, N, q) row-major) are device pointers."""
+        self.check(self.lib.gdca_mutation_scan_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), C.c_void_p(X_ptr), int(K),
+                                                   int(what), C.c_void_p(D_ptr)))
 
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):

@@ -34,13 +34,14 @@ struct gdca_gate {
 };
 
 // What the score stage of a run computes, handed to score_stage by whoever calls it: the contact score (FN or DI, with or without
-// APC), or -- the fused energy entries -- the model scored on sequences X, or on the pairings across a split.  The enqueued run keeps
+// APC), or -- the fused energy entries -- the model scored on sequences X, on the pairings across a split, or scanned for every single
+// substitution of sequences X.  The enqueued run keeps
 // its own (gdca_pending::target): a second attempt, refinement or fallback at collect time scores the same thing again.
 struct score_target {
-    enum { CONTACT, ENERGY, PAIR } kind;
-    double *out;                       // S (N x N), E (K) or E (KA x KB)
+    enum { CONTACT, ENERGY, PAIR, MUTATION } kind;
+    double *out;                       // S (N x N), E (K), E (KA x KB) or D (q x N x K)
     int score, apc;                    // contact
-    const int8_t *X;                   // energy (k_energy.hip): N x K
+    const int8_t *X;                   // energy (k_energy.hip) and mutation scan (k_mutation.hip, with `what`): N x K
     int K;
     const int8_t *XA, *XB;             // pair (k_pair_energy.hip): as pair_stage takes them
     size_t strideA, strideB;
@@ -906,10 +907,32 @@ static gdca_status pair_stage(gdca_ctx *ctx, const double *A, size_t ld, double 
     return check_launch(ctx, "pair energies");
 }
 
+// D[(b - 1) + q (i + N k)]: the site potentials V (what = GDCA_MUT_POTENTIAL) or the energy changes dE (GDCA_MUT_DELTA) of every single
+// substitution of the K sequences X (N x K) (k_mutation.hip) from the element-wise lower triangle of A (ld, sign as energy_stage).  The
+// packed symbols and g live in the energy stage's buffers.  Illegal bytes of X: sc->bad_symbol bit 2.
+static gdca_status mutation_stage(gdca_ctx *ctx, const double *A, size_t ld, double sign, const double *Pi, int N, int q, const int8_t *X_dev,
+                                  int K, int what, double *D_dev)
+{
+    hipStream_t s = ctx->stream;
+    const int sdim = q - 1, n = N * sdim;
+    const int nI = gdca_energy_blocks(N), nb = gdca_energy_gblocks(n);
+    CHK(ensure(ctx, ctx->Xg, (size_t)nI * K * sizeof(uint32_t)));
+    CHK(ensure(ctx, ctx->gpart, (size_t)nb * nb * 64 * sizeof(double)));
+    CHK(ensure(ctx, ctx->gvec, ((size_t)n + 1) * sizeof(double)));
+    double *g = (double *)ctx->gvec.p;
+    gdca_launch_energy_pack(s, X_dev, (uint32_t *)ctx->Xg.p, N, K, q, (gdca_dev_scalars *)ctx->sc.p);
+    gdca_launch_energy_g(s, A, ld, sign, n, Pi, (double *)ctx->gpart.p, g, g + n);
+    HIPCHK(gdca_launch_mutation_scan(s, A, ld, sign, g, (const uint32_t *)ctx->Xg.p, N, sdim, K, what, D_dev, ctx->ncu));
+    return check_launch(ctx, "mutation scan");
+}
+
 // -mJ in ctx->A (ld = n_pad) -> what `t` asks for
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t, bool time_fn = false)
 {
     hipStream_t s = ctx->stream;
+    if (t.kind == score_target::MUTATION)  // gdca_run_mutation_scan: the model is scanned for every single substitution of X
+        return mutation_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, t.X, t.K, t.what,
+                              t.out);
     if (t.kind == score_target::PAIR)  // gdca_run_pair_energies: the model is scored on the pairings across the split
         return pair_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, t.split, t.XA, t.strideA,
                           t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
@@ -2434,6 +2457,43 @@ gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
     return run_target(ctx, Z_dev, N, M, q, p, t, st);
 }
 
+// the argument checks the four mutation-scan entry points share (nothing has run when one fails); K as it will be used
+static gdca_status validate_mutation(gdca_ctx *ctx, int N, int q, long long K, int what)
+{
+    CHK(validate(ctx, N, 1, q));
+    // (the grids round K up to whole workgroups of 256 sequences in 32-bit arithmetic)
+    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (what != GDCA_MUT_DELTA && what != GDCA_MUT_POTENTIAL) return fail(ctx, GDCA_EINVAL, "invalid value of `what`%s%s", "", "");
+    return GDCA_OK;
+}
+
+gdca_status gdca_mutation_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                   int32_t K, int32_t what, double *D_dev)
+{
+    CHK(validate_mutation(ctx, N, q, K, what));
+    if (!mJ_dev || !Pi_dev || !X_dev || !D_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(begin(ctx));
+    CHK(mutation_stage(ctx, mJ_dev, (size_t)N * (q - 1), 1.0, Pi_dev, N, q, X_dev, K, what, D_dev));
+    CHK(fetch_scalars(ctx));
+    if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
+    return GDCA_OK;
+}
+
+gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                       const int8_t *X_dev, int32_t K, int32_t what, double *D_dev, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_mutation(ctx, N, q, X_dev ? K : M, what));
+    if (!Z_dev || !D_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    score_target t{};
+    t.kind = score_target::MUTATION;
+    t.out = D_dev;
+    t.X = X_dev ? X_dev : Z_dev;
+    t.K = X_dev ? K : M;
+    t.what = what;
+    return run_target(ctx, Z_dev, N, M, q, p, t, st);
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -2660,6 +2720,38 @@ gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
                                    XA_host ? (const int8_t *)ctx->scratch[3].p : nullptr, KA, XB_host ? (const int8_t *)ctx->scratch[4].p : nullptr,
                                    KB, what, (double *)ctx->scratch[5].p, st));
     return to_host(ctx, E_host, ctx->scratch[5], ne);
+}
+
+gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                               int32_t what, double *D)
+{
+    CHK(validate_mutation(ctx, N, q, K, what));
+    if (!mJ || !Pi || !X || !D) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)N * (q - 1), nd = (size_t)q * (size_t)N * (size_t)K * sizeof(double);
+    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
+    CHK(to_dev(ctx, ctx->scratch[2], Pi, n * sizeof(double)));
+    CHK(to_dev(ctx, ctx->scratch[0], X, (size_t)N * K));
+    CHK(ensure(ctx, ctx->scratch[5], nd));
+    CHK(gdca_mutation_scan_dev(ctx, (const double *)ctx->scratch[1].p, (const double *)ctx->scratch[2].p, N, q, (const int8_t *)ctx->scratch[0].p,
+                               K, what, (double *)ctx->scratch[5].p));
+    return to_host(ctx, D, ctx->scratch[5], nd);
+}
+
+gdca_status gdca_run_mutation_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                   const int8_t *X_host, int32_t K, int32_t what, double *D_host, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_mutation(ctx, N, q, X_host ? K : M, what));
+    if (!Z_host || !D_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nd = (size_t)q * (size_t)N * (size_t)(X_host ? K : M) * sizeof(double);
+    CHK(to_dev(ctx, ctx->scratch[0], Z_host, (size_t)N * M));
+    if (X_host) CHK(to_dev(ctx, ctx->scratch[3], X_host, (size_t)N * K));
+    CHK(ensure(ctx, ctx->scratch[5], nd));
+    CHK(gdca_run_mutation_scan_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, X_host ? (const int8_t *)ctx->scratch[3].p : nullptr, K,
+                                   what, (double *)ctx->scratch[5].p, st));
+    return to_host(ctx, D_host, ctx->scratch[5], nd);
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

@@ -256,3 +256,10 @@ void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const
 // T: Ac x (N - split) * sdim doubles.  EAB (KA + KB marginal energies) and c0: the energy; EAB == nullptr: the coupling R alone
 void gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N, int split,
                             int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E, int ncu);
+
+// ---- k_mutation.hip: V(x; i, c) / dE(x; i, b) of every single substitution of K sequences ------------------------------------------------
+// D[(b - 1) + q (i + N k)] (q = sdim + 1; what: GDCA_MUT_DELTA | GDCA_MUT_POTENTIAL) of the K sequences packed by gdca_launch_energy_pack
+// (Xg) from the element-wise lower triangle of A (ld; sign -1: A holds -mJ) and g = mJ Pi (gdca_launch_energy_g).  An error: the
+// dynamic LDS limit could not be raised for the tile, nothing was launched
+hipError_t gdca_launch_mutation_scan(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const uint32_t *Xg, int N, int sdim,
+                               int K, int what, double *D, int ncu);

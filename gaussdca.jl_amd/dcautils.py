@@ -389,6 +389,42 @@ def pair_energies(mJ, Pi, XA, XB, q: int = 21, what="energy", ctx=None) -> np.nd
     return E
 
 
+def _mut_what_arg(what) -> int:
+    w = str(what).lstrip(":")
+    if w == "delta":
+        return _lib.MUT_DELTA
+    if w == "potential":
+        return _lib.MUT_POTENTIAL
+    raise ArgumentError(f"invalid what value: {what} (must be either delta or potential)")
+
+
+def mutation_scan(mJ, Pi, X, q: int = 21, what="delta", ctx=None) -> np.ndarray:
+    """D[k, i, b - 1] for every single substitution of the K columns of X (shape (N, K) like Z, symbols 1..q, q = the gap) under the
+    Gaussian model (mJ, Pi): ``what="delta"`` the energy change E(x_k with site i set to b) - E(x_k) in the sense of
+    ``sequence_energies`` (exactly +0.0 at b = x_i; b = q deletes the residue), ``what="potential"`` the site potential
+    V(x; i, c) = sum_{j != i} mJ[r(i,c), r(j,x_j)] + mJ[r(i,c), r(i,c)] / 2 - (mJ Pi)[r(i,c)] (0 for the gap), of which the change is
+    the difference V(b) - V(x_i).  Returns a (K, N, q) array.  mJ must be symmetric (its lower triangle is read)."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    w = _mut_what_arg(what)
+    Xf = _symbols(X, "X")
+    N, K = Xf.shape
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = N * (int(q) - 1)
+    if N < 1 or mJ.shape != (n, n) or Pi.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: X has N = {N} sites, q = {q}, so mJ must be {n} x {n} and Pi have {n} entries "
+                            f"(got {mJ.shape} and {Pi.shape})")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    ctx = ctx or default_context()
+    D = np.empty((K, N, int(q)), dtype=np.float64)
+    ctx.check(ctx.lib.gdca_mutation_scan(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xf), K, w, _lib._p(D)))
+    return D
+
+
 def printrank(io, R: Sequence[Tuple[int, int, float]] = None):
     """printrank(io, R) / printrank(filename, R): one "%i %i %e" line per entry
     (src/GaussDCA.jl:67-74).  printrank(R) alone writes to stdout (the reference's one-argument

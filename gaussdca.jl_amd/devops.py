@@ -99,6 +99,14 @@ def pair_energies_dev(ctx: Context, dmJ, dPi, N: int, q: int, split: int, dXA, K
     return dE
 
 
+def mutation_scan_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, what: int = 0, dD=None):
+    """D[(b - 1) + q (i + N k)] of every single substitution of the K sequences X (N x K int8) with every array in HBM
+    (gdca_mutation_scan_dev): what = _lib.MUT_DELTA (the energy change) or _lib.MUT_POTENTIAL (the site potentials)"""
+    dD = dD or DeviceBuffer(ctx, 8 * int(q) * N * K)
+    ctx.mutation_scan_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), _ptr(dX).value, int(K), int(what), _ptr(dD).value)
+    return dD
+
+
 def scores_stepwise(Z, q: int, pseudocount: float = 0.8, theta=":auto", score: str = "frob", ctx: Context = None
                     ) -> Tuple[np.ndarray, dict]:
     """The six statements of src/GaussDCA.jl:28-42 one by one, arrays resident in HBM.  Z: (N, M) int8.

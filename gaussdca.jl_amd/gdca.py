@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, default_context
-from .dcautils import (FastaAlignment, Ranking, _symbols, _theta_arg, _what_arg, read_fasta_alignment, remove_duplicate_sequences)
+from .dcautils import (FastaAlignment, Ranking, _mut_what_arg, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
+                       remove_duplicate_sequences)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
 last_multi_stats = None  # gDCA_multi: one stats dict per setting of its most recent call, in the order of the settings
@@ -84,21 +85,12 @@ def gDCA(filename: str, pseudocount: float = 0.8, theta=":auto", max_gap_fractio
     return Ranking(ii, jj, sc)
 
 
-def gDCA_energies(filename: str, sequences=None, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
-                  remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
-    """Energies of sequences under the Gaussian model gDCA fits to the alignment in ``filename`` (same reading, reweighting,
-    pseudocount, covariance and inverse; same validation and messages): E(x) = 1/2 (x - Pi)' mJ (x - Pi), minus the log-likelihood
-    up to the model's constant.  Lower = fits the family better.
-
-    ``sequences``: ``None`` scores the alignment's own sequences (after the gap filter and the optional deduplication); an
-    ``(N, K)`` int8 array (symbols 1..q like ``Z``) scores its columns; a string names a second FASTA file, read with the same reader
-    and ``max_gap_fraction = 1.0`` -- every record is kept, so the energies line up with the records.  Stats go to ``last_stats``."""
+def _fit_then_score(filename, sequences, pseudocount, theta, max_gap_fraction, remove_dups, ctx, run, unreliable):
+    """What the fused entries that score ``sequences`` under the fitted model share (gDCA_energies, gDCA_mutation_scan): the
+    ``sequences`` conventions and their checks, the alignment with or without deduplication, the stats and the conditioning warning.
+    ``run(c, ptr, N, M, q, X_ptr, K)`` is the context call (X_ptr None: the alignment's own sequences); ``unreliable`` names the result
+    in the warning.  Called after check_arguments."""
     global last_stats
-    if "θ" in kw:
-        theta = kw.pop("θ")
-    if kw:
-        raise TypeError(f"gDCA_energies() got unexpected keyword arguments {sorted(kw)}")
-    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
     if isinstance(sequences, (str, bytes, os.PathLike)):
         if not os.path.isfile(sequences):
             raise ArgumentError(f"cannot open file {sequences}")
@@ -122,25 +114,42 @@ def gDCA_energies(filename: str, sequences=None, pseudocount: float = 0.8, theta
         if X is not None and X.shape[1] < 1:
             raise ArgumentError("sequences holds no sequence")
         c = ctx or default_context()
-        if X is None:
-            return c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta))
-        return c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), X.ctypes.data, X.shape[1])
+        return run(c, ptr, N, M, q, None if X is None else X.ctypes.data, 0 if X is None else X.shape[1])
 
     if remove_dups:
         Z = read_fasta_alignment(filename, max_gap_fraction)
         Z, _ = remove_duplicate_sequences(Z)
         Zf = np.asfortranarray(Z, dtype=np.int8)
-        E, last_stats = _run(Zf.ctypes.data, Zf.shape[0], Zf.shape[1], int(Z.max()))
+        out, last_stats = _run(Zf.ctypes.data, Zf.shape[0], Zf.shape[1], int(Z.max()))
     else:
         with FastaAlignment(filename, max_gap_fraction) as fa:
-            E, last_stats = _run(fa.ptr, fa.N, fa.M, fa.q)
+            out, last_stats = _run(fa.ptr, fa.N, fa.M, fa.q)
     if last_stats.get("refined", 0) < 0:
         import warnings
 
         warnings.warn("gDCA: the covariance is too ill-conditioned for the block sweep even with its refinement step "
-                      f"(||inv(C)||_1 = {last_stats['inverse_norm1']:.3g}; pseudocount {pseudocount}): energies are unreliable",
-                      RuntimeWarning, stacklevel=2)
-    return E
+                      f"(||inv(C)||_1 = {last_stats['inverse_norm1']:.3g}; pseudocount {pseudocount}): {unreliable} are unreliable",
+                      RuntimeWarning, stacklevel=3)
+    return out
+
+
+def gDCA_energies(filename: str, sequences=None, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+                  remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
+    """Energies of sequences under the Gaussian model gDCA fits to the alignment in ``filename`` (same reading, reweighting,
+    pseudocount, covariance and inverse; same validation and messages): E(x) = 1/2 (x - Pi)' mJ (x - Pi), minus the log-likelihood
+    up to the model's constant.  Lower = fits the family better.
+
+    ``sequences``: ``None`` scores the alignment's own sequences (after the gap filter and the optional deduplication); an
+    ``(N, K)`` int8 array (symbols 1..q like ``Z``) scores its columns; a string names a second FASTA file, read with the same reader
+    and ``max_gap_fraction = 1.0`` -- every record is kept, so the energies line up with the records.  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_energies() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    return _fit_then_score(filename, sequences, pseudocount, theta, max_gap_fraction, remove_dups, ctx,
+                           lambda c, ptr, N, M, q, X_ptr, K: c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), X_ptr, K),
+                           "energies")
 
 
 def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what="energy", pseudocount: float = 0.8, theta=":auto",
@@ -203,6 +212,29 @@ def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what
                       f"(||inv(C)||_1 = {last_stats['inverse_norm1']:.3g}; pseudocount {pseudocount}): energies are unreliable",
                       RuntimeWarning, stacklevel=2)
     return E
+
+
+def gDCA_mutation_scan(filename: str, sequences=None, what="delta", pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+                       remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
+    """The mutational landscape of sequences under the Gaussian model gDCA fits to the alignment in ``filename`` (same reading,
+    reweighting, pseudocount, covariance and inverse; same validation and messages): a ``(K, N, q)`` array D with D[k, i, b - 1] the
+    energy change, in the sense of ``gDCA_energies``, of setting site i of sequence k to symbol b (``what="delta"``: exactly 0 at the
+    sequence's own symbol, b = q deletes the residue; negative = the mutant fits the family better), or the site potentials V the
+    changes are differences of (``what="potential"``).
+
+    ``sequences`` as for ``gDCA_energies``: ``None`` scans the alignment's own sequences (after the gap filter and the optional
+    deduplication); an ``(N, K)`` int8 array (symbols 1..q like ``Z``) scans its columns; a string names a second FASTA file, read
+    with ``max_gap_fraction = 1.0`` so every record is kept.  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_mutation_scan() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    w = _mut_what_arg(what)
+    return _fit_then_score(filename, sequences, pseudocount, theta, max_gap_fraction, remove_dups, ctx,
+                           lambda c, ptr, N, M, q, X_ptr, K: c.run_mutation_scan_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta),
+                                                                                     X_ptr, K, w),
+                           "energy changes")
 
 
 def _setting(s):

@@ -337,6 +337,34 @@ gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                                        int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what,
                                        double *E_dev, gdca_stats *st);
 
+/* ---- mutation scan: the energy change of every single substitution ---------------------------------------------------------
+ * The mutational landscape of a sequence under the model (what is compared with deep mutational scans).  Conventions as for the
+ * energies above: s = q - 1, n = N s, r(i, c) = i s + c - 1 for symbol c in 1..s at 0-based site i, the gap q has no row, Pi is
+ * add_pseudocount's first result, g = mJ Pi.  For a sequence x (N symbols), a site i and a symbol c the SITE POTENTIAL is
+ *     V(x; i, c) = sum over the sites j != i with x_j no gap of mJ[r(i,c), r(j,x_j)]  +  1/2 mJ[r(i,c), r(i,c)]  -  g[r(i,c)],   c in 1..s,
+ *     V(x; i, q) = 0   (exactly +0.0),
+ * and E(x with site i set to c) = V(x; i, c) + a term that does not depend on c, so the energy change of the substitution x_i -> b is
+ *     dE(x; i, b) = V(x; i, b) - V(x; i, x_i)
+ * -- the gdca_energies energy of the mutant minus that of x up to rounding -- at N gathers an entry where the explicit mutant costs
+ * N^2 / 2; no mutant is written down.
+ *     what = GDCA_MUT_POTENTIAL:  D = V,
+ *     what = GDCA_MUT_DELTA:      D = dE, ONE f64 subtraction of the two potentials the other mode returns: D[k, i, b] is bit-equal to
+ *                                 V[k, i, b] - V[k, i, x_i], and the entry b = x_i is exactly +0.0.
+ * X is N x K int8 column-major like Z, K >= 1.  D has q N K doubles, column-major q x N x K: D[(b - 1) + q (i + N k)] (64-bit index;
+ * a (K, N, q) array in row-major terms); column q is the gap target ("delete this residue").  mJ as for gdca_energies: symmetric,
+ * only its lower triangle is read.  Every sum is taken in a fixed order in f64 (no floating-point atomics): the bits of D[k, i, :]
+ * depend only on the model, x_k and `what` -- not on K, on where x_k stands in the batch or on the kernel instance.
+ * GDCA_EINVAL: K < 1 or K > INT32_MAX - 256, q outside 2..31, an unknown `what`, a null pointer -- nothing is run -- or a byte of X outside 1..q (detected on
+ * the device; nothing is read out of bounds for it).  On failure D is unspecified.  Synchronous. */
+enum { GDCA_MUT_DELTA = 0, GDCA_MUT_POTENTIAL = 1 };
+gdca_status gdca_mutation_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                   int32_t K, int32_t what, double *D_dev);
+/* Fused: fits the model on Z exactly as gdca_run_energies does (the same code, the same conditioning screen), then the scan on it; mJ
+ * never leaves HBM.  X == NULL scans Z's own M sequences (K is then ignored and q N M doubles are written).  p->score and p->apc are
+ * ignored.  Stats as gdca_run_energies: ms_score is the scan stage, ms_fn 0. */
+gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                       const int8_t *X_dev, int32_t K, int32_t what, double *D_dev, gdca_stats *st);
+
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* compute_theta's all-pairs identity sum (inside compute_weighted_frequencies, :28) */
 gdca_status gdca_pair_identity_sum(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, uint64_t *out);
@@ -382,6 +410,12 @@ gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi
 gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                    int32_t split, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, int32_t what,
                                    double *E_host, gdca_stats *st);
+
+/* mutation scan with host pointers: upload, the _dev form, download */
+gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                               int32_t what, double *D);
+gdca_status gdca_run_mutation_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                   const int8_t *X_host, int32_t K, int32_t what, double *D_host, gdca_stats *st);
 
 /* ---- host-side utilities around the hot path (plain C++, no GPU): the reference's callers of the path -------- */
 /* CPUs this process can really use: hardware threads capped by the cgroup CPU quota (a container may see 256 threads and be given

@@ -15,7 +15,7 @@
 module GaussDCAHip
 
 export gDCA, gDCA_stepwise, printrank, compute_weights, compute_weighted_frequencies, add_pseudocount,
-       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, pair_energies
+       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, pair_energies, mutation_scan, gDCA_mutation_scan
 
 using LinearAlgebra
 import DCAUtils                                   # host-side I/O only: read_fasta_alignment, remove_duplicate_sequences
@@ -226,6 +226,51 @@ function gDCA_energies(filename::AbstractString; sequences = nothing, pseudocoun
     check(rc, st.info)
     st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: energies are unreliable" pseudocount
     return E
+end
+
+# D[b, i, k] for every single substitution of the K columns of X (N x K like Z) under the model (include/gdca.h, "mutation scan"):
+# what = :delta, the energy change of setting site i of sequence k to symbol b (exactly 0 at the sequence's own symbol; b = q deletes
+# the residue), or :potential, the site potentials V the changes are differences of.  A q x N x K array.
+function mutation_scan(mJ::Matrix{Float64}, Pi::Vector{Float64}, X::Matrix{Int8}, q::Integer = 21; what::Symbol = :delta)
+    what in (:delta, :potential) || throw(ArgumentError("invalid what value: $what (must be either :delta or :potential)"))
+    N, K = size(X); n = N * (q - 1)
+    (size(mJ) == (n, n) && length(Pi) == n) || throw(ArgumentError("incompatible sizes of mJ, Pi, X and q"))
+    D = Array{Float64, 3}(undef, q, N, K)
+    GC.@preserve mJ Pi X D check(ccall((:gdca_mutation_scan, libgdca), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int8}, Int32, Int32, Ptr{Float64}),
+        ctx(), mJ, Pi, N, q, X, K, what == :potential ? 1 : 0, D))
+    return D
+end
+
+# gDCA's fit (same keywords as gDCA_energies), then the scan of `sequences` under it: nothing = the alignment's own sequences, a
+# Matrix{Int8} (N x K), or the name of a second FASTA file (read with max_gap_fraction = 1: every record kept)
+function gDCA_mutation_scan(filename::AbstractString; sequences = nothing, what::Symbol = :delta, pseudocount::Real = 0.8, θ = :auto,
+                            max_gap_fraction::Real = 0.9, remove_dups::Bool = false)
+    check_arguments(filename, pseudocount, θ, max_gap_fraction, :frob, 1)
+    what in (:delta, :potential) || throw(ArgumentError("invalid what value: $what (must be either :delta or :potential)"))
+    Z = DCAUtils.read_fasta_alignment(filename, max_gap_fraction)
+    if remove_dups
+        Z, _ = DCAUtils.remove_duplicate_sequences(Z)
+    end
+    q = Int(maximum(Z))
+    q ≥ 32 && error("parameter q=$q is too big (max 31 is allowed)")
+    X = sequences isa AbstractString ? DCAUtils.read_fasta_alignment(sequences, 1.0) : sequences
+    (X === nothing || X isa Matrix{Int8}) || throw(ArgumentError("sequences must be a Matrix{Int8} of symbols 1..q, a FASTA file name or nothing"))
+    N, M = size(Z)
+    (X === nothing || size(X, 1) == N) || throw(ArgumentError("sequences have $(size(X, 1)) sites, the alignment has $N"))
+    K = X === nothing ? M : size(X, 2)
+    D = Array{Float64, 3}(undef, q, N, K)
+    p = Ref(GdcaParams(Float64(pseudocount), theta_arg(θ), 0, 0))
+    st = GdcaStats()
+    Xp = X === nothing ? Ptr{Int8}(C_NULL) : pointer(X)
+    GC.@preserve Z X D begin
+        rc = ccall((:gdca_run_mutation_scan, libgdca), Cint,
+                   (Ptr{Cvoid}, Ptr{Int8}, Int32, Int32, Int32, Ref{GdcaParams}, Ptr{Int8}, Int32, Int32, Ptr{Float64}, Ref{GdcaStats}),
+                   ctx(), Z, N, M, q, p, Xp, K, what == :potential ? 1 : 0, D, st)
+    end
+    check(rc, st.info)
+    st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: energy changes are unreliable" pseudocount
+    return D
 end
 
 function compute_DI_gauss(mJ::Matrix{Float64}, C::Matrix{Float64}, q::Integer = 21)
