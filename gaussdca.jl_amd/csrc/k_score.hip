@@ -41,30 +41,28 @@ __device__ __forceinline__ double wave_sum(double v)
 // unchanged: scores are bit for bit those of the old kernel.
 #define FN_PG 4
 
-// FN_MAXU: 16-byte loads per thread that hold a workgroup's image, ceil(s (FN_PG s / 2) / 256).  SDIM: s as a compile-time
-// constant (20 = the q = 21 alphabet: the loops over a block unroll, their LDS reads are issued back to back instead of one
-// round trip per addition) or 0 = run-time s.
+// FN_MAXU: 16-byte loads per thread that hold a workgroup's image, ceil(s (FN_PG s / 2) / 256).  s is a run-time value in every
+// instance: the one size worth a form of its own, s = 20, has `k_fn20` below.
 struct k_fn_args {
     const double *A;
     size_t ld;
     int N;
-    int sdim_rt;
+    int sdim;
     double *S;
 };
-static inline k_fn_args k_fn_mk(const double *A, size_t ld, int N, int sdim_rt, double *S)
+static inline k_fn_args k_fn_mk(const double *A, size_t ld, int N, int sdim, double *S)
 {
-    return k_fn_args{A, ld, N, sdim_rt, S};
+    return k_fn_args{A, ld, N, sdim, S};
 }
-template <int CAP, int FN_MAXU, int SDIM>
+template <int CAP, int FN_MAXU>
 __global__ __launch_bounds__(256) void k_fn(const BatchArgs<k_fn_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
     const double *__restrict__ A = a_.A;
     size_t ld = a_.ld;
     int N = a_.N;
-    int sdim_rt = a_.sdim_rt;
+    const int sdim = a_.sdim;
     double *__restrict__ S = a_.S;
-    const int sdim = SDIM ? SDIM : sdim_rt;
     extern __shared__ __attribute__((aligned(16))) double fsm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int ss = sdim * sdim;
@@ -324,20 +322,19 @@ void gdca_launch_fn(hipStream_t s, const double *A, size_t ld, int N, int sdim, 
     const int nJ = (N + FN_PG - 1) / FN_PG;   // row chunks (a column site's workgroups past its last chunk leave at once)
     const dim3 nwg((unsigned)nJ, (unsigned)(N - 1));
     const size_t lds = ((size_t)sdim * (FN_PG * sdim + 2) + 4 * 64) * sizeof(double);
-    const int units = (sdim * (FN_PG * sdim / 2) + 255) / 256;   // s = 20: 7
-    constexpr int units20 = (20 * (FN_PG * 20 / 2) + 255) / 256;
-    if (sdim == 20 && (ld & 1) == 0) {
+    const int units = (sdim * (FN_PG * sdim / 2) + 255) / 256;
+    // (ld is the padded order of the staged matrix, a multiple of GDCA_TILE = 128 at every caller: the 16-byte loads of both
+    // kernels rest on an even ld, and there is no form for an odd one)
+    if (sdim == 20) {
         const int total = fn20_first(N - 1, N);
         const int grid = std::min(total, FN20_WG * (ncu > 0 ? ncu : 256));
         (gdca_launch<k_fn20_args, k_fn20<1>, k_fn20<GDCA_MAXB>>(dim3((unsigned)grid), dim3(FN20_THREADS), 0, s, k_fn20_mk(A, ld, N, total, S)));
-    } else if (sdim == 20)
-        (gdca_launch<k_fn_args, k_fn<1, units20, 20>, k_fn<GDCA_MAXB, units20, 20>>(nwg, dim3(256), lds, s, k_fn_mk(A, ld, N, sdim, S)));
-    else if (units <= 4)
-        (gdca_launch<k_fn_args, k_fn<1, 4, 0>, k_fn<GDCA_MAXB, 4, 0>>(nwg, dim3(256), lds, s, k_fn_mk(A, ld, N, sdim, S)));
+    } else if (units <= 4)
+        (gdca_launch<k_fn_args, k_fn<1, 4>, k_fn<GDCA_MAXB, 4>>(nwg, dim3(256), lds, s, k_fn_mk(A, ld, N, sdim, S)));
     else if (units <= 7)
-        (gdca_launch<k_fn_args, k_fn<1, 7, 0>, k_fn<GDCA_MAXB, 7, 0>>(nwg, dim3(256), lds, s, k_fn_mk(A, ld, N, sdim, S)));
+        (gdca_launch<k_fn_args, k_fn<1, 7>, k_fn<GDCA_MAXB, 7>>(nwg, dim3(256), lds, s, k_fn_mk(A, ld, N, sdim, S)));
     else
-        (gdca_launch<k_fn_args, k_fn<1, 16, 0>, k_fn<GDCA_MAXB, 16, 0>>(nwg, dim3(256), lds, s, k_fn_mk(A, ld, N, sdim, S)));
+        (gdca_launch<k_fn_args, k_fn<1, 16>, k_fn<GDCA_MAXB, 16>>(nwg, dim3(256), lds, s, k_fn_mk(A, ld, N, sdim, S)));
 }
 
 // ---- Cholesky factors of the diagonal blocks of C ------------------------------------------------------
@@ -535,10 +532,13 @@ __global__ __launch_bounds__(64) void k_di_tridiag(const BatchArgs<k_di_tridiag_
         const int m = sdim - k - 1;                  // order of the trailing block V22 = V[k+1.., k+1..]
         const double *x = V + (k + 1) + k * sdim;    // x[t] = V(k+1+t, k)
         const double xt = (live && r < m) ? x[r] : 0.0;
-        const double sigma = half_sum(xt * xt);
         const double x0 = live ? x[0] : 0.0;
-        const double tail = sigma - x0 * x0;
-        const bool act = tail > 0.0 && sigma > 0.0;
+        // the tail x[1..] is summed on its own, never as sigma - x0^2: below 1.5e-8 of x0 that difference rounds to 0, the column
+        // counts as reduced and its small entries are dropped -- 1e-11 of error in DI where the reflector costs 1e-16
+        // (tests/test_gpu_score.py, the graded column)
+        const double tail = half_sum(r >= 1 ? xt * xt : 0.0);
+        const double sigma = tail + x0 * x0;
+        const bool act = tail > 0.0;
         const double alpha = act ? ((x0 >= 0.0) ? -sqrt(sigma) : sqrt(sigma)) : x0;  // x0: the column is already reduced
         const double v0 = x0 - alpha;
         const double beta = act ? 2.0 / (tail + v0 * v0) : 0.0;
