@@ -311,6 +311,21 @@ class Context:
         self.check(rc, st.info)
         return ii, jj, sc, st.as_dict()
 
+    # ---- read-outs of the fitted model: energies, pair energies, mutation scan ----
+    @staticmethod
+    def _opt(ptr):
+        """an address as a void pointer; None (an optional argument left out) stays NULL"""
+        return C.c_void_p(ptr) if ptr is not None else None
+
+    def _run_readout(self, fn, Z_ptr, N, M, q, pseudocount, theta, *rest):
+        """The frame of the fused read-outs: fn(ctx, Z, N, M, q, params, *rest, stats) with the read-outs' params (no contact score),
+        checked.  Returns the stats dict."""
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rc = fn(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm), *rest, C.byref(st))
+        self.check(rc, st.info)
+        return st.as_dict()
+
     # ---- energies of sequences under the fitted model (gdca_run_energies) ----
     def run_energies_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None, K: int = 0):
         """gdca_run_energies on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run() fits
@@ -318,21 +333,12 @@ class Context:
         Returns (E float64[K], stats)."""
         Ke = int(K) if X_ptr is not None else int(M)
         E = np.empty(max(Ke, 0), dtype=np.float64)
-        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
-        st = Stats()
-        rc = self.lib.gdca_run_energies(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
-                                        C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), _p(E), C.byref(st))
-        self.check(rc, st.info)
-        return E, st.as_dict()
+        return E, self._run_readout(self.lib.gdca_run_energies, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), _p(E))
 
     def run_energies_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int, E_ptr: int):
         """Device-pointer form (Z, X and E resident in HBM).  Returns the stats dict."""
-        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
-        st = Stats()
-        rc = self.lib.gdca_run_energies_dev(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
-                                            C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), C.c_void_p(E_ptr), C.byref(st))
-        self.check(rc, st.info)
-        return st.as_dict()
+        return self._run_readout(self.lib.gdca_run_energies_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                 C.c_void_p(E_ptr))
 
     def energies_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int, K: int, E_ptr: int) -> None:
         """gdca_energies_dev: mJ (n x n), Pi (n), X (N x K int8) and E (K) are device pointers."""
@@ -348,33 +354,21 @@ class Context:
         ka = int(KA) if XA_ptr is not None else int(M)
         kb = int(KB) if XB_ptr is not None else int(M)
         E = np.empty((max(ka, 0), max(kb, 0)), dtype=np.float64, order="F")
-        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
-        st = Stats()
-        rc = self.lib.gdca_run_pair_energies(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm), int(split),
-                                             C.c_void_p(XA_ptr) if XA_ptr is not None else None, int(KA),
-                                             C.c_void_p(XB_ptr) if XB_ptr is not None else None, int(KB), int(what), _p(E), C.byref(st))
-        self.check(rc, st.info)
-        return E, st.as_dict()
+        return E, self._run_readout(self.lib.gdca_run_pair_energies, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr),
+                                    int(KA), self._opt(XB_ptr), int(KB), int(what), _p(E))
 
     def run_pair_energies_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int, XA_ptr: int | None,
                               KA: int, XB_ptr: int | None, KB: int, what: int, E_ptr: int):
         """Device-pointer form (Z, XA, XB and E resident in HBM; E column-major KA x KB).  Returns the stats dict."""
-        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
-        st = Stats()
-        rc = self.lib.gdca_run_pair_energies_dev(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm), int(split),
-                                                 C.c_void_p(XA_ptr) if XA_ptr is not None else None, int(KA),
-                                                 C.c_void_p(XB_ptr) if XB_ptr is not None else None, int(KB), int(what), C.c_void_p(E_ptr),
-                                                 C.byref(st))
-        self.check(rc, st.info)
-        return st.as_dict()
+        return self._run_readout(self.lib.gdca_run_pair_energies_dev, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr),
+                                 int(KA), self._opt(XB_ptr), int(KB), int(what), C.c_void_p(E_ptr))
 
     def pair_energies_dev(self, mJ_ptr: int, Pi_ptr: int | None, N: int, q: int, split: int, XA_ptr: int, KA: int, XB_ptr: int, KB: int,
                           what: int, E_ptr: int) -> None:
         """gdca_pair_energies_dev: mJ (n x n), Pi (n; None for PAIR_COUPLING), XA (split x KA int8), XB ((N - split) x KB int8) and E
         (KA x KB, column-major) are device pointers."""
-        self.check(self.lib.gdca_pair_energies_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr) if Pi_ptr is not None else None, int(N),
-                                                   int(q), int(split), C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB), int(what),
-                                                   C.c_void_p(E_ptr)))
+        self.check(self.lib.gdca_pair_energies_dev(self.h, C.c_void_p(mJ_ptr), self._opt(Pi_ptr), int(N), int(q), int(split),
+                                                   C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB), int(what), C.c_void_p(E_ptr)))
 
     # ---- the energy change of every single substitution (gdca_run_mutation_scan) ----
     def run_mutation_scan_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None,
@@ -384,23 +378,14 @@ class Context:
         to symbol b (``what`` = MUT_DELTA), or the site potential V (MUT_POTENTIAL).  Returns (D float64 (K, N, q), stats)."""
         Ke = int(K) if X_ptr is not None else int(M)
         D = np.empty((max(Ke, 0), int(N), int(q)), dtype=np.float64)
-        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
-        st = Stats()
-        rc = self.lib.gdca_run_mutation_scan(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
-                                             C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), int(what), _p(D), C.byref(st))
-        self.check(rc, st.info)
-        return D, st.as_dict()
+        return D, self._run_readout(self.lib.gdca_run_mutation_scan, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                    int(what), _p(D))
 
     def run_mutation_scan_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int,
                               what: int, D_ptr: int):
         """Device-pointer form (Z, X and D resident in HBM; D holds q N K doubles).  Returns the stats dict."""
-        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
-        st = Stats()
-        rc = self.lib.gdca_run_mutation_scan_dev(self.h, C.c_void_p(Z_ptr), int(N), int(M), int(q), C.byref(prm),
-                                                 C.c_void_p(X_ptr) if X_ptr is not None else None, int(K), int(what), C.c_void_p(D_ptr),
-                                                 C.byref(st))
-        self.check(rc, st.info)
-        return st.as_dict()
+        return self._run_readout(self.lib.gdca_run_mutation_scan_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                 int(what), C.c_void_p(D_ptr))
 
     def mutation_scan_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int, K: int, what: int, D_ptr: int) -> None:
         """gdca_mutation_scan_dev: mJ (n x n), Pi (n), X (N x K int8) and D (q N K doubles, (K, N, q) row-major) are device pointers."""

@@ -58,6 +58,43 @@ static score_target contact_target(int score, int apc, double *S_dev)
     return t;
 }
 
+// The read-outs of the fused entries: X == NULL (XA / XB likewise) means the alignment's own M sequences -- for a pair target their
+// halves as they lie in Z (N x M), N bytes apart.
+static score_target energy_target(const int8_t *Z, int M, const int8_t *X, int K, double *E_dev)
+{
+    score_target t{};
+    t.kind = score_target::ENERGY;
+    t.out = E_dev;
+    t.X = X ? X : Z;
+    t.K = X ? K : M;
+    return t;
+}
+
+static score_target pair_target(const int8_t *Z, int N, int M, int split, const int8_t *XA, int KA, const int8_t *XB, int KB, int what,
+                                double *E_dev)
+{
+    score_target t{};
+    t.kind = score_target::PAIR;
+    t.out = E_dev;
+    t.split = split;
+    t.what = what;
+    t.XA = XA ? XA : Z;
+    t.strideA = XA ? (size_t)split : (size_t)N;
+    t.KA = XA ? KA : M;
+    t.XB = XB ? XB : Z + split;
+    t.strideB = XB ? (size_t)(N - split) : (size_t)N;
+    t.KB = XB ? KB : M;
+    return t;
+}
+
+static score_target mutation_target(const int8_t *Z, int M, const int8_t *X, int K, int what, double *D_dev)
+{
+    score_target t = energy_target(Z, M, X, K, D_dev);
+    t.kind = score_target::MUTATION;
+    t.what = what;
+    return t;
+}
+
 // The enqueued, not yet collected run (gdca_run_dev_async / gdca_run_collect): all a collect needs to know, grouped by who writes it.
 // The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev, operator_inverse_retry) borrows n, n_pad, timed and
 // at.attempt, so that it can go through run_inverses.
@@ -855,74 +892,72 @@ static gdca_status inverse_stage(gdca_ctx *ctx, int n, int n_pad, bool timed, in
     return check_launch(ctx, "spd_inverse");
 }
 
-// E[K] = 1/2 (x - Pi)' mJ (x - Pi) of the K sequences X (N x K) from the element-wise lower triangle of A (ld): mJ itself (sign +1: the
-// operator-level entry) or -mJ where the sweep left it (sign -1: ctx->A of the fused path).  Illegal bytes of X: sc->bad_symbol bit 2.
-static gdca_status energy_stage(gdca_ctx *ctx, const double *A, size_t ld, double sign, const double *Pi, int N, int q, const int8_t *X_dev,
-                                int K, double *E_dev)
+// What the energies and the mutation scan open with: the K sequences X (N x K) packed into ctx->Xg (illegal bytes: sc->bad_symbol
+// bit 2), g = mJ Pi in ctx->gvec and c0 = Pi' g behind it.
+static gdca_status pack_and_g(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K)
 {
-    hipStream_t s = ctx->stream;
-    const int sdim = q - 1, n = N * sdim;
-    const int nI = gdca_energy_blocks(N), nb = gdca_energy_gblocks(n), Kc = gdca_energy_chunk(N, K, ctx->tune.energy_chunk);
-    CHK(ensure(ctx, ctx->Xg, (size_t)nI * K * sizeof(uint32_t)));
-    CHK(ensure(ctx, ctx->Epart, (size_t)nI * Kc * sizeof(double)));
+    const int n = m.N * (m.q - 1), nb = gdca_energy_gblocks(n);
+    CHK(ensure(ctx, ctx->Xg, (size_t)gdca_energy_blocks(m.N) * K * sizeof(uint32_t)));
     CHK(ensure(ctx, ctx->gpart, (size_t)nb * nb * 64 * sizeof(double)));
     CHK(ensure(ctx, ctx->gvec, ((size_t)n + 1) * sizeof(double)));
-    double *g = (double *)ctx->gvec.p, *c0 = g + n;
-    gdca_launch_energy_pack(s, X_dev, (uint32_t *)ctx->Xg.p, N, K, q, (gdca_dev_scalars *)ctx->sc.p);
-    gdca_launch_energy_g(s, A, ld, sign, n, Pi, (double *)ctx->gpart.p, g, c0);
+    double *g = (double *)ctx->gvec.p;
+    gdca_launch_energy_pack(ctx->stream, X_dev, (size_t)m.N, m.N, K, m.q, (uint32_t *)ctx->Xg.p, (gdca_dev_scalars *)ctx->sc.p);
+    gdca_launch_energy_g(ctx->stream, m.A, m.ld, m.sign, n, m.Pi, (double *)ctx->gpart.p, g, g + n);
+    return GDCA_OK;
+}
+
+// E[K] = 1/2 (x - Pi)' mJ (x - Pi) of the K sequences X (N x K) under the model m.  Illegal bytes of X: sc->bad_symbol bit 2.
+static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, double *E_dev)
+{
+    const int sdim = m.q - 1, n = m.N * sdim;
+    const int Kc = gdca_energy_chunk(m.N, K, ctx->tune.energy_chunk);
+    CHK(ensure(ctx, ctx->Epart, (size_t)gdca_energy_blocks(m.N) * Kc * sizeof(double)));
+    CHK(pack_and_g(ctx, m, X_dev, K));
+    const double *g = (const double *)ctx->gvec.p;
     for (int k0 = 0; k0 < K; k0 += Kc)
-        gdca_launch_energy_rows(s, A, ld, sign, g, c0, (const uint32_t *)ctx->Xg.p, N, sdim, K, k0, std::min(Kc, K - k0), (double *)ctx->Epart.p,
-                                E_dev, ctx->ncu);
+        HIPCHK(gdca_launch_energy_rows(ctx->stream, m.A, m.ld, m.sign, g, g + n, (const uint32_t *)ctx->Xg.p, m.N, sdim, K, k0,
+                                       std::min(Kc, K - k0), (double *)ctx->Epart.p, E_dev, ctx->ncu));
     return check_launch(ctx, "energies");
 }
 
-// E[a + KA * b] of the KA x KB pairings a (+) b across the split (k_pair_energy.hip) from the element-wise lower triangle of A (ld, sign
-// as energy_stage).  XA / XB point at the first site of sequence 0's half; sequence k's starts strideA / strideB bytes on (so the
-// columns of an alignment serve as they lie).  what = GDCA_PAIR_ENERGY: the marginal energies through energy_stage on the gap-padded
-// halves (Pi needed), combined in the gather kernel's epilogue; GDCA_PAIR_COUPLING: R alone.  Illegal bytes: sc->bad_symbol bit 2.
-static gdca_status pair_stage(gdca_ctx *ctx, const double *A, size_t ld, double sign, const double *Pi, int N, int q, int split,
-                              const int8_t *XA, size_t strideA, int KA, const int8_t *XB, size_t strideB, int KB, int what, double *E_dev)
+// E[a + KA * b] of the KA x KB pairings a (+) b across the split (k_pair_energy.hip) under the model m.  XA / XB point at the first
+// site of sequence 0's half; sequence k's starts strideA / strideB bytes on (so the columns of an alignment serve as they lie).
+// what = GDCA_PAIR_ENERGY: the marginal energies through energy_stage on the gap-padded halves (m.Pi needed), combined in the gather
+// kernel's epilogue; GDCA_PAIR_COUPLING: R alone, no g.  Illegal bytes: sc->bad_symbol bit 2.
+static gdca_status pair_stage(gdca_ctx *ctx, const gdca_model &m, int split, const int8_t *XA, size_t strideA, int KA, const int8_t *XB,
+                              size_t strideB, int KB, int what, double *E_dev)
 {
     hipStream_t s = ctx->stream;
-    const int sdim = q - 1, n = N * sdim, nB = (N - split) * sdim;
+    const int N = m.N, q = m.q, sdim = q - 1, n = N * sdim, nB = (N - split) * sdim;
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    CHK(ensure(ctx, ctx->PXa, (size_t)gdca_pair_blocks(split) * KA * sizeof(uint32_t)));
-    CHK(ensure(ctx, ctx->PXb, (size_t)gdca_pair_blocks(N - split) * KB * sizeof(uint32_t)));
-    gdca_launch_pair_pack(s, XA, strideA, split, KA, q, (uint32_t *)ctx->PXa.p, sc);
-    gdca_launch_pair_pack(s, XB, strideB, N - split, KB, q, (uint32_t *)ctx->PXb.p, sc);
+    CHK(ensure(ctx, ctx->PXa, (size_t)gdca_energy_blocks(split) * KA * sizeof(uint32_t)));
+    CHK(ensure(ctx, ctx->PXb, (size_t)gdca_energy_blocks(N - split) * KB * sizeof(uint32_t)));
+    gdca_launch_energy_pack(s, XA, strideA, split, KA, q, (uint32_t *)ctx->PXa.p, sc);
+    gdca_launch_energy_pack(s, XB, strideB, N - split, KB, q, (uint32_t *)ctx->PXb.p, sc);
     const double *EAB = nullptr, *c0 = nullptr;
     if (what == GDCA_PAIR_ENERGY) {
         CHK(ensure(ctx, ctx->PXpad, (size_t)N * ((size_t)KA + (size_t)KB)));
         CHK(ensure(ctx, ctx->PEab, ((size_t)KA + (size_t)KB) * sizeof(double)));
         gdca_launch_pair_pad(s, XA, strideA, XB, strideB, N, split, KA, KB, q, (int8_t *)ctx->PXpad.p);
-        CHK(energy_stage(ctx, A, ld, sign, Pi, N, q, (const int8_t *)ctx->PXpad.p, KA + KB, (double *)ctx->PEab.p));
+        CHK(energy_stage(ctx, m, (const int8_t *)ctx->PXpad.p, KA + KB, (double *)ctx->PEab.p));
         EAB = (const double *)ctx->PEab.p;
         c0 = (const double *)ctx->gvec.p + n;
     }
     const int Ac = gdca_pair_chunk(nB, KA, ctx->tune.pair_chunk);
     CHK(ensure(ctx, ctx->PT, (size_t)Ac * nB * sizeof(double)));
     for (int a0 = 0; a0 < KA; a0 += Ac)
-        gdca_launch_pair_chunk(s, A, ld, sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim, KA, KB, a0,
-                               std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev, ctx->ncu);
+        HIPCHK(gdca_launch_pair_chunk(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim, KA, KB,
+                                      a0, std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev, ctx->ncu));
     return check_launch(ctx, "pair energies");
 }
 
 // D[(b - 1) + q (i + N k)]: the site potentials V (what = GDCA_MUT_POTENTIAL) or the energy changes dE (GDCA_MUT_DELTA) of every single
-// substitution of the K sequences X (N x K) (k_mutation.hip) from the element-wise lower triangle of A (ld, sign as energy_stage).  The
-// packed symbols and g live in the energy stage's buffers.  Illegal bytes of X: sc->bad_symbol bit 2.
-static gdca_status mutation_stage(gdca_ctx *ctx, const double *A, size_t ld, double sign, const double *Pi, int N, int q, const int8_t *X_dev,
-                                  int K, int what, double *D_dev)
+// substitution of the K sequences X (N x K) (k_mutation.hip) under the model m.  Illegal bytes of X: sc->bad_symbol bit 2.
+static gdca_status mutation_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, int what, double *D_dev)
 {
-    hipStream_t s = ctx->stream;
-    const int sdim = q - 1, n = N * sdim;
-    const int nI = gdca_energy_blocks(N), nb = gdca_energy_gblocks(n);
-    CHK(ensure(ctx, ctx->Xg, (size_t)nI * K * sizeof(uint32_t)));
-    CHK(ensure(ctx, ctx->gpart, (size_t)nb * nb * 64 * sizeof(double)));
-    CHK(ensure(ctx, ctx->gvec, ((size_t)n + 1) * sizeof(double)));
-    double *g = (double *)ctx->gvec.p;
-    gdca_launch_energy_pack(s, X_dev, (uint32_t *)ctx->Xg.p, N, K, q, (gdca_dev_scalars *)ctx->sc.p);
-    gdca_launch_energy_g(s, A, ld, sign, n, Pi, (double *)ctx->gpart.p, g, g + n);
-    HIPCHK(gdca_launch_mutation_scan(s, A, ld, sign, g, (const uint32_t *)ctx->Xg.p, N, sdim, K, what, D_dev, ctx->ncu));
+    CHK(pack_and_g(ctx, m, X_dev, K));
+    HIPCHK(gdca_launch_mutation_scan(ctx->stream, m.A, m.ld, m.sign, (const double *)ctx->gvec.p, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K,
+                                     what, D_dev, ctx->ncu));
     return check_launch(ctx, "mutation scan");
 }
 
@@ -930,14 +965,14 @@ static gdca_status mutation_stage(gdca_ctx *ctx, const double *A, size_t ld, dou
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t, bool time_fn = false)
 {
     hipStream_t s = ctx->stream;
-    if (t.kind == score_target::MUTATION)  // gdca_run_mutation_scan: the model is scanned for every single substitution of X
-        return mutation_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, t.X, t.K, t.what,
-                              t.out);
-    if (t.kind == score_target::PAIR)  // gdca_run_pair_energies: the model is scored on the pairings across the split
-        return pair_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, t.split, t.XA, t.strideA,
-                          t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
-    if (t.kind == score_target::ENERGY)  // gdca_run_energies: the model is scored on X instead of being turned into a contact score
-        return energy_stage(ctx, (const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1, t.X, t.K, t.out);
+    // the model as the sweep left it, for the fused read-outs: scored on t's sequences in the place of the contact score
+    const gdca_model m{(const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1};
+    switch (t.kind) {
+    case score_target::ENERGY: return energy_stage(ctx, m, t.X, t.K, t.out);
+    case score_target::PAIR: return pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
+    case score_target::MUTATION: return mutation_stage(ctx, m, t.X, t.K, t.what, t.out);
+    case score_target::CONTACT: break;
+    }
     double *S_dev = t.out;
     if (t.score == GDCA_SCORE_DI) {
         CHK(ensure(ctx, ctx->Tws, gdca_di_ws_bytes(N, sdim)));
@@ -2370,13 +2405,16 @@ gdca_status gdca_di_dev(gdca_ctx *ctx, const double *mJ_dev, const double *C_dev
     return GDCA_OK;
 }
 
-gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev, int32_t K,
-                              double *E_dev)
+// ---- the model read-outs: operator forms (the caller's mJ_dev / Pi_dev) and fused forms (run_target) ----
+// an operator's model: mJ itself, dense n x n
+static gdca_model operator_model(const double *mJ_dev, const double *Pi_dev, int N, int q)
 {
-    CHK(validate(ctx, N, K, q));
-    if (!mJ_dev || !Pi_dev || !X_dev || !E_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    CHK(begin(ctx));
-    CHK(energy_stage(ctx, mJ_dev, (size_t)N * (q - 1), 1.0, Pi_dev, N, q, X_dev, K, E_dev));
+    return gdca_model{mJ_dev, (size_t)N * (q - 1), 1.0, Pi_dev, N, q};
+}
+
+// how the operator forms end: the stage's flags fetched, an illegal byte among the sequences reported
+static gdca_status sequences_checked(gdca_ctx *ctx)
+{
     CHK(fetch_scalars(ctx));
     if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
     return GDCA_OK;
@@ -2398,18 +2436,23 @@ static gdca_status run_target(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int
     return gdca_run_collect(ctx, st);
 }
 
+gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev, int32_t K,
+                              double *E_dev)
+{
+    CHK(validate(ctx, N, K, q));
+    if (!mJ_dev || !Pi_dev || !X_dev || !E_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(begin(ctx));
+    CHK(energy_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, E_dev));
+    return sequences_checked(ctx);
+}
+
 gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                   const int8_t *X_dev, int32_t K, double *E_dev, gdca_stats *st)
 {
     CHK(validate(ctx, N, M, q));
     if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     if (X_dev && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    score_target t{};
-    t.kind = score_target::ENERGY;
-    t.out = E_dev;
-    t.X = X_dev ? X_dev : Z_dev;
-    t.K = X_dev ? K : M;
-    return run_target(ctx, Z_dev, N, M, q, p, t, st);
+    return run_target(ctx, Z_dev, N, M, q, p, energy_target(Z_dev, M, X_dev, K, E_dev), st);
 }
 
 // the argument checks the four pair entry points share (nothing has run when one fails); KA / KB as they will be used
@@ -2429,11 +2472,8 @@ gdca_status gdca_pair_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const do
     if (!mJ_dev || !XA_dev || !XB_dev || !E_dev || (what == GDCA_PAIR_ENERGY && !Pi_dev))
         return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     CHK(begin(ctx));
-    CHK(pair_stage(ctx, mJ_dev, (size_t)N * (q - 1), 1.0, Pi_dev, N, q, split, XA_dev, (size_t)split, KA, XB_dev, (size_t)(N - split), KB, what,
-                   E_dev));
-    CHK(fetch_scalars(ctx));
-    if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
-    return GDCA_OK;
+    CHK(pair_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), split, XA_dev, (size_t)split, KA, XB_dev, (size_t)(N - split), KB, what, E_dev));
+    return sequences_checked(ctx);
 }
 
 gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
@@ -2443,18 +2483,7 @@ gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
     CHK(validate(ctx, N, M, q));
     CHK(validate_pair(ctx, N, q, split, XA_dev ? KA : M, XB_dev ? KB : M, what));
     if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    score_target t{};
-    t.kind = score_target::PAIR;
-    t.out = E_dev;
-    t.split = split;
-    t.what = what;
-    t.XA = XA_dev ? XA_dev : Z_dev;  // (the A halves of Z's own sequences lie N bytes apart)
-    t.strideA = XA_dev ? (size_t)split : (size_t)N;
-    t.KA = XA_dev ? KA : M;
-    t.XB = XB_dev ? XB_dev : Z_dev + split;
-    t.strideB = XB_dev ? (size_t)(N - split) : (size_t)N;
-    t.KB = XB_dev ? KB : M;
-    return run_target(ctx, Z_dev, N, M, q, p, t, st);
+    return run_target(ctx, Z_dev, N, M, q, p, pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, what, E_dev), st);
 }
 
 // the argument checks the four mutation-scan entry points share (nothing has run when one fails); K as it will be used
@@ -2473,10 +2502,8 @@ gdca_status gdca_mutation_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const do
     CHK(validate_mutation(ctx, N, q, K, what));
     if (!mJ_dev || !Pi_dev || !X_dev || !D_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     CHK(begin(ctx));
-    CHK(mutation_stage(ctx, mJ_dev, (size_t)N * (q - 1), 1.0, Pi_dev, N, q, X_dev, K, what, D_dev));
-    CHK(fetch_scalars(ctx));
-    if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
-    return GDCA_OK;
+    CHK(mutation_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, what, D_dev));
+    return sequences_checked(ctx);
 }
 
 gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
@@ -2485,13 +2512,7 @@ gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
     CHK(validate(ctx, N, M, q));
     CHK(validate_mutation(ctx, N, q, X_dev ? K : M, what));
     if (!Z_dev || !D_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    score_target t{};
-    t.kind = score_target::MUTATION;
-    t.out = D_dev;
-    t.X = X_dev ? X_dev : Z_dev;
-    t.K = X_dev ? K : M;
-    t.what = what;
-    return run_target(ctx, Z_dev, N, M, q, p, t, st);
+    return run_target(ctx, Z_dev, N, M, q, p, mutation_target(Z_dev, M, X_dev, K, what, D_dev), st);
 }
 
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
@@ -2655,19 +2676,36 @@ gdca_status gdca_apc(gdca_ctx *ctx, double *S, int32_t N)
     return to_host(ctx, S, ctx->scratch[2], (size_t)N * N * sizeof(double));
 }
 
+// The staging of the model read-outs' host-pointer forms: a host array into scratch slot `slot`, its device address returned; nullptr
+// for an absent optional one (host == nullptr), and where an upload has failed (*st then says why; later uploads do nothing)
+static const void *upload(gdca_ctx *ctx, int slot, const void *host, size_t bytes, gdca_status *st)
+{
+    if (!host || *st != GDCA_OK) return nullptr;
+    *st = to_dev(ctx, ctx->scratch[slot], host, bytes);
+    return *st == GDCA_OK ? ctx->scratch[slot].p : nullptr;
+}
+
+// ... and room for their result in scratch slot `slot` (nothing is done once *st holds an error)
+static double *staged_out(gdca_ctx *ctx, int slot, size_t bytes, gdca_status *st)
+{
+    if (*st == GDCA_OK) *st = ensure(ctx, ctx->scratch[slot], bytes);
+    return *st == GDCA_OK ? (double *)ctx->scratch[slot].p : nullptr;
+}
+
 gdca_status gdca_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K, double *E)
 {
     CHK(validate(ctx, N, K, q));
     if (!mJ || !Pi || !X || !E) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)N * (q - 1);
-    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[2], Pi, n * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[0], X, (size_t)N * K));
-    CHK(ensure(ctx, ctx->scratch[3], (size_t)K * sizeof(double)));
-    CHK(gdca_energies_dev(ctx, (const double *)ctx->scratch[1].p, (const double *)ctx->scratch[2].p, N, q, (const int8_t *)ctx->scratch[0].p, K,
-                          (double *)ctx->scratch[3].p));
-    return to_host(ctx, E, ctx->scratch[3], (size_t)K * sizeof(double));
+    const size_t n = (size_t)N * (q - 1), ne = (size_t)K * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
+    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
+    double *E_dev = staged_out(ctx, 3, ne, &up);
+    CHK(up);
+    CHK(gdca_energies_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, E_dev));
+    return to_host(ctx, E, ctx->scratch[3], ne);
 }
 
 gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, const int8_t *X_host,
@@ -2677,13 +2715,14 @@ gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, in
     if (!Z_host || !E_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     if (X_host && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
     HIPCHK(hipSetDevice(ctx->device));
-    const int Ke = X_host ? K : M;
-    CHK(to_dev(ctx, ctx->scratch[0], Z_host, (size_t)N * M));
-    if (X_host) CHK(to_dev(ctx, ctx->scratch[3], X_host, (size_t)N * K));
-    CHK(ensure(ctx, ctx->scratch[5], (size_t)Ke * sizeof(double)));
-    CHK(gdca_run_energies_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, X_host ? (const int8_t *)ctx->scratch[3].p : nullptr, K,
-                              (double *)ctx->scratch[5].p, st));
-    return to_host(ctx, E_host, ctx->scratch[5], (size_t)Ke * sizeof(double));
+    const size_t ne = (size_t)(X_host ? K : M) * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
+    double *E_dev = staged_out(ctx, 5, ne, &up);
+    CHK(up);
+    CHK(gdca_run_energies_dev(ctx, Z_dev, N, M, q, p, X_dev, K, E_dev, st));
+    return to_host(ctx, E_host, ctx->scratch[5], ne);
 }
 
 gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split, const int8_t *XA,
@@ -2693,13 +2732,14 @@ gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi
     if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)N * (q - 1), ne = (size_t)KA * (size_t)KB * sizeof(double);
-    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
-    if (Pi) CHK(to_dev(ctx, ctx->scratch[2], Pi, n * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[0], XA, (size_t)split * KA));
-    CHK(to_dev(ctx, ctx->scratch[3], XB, (size_t)(N - split) * KB));
-    CHK(ensure(ctx, ctx->scratch[5], ne));
-    CHK(gdca_pair_energies_dev(ctx, (const double *)ctx->scratch[1].p, Pi ? (const double *)ctx->scratch[2].p : nullptr, N, q, split,
-                               (const int8_t *)ctx->scratch[0].p, KA, (const int8_t *)ctx->scratch[3].p, KB, what, (double *)ctx->scratch[5].p));
+    gdca_status up = GDCA_OK;
+    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
+    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 0, XA, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 3, XB, (size_t)(N - split) * KB, &up);
+    double *E_dev = staged_out(ctx, 5, ne, &up);
+    CHK(up);
+    CHK(gdca_pair_energies_dev(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, what, E_dev));
     return to_host(ctx, E, ctx->scratch[5], ne);
 }
 
@@ -2712,13 +2752,13 @@ gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
     if (!Z_host || !E_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t ne = (size_t)(XA_host ? KA : M) * (size_t)(XB_host ? KB : M) * sizeof(double);
-    CHK(to_dev(ctx, ctx->scratch[0], Z_host, (size_t)N * M));
-    if (XA_host) CHK(to_dev(ctx, ctx->scratch[3], XA_host, (size_t)split * KA));
-    if (XB_host) CHK(to_dev(ctx, ctx->scratch[4], XB_host, (size_t)(N - split) * KB));
-    CHK(ensure(ctx, ctx->scratch[5], ne));
-    CHK(gdca_run_pair_energies_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, split,
-                                   XA_host ? (const int8_t *)ctx->scratch[3].p : nullptr, KA, XB_host ? (const int8_t *)ctx->scratch[4].p : nullptr,
-                                   KB, what, (double *)ctx->scratch[5].p, st));
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
+    double *E_dev = staged_out(ctx, 5, ne, &up);
+    CHK(up);
+    CHK(gdca_run_pair_energies_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, what, E_dev, st));
     return to_host(ctx, E_host, ctx->scratch[5], ne);
 }
 
@@ -2729,12 +2769,13 @@ gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi
     if (!mJ || !Pi || !X || !D) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)N * (q - 1), nd = (size_t)q * (size_t)N * (size_t)K * sizeof(double);
-    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[2], Pi, n * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[0], X, (size_t)N * K));
-    CHK(ensure(ctx, ctx->scratch[5], nd));
-    CHK(gdca_mutation_scan_dev(ctx, (const double *)ctx->scratch[1].p, (const double *)ctx->scratch[2].p, N, q, (const int8_t *)ctx->scratch[0].p,
-                               K, what, (double *)ctx->scratch[5].p));
+    gdca_status up = GDCA_OK;
+    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
+    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
+    double *D_dev = staged_out(ctx, 5, nd, &up);
+    CHK(up);
+    CHK(gdca_mutation_scan_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, what, D_dev));
     return to_host(ctx, D, ctx->scratch[5], nd);
 }
 
@@ -2746,11 +2787,12 @@ gdca_status gdca_run_mutation_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
     if (!Z_host || !D_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t nd = (size_t)q * (size_t)N * (size_t)(X_host ? K : M) * sizeof(double);
-    CHK(to_dev(ctx, ctx->scratch[0], Z_host, (size_t)N * M));
-    if (X_host) CHK(to_dev(ctx, ctx->scratch[3], X_host, (size_t)N * K));
-    CHK(ensure(ctx, ctx->scratch[5], nd));
-    CHK(gdca_run_mutation_scan_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, X_host ? (const int8_t *)ctx->scratch[3].p : nullptr, K,
-                                   what, (double *)ctx->scratch[5].p, st));
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
+    double *D_dev = staged_out(ctx, 5, nd, &up);
+    CHK(up);
+    CHK(gdca_run_mutation_scan_dev(ctx, Z_dev, N, M, q, p, X_dev, K, what, D_dev, st));
     return to_host(ctx, D_host, ctx->scratch[5], nd);
 }
 

@@ -229,37 +229,48 @@ void gdca_launch_di(hipStream_t s, const double *A, size_t ld, const double *Ld,
                     double *Tws, gdca_dev_scalars *sc);
 void gdca_launch_apc(hipStream_t s, double *S, int N, double *rowsum_ws);
 
+// ---- the model read-outs (k_energy.hip, k_pair_energy.hip, k_mutation.hip) ------------------------------------------------------------
+// The fitted model as the read-outs see it: mJ (sign +1) or -mJ (sign -1) in the element-wise lower triangle of A -- element (row,
+// col), row >= col, at A[col * ld + row] -- and Pi, the n = N (q - 1) single-site frequencies with pseudocount.  Made in two places
+// (gdca_api.hip): from the sweep's storage of a fused run and from an operator's mJ_dev / Pi_dev.
+struct gdca_model {
+    const double *A;
+    size_t ld;
+    double sign;
+    const double *Pi;
+    int N, q;
+};
+
 // ---- k_energy.hip: E(x) = 1/2 (x - Pi)' mJ (x - Pi) of K sequences ---------------------------------------------------------------
-int gdca_energy_blocks(int N);        // site blocks (of four sites) of the gather kernel
+int gdca_energy_blocks(int Ns);       // site blocks (of four sites = one packed dword) of Ns sites
 int gdca_energy_gblocks(int n);       // 64-blocks of the g pass
 int gdca_energy_chunk(int N, int K, int wanted);  // sequences one launch of the gather kernel takes (wanted > 0: that many)
-// Xg: uint32 [gdca_energy_blocks(N)][K]; bytes of X outside 1..q set bit 2 of sc->bad_symbol (and count as gaps)
-void gdca_launch_energy_pack(hipStream_t s, const int8_t *X, uint32_t *Xg, int N, int K, int q, gdca_dev_scalars *sc);
+// Xg: uint32 [gdca_energy_blocks(Ns)][K] from the Ns sites X points at (sequence k: X + k * stride; whole sequences: stride = Ns = N);
+// bytes outside 1..q set bit 2 of sc->bad_symbol (and count as gaps)
+void gdca_launch_energy_pack(hipStream_t s, const int8_t *X, size_t stride, int Ns, int K, int q, uint32_t *Xg, gdca_dev_scalars *sc);
 // g = mJ Pi (n entries) and c0 = Pi' g from the element-wise lower triangle of A (ld; sign -1: A holds -mJ, the sweep's storage);
 // part: nb x (nb * 64) doubles, nb = gdca_energy_gblocks(n)
 void gdca_launch_energy_g(hipStream_t s, const double *A, size_t ld, double sign, int n, const double *Pi, double *part, double *g,
                           double *c0);
-// E[k0 .. k0 + Kc - 1]; part: gdca_energy_blocks(N) x Kc doubles
-void gdca_launch_energy_rows(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const double *c0, const uint32_t *Xg,
-                             int N, int sdim, int K, int k0, int Kc, double *part, double *E, int ncu);
+// E[k0 .. k0 + Kc - 1]; part: gdca_energy_blocks(N) x Kc doubles.  An error (here and below): the dynamic LDS limit could not be raised
+// for a kernel's tile; that kernel was not launched
+hipError_t gdca_launch_energy_rows(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const double *c0,
+                                   const uint32_t *Xg, int N, int sdim, int K, int k0, int Kc, double *part, double *E, int ncu);
 
 // ---- k_pair_energy.hip: E(a (+) b) of K_A x K_B pairings across a split alignment -------------------------------------------------------
-int gdca_pair_blocks(int Ns);                       // site blocks (of four sites) of a packed range of Ns sites
 int gdca_pair_chunk(int nB, int KA, int wanted);    // sequences a one launch of the fold / gather kernels takes (wanted > 0: that many)
-// out: uint32 [gdca_pair_blocks(Ns)][K] from the Ns sites X points at (sequence k: X + k * stride); bytes outside 1..q set bit 2 of
-// sc->bad_symbol (and count as gaps)
-void gdca_launch_pair_pack(hipStream_t s, const int8_t *X, size_t stride, int Ns, int K, int q, uint32_t *out, gdca_dev_scalars *sc);
 // Xp (N x (KA + KB)): a (+) gaps for the KA sequences of XA (split sites each), then gaps (+) b for the KB of XB (N - split sites each)
 void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const int8_t *XB, size_t strideB, int N, int split, int KA, int KB,
                           int q, int8_t *Xp);
 // E[a + KA * b], a0 <= a < a0 + Ac, all b, from the block rows >= split * sdim, columns < split * sdim of A (ld; sign -1: A holds -mJ);
-// T: Ac x (N - split) * sdim doubles.  EAB (KA + KB marginal energies) and c0: the energy; EAB == nullptr: the coupling R alone
-void gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N, int split,
-                            int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E, int ncu);
+// XAg / XBg: the halves packed by gdca_launch_energy_pack; T: Ac x (N - split) * sdim doubles.  EAB (KA + KB marginal energies) and c0:
+// the energy; EAB == nullptr: the coupling R alone
+hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N,
+                                  int split, int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E,
+                                  int ncu);
 
 // ---- k_mutation.hip: V(x; i, c) / dE(x; i, b) of every single substitution of K sequences ------------------------------------------------
 // D[(b - 1) + q (i + N k)] (q = sdim + 1; what: GDCA_MUT_DELTA | GDCA_MUT_POTENTIAL) of the K sequences packed by gdca_launch_energy_pack
-// (Xg) from the element-wise lower triangle of A (ld; sign -1: A holds -mJ) and g = mJ Pi (gdca_launch_energy_g).  An error: the
-// dynamic LDS limit could not be raised for the tile, nothing was launched
+// (Xg) from the element-wise lower triangle of A (ld; sign -1: A holds -mJ) and g = mJ Pi (gdca_launch_energy_g)
 hipError_t gdca_launch_mutation_scan(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const uint32_t *Xg, int N, int sdim,
                                int K, int what, double *D, int ncu);

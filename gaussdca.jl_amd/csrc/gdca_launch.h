@@ -165,6 +165,19 @@ inline void gdca_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const 
         hipLaunchKernelGGL(__VA_ARGS__); \
     } while (0)
 
+// ---- what the launchers of the model read-outs (k_energy.hip, k_pair_energy.hip, k_mutation.hip) share -------------------------------
+// A gather kernel has a wide and a narrow instance: the wide one, unless its workgroups (`items` in steps of `per_wide`, times the
+// grid's other dimension) would be fewer than two a compute unit.  (items may be anything up to INT32_MAX: 64-bit counts)
+inline bool gdca_wide_instance(long long items, int per_wide, int other, int ncu)
+{
+    return (items + per_wide - 1) / per_wide * other >= 2 * ncu;
+}
+// a kernel whose dynamic LDS is beyond 48 KB has its limit raised first; an error: refused, launch nothing
+inline hipError_t gdca_raise_lds_limit(const void *kern, size_t lds)
+{
+    return lds > 48 * 1024 ? hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
+
 // stream operations of the host code in their recordable forms (gdca_api.hip): a fill of 32-bit words, a device time stamp
 void gdca_fill_async(hipStream_t s, void *p, int byte_value, size_t bytes);
 struct gdca_dev_scalars;

@@ -15,7 +15,8 @@
 // Per sequence that is a gather of N^2 / 2 doubles from a matrix that fits no cache, so the gathers are turned into LDS reads:
 //   k_energy_pack   X [K][N] -> Xg [ceil(N / 4)][K] dwords: the four symbols of a site block as LDS row indices a - 1 (gap, a site
 //                   beyond N and an illegal byte -> s, a row of zeros); illegal bytes are flagged (sc->bad_symbol bit 2) HERE, so
-//                   nothing downstream can index out of bounds;
+//                   nothing downstream can index out of bounds (the one pack kernel: the pair energies and the mutation scan
+//                   pack with it too, the former a range of sites with a stride of its own);
 //   k_energy_gtile / _gfin / _c0   g and c0 in one streaming pass over the lower triangle (64 x 64 tiles, each giving its rows' and,
 //                   transposed, its columns' partial products; partials summed in tile order);
 //   k_energy_rows   a workgroup owns site block I (4 sites) and 256 x SEQ sequences; it walks the tiles (I, J), J = 0 .. I, of the
@@ -34,9 +35,11 @@
 #define ESEQ_NARROW 2  // ... and where that would leave compute units without a workgroup (small N or K)
 #define GT 64        // tile edge of the g pass
 
-// ---- X -> packed LDS row indices, with the symbol check ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_energy_pack(const int8_t *__restrict__ X, uint32_t *__restrict__ Xg, int N, int K, int q,
-                                                     gdca_dev_scalars *sc)
+// ---- Ns sites of X -> packed LDS row indices, with the symbol check ---------------------------------------------------------------
+// X points at the first site of the range in sequence 0; sequence k starts `stride` bytes on (whole sequences: stride = Ns = N; a
+// half of a split alignment, k_pair_energy.hip: its own site count, and Z's own columns serve as they lie with stride N)
+__global__ __launch_bounds__(256) void k_energy_pack(const int8_t *__restrict__ X, size_t stride, int Ns, int K, int q,
+                                                     uint32_t *__restrict__ Xg, gdca_dev_scalars *sc)
 {
     const int k = blockIdx.x * 256 + threadIdx.x, blk = blockIdx.y;
     if (k >= K) return;
@@ -47,8 +50,8 @@ __global__ __launch_bounds__(256) void k_energy_pack(const int8_t *__restrict__ 
     for (int l = 0; l < ET; ++l) {
         const int i = blk * ET + l;
         int idx = sdim;
-        if (i < N) {
-            const int a = X[(size_t)k * N + i];
+        if (i < Ns) {
+            const int a = X[(size_t)k * stride + i];
             if (a < 1 || a > q)
                 bad = true;
             else
@@ -249,9 +252,9 @@ __global__ __launch_bounds__(256) void k_energy_final(const double *__restrict__
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------
-int gdca_energy_blocks(int N)
+int gdca_energy_blocks(int Ns)
 {
-    return (N + ET - 1) / ET;
+    return (Ns + ET - 1) / ET;
 }
 
 int gdca_energy_gblocks(int n)
@@ -270,9 +273,9 @@ int gdca_energy_chunk(int N, int K, int wanted)
     return (int)(kc < K ? kc : K);
 }
 
-void gdca_launch_energy_pack(hipStream_t s, const int8_t *X, uint32_t *Xg, int N, int K, int q, gdca_dev_scalars *sc)
+void gdca_launch_energy_pack(hipStream_t s, const int8_t *X, size_t stride, int Ns, int K, int q, uint32_t *Xg, gdca_dev_scalars *sc)
 {
-    GDCA_LAUNCH_DIRECT(k_energy_pack, dim3((K + 255) / 256, gdca_energy_blocks(N)), dim3(256), 0, s, X, Xg, N, K, q, sc);
+    GDCA_LAUNCH_DIRECT(k_energy_pack, dim3((K + 255) / 256, gdca_energy_blocks(Ns)), dim3(256), 0, s, X, stride, Ns, K, q, Xg, sc);
 }
 
 // g (n entries) and c0 (one) from the lower triangle of A (ld; sign -1: A holds -mJ); part: nb x (nb * 64) doubles, nb = gdca_energy_gblocks(n)
@@ -286,8 +289,9 @@ void gdca_launch_energy_g(hipStream_t s, const double *A, size_t ld, double sign
     GDCA_LAUNCH_DIRECT(k_energy_c0, dim3(1), dim3(256), 0, s, Pi, g, n, c0);
 }
 
-// E[k0 .. k0 + Kc - 1] of the packed sequences Xg ([nI][K]); part: nI x Kc doubles
-void gdca_launch_energy_rows(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const double *c0, const uint32_t *Xg,
+// E[k0 .. k0 + Kc - 1] of the packed sequences Xg ([nI][K]); part: nI x Kc doubles.  An error: the dynamic LDS limit could not be
+// raised for the tile (s >= 21), nothing was launched
+hipError_t gdca_launch_energy_rows(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const double *c0, const uint32_t *Xg,
                              int N, int sdim, int K, int k0, int Kc, double *part, double *E, int ncu)
 {
     const int nI = gdca_energy_blocks(N);
@@ -295,13 +299,14 @@ void gdca_launch_energy_rows(hipStream_t s, const double *A, size_t ld, double s
     const int TD = ET * (sdim + 1);
     const size_t lds = (size_t)(TD * TD + TD) * sizeof(double);
     // eight sequences a thread -- or two, where eight would give fewer than two workgroups a compute unit (small N or K)
-    const bool wide = (long long)((Kc + 256 * ESEQ_WIDE - 1) / (256 * ESEQ_WIDE)) * nI >= 2 * ncu;
+    const bool wide = gdca_wide_instance(Kc, 256 * ESEQ_WIDE, nI, ncu);
     const int per = 256 * (wide ? ESEQ_WIDE : ESEQ_NARROW);
     const dim3 grid((Kc + per - 1) / per, nI);
     void (*kern)(k_energy_rows_args) = sdim == 20 ? (wide ? k_energy_rows<20, ESEQ_WIDE> : k_energy_rows<20, ESEQ_NARROW>)
                                                   : (wide ? k_energy_rows<0, ESEQ_WIDE> : k_energy_rows<0, ESEQ_NARROW>);
-    // (as gdca_issue does for the batched kernels: a refusal shows up as the launch's own error, which the caller's check_launch reports)
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    if (e != hipSuccess) return e;
     GDCA_LAUNCH_DIRECT(kern, grid, dim3(256), lds, s, a);
     GDCA_LAUNCH_DIRECT(k_energy_final, dim3((Kc + 255) / 256), dim3(256), 0, s, part, Kc, nI, c0, E + k0);
+    return hipSuccess;
 }

@@ -175,16 +175,13 @@ hipError_t gdca_launch_mutation_scan(hipStream_t s, const double *A, size_t ld, 
     const k_mut_args a{A, ld, sign, g, Xg, D, N, sdim, N * sdim, K, what};
     const int spb = 64 / sdim, nR = (N + spb - 1) / spb;
     // 128 sequences a workgroup -- or 16, where 128 would give fewer than two workgroups a compute unit
-    // (K may be anything up to INT32_MAX: the counts of workgroups in 64 bits)
-    const bool wide = (((long long)K + 4 * MAU_WIDE - 1) / (4 * MAU_WIDE)) * nR >= 2 * ncu;
+    const bool wide = gdca_wide_instance(K, 4 * MAU_WIDE, nR, ncu);
     const int per = 4 * (wide ? MAU_WIDE : MAU_NARROW);
     const size_t lds = (size_t)MT * (sdim + 1) * MLD * sizeof(double);
     void (*kern)(k_mut_args) = sdim == 20 ? (wide ? k_mut_rows<20, MAU_WIDE> : k_mut_rows<20, MAU_NARROW>)
                                           : (wide ? k_mut_rows<0, MAU_WIDE> : k_mut_rows<0, MAU_NARROW>);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    if (e != hipSuccess) return e;
     // (the sequence chunks run fastest: the workgroups that share a row block walk the same tiles at the same time)
     GDCA_LAUNCH_DIRECT(kern, dim3((unsigned)(((long long)K + per - 1) / per), nR), dim3(256), lds, s, a);
     return hipSuccess;

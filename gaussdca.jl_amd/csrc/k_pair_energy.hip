@@ -12,9 +12,7 @@
 // the sign flipped: `sign` = -1, ld = n_pad; the operator form: sign +1, ld = n).  Nothing else of mJ is read here.
 //
 // Materialising the K_A K_B concatenations costs N^2 / 2 gathers a pair; here a pair costs N_B:
-//   k_pair_pack    the symbols of a range of sites of X (column stride given: an alignment's own columns serve as they lie) -> dwords
-//                  [ceil(Ns / 4)][K] of row indices a - 1 (gap, a site beyond the range and an illegal byte -> s, a row of zeros);
-//                  illegal bytes are flagged (sc->bad_symbol bit 2) HERE, so nothing downstream can index out of bounds;
+//   k_energy_pack  (k_energy.hip) the symbols of each half's range of sites, dwords [ceil(Ns / 4)][K], with the symbol check;
 //   k_pair_pad     a (+) gaps and gaps (+) b as N x (K_A + K_B) sequences for the energy stage;
 //   k_pair_fold    T[a][row] = sum_{i in A} sign A[n_A + row, r_a(i)] over the n_B rows of the block: a workgroup owns 64 rows and
 //                  4 x AU sequences; it walks the A site blocks (4 sites), tile -> LDS as 4 (s + 1) columns of 64 rows (42 KB at
@@ -31,7 +29,7 @@
 #include "gdca_internal.h"
 #include "gdca_launch.h"
 
-#define PT 4          // sites per tile of k_pair_fold (= symbols per packed dword)
+#define PT 4          // sites per tile of k_pair_fold (= symbols per packed dword: k_energy_pack's four)
 #define PROWS 64      // rows of the block per workgroup of k_pair_fold
 #define PAU_WIDE 32   // sequences a per wave of k_pair_fold ...
 #define PAU_NARROW 4  // ... and where that would leave compute units without a workgroup
@@ -39,33 +37,6 @@
 #define PBU_WIDE 2    // sequences b per thread of k_pair_gather / where that would leave compute units without a workgroup
 #define PBU_NARROW 1
 #define PSEG_ROWS 1020  // T rows per LDS segment of k_pair_gather: (1020 + 1) x 8 doubles = 63.8 KB, two workgroups a compute unit
-
-// ---- X[site0 .. site0 + Ns - 1] -> packed row indices, with the symbol check ---------------------------------------------------------
-// X points at the first site of the range in sequence 0; sequence k starts `stride` bytes on
-__global__ __launch_bounds__(256) void k_pair_pack(const int8_t *__restrict__ X, size_t stride, int Ns, int K, int q,
-                                                   uint32_t *__restrict__ out, gdca_dev_scalars *sc)
-{
-    const int k = blockIdx.x * 256 + threadIdx.x, blk = blockIdx.y;
-    if (k >= K) return;
-    const int sdim = q - 1;
-    uint32_t w = 0;
-    bool bad = false;
-#pragma unroll
-    for (int l = 0; l < PT; ++l) {
-        const int i = blk * PT + l;
-        int idx = sdim;
-        if (i < Ns) {
-            const int a = X[(size_t)k * stride + i];
-            if (a < 1 || a > q)
-                bad = true;
-            else
-                idx = a - 1;
-        }
-        w |= (uint32_t)idx << (8 * l);
-    }
-    out[(size_t)blk * K + k] = w;
-    if (bad) atomicOr(&sc->bad_symbol, 4);
-}
 
 // Xp (N x (KA + KB)): sequence k < KA = a_k (+) gaps, sequence KA + k = gaps (+) b_k (bytes copied as they are: the energy stage's own
 // pack flags an illegal one)
@@ -220,11 +191,6 @@ __global__ __launch_bounds__(256) void k_pair_gather(const k_pair_gather_args p)
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------
-int gdca_pair_blocks(int Ns)
-{
-    return (Ns + PT - 1) / PT;
-}
-
 // sequences a one launch of the fold / gather kernels takes: a multiple of the fold workgroup's 4 x PAU_WIDE whose T stays within
 // ~256 MB, at most 32768 (wanted > 0: option PAIR_CHUNK, any SMALLER count -- tests; it never raises the buffer beyond the rule)
 int gdca_pair_chunk(int nB, int KA, int wanted)
@@ -237,11 +203,6 @@ int gdca_pair_chunk(int nB, int KA, int wanted)
     return (int)(kc < KA ? kc : KA);
 }
 
-void gdca_launch_pair_pack(hipStream_t s, const int8_t *X, size_t stride, int Ns, int K, int q, uint32_t *out, gdca_dev_scalars *sc)
-{
-    GDCA_LAUNCH_DIRECT(k_pair_pack, dim3((K + 255) / 256, gdca_pair_blocks(Ns)), dim3(256), 0, s, X, stride, Ns, K, q, out, sc);
-}
-
 void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const int8_t *XB, size_t strideB, int N, int split, int KA, int KB,
                           int q, int8_t *Xp)
 {
@@ -251,7 +212,8 @@ void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const
 }
 
 // E[a0 .. a0 + Ac - 1][all b] from the block of A (ld, sign) and the packed symbols; T: Ac x nB doubles.  EAB == nullptr: the coupling R.
-void gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N, int split,
+// An error: the dynamic LDS limit could not be raised for a tile; the kernel it was for and those behind it were not launched
+hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N, int split,
                             int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E, int ncu)
 {
     const int NA = split, NB = N - split, nA = NA * sdim, nB = NB * sdim;
@@ -259,11 +221,12 @@ void gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double si
         const k_pair_fold_args a{A, ld, sign, XAg, T, NA, sdim, nA, nB, KA, a0, Ac};
         const int rt = (nB + PROWS - 1) / PROWS;
         // 128 sequences a workgroup -- or 16, where 128 would give fewer than two workgroups a compute unit
-        const bool wide = (long long)((Ac + 4 * PAU_WIDE - 1) / (4 * PAU_WIDE)) * rt >= 2 * ncu;
+        const bool wide = gdca_wide_instance(Ac, 4 * PAU_WIDE, rt, ncu);
         const int per = 4 * (wide ? PAU_WIDE : PAU_NARROW);
         const size_t lds = (size_t)PT * (sdim + 1) * PROWS * sizeof(double);
         void (*kern)(k_pair_fold_args) = wide ? k_pair_fold<PAU_WIDE> : k_pair_fold<PAU_NARROW>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
         GDCA_LAUNCH_DIRECT(kern, dim3(rt, (Ac + per - 1) / per), dim3(256), lds, s, a);
     }
     {
@@ -271,10 +234,11 @@ void gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double si
         if (SB > ((NB + PT - 1) & ~(PT - 1))) SB = (NB + PT - 1) & ~(PT - 1);
         const size_t lds = ((size_t)SB * sdim + 1) * PGA * sizeof(double);
         const int ga = (Ac + PGA - 1) / PGA;
-        const bool wide = (long long)((KB + 256 * PBU_WIDE - 1) / (256 * PBU_WIDE)) * ga >= 2 * ncu;
+        const bool wide = gdca_wide_instance(KB, 256 * PBU_WIDE, ga, ncu);
         const int per = 256 * (wide ? PBU_WIDE : PBU_NARROW);
         void (*kern)(k_pair_gather_args) = wide ? k_pair_gather<PBU_WIDE> : k_pair_gather<PBU_NARROW>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
         const long long maxb = (long long)65535 * per;  // sequences b one launch's grid covers
         for (long long b0 = 0; b0 < KB; b0 += maxb) {
             const long long kb = KB - b0 < maxb ? KB - b0 : maxb;
@@ -282,4 +246,5 @@ void gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double si
             GDCA_LAUNCH_DIRECT(kern, dim3(ga, (unsigned)((kb + per - 1) / per)), dim3(256), lds, s, a);
         }
     }
+    return hipSuccess;
 }

@@ -347,11 +347,11 @@ def _what_arg(what) -> int:
     raise ArgumentError(f"invalid what value: {what} (must be either energy or coupling)")
 
 
-def _symbols(X, name: str) -> np.ndarray:
+def _symbols(X, name: str, dims: str = "a sites x K") -> np.ndarray:
     """(sites, K) symbols -> int8, column-major; a wider type is not cast blindly (261 would wrap to the legal symbol 5)"""
     Xa = np.asarray(X)
     if Xa.ndim != 2:
-        raise ArgumentError(f"{name} must be a sites x K matrix")
+        raise ArgumentError(f"{name} must be {dims} matrix")
     if Xa.dtype != np.int8:
         if not np.issubdtype(Xa.dtype, np.integer) or (Xa.size and (Xa.min() < 1 or Xa.max() > 31)):
             raise ArgumentError(f"{name} must hold integer symbols between 1 and q")

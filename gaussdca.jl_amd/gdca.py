@@ -85,36 +85,42 @@ def gDCA(filename: str, pseudocount: float = 0.8, theta=":auto", max_gap_fractio
     return Ranking(ii, jj, sc)
 
 
-def _fit_then_score(filename, sequences, pseudocount, theta, max_gap_fraction, remove_dups, ctx, run, unreliable):
-    """What the fused entries that score ``sequences`` under the fitted model share (gDCA_energies, gDCA_mutation_scan): the
-    ``sequences`` conventions and their checks, the alignment with or without deduplication, the stats and the conditioning warning.
-    ``run(c, ptr, N, M, q, X_ptr, K)`` is the context call (X_ptr None: the alignment's own sequences); ``unreliable`` names the result
-    in the warning.  Called after check_arguments."""
+def _sequences_arg(seqs, name: str, dims: str):
+    """The ``sequences`` / ``seqs_a`` / ``seqs_b`` conventions of the fused read-outs: an array of symbols, a string naming a FASTA
+    file (read with ``max_gap_fraction = 1.0``: every record is kept) or None (the alignment's own) -> int8 column-major, or None."""
+    if seqs is None:
+        return None
+    if isinstance(seqs, (str, bytes, os.PathLike)):
+        if not os.path.isfile(seqs):
+            raise ArgumentError(f"cannot open file {seqs}")
+        return np.asfortranarray(read_fasta_alignment(os.fspath(seqs) if not isinstance(seqs, bytes) else seqs.decode(), 1.0), dtype=np.int8)
+    return _symbols(seqs, name, dims)
+
+
+def _ptr_count(X):
+    """parsed sequences as the context calls take them: (pointer, count); (None, 0): the alignment's own"""
+    return (None, 0) if X is None else (X.ctypes.data, X.shape[1])
+
+
+def _check_whole_sequences(X, N):
+    if X is not None and X.shape[0] != N:
+        raise ArgumentError(f"sequences have {X.shape[0]} sites, the alignment has {N}")
+    if X is not None and X.shape[1] < 1:
+        raise ArgumentError("sequences holds no sequence")
+
+
+def _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, check, run, unreliable):
+    """What the fused read-outs of the fitted model share (gDCA_energies, gDCA_pair_energies, gDCA_mutation_scan): the alignment with
+    or without deduplication, the stats and the conditioning warning.  ``check(N)`` holds the entry's own arguments against the
+    alignment, ``run(c, ptr, N, M, q)`` is the context call, ``unreliable`` names the result in the warning.  Called by the entry
+    itself, after check_arguments: the warning points at the entry's caller."""
     global last_stats
-    if isinstance(sequences, (str, bytes, os.PathLike)):
-        if not os.path.isfile(sequences):
-            raise ArgumentError(f"cannot open file {sequences}")
-        X = read_fasta_alignment(os.fspath(sequences) if not isinstance(sequences, bytes) else sequences.decode(), 1.0)
-    elif sequences is not None:
-        X = np.asarray(sequences)
-        if X.ndim != 2:
-            raise ArgumentError("sequences must be an N x K matrix")
-        if X.dtype != np.int8:  # (a wider type is not cast blindly: 261 would wrap to the legal symbol 5)
-            if not np.issubdtype(X.dtype, np.integer) or (X.size and (X.min() < 1 or X.max() > 31)):
-                raise ArgumentError("sequences must hold integer symbols between 1 and q")
-        X = np.asfortranarray(X, dtype=np.int8)
-    else:
-        X = None
 
     def _run(ptr, N, M, q):
         if q >= 32:
             raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
-        if X is not None and X.shape[0] != N:
-            raise ArgumentError(f"sequences have {X.shape[0]} sites, the alignment has {N}")
-        if X is not None and X.shape[1] < 1:
-            raise ArgumentError("sequences holds no sequence")
-        c = ctx or default_context()
-        return run(c, ptr, N, M, q, None if X is None else X.ctypes.data, 0 if X is None else X.shape[1])
+        check(N)
+        return run(ctx or default_context(), ptr, N, M, q)
 
     if remove_dups:
         Z = read_fasta_alignment(filename, max_gap_fraction)
@@ -147,8 +153,9 @@ def gDCA_energies(filename: str, sequences=None, pseudocount: float = 0.8, theta
     if kw:
         raise TypeError(f"gDCA_energies() got unexpected keyword arguments {sorted(kw)}")
     check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
-    return _fit_then_score(filename, sequences, pseudocount, theta, max_gap_fraction, remove_dups, ctx,
-                           lambda c, ptr, N, M, q, X_ptr, K: c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), X_ptr, K),
+    X = _sequences_arg(sequences, "sequences", "an N x K")
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N),
+                           lambda c, ptr, N, M, q: c.run_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), *_ptr_count(X)),
                            "energies")
 
 
@@ -164,26 +171,15 @@ def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what
     deduplication; both None: the diagonal holds the native pairs); a ``(split, K_A)`` / ``(N - split, K_B)`` int8 array (symbols
     1..q); or a string naming a FASTA file of that half alone, read with ``max_gap_fraction = 1.0`` so every record is kept.
     Stats go to ``last_stats``."""
-    global last_stats
     if "θ" in kw:
         theta = kw.pop("θ")
     if kw:
         raise TypeError(f"gDCA_pair_energies() got unexpected keyword arguments {sorted(kw)}")
     check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
     w = _what_arg(what)
+    XA, XB = _sequences_arg(seqs_a, "seqs_a", "a sites x K"), _sequences_arg(seqs_b, "seqs_b", "a sites x K")
 
-    def _half(seqs, name):
-        if isinstance(seqs, (str, bytes, os.PathLike)):
-            if not os.path.isfile(seqs):
-                raise ArgumentError(f"cannot open file {seqs}")
-            return np.asfortranarray(read_fasta_alignment(os.fspath(seqs) if not isinstance(seqs, bytes) else seqs.decode(), 1.0), dtype=np.int8)
-        return None if seqs is None else _symbols(seqs, name)
-
-    XA, XB = _half(seqs_a, "seqs_a"), _half(seqs_b, "seqs_b")
-
-    def _run(ptr, N, M, q):
-        if q >= 32:
-            raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+    def check(N):
         if not isinstance(split, (int, np.integer)) or not 1 <= split <= N - 1:
             raise ArgumentError(f"invalid split value: {split} (must be between 1 and N - 1 = {N - 1})")
         if XA is not None and XA.shape[0] != split:
@@ -192,26 +188,11 @@ def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what
             raise ArgumentError(f"seqs_b have {XB.shape[0]} sites, protein B has {N - split}")
         if (XA is not None and XA.shape[1] < 1) or (XB is not None and XB.shape[1] < 1):
             raise ArgumentError("seqs_a or seqs_b holds no sequence")
-        c = ctx or default_context()
-        return c.run_pair_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split),
-                                       None if XA is None else XA.ctypes.data, 0 if XA is None else XA.shape[1],
-                                       None if XB is None else XB.ctypes.data, 0 if XB is None else XB.shape[1], w)
 
-    if remove_dups:
-        Z = read_fasta_alignment(filename, max_gap_fraction)
-        Z, _ = remove_duplicate_sequences(Z)
-        Zf = np.asfortranarray(Z, dtype=np.int8)
-        E, last_stats = _run(Zf.ctypes.data, Zf.shape[0], Zf.shape[1], int(Z.max()))
-    else:
-        with FastaAlignment(filename, max_gap_fraction) as fa:
-            E, last_stats = _run(fa.ptr, fa.N, fa.M, fa.q)
-    if last_stats.get("refined", 0) < 0:
-        import warnings
-
-        warnings.warn("gDCA: the covariance is too ill-conditioned for the block sweep even with its refinement step "
-                      f"(||inv(C)||_1 = {last_stats['inverse_norm1']:.3g}; pseudocount {pseudocount}): energies are unreliable",
-                      RuntimeWarning, stacklevel=2)
-    return E
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, check,
+                           lambda c, ptr, N, M, q: c.run_pair_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split),
+                                                                           *_ptr_count(XA), *_ptr_count(XB), w),
+                           "energies")
 
 
 def gDCA_mutation_scan(filename: str, sequences=None, what="delta", pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
@@ -231,9 +212,10 @@ def gDCA_mutation_scan(filename: str, sequences=None, what="delta", pseudocount:
         raise TypeError(f"gDCA_mutation_scan() got unexpected keyword arguments {sorted(kw)}")
     check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
     w = _mut_what_arg(what)
-    return _fit_then_score(filename, sequences, pseudocount, theta, max_gap_fraction, remove_dups, ctx,
-                           lambda c, ptr, N, M, q, X_ptr, K: c.run_mutation_scan_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta),
-                                                                                     X_ptr, K, w),
+    X = _sequences_arg(sequences, "sequences", "an N x K")
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N),
+                           lambda c, ptr, N, M, q: c.run_mutation_scan_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta),
+                                                                           *_ptr_count(X), w),
                            "energy changes")
 
 

@@ -1,8 +1,18 @@
 """Shared helpers for the parity tests: the reference test-suite's cases and comparator
 (/root/reference/test/runtests.jl:29-50) plus the tie rule of SURVEY.md 4.3."""
+import os
+import re
+import subprocess
 from itertools import groupby
 
 import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gaussdca.jl_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-Wno-unused-function", "-Wno-pass-failed",
+         "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
 # the four golden cases of test/runtests.jl:52-76 (keyword names as in src/GaussDCA.jl:10-15,
 # with theta spelled out)
@@ -112,3 +122,142 @@ def edge_family(M, N, q, seed):
         Z[-1, 3] = 1
     Z[:, 4] = np.where(np.arange(M) % 3 == 0, c(4), Z[:, 4])
     return np.asfortranarray(Z.T.astype(np.int8))
+
+
+# ---- the model read-outs (energies, pair energies, mutation scan): what their GPU tests share ---------------------------------------------
+@pytest.fixture(scope="module")
+def g():
+    import gaussdca.jl_amd as g
+
+    assert os.path.exists(g._lib.LIB_PATH), "libgdca.so missing: the GPU tests never fall back to the CPU"
+    assert g.load().gdca_device_count() > 0, "no HIP device"
+    return g
+
+
+@pytest.fixture(scope="module")
+def ctx(g):
+    c = g.Context(0)
+    yield c
+    c.close()
+
+
+_models = {}  # one cache for every file: an oracle model is fitted once per run of the suite
+
+
+def golden_model(refdata, name, pc, theta="auto", dedup=False):
+    """(Zo (M, N), q, mJ, Pi) of the oracle chain on a golden alignment"""
+    import energy_model as em
+    from oracle import gdca_oracle as o
+
+    key = (name, pc, theta, dedup)
+    if key not in _models:
+        Zo = o.read_fasta_alignment(os.path.join(refdata, name), 0.9)
+        if dedup:
+            Zo = o.remove_duplicate_sequences(Zo)[0]
+        q = int(Zo.max())
+        _models[key] = (Zo, q) + em.model_from_Z(Zo, q, pc, theta)
+    return _models[key]
+
+
+def synth_model(q, N, seed=None):
+    import energy_model as em
+    from gaussdca.jl_amd.synth import synth_family
+
+    key = ("synth", q, N)
+    if key not in _models:
+        Zo = synth_family(N, 300, q, seed=seed or 1000 * q + N)
+        _models[key] = (Zo, q) + em.model_from_Z(Zo, q, 0.5)
+    return _models[key]
+
+
+def mixed_sequences(rng, Zo, q, K, shift=0):
+    """(N, K) int8: column j is, by (j + shift) % 4: all gaps, a sequence without gaps, a uniformly random one (gaps included), a
+    member of the family Zo (M, N)"""
+    M, N = Zo.shape
+    X = np.empty((N, K), dtype=np.int8)
+    for j in range(K):
+        kind = (j + shift) % 4
+        if kind == 0:
+            X[:, j] = q
+        elif kind == 1:
+            X[:, j] = rng.integers(1, q, size=N)
+        elif kind == 2:
+            X[:, j] = rng.integers(1, q + 1, size=N)
+        else:
+            X[:, j] = Zo[rng.integers(0, M)]
+    return np.asfortranarray(X)
+
+
+def assert_within_order_bound(E, mJ, Pi, X, q, what):
+    """energies E of the sequences X against tests/energy_model.py, within its bound of any summation order"""
+    import energy_model as em
+
+    E_ref, B, c0 = em.energies_gather(mJ, Pi, X, q)
+    bound = em.order_bound(X.shape[0], q, B)
+    err = np.abs(E - E_ref)
+    print("%s: max |E - E_ref| / bound = %.3g, bound / |E| = %.3g .. %.3g" %
+          (what, float((err / bound).max()), float((bound / np.abs(E_ref)).min()), float((bound / np.abs(E_ref)).max())))
+    assert np.all(err <= bound), (what, float((err / bound).max()))
+    return E_ref, c0, bound
+
+
+def mutation_reference(mJ, Pi, X, q):
+    """tests/mutation_model.py on the sequences X: (V, bound of V, dE, bound of dE), all (K, N, q)"""
+    import mutation_model as mm
+
+    N = X.shape[0]
+    V, B, Vl = mm.potentials_exact(mJ, Pi, X, q)
+    dE = mm.delta_exact(Vl, X, q)
+    return V, mm.bound_V(N, q, B), dE, mm.delta_bound(N, q, B, X, dE)
+
+
+def ratio(D, ref, bound):
+    """max |D - ref| / bound over the entries with a bound; where the bound is 0 (the gap target of V, the b = x_i entry of a gap site)
+    the entry must be exact"""
+    err = np.abs(D - ref)
+    z = bound == 0
+    assert np.all(err[z] == 0)
+    return float((err[~z] / bound[~z]).max()) if (~z).any() else 0.0
+
+
+def compiler_report(tmp_path, file, kernels=None, min_loops=None):
+    """The compiler's report on one kernel file of csrc (tests/test_kernel_resources.py has a fixed list of files).
+    ``kernels``: the file is compiled with the resource-usage remarks; every name of ``kernels`` must be among its kernels, and EVERY
+    kernel of the file must be free of spills and scratch.  Returns [(kernel name, field)], field(label) = that kernel's number.
+    ``min_loops``: the file's assembly must carry at least that many of the compiler's loop annotations, and no barrier may sit inside
+    a divergent loop (tools/asm_loops.py)."""
+    src = os.path.join(CSRC, file)
+    report = []
+    if kernels is not None:
+        r = subprocess.run([HIPCC, *FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", str(tmp_path / "x.o")],
+                           capture_output=True, text=True, timeout=1200)
+        assert r.returncode == 0, r.stderr[-3000:]
+        blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
+        names = [b.split()[0] for b in blocks]
+        for k in kernels:
+            assert any(k in n for n in names), (k, names)
+        for b in blocks:
+            name = b.split()[0]
+
+            def field(label, b=b, name=name):
+                m = re.search(label + r": (\d+)", b)
+                assert m, (name, label)
+                return int(m.group(1))
+
+            spills, scratch, vgprs = field("VGPRs Spill"), field(r"ScratchSize \[bytes/lane\]"), field("VGPRs")
+            print("%-60s VGPRs %3d spilled %3d scratch %3d B" % (name, vgprs, spills, scratch))
+            assert spills == 0 and scratch == 0, (name, vgprs, spills, scratch)
+            report.append((name, field))
+    if min_loops is not None:
+        import importlib.util
+
+        spec = importlib.util.spec_from_file_location("asm_loops", os.path.join(ROOT, "tools", "asm_loops.py"))
+        al = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(al)
+        out = tmp_path / (file + ".s")
+        r = subprocess.run([HIPCC, *FLAGS, "--cuda-device-only", "-S", src, "-o", str(out)], capture_output=True, text=True, timeout=1200)
+        assert r.returncode == 0, r.stderr[-3000:]
+        bad, seen = al.divergent_barrier_loops(out.read_text())
+        assert seen >= min_loops, seen  # (the compiler's loop annotations are there)
+        assert not bad, bad
+    return report

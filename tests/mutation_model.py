@@ -92,24 +92,6 @@ def delta_bound(N, q, B, X, dE):
     return bv + wild_type(bv, X, q) + 2.0 * U * np.abs(dE)
 
 
-def mixed_sequences(rng, Zo, q, K, shift=0):
-    """(N, K) int8: column j is, by (j + shift) % 4: all gaps, a sequence without gaps, a uniformly random one (gaps included), a
-    member of the family Zo (M, N)"""
-    M, N = Zo.shape
-    X = np.empty((N, K), dtype=np.int8)
-    for j in range(K):
-        kind = (j + shift) % 4
-        if kind == 0:
-            X[:, j] = q
-        elif kind == 1:
-            X[:, j] = rng.integers(1, q, size=N)
-        elif kind == 2:
-            X[:, j] = rng.integers(1, q + 1, size=N)
-        else:
-            X[:, j] = Zo[rng.integers(0, M)]
-    return np.asfortranarray(X)
-
-
 def single_mutants(x, q):
     """x (N,) -> (N, N q) int8: column i q + (b - 1) is x with site i set to b"""
     N = x.shape[0]

@@ -4,18 +4,13 @@ exported surface, the order of the argument checks, and the compiler's report on
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import energy_model as em
+from gdca_testutil import HIPCC, ROOT, compiler_report
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gaussdca.jl_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-Wno-unused-function", "-Wno-pass-failed",
-         "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 NEW_SYMBOLS = ["gdca_energies_dev", "gdca_energies", "gdca_run_energies_dev", "gdca_run_energies"]
 
 
@@ -124,38 +119,11 @@ def test_argument_errors_come_first_then_no_cpu_fallback(refdata, tmp_path):
 def test_energy_kernels_do_not_spill(tmp_path):
     if not os.path.exists(HIPCC) or shutil.which("c++filt") is None:
         pytest.skip("no hipcc")
-    r = subprocess.run([HIPCC, *FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "k_energy.hip"), "-o", str(tmp_path / "x.o")],
-                       capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-3000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
-    names = [b.split()[0] for b in blocks]
-    for k in ("k_energy_pack", "k_energy_gtile", "k_energy_gfin", "k_energy_c0", "k_energy_rowsILi20ELi8E", "k_energy_rowsILi20ELi2E", "k_energy_rowsILi0ELi8E", "k_energy_rowsILi0ELi2E", "k_energy_final"):
-        assert any(k in n for n in names), (k, names)
-    for b in blocks:
-        name = b.split()[0]
-
-        def field(label):
-            m = re.search(label + r": (\d+)", b)
-            assert m, (name, label)
-            return int(m.group(1))
-
-        spills, scratch, vgprs = field("VGPRs Spill"), field(r"ScratchSize \[bytes/lane\]"), field("VGPRs")
-        print("%-60s VGPRs %3d spilled %3d scratch %3d B" % (name, vgprs, spills, scratch))
-        assert spills == 0 and scratch == 0, (name, vgprs, spills, scratch)
+    compiler_report(tmp_path, "k_energy.hip", kernels=("k_energy_pack", "k_energy_gtile", "k_energy_gfin", "k_energy_c0", "k_energy_rowsILi20ELi8E",
+                                                       "k_energy_rowsILi20ELi2E", "k_energy_rowsILi0ELi8E", "k_energy_rowsILi0ELi2E", "k_energy_final"))
 
 
 def test_no_barrier_sits_inside_a_divergent_loop_of_the_energy_kernels(tmp_path):
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("asm_loops", os.path.join(ROOT, "tools", "asm_loops.py"))
-    al = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(al)
-    out = tmp_path / "k_energy.s"
-    r = subprocess.run([HIPCC, *FLAGS, "--cuda-device-only", "-S", os.path.join(CSRC, "k_energy.hip"), "-o", str(out)], capture_output=True,
-                       text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-3000:]
-    bad, seen = al.divergent_barrier_loops(out.read_text())
-    assert seen >= 4, seen  # (the compiler's loop annotations are there: the tile walk, the g pass, the reductions)
-    assert not bad, bad
+    compiler_report(tmp_path, "k_energy.hip", min_loops=4)  # (the tile walk, the g pass, the reductions)

@@ -11,71 +11,11 @@ import numpy as np
 import pytest
 
 import energy_model as em
+from gdca_testutil import assert_within_order_bound, ctx, g, golden_model, mixed_sequences  # noqa: F401 (g, ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 GOLD = ["small.fasta.gz", "large.fasta.gz"]
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gaussdca.jl_amd as g
-
-    assert os.path.exists(g._lib.LIB_PATH), "libgdca.so missing: the GPU tests never fall back to the CPU"
-    assert g.load().gdca_device_count() > 0, "no HIP device"
-    return g
-
-
-@pytest.fixture(scope="module")
-def ctx(g):
-    c = g.Context(0)
-    yield c
-    c.close()
-
-
-_models = {}
-
-
-def golden_model(refdata, name, pc, theta="auto", dedup=False):
-    """(Zo (M, N), q, mJ, Pi) of the oracle chain on a golden alignment"""
-    from oracle import gdca_oracle as o
-
-    key = (name, pc, theta, dedup)
-    if key not in _models:
-        Zo = o.read_fasta_alignment(os.path.join(refdata, name), 0.9)
-        if dedup:
-            Zo = o.remove_duplicate_sequences(Zo)[0]
-        q = int(Zo.max())
-        _models[key] = (Zo, q) + em.model_from_Z(Zo, q, pc, theta)
-    return _models[key]
-
-
-def mixed_sequences(rng, Zo, q, K, shift=0):
-    """(N, K) int8: column j is, by (j + shift) % 4: all gaps, a sequence without gaps, a uniformly random one (gaps included), a
-    member of the family"""
-    M, N = Zo.shape
-    X = np.empty((N, K), dtype=np.int8)
-    for j in range(K):
-        kind = (j + shift) % 4
-        if kind == 0:
-            X[:, j] = q
-        elif kind == 1:
-            X[:, j] = rng.integers(1, q, size=N)
-        elif kind == 2:
-            X[:, j] = rng.integers(1, q + 1, size=N)
-        else:
-            X[:, j] = Zo[rng.integers(0, M)]
-    return np.asfortranarray(X)
-
-
-def assert_within_order_bound(E, mJ, Pi, X, q, what):
-    E_ref, B, c0 = em.energies_gather(mJ, Pi, X, q)
-    bound = em.order_bound(X.shape[0], q, B)
-    err = np.abs(E - E_ref)
-    print("%s: max |E - E_ref| / bound = %.3g, bound / |E| = %.3g .. %.3g" %
-          (what, float((err / bound).max()), float((bound / np.abs(E_ref)).min()), float((bound / np.abs(E_ref)).max())))
-    assert np.all(err <= bound), (what, float((err / bound).max()))
-    return E_ref, c0, bound
 
 
 # ---- 1. operator parity, derived bound ------------------------------------------------------------------------------------------------

@@ -13,70 +13,11 @@ import pytest
 
 import energy_model as em
 import mutation_model as mm
+from gdca_testutil import ctx, g, golden_model, mixed_sequences, mutation_reference as reference, ratio, synth_model  # noqa: F401 (g, ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 GOLD = ["small.fasta.gz", "large.fasta.gz"]
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gaussdca.jl_amd as g
-
-    assert os.path.exists(g._lib.LIB_PATH), "libgdca.so missing: the GPU tests never fall back to the CPU"
-    assert g.load().gdca_device_count() > 0, "no HIP device"
-    return g
-
-
-@pytest.fixture(scope="module")
-def ctx(g):
-    c = g.Context(0)
-    yield c
-    c.close()
-
-
-_models = {}
-
-
-def golden_model(refdata, name, pc, theta="auto", dedup=False):
-    """(Zo (M, N), q, mJ, Pi) of the oracle chain on a golden alignment"""
-    from oracle import gdca_oracle as o
-
-    key = (name, pc, theta, dedup)
-    if key not in _models:
-        Zo = o.read_fasta_alignment(os.path.join(refdata, name), 0.9)
-        if dedup:
-            Zo = o.remove_duplicate_sequences(Zo)[0]
-        q = int(Zo.max())
-        _models[key] = (Zo, q) + em.model_from_Z(Zo, q, pc, theta)
-    return _models[key]
-
-
-def synth_model(q, N, seed=None):
-    from gaussdca.jl_amd.synth import synth_family
-
-    key = ("synth", q, N)
-    if key not in _models:
-        Zo = synth_family(N, 300, q, seed=seed or 1000 * q + N)
-        _models[key] = (Zo, q) + em.model_from_Z(Zo, q, 0.5)
-    return _models[key]
-
-
-def reference(mJ, Pi, X, q):
-    """(V, bound of V, dE, bound of dE), all (K, N, q)"""
-    N = X.shape[0]
-    V, B, Vl = mm.potentials_exact(mJ, Pi, X, q)
-    dE = mm.delta_exact(Vl, X, q)
-    return V, mm.bound_V(N, q, B), dE, mm.delta_bound(N, q, B, X, dE)
-
-
-def ratio(D, ref, bound):
-    """max |D - ref| / bound over the entries with a bound; where the bound is 0 (the gap target of V, the b = x_i entry of a gap site)
-    the entry must be exact"""
-    err = np.abs(D - ref)
-    z = bound == 0
-    assert np.all(err[z] == 0)
-    return float((err[~z] / bound[~z]).max()) if (~z).any() else 0.0
 
 
 def assert_both_modes(g, ctx, mJ, Pi, X, q, tag):
@@ -95,7 +36,7 @@ def assert_both_modes(g, ctx, mJ, Pi, X, q, tag):
 @pytest.mark.parametrize("pc", [0.8, 0.2])
 def test_operator_parity_goldens(g, ctx, refdata, name, pc):
     Zo, q, mJ, Pi = golden_model(refdata, name, pc)
-    X = mm.mixed_sequences(np.random.default_rng(11), Zo, q, 24)
+    X = mixed_sequences(np.random.default_rng(11), Zo, q, 24)
     assert np.all(X[:, 0] == q)
     assert_both_modes(g, ctx, mJ, Pi, X, q, "%s pc %g" % (name, pc))
 
@@ -106,7 +47,7 @@ SYNTH = [(21, 53), (5, 30), (31, 41), (21, 200)]
 @pytest.mark.parametrize("q,N", SYNTH, ids=["q%d-N%d" % c for c in SYNTH])
 def test_operator_parity_synthetic(g, ctx, q, N):
     Zo, q, mJ, Pi = synth_model(q, N)
-    X = mm.mixed_sequences(np.random.default_rng(q * 1000 + N), Zo, q, 36, shift=1)
+    X = mixed_sequences(np.random.default_rng(q * 1000 + N), Zo, q, 36, shift=1)
     assert_both_modes(g, ctx, mJ, Pi, X, q, "q %d N %d" % (q, N))
 
 
@@ -115,7 +56,7 @@ def test_delta_matches_the_energies_of_the_explicit_mutants(g, ctx, refdata):
     Zo, q, mJ, Pi = golden_model(refdata, "small.fasta.gz", 0.8)
     N = Zo.shape[1]
     assert (N, q) == (53, 21)
-    X = mm.mixed_sequences(np.random.default_rng(2), Zo, q, 3, shift=1)  # no gaps, random with gaps, a member
+    X = mixed_sequences(np.random.default_rng(2), Zo, q, 3, shift=1)  # no gaps, random with gaps, a member
     D = g.mutation_scan(mJ, Pi, X, q, ctx=ctx)
     _, _, dE_ref, bD = reference(mJ, Pi, X, q)
     E_wt = g.sequence_energies(mJ, Pi, X, q, ctx=ctx)
@@ -137,7 +78,7 @@ def test_delta_matches_the_energies_of_the_explicit_mutants(g, ctx, refdata):
 @pytest.mark.parametrize("q,N", [(21, 53), (31, 41), (5, 30)])
 def test_exact_relations_of_the_two_modes(g, ctx, q, N):
     Zo, q, mJ, Pi = synth_model(q, N)
-    X = mm.mixed_sequences(np.random.default_rng(N), Zo, q, 40)
+    X = mixed_sequences(np.random.default_rng(N), Zo, q, 40)
     V = g.mutation_scan(mJ, Pi, X, q, what="potential", ctx=ctx)
     D = g.mutation_scan(mJ, Pi, X, q, what="delta", ctx=ctx)
     assert np.array_equal(D, V - mm.wild_type(V, X, q))
@@ -150,7 +91,7 @@ def test_exact_relations_of_the_two_modes(g, ctx, q, N):
 def test_order_fixed_sums(g, ctx, refdata):
     Zo, q, mJ, Pi = golden_model(refdata, "small.fasta.gz", 0.8)
     rng = np.random.default_rng(5)
-    X = mm.mixed_sequences(rng, Zo, q, 1000, shift=3)
+    X = mixed_sequences(rng, Zo, q, 1000, shift=3)
     D = g.mutation_scan(mJ, Pi, X, q, ctx=ctx)
     assert np.array_equal(D, g.mutation_scan(mJ, Pi, X, q, ctx=ctx))  # run to run
     x = np.asfortranarray(X[:, 417:418])
@@ -171,7 +112,7 @@ def test_wide_and_narrow_instances_give_the_same_bits(g, ctx, q):
     N, K = 200, 1001
     Zo, q, mJ, Pi = synth_model(q, N, seed=4242 + q)
     rng = np.random.default_rng(q)
-    X64 = mm.mixed_sequences(rng, Zo, q, 64)
+    X64 = mixed_sequences(rng, Zo, q, 64)
     spb = 64 // (q - 1)
     assert 1 * -(-N // spb) < 512 <= -(-K // 128) * -(-N // spb) and K % 128 and K % 16
     for what in ("delta", "potential"):
@@ -196,7 +137,7 @@ def test_fused_parity(g, ctx, refdata, name, pc, theta, dedup):
     Zo, q, mJ, Pi = golden_model(refdata, name, pc, theta, dedup)
     fasta = os.path.join(refdata, name)
     kw = dict(pseudocount=pc, theta=theta if theta != "auto" else ":auto", remove_dups=dedup, ctx=ctx)
-    X = mm.mixed_sequences(np.random.default_rng(3), Zo, q, 12)
+    X = mixed_sequences(np.random.default_rng(3), Zo, q, 12)
     V_ref, bV, dE_ref, bD = reference(mJ, Pi, X, q)
     D = g.gDCA_mutation_scan(fasta, X, **kw)
     assert D.shape == (12, Zo.shape[1], q) and close_to_oracle(D, dE_ref, bD)
@@ -218,7 +159,7 @@ def test_fused_is_the_operator_on_the_librarys_own_model(g, ctx, M, N, q, pc, th
 
     Zo = synth_family(N, M, q, seed=77 + N)
     Zf = np.asfortranarray(Zo.T)
-    X = mm.mixed_sequences(np.random.default_rng(N), Zo, q, 50)
+    X = mixed_sequences(np.random.default_rng(N), Zo, q, 50)
     dZ = torch.from_numpy(Zo).cuda()
     dX = torch.from_numpy(np.ascontiguousarray(X.T)).cuda()
     Pi_true, Pij_true, _, _ = g.compute_weighted_frequencies(Zf, q, theta if theta >= 0 else ":auto", ctx=ctx)
@@ -243,7 +184,7 @@ def test_fused_parity_through_the_collect_time_branches(g, refdata, option, valu
     """The scan is run AGAIN at collect time after the blocked Cholesky fallback, after a Newton-Schulz step and after the sweep's
     second attempt, as the energy targets are."""
     Zo, q, mJ, Pi = golden_model(refdata, "small.fasta.gz", 0.8)
-    X = mm.mixed_sequences(np.random.default_rng(8), Zo, q, 12)
+    X = mixed_sequences(np.random.default_rng(8), Zo, q, 12)
     V_ref, bV, dE_ref, bD = reference(mJ, Pi, X, q)
     c = g.Context(0)
     try:
@@ -262,7 +203,7 @@ def test_a_fused_scan_leaves_nothing_behind(g, refdata):
     Zo, q, mJ, Pi = golden_model(refdata, "small.fasta.gz", 0.8)
     Zf = np.asfortranarray(Zo.T)
     N, M = Zf.shape
-    X = mm.mixed_sequences(np.random.default_rng(21), Zo, q, 10)
+    X = mixed_sequences(np.random.default_rng(21), Zo, q, 10)
     used, fresh = g.Context(0), g.Context(0)
     try:
         D, _ = used.run_mutation_scan_ptr(Zf.ctypes.data, N, M, q, 0.8, -1.0, X.ctypes.data, 10, g._lib.MUT_DELTA)
@@ -280,7 +221,7 @@ def test_failure_modes(g, ctx, refdata):
     import ctypes as C
 
     Zo, q, mJ, Pi = golden_model(refdata, "small.fasta.gz", 0.8)
-    X = mm.mixed_sequences(np.random.default_rng(9), Zo, q, 10)
+    X = mixed_sequences(np.random.default_rng(9), Zo, q, 10)
     good = g.mutation_scan(mJ, Pi, X, q, ctx=ctx)
     for byte in (0, q + 1):
         Y = X.copy(order="F")

@@ -11,28 +11,12 @@ import pytest
 
 import energy_model as em
 import pair_energy_model as pm
-from test_gpu_energy import golden_model  # (one cache of the oracle models for both files)
+from gdca_testutil import ctx, g, golden_model  # noqa: F401 (g, ctx: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 GOLD = ["small.fasta.gz", "large.fasta.gz"]
 SPLITS = {"small.fasta.gz": (26, 1, 52), "large.fasta.gz": (20, 399)}
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gaussdca.jl_amd as g
-
-    assert os.path.exists(g._lib.LIB_PATH), "libgdca.so missing: the GPU tests never fall back to the CPU"
-    assert g.load().gdca_device_count() > 0, "no HIP device"
-    return g
-
-
-@pytest.fixture(scope="module")
-def ctx(g):
-    c = g.Context(0)
-    yield c
-    c.close()
 
 
 def assert_pair_parity(g, ctx, mJ, Pi, XA, XB, q, tag):

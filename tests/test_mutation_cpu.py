@@ -3,19 +3,14 @@ the energies of the explicit mutants for EVERY (k, i, b) of a handful of sequenc
 argument checks, the sanity property of the GPU test on the numpy model alone, and the compiler's report on k_mutation.hip."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import energy_model as em
 import mutation_model as mm
+from gdca_testutil import CSRC, HIPCC, ROOT, compiler_report, mixed_sequences
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gaussdca.jl_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-Wno-unused-function", "-Wno-pass-failed",
-         "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 NEW_SYMBOLS = ["gdca_mutation_scan_dev", "gdca_mutation_scan", "gdca_run_mutation_scan_dev", "gdca_run_mutation_scan"]
 
 
@@ -30,7 +25,7 @@ def handful(Zo, q, seed):
     """(N, 6): two members of the family (one of them with gaps), an all-gap sequence, one without gaps, one uniformly random (gaps
     included), one more member"""
     rng = np.random.default_rng(seed)
-    X = mm.mixed_sequences(rng, Zo, q, 5, shift=3)  # member, all gaps, no gaps, random, member
+    X = mixed_sequences(rng, Zo, q, 5, shift=3)  # member, all gaps, no gaps, random, member
     gappy = Zo[np.argmax((Zo == q).sum(axis=1))]
     return np.asfortranarray(np.concatenate([X, gappy[:, None]], axis=1))
 
@@ -199,27 +194,13 @@ def test_native_residues_sit_in_minima_on_the_numpy_model(refdata, name):
 def test_mutation_kernels_do_not_spill_and_two_workgroups_share_a_compute_unit(tmp_path):
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
-    src = os.path.join(CSRC, "k_mutation.hip")
-    r = subprocess.run([HIPCC, *FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", str(tmp_path / "x.o")],
-                       capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-3000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
-    names = [b.split()[0] for b in blocks]
-    for k in ("k_mut_rowsILi20ELi32E", "k_mut_rowsILi20ELi4E", "k_mut_rowsILi0ELi32E", "k_mut_rowsILi0ELi4E"):
-        assert any(k in n for n in names), (k, names)
-    text = open(src).read()
+    report = compiler_report(tmp_path, "k_mutation.hip",
+                             kernels=("k_mut_rowsILi20ELi32E", "k_mut_rowsILi20ELi4E", "k_mut_rowsILi0ELi32E", "k_mut_rowsILi0ELi4E"))
+    text = open(os.path.join(CSRC, "k_mutation.hip")).read()
     MT, MLD = (int(re.search(r"#define %s (\d+)" % d, text).group(1)) for d in ("MT", "MLD"))
-    for b in blocks:
-        name = b.split()[0]
-
-        def field(label):
-            m = re.search(label + r": (\d+)", b)
-            assert m, (name, label)
-            return int(m.group(1))
-
-        spills, scratch, vgprs, occ = field("VGPRs Spill"), field(r"ScratchSize \[bytes/lane\]"), field("VGPRs"), field(r"Occupancy \[waves/SIMD\]")
-        print("%-50s VGPRs %3d spilled %3d scratch %3d B, %d waves / SIMD" % (name, vgprs, spills, scratch, occ))
-        assert spills == 0 and scratch == 0, (name, vgprs, spills, scratch)
+    for name, field in report:
+        occ = field(r"Occupancy \[waves/SIMD\]")
+        print("%-50s %d waves / SIMD" % (name, occ))
         if "ILi20E" in name:
             # two workgroups of four waves on a compute unit's four SIMDs = two waves a SIMD, and twice the tile within the 160 KB of LDS
             assert occ >= 2, (name, occ)

@@ -4,19 +4,14 @@ concatenation on models built by the oracle chain from both golden alignments, t
 checks, the partner-matching check on the numpy model alone, and the compiler's report on k_pair_energy.hip."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import energy_model as em
 import pair_energy_model as pm
+from gdca_testutil import HIPCC, ROOT, compiler_report
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gaussdca.jl_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-std=c++17", "-Wno-unused-function", "-Wno-pass-failed",
-         "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 NEW_SYMBOLS = ["gdca_pair_energies_dev", "gdca_pair_energies", "gdca_run_pair_energies_dev", "gdca_run_pair_energies"]
 SPLITS = {"small.fasta.gz": 26, "large.fasta.gz": 20}
 
@@ -166,38 +161,11 @@ def test_partner_matching_on_the_numpy_model():
 def test_pair_energy_kernels_do_not_spill(tmp_path):
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
-    r = subprocess.run([HIPCC, *FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "k_pair_energy.hip"), "-o",
-                        str(tmp_path / "x.o")], capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-3000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
-    names = [b.split()[0] for b in blocks]
-    for k in ("k_pair_pack", "k_pair_pad", "k_pair_foldILi32E", "k_pair_foldILi4E", "k_pair_gatherILi2E", "k_pair_gatherILi1E"):
-        assert any(k in n for n in names), (k, names)
-    for b in blocks:
-        name = b.split()[0]
-
-        def field(label):
-            m = re.search(label + r": (\d+)", b)
-            assert m, (name, label)
-            return int(m.group(1))
-
-        spills, scratch, vgprs = field("VGPRs Spill"), field(r"ScratchSize \[bytes/lane\]"), field("VGPRs")
-        print("%-60s VGPRs %3d spilled %3d scratch %3d B" % (name, vgprs, spills, scratch))
-        assert spills == 0 and scratch == 0, (name, vgprs, spills, scratch)
+    # (the halves are packed by k_energy_pack: tests/test_energy_cpu.py)
+    compiler_report(tmp_path, "k_pair_energy.hip", kernels=("k_pair_pad", "k_pair_foldILi32E", "k_pair_foldILi4E", "k_pair_gatherILi2E", "k_pair_gatherILi1E"))
 
 
 def test_no_barrier_sits_inside_a_divergent_loop_of_the_pair_energy_kernels(tmp_path):
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("asm_loops", os.path.join(ROOT, "tools", "asm_loops.py"))
-    al = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(al)
-    out = tmp_path / "k_pair_energy.s"
-    r = subprocess.run([HIPCC, *FLAGS, "--cuda-device-only", "-S", os.path.join(CSRC, "k_pair_energy.hip"), "-o", str(out)],
-                       capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-3000:]
-    bad, seen = al.divergent_barrier_loops(out.read_text())
-    assert seen >= 4, seen  # (the compiler's loop annotations are there: the tile walks and the segment walks of both instances)
-    assert not bad, bad
+    compiler_report(tmp_path, "k_pair_energy.hip", min_loops=4)  # (the tile walks and the segment walks of both instances)
