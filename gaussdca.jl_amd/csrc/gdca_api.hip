@@ -151,7 +151,7 @@ struct gdca_ctx {
     gdca_buf hcand;               // reweighting, bound forms: the list of candidate pairs
     gdca_buf himg;                // reweighting, fp4 form: the image of the three low bit planes as E2M1 nibbles
     gdca_buf rankws;              // device ranking: keys, values, histograms, the three output arrays
-    gdca_buf keep;                // pair tally, TALLY_SKIP: the sequences each column's tally visits, their counts and sigma (k_tally_keep)
+    gdca_buf keep;                // pair tally, TALLY_SKIP: the sequences each column's tally visits, their counts and sigma (k_pi_keep)
     gdca_buf Pij;                 // gdca_run_multi: Pij_true of the alignment (n x n, ld = n), the covariance of every pseudocount is built from it
     gdca_buf sc_front;            // gdca_run_multi: the scalars as the front end left them (every pseudocount group starts from them)
     gdca_buf Xg, Epart, gpart, gvec;  // energies (k_energy.hip): the packed sequences, the per-site-block partial energies, the partials of g = mJ Pi, g and c0
@@ -719,14 +719,11 @@ static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, 
 {
     hipStream_t s = ctx->stream;
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    CHK(ensure(ctx, ctx->hist, (size_t)N * 32 * sizeof(uint32_t)));
+    CHK(ensure(ctx, ctx->hist, gdca_column_hist_bytes(N, M)));
     if (fixed_thresh >= 0) {
         gdca_launch_set_thresh(s, sc, fixed_thresh);
     } else {
-        if (theta_in < 0.0) {
-            gdca_fill_async(s, ctx->hist.p, 0, (size_t)N * 32 * sizeof(uint32_t));
-            gdca_launch_column_hist(s, Zd, (uint32_t *)ctx->hist.p, N, M);
-        }
+        if (theta_in < 0.0) gdca_launch_column_hist(s, Zd, (uint32_t *)ctx->hist.p, N, M);
         gdca_launch_theta_finalize(s, (const uint32_t *)ctx->hist.p, N, M, theta_in, sc);
     }
     CHK(check_launch(ctx, "theta"));
@@ -780,24 +777,21 @@ static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, in
     const bool skip = gdca_tally_skip(q, TJ, ctx->tune.tally_skip, M);
     const size_t keep_list = (size_t)N * M * sizeof(uint32_t);  // then keep_n (N int), sigma (N bytes)
     if (skip) CHK(ensure(ctx, ctx->keep, keep_list + (size_t)N * sizeof(int) + N));
-    CHK(ensure(ctx, ctx->Zt, (size_t)N * M));
+    CHK(ensure(ctx, ctx->Zt, (size_t)N * M + 3));  // (k_pi_keep reads whole aligned dwords)
     CHK(ensure(ctx, ctx->Zp, (size_t)round_up(N, 64) * M + 64));
     CHK(ensure(ctx, ctx->Pifix, (size_t)N * 32 * sizeof(unsigned long long)));
     CHK(ensure(ctx, ctx->Pipc, (size_t)n * sizeof(double)));
-    gdca_launch_transpose_i8(s, Zd, (int8_t *)ctx->Zt.p, N, M);
-    gdca_launch_colblock(s, Zd, (int8_t *)ctx->Zp.p, N, M, TJ);
-    gdca_fill_async(s, ctx->Pifix.p, 0, (size_t)N * 32 * sizeof(unsigned long long));
-    gdca_launch_pi_tally(s, Zd, (const unsigned long long *)ctx->Wfix.p, (unsigned long long *)ctx->Pifix.p, N, M, q,
-                         (gdca_dev_scalars *)ctx->sc.p);
+    uint32_t *keep = skip ? (uint32_t *)ctx->keep.p : nullptr;
+    int *keep_n = skip ? (int *)((char *)ctx->keep.p + keep_list) : nullptr;
+    uint8_t *sigma = skip ? (uint8_t *)(keep_n + N) : nullptr;
+    gdca_launch_relayout(s, Zd, (int8_t *)ctx->Zt.p, (int8_t *)ctx->Zp.p, N, M, TJ);
+    // single-site sums and (TALLY_SKIP) the lists of the pair tally: one kernel over Zt, every output stored by its one owner
+    gdca_launch_pi_keep(s, (const int8_t *)ctx->Zt.p, (const unsigned long long *)ctx->Wfix.p, (unsigned long long *)ctx->Pifix.p, keep, keep_n,
+                        sigma, N, M, q, (gdca_dev_scalars *)ctx->sc.p);
     gdca_launch_pi_finalize(s, (const unsigned long long *)ctx->Pifix.p, N, q, shift, Meff_dev, pc, Pi_true_out,
                             (double *)ctx->Pipc.p, want_norm1 ? &((gdca_dev_scalars *)ctx->sc.p)->pi_max : nullptr);
     const bool tm = want_norm1 && ctx->timing && ctx->n_ev >= 18;  // (the fused path's first build: its own device time, gdca_stats.ms_pair_tally)
     if (tm) CHK(mark(ctx, 9));
-    uint32_t *keep = skip ? (uint32_t *)ctx->keep.p : nullptr;
-    int *keep_n = skip ? (int *)((char *)ctx->keep.p + keep_list) : nullptr;
-    uint8_t *sigma = skip ? (uint8_t *)(keep_n + N) : nullptr;
-    if (skip)  // (inside events 9 / 10: gdca_stats.ms_pair_tally is the whole tally)
-        gdca_launch_tally_keep(s, (const int8_t *)ctx->Zt.p, (const unsigned long long *)ctx->Pifix.p, keep, keep_n, sigma, N, M, q);
     gdca_launch_pair_tally(s, (const int8_t *)ctx->Zp.p, (const int8_t *)ctx->Zt.p,
                            (const unsigned long long *)ctx->Wfix.p, N, M, q, shift, Meff_dev, pc,
                            (const double *)ctx->Pipc.p, mode, out, ld, TJ, keep, keep_n, sigma,

@@ -78,8 +78,11 @@ void gdca_tuning_from_env(gdca_tuning *t);
 bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value);
 
 // ---- k_theta.hip -------------------------------------------------------------------------
-void gdca_launch_transpose_i8(hipStream_t s, const int8_t *Z, int8_t *Zt, int N, int M);
-// cnt: uint32 [N][32], zeroed by the caller
+// Z [M][N] (any alignment) -> Zt [N][M] (Z transposed) and Zc [ceil(N/TJ)][M][TJ] (zero padded; 16-byte aligned), TJ = gdca_tally_tj(q)
+void gdca_launch_relayout(hipStream_t s, const int8_t *Z, int8_t *Zt, int8_t *Zc, int N, int M, int TJ);
+// cnt: gdca_column_hist_bytes(N, M) bytes: uint32 [N][32], the counts (every one written: nothing to zero), then the kernel's
+// per-chunk partial counts
+size_t gdca_column_hist_bytes(int N, int M);
 void gdca_launch_column_hist(hipStream_t s, const int8_t *Z, uint32_t *cnt, int N, int M);
 // theta_in < 0: theta = :auto from cnt; else theta = theta_in.  Writes theta, thresh, pair_sum.
 void gdca_launch_theta_finalize(hipStream_t s, const uint32_t *cnt, int N, int M, double theta_in,
@@ -115,9 +118,12 @@ void gdca_launch_fix_weights(hipStream_t s, const double *W, int M, int fix_shif
 int gdca_fix_shift(int M);
 
 // ---- k_tally.hip -------------------------------------------------------------------------
-// Pifix: u64 [N][32] zeroed by the caller; adds sum_k Wfix[k] [Z[i,k]==a] at [i][a-1]
-void gdca_launch_pi_tally(hipStream_t s, const int8_t *Z, const unsigned long long *Wfix,
-                          unsigned long long *Pifix, int N, int M, int q, gdca_dev_scalars *sc);
+// Pifix: u64 [N][32], every entry written: sum_k Wfix[k] [Z[i,k] & 31 == z] at [i][z] (bytes outside 1..q set bit 0 of sc->bad_symbol).
+// Zt: Z transposed (N rows of M; 4-byte aligned, 3 bytes of slack behind it).  keep != nullptr (TALLY_SKIP): also keep (uint32
+// [N][M]; per column i: keep_n[i] entries (k << 5) | Z[i,k], ascending k, every sequence whose Z[i,k] is a legal symbol other than
+// sigma[i] = the argmax of Pifix[i][1..q], ties to the smallest), keep_n and sigma
+void gdca_launch_pi_keep(hipStream_t s, const int8_t *Zt, const unsigned long long *Wfix, unsigned long long *Pifix, uint32_t *keep,
+                         int *keep_n, uint8_t *sigma, int N, int M, int q, gdca_dev_scalars *sc);
 // Pi_true[i*s+a] = Pifix * 2^-shift / Meff;  Pi_pc = (1-pc) Pi_true + pc/q
 void gdca_launch_pi_finalize(hipStream_t s, const unsigned long long *Pifix, int N, int q, int fix_shift,
                              const double *Meff_dev, double pc, double *Pi_true, double *Pi_pc, double *pi_max = nullptr);
@@ -127,16 +133,11 @@ void gdca_launch_cov_norm1(hipStream_t s, const double *C, size_t ld, int N, int
                            int always);
 // Pair tallies.  mode 0: out = Pij_true (full symmetric, ld);  mode 1: out = C =
 // add_pseudocount + compute_C fused (full symmetric, ld).  Pi_pc used by mode 1 only.
-// Zc: the alignment regrouped as [ceil(N/TJ)][M][TJ] (gdca_launch_colblock), TJ = gdca_tally_tj(q).
+// Zc: the alignment regrouped as [ceil(N/TJ)][M][TJ] (gdca_launch_relayout), TJ = gdca_tally_tj(q).
 int gdca_tally_tj(int q, int tj_wanted);
-void gdca_launch_colblock(hipStream_t s, const int8_t *Z, int8_t *Zc, int N, int M, int TJ);
 // TALLY_SKIP where the [q][q][TJ] histograms fit as many workgroups per CU as the full loop's (and M <= 2^27)
 bool gdca_tally_skip(int q, int TJ, int skip_wanted, int M);
-// keep: uint32 [N][M] (per column i: keep_n[i] entries (k << 5) | Z[i,k], ascending k, every sequence whose Z[i,k] is a legal
-// symbol other than sigma[i] = the argmax of Pifix[i][1..q], ties to the smallest); Zt: Z transposed (N rows of M)
-void gdca_launch_tally_keep(hipStream_t s, const int8_t *Zt, const unsigned long long *Pifix, uint32_t *keep, int *keep_n,
-                            uint8_t *sigma, int N, int M, int q);
-// keep == nullptr: the full loop over all M sequences; else keep / keep_n / sigma of gdca_launch_tally_keep and Pifix (the SKIP form)
+// keep == nullptr: the full loop over all M sequences; else keep / keep_n / sigma of gdca_launch_pi_keep and Pifix (the SKIP form)
 void gdca_launch_pair_tally(hipStream_t s, const int8_t *Zc, const int8_t *Zt, const unsigned long long *Wfix,
                             int N, int M, int q, int fix_shift, const double *Meff_dev, double pc,
                             const double *Pi_pc, int mode, double *out, size_t ld, int TJ, const uint32_t *keep = nullptr,

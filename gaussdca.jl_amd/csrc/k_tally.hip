@@ -25,80 +25,199 @@
 
 typedef unsigned long long u64;
 
-// ---- single-site sums -----------------------------------------------------------------------------
-struct k_pi_tally_args {
-    const int8_t *Z;
+// ---- single-site sums and the sequences each column's pair tally visits: one kernel over Zt, one workgroup per column ------------
+// Column i's M bytes are contiguous in Zt (k_relayout has just written them).  The row is walked in ALIGNED dwords -- four
+// consecutive sequences per lane; where the row does not start on a dword (M % 4 != 0) the first and last dword reach into the
+// neighbouring rows and those bytes are masked by their sequence index, so Zt needs 4-byte alignment and 3 bytes of slack.
+//
+// Pass one: Pifix[i][z] = sum_k Wfix[k] [Zt[i][k] & 31 == z] in u64, all 32 of them (bytes outside 1..q land where their low five
+// bits say and set bit 0 of sc->bad_symbol).  The sums are taken in bins[z][lane] in LDS: the lane index makes the 64 lanes of an
+// ds_add_u64 conflict-free whatever the symbols are, the workgroup's waves share the bins, and nothing waits for an add.  The 64
+// partial sums of a symbol are then added in a fixed order (integers: any order gives these bits) and stored -- one owner per sum.
+//
+// Pass two (TALLY_SKIP: keep != nullptr), from the same bytes, now in L2:
+// sigma(i) = the symbol of column i with the largest single-site sum (1..q, ties to the smallest).  Only the sequences whose
+// Z[i,k] is a legal symbol other than sigma(i) are tallied by k_pair_tally; row sigma(i) of every histogram is recovered afterwards
+// from the column sums  sum_a H[a][b] = Pifix[j][b]  in u64 (exact: wrap-around cancels, the true value is < 2^63).  Those
+// sequences are written in ascending order as  (k << 5) | Z[i,k]  into keep[i][0 .. keep_n[i]-1]: wave ballots place a kept
+// sequence inside its wave, one wave scans the (slab, wave) counts of a step of PIK_THREADS * PIK_SLABS * 4 sequences.
+#define PIK_THREADS 512  // (measured at N = 500, M = 50 000: 256 threads 52.7 us, 512 39.0, 1024 47.5)
+#define PIK_SLABS 4
+struct k_pi_keep_args {
+    const int8_t *Zt;
     const u64 *Wfix;
     u64 *Pifix;
+    uint32_t *keep;
+    int *keep_n;
+    uint8_t *sigma;
     int N;
     int M;
-    int seq_per_block;
     int q;
     gdca_dev_scalars *sc;
 };
-static inline k_pi_tally_args k_pi_tally_mk(const int8_t *Z, const u64 *Wfix, u64 *Pifix, int N, int M, int seq_per_block, int q, gdca_dev_scalars *sc)
+static inline k_pi_keep_args k_pi_keep_mk(const int8_t *Zt, const u64 *Wfix, u64 *Pifix, uint32_t *keep, int *keep_n, uint8_t *sigma, int N, int M, int q, gdca_dev_scalars *sc)
 {
-    return k_pi_tally_args{Z, Wfix, Pifix, N, M, seq_per_block, q, sc};
+    return k_pi_keep_args{Zt, Wfix, Pifix, keep, keep_n, sigma, N, M, q, sc};
 }
 template <int CAP>
-__global__ __launch_bounds__(128) void k_pi_tally(const BatchArgs<k_pi_tally_args, CAP> B_)
+__global__ __launch_bounds__(PIK_THREADS) void k_pi_keep(const BatchArgs<k_pi_keep_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
-    const int8_t *__restrict__ Z = a_.Z;
     const u64 *__restrict__ Wfix = a_.Wfix;
     u64 *__restrict__ Pifix = a_.Pifix;
-    int N = a_.N;
+    uint32_t *__restrict__ keep = a_.keep;
     int M = a_.M;
-    int seq_per_block = a_.seq_per_block;
     int q = a_.q;
     gdca_dev_scalars *sc = a_.sc;
-    __shared__ u64 h[32][128];
+    constexpr int NW = PIK_THREADS / 64;
+    constexpr int NC = PIK_SLABS * NW;  // (slab, wave) counts of one step, slab-major = ascending k
+    static_assert(PIK_THREADS >= 256 && NC <= 64, "the fold below takes 256 threads; one wave scans the counts");
+    __shared__ u64 bins[32 * 64];
+    __shared__ u64 tot[32];
+    __shared__ unsigned wcnt[2][NC], woff[2][NC + 1];
+    const int i = blockIdx.x;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int8_t *zi = a_.Zt + (size_t)i * M;
+    const int off = (int)(reinterpret_cast<uintptr_t>(zi) & 3);
+    const uint32_t *__restrict__ zw = reinterpret_cast<const uint32_t *>(zi - off);  // dword d holds sequences 4 d - off .. + 3
+    const int D = (off + M + 3) >> 2;
+    const bool wpair = off == 0 && (reinterpret_cast<uintptr_t>(Wfix) & 15) == 0;  // four weights of a dword as two 16-byte loads
+    for (int e = t; e < 32 * 64; e += PIK_THREADS) bins[e] = 0;
+    __syncthreads();
     unsigned bad = 0;  // any byte outside 1..q
-    const int t = threadIdx.x;
-    const int i = blockIdx.x * 128 + t;
+    for (int d0 = 0; d0 < D; d0 += PIK_THREADS * PIK_SLABS) {
+        uint32_t z[PIK_SLABS];
+        u64 w[PIK_SLABS][4];
 #pragma unroll
-    for (int z = 0; z < 32; ++z) h[z][t] = 0;
-    const int kbeg = blockIdx.y * seq_per_block;
-    const int kend = min(M, kbeg + seq_per_block);
-    if (i < N) {
-        const int8_t *p = Z + (size_t)kbeg * N + i;
-        int k = kbeg;
-        for (; k + 16 <= kend; k += 16) {  // 16 strided byte loads in flight before the dependent LDS adds
-            int z[16];
+        for (int u = 0; u < PIK_SLABS; ++u) {
+            const int d = d0 + u * PIK_THREADS + t;
+            const int k = 4 * d - off;
+            z[u] = 0;
 #pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const unsigned raw = (uint8_t)p[(size_t)u * N];
-                bad |= (raw - 1u) >= (unsigned)q;
-                z[u] = raw & 31;
+            for (int j = 0; j < 4; ++j) w[u][j] = 0;
+            if (d < D) {
+                z[u] = zw[d];
+                if (wpair && k + 3 < M) {
+                    const ulonglong2 w0 = reinterpret_cast<const ulonglong2 *>(Wfix + k)[0];
+                    const ulonglong2 w1 = reinterpret_cast<const ulonglong2 *>(Wfix + k)[1];
+                    w[u][0] = w0.x;
+                    w[u][1] = w0.y;
+                    w[u][2] = w1.x;
+                    w[u][3] = w1.y;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if ((unsigned)(k + j) < (unsigned)M) w[u][j] = Wfix[k + j];
+                }
             }
+        }
 #pragma unroll
-            for (int u = 0; u < 16; ++u) h[z[u]][t] += Wfix[k + u];
-            p += (size_t)16 * N;
-        }
-        for (; k < kend; ++k) {
-            const unsigned raw = (uint8_t)p[0];
-            bad |= (raw - 1u) >= (unsigned)q;
-            h[raw & 31][t] += Wfix[k];
-            p += N;
-        }
-        if (bad) atomicOr(&sc->bad_symbol, 1);
+        for (int u = 0; u < PIK_SLABS; ++u) {
+            const int d = d0 + u * PIK_THREADS + t;
+            const int k = 4 * d - off;
+            if (d < D) {
 #pragma unroll
-        for (int z = 0; z < 32; ++z) {
-            const u64 v = h[z][t];
-            if (v) atomicAdd(&Pifix[(size_t)i * 32 + z], v);
+                for (int j = 0; j < 4; ++j) {
+                    if ((unsigned)(k + j) < (unsigned)M) {
+                        const unsigned raw = (z[u] >> (8 * j)) & 255u;
+                        bad |= (raw - 1u) >= (unsigned)q;
+                        atomicAdd(&bins[(raw & 31u) * 64 + lane], w[u][j]);
+                    }
+                }
+            }
         }
+    }
+    if (bad) atomicOr(&sc->bad_symbol, 1);
+    __syncthreads();
+    if (t < 256) {  // eight threads fold the 64 partial sums of one symbol
+        const int z = t >> 3, part = t & 7;
+        u64 v = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v += bins[z * 64 + part * 8 + e];
+        v += __shfl_xor(v, 1, 64);
+        v += __shfl_xor(v, 2, 64);
+        v += __shfl_xor(v, 4, 64);
+        if (part == 0) {
+            tot[z] = v;
+            Pifix[(size_t)i * 32 + z] = v;
+        }
+    }
+    if (keep == nullptr) return;  // (uniform) the full loop needs no lists
+    __syncthreads();
+    unsigned sig = 1;
+    u64 best = tot[1];
+    for (int a = 2; a <= q; ++a) {
+        const u64 v = tot[a];
+        if (v > best) {
+            best = v;
+            sig = (unsigned)a;
+        }
+    }
+    uint32_t *out = keep + (size_t)i * M;
+    const u64 lt = (1ull << lane) - 1ull;
+    unsigned base = 0;
+    int par = 0;  // wcnt / woff are double-buffered by the step's parity: two barriers per step
+    for (int d0 = 0; d0 < D; d0 += PIK_THREADS * PIK_SLABS, par ^= 1) {
+        uint32_t z[PIK_SLABS];
+        unsigned kpm[PIK_SLABS], pos[PIK_SLABS];
+#pragma unroll
+        for (int u = 0; u < PIK_SLABS; ++u) {
+            const int d = d0 + u * PIK_THREADS + t;
+            z[u] = d < D ? zw[d] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < PIK_SLABS; ++u) {
+            const int d = d0 + u * PIK_THREADS + t;
+            const int k = 4 * d - off;
+            unsigned m = 0, pre = 0, cnt = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned raw = (z[u] >> (8 * j)) & 255u;
+                const bool kp = d < D && (unsigned)(k + j) < (unsigned)M && (raw - 1u) < (unsigned)q && raw != sig;
+                const u64 bal = __ballot(kp);
+                pre += (unsigned)__popcll(bal & lt);
+                cnt += (unsigned)__popcll(bal);
+                m |= (kp ? 1u : 0u) << j;
+            }
+            kpm[u] = m;
+            pos[u] = pre;  // kept sequences of this slab in the lanes below this one
+            if (lane == 0) wcnt[par][u * NW + wv] = cnt;
+        }
+        __syncthreads();
+        if (wv == 0) {
+            const unsigned v = lane < NC ? wcnt[par][lane] : 0u;
+            unsigned incl = v;
+#pragma unroll
+            for (int o = 1; o < NC; o <<= 1) {
+                const unsigned nb = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += nb;
+            }
+            if (lane < NC) woff[par][lane] = base + incl - v;
+            if (lane == NC - 1) woff[par][NC] = base + incl;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < PIK_SLABS; ++u) {
+            if (kpm[u]) {
+                const int k = 4 * (d0 + u * PIK_THREADS + t) - off;
+                unsigned o = woff[par][u * NW + wv] + pos[u];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((kpm[u] >> j) & 1u) out[o++] = ((unsigned)(k + j) << 5) | ((z[u] >> (8 * j)) & 255u);
+            }
+        }
+        base = woff[par][NC];
+    }
+    if (t == 0) {
+        a_.keep_n[i] = (int)base;
+        a_.sigma[i] = (uint8_t)sig;
     }
 }
 
-void gdca_launch_pi_tally(hipStream_t s, const int8_t *Z, const u64 *Wfix, u64 *Pifix, int N, int M, int q,
-                          gdca_dev_scalars *sc)
+void gdca_launch_pi_keep(hipStream_t s, const int8_t *Zt, const u64 *Wfix, u64 *Pifix, uint32_t *keep, int *keep_n, uint8_t *sigma, int N, int M,
+                         int q, gdca_dev_scalars *sc)
 {
-    const int cb = (N + 127) / 128;
-    int chunks = (512 + cb - 1) / cb;  // every chunk ends in one global atomic per counter
-    int spb = (M + chunks - 1) / chunks;
-    if (spb < 64) spb = 64;
-    chunks = (M + spb - 1) / spb;
-    (gdca_launch<k_pi_tally_args, k_pi_tally<1>, k_pi_tally<GDCA_MAXB>>(dim3(cb, chunks), dim3(128), 0, s, k_pi_tally_mk(Z, Wfix, Pifix, N, M, spb, q, sc)));
+    (gdca_launch<k_pi_keep_args, k_pi_keep<1>, k_pi_keep<GDCA_MAXB>>(dim3(N, 1), dim3(PIK_THREADS), 0, s, k_pi_keep_mk(Zt, Wfix, Pifix, keep, keep_n, sigma, N, M, q, sc)));
 }
 
 struct k_pi_finalize_args {
@@ -216,143 +335,6 @@ void gdca_launch_pi_finalize(hipStream_t s, const u64 *Pifix, int N, int q, int 
 #define TALLY_THREADS 1024
 #define TALLY_CHUNK 1024  // sequences staged per pass (one per thread)
 
-// Z [M][N] -> Zc [ceil(N/TJ)][M][TJ] (zero padded): for one column block the TJ bytes of
-// consecutive sequences are consecutive in memory, so a workgroup's staging loads are fully
-// coalesced 16-byte accesses with no over-fetch.  Tile transpose through LDS.
-struct k_colblock_args {
-    const int8_t *Z;
-    int8_t *Zc;
-    int N;
-    int M;
-    int TJ;
-};
-static inline k_colblock_args k_colblock_mk(const int8_t *Z, int8_t *Zc, int N, int M, int TJ)
-{
-    return k_colblock_args{Z, Zc, N, M, TJ};
-}
-template <int CAP>
-__global__ __launch_bounds__(256) void k_colblock(const BatchArgs<k_colblock_args, CAP> B_)
-{
-    GDCA_MEMBER(B_);
-    const int8_t *__restrict__ Z = a_.Z;
-    int8_t *__restrict__ Zc = a_.Zc;
-    int N = a_.N;
-    int M = a_.M;
-    int TJ = a_.TJ;
-    __shared__ int8_t tile[64][64 + 4];
-    const int k0 = blockIdx.y * 64, c0 = blockIdx.x * 64;  // 64 sequences x 64 columns
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int k = k0 + r * 4 + ty, c = c0 + tx;
-        tile[r * 4 + ty][tx] = (k < M && c < N) ? Z[(size_t)k * N + c] : (int8_t)0;
-    }
-    __syncthreads();
-    // write: for each column block inside this 64-column strip, rows of TJ bytes per sequence
-    const int nb = 64 / TJ;  // column blocks in the strip (2 or 4)
-    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-        const int blk = e / (64 * TJ), rem = e % (64 * TJ);
-        const int kl = rem / TJ, cl = rem % TJ;
-        const int k = k0 + kl;
-        const int cb = c0 / TJ + blk;
-        if (blk < nb && k < M && cb * TJ < ((N + TJ - 1) / TJ) * TJ)
-            Zc[((size_t)cb * M + k) * TJ + cl] = tile[kl][blk * TJ + cl];
-    }
-}
-
-void gdca_launch_colblock(hipStream_t s, const int8_t *Z, int8_t *Zc, int N, int M, int TJ)
-{
-    dim3 grid((N + 63) / 64, (M + 63) / 64);
-    (gdca_launch<k_colblock_args, k_colblock<1>, k_colblock<GDCA_MAXB>>(grid, dim3(256), 0, s, k_colblock_mk(Z, Zc, N, M, TJ)));
-}
-
-// ---- the sequences the pair tally of column i has to visit (TALLY_SKIP) ----
-// sigma(i) = the symbol of column i with the largest single-site sum Pifix[i][.] (1..q, ties to the smallest).  Only the sequences
-// whose Z[i,k] is a legal symbol other than sigma(i) are tallied; row sigma(i) of every histogram is recovered afterwards from the
-// column sums  sum_a H[a][b] = Pifix[j][b]  in u64 (exact: wrap-around cancels, the true value is < 2^63).  This kernel writes, per
-// column i, those sequences in ascending order as  (k << 5) | Z[i,k]  into keep[i][0 .. keep_n[i]-1], and sigma[i].
-// One workgroup per column, 256 threads x KEEP_SLABS sequences per step: a wave ballot gives each kept sequence its place.
-#define KEEP_THREADS 256
-#define KEEP_SLABS 16
-struct k_tally_keep_args {
-    const int8_t *Zt;
-    const u64 *Pifix;
-    uint32_t *keep;
-    int *keep_n;
-    uint8_t *sigma;
-    int N;
-    int M;
-    int q;
-};
-static inline k_tally_keep_args k_tally_keep_mk(const int8_t *Zt, const u64 *Pifix, uint32_t *keep, int *keep_n, uint8_t *sigma, int N, int M, int q)
-{
-    return k_tally_keep_args{Zt, Pifix, keep, keep_n, sigma, N, M, q};
-}
-template <int CAP>
-__global__ __launch_bounds__(KEEP_THREADS) void k_tally_keep(const BatchArgs<k_tally_keep_args, CAP> B_)
-{
-    GDCA_MEMBER(B_);
-    const int8_t *__restrict__ Zt = a_.Zt;
-    const u64 *__restrict__ Pifix = a_.Pifix;
-    uint32_t *__restrict__ keep = a_.keep;
-    int M = a_.M;
-    int q = a_.q;
-    constexpr int NW = KEEP_THREADS / 64;
-    __shared__ unsigned wcnt[KEEP_SLABS * NW], woff[KEEP_SLABS * NW];  // kept sequences per (slab, wave), slab-major = ascending k
-    const int i = blockIdx.x;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const u64 *P = Pifix + (size_t)i * 32;
-    unsigned sig = 1;
-    u64 best = P[1];
-    for (int a = 2; a <= q; ++a) {
-        const u64 v = P[a];
-        if (v > best) {
-            best = v;
-            sig = (unsigned)a;
-        }
-    }
-    const int8_t *zi = Zt + (size_t)i * M;
-    uint32_t *out = keep + (size_t)i * M;
-    const u64 lt = (1ull << lane) - 1ull;
-    unsigned base = 0;
-    for (int kc = 0; kc < M; kc += KEEP_THREADS * KEEP_SLABS) {
-        unsigned raw[KEEP_SLABS], pos[KEEP_SLABS];
-#pragma unroll
-        for (int u = 0; u < KEEP_SLABS; ++u) {
-            const int k = kc + u * KEEP_THREADS + t;
-            raw[u] = k < M ? (unsigned)(uint8_t)zi[k] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < KEEP_SLABS; ++u) {
-            const bool kp = (raw[u] - 1u) < (unsigned)q && raw[u] != sig;
-            const u64 bal = __ballot(kp);
-            pos[u] = kp ? (unsigned)__popcll(bal & lt) : ~0u;
-            if (lane == 0) wcnt[u * NW + wv] = (unsigned)__popcll(bal);
-        }
-        __syncthreads();
-        if (t < KEEP_SLABS * NW) {
-            unsigned o = base;
-            for (int e = 0; e < t; ++e) o += wcnt[e];
-            woff[t] = o;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < KEEP_SLABS; ++u)
-            if (pos[u] != ~0u) out[woff[u * NW + wv] + pos[u]] = ((unsigned)(kc + u * KEEP_THREADS + t) << 5) | raw[u];
-        base = woff[KEEP_SLABS * NW - 1] + wcnt[KEEP_SLABS * NW - 1];
-        __syncthreads();  // wcnt / woff are rewritten by the next step
-    }
-    if (t == 0) {
-        a_.keep_n[i] = (int)base;
-        a_.sigma[i] = (uint8_t)sig;
-    }
-}
-
-void gdca_launch_tally_keep(hipStream_t s, const int8_t *Zt, const u64 *Pifix, uint32_t *keep, int *keep_n, uint8_t *sigma, int N, int M, int q)
-{
-    (gdca_launch<k_tally_keep_args, k_tally_keep<1>, k_tally_keep<GDCA_MAXB>>(dim3(N), dim3(KEEP_THREADS), 0, s, k_tally_keep_mk(Zt, Pifix, keep, keep_n, sigma, N, M, q)));
-}
-
 // Workgroup = (column i) x (block of TJ columns j >= i's block), 1024 threads = 16 waves (the
 // histograms take most of the LDS, so one workgroup per CU: the waves have to come from here).
 // Per pass of 1024 sequences the block's TJ bytes of every sequence and a packed
@@ -365,7 +347,7 @@ void gdca_launch_tally_keep(hipStream_t s, const int8_t *Zt, const u64 *Pifix, u
 // the inner loop needs no validity test at all: an invalid Z[i,k] is staged as weight 0, lanes left
 // of the diagonal tally into columns the epilogue never reads.
 //
-// SKIP (TALLY_SKIP, the default where it fits): the staged sequences of column i are k_tally_keep's list -- every sequence but
+// SKIP (TALLY_SKIP, the default where it fits): the staged sequences of column i are k_pi_keep's list -- every sequence but
 // those with Z[i,k] = sigma(i) or an illegal byte -- so at config C a pass of 1024 staged sequences is 1024 useful ones out of
 // ~2400.  The histogram then has a row AND a column per symbol, [q][q][TJ] indexed by symbol - 1 (the gap's row takes the gap
 // sequences, which the recovery needs; the gap's column also takes the zero padding and any illegal byte), and row sigma(i) is
@@ -385,7 +367,7 @@ struct k_pair_tally_args {
     int mode;
     double *out;
     size_t ld;
-    const uint32_t *keep;   // SKIP: k_tally_keep's lists, keep_n, sigma; Pifix for the recovery
+    const uint32_t *keep;   // SKIP: k_pi_keep's lists, keep_n, sigma; Pifix for the recovery
     const int *keep_n;
     const uint8_t *sigma;
     const u64 *Pifix;

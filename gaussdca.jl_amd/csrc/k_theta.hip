@@ -8,111 +8,244 @@
 #include "gdca_internal.h"
 #include "gdca_launch.h"
 
-// ---- Z [M][N] -> Zt [N][M] (byte transpose through LDS, 64 x 64 tiles) ---------------------
-struct k_transpose_i8_args {
+// ---- Z [M][N] -> Zt [N][M] and Zc [ceil(N/TJ)][M][TJ] in one pass (64 x 64 byte tiles through LDS) --------------------------
+// The tile is read once -- one dword (four neighbouring columns) per lane where the rows are 4-byte aligned (N % 4 == 0 and an
+// aligned Z), byte by byte otherwise: Z is the caller's pointer -- and leaves twice:
+//   Zt: a thread transposes a 4 x 4 byte block in registers and stores one dword (four consecutive sequences) per column;
+//   Zc: the TJ bytes of (column block, sequence) are contiguous in the tile's row: one 16-byte store per thread.
+// Zc is what k_pair_tally stages from (zero padded up to the last column block; 16-byte aligned: the context's own buffer).
+struct k_relayout_args {
     const int8_t *Z;
     int8_t *Zt;
+    int8_t *Zc;
     int N;
     int M;
+    int TJ;
 };
-static inline k_transpose_i8_args k_transpose_i8_mk(const int8_t *Z, int8_t *Zt, int N, int M)
+static inline k_relayout_args k_relayout_mk(const int8_t *Z, int8_t *Zt, int8_t *Zc, int N, int M, int TJ)
 {
-    return k_transpose_i8_args{Z, Zt, N, M};
+    return k_relayout_args{Z, Zt, Zc, N, M, TJ};
 }
 template <int CAP>
-__global__ __launch_bounds__(256) void k_transpose_i8(const BatchArgs<k_transpose_i8_args, CAP> B_)
+__global__ __launch_bounds__(256) void k_relayout(const BatchArgs<k_relayout_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
     const int8_t *__restrict__ Z = a_.Z;
     int8_t *__restrict__ Zt = a_.Zt;
+    int8_t *__restrict__ Zc = a_.Zc;
     int N = a_.N;
     int M = a_.M;
-    __shared__ int8_t tile[64][65];
-    const int k0 = blockIdx.y * 64, i0 = blockIdx.x * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    int TJ = a_.TJ;
+    __shared__ uint32_t tile[64][17];  // [sequence][four columns]; 17: the transposed reads below hit 64 different banks
+    const int k0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+    const int t = threadIdx.x;
+    if (((N & 3) == 0) && ((reinterpret_cast<uintptr_t>(Z) & 3) == 0)) {
+        const int d = t & 15, c = c0 + 4 * d;  // (N % 4 == 0: a dword is inside the row or outside it, never across its end)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int k = k0 + r * 4 + ty, i = i0 + tx;
-        tile[r * 4 + ty][tx] = (k < M && i < N) ? Z[(size_t)k * N + i] : (int8_t)0;
+        for (int r = 0; r < 4; ++r) {
+            const int kl = r * 16 + (t >> 4), k = k0 + kl;
+            uint32_t v = 0;
+            if (k < M && c < N) v = *reinterpret_cast<const uint32_t *>(Z + (size_t)k * N + c);
+            tile[kl][d] = v;
+        }
+    } else {
+        uint8_t *tb = reinterpret_cast<uint8_t *>(&tile[0][0]);
+        const int tx = t & 63, ty = t >> 6;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int kl = r * 4 + ty, k = k0 + kl, c = c0 + tx;
+            tb[kl * 68 + tx] = (k < M && c < N) ? (uint8_t)Z[(size_t)k * N + c] : (uint8_t)0;
+        }
     }
     __syncthreads();
+    {  // Zc: 64 sequences x (64 / TJ) column blocks x (TJ / 16) 16-byte pieces = 256 stores, one per thread
+        const int q16 = TJ >> 4;
+        const int blk = t / (64 * q16), rem = t % (64 * q16);
+        const int kl = rem / q16, h = rem % q16;
+        const int k = k0 + kl, cb = c0 / TJ + blk;
+        if (k < M && cb * TJ < N) {  // (column blocks past the last one that holds a column are not written)
+            const int d0 = blk * (TJ >> 2) + 4 * h;
+            const uint4 v = make_uint4(tile[kl][d0], tile[kl][d0 + 1], tile[kl][d0 + 2], tile[kl][d0 + 3]);
+            *reinterpret_cast<uint4 *>(Zc + ((size_t)cb * M + k) * TJ + 16 * h) = v;
+        }
+    }
+    {  // Zt: thread = (four sequences bk, four columns bc)
+        const bool wide = ((M & 3) == 0) && ((reinterpret_cast<uintptr_t>(Zt) & 3) == 0);
+        const int bk = t & 15, bc = t >> 4;
+        uint32_t r[4];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int i = i0 + r * 4 + ty, k = k0 + tx;
-        if (i < N && k < M) Zt[(size_t)i * M + k] = tile[tx][r * 4 + ty];
+        for (int j = 0; j < 4; ++j) r[j] = tile[4 * bk + j][bc];
+        const int k = k0 + 4 * bk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = c0 + 4 * bc + j;
+            const uint32_t o = ((r[0] >> (8 * j)) & 255u) | (((r[1] >> (8 * j)) & 255u) << 8) | (((r[2] >> (8 * j)) & 255u) << 16) |
+                               (((r[3] >> (8 * j)) & 255u) << 24);
+            if (i < N && k < M) {
+                int8_t *dst = Zt + (size_t)i * M + k;
+                if (wide) {
+                    *reinterpret_cast<uint32_t *>(dst) = o;  // (M % 4 == 0: k + 3 < M)
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (k + e < M) dst[e] = (int8_t)((o >> (8 * e)) & 255u);
+                }
+            }
+        }
     }
 }
 
-void gdca_launch_transpose_i8(hipStream_t s, const int8_t *Z, int8_t *Zt, int N, int M)
+void gdca_launch_relayout(hipStream_t s, const int8_t *Z, int8_t *Zt, int8_t *Zc, int N, int M, int TJ)
 {
     dim3 grid((N + 63) / 64, (M + 63) / 64);
-    (gdca_launch<k_transpose_i8_args, k_transpose_i8<1>, k_transpose_i8<GDCA_MAXB>>(grid, dim3(256), 0, s, k_transpose_i8_mk(Z, Zt, N, M)));
+    (gdca_launch<k_relayout_args, k_relayout<1>, k_relayout<GDCA_MAXB>>(grid, dim3(256), 0, s, k_relayout_mk(Z, Zt, Zc, N, M, TJ)));
 }
 
 // ---- per-column symbol counts ---------------------------------------------------------------
-// One thread owns one alignment column; its 32 counters sit in LDS as h[z][thread] so that a
-// wave's 64 lanes always hit 64 different banks whatever the symbols are.  No atomics inside
-// the workgroup (each counter has one owner); one global integer atomic per non-zero counter.
+// A workgroup owns a strip of 256 columns over a chunk of the sequences.  A wave reads one sequence's 256 bytes of the strip per
+// instruction -- a dword, four neighbouring columns, per lane (byte loads where the rows are not 4-byte aligned) -- with
+// HIST_ROWS sequences in flight, and counts into h[symbol][j][lane] in LDS: lane and j name the column, so the 64 lanes of an
+// instruction hit 64 different banks whatever the symbols are, and the LDS adds (the workgroup's waves share the counters) return
+// nothing the loop waits for.  Every counter of the output has ONE writer: chunk y's counts go to out + y * N * 32 with plain
+// stores, and where the sequences are split k_column_hist_sum adds the chunks in a fixed order.  No global atomics, nothing to zero.
+#define HIST_THREADS 1024  // (measured at N = 500, M = 50 000: 512 threads 17.1 us, 1024 14.2)
+#define HIST_ROWS 8
 struct k_column_hist_args {
     const int8_t *Z;
-    uint32_t *cnt;
+    uint32_t *out;
     int N;
     int M;
     int seq_per_block;
 };
-static inline k_column_hist_args k_column_hist_mk(const int8_t *Z, uint32_t *cnt, int N, int M, int seq_per_block)
+static inline k_column_hist_args k_column_hist_mk(const int8_t *Z, uint32_t *out, int N, int M, int seq_per_block)
 {
-    return k_column_hist_args{Z, cnt, N, M, seq_per_block};
+    return k_column_hist_args{Z, out, N, M, seq_per_block};
 }
 template <int CAP>
-__global__ __launch_bounds__(256) void k_column_hist(const BatchArgs<k_column_hist_args, CAP> B_)
+__global__ __launch_bounds__(HIST_THREADS) void k_column_hist(const BatchArgs<k_column_hist_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
     const int8_t *__restrict__ Z = a_.Z;
-    uint32_t *__restrict__ cnt = a_.cnt;
+    uint32_t *__restrict__ out = a_.out;
     int N = a_.N;
     int M = a_.M;
     int seq_per_block = a_.seq_per_block;
-    __shared__ uint32_t h[32][256];
-    const int t = threadIdx.x;
-    const int i = blockIdx.x * 256 + t;
-#pragma unroll
-    for (int z = 0; z < 32; ++z) h[z][t] = 0;
+    constexpr int NW = HIST_THREADS / 64;
+    static_assert(HIST_THREADS >= 512, "the store of the counts takes 512 threads");
+    __shared__ __attribute__((aligned(16))) uint32_t h[32 * 256];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    for (int e = t; e < 32 * 256; e += HIST_THREADS) h[e] = 0;
+    const int c = blockIdx.x * 256 + 4 * lane;
+    const int nv = N - c < 4 ? N - c : 4;  // columns of this lane inside the alignment (<= 0: none)
     const int kbeg = blockIdx.y * seq_per_block;
     const int kend = min(M, kbeg + seq_per_block);
-    if (i < N) {
-        const int8_t *p = Z + (size_t)kbeg * N + i;
-        int k = kbeg;
-        // 16 strided byte loads in flight per thread before the dependent LDS increments: the loop is bound by
-        // memory latency, not by bandwidth (25 MB in total)
-        for (; k + 16 <= kend; k += 16) {
-            int z[16];
+    const bool wide = ((N & 3) == 0) && ((reinterpret_cast<uintptr_t>(Z) & 3) == 0);  // (then nv is 4 or <= 0)
+    __syncthreads();
+    if (nv > 0) {
+        for (int k = kbeg + wv; k < kend; k += NW * HIST_ROWS) {
+            uint32_t v[HIST_ROWS];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) z[u] = p[(size_t)u * N] & 31;
+            for (int u = 0; u < HIST_ROWS; ++u) {
+                const int ku = k + u * NW;
+                v[u] = 0;
+                if (ku < kend) {
+                    const int8_t *p = Z + (size_t)ku * N + c;
+                    if (wide) {
+                        v[u] = *reinterpret_cast<const uint32_t *>(p);
+                    } else {
 #pragma unroll
-            for (int u = 0; u < 16; ++u) h[z[u]][t] += 1;
-            p += (size_t)16 * N;
+                        for (int j = 0; j < 4; ++j)
+                            if (j < nv) v[u] |= (uint32_t)(uint8_t)p[j] << (8 * j);
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < HIST_ROWS; ++u) {
+                if (k + u * NW < kend) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (j < nv) atomicAdd(&h[((v[u] >> (8 * j)) & 31u) * 256 + j * 64 + lane], 1u);
+                }
+            }
         }
-        for (; k < kend; ++k) {
-            h[p[0] & 31][t] += 1;
-            p += N;
-        }
+    }
+    __syncthreads();
+    {  // thread = (column, half of the symbols): 16 counters, 64 contiguous bytes of the output
+        const int x = t & 255, half = t >> 8;
+        const int l = x & 63, j = x >> 6;
+        const int col = blockIdx.x * 256 + 4 * l + j;
+        if (t < 512 && col < N) {
+            uint32_t *dst = out + ((size_t)blockIdx.y * N + col) * 32 + 16 * half;
 #pragma unroll
-        for (int z = 0; z < 32; ++z) {
-            const uint32_t v = h[z][t];
-            if (v) atomicAdd(&cnt[(size_t)i * 32 + z], v);
+            for (int g = 0; g < 4; ++g) {
+                const int z = 16 * half + 4 * g;
+                const uint4 o = make_uint4(h[z * 256 + j * 64 + l], h[(z + 1) * 256 + j * 64 + l], h[(z + 2) * 256 + j * 64 + l],
+                                           h[(z + 3) * 256 + j * 64 + l]);
+                reinterpret_cast<uint4 *>(dst)[g] = o;
+            }
         }
     }
 }
 
-void gdca_launch_column_hist(hipStream_t s, const int8_t *Z, uint32_t *cnt, int N, int M)
+struct k_column_hist_sum_args {
+    const uint32_t *part;
+    uint32_t *cnt;
+    int total;
+    int chunks;
+};
+static inline k_column_hist_sum_args k_column_hist_sum_mk(const uint32_t *part, uint32_t *cnt, int total, int chunks)
 {
-    const int cb = (N + 255) / 256;
-    int chunks = (256 + cb - 1) / cb;  // ~256 workgroups: every chunk ends in one global atomic per counter
+    return k_column_hist_sum_args{part, cnt, total, chunks};
+}
+template <int CAP>
+__global__ __launch_bounds__(256) void k_column_hist_sum(const BatchArgs<k_column_hist_sum_args, CAP> B_)
+{
+    GDCA_MEMBER(B_);
+    const uint32_t *__restrict__ part = a_.part;
+    uint32_t *__restrict__ cnt = a_.cnt;
+    int total = a_.total;
+    int chunks = a_.chunks;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    uint32_t acc = 0;
+    int c = 0;
+    for (; c + 8 <= chunks; c += 8) {
+        uint32_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(c + u) * total + e];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += v[u];
+    }
+    for (; c < chunks; ++c) acc += part[(size_t)c * total + e];
+    cnt[e] = acc;
+}
+
+// chunks the sequences are split into: about one workgroup per compute unit, at least 64 sequences each
+static int column_hist_split(int N, int M, int *spb_out)
+{
+    const int strips = (N + 255) / 256;
+    int chunks = (256 + strips - 1) / strips;
     int spb = (M + chunks - 1) / chunks;
     if (spb < 64) spb = 64;
     chunks = (M + spb - 1) / spb;
-    (gdca_launch<k_column_hist_args, k_column_hist<1>, k_column_hist<GDCA_MAXB>>(dim3(cb, chunks), dim3(256), 0, s, k_column_hist_mk(Z, cnt, N, M, spb)));
+    if (spb_out) *spb_out = spb;
+    return chunks;
+}
+
+size_t gdca_column_hist_bytes(int N, int M)
+{
+    const int chunks = column_hist_split(N, M, nullptr);
+    return (size_t)N * 32 * sizeof(uint32_t) * (size_t)(chunks > 1 ? 1 + chunks : 1);
+}
+
+void gdca_launch_column_hist(hipStream_t s, const int8_t *Z, uint32_t *cnt, int N, int M)
+{
+    int spb;
+    const int chunks = column_hist_split(N, M, &spb);
+    uint32_t *out = chunks > 1 ? cnt + (size_t)N * 32 : cnt;  // one chunk: its counts are the result
+    (gdca_launch<k_column_hist_args, k_column_hist<1>, k_column_hist<GDCA_MAXB>>(dim3((N + 255) / 256, chunks), dim3(HIST_THREADS), 0, s, k_column_hist_mk(Z, out, N, M, spb)));
+    if (chunks > 1)
+        (gdca_launch<k_column_hist_sum_args, k_column_hist_sum<1>, k_column_hist_sum<GDCA_MAXB>>(dim3((N * 32 + 255) / 256, 1), dim3(256), 0, s, k_column_hist_sum_mk(out, cnt, N * 32, chunks)));
 }
 
 // ---- theta, threshold -------------------------------------------------------------------------
