@@ -323,7 +323,7 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         {"GROUP", &t->group, -1, 4},        {"RAMP", &t->ramp, 0, 1},          {"RAGGED", &t->ragged, 0, 1},
         {"REM_TAIL", &t->rem_tail, -1, 1 << 20}, {"PANEL_HALVES", &t->panel_halves, -1, 1}, {"SLAB", &t->slab, 0, 1},
         {"RING", &t->ring, 2, 8},           {"MCUS", &t->mcus, -1, 32},        {"MCU_SOLO", &t->mcu_solo, -1, 1},       {"SWEEP_DEBUG", &t->sweep_debug, 0, 63}, {"SWEEP_RETRIES", &t->sweep_retries, 0, 5},
-        {"TALLY_TJ", &t->tally_tj, 0, 32},  {"TALLY_SKIP", &t->tally_skip, 0, 1}, {"MERGE", &t->merge, 1, 8},        {"MERGE_BLOCKS", &t->merge_blocks, 1, 64},
+        {"HAM_CUT", &t->ham_cut, 0, 1 << 20}, {"TALLY_TJ", &t->tally_tj, 0, 32},  {"TALLY_SKIP", &t->tally_skip, 0, 1}, {"MERGE", &t->merge, 1, 8},        {"MERGE_BLOCKS", &t->merge_blocks, 1, 64},
         {"MERGE_MCUS", &t->merge_mcus, -1, 16},  {"MERGE_GROUP", &t->merge_group, -1, 4}, {"MERGE_TILES", &t->merge_tiles, 1, 1 << 20},
         {"CHOLESKY", &t->cholesky, 0, 2},  {"PHASED_FRONTS", &t->phased_fronts, 0, 1}, {"PHASED_GRIDS", &t->phased_grids, -1, 8}, {"PHASED_STREAMS", &t->phased_streams, 1, 64},
         {"ENERGY_CHUNK", &t->energy_chunk, 0, 1 << 30}, {"PAIR_CHUNK", &t->pair_chunk, 0, 1 << 30},
@@ -385,7 +385,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     t->cholesky = 1;
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
                                         "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
-                                        "GDCA_HAMMING_MODE", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
+                                        "GDCA_HAMMING_MODE", "GDCA_HAM_CUT", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
                                         "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK"};
     for (const char *nm : names)
         if (const char *v = getenv(nm)) (void)gdca_tuning_set(t, nm, v);  // an unusable value leaves the default
@@ -748,7 +748,7 @@ static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, 
     if (ctx->tune.force_fallback)
         gdca_launch_hamming_fallback(s, Zd, (int32_t *)ctx->hcnt.p, N, M, sc);
     else
-        gdca_launch_hamming(s, (const uint32_t *)ctx->Zb.p, Zd, (int32_t *)ctx->hcnt.p, N, M, sc, ctx->tune.hamming_mode, ctx->hcand.p, fp4 ? ctx->himg.p : nullptr);
+        gdca_launch_hamming(s, (const uint32_t *)ctx->Zb.p, Zd, (int32_t *)ctx->hcnt.p, N, M, sc, ctx->tune.hamming_mode, ctx->hcand.p, fp4 ? ctx->himg.p : nullptr, ctx->tune.ham_cut);
     gdca_launch_weights(s, (const int32_t *)ctx->hcnt.p, M, gdca_fix_shift(M), (int32_t *)ctx->nk.p,
                         (double *)ctx->W.p, (unsigned long long *)ctx->Wfix.p);
     // (Meff: an exact integer sum by one workgroup, microseconds.  Rounds 1-4 summed left to right in f64 -- 0.3 ms of dependent adds at

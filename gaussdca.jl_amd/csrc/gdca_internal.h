@@ -35,7 +35,9 @@ struct gdca_dev_scalars {
     // launch of its own would have recorded (gdca_api.hip: EV_*)
     unsigned long long stamp[GDCA_STAMPS];
     int ham_cand2;   // pairs of the sampled tiles the fp4 form would list (D < 3 thresh)
-    int pad_;
+    int ham_cut;     // word at which the three-plane bound form goes from all pairs of a tile to the list of those still below the threshold
+                     // (k_hamming_decide; >= NW: never)
+    unsigned ham_alive[64];  // k_hamming's probe: pairs of the sampled tiles still below the threshold after w + 1 words (HAM_ALIVE_SLOTS)
 };
 
 // Tuning switches of one context (gdca_ctx_set_option): initialised from the GDCA_* environment variables when the context is
@@ -57,6 +59,7 @@ struct gdca_tuning {
     int tally_tj;           // GDCA_TALLY_TJ: 32 = the wide pair-tally form
     int tally_skip;         // GDCA_TALLY_SKIP: 1 = the pair tally skips each column's most frequent symbol and recovers its row (default), 0 = the full loop
     int hamming_mode;       // GDCA_HAMMING_MODE: -1 = probe, 0 = full (exact five-plane distances), 1 = bound (three planes + refinement), 2 = mfma (bit counts on the fp4 matrix pipe + refinement)
+    int ham_cut;            // GDCA_HAM_CUT (tests, measurements): 0 = the bound form's cut word from the probe (default), k >= 1 = switch at word k (k >= NW: never)
     int force_fallback;     // GDCA_FORCE_FALLBACK: 1 = the independent byte-compare Hamming kernel
     int merge;              // GDCA_MERGE: families one merged sweep launch may carry in gdca_run_dev_phased (1 = never merge)
     int merge_blocks;       // GDCA_MERGE_BLOCKS: largest member of a merged launch, in 128-blocks
@@ -98,13 +101,14 @@ void gdca_launch_bitplane_pack(hipStream_t s, const int8_t *Z, uint32_t *Zb, int
                                gdca_dev_scalars *sc);
 // cnt: int32 [Mt*128], zeroed by the caller; adds #{l != k: d(k,l) < sc->thresh}
 // force: -1 = decide per family from a sample of tiles, 0 = the exact form, 1 = the lower bound with refinement
+// cut: 0 = the bound form's cut word from the sample as well, k >= 1 = at word k (k >= NW: never)
 size_t gdca_hamming_cand_cap(int M);  // pairs the bound forms' candidate list holds (8 bytes each)
 // ---- k_hamming_fp4.hip: the bit-count lower bound on the fp4 matrix pipe (sc->ham_mode == 2) ----
 size_t gdca_fp4_image_bytes(int N, int M);
 void gdca_launch_hamming_fp4_probe(hipStream_t s, const uint32_t *Zb, int N, int M, int nprobe, gdca_dev_scalars *sc);
 void gdca_launch_hamming_fp4(hipStream_t s, const uint32_t *Zb, void *img, int N, int M, gdca_dev_scalars *sc, void *cand_list, unsigned cap);
 void gdca_launch_hamming(hipStream_t s, const uint32_t *Zb, const int8_t *Z, int32_t *cnt, int N, int M, gdca_dev_scalars *sc, int force,
-                         void *cand_list, void *fp4_img);
+                         void *cand_list, void *fp4_img, int cut);
 // the same counts by an independent plain byte-compare kernel straight from Z (GDCA_FORCE_FALLBACK; overwrites cnt[0..M-1])
 void gdca_launch_hamming_fallback(hipStream_t s, const int8_t *Z, int32_t *cnt, int N, int M, const gdca_dev_scalars *sc);
 // n_out[k] = 1 + cnt[k]; W[k] = 1/n_k; Wfix[k] = rint(W[k] * 2^fix_shift)

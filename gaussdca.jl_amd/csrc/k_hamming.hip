@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "gdca_hamming_cut.h"
 #include "gdca_internal.h"
 #include "gdca_launch.h"
 
@@ -141,6 +142,14 @@ __device__ __forceinline__ void tri_decode(int t, int Mt, int &I, int &J)
 // three-dimensional thread index for its own LDS slot: its y and z parts were hoisted out of the chunk loop and kept in scratch.)
 __shared__ int hm_any[3];
 __shared__ unsigned hm_tile_n, hm_tile_base;  // the bound form: candidates of the tile, and where its range of the list starts
+// the bound form past its cut word: every wave's list of the pairs still below the threshold, one u32 per pair -- tile row (7 bits),
+// tile column (7 bits), partial distance (18 bits) -- and how many pairs the wave found (beyond HAM_LIST_WAVE: not written)
+__shared__ uint32_t hm_list[4][HAM_LIST_WAVE];
+__shared__ int hm_wave_n[4];
+__shared__ unsigned hm_alive[HAM_ALIVE_SLOTS];  // the probe: pairs of the tile still below the threshold after each word
+#define HAM_ENT_DIST 0x3ffffu
+#define HAM_NO_PAIR 0x40000000u  // an accumulator that is no pair of the tile: beyond every threshold, and 32 NW more do not wrap it
+static_assert(sizeof(((gdca_dev_scalars *)nullptr)->ham_alive) == HAM_ALIVE_SLOTS * sizeof(unsigned), "one slot per word the probe counts");
 __device__ __forceinline__ bool wg_any(bool pred, int &k)
 {
     const int s = k % 3, n = (k + 1) % 3;
@@ -258,8 +267,10 @@ static inline k_hamming_args k_hamming_mk(const uint32_t *Zb, int32_t *cnt, int 
 {
     return k_hamming_args{Zb, cnt, NW, M, Mt, sc, cand_list, cand_cap};
 }
+// (the bound form proper is held to 128 registers, four workgroups a compute unit: what it had before it carried the switch and
+// the sparse phase -- left to itself it takes 167 and runs three, 3 .. 6 % slower at config C, profiles/hamming_cut_sweep.log)
 template <int CAP, int NP, bool PROBE>
-__global__ __launch_bounds__(256, 3) void k_hamming(const BatchArgs<k_hamming_args, CAP> B_)
+__global__ __launch_bounds__(256, (NP < NPLANES && !PROBE) ? 4 : 3) void k_hamming(const BatchArgs<k_hamming_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
     const uint32_t *__restrict__ Zb = a_.Zb;
@@ -302,14 +313,44 @@ __global__ __launch_bounds__(256, 3) void k_hamming(const BatchArgs<k_hamming_ar
     for (int r = 0; r < 8; ++r)
 #pragma unroll
         for (int c = 0; c < 8; ++c) acc[r][c] = 0;
+    if constexpr (NP < NPLANES) {
+        // the bound form asks "is this pair still below the threshold?" again and again (the probe's alive counts, the switch, the
+        // candidates): pairs a diagonal tile holds twice and rows or columns beyond M start beyond every threshold, so that nobody
+        // has to ask "and is it a pair at all?" as well.  Uniform: a tile that is neither diagonal nor the last of its row (I <= J)
+        // has every pair in range, once.
+        if (I == J || (J + 1) * GDCA_HTILE > M) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const int lc = (c < 4) ? (tx * 4 + c) : (64 + tx * 4 + (c - 4));
+                    const int gr = I * GDCA_HTILE + ty * 8 + r, gc = J * GDCA_HTILE + lc;
+                    // (the probe counts a diagonal tile's pairs twice, as ever: sc->ham_cand and the form it decides stay what they were)
+                    acc[r][c] = (gr < M && gc < M && (I == J ? (PROBE ? gr != gc : gr < gc) : true)) ? 0u : HAM_NO_PAIR;
+                }
+        }
+    }
     bool all_beyond = false;  // the main loop ended early: every pair of the tile is at or beyond the threshold
 
     const uint32_t *Ag = Zb + (size_t)I * NPLANES * NW * GDCA_HTILE;
     const uint32_t *Bg = Zb + (size_t)J * NPLANES * NW * GDCA_HTILE;
 
-    for (int w0 = 0; w0 < NW; w0 += WCHUNK) {
-        __syncthreads();
-        // stage: per plane a contiguous run of WCHUNK*128 dwords = 4 KB = 256 threads x 16 B
+    // The bound form in two phases: DENSE -- every pair of the tile, 8 x 8 per thread -- over the words 0 .. cut - 1,
+    // then, once, the SWITCH: the pairs still below the threshold go into the waves' lists in LDS, and the remaining words are
+    // walked SPARSE, lane = list entry.  cut = sc->ham_cut (k_hamming_decide: from the probe's alive counts, or the option
+    // HAM_CUT), uniform over the workgroup; cut = NW: dense to the end, the form of old.
+    constexpr bool CUTTING = NP < NPLANES && !PROBE;
+    int cut = NW;
+    if constexpr (CUTTING) {
+        const int c = sc->ham_cut;
+        if (c > 0 && c < NW && NW < HAM_CUT_MAX_NW) cut = c;
+    }
+    bool sparse = false;  // (uniform) the switch happened: the lists hold what is left of the tile
+    if constexpr (PROBE)
+        if (tid < HAM_ALIVE_SLOTS) hm_alive[tid] = 0u;
+
+    // stage: per plane a contiguous run of WCHUNK*128 dwords = 4 KB = 256 threads x 16 B
+    auto stage = [&](int w0) {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const int wl = tid >> 5;  // dword row inside the chunk (32 threads x 16 B = 128 dwords)
@@ -322,9 +363,19 @@ __global__ __launch_bounds__(256, 3) void k_hamming(const BatchArgs<k_hamming_ar
             *reinterpret_cast<uint4 *>(&As[p][wl][(tid & 31) * 4]) = va;
             *reinterpret_cast<uint4 *>(&Bs[p][wl][(tid & 31) * 4]) = vb;
         }
+    };
+
+    int w0 = 0;  // (after the loop: the chunk that is staged)
+    for (; w0 < NW; w0 += WCHUNK) {
+        __syncthreads();
+        stage(w0);
         __syncthreads();
         const int wn = min(WCHUNK, NW - w0);
-        for (int w = 0; w < wn; ++w) {
+        int w = 0;
+        bool again;  // (CUTTING: a list overflowed at the switch -- the rest of the chunk is walked dense after all)
+        do {
+        again = false;
+        for (const int wend = CUTTING ? min(wn, cut - w0) : wn; w < wend; ++w) {
             uint32_t a[NP][8], b[NP][8];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
@@ -347,7 +398,58 @@ __global__ __launch_bounds__(256, 3) void k_hamming(const BatchArgs<k_hamming_ar
                         x = __builtin_amdgcn_bitop3_b32(a[p][r], b[p][c], x, 0xBE);
                     acc[r][c] += __builtin_popcount(x);
                 }
+            if constexpr (PROBE) {
+                // where does the bound decide?  Pairs of the tile still below the threshold after this word: a compare per
+                // accumulator, its lane mask counted on the scalar side; one LDS atomic per wave and word.
+                if (w0 + w < HAM_ALIVE_SLOTS) {
+                    int alive = 0;
+#pragma unroll
+                    for (int r = 0; r < 8; ++r)
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) alive += __builtin_popcountll(__ballot((int)acc[r][c] < thresh));
+                    if ((tid & 63) == 0 && alive) atomicAdd(&hm_alive[w0 + w], (unsigned)alive);
+                }
+            }
         }
+        if constexpr (CUTTING) {
+            if (w0 + w == cut && cut < NW) {
+                // the SWITCH.  Static indices only (a dynamically indexed accumulator goes to scratch); per accumulator a compare and
+                // a branch the whole wave takes or not; where any lane holds a live pair, the wave appends its live lanes' entries
+                // behind one another (lane mask prefix counts: no atomics).  (What is no pair of the tile is not alive: HAM_NO_PAIR.)
+                const uint32_t rc0 = ((uint32_t)(ty * 8) << 25) | ((uint32_t)(tx * 4) << 18);
+                uint32_t *const mylist = hm_list[tid >> 6];
+                int wcount = 0;  // (uniform over the wave)
+#pragma unroll
+                for (int r = 0; r < 8; ++r)
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) {
+                        const bool lv = (int)acc[r][c] < thresh;
+                        const unsigned long long m = __ballot(lv);
+                        if (m != 0ull) {
+                            if (lv) {
+                                const int pos = wcount + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                                const uint32_t rc = ((uint32_t)r << 25) | ((uint32_t)((c < 4) ? c : 64 + (c - 4)) << 18);
+                                if (pos < HAM_LIST_WAVE) mylist[pos] = acc[r][c] + (rc0 + rc);  // (acc < thresh <= 32 NW < 2^18)
+                            }
+                            wcount += __builtin_popcountll(m);
+                        }
+                    }
+                if ((tid & 63) == 0) hm_wave_n[tid >> 6] = wcount;
+                __syncthreads();
+                const int n0 = hm_wave_n[0], n1 = hm_wave_n[1], n2 = hm_wave_n[2], n3 = hm_wave_n[3];
+                if (max(max(n0, n1), max(n2, n3)) > HAM_LIST_WAVE) {
+                    // a list is full (relatives, or a cut chosen too early): this tile stays dense to the end and lists as ever
+                    cut = NW;
+                    again = w < wn;
+                } else if ((n0 | n1 | n2 | n3) == 0) {
+                    all_beyond = true;  // nothing of the tile is left: the early exit below, at any word
+                } else {
+                    sparse = true;
+                }
+            }
+        }
+        } while (again);
+        if (CUTTING && (sparse || all_beyond)) break;
         // early exit: distances only grow, so once every pair of the tile is at or beyond the
         // threshold no later position can make it a neighbour
         if (w0 + WCHUNK < NW) {
@@ -378,9 +480,65 @@ __global__ __launch_bounds__(256, 3) void k_hamming(const BatchArgs<k_hamming_ar
         if (cand) atomicAdd(&rc[0], cand);
         __syncthreads();
         if (tid == 0 && rc[0]) atomicAdd(&sc->ham_cand, rc[0]);
+        if (tid < HAM_ALIVE_SLOTS && hm_alive[tid]) atomicAdd(&sc->ham_alive[tid], hm_alive[tid]);
         return;
     }
     if (all_beyond) return;  // nothing of this tile counts (the usual end of a tile of unrelated sequences): no list, no atomics
+    if constexpr (CUTTING) {
+        if (sparse) {
+            // the SPARSE phase: lane = entry of its wave's list, the words cut .. NW - 1 from the chunks in LDS (a lane reads one
+            // dword per side, plane and word).  An entry that reaches the threshold is dropped where it stands: it is no longer
+            // advanced, and not listed.  Staging and its barriers stay at workgroup level.
+            const int lane = tid & 63, nmine = hm_wave_n[tid >> 6];
+            uint32_t *const mylist = hm_list[tid >> 6];
+            for (int ws = cut; ws < NW; ws = w0 + WCHUNK) {
+                if (ws >= w0 + WCHUNK) {  // (uniform: the cut sat on a chunk boundary, or the chunk is used up)
+                    w0 += WCHUNK;
+                    __syncthreads();
+                    stage(w0);
+                    __syncthreads();
+                }
+                const int wn = min(WCHUNK, NW - w0);
+                bool left = false;
+                for (int e = lane; e < nmine; e += 64) {
+                    const uint32_t ent = mylist[e];
+                    uint32_t d = ent & HAM_ENT_DIST;
+                    if ((int)d < thresh) {
+                        const int row = (int)(ent >> 25), col = (int)((ent >> 18) & 127u);
+                        for (int w = ws - w0; w < wn; ++w) {
+                            uint32_t x = As[0][w][row] ^ Bs[0][w][col];
+#pragma unroll
+                            for (int p = 1; p < NP; ++p) x = __builtin_amdgcn_bitop3_b32(As[p][w][row], Bs[p][w][col], x, 0xBE);
+                            d += __builtin_popcount(x);
+                        }
+                        mylist[e] = (ent & ~HAM_ENT_DIST) | d;  // (d <= 32 NW < 2^18)
+                        left |= (int)d < thresh;
+                    }
+                }
+                if (w0 + WCHUNK < NW && !wg_any(left, any_calls)) return;  // (uniform) every entry is at or beyond the threshold
+            }
+            // what is left below the threshold are the tile's candidates: into the global list by the scheme below
+            unsigned mine = 0u;
+            for (int e = lane; e < nmine; e += 64) mine += (int)(mylist[e] & HAM_ENT_DIST) < thresh;
+            if (!wg_any(mine != 0u, any_calls)) return;  // (uniform)
+            const unsigned off = mine ? atomicAdd(&hm_tile_n, mine) : 0u;
+            __syncthreads();
+            if (tid == 0) {
+                const unsigned long long base = atomicAdd(&sc->ham_ncand, (unsigned long long)hm_tile_n);
+                hm_tile_base = base > (unsigned long long)cand_cap ? cand_cap : (unsigned)base;
+            }
+            __syncthreads();
+            unsigned slot = hm_tile_base + off;
+            for (int e = lane; e < nmine; e += 64) {
+                const uint32_t ent = mylist[e];
+                if ((int)(ent & HAM_ENT_DIST) < thresh) {
+                    if (slot < cand_cap) cand_list[slot] = make_int2(I * GDCA_HTILE + (int)(ent >> 25), J * GDCA_HTILE + (int)((ent >> 18) & 127u));
+                    ++slot;
+                }
+            }
+            return;
+        }
+    }
     if constexpr (NP < NPLANES) {
         // candidates -> the list (the bound can only be too small, so nothing else can be a neighbour).  A diagonal tile holds every
         // pair twice: its upper half is listed.  (Most threads hold no candidate at all: 63 minima decide that.)
@@ -475,10 +633,12 @@ struct k_hamming_decide_args {
     long long sampled_pairs;
     int force;
     int fp4_ok;  // the fp4 form may be chosen (its image buffer exists)
+    int NW;
+    int cut;     // option HAM_CUT: 0 = from the probe's alive counts (no probe: no cut), k >= 1 = the bound form switches at word k
 };
-static inline k_hamming_decide_args k_hamming_decide_mk(gdca_dev_scalars *sc, long long sampled_pairs, int force, int fp4_ok)
+static inline k_hamming_decide_args k_hamming_decide_mk(gdca_dev_scalars *sc, long long sampled_pairs, int force, int fp4_ok, int NW, int cut)
 {
-    return k_hamming_decide_args{sc, sampled_pairs, force, fp4_ok};
+    return k_hamming_decide_args{sc, sampled_pairs, force, fp4_ok, NW, cut};
 }
 template <int CAP>
 __global__ void k_hamming_decide(const BatchArgs<k_hamming_decide_args, CAP> B_)
@@ -494,13 +654,16 @@ __global__ void k_hamming_decide(const BatchArgs<k_hamming_decide_args, CAP> B_)
         const double pairs = (double)sampled_pairs;
         sc->ham_mode = force >= 0 ? force : ((a_.fp4_ok && (double)sc->ham_cand2 < 2e-3 * pairs) ? 2 : ((double)sc->ham_cand < 1e-3 * pairs ? 1 : 0));
         sc->ham_ncand = 0u;
+        // where the bound form stops carrying every pair (gdca_hamming_cut.h: the cost model and its measured constants); a family
+        // that was not probed (tiny, or a forced form) has no alive counts: no cut
+        sc->ham_cut = a_.cut > 0 ? a_.cut : (force < 0 ? gdca_hamming_pick_cut(sc->ham_alive, pairs, a_.NW) : a_.NW);
     }
 }
 
 // Z: the alignment's bytes ([M][N], what the bit planes were packed from); cand_list: gdca_hamming_cand_cap(M) pairs of scratch;
 // fp4_img: gdca_fp4_image_bytes(N, M) of scratch for the fp4 form, or nullptr (that form is then never chosen)
 void gdca_launch_hamming(hipStream_t s, const uint32_t *Zb, const int8_t *Z, int32_t *cnt, int N, int M, gdca_dev_scalars *sc, int force,
-                         void *cand_list, void *fp4_img)
+                         void *cand_list, void *fp4_img, int cut)
 {
     const int Mt = (M + GDCA_HTILE - 1) / GDCA_HTILE, NW = (N + 31) / 32;
     const long long ntile = (long long)Mt * (Mt + 1) / 2;
@@ -516,9 +679,9 @@ void gdca_launch_hamming(hipStream_t s, const uint32_t *Zb, const int8_t *Z, int
     if (force < 0 && ntile >= 64) {
         (gdca_launch<k_hamming_args, k_hamming<1, HAM_BOUND_PLANES, true>, k_hamming<GDCA_MAXB, HAM_BOUND_PLANES, true>>(dim3((unsigned)nprobe), dim3(256), 0, s, k_hamming_mk(Zb, cnt, NW, M, Mt, sc, list, cap)));
         if (fp4_img) gdca_launch_hamming_fp4_probe(s, Zb, N, M, nprobe, sc);
-        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, (long long)nprobe * GDCA_HTILE * GDCA_HTILE, -1, fp4_img ? 1 : 0)));
+        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, (long long)nprobe * GDCA_HTILE * GDCA_HTILE, -1, fp4_img ? 1 : 0, NW, cut)));
     } else {
-        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, 1ll, force < 0 ? 0 : force, 0)));  // tiny families: the exact form
+        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, 1ll, force < 0 ? 0 : force, 0, NW, cut)));  // tiny families: the exact form
     }
     // every form that may run is launched: where the device decides between them, and behind a forced bound form, whose list may
     // overflow (a form that has nothing to do exits on sc->ham_mode / sc->ham_ncand: empty workgroups)
