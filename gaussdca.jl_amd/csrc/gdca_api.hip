@@ -9,6 +9,7 @@
 #include <string.h>
 #include <strings.h>
 
+#include "gdca_hamming_form.h"
 #include "gdca_internal.h"
 #include "gdca_launch.h"
 
@@ -149,7 +150,7 @@ struct gdca_ctx {
     gdca_buf normws, C2, B0, Rt;  // ||X||_1 workspace; Newton-Schulz refinement (allocated when a run first needs it): C again, X0 in full, I - X0 C
     gdca_buf Wd;                  // Cholesky fallback: the inverses of the diagonal tiles of the factor
     gdca_buf hcand;               // reweighting, bound forms: the list of candidate pairs
-    gdca_buf himg;                // reweighting, fp4 form: the image of the three low bit planes as E2M1 nibbles
+    gdca_buf himg;                // reweighting, consensus form: the image of the consensus plane as E2M1 nibbles, and sigma
     gdca_buf rankws;              // device ranking: keys, values, histograms, the three output arrays
     gdca_buf keep;                // pair tally, TALLY_SKIP: the sequences each column's tally visits, their counts and sigma (k_pi_keep)
     gdca_buf Pij;                 // gdca_run_multi: Pij_true of the alignment (n x n, ld = n), the covariance of every pseudocount is built from it
@@ -734,9 +735,9 @@ static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, 
     CHK(ensure(ctx, ctx->Zb, gdca_bitplane_bytes(N, M)));
     CHK(ensure(ctx, ctx->hcnt, (size_t)Mt * GDCA_HTILE * sizeof(int32_t)));
     if (!ctx->tune.force_fallback && ctx->tune.hamming_mode != 0) CHK(ensure(ctx, ctx->hcand, gdca_hamming_cand_cap(M) * 8));
-    // (the fp4 form's image of the three low bit planes: 1.5 N bytes per sequence)
-    // (only where the option asks for that form: the automatic choice never takes it -- k_hamming_fp4.hip says why)
-    const bool fp4 = !ctx->tune.force_fallback && ctx->tune.hamming_mode == 2;
+    // (the consensus form's image, N / 2 bytes per sequence: where the option asks for that form, and where the automatic rule may
+    // choose it -- gdca_hamming_form.h: small families are not even probed for it)
+    const bool fp4 = !ctx->tune.force_fallback && (ctx->tune.hamming_mode == 2 || (ctx->tune.hamming_mode < 0 && gdca_hamming_consensus_gate(N, M)));
     if (fp4) CHK(ensure(ctx, ctx->himg, gdca_fp4_image_bytes(N, M)));
     CHK(ensure(ctx, ctx->nk, (size_t)M * sizeof(int32_t)));
     CHK(ensure(ctx, ctx->W, (size_t)M * sizeof(double)));
@@ -745,10 +746,16 @@ static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, 
     gdca_launch_bitplane_pack(s, Zd, (uint32_t *)ctx->Zb.p, N, M, q, sc);  // (also the symbol-range check)
     // option GDCA_FORCE_FALLBACK: the independent byte-compare kernel instead of the bit-sliced one -- the analogue of
     // DCAUTILS_FORCE_FALLBACK in the reference's tests (test/runtests.jl:78-86)
-    if (ctx->tune.force_fallback)
+    if (ctx->tune.force_fallback) {
         gdca_launch_hamming_fallback(s, Zd, (int32_t *)ctx->hcnt.p, N, M, sc);
-    else
+    } else {
+        if (fp4) {
+            // sigma comes from the column histogram, which so far only theta = :auto has counted
+            if (!(fixed_thresh < 0 && theta_in < 0.0)) gdca_launch_column_hist(s, Zd, (uint32_t *)ctx->hist.p, N, M);
+            gdca_launch_hamming_fp4_image(s, Zd, (const uint32_t *)ctx->hist.p, ctx->himg.p, N, M);
+        }
         gdca_launch_hamming(s, (const uint32_t *)ctx->Zb.p, Zd, (int32_t *)ctx->hcnt.p, N, M, sc, ctx->tune.hamming_mode, ctx->hcand.p, fp4 ? ctx->himg.p : nullptr, ctx->tune.ham_cut);
+    }
     gdca_launch_weights(s, (const int32_t *)ctx->hcnt.p, M, gdca_fix_shift(M), (int32_t *)ctx->nk.p,
                         (double *)ctx->W.p, (unsigned long long *)ctx->Wfix.p);
     // (Meff: an exact integer sum by one workgroup, microseconds.  Rounds 1-4 summed left to right in f64 -- 0.3 ms of dependent adds at

@@ -20,7 +20,7 @@ struct gdca_dev_scalars {
     int info;
     int bad_symbol;  // bit 0: a byte of Z is outside 1..q; bit 1: a caller-given weight is outside [0, 1] (GDCA_EINVAL)
     int di_noconv;   // number of site pairs whose tridiagonal QL iteration did not converge (DI score)
-    int ham_mode;    // all-pairs Hamming kernel chosen for this family: 0 = exact distances, 1 = three-plane lower bound + refinement, 2 = the bit-count
+    int ham_mode;    // all-pairs Hamming kernel chosen for this family: 0 = exact distances, 1 = three-plane lower bound + refinement, 2 = the consensus
                      // lower bound on the fp4 matrix pipe + refinement (k_hamming_fp4.hip)
     int ham_cand;    // candidate pairs (bound below the threshold) in the sampled tiles of k_hamming_probe
     unsigned long long ham_ncand;  // pairs the bound form has put (or tried to put) into its candidate list: beyond the list's capacity the exact form counts
@@ -34,7 +34,7 @@ struct gdca_dev_scalars {
     // between them -- an event per member and stage was most of the host's work for a batch): slot = the index of the event a
     // launch of its own would have recorded (gdca_api.hip: EV_*)
     unsigned long long stamp[GDCA_STAMPS];
-    int ham_cand2;   // pairs of the sampled tiles the fp4 form would list (D < 3 thresh)
+    int ham_cand2;   // pairs of the sampled tiles the consensus form would list (D1 < thresh)
     int ham_cut;     // word at which the three-plane bound form goes from all pairs of a tile to the list of those still below the threshold
                      // (k_hamming_decide; >= NW: never)
     unsigned ham_alive[64];  // k_hamming's probe: pairs of the sampled tiles still below the threshold after w + 1 words (HAM_ALIVE_SLOTS)
@@ -58,7 +58,7 @@ struct gdca_tuning {
     int sweep_retries;      // GDCA_SWEEP_RETRIES: attempts an inverse gets after its launch was ended by the watchdog (default 2; 0 = none: GDCA_EHIP at once)
     int tally_tj;           // GDCA_TALLY_TJ: 32 = the wide pair-tally form
     int tally_skip;         // GDCA_TALLY_SKIP: 1 = the pair tally skips each column's most frequent symbol and recovers its row (default), 0 = the full loop
-    int hamming_mode;       // GDCA_HAMMING_MODE: -1 = probe, 0 = full (exact five-plane distances), 1 = bound (three planes + refinement), 2 = mfma (bit counts on the fp4 matrix pipe + refinement)
+    int hamming_mode;       // GDCA_HAMMING_MODE: -1 = probe, 0 = full (exact five-plane distances), 1 = bound (three planes + refinement), 2 = mfma (the consensus plane on the fp4 matrix pipe + refinement)
     int ham_cut;            // GDCA_HAM_CUT (tests, measurements): 0 = the bound form's cut word from the probe (default), k >= 1 = switch at word k (k >= NW: never)
     int force_fallback;     // GDCA_FORCE_FALLBACK: 1 = the independent byte-compare Hamming kernel
     int merge;              // GDCA_MERGE: families one merged sweep launch may carry in gdca_run_dev_phased (1 = never merge)
@@ -103,10 +103,12 @@ void gdca_launch_bitplane_pack(hipStream_t s, const int8_t *Z, uint32_t *Zb, int
 // force: -1 = decide per family from a sample of tiles, 0 = the exact form, 1 = the lower bound with refinement
 // cut: 0 = the bound form's cut word from the sample as well, k >= 1 = at word k (k >= NW: never)
 size_t gdca_hamming_cand_cap(int M);  // pairs the bound forms' candidate list holds (8 bytes each)
-// ---- k_hamming_fp4.hip: the bit-count lower bound on the fp4 matrix pipe (sc->ham_mode == 2) ----
-size_t gdca_fp4_image_bytes(int N, int M);
-void gdca_launch_hamming_fp4_probe(hipStream_t s, const uint32_t *Zb, int N, int M, int nprobe, gdca_dev_scalars *sc);
-void gdca_launch_hamming_fp4(hipStream_t s, const uint32_t *Zb, void *img, int N, int M, gdca_dev_scalars *sc, void *cand_list, unsigned cap);
+// ---- k_hamming_fp4.hip: the consensus lower bound on the fp4 matrix pipe (sc->ham_mode == 2) ----
+size_t gdca_fp4_image_bytes(int N, int M);  // the image and sigma
+// hist: the column histogram [N][32] (gdca_launch_column_hist), already enqueued
+void gdca_launch_hamming_fp4_image(hipStream_t s, const int8_t *Z, const uint32_t *hist, void *img, int N, int M);
+void gdca_launch_hamming_fp4_probe(hipStream_t s, const void *img, int N, int M, int nprobe, gdca_dev_scalars *sc);
+void gdca_launch_hamming_fp4(hipStream_t s, const void *img, int N, int M, gdca_dev_scalars *sc, void *cand_list, unsigned cap);
 void gdca_launch_hamming(hipStream_t s, const uint32_t *Zb, const int8_t *Z, int32_t *cnt, int N, int M, gdca_dev_scalars *sc, int force,
                          void *cand_list, void *fp4_img, int cut);
 // the same counts by an independent plain byte-compare kernel straight from Z (GDCA_FORCE_FALLBACK; overwrites cnt[0..M-1])

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "gdca_hamming_cut.h"
+#include "gdca_hamming_form.h"
 #include "gdca_internal.h"
 #include "gdca_launch.h"
 
@@ -167,9 +168,8 @@ __device__ __forceinline__ bool wg_any(bool pred, int &k)
 // trip -- with one integer atomic per end of a neighbour pair.  (Round 3 refined inside the tile's workgroup, from the five bit
 // planes: 16 scattered dwords per lane and plane, and the refinement's loops shared the main loop's registers -- 36 of them parked
 // in scratch on EVERY tile, 2.2 GB written per launch at N = 500, M = 50 000 for 200 KB of results.)  The list holds HAM_CAND_PER_TILE
-// pairs per tile on average -- sixteen times the density at which the bound form is chosen at all; a family that overflows it
-// anyway (clustered where the sampled tiles were not) is counted by the exact form instead: nothing is ever dropped.
-#define HAM_CAND_PER_TILE 16
+// (gdca_hamming_form.h) pairs per tile on average -- twice the density at which a bound form is chosen at all; a family that
+// overflows it anyway (clustered where the sampled tiles were not) is counted by the exact form instead: nothing is ever dropped.
 
 size_t gdca_hamming_cand_cap(int M)
 {
@@ -626,19 +626,18 @@ __global__ __launch_bounds__(256, (NP < NPLANES && !PROBE) ? 4 : 3) void k_hammi
     }
 }
 
-// sc->ham_mode from the sample: 1 (lower bound first) if fewer than 1 pair in 1000 of the sampled tiles is a candidate -- beyond
-// that the refinement costs more than the two instructions per word the bound saves
+// sc->ham_mode from the samples (gdca_hamming_form.h: the rule and its measured constants), sc->ham_cut (gdca_hamming_cut.h)
 struct k_hamming_decide_args {
     gdca_dev_scalars *sc;
     long long sampled_pairs;
     int force;
-    int fp4_ok;  // the fp4 form may be chosen (its image buffer exists)
-    int NW;
+    int consensus;  // the consensus form was probed too (its image exists, sc->ham_cand2 is its count)
+    int N, M;
     int cut;     // option HAM_CUT: 0 = from the probe's alive counts (no probe: no cut), k >= 1 = the bound form switches at word k
 };
-static inline k_hamming_decide_args k_hamming_decide_mk(gdca_dev_scalars *sc, long long sampled_pairs, int force, int fp4_ok, int NW, int cut)
+static inline k_hamming_decide_args k_hamming_decide_mk(gdca_dev_scalars *sc, long long sampled_pairs, int force, int consensus, int N, int M, int cut)
 {
-    return k_hamming_decide_args{sc, sampled_pairs, force, fp4_ok, NW, cut};
+    return k_hamming_decide_args{sc, sampled_pairs, force, consensus, N, M, cut};
 }
 template <int CAP>
 __global__ void k_hamming_decide(const BatchArgs<k_hamming_decide_args, CAP> B_)
@@ -648,20 +647,19 @@ __global__ void k_hamming_decide(const BatchArgs<k_hamming_decide_args, CAP> B_)
     long long sampled_pairs = a_.sampled_pairs;
     int force = a_.force;
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        // the bit-count bound on the fp4 matrix pipe (k_hamming_fp4.hip) where it would list fewer than 2 pairs in 1000 (its product is
-        // five times cheaper than the three-plane form's loop, its list about twice as long); else the three-plane form below 1 in 1000
-        // (a pair refined costs ~50 pairs skipped); else exact distances
         const double pairs = (double)sampled_pairs;
-        sc->ham_mode = force >= 0 ? force : ((a_.fp4_ok && (double)sc->ham_cand2 < 2e-3 * pairs) ? 2 : ((double)sc->ham_cand < 1e-3 * pairs ? 1 : 0));
-        sc->ham_ncand = 0u;
+        const int NW = (a_.N + 31) / 32;
         // where the bound form stops carrying every pair (gdca_hamming_cut.h: the cost model and its measured constants); a family
         // that was not probed (tiny, or a forced form) has no alive counts: no cut
-        sc->ham_cut = a_.cut > 0 ? a_.cut : (force < 0 ? gdca_hamming_pick_cut(sc->ham_alive, pairs, a_.NW) : a_.NW);
+        const int cut = a_.cut > 0 ? a_.cut : (force < 0 ? gdca_hamming_pick_cut(sc->ham_alive, pairs, NW) : NW);
+        sc->ham_cut = cut;
+        sc->ham_mode = force >= 0 ? force : gdca_hamming_pick_form((double)sc->ham_cand, a_.consensus ? (double)sc->ham_cand2 : -1.0, pairs, a_.N, a_.M, cut);
+        sc->ham_ncand = 0u;
     }
 }
 
 // Z: the alignment's bytes ([M][N], what the bit planes were packed from); cand_list: gdca_hamming_cand_cap(M) pairs of scratch;
-// fp4_img: gdca_fp4_image_bytes(N, M) of scratch for the fp4 form, or nullptr (that form is then never chosen)
+// fp4_img: the consensus form's image (gdca_launch_hamming_fp4_image has been enqueued), or nullptr: that form is not considered
 void gdca_launch_hamming(hipStream_t s, const uint32_t *Zb, const int8_t *Z, int32_t *cnt, int N, int M, gdca_dev_scalars *sc, int force,
                          void *cand_list, void *fp4_img, int cut)
 {
@@ -678,16 +676,16 @@ void gdca_launch_hamming(hipStream_t s, const uint32_t *Zb, const int8_t *Z, int
     if (force < 0 && NW <= 2) force = 0;
     if (force < 0 && ntile >= 64) {
         (gdca_launch<k_hamming_args, k_hamming<1, HAM_BOUND_PLANES, true>, k_hamming<GDCA_MAXB, HAM_BOUND_PLANES, true>>(dim3((unsigned)nprobe), dim3(256), 0, s, k_hamming_mk(Zb, cnt, NW, M, Mt, sc, list, cap)));
-        if (fp4_img) gdca_launch_hamming_fp4_probe(s, Zb, N, M, nprobe, sc);
-        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, (long long)nprobe * GDCA_HTILE * GDCA_HTILE, -1, fp4_img ? 1 : 0, NW, cut)));
+        if (fp4_img) gdca_launch_hamming_fp4_probe(s, fp4_img, N, M, nprobe, sc);
+        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, (long long)nprobe * GDCA_HTILE * GDCA_HTILE, -1, fp4_img ? 1 : 0, N, M, cut)));
     } else {
-        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, 1ll, force < 0 ? 0 : force, 0, NW, cut)));  // tiny families: the exact form
+        (gdca_launch<k_hamming_decide_args, k_hamming_decide<1>, k_hamming_decide<GDCA_MAXB>>(dim3(1), dim3(1), 0, s, k_hamming_decide_mk(sc, 1ll, force < 0 ? 0 : force, 0, N, M, cut)));  // tiny families: the exact form
     }
     // every form that may run is launched: where the device decides between them, and behind a forced bound form, whose list may
     // overflow (a form that has nothing to do exits on sc->ham_mode / sc->ham_ncand: empty workgroups)
     const bool decided = !(force < 0 && ntile >= 64);
     const int form = decided ? (force < 0 ? 0 : force) : -1;
-    if (fp4_img && (form == 2 || form < 0)) gdca_launch_hamming_fp4(s, Zb, fp4_img, N, M, sc, list, cap);
+    if (fp4_img && (form == 2 || form < 0)) gdca_launch_hamming_fp4(s, fp4_img, N, M, sc, list, cap);
     if (form == 1 || form < 0)
         (gdca_launch<k_hamming_args, k_hamming<1, HAM_BOUND_PLANES, false>, k_hamming<GDCA_MAXB, HAM_BOUND_PLANES, false>>(dim3((unsigned)ntile), dim3(256), 0, s, k_hamming_mk(Zb, cnt, NW, M, Mt, sc, list, cap)));
     if (form != 0)

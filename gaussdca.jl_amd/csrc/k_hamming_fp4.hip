@@ -1,39 +1,38 @@
 // All-pairs Hamming reweighting (compute_weights inside DCAUtils' compute_weighted_frequencies; reference call site
-// src/GaussDCA.jl:28): a LOWER BOUND of every pair's distance on the fp4 matrix pipe (round 6).
+// src/GaussDCA.jl:28): a LOWER BOUND of every pair's distance on the fp4 matrix pipe -- the CONSENSUS bound.
 //
 // Only pairs below the threshold count, so any cheap quantity that is never larger than the distance sorts the pairs: what passes
 // goes to k_hamming_refine (k_hamming.hip), which counts exactly from the alignment's bytes -- the neighbour counts are the same
-// integers whatever bound made the list.  Round 3's bound is the distance on the three low bit planes, d3 <= d, 4 VALU instructions
-// per 32 symbol compares (k_hamming<3>: 2.39 ms at N = 500, M = 50 000, VALU issue bound).  This one is weaker and ten times cheaper:
-//     D = number of BITS in which two sequences' three low planes differ;  a position that differs there differs in 1..3 bits, so
-//     d >= d3 >= D / 3, and a pair can only be a neighbour if D < 3 thresh.
-// D is a Gram matrix: with every bit b coded as the fp4 number (+1.0, -1.0)[b], S = sum over the 96 NW bit positions of a * b =
-// (agreeing bits) - (differing bits) = K - 2 D.  v_mfma_scale_f32_32x32x64_f8f6f4 with both operands E2M1 multiplies 32 x 32 x 64 of
-// them per instruction, exactly (|S| <= 3072 in f32 accumulators), at 4.3 PMAC/s out of LDS (tools/ubench_fp4.hip,
-// profiles/r06_ubench_fp4.log): 1.9e12 MACs at config C instead of 6.25e11 x 4 / 32 VALU instructions.
+// integers whatever bound made the list.
 //
-// MEASURED, AND NOT CHOSEN BY THE AUTOMATIC RULE (profiles/r06_hamming_fp4.log).  The counts are exact in every case tried (the parity
-// tests force this form: tests/test_gpu_parity.py), but the bound is too weak for the families gDCA sees.  theta = :auto puts the
-// threshold at 0.1216 / (mean identity) -- 0.35 N for the benchmark family, whose TYPICAL pair sits at d = 0.65 N, not at N: the
-// sequences of a protein family all descend from one root.  d3 loses 9 % of d, the bit count another factor 1.72 / 3: a typical pair has
-// D / 3 = 0.52 d = 170 against thresh = 174, and 56 % of ALL pairs land in the list (2.5e-4 for the three-plane form, 1.7e-4 true
-// neighbours); the list overflows and the exact form counts the family after all.  A bound that rejects typical pairs has to keep more
-// than ~0.6 of d, i.e. needs the positions, not the bits: the class-one-hot form (8 nibbles per position, or 7 with a simplex code) is
-// 5.0e12 MACs at config C = 1.2 ms at the rate the micro-benchmark sustains out of LDS, against 2.39 ms today -- and this kernel, as
-// first written (one 256 x 256 tile per 1024-thread workgroup, one chunk of prefetch), reaches 1.07 PMAC/s of those 4.3 (1.77 ms for
-// the 1.9e12 MACs of config C: a chunk's 0.86 us of MFMA time does not cover the ~2 us of its successor's loads, and 114 registers
-// leave no room for a second chunk in flight).  The one-hot form would need this loop at three times its efficiency to win 0.8 ms of
-// a 22.5-ms family: not built.  The form stays selectable (GDCA_HAMMING_MODE=mfma) for families of unrelated sequences and as the
-// exactness-tested starting point of that kernel; the automatic rule chooses between the three-plane and the exact form as before.
+// The bound.  sigma(i) = the most frequent symbol of column i (the argmax of the column histogram, ties to the smallest symbol), and
+// x_k(i) = [Z[k, i] != sigma(i)].  Where exactly one of two sequences carries sigma(i) the two differ, so
+//     D1(k, l) = popcount(x_k xor x_l) <= d(k, l),
+// and D1 counts POSITIONS.  (Round 6's first bound on this pipe counted the differing BITS of the three low planes, D / 3 <= d: it
+// kept 0.52 of d and listed 56 % of all pairs of the benchmark family, whose typical pair sits at d = 0.65 N with the threshold at
+// 0.35 N; measured, never chosen, replaced by this one.  D1 keeps 0.75 of d there -- median 244 of 325 at N = 500 -- and lists 9.3e-4
+// of the pairs against 1.85e-4 true neighbours and 2.4e-4 for the three-plane bound of k_hamming<3>; tools/hamming_alive.py
+// --bound consensus reproduces the figures on the CPU.)  Any sigma gives a valid bound -- it only has to be the same for both
+// operands, and deterministic, so that the list is reproducible.
+// D1 is a Gram matrix: with x coded as the fp4 number (+1.0, -1.0)[x], S = sum over the N positions of a * b = N - 2 D1.
+// v_mfma_scale_f32_32x32x64_f8f6f4 with both operands E2M1 multiplies 32 x 32 x 64 of them per instruction, exactly (|S| <= N in f32
+// accumulators): M^2 / 2 x 32 NW MACs, 6.4e11 at config C, where the three-plane loop issues 6.25e11 x 4 / 32 VALU instructions.
 //
-// Layout.  k_fp4_image expands the three low bit planes of the bit-plane image (k_bitplane_pack) ONCE into a row-major image of
-// nibbles: row = sequence, 16 bytes per (32-position word w, plane p) entry e = 3 w + p, entries padded to whole LDS chunks (eight) and
-// rows to a multiple of 256 with 0.0 nibbles, which add nothing to S (a row of them: S = 0, never a candidate).  One k step of the MFMA is 64
-// nibbles = two entries; a lane holds row (lane % 32) and entry (lane / 32) of the step for A and for B alike -- the sum over k does
-// not care in which order the nibbles sit inside a lane as long as both operands use the same, and both come from the same image.
-// k_hamming_fp4: one 1024-thread workgroup per 256 x 256 pair tile of the upper triangle (16 waves of 64 x 64 = 2 x 2 MFMA blocks),
-// operands staged global -> registers -> LDS in chunks of four k steps, double-buffered, one barrier per chunk; the epilogue compares
-// S with K - 6 thresh and lists the pairs (the three-plane form's list: one LDS counter, one device-wide atomic per tile).
+// Layout.  k_fp4_image writes a row-major image of nibbles straight from the alignment's bytes: row = sequence, one 16-byte entry
+// per 32-position word, entries padded to whole LDS chunks (eight) and rows to a multiple of 256.  Nibble = +1.0 where Z = sigma,
+// -1.0 where not; positions beyond N, pad entries and rows beyond M are 0.0 nibbles, which add nothing to S -- so K, the number of
+// terms of S that are +-1, is N for every pair of real sequences, and a row of 0.0 has S = 0 (it is kept out by its index, not by S).
+// One k step of the MFMA is 64 nibbles = two entries; a lane holds row (lane % 32) and entry (lane / 32) of the step for A and for
+// B alike -- the sum over k does not care in which order the nibbles sit inside a lane as long as both operands use the same, and
+// both come from the same image.
+// k_hamming_fp4: a 1024-thread workgroup (16 waves of 64 x 64 = 2 x 2 MFMA blocks) walks up to F4_SEG consecutive 256 x 256 tiles
+// J of ONE tile row I of the upper triangle.  Operands are staged global -> registers -> LDS in chunks of four k steps; the stream
+// of chunks runs across the tiles of the walk, double-buffered, one barrier per chunk, so only the first chunk of a walk is waited
+// for with nothing to do.  Where a row strip is at most two chunks (N <= 512) the A strip is loaded once and stays in LDS for the
+// whole walk (ARES): the kernel is bound by what a compute unit can fetch (64 KB a chunk for both operands against 0.86 us of
+// MFMA time), and a resident A halves it.  Rows of the triangle are cut into walks of F4_SEG tiles, all about equally long, which
+// balances the triangle.  The epilogue, per tile, compares S with N - 2 thresh and lists the pairs (the three-plane form's list: one
+// LDS counter, one device-wide atomic per tile).
 #include <algorithm>
 
 #include "gdca_internal.h"
@@ -46,49 +45,117 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 #define F4_KC 4              // k steps (of 64 nibbles = 32 bytes per row) per LDS chunk
 #define F4_ROW (F4_KC * 32 + 16)  // bytes per row of a chunk in LDS: 128 + a 16-byte pad (16-byte reads of 32 rows: no bank is hit twice in a phase)
 #define F4_OP (F4_TILE * F4_ROW)  // one operand's chunk
-#define F4_LDS (4 * F4_OP)        // A and B, two buffers: 147 456 bytes
+#define F4_LDS (4 * F4_OP)        // A (two chunks: resident, or two buffers) and B (two buffers): 147 456 bytes
+#define F4_SEG 8             // tiles of one row a workgroup walks
 
-// entries per row of the image: the 3 NW real ones, padded with 0.0 nibbles (which add nothing to S) to whole LDS chunks of 2 F4_KC
-static inline int f4_entries(int NW) { return (3 * NW + 2 * F4_KC - 1) / (2 * F4_KC) * (2 * F4_KC); }
-size_t gdca_fp4_image_bytes(int N, int M)
+// entries per row of the image: the NW real ones, padded with 0.0 nibbles (which add nothing to S) to whole LDS chunks of 2 F4_KC
+static inline int f4_entries(int NW) { return (NW + 2 * F4_KC - 1) / (2 * F4_KC) * (2 * F4_KC); }
+static inline size_t f4_image_only_bytes(int N, int M)
 {
     const size_t NW = (size_t)(N + 31) / 32, rows = ((size_t)M + F4_TILE - 1) / F4_TILE * F4_TILE;
     return rows * (size_t)f4_entries((int)NW) * 16;
 }
+// the image, and behind it sigma: one byte per position of the padded row (32 per entry)
+size_t gdca_fp4_image_bytes(int N, int M)
+{
+    return f4_image_only_bytes(N, M) + (size_t)f4_entries((N + 31) / 32) * 32;
+}
 
-// 8 bits -> 8 nibbles (0x2 | bit << 3: +1.0 / -1.0 in E2M1), bit i in nibble i
+// 8 bits -> 8 nibbles (0x2 | bit << 3: +1.0 / -1.0 in E2M1), bit i in nibble i; nibbles whose bit of `valid` is clear: 0.0
 __device__ __forceinline__ uint32_t f4_spread8(uint32_t b)
 {
     uint32_t x = b & 0xffu;
     x = (x | (x << 12)) & 0x000f000fu;
     x = (x | (x << 6)) & 0x03030303u;
     x = (x | (x << 3)) & 0x11111111u;
-    return (x << 3) | 0x22222222u;
+    return x;
+}
+__device__ __forceinline__ uint32_t f4_nibbles8(uint32_t differs, uint32_t valid)
+{
+    return ((f4_spread8(differs) << 3) | 0x22222222u) & (f4_spread8(valid) * 0xfu);
+}
+// the sign bits of 8 nibbles -> 8 bits (the inverse of f4_spread8 on bit 3 of every nibble)
+__device__ __forceinline__ uint32_t f4_signs8(uint32_t v)
+{
+    uint32_t x = (v >> 3) & 0x11111111u;
+    x = (x | (x >> 3)) & 0x03030303u;
+    x = (x | (x >> 6)) & 0x000f000fu;
+    x = (x | (x >> 12)) & 0xffu;
+    return x;
 }
 
-// ---- the fp4 image of the three low bit planes -------------------------------------------------------------------------------------
+// ---- sigma: the most frequent symbol of every column ------------------------------------------------------------------------------
+struct k_fp4_sigma_args {
+    const uint32_t *hist;  // [N][32] counts of (byte & 31) (k_column_hist)
+    uint8_t *sigma;        // [32 E]: positions beyond N: 0
+    int N, NP;             // NP = 32 E
+};
+template <int CAP>
+__global__ __launch_bounds__(256) void k_fp4_sigma(const BatchArgs<k_fp4_sigma_args, CAP> B_)
+{
+    GDCA_MEMBER(B_);
+    const uint32_t *__restrict__ hist = a_.hist;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a_.NP) return;
+    uint32_t best = 0u, bz = 0u;
+    if (i < a_.N) {
+        const uint4 *h = reinterpret_cast<const uint4 *>(hist + (size_t)i * 32);
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+            const uint4 v = h[g];
+            const uint32_t c[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c[j] > best) {  // (strict: a tie stays with the smaller symbol)
+                    best = c[j];
+                    bz = (uint32_t)(4 * g + j);
+                }
+        }
+    }
+    a_.sigma[i] = (uint8_t)bz;
+}
+
+// ---- the fp4 image of the consensus plane ---------------------------------------------------------------------------------------------
+// thread <-> (sequence, word), words fastest: the threads of a row read its bytes and write its entries side by side
 struct k_fp4_image_args {
-    const uint32_t *Zb;  // bit planes [Mt128][5][NW][128]
-    uint4 *img;          // [rows][E] x 16 bytes
-    int NW, M, E;
-    const gdca_dev_scalars *sc;
+    const int8_t *Z;       // [M][N]
+    const uint8_t *sigma;  // [32 E]
+    uint4 *img;            // [rows][E] x 16 bytes
+    int N, M, E, rows;
 };
 template <int CAP>
 __global__ __launch_bounds__(256) void k_fp4_image(const BatchArgs<k_fp4_image_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
-    if (a_.sc->ham_mode != 2) return;  // (another form was chosen for this family)
-    const uint32_t *__restrict__ Zb = a_.Zb;
+    const int8_t *__restrict__ Z = a_.Z;
+    const uint8_t *__restrict__ sigma = a_.sigma;
     uint4 *__restrict__ img = a_.img;
-    const int NW = a_.NW, M = a_.M, E = a_.E;
-    const int k = blockIdx.x * 256 + threadIdx.x, e = blockIdx.y;  // sequence (row of the image), entry
-    const int w = e / 3, p = e - 3 * w;
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);  // rows beyond the alignment and pad entries: 0.0
-    if (k < M && e < 3 * NW) {
-        const uint32_t word = Zb[(((size_t)(k >> 7) * 5 + p) * NW + w) * 128 + (k & 127)];
-        v = make_uint4(f4_spread8(word), f4_spread8(word >> 8), f4_spread8(word >> 16), f4_spread8(word >> 24));
+    const int N = a_.N, M = a_.M, E = a_.E;
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= (long long)a_.rows * E) return;
+    const int k = (int)(g / E), w = (int)(g - (long long)k * E);
+    uint32_t diff = 0u, valid = 0u;  // bit b: position 32 w + b differs from sigma / is a position of the alignment
+    const int nb = min(32, N - w * 32);  // (<= 0: a pad entry)
+    if (k < M && nb > 0) {
+        const int8_t *src = Z + (size_t)k * N + (size_t)w * 32;
+        valid = nb == 32 ? 0xffffffffu : ((1u << nb) - 1u);
+        if (nb == 32 && (N & 3) == 0 && (reinterpret_cast<uintptr_t>(Z) & 3) == 0) {
+            const uint32_t *s4 = reinterpret_cast<const uint32_t *>(src), *g4 = reinterpret_cast<const uint32_t *>(sigma + w * 32);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                uint32_t x = (s4[j] & 0x1f1f1f1fu) ^ g4[j];  // bytes that differ -> one bit each
+                x |= x >> 4;
+                x |= x >> 2;
+                x |= x >> 1;
+                x &= 0x01010101u;
+                diff |= (((x * 0x01020408u) >> 24) & 0xfu) << (4 * j);
+            }
+        } else {
+            for (int b = 0; b < nb; ++b) diff |= (uint32_t)(((uint32_t)(uint8_t)src[b] & 31u) != (uint32_t)sigma[w * 32 + b]) << b;
+        }
     }
-    img[(size_t)k * E + e] = v;
+    // (rows beyond the alignment and pad entries: valid = 0, all 0.0)
+    img[g] = make_uint4(f4_nibbles8(diff, valid), f4_nibbles8(diff >> 8, valid >> 8), f4_nibbles8(diff >> 16, valid >> 16), f4_nibbles8(diff >> 24, valid >> 24));
 }
 
 // ---- S = X X^T by 256 x 256 tiles, thresholded ---------------------------------------------------------------------------------------
@@ -107,13 +174,14 @@ __device__ __forceinline__ void f4_tri_decode(int t, int Mt, int &I, int &J)
 
 struct k_hamming_fp4_args {
     const unsigned char *img;  // the image, E entries of 16 bytes per row
-    int E, M, Mt, NW;          // Mt: 256-tiles per side
+    int E, M, Mt, N;           // Mt: 256-tiles per side
     gdca_dev_scalars *sc;
     int2 *cand_list;
     unsigned cand_cap;
 };
-__shared__ unsigned f4_tile_n, f4_tile_base;
-template <int CAP>
+__shared__ unsigned f4_tile_n[2], f4_tile_base;  // (f4_tile_n: tile t of a walk counts into slot t % 2)
+// ARES: the A strip (at most two chunks) is loaded once and stays in LDS; else A is streamed beside B
+template <int CAP, bool ARES>
 __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_fp4_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
@@ -122,41 +190,57 @@ __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_
     const int thresh = sc->thresh;
     if (thresh <= 0) return;  // theta == 0: every n_k = 1
     const unsigned char *__restrict__ img = a_.img;
-    const int E = a_.E, M = a_.M, Mt = a_.Mt, NW = a_.NW;
+    const int E = a_.E, M = a_.M, Mt = a_.Mt;
     int2 *__restrict__ cand_list = a_.cand_list;
     const unsigned cand_cap = a_.cand_cap;
     extern __shared__ __attribute__((aligned(16))) unsigned char f4_lds[];
 
-    int I, J;
-    f4_tri_decode((int)blockIdx.x, Mt, I, J);
+    // the walk: tiles J0 .. J1 - 1 of row I (grid: x = walk of the row, y = row; rows near the bottom of the triangle have fewer walks)
+    const int I = (int)blockIdx.y, J0 = I + (int)blockIdx.x * F4_SEG;
+    if (J0 >= Mt) return;
+    const int J1 = min(Mt, J0 + F4_SEG);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv & 3, wc = wv >> 2;
     const int l32 = lane & 31, lh = lane >> 5;
-    if (tid == 0) f4_tile_n = 0u;
+    if (tid == 0) {
+        f4_tile_n[0] = 0u;
+        f4_tile_n[1] = 0u;
+    }
     const size_t rowbytes = (size_t)E * 16;
-    const int nchunk = E / (2 * F4_KC);  // (rows hold whole chunks)
+    const int nchunk = E / (2 * F4_KC);  // (rows hold whole chunks; ARES: 1 or 2)
+    const int total = (J1 - J0) * nchunk;  // chunks of the walk
 
-    // staging: a chunk is 2 x 256 rows x 8 pieces of 16 bytes; thread t takes pieces t, t + 1024 (operand A: tile row I) and t + 2048,
-    // t + 3072 (operand B: tile row J): piece id -> row (id % 2048) / 8, piece id % 8 (eight consecutive threads: 128 contiguous bytes of
-    // a row).  Named registers: as an array behind lambdas the four pieces lived in scratch.
+    // staging: a chunk is 256 rows x 8 pieces of 16 bytes per operand; thread t takes pieces t and t + 1024 of either: piece id -> row
+    // id / 8, piece id % 8 (eight consecutive threads: 128 contiguous bytes of a row).  Named registers: as an array behind lambdas
+    // the pieces lived in scratch.  LDS: regions 0, 1 = A (ARES: chunks 0, 1 of the strip; else two buffers), 2, 3 = B's two buffers.
     const int srow = tid >> 3, spc = tid & 7;  // (pieces t and t + 1024: rows srow and srow + 128)
-    const unsigned char *ga = img + ((size_t)I * F4_TILE + srow) * rowbytes + spc * 16, *gb = img + ((size_t)J * F4_TILE + srow) * rowbytes + spc * 16;
-    const size_t half = (size_t)128 * rowbytes;
-    unsigned char *la = f4_lds + srow * F4_ROW + spc * 16;  // (+ 128 F4_ROW: the second piece; + F4_OP: operand B; + 2 F4_OP: the other buffer)
+    const unsigned char *ga = img + ((size_t)I * F4_TILE + srow) * rowbytes + spc * 16;
+    const unsigned char *gb0 = img + (size_t)srow * rowbytes + spc * 16;  // (+ J F4_TILE rowbytes)
+    const size_t half = (size_t)128 * rowbytes, tilebytes = (size_t)F4_TILE * rowbytes;
+    unsigned char *la = f4_lds + srow * F4_ROW + spc * 16;
     uint4 s0, s1, s2, s3;
-#define F4_LOAD(ch)                                                                       \
+    s0 = s1 = make_uint4(0u, 0u, 0u, 0u);
+#define F4_LOAD_A(ch)                                                                     \
     do {                                                                                  \
         s0 = *reinterpret_cast<const uint4 *>(ga + (size_t)(ch) * (32 * F4_KC));          \
         s1 = *reinterpret_cast<const uint4 *>(ga + half + (size_t)(ch) * (32 * F4_KC));   \
-        s2 = *reinterpret_cast<const uint4 *>(gb + (size_t)(ch) * (32 * F4_KC));          \
-        s3 = *reinterpret_cast<const uint4 *>(gb + half + (size_t)(ch) * (32 * F4_KC));   \
     } while (0)
-#define F4_STORE(buf)                                                                     \
+#define F4_LOAD_B(J, ch)                                                                                      \
+    do {                                                                                                      \
+        const unsigned char *g_ = gb0 + (size_t)(J) * tilebytes + (size_t)(ch) * (32 * F4_KC);                \
+        s2 = *reinterpret_cast<const uint4 *>(g_);                                                            \
+        s3 = *reinterpret_cast<const uint4 *>(g_ + half);                                                     \
+    } while (0)
+#define F4_STORE_A(region)                                                                \
     do {                                                                                  \
-        unsigned char *d_ = la + (size_t)(2 * (buf)) * F4_OP;                             \
+        unsigned char *d_ = la + (size_t)(region) * F4_OP;                                \
         *reinterpret_cast<uint4 *>(d_) = s0;                                              \
         *reinterpret_cast<uint4 *>(d_ + 128 * F4_ROW) = s1;                               \
-        *reinterpret_cast<uint4 *>(d_ + F4_OP) = s2;                                      \
-        *reinterpret_cast<uint4 *>(d_ + F4_OP + 128 * F4_ROW) = s3;                       \
+    } while (0)
+#define F4_STORE_B(buf)                                                                   \
+    do {                                                                                  \
+        unsigned char *d_ = la + (size_t)(2 + (buf)) * F4_OP;                             \
+        *reinterpret_cast<uint4 *>(d_) = s2;                                              \
+        *reinterpret_cast<uint4 *>(d_ + 128 * F4_ROW) = s3;                               \
     } while (0)
 
     f32x16_t acc[2][2];
@@ -169,14 +253,35 @@ __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_
     const int one = 0x7f7f7f7f;  // E8M0 scale 2^0 for both operands
 
     // this lane's rows of the two operands inside a chunk: row (lane % 32) of its wave's first block, entry (lane / 32) of a k step
-    const unsigned char *abase = f4_lds + (wr * 64 + l32) * F4_ROW + lh * 16, *bbase = f4_lds + F4_OP + (wc * 64 + l32) * F4_ROW + lh * 16;
-    F4_LOAD(0);
-    F4_STORE(0);
+    const unsigned char *abase = f4_lds + (wr * 64 + l32) * F4_ROW + lh * 16, *bbase = f4_lds + 2 * F4_OP + (wc * 64 + l32) * F4_ROW + lh * 16;
+    // candidates: S > N - 2 thresh  <=>  D1 = (N - S) / 2 < thresh.  (K = N: the positions beyond N are 0.0 nibbles in both operands.)
+    const float limit = (float)(a_.N - 2 * thresh);
+
+    if constexpr (ARES) {
+        F4_LOAD_A(0);
+        F4_STORE_A(0);
+        if (nchunk > 1) {
+            F4_LOAD_A(1);
+            F4_STORE_A(1);
+        }
+    } else {
+        F4_LOAD_A(0);
+        F4_STORE_A(0);
+    }
+    F4_LOAD_B(J0, 0);
+    F4_STORE_B(0);
     __syncthreads();
-    for (int ch = 0; ch < nchunk; ++ch) {
-        const int buf = ch & 1;
-        if (ch + 1 < nchunk) F4_LOAD(ch + 1);  // in flight under this chunk's MFMAs
-        const unsigned char *As = abase + (size_t)(2 * buf) * F4_OP, *Bs = bbase + (size_t)(2 * buf) * F4_OP;
+    int J = J0, ch = 0;  // the chunk being multiplied
+    for (int it = 0; it < total; ++it) {
+        const int buf = it & 1;
+        const bool more = it + 1 < total;
+        const bool last = ch + 1 == nchunk;  // (of tile J)
+        const int Jn = last ? J + 1 : J, chn = last ? 0 : ch + 1;
+        if (more) {  // in flight under this chunk's MFMAs
+            if constexpr (!ARES) F4_LOAD_A(chn);
+            F4_LOAD_B(Jn, chn);
+        }
+        const unsigned char *As = abase + (size_t)(ARES ? ch : buf) * F4_OP, *Bs = bbase + (size_t)buf * F4_OP;
         // (one k step at a time: unrolled, the compiler hoists all sixteen 16-byte reads of the chunk in front of the first MFMA and the
         // kernel no longer fits the 128 registers a 1024-thread workgroup has per lane; four waves per SIMD cover a step's read latency)
 #pragma unroll 1
@@ -198,132 +303,176 @@ __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[i], b[j], acc[i][j], 4, 4, 0, one, 0, one);
         }
-        if (ch + 1 < nchunk) F4_STORE(buf ^ 1);  // (the other buffer: its readers passed the barrier of the chunk before)
-        __syncthreads();
-    }
-
-    // ---- candidates: S > K - 6 thresh  <=>  D = (K - S) / 2 < 3 thresh ----
-    // accumulator element e of block (i, j): row 8 (e / 4) + 4 (lane / 32) + e % 4, column lane % 32
-    const float limit = (float)(96 * NW - 6 * thresh);  // K = the 96 NW real bit positions (pad bits of the last word agree: both 0)
-    const bool diag = I == J;
-    unsigned mine = 0;
-    unsigned long long cand[2] = {0ull, 0ull};  // bit 16 j + e of cand[i]: element e of block (i, j)
-    // (most lanes of most tiles hold nothing above the limit: one maximum over the 64 accumulators decides that)
-    float mx = acc[0][0][0];
+        if (more) {  // (the other buffers: their readers passed the barrier of the chunk before)
+            if constexpr (!ARES) F4_STORE_A(buf ^ 1);
+            F4_STORE_B(buf ^ 1);
+        }
+        if (last) {
+            // ---- tile J is complete: its candidates, then the accumulators start over ----
+            // accumulator element e of block (i, j): row 8 (e / 4) + 4 (lane / 32) + e % 4, column lane % 32
+            const int slot_n = (J - J0) & 1;
+            const bool diag = I == J;
+            unsigned mine = 0;
+            unsigned long long cand[2] = {0ull, 0ull};  // bit 16 j + e of cand[i]: element e of block (i, j)
+            // (most lanes of most tiles hold nothing above the limit: one maximum over the 64 accumulators decides that)
+            float mx = acc[0][0][0];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, acc[i][j][e]);
-    if (mx > limit) {
+                    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, acc[i][j][e]);
+            if (mx > limit) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int gc = J * F4_TILE + wc * 64 + j * 32 + l32;
+                    for (int j = 0; j < 2; ++j) {
+                        const int gc = J * F4_TILE + wc * 64 + j * 32 + l32;
 #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int gr = I * F4_TILE + wr * 64 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
-                    if (acc[i][j][e] > limit && gr < M && gc < M && (diag ? gr < gc : true)) {
-                        cand[i] |= 1ull << (16 * j + e);
-                        ++mine;
+                        for (int e = 0; e < 16; ++e) {
+                            const int gr = I * F4_TILE + wr * 64 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
+                            if (acc[i][j][e] > limit && gr < M && gc < M && (diag ? gr < gc : true)) {
+                                cand[i] |= 1ull << (16 * j + e);
+                                ++mine;
+                            }
+                        }
+                    }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+            const unsigned off = mine ? atomicAdd(&f4_tile_n[slot_n], mine) : 0u;
+            __syncthreads();
+            const unsigned ntile = f4_tile_n[slot_n];  // (uniform)
+            // (the other slot: its readers -- the tile before -- are all past this barrier, its next writers behind the chunk's barrier below)
+            if (tid == 0) f4_tile_n[slot_n ^ 1] = 0u;
+            if (ntile != 0u) {
+                if (tid == 0) {
+                    const unsigned long long base = atomicAdd(&sc->ham_ncand, (unsigned long long)ntile);
+                    f4_tile_base = base > (unsigned long long)cand_cap ? cand_cap : (unsigned)base;  // (beyond the capacity nothing is written)
+                }
+                __syncthreads();
+                unsigned slot = f4_tile_base + off;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    unsigned long long c = cand[i];
+                    while (c) {
+                        const int bit = __builtin_ctzll(c), j = bit >> 4, e = bit & 15;
+                        const int gr = I * F4_TILE + wr * 64 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
+                        const int gc = J * F4_TILE + wc * 64 + j * 32 + l32;
+                        if (slot < cand_cap) cand_list[slot] = make_int2(gr, gc);
+                        ++slot;
+                        c &= c - 1;
                     }
                 }
             }
-    }
-    const unsigned off = mine ? atomicAdd(&f4_tile_n, mine) : 0u;
-    __syncthreads();
-    if (f4_tile_n == 0u) return;  // (uniform)
-    if (tid == 0) {
-        const unsigned long long base = atomicAdd(&sc->ham_ncand, (unsigned long long)f4_tile_n);
-        f4_tile_base = base > (unsigned long long)cand_cap ? cand_cap : (unsigned)base;  // (beyond the capacity nothing is written)
-    }
-    __syncthreads();
-    unsigned slot = f4_tile_base + off;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        unsigned long long c = cand[i];
-        while (c) {
-            const int bit = __builtin_ctzll(c), j = bit >> 4, e = bit & 15;
-            const int gr = I * F4_TILE + wr * 64 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
-            const int gc = J * F4_TILE + wc * 64 + j * 32 + l32;
-            if (slot < cand_cap) cand_list[slot] = make_int2(gr, gc);
-            ++slot;
-            c &= c - 1;
         }
+        J = Jn;
+        ch = chn;
+        __syncthreads();
     }
 }
 
-// ---- how many pairs would this form list?  (a sample of 128 x 128 tiles, as k_hamming<3, PROBE> takes for the three-plane form) ------
-// D counted with plain popcounts from the bit planes: 192 tiles, microseconds.  sc->ham_cand2 += pairs of the sampled tiles with D < 3 thresh.
+// ---- how many pairs would this form list?  (a sample of 128 x 128 tiles, the very tiles k_hamming<3, PROBE> takes for the three-plane form) ------
+// D1 counted with plain popcounts of the image's sign bits: 192 tiles, microseconds.  sc->ham_cand2 += pairs of the sampled tiles with
+// D1 < thresh (a diagonal tile's pairs twice, as the three-plane probe counts them).
+#define F4_PW 8  // words per round of the probe
 struct k_fp4_probe_args {
-    const uint32_t *Zb;
-    int NW, M, Mt;  // Mt: 128-tiles per side
+    const uint4 *img;
+    int E, NW, M, Mt;  // Mt: 128-tiles per side
     gdca_dev_scalars *sc;
 };
 template <int CAP>
 __global__ __launch_bounds__(256) void k_fp4_probe(const BatchArgs<k_fp4_probe_args, CAP> B_)
 {
     GDCA_MEMBER(B_);
-    const uint32_t *__restrict__ Zb = a_.Zb;
-    const int NW = a_.NW, M = a_.M, Mt = a_.Mt;
+    const uint4 *__restrict__ img = a_.img;
+    const int E = a_.E, NW = a_.NW, M = a_.M, Mt = a_.Mt;
     gdca_dev_scalars *sc = a_.sc;
     const int thresh = sc->thresh;
     if (thresh <= 0) return;
     __shared__ int total;
+    __shared__ uint32_t bits[2][F4_PW][128];  // [operand][word of the round][row of the tile]
     int I, J;
-    // (gridDim.x tiles spread evenly over the upper triangle's Mt (Mt + 1) / 2, the very tiles the three-plane probe samples)
+    // (gridDim.x tiles spread evenly over the upper triangle's Mt (Mt + 1) / 2)
     f4_tri_decode((int)(((long long)blockIdx.x * ((long long)Mt * (Mt + 1) / 2)) / gridDim.x), Mt, I, J);
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     if (tid == 0) total = 0;
-    __syncthreads();
     int D[8][8];
 #pragma unroll
     for (int r = 0; r < 8; ++r)
 #pragma unroll
         for (int c = 0; c < 8; ++c) D[r][c] = 0;
-    const uint32_t *Ag = Zb + (size_t)I * 5 * NW * 128, *Bg = Zb + (size_t)J * 5 * NW * 128;
-    for (int w = 0; w < NW; ++w)
+    // thread t < 128: row t of tile row I; else row t - 128 of tile row J (the image's rows are padded to 256: in bounds)
+    const uint4 *mine = img + (size_t)((tid < 128 ? I : J) * 128 + (tid & 127)) * E;
+    for (int w0 = 0; w0 < NW; w0 += F4_PW) {
+        __syncthreads();
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
+        for (int u = 0; u < F4_PW; ++u) {
+            uint32_t b = 0u;
+            if (w0 + u < NW) {
+                const uint4 v = mine[w0 + u];
+                b = f4_signs8(v.x) | (f4_signs8(v.y) << 8) | (f4_signs8(v.z) << 16) | (f4_signs8(v.w) << 24);
+            }
+            bits[tid >> 7][u][tid & 127] = b;
+        }
+        __syncthreads();
+        const int wn = min(F4_PW, NW - w0);
+        for (int u = 0; u < wn; ++u) {
             uint32_t a[8], b[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) a[r] = Ag[((size_t)p * NW + w) * 128 + ty * 8 + r];
+            for (int r = 0; r < 8; ++r) a[r] = bits[0][u][ty * 8 + r];
 #pragma unroll
-            for (int c = 0; c < 8; ++c) b[c] = Bg[((size_t)p * NW + w) * 128 + tx * 8 + c];
+            for (int c = 0; c < 8; ++c) b[c] = bits[1][u][tx * 8 + c];
 #pragma unroll
             for (int r = 0; r < 8; ++r)
 #pragma unroll
                 for (int c = 0; c < 8; ++c) D[r][c] += __builtin_popcount(a[r] ^ b[c]);
         }
+    }
     int cand = 0;
 #pragma unroll
     for (int r = 0; r < 8; ++r)
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const int gr = I * 128 + ty * 8 + r, gc = J * 128 + tx * 8 + c;
-            cand += (gr < M) && (gc < M) && (gr != gc) && (D[r][c] < 3 * thresh);
+            cand += (gr < M) && (gc < M) && (gr != gc) && (D[r][c] < thresh);
         }
     if (cand) atomicAdd(&total, cand);
     __syncthreads();
     if (tid == 0 && total) atomicAdd(&sc->ham_cand2, total);
 }
 
-void gdca_launch_hamming_fp4_probe(hipStream_t s, const uint32_t *Zb, int N, int M, int nprobe, gdca_dev_scalars *sc)
+// sigma and the image: before the probe and the decision (the probe reads the image), for every family that may take this form
+void gdca_launch_hamming_fp4_image(hipStream_t s, const int8_t *Z, const uint32_t *hist, void *img, int N, int M)
 {
-    const int NW = (N + 31) / 32, Mt = (M + 127) / 128;
-    gdca_launch<k_fp4_probe_args, k_fp4_probe<1>, k_fp4_probe<GDCA_MAXB>>(dim3((unsigned)nprobe), dim3(256), 0, s, k_fp4_probe_args{Zb, NW, M, Mt, sc});
+    const int NW = (N + 31) / 32, E = f4_entries(NW), rows = (M + F4_TILE - 1) / F4_TILE * F4_TILE;
+    uint8_t *sigma = (uint8_t *)img + f4_image_only_bytes(N, M);
+    gdca_launch<k_fp4_sigma_args, k_fp4_sigma<1>, k_fp4_sigma<GDCA_MAXB>>(dim3((unsigned)((32 * E + 255) / 256)), dim3(256), 0, s, k_fp4_sigma_args{hist, sigma, N, 32 * E});
+    const long long items = (long long)rows * E;
+    gdca_launch<k_fp4_image_args, k_fp4_image<1>, k_fp4_image<GDCA_MAXB>>(dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s,
+                                                                           k_fp4_image_args{Z, sigma, (uint4 *)img, N, M, E, rows});
 }
 
-// Enqueues the image build and the tile products; both leave at once unless k_hamming_decide chose this form (sc->ham_mode == 2).
-// img: gdca_fp4_image_bytes(N, M) of scratch; cand_list / cap: the list k_hamming_refine consumes.
-void gdca_launch_hamming_fp4(hipStream_t s, const uint32_t *Zb, void *img, int N, int M, gdca_dev_scalars *sc, void *cand_list, unsigned cap)
+void gdca_launch_hamming_fp4_probe(hipStream_t s, const void *img, int N, int M, int nprobe, gdca_dev_scalars *sc)
+{
+    const int NW = (N + 31) / 32, Mt = (M + 127) / 128;
+    gdca_launch<k_fp4_probe_args, k_fp4_probe<1>, k_fp4_probe<GDCA_MAXB>>(dim3((unsigned)nprobe), dim3(256), 0, s,
+                                                                           k_fp4_probe_args{(const uint4 *)img, f4_entries(NW), NW, M, Mt, sc});
+}
+
+// Enqueues the tile products; they leave at once unless k_hamming_decide chose this form (sc->ham_mode == 2).
+// img: the image gdca_launch_hamming_fp4_image built; cand_list / cap: the list k_hamming_refine consumes.
+void gdca_launch_hamming_fp4(hipStream_t s, const void *img, int N, int M, gdca_dev_scalars *sc, void *cand_list, unsigned cap)
 {
     const int NW = (N + 31) / 32, E = f4_entries(NW), Mt = (M + F4_TILE - 1) / F4_TILE;
-    const long long ntile = (long long)Mt * (Mt + 1) / 2;
-    gdca_launch<k_fp4_image_args, k_fp4_image<1>, k_fp4_image<GDCA_MAXB>>(dim3((unsigned)Mt, (unsigned)E), dim3(256), 0, s,
-                                                                           k_fp4_image_args{Zb, (uint4 *)img, NW, M, E, sc});
-    gdca_launch<k_hamming_fp4_args, k_hamming_fp4<1>, k_hamming_fp4<GDCA_MAXB>>(dim3((unsigned)ntile), dim3(1024), F4_LDS, s,
-                                                                                 k_hamming_fp4_args{(const unsigned char *)img, E, M, Mt, NW, sc, (int2 *)cand_list, cap});
+    const dim3 grid((unsigned)((Mt + F4_SEG - 1) / F4_SEG), (unsigned)Mt);
+    const k_hamming_fp4_args a{(const unsigned char *)img, E, M, Mt, N, sc, (int2 *)cand_list, cap};
+    if (E <= 4 * F4_KC)
+        gdca_launch<k_hamming_fp4_args, k_hamming_fp4<1, true>, k_hamming_fp4<GDCA_MAXB, true>>(grid, dim3(1024), F4_LDS, s, a);
+    else
+        gdca_launch<k_hamming_fp4_args, k_hamming_fp4<1, false>, k_hamming_fp4<GDCA_MAXB, false>>(grid, dim3(1024), F4_LDS, s, a);
 }

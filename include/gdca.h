@@ -168,7 +168,8 @@ gdca_status gdca_ctx_set_timing(gdca_ctx *ctx, int32_t enabled);
  * or without the GDCA_ prefix, any case; value = what the variable would hold.  Schedule of the SPD inverse: GROUP (1..4, -1 = the
  * measured rule), RAMP, RAGGED, REM_TAIL, PANEL_HALVES, SLAB, RING, MCUS, MCU_SOLO; SWEEP_TIMEOUT_MS (bound of one dependency wait inside
  * the sweep kernel; 0 = scaled with the problem, at least 4 s), SWEEP_RETRIES (0..5: further attempts of an inverse whose launch the watchdog ended), SWEEP_DEBUG, SWEEP_TRACE (file); HAMMING_MODE (auto | full |
- * bound | mfma: the bit-count lower bound on the fp4 matrix pipe -- exact counts, never the automatic choice), HAM_CUT (tests, measurements: the word at which the three-plane bound goes from all pairs of a tile to
+ * bound | mfma: which form counts the neighbours -- auto [default] picks per family from sampled tiles; full = exact five-plane distances; bound = the three low planes as a lower bound; mfma = the consensus plane,
+ * "differs from the column's most frequent symbol", as a lower bound on the fp4 matrix pipe; either bound's listed pairs are counted exactly: the same integers whatever the form), HAM_CUT (tests, measurements: the word at which the three-plane bound goes from all pairs of a tile to
  * the pairs still below the threshold; 0 = chosen per family from the sampled tiles [default], k >= 1 = word k, beyond the last word = never: the same counts whatever it is), FORCE_FALLBACK (the independent byte-compare Hamming kernel, cf. DCAUTILS_FORCE_FALLBACK in test/runtests.jl:78-86),
  * TALLY_TJ; TALLY_SKIP (1 = the pair tally skips each column's most frequent symbol and recovers that row from the single-site sums
  * [default], 0 = it tallies every sequence: the same bits either way); MERGE (families per merged SPD-inverse launch in gdca_run_dev_phased, 1 = off), MERGE_BLOCKS (largest member, in
