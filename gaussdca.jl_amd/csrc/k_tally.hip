@@ -336,7 +336,7 @@ void gdca_launch_pi_finalize(hipStream_t s, const u64 *Pifix, int N, int q, int 
 #define TALLY_CHUNK 1024  // sequences staged per pass (one per thread)
 
 // Workgroup = (column i) x (block of TJ columns j >= i's block), 1024 threads = 16 waves (the
-// histograms take most of the LDS, so one workgroup per CU: the waves have to come from here).
+// histograms take most of the LDS, so one or two workgroups per CU: the waves have to come from here).
 // Per pass of 1024 sequences the block's TJ bytes of every sequence and a packed
 // {row(Z[i,k]), Wfix[k]} word are staged in LDS (the next pass's global loads are in flight while
 // the current one is tallied), then each wave walks 64 sequences, 64/TJ at a time: lane =
@@ -396,14 +396,29 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
     size_t ld = a_.ld;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int s = q - 1;
+#ifdef GDCA_TALLY_OLD_MAP  // (measurement builds only: the rectangular grid with the skewed column block, empty workgroups left of the diagonal)
     const int i = blockIdx.y;
-    // Skewed column-block index: workgroups go to the 8 XCDs round-robin in linear block order, and with the
-    // plain mapping XCD x would get the column blocks == x (mod 8), whose share of non-empty (j >= i) blocks
-    // differs by 2x between the first and the last.  The skew spreads the early-exit blocks evenly
-    // (measured at N=500, M=50k: 5.9 -> 3.7 ms).
     const int jblk = (blockIdx.x + blockIdx.y) % gridDim.x;
     const int j0 = jblk * TJ;
-    if (j0 + TJ - 1 < i) return;  // block entirely left of the diagonal: its mirror does the work
+    if (j0 + TJ - 1 < i) return;
+#else
+    // The grid is the member's working workgroups and nothing else (tally_grid), in one line: column block OUTERMOST, the widest
+    // (last) first, row i fastest.  Column block jb pairs with rows 0 .. min(N, (jb + 1) TJ) - 1, so counted from the back the
+    // blocks in front of jb hold TJ jb (jb + 1) / 2 ids: a closed form, inverted with a square root and corrected in integers.
+    // Workgroups go to the 8 XCDs round-robin by linear id and a CU holds two, so the 512 resident at any time are consecutive rows
+    // of the same one or two column blocks: every XCD's L2 is asked for the same 16 M bytes of Zc and the same Wfix, walked in the
+    // same direction of k, and the rows -- whose kept lists are what makes a workgroup long or short -- are dealt round-robin.
+    // (The rectangular grid it replaces, column block skewed by the row, had the 64 workgroups of an XCD on all 32 column blocks:
+    // at N = 500, M = 50k its L2 hit rate was 37 % against 83 % now, and 7 564 of its 16 000 workgroups returned at once.)
+    const unsigned lin = gridDim.x * gridDim.y - 1u - (blockIdx.y * gridDim.x + blockIdx.x);  // counted from the back: ascending (jb, i)
+    const unsigned tri = lin / TJ;
+    unsigned jb = (unsigned)((sqrtf(8.0f * (float)tri + 1.0f) - 1.0f) * 0.5f);
+    while (jb * (jb + 1u) / 2u > tri) --jb;
+    while ((jb + 1u) * (jb + 2u) / 2u <= tri) ++jb;  // (the last block may be narrow: its N rows are fewer ids than a full block's)
+    const int jblk = (int)jb;
+    const int j0 = jblk * TJ;
+    const int i = (int)(lin - (unsigned)TJ * (jb * (jb + 1u) / 2u));
+#endif
 
     const int NROW = SKIP ? q : s;                                                // histogram rows
     const int CB = SKIP ? 0 : 1;                                                  // histogram column of state b (0..s-1): b + CB
@@ -433,14 +448,24 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
     uint4 z0 = make_uint4(0, 0, 0, 0), z1 = z0;
     u64 wf = 0;
     int8_t av = 0;
+    // SKIP: the list entry of the sequence TALLY_FETCH gathers next.  It is loaded a whole pass before that fetch (TALLY_ENTRY), so
+    // the fetch issues its Zc and Wfix gathers from a register and no wave waits, right behind the staging barriers, for a load it
+    // has only just issued.
+    uint32_t en = 0;
+#define TALLY_ENTRY(KC)                                                                       \
+    do {                                                                                      \
+        if (SKIP) {                                                                           \
+            int k_ = (KC) + tid;                                                              \
+            en = keep_i[k_ < nk ? k_ : nk - 1]; /* the same clamp as the fetch it feeds */    \
+        }                                                                                     \
+    } while (0)
 #define TALLY_FETCH(KC)                                                                       \
     do {                                                                                      \
         int k_ = (KC) + tid;                                                                  \
         k_ = k_ < nk ? k_ : nk - 1; /* clamp: the tail is staged with weight 0 */             \
         if (SKIP) {                                                                           \
-            const uint32_t e_ = keep_i[k_];                                                   \
-            av = (int8_t)(e_ & 31u);                                                          \
-            k_ = (int)(e_ >> 5);                                                              \
+            av = (int8_t)(en & 31u);                                                          \
+            k_ = (int)(en >> 5);                                                              \
         }                                                                                     \
         const uint4 *src_ = reinterpret_cast<const uint4 *>(Zblk + (size_t)k_ * TJ);          \
         z0 = src_[0];                                                                         \
@@ -448,7 +473,12 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
         if (!SKIP) av = Zt[(size_t)i * M + k_];                                               \
         wf = Wfix[k_];                                                                        \
     } while (0)
-    if (nk > 0) TALLY_FETCH(0);  // (SKIP: an empty list stages nothing)
+    if (nk > 0) {  // (SKIP: an empty list stages nothing)
+        TALLY_ENTRY(0);
+        TALLY_FETCH(0);
+        TALLY_ENTRY(TALLY_CHUNK);  // (unconditional, here and below: the clamp keeps it inside the list, and a load under a condition
+                                   // of its own is waited for where it is issued)
+    }
     for (int kc = 0; kc < nk; kc += TALLY_CHUNK) {
         __syncthreads();  // previous pass fully consumed (and hist zeroed, first time)
         {
@@ -459,10 +489,17 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_pair_tally(const BatchArgs<k_
             meta_s[tid] = valid ? (((u64)a << 59) | (wf & wmask)) : 0ull;
         }
         __syncthreads();
-        if (kc + TALLY_CHUNK < nk) TALLY_FETCH(kc + TALLY_CHUNK);
+        if (kc + TALLY_CHUNK < nk) {
+            TALLY_FETCH(kc + TALLY_CHUNK);
+            TALLY_ENTRY(kc + 2 * TALLY_CHUNK);
+        }
         const int kw = wv * SEQ_PER_WAVE;
+        // the last pass: a wave whose slice starts at or behind nk has nothing to add, one that straddles nk stops behind the step
+        // of four instructions that covers it (the staged tail has weight 0: adds that feed nothing).  Wave-uniform, no barrier inside.
+        const int left = nk - kc - __builtin_amdgcn_readfirstlane(kw);
+        const int nit = left >= SEQ_PER_WAVE ? SEQ_PER_WAVE / SPI : left > 0 ? (left + 4 * SPI - 1) / (4 * SPI) * 4 : 0;
 #pragma unroll 2
-        for (int it = 0; it < SEQ_PER_WAVE / SPI; it += 4) {
+        for (int it = 0; it < nit; it += 4) {
             u64 m4[4];
             unsigned b4[4];
 #pragma unroll
@@ -553,6 +590,18 @@ static size_t tally_lds_bytes(int s, int TJ, bool skip = false)
     return hist + (size_t)TALLY_CHUNK * 8 + (size_t)TALLY_CHUNK * TJ;
 }
 
+// The workgroups of one family, in one line: column block jb against its rows 0 .. min(N, (jb + 1) TJ) - 1 (what k_pair_tally
+// decodes).  The blocks in front of the last are full, so they hold TJ (1 + 2 + ... + (nblk - 1)) ids, and the last holds N.
+static dim3 tally_grid(int N, int TJ)
+{
+#ifdef GDCA_TALLY_OLD_MAP
+    return dim3((N + TJ - 1) / TJ, N);
+#else
+    const unsigned long long nblk = ((unsigned)N + TJ - 1) / TJ;
+    return dim3((unsigned)((unsigned long long)TJ * (nblk * (nblk - 1) / 2) + (unsigned)N), 1);
+#endif
+}
+
 int gdca_tally_tj(int q, int tj_wanted)
 {
     // 16 columns per workgroup: 80 KB of histograms at s = 20, so TWO 1024-thread workgroups share a CU and one's staging
@@ -579,16 +628,17 @@ void gdca_launch_pair_tally(hipStream_t st, const int8_t *Zc, const int8_t *Zt, 
     const bool skip = keep != nullptr;
     const k_pair_tally_args a = k_pair_tally_mk(Zc, Zt, Wfix, N, M, q, fix_shift, Meff_dev, pc, Pi_pc, mode, out, ld, keep, keep_n, sigma, Pifix);
     const size_t lds = tally_lds_bytes(s, TJ, skip);
+    const dim3 grid = tally_grid(N, TJ);
     if (TJ == 32) {
         if (skip)
-            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 32, true>, k_pair_tally<GDCA_MAXB, 32, true>>(dim3((N + 31) / 32, N), dim3(TALLY_THREADS), lds, st, a));
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 32, true>, k_pair_tally<GDCA_MAXB, 32, true>>(grid, dim3(TALLY_THREADS), lds, st, a));
         else
-            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 32, false>, k_pair_tally<GDCA_MAXB, 32, false>>(dim3((N + 31) / 32, N), dim3(TALLY_THREADS), lds, st, a));
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 32, false>, k_pair_tally<GDCA_MAXB, 32, false>>(grid, dim3(TALLY_THREADS), lds, st, a));
     } else {
         if (skip)
-            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16, true>, k_pair_tally<GDCA_MAXB, 16, true>>(dim3((N + 15) / 16, N), dim3(TALLY_THREADS), lds, st, a));
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16, true>, k_pair_tally<GDCA_MAXB, 16, true>>(grid, dim3(TALLY_THREADS), lds, st, a));
         else
-            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16, false>, k_pair_tally<GDCA_MAXB, 16, false>>(dim3((N + 15) / 16, N), dim3(TALLY_THREADS), lds, st, a));
+            (gdca_launch<k_pair_tally_args, k_pair_tally<1, 16, false>, k_pair_tally<GDCA_MAXB, 16, false>>(grid, dim3(TALLY_THREADS), lds, st, a));
     }
 }
 

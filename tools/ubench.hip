@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
+#include <string.h>
 #include <vector>
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -79,8 +80,14 @@ int run_probe_i8(int wps)
 }
 
 // ---- tally-loop replica: per wave-instruction 2 LDS reads (b64 broadcast per half-wave + u8) and
-// one ds_add_u64; `same_pct` = percent of instructions whose two half-waves use the same row set ----
-__global__ __launch_bounds__(1024) void k_tally_like(unsigned long long *out, int iters, int same_pct, int with_reads)
+// one ds_add_u64; `same_pct` = percent of instructions whose two half-waves use the same row set.
+// MASKED: the add sits under a per-lane predicate (what a two-sided skip of the pair tally would do: a lane whose Z[j,k] is its
+// column's commonest symbol adds nothing).  `active_pct` = percent of (sequence, column) cells that do add, drawn with a fixed seed;
+// -1 = the structured case, columns 4..15 of every 16 off in every sequence.  Does a lane that is switched off cost what an active
+// one does?  (MASKED = false is the loop of old, instruction for instruction.) ----
+#define TALLY_LIKE_OFF 0x80u  // bit 7 of a staged symbol byte: this cell adds nothing
+template <bool MASKED>
+__global__ __launch_bounds__(1024) void k_tally_like(unsigned long long *out, int iters, int same_pct, int with_reads, int active_pct)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     unsigned long long *h = reinterpret_cast<unsigned long long *>(sm);       // [400][32]
@@ -101,6 +108,14 @@ __global__ __launch_bounds__(1024) void k_tally_like(unsigned long long *out, in
             rng = rng * 1664525u + 1013904223u;
             zs[tid * 32 + c] = 1 + ((rng >> 10) % 20);
             if (same_pct < 0 && ((rng >> 20) % 100) < (unsigned)(-same_pct)) zs[tid * 32 + c] = 1 + (c % 20);  // conserved column
+            if (MASKED) {
+                unsigned h = ((unsigned)tid * 32u + (unsigned)c) * 2246822519u + 0x9e3779b9u;
+                h ^= h >> 15;
+                h *= 2654435761u;
+                h ^= h >> 13;
+                const bool off = active_pct < 0 ? (c & 15) >= 4 : (h >> 8) % 100u >= (unsigned)active_pct;
+                if (off) zs[tid * 32 + c] |= TALLY_LIKE_OFF;
+            }
         }
     }
     __syncthreads();
@@ -124,8 +139,8 @@ __global__ __launch_bounds__(1024) void k_tally_like(unsigned long long *out, in
             b = 1 + ((it * 3 + lane) % 20);
         }
         const unsigned a = (unsigned)(m >> 56);
-        const unsigned idx = ((a - 1) * 20 + (b - 1)) * 32 + jl;
-        atomicAdd(&h[idx], m & 0xffffffull);
+        const unsigned idx = ((a - 1) * 20 + ((b & 0x7f) - 1)) * 32 + jl;
+        if (!MASKED || !((unsigned)b & TALLY_LIKE_OFF)) atomicAdd(&h[idx], m & 0xffffffull);
     }
     __syncthreads();
     unsigned long long acc = 0;
@@ -133,25 +148,31 @@ __global__ __launch_bounds__(1024) void k_tally_like(unsigned long long *out, in
     out[blockIdx.x * blockDim.x + tid] = acc;
 }
 
-int run_tally_like(int same_pct, int with_reads, int threads = 512)
+template <bool MASKED = false>
+int run_tally_like(int same_pct, int with_reads, int threads = 512, int active_pct = 100)
 {
     const int blocks = 256, iters = 20000;
     unsigned long long *out;
     CK(hipMalloc(&out, 8 * blocks * threads));
     size_t lds = 8 * (400 * 32 + 64) + 8 * 1024 + 1024 * 32;
-    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tally_like), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tally_like<MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    hipLaunchKernelGGL(k_tally_like, dim3(blocks), dim3(threads), lds, 0, out, 100, same_pct, with_reads);
+    hipLaunchKernelGGL(k_tally_like<MASKED>, dim3(blocks), dim3(threads), lds, 0, out, 100, same_pct, with_reads, active_pct);
     CK(hipEventRecord(e0));
-    hipLaunchKernelGGL(k_tally_like, dim3(blocks), dim3(threads), lds, 0, out, iters, same_pct, with_reads);
+    hipLaunchKernelGGL(k_tally_like<MASKED>, dim3(blocks), dim3(threads), lds, 0, out, iters, same_pct, with_reads, active_pct);
     CK(hipEventRecord(e1));
     CK(hipDeviceSynchronize());
     float ms;
     CK(hipEventElapsedTime(&ms, e0, e1));
-    printf("tally-like threads=%d same_pct=%3d reads=%d: %.3f ms, %.2f clk@2.4GHz per wave-instr per CU\n", threads, same_pct, with_reads, ms,
-           ms * 1e-3 * 2.4e9 / ((double)iters * threads / 64));
+    if (MASKED)
+        printf("tally-like threads=%d same_pct=%3d reads=%d masked, active %s%d%s: %.3f ms, %.2f clk@2.4GHz per wave-instr per CU\n", threads, same_pct,
+               with_reads, active_pct < 0 ? "columns 0..3 of 16 (" : "", active_pct < 0 ? 25 : active_pct, active_pct < 0 ? " %)" : " % at random", ms,
+               ms * 1e-3 * 2.4e9 / ((double)iters * threads / 64));
+    else
+        printf("tally-like threads=%d same_pct=%3d reads=%d: %.3f ms, %.2f clk@2.4GHz per wave-instr per CU\n", threads, same_pct, with_reads, ms,
+               ms * 1e-3 * 2.4e9 / ((double)iters * threads / 64));
     CK(hipFree(out));
     return 0;
 }
@@ -263,8 +284,15 @@ int run_atomic(const char *name, int rows)
     return 0;
 }
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "masked")) {  // the masked-lane question alone (profiles/ubench_lds_atomics_masked.log)
+        for (int threads : {1024, 512}) {
+            run_tally_like(0, 1, threads);
+            for (int pct : {100, 75, 45, 25, -1}) run_tally_like<true>(0, 1, threads, pct);
+        }
+        return 0;
+    }
     run_probe_i8<1>(1);
     run_probe_i8<2>(1);
     run_probe_i8<4>(1);
