@@ -13,7 +13,6 @@
 #include "gdca_internal.h"
 #include "gdca_launch.h"
 
-#define MAX_EV 1024
 #define N_SCRATCH 10
 
 struct gdca_buf {
@@ -97,28 +96,26 @@ static score_target mutation_target(const int8_t *Z, int M, const int8_t *X, int
 }
 
 // The enqueued, not yet collected run (gdca_run_dev_async / gdca_run_collect): all a collect needs to know, grouped by who writes it.
-// The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev, operator_inverse_retry) borrows n, n_pad, timed and
-// at.attempt, so that it can go through run_inverses.
+// The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev, operator_inverse_retry) borrows n, n_pad, timed
+// (false: begin()) and at.attempt, so that it can go through run_inverses.
 struct gdca_pending {
     // ---- the front end (pending_front) ----
     int N, M, q, n, n_pad;
     const int8_t *Z;           // what a refinement at collect time needs to build C again
     const double *pij;         // ... or, a pseudocount group of gdca_run_multi, the stored Pij_true C is built again from (nullptr: the tallies)
     gdca_params p;
-    bool timed;
-    bool stamped;              // the run marked its stages with device time stamps (gdca_ctx::stamped): its collect reads the stamps
+    // the run's timeline (open_timeline, mark, elapsed): whether it is timed at all, its clock -- device time stamps for a member of a
+    // batch issued as batched grids, HIP events otherwise --, and which boundaries have been marked so far, by which of the two clocks
+    bool timed, stamped;
+    unsigned ev_marks, stamp_marks;
     int front_batch;           // members that shared this run's batched front-end grids (1: grids of its own); their stage times are the grids' divided by it
-    int score_batch;           // ... and its score grids (run_phased sets both)
-    bool tally_timed;          // events 9 / 10 around k_pair_tally were recorded by this run
+    int score_batch;           // ... and its score grids (run_phased sets both; 1 again once the stage has run alone at collect time)
     // ---- the inverse (run_inverse, run_inverse_merged) ----
     int n_upd;
     int batch;                 // families that shared this run's SPD-inverse launch (1: a launch of its own)
-    bool inv_stamped;          // the inverse was a merged launch bracketed by stamps (slots 6 / 16 before, 17 / 4 behind) instead of events
-    hipEvent_t upd_ev[2];      // the two events around that launch (this context's own, also for a merged launch)
     double upd_flops;
     // ---- the score stage (run_score) ----
     score_target target;
-    bool fn_timed;             // events 7 / 8 around k_fn were recorded by this run
     bool sc_published;         // the run ends with k_publish_scalars: its collect reads sc_host after a stream synchronisation
     // ---- progress at collect time (zero when a run begins) ----
     struct progress {
@@ -165,10 +162,8 @@ struct gdca_ctx {
     gdca_buf scratch[N_SCRATCH];
     gdca_dev_scalars *sc_host;  // pinned
     gdca_dev_scalars *sc_host_dev;  // ... as the device addresses it (k_publish_scalars)
-    hipEvent_t ev[MAX_EV];
-    int n_ev;
+    hipEvent_t ev[T_COUNT];    // the stage boundaries of a timed run (made when the first one opens its timeline)
     hipEvent_t ev_batch, ev_upload;
-    bool stamped;              // the run being enqueued marks its stages with device time stamps (sc->stamp) instead of HIP events: a member of a batch issued as batched grids
     bool pending;              // a run is enqueued and not yet collected ...
     gdca_pending pend;         // ... this one
 };
@@ -267,7 +262,7 @@ void gdca_fill_async(hipStream_t s, void *p, int byte_value, size_t bytes)
 
 struct k_stamp_args {
     gdca_dev_scalars *sc;
-    int slot, slot2;
+    int slot, slot2;  // gdca_boundary (slot2: T_NONE for one slot)
 };
 template <int CAP>
 __global__ __launch_bounds__(64) void k_stamp(const BatchArgs<k_stamp_args, CAP> B_)
@@ -595,7 +590,8 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
         }
         free(ctx->gate);
     }
-    for (int i = 0; i < ctx->n_ev; ++i) (void)hipEventDestroy(ctx->ev[i]);
+    for (hipEvent_t e : ctx->ev)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->item0_host) (void)hipHostFree(ctx->item0_host);
     if (ctx->ev_batch) (void)hipEventDestroy(ctx->ev_batch);
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
@@ -635,33 +631,90 @@ gdca_status gdca_ctx_set_option(gdca_ctx *ctx, const char *key, const char *valu
 
 }  // extern "C"
 
-static gdca_status need_events(gdca_ctx *ctx, int n)
+// ---- the timeline of a run: every gdca_stats.ms_* is the time between two named boundaries (gdca_boundary) ----------------------------
+// A timed run marks its boundaries with ONE clock, fixed when it is enqueued: HIP events of its context, or -- a member of a batch
+// whose kernels go out as batched grids -- device time stamps written by kernels of the batch (one launch stamps all members).  Only
+// an inverse launch of its own is bracketed by events inside a stamped run too.  An untimed run, and the operator-level entries
+// (begin() closes the timeline), mark nothing.
+static gdca_status open_timeline(gdca_ctx *ctx, bool timed, bool stamped)
 {
-    if (n > MAX_EV) n = MAX_EV;
-    while (ctx->n_ev < n) {
-        HIPCHK(hipEventCreate(&ctx->ev[ctx->n_ev]));
-        ++ctx->n_ev;
+    gdca_pending &r = ctx->pend;
+    r.timed = timed;
+    r.stamped = stamped;
+    r.ev_marks = r.stamp_marks = 0;
+    for (int t = 0; timed && t < T_COUNT; ++t)
+        if (!ctx->ev[t]) HIPCHK(hipEventCreate(&ctx->ev[t]));
+    return GDCA_OK;
+}
+
+static void note_mark(gdca_pending &r, gdca_boundary t, bool stamp)
+{
+    (stamp ? r.stamp_marks : r.ev_marks) |= 1u << t;
+    (stamp ? r.ev_marks : r.stamp_marks) &= ~(1u << t);
+}
+
+// boundary t of the context's run, here on its stream.  own_launch: by an event whatever the run's clock
+static gdca_status mark(gdca_ctx *ctx, gdca_boundary t, bool own_launch = false)
+{
+    gdca_pending &r = ctx->pend;
+    if (!r.timed) return GDCA_OK;
+    const bool stamp = r.stamped && !own_launch;
+    if (stamp)
+        gdca_launch_stamp(ctx->stream, (gdca_dev_scalars *)ctx->sc.p, t, T_NONE);
+    else
+        HIPCHK(hipEventRecord(ctx->ev[t], ctx->stream));
+    note_mark(r, t, stamp);
+    return GDCA_OK;
+}
+
+// boundaries a and b, one instant on stream s, of all K members of a merged launch (all timed): two events of ITS OWN for every
+// member -- members may be collected, enqueued again or destroyed in any order, and a collect must never read another context's events
+//  -- or, stamps: one launch of the batched k_stamp for all of them (2 launches around a merged sweep instead of 4 K records)
+static gdca_status mark_members(hipStream_t s, gdca_ctx *const *mem, int K, gdca_boundary a, gdca_boundary b, bool stamps)
+{
+    gdca_ctx *ctx = mem[0];
+    if (stamps) {
+        gdca_recorder *&act = gdca_recorder::active();
+        gdca_recorder *outer = act;
+        if (outer) (void)outer->flush();
+        gdca_recorder rec;
+        rec.begin(s, K);
+        for (int k = 0; k < K; ++k) {
+            rec.member(k);
+            gdca_launch_stamp(s, (gdca_dev_scalars *)mem[k]->sc.p, a, b);
+        }
+        (void)rec.end();
+        act = outer;
+    } else
+        for (int k = 0; k < K; ++k) {
+            HIPCHK(hipEventRecord(mem[k]->ev[a], s));
+            HIPCHK(hipEventRecord(mem[k]->ev[b], s));
+        }
+    for (int k = 0; k < K; ++k) {
+        note_mark(mem[k]->pend, a, stamps);
+        note_mark(mem[k]->pend, b, stamps);
     }
     return GDCA_OK;
 }
 
-// A stage boundary of the run being enqueued: a HIP event of the context -- or, for a member of a batch whose kernels go out as
-// batched grids, a device time stamp written by a kernel of the batch (slot = the event's index: one launch stamps all members)
-static gdca_status mark(gdca_ctx *ctx, int slot)
+// the two events the sweep launchers record themselves, behind k_sweep_prep (null: an untimed run)
+static void sweep_events(gdca_ctx *ctx, hipEvent_t *begin, hipEvent_t *end)
 {
-    if (ctx->stamped) {
-        gdca_launch_stamp(ctx->stream, (gdca_dev_scalars *)ctx->sc.p, slot, -1);
-        return GDCA_OK;
-    }
-    HIPCHK(hipEventRecord(ctx->ev[slot], ctx->stream));
-    return GDCA_OK;
+    const bool timed = ctx->pend.timed;
+    *begin = timed ? ctx->ev[T_SWEEP_BEGIN] : nullptr;
+    *end = timed ? ctx->ev[T_SWEEP_END] : nullptr;
+    note_mark(ctx->pend, T_SWEEP_BEGIN, false);
+    note_mark(ctx->pend, T_SWEEP_END, false);
 }
 
-// device time between two stage boundaries of the enqueued run: HIP events of this context, or -- a run whose kernels went out as
-// batched grids -- the 100 MHz time stamps kernels of the batch wrote into its scalars (slot = the event's index)
-static double between(const gdca_ctx *ctx, int a, int b, bool *failed)
+// milliseconds of device time from boundary a to boundary b of the collected run: both marked by the same clock, 0 otherwise
+static double elapsed(const gdca_ctx *ctx, gdca_boundary a, gdca_boundary b, bool *failed)
 {
-    if (ctx->pend.stamped) return (double)(long long)(ctx->sc_host->stamp[b] - ctx->sc_host->stamp[a]) * 1e-5;
+    const gdca_pending &r = ctx->pend;
+    const unsigned both = 1u << a | 1u << b;
+    if (!r.timed) return 0.0;
+    if ((r.stamp_marks & both) == both) return (double)(long long)(ctx->sc_host->stamp[b] - ctx->sc_host->stamp[a]) * 1e-5;
+    if ((r.ev_marks & both) != both) return 0.0;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ctx->ev[a], ctx->ev[b]) != hipSuccess) *failed = true;
     return ms;
@@ -716,7 +769,7 @@ static int round_up(int x, int m)
 
 // stage 1+2: theta, threshold, neighbour counts, W, Wfix, Meff  (all on device)
 static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, int q, double theta_in, int fixed_thresh,
-                                 bool want_theta_only, int mark_after_theta)
+                                 bool want_theta_only)
 {
     hipStream_t s = ctx->stream;
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
@@ -728,7 +781,7 @@ static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, 
         gdca_launch_theta_finalize(s, (const uint32_t *)ctx->hist.p, N, M, theta_in, sc);
     }
     CHK(check_launch(ctx, "theta"));
-    if (mark_after_theta >= 0) CHK(mark(ctx, mark_after_theta));
+    CHK(mark(ctx, T_THETA));
     if (want_theta_only) return GDCA_OK;
 
     const int Mt = (M + GDCA_HTILE - 1) / GDCA_HTILE;
@@ -797,13 +850,12 @@ static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, in
                         sigma, N, M, q, (gdca_dev_scalars *)ctx->sc.p);
     gdca_launch_pi_finalize(s, (const unsigned long long *)ctx->Pifix.p, N, q, shift, Meff_dev, pc, Pi_true_out,
                             (double *)ctx->Pipc.p, want_norm1 ? &((gdca_dev_scalars *)ctx->sc.p)->pi_max : nullptr);
-    const bool tm = want_norm1 && ctx->timing && ctx->n_ev >= 18;  // (the fused path's first build: its own device time, gdca_stats.ms_pair_tally)
-    if (tm) CHK(mark(ctx, 9));
+    if (want_norm1) CHK(mark(ctx, T_TALLY_BEGIN));  // (the fused path's first build: its own device time, gdca_stats.ms_pair_tally)
     gdca_launch_pair_tally(s, (const int8_t *)ctx->Zp.p, (const int8_t *)ctx->Zt.p,
                            (const unsigned long long *)ctx->Wfix.p, N, M, q, shift, Meff_dev, pc,
                            (const double *)ctx->Pipc.p, mode, out, ld, TJ, keep, keep_n, sigma,
                            (const unsigned long long *)ctx->Pifix.p);
-    if (tm) CHK(mark(ctx, 10));
+    if (want_norm1) CHK(mark(ctx, T_TALLY_END));
     // ||C||_1 for the refinement screen, where the bound that costs nothing (2 N pi_max) does not settle it (k_cov_norm1)
     // (not even launched where the answer is known on the host: pi_max <= (1 - pc) + pc / q whatever the alignment)
     if (want_norm1 && !norm1_settled(ctx, N, q, pc))
@@ -867,29 +919,23 @@ static gdca_status poison_inverse_ws(gdca_ctx *ctx, hipStream_t s)
     return GDCA_OK;
 }
 
-static gdca_status inverse_stage(gdca_ctx *ctx, int n, int n_pad, bool timed, int *n_upd, double *upd_flops)
+static gdca_status inverse_stage(gdca_ctx *ctx, int n, int n_pad, double *upd_flops)
 {
     gdca_inverse_job job;
     CHK(inverse_job(ctx, n, n_pad, &job));
-    hipEvent_t *uev = nullptr;
-    int max_ev = 0;
-    if (timed) {
-        CHK(need_events(ctx, 18));
-        uev = ctx->ev + 16;
-        max_ev = 2;
-    }
+    hipEvent_t sweep_begin, sweep_end;
+    sweep_events(ctx, &sweep_begin, &sweep_end);
     // tests (option SWEEP_DEBUG): bit 4 = the panel / scratch buffers are poisoned with NaNs first (an item that reads a buffer
     // before its producer wrote it can then not pass on the leftovers of an earlier, identical run); bit 3 = the merged kernel
     // carries this single inverse
     if (ctx->tune.sweep_debug & 16) CHK(poison_inverse_ws(ctx, ctx->stream));
     if (ctx->tune.sweep_debug & 8) {
         double fl = 0.0;
-        gdca_launch_spd_inverse_merged(ctx->stream, &job, 1, uev, max_ev, &fl);
-        if (n_upd) *n_upd = 1;
+        gdca_launch_spd_inverse_merged(ctx->stream, &job, 1, sweep_begin, sweep_end, &fl);
         if (upd_flops) *upd_flops = fl;
         return check_launch(ctx, "spd_inverse_merged");
     }
-    gdca_launch_spd_inverse(ctx->stream, job, uev, max_ev, n_upd, upd_flops);
+    gdca_launch_spd_inverse(ctx->stream, job, sweep_begin, sweep_end, upd_flops);
     return check_launch(ctx, "spd_inverse");
 }
 
@@ -963,7 +1009,7 @@ static gdca_status mutation_stage(gdca_ctx *ctx, const gdca_model &m, const int8
 }
 
 // -mJ in ctx->A (ld = n_pad) -> what `t` asks for
-static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t, bool time_fn = false)
+static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t)
 {
     hipStream_t s = ctx->stream;
     // the model as the sweep left it, for the fused read-outs: scored on t's sequences in the place of the contact score
@@ -980,11 +1026,9 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
         gdca_launch_di(s, (const double *)ctx->A.p, (size_t)n_pad, (const double *)ctx->Ld.p, N, sdim, S_dev,
                        (double *)ctx->Tws.p, (gdca_dev_scalars *)ctx->sc.p);
     } else {
-        const bool tm = time_fn && ctx->n_ev >= 18;  // (a timed fused run: gdca_stats.ms_fn)
-        if (tm) CHK(mark(ctx, 7));
+        CHK(mark(ctx, T_FN_BEGIN));  // (gdca_stats.ms_fn)
         gdca_launch_fn(s, (const double *)ctx->A.p, (size_t)n_pad, N, sdim, S_dev, ctx->ncu);
-        if (tm) CHK(mark(ctx, 8));
-        if (time_fn) ctx->pend.fn_timed = tm;
+        CHK(mark(ctx, T_FN_END));
     }
     if (t.apc) {
         CHK(ensure(ctx, ctx->colsum, (size_t)N * sizeof(double)));
@@ -1111,13 +1155,26 @@ static gdca_status rebuild_padded(gdca_ctx *ctx, void *dst)
     return GDCA_OK;
 }
 
-// ... and ends with: the enqueued run's score stage again on the inverse now in ctx->A, the scalars fetched.  mark_end: a second
-// attempt of a timed run records the run's last event again
-static gdca_status rescore(gdca_ctx *ctx, bool mark_end = false)
+// the score stage of the run (pend.target) between its two boundaries; k_fn's are this stage's own
+static gdca_status marked_score_stage(gdca_ctx *ctx)
+{
+    gdca_pending &r = ctx->pend;
+    const unsigned fn = 1u << T_FN_BEGIN | 1u << T_FN_END;
+    r.ev_marks &= ~fn;
+    r.stamp_marks &= ~fn;
+    CHK(mark(ctx, T_SCORE_BEGIN));
+    CHK(score_stage(ctx, r.N, r.q - 1, r.n_pad, r.target));
+    return mark(ctx, T_END);
+}
+
+// ... and ends with: the enqueued run's score stage again on the inverse now in ctx->A, the scalars fetched.  again: the stage of a
+// second attempt (or of a further member of a gdca_run_multi group) -- it runs alone and is marked in the run's clock like the first,
+// so that ms_score is its time and ms_total ends with it; a refinement or fallback marks k_fn's two again and nothing else (its ms_fn is 0)
+static gdca_status rescore(gdca_ctx *ctx, bool again = false)
 {
     HIPCHK(hipMemsetAsync(&((gdca_dev_scalars *)ctx->sc.p)->di_noconv, 0, sizeof(int), ctx->stream));
-    CHK(score_stage(ctx, ctx->pend.N, ctx->pend.q - 1, ctx->pend.n_pad, ctx->pend.target));
-    if (mark_end && ctx->pend.timed && !ctx->pend.stamped) CHK(mark(ctx, 5));
+    if (again) ctx->pend.score_batch = 1;
+    CHK(again ? marked_score_stage(ctx) : score_stage(ctx, ctx->pend.N, ctx->pend.q - 1, ctx->pend.n_pad, ctx->pend.target));
     return fetch_scalars(ctx);
 }
 
@@ -1128,6 +1185,7 @@ static gdca_status begin(gdca_ctx *ctx)
     CHK(ensure(ctx, ctx->sc, sizeof(gdca_dev_scalars)));
     gdca_fill_async(ctx->stream, ctx->sc.p, 0, sizeof(gdca_dev_scalars));
     ctx->pend.at = gdca_pending::progress{};
+    ctx->pend.timed = false;  // (a fused run opens its timeline next, open_timeline)
     return GDCA_OK;
 }
 
@@ -1214,7 +1272,19 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
 
 }  // extern "C"
 
-// gdca_stats of the run just collected: the scalars in sc_host, the pending record and, for a timed run, its stage times
+// the times that end with the score stage just run: of the collected run, or of a further member of a gdca_run_multi group
+static gdca_status score_times(gdca_ctx *ctx, gdca_stats *st)
+{
+    bool tfail = false;
+    const double sbatch = (double)(ctx->pend.score_batch > 0 ? ctx->pend.score_batch : 1);
+    st->ms_total = elapsed(ctx, T_BEGIN, T_END, &tfail);
+    st->ms_score = elapsed(ctx, T_SCORE_BEGIN, T_END, &tfail) / sbatch;
+    st->ms_fn = ctx->pend.at.refined == 0 ? elapsed(ctx, T_FN_BEGIN, T_FN_END, &tfail) / sbatch : 0.0;
+    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
+    return GDCA_OK;
+}
+
+// gdca_stats of the run just collected: the scalars in sc_host, the pending record and its stage times (all 0 for an untimed run)
 static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st)
 {
     const gdca_dev_scalars &h = *ctx->sc_host;
@@ -1239,33 +1309,20 @@ static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st)
     st->inverse_flops = inverse_flops_model((double)ctx->pend.n);
     st->update_flops = ctx->pend.upd_flops;
     st->sweep_ghz = h.sweep_ticks ? (double)h.sweep_cycles / (double)h.sweep_ticks * 0.1 : 0.0;
-    if (!ctx->pend.timed) return GDCA_OK;
     bool tfail = false;
-    // (stages issued as batched grids carry the whole batch: a member reports its share, as for a merged inverse)
+    // (stages issued as batched grids carry the whole batch: a member reports its share, as for a merged inverse -- a family whose
+    // inverse shared a merged launch with others reports the launch's time divided by the families it carried: the sum over the
+    // members is the launch)
     const double fshare = 1.0 / (double)(ctx->pend.front_batch > 0 ? ctx->pend.front_batch : 1);
-    const double sbatch = (double)(ctx->pend.score_batch > 0 ? ctx->pend.score_batch : 1);
-    st->ms_total = between(ctx, 0, 5, &tfail);
-    st->ms_theta = between(ctx, 0, 1, &tfail) * fshare;
-    st->ms_weights = between(ctx, 1, 2, &tfail) * fshare;
-    st->ms_covariance = between(ctx, 2, 3, &tfail) * fshare;
-    // (a family whose inverse shared a merged launch with others reports its share of that launch: the launch's time
-    // divided by the families it carried -- the sum over the members is the launch)
     const double share = 1.0 / (double)(ctx->pend.batch > 0 ? ctx->pend.batch : 1);
-    st->ms_score = between(ctx, 11, 5, &tfail) / sbatch;
-    if (ctx->pend.inv_stamped) {
-        st->ms_inverse = (double)(long long)(h.stamp[4] - h.stamp[6]) * 1e-5 * share;
-        st->ms_inverse_update = (double)(long long)(h.stamp[17] - h.stamp[16]) * 1e-5 * share;
-    } else {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[4]));  // from the start of its turn (after any pipeline gate)
-        st->ms_inverse = ms * share;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->pend.upd_ev[0], ctx->pend.upd_ev[1]));
-        st->ms_inverse_update = ms * share;
-    }
-    if (ctx->pend.fn_timed && ctx->pend.at.refined == 0) st->ms_fn = between(ctx, 7, 8, &tfail) / sbatch;
-    if (ctx->pend.tally_timed && ctx->pend.at.refined == 0) st->ms_pair_tally = between(ctx, 9, 10, &tfail) * fshare;
+    st->ms_theta = elapsed(ctx, T_BEGIN, T_THETA, &tfail) * fshare;
+    st->ms_weights = elapsed(ctx, T_THETA, T_WEIGHTS, &tfail) * fshare;
+    st->ms_covariance = elapsed(ctx, T_WEIGHTS, T_COV, &tfail) * fshare;
+    if (ctx->pend.at.refined == 0) st->ms_pair_tally = elapsed(ctx, T_TALLY_BEGIN, T_TALLY_END, &tfail) * fshare;
+    st->ms_inverse = elapsed(ctx, T_INV_BEGIN, T_INV_END, &tfail) * share;
+    st->ms_inverse_update = elapsed(ctx, T_SWEEP_BEGIN, T_SWEEP_END, &tfail) * share;
     if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
-    return GDCA_OK;
+    return score_times(ctx, st);
 }
 
 // The three phases of one run, enqueued on `s` (the ctx's own stream, or the leader's when several families are batched by
@@ -1289,9 +1346,8 @@ static gdca_status run_check_args(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N,
     return GDCA_OK;
 }
 
-// the front-end part of the pending record.  pij: the stored Pij_true of gdca_run_multi (whose tallies are not the fused build:
-// no time of their own), nullptr for a single run
-static void pending_front(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int q, const gdca_params *p, const double *pij, bool timed)
+// the front-end part of the pending record.  pij: the stored Pij_true of gdca_run_multi, nullptr for a single run
+static void pending_front(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int q, const gdca_params *p, const double *pij)
 {
     gdca_pending &r = ctx->pend;
     r.N = N;
@@ -1302,78 +1358,61 @@ static void pending_front(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int 
     r.Z = Z_dev;
     r.pij = pij;
     r.p = *p;
-    r.timed = timed;
-    r.stamped = ctx->stamped;
     r.front_batch = r.score_batch = 1;  // (run_phased knows better)
-    r.tally_timed = timed && !pij && ctx->tune.refine != 0;
-    r.fn_timed = false;
 }
 
-static gdca_status run_front(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p)
+// how every fused run opens: its timeline (stamped: a member of a batch issued as batched grids), theta and the reweighting
+static gdca_status front_weights(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int q, double theta, bool stamped)
 {
     CHK(begin(ctx));  // (one run may be outstanding per ctx: its scalars and events would be overwritten -> GDCA_EINVAL)
+    CHK(open_timeline(ctx, ctx->timing, stamped));
+    CHK(mark(ctx, T_BEGIN));
+    CHK(weights_stage(ctx, Z_dev, N, M, q, theta, -1, false));
+    return mark(ctx, T_WEIGHTS);
+}
+
+// ... and how the covariance in ctx->A (ld = n_pad) becomes the inverse's input: its identity padding, and for the DI score its
+// diagonal blocks saved and factored
+static gdca_status covariance_tail(gdca_ctx *ctx, int N, int sdim, int n_pad, bool di)
+{
     hipStream_t s = ctx->stream;
-    const int sdim = q - 1, n = N * sdim, n_pad = round_up(n, GDCA_TILE);
-    const bool timed = ctx->timing;
-    if (timed) CHK(need_events(ctx, 18));
-    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-
-    if (timed) CHK(mark(ctx, 0));
-    CHK(weights_stage(ctx, Z_dev, N, M, q, p->theta, -1, false, timed ? 1 : -1));
-    if (timed) CHK(mark(ctx, 2));
-
-    CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
-    CHK(tally_stage(ctx, Z_dev, N, M, q, &sc->Meff, p->pseudocount, 1, nullptr, (double *)ctx->A.p, (size_t)n_pad, ctx->tune.refine != 0));
-    gdca_launch_pad_identity(s, (double *)ctx->A.p, n, n_pad);
-    if (p->score == GDCA_SCORE_DI) {
+    gdca_launch_pad_identity(s, (double *)ctx->A.p, N * sdim, n_pad);
+    if (di) {
         CHK(ensure(ctx, ctx->Dblk, (size_t)N * sdim * sdim * sizeof(double)));
         CHK(ensure(ctx, ctx->Ld, (size_t)N * sdim * sdim * sizeof(double)));
         gdca_launch_save_diag_blocks(s, (const double *)ctx->A.p, (size_t)n_pad, N, sdim, (double *)ctx->Dblk.p);
         gdca_launch_diag_chol(s, (const double *)ctx->Dblk.p, N, sdim, (double *)ctx->Ld.p);
     }
     CHK(check_launch(ctx, "covariance"));
-    if (timed) CHK(mark(ctx, 3));
-    pending_front(ctx, Z_dev, N, M, q, p, nullptr, timed);
+    return mark(ctx, T_COV);
+}
+
+static gdca_status run_front(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, bool stamped = false)
+{
+    CHK(front_weights(ctx, Z_dev, N, M, q, p->theta, stamped));
+    const int sdim = q - 1, n_pad = round_up(N * sdim, GDCA_TILE);
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
+    CHK(tally_stage(ctx, Z_dev, N, M, q, &sc->Meff, p->pseudocount, 1, nullptr, (double *)ctx->A.p, (size_t)n_pad, ctx->tune.refine != 0));
+    CHK(covariance_tail(ctx, N, sdim, n_pad, p->score == GDCA_SCORE_DI));
+    pending_front(ctx, Z_dev, N, M, q, p, nullptr);
     return GDCA_OK;
 }
 
+// the inverse of the context's run as a launch of its own: bracketed by events, inside a stamped run too
 static gdca_status run_inverse(gdca_ctx *ctx)
 {
     hipStream_t s = ctx->stream;
-    const bool timed = ctx->pend.timed;
-    hipEvent_t *ev = ctx->ev;
-    int n_upd = 0;
     double upd_flops = 0.0;
     if (ctx->gate) HIPCHK(gate_wait(ctx->gate, s));
-    if (timed) HIPCHK(hipEventRecord(ev[6], s));  // start of this family's turn on the MFMA pipe
-    CHK(inverse_stage(ctx, ctx->pend.n, ctx->pend.n_pad, timed, &n_upd, &upd_flops));
-    if (timed) HIPCHK(hipEventRecord(ev[4], s));
+    CHK(mark(ctx, T_INV_BEGIN, true));  // start of this family's turn on the MFMA pipe
+    CHK(inverse_stage(ctx, ctx->pend.n, ctx->pend.n_pad, &upd_flops));
+    CHK(mark(ctx, T_INV_END, true));
     if (ctx->gate) HIPCHK(gate_pass(ctx->gate, s));
-    ctx->pend.n_upd = n_upd;
+    ctx->pend.n_upd = 1;
     ctx->pend.upd_flops = upd_flops;
     ctx->pend.batch = 1;
-    ctx->pend.inv_stamped = false;
-    if (timed) {
-        ctx->pend.upd_ev[0] = ev[16];
-        ctx->pend.upd_ev[1] = ev[17];
-    }
     return GDCA_OK;
-}
-
-// one launch that stamps slot a (and b, if >= 0) of every given context's scalars (the batched k_stamp)
-static void stamp_members(hipStream_t s, gdca_ctx *const *mem, int K, int a, int b)
-{
-    gdca_recorder *&act = gdca_recorder::active();
-    gdca_recorder *outer = act;
-    if (outer) (void)outer->flush();
-    gdca_recorder rec;
-    rec.begin(s, K);
-    for (int k = 0; k < K; ++k) {
-        rec.member(k);
-        gdca_launch_stamp(s, (gdca_dev_scalars *)mem[k]->sc.p, a, b);
-    }
-    (void)rec.end();
-    act = outer;
 }
 
 // The inverses of K members of a phase batch as ONE merged launch on the batch's stream (k_sweep_merged: small matrices, which
@@ -1386,13 +1425,13 @@ static gdca_status run_inverse_merged(gdca_ctx *lead, gdca_ctx *const *mem, int 
     gdca_tuning tun[8];  // a member's schedule switches are its own context's, the switches of the merged launch the leader's
     double flops[8];
     if (K > gdca_inverse_max_merge() || K > 8) return fail(ctx, GDCA_EINVAL, "too many members in a merged inverse%s%s", "", "");
-    bool timed = true, stamped = true;
+    bool timed = true, stamps = true;
     // (the members of a batch are normally peers of ONE pipeline: one wait and one record per distinct gate, not per member)
     gdca_gate *gates[8];
     int n_gates = 0;
     for (int k = 0; k < K; ++k) {
         timed = timed && mem[k]->pend.timed;
-        stamped = stamped && mem[k]->pend.stamped;
+        stamps = stamps && mem[k]->pend.stamped;
         gdca_gate *g = mem[k]->gate;
         bool seen = !g;
         for (int j = 0; j < n_gates && !seen; ++j) seen = gates[j] == g;
@@ -1401,9 +1440,8 @@ static gdca_status run_inverse_merged(gdca_ctx *lead, gdca_ctx *const *mem, int 
             HIPCHK(gate_wait(g, s));
         }
     }
-    stamped = stamped && timed;
     for (int k = 0; k < K; ++k) {
-        if (mem[k]->pend.timed && !stamped) HIPCHK(hipEventRecord(mem[k]->ev[6], s));
+        mem[k]->pend.timed = timed;  // (the launch is timed for all its members or for none)
         CHK(inverse_job(mem[k], mem[k]->pend.n, mem[k]->pend.n_pad, &jobs[k]));
         tun[k] = mem[k]->tune;
         tun[k].merge_group = lead->tune.merge_group;
@@ -1411,36 +1449,15 @@ static gdca_status run_inverse_merged(gdca_ctx *lead, gdca_ctx *const *mem, int 
         jobs[k].tune = &tun[k];
         if (lead->tune.sweep_debug & 16) CHK(poison_inverse_ws(mem[k], s));
     }
-    // every timed member brackets the launch with events of ITS OWN: members may be collected, enqueued again or destroyed in any
-    // order, and a collect must never read another context's events -- or, members of a batch issued as batched grids,
-    // with two launches that stamp every member's scalars (2 launches instead of 4 K event records)
-    if (stamped)
-        stamp_members(s, mem, K, 6, 16);
-    else if (timed)
-        for (int k = 0; k < K; ++k) {
-            CHK(need_events(mem[k], 18));
-            HIPCHK(hipEventRecord(mem[k]->ev[16], s));
-        }
-    gdca_launch_spd_inverse_merged(s, jobs, K, nullptr, 0, flops);
+    if (timed) CHK(mark_members(s, mem, K, T_INV_BEGIN, T_SWEEP_BEGIN, stamps));
+    gdca_launch_spd_inverse_merged(s, jobs, K, nullptr, nullptr, flops);
     CHK(check_launch(ctx, "spd_inverse_merged"));
-    if (stamped)
-        stamp_members(s, mem, K, 17, 4);
-    else if (timed)
-        for (int k = 0; k < K; ++k) HIPCHK(hipEventRecord(mem[k]->ev[17], s));
+    if (timed) CHK(mark_members(s, mem, K, T_SWEEP_END, T_INV_END, stamps));
     for (int j = 0; j < n_gates; ++j) HIPCHK(gate_pass(gates[j], s));
     for (int k = 0; k < K; ++k) {
-        gdca_ctx *m = mem[k];
-        if (m->pend.timed && !stamped) HIPCHK(hipEventRecord(m->ev[4], s));
-        m->pend.n_upd = k == 0 ? 1 : 0;
-        m->pend.upd_flops = flops[k];
-        m->pend.batch = K;
-        // (a member without timing of its own still gets valid events to read: the launch's, or none -- collect reads them only if timed)
-        m->pend.timed = m->pend.timed && timed;
-        m->pend.inv_stamped = stamped;
-        if (timed && !stamped) {
-            m->pend.upd_ev[0] = m->ev[16];
-            m->pend.upd_ev[1] = m->ev[17];
-        }
+        mem[k]->pend.n_upd = k == 0 ? 1 : 0;
+        mem[k]->pend.upd_flops = flops[k];
+        mem[k]->pend.batch = K;
     }
     return GDCA_OK;
 }
@@ -1449,9 +1466,7 @@ static gdca_status run_score(gdca_ctx *ctx, const score_target &t)
 {
     ctx->pend.target = t;
     // (the start of THIS run's score stage: in a phase batch the members' stages follow one another behind the shared inverse)
-    if (ctx->pend.timed) CHK(mark(ctx, 11));
-    CHK(score_stage(ctx, ctx->pend.N, ctx->pend.q - 1, ctx->pend.n_pad, t, ctx->pend.timed));
-    if (ctx->pend.timed) CHK(mark(ctx, 5));
+    CHK(marked_score_stage(ctx));
     ctx->pend.sc_published = false;
     if (ctx->sc_host_dev) {
         gdca_launch_publish_scalars(ctx->stream, (const gdca_dev_scalars *)ctx->sc.p, ctx->sc_host_dev);
@@ -1588,9 +1603,8 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
             rec.begin(sg, K);
             for (int k = gi; k < K && st == GDCA_OK; k += G) {
                 ctxs[k]->stream = sg;
-                ctxs[k]->stamped = true;
                 rec.member(k);
-                st = run_front(ctxs[k], Z_dev[k], N[k], M[k], q[k], p);
+                st = run_front(ctxs[k], Z_dev[k], N[k], M[k], q[k], p, true);
                 if (st == GDCA_OK) {
                     ++done_front;
                     ++in_group[gi];
@@ -1625,10 +1639,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         // the members' collects synchronise THEIR stream: every one of them waits for the batch (one event on the batch's stream)
         bool chained = st == GDCA_OK && hipEventRecord(lead->ev_batch, bs) == hipSuccess;
         for (int k = bs == own[0] ? 1 : 0; k < K && chained; ++k) chained = hipStreamWaitEvent(own[k], lead->ev_batch, 0) == hipSuccess;
-        for (int k = 0; k < K; ++k) {
-            ctxs[k]->stream = own[k];
-            ctxs[k]->stamped = false;
-        }
+        for (int k = 0; k < K; ++k) ctxs[k]->stream = own[k];
         if (st != GDCA_OK) {
             (void)hipStreamSynchronize(bs);
             for (int k = 0; k < K; ++k) {
@@ -1912,19 +1923,14 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
         done[k] = false;
     }
     // ---- the front end, once: theta, reweighting, Pi, Pij_true (ld = n) ----
-    CHK(begin(ctx));
-    const bool timed = ctx->timing;
-    if (timed) CHK(need_events(ctx, 18));
+    CHK(front_weights(ctx, Z_dev, N, M, q, p[0].theta, false));
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    if (timed) CHK(mark(ctx, 0));
-    CHK(weights_stage(ctx, Z_dev, N, M, q, p[0].theta, -1, false, timed ? 1 : -1));
-    if (timed) CHK(mark(ctx, 2));
     CHK(ensure(ctx, ctx->Pij, (size_t)n * n * sizeof(double)));
     CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
     CHK(ensure(ctx, ctx->sc_front, sizeof(gdca_dev_scalars)));
     CHK(tally_stage(ctx, Z_dev, N, M, q, &sc->Meff, p[0].pseudocount, 0, nullptr, (double *)ctx->Pij.p, (size_t)n));
     HIPCHK(hipMemcpyAsync(ctx->sc_front.p, sc, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
-    pending_front(ctx, Z_dev, N, M, q, &p[0], (const double *)ctx->Pij.p, timed);
+    pending_front(ctx, Z_dev, N, M, q, &p[0], (const double *)ctx->Pij.p);
     double ms_theta = 0.0, ms_weights = 0.0;
     bool first = true;
     for (int k0 = 0; k0 < K; ++k0) {
@@ -1937,20 +1943,11 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
             // (every group starts from the scalars the front end left: theta, Meff, ...; its own -- pi_max, norms, info -- zero)
             HIPCHK(hipMemcpyAsync(sc, ctx->sc_front.p, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
             ctx->pend.at = gdca_pending::progress{};
-            if (timed) CHK(mark(ctx, 2));
+            CHK(mark(ctx, T_WEIGHTS));
         }
         ctx->pend.p = p[k0];
-        ctx->pend.fn_timed = false;
         CHK(cov_from_pij_stage(ctx, N, M, q, pc, (double *)ctx->A.p, (size_t)n_pad, ctx->tune.refine != 0));
-        gdca_launch_pad_identity(s, (double *)ctx->A.p, n, n_pad);
-        if (di) {
-            CHK(ensure(ctx, ctx->Dblk, (size_t)N * sdim * sdim * sizeof(double)));
-            CHK(ensure(ctx, ctx->Ld, (size_t)N * sdim * sdim * sizeof(double)));
-            gdca_launch_save_diag_blocks(s, (const double *)ctx->A.p, (size_t)n_pad, N, sdim, (double *)ctx->Dblk.p);
-            gdca_launch_diag_chol(s, (const double *)ctx->Dblk.p, N, sdim, (double *)ctx->Ld.p);
-        }
-        CHK(check_launch(ctx, "covariance"));
-        if (timed) CHK(mark(ctx, 3));
+        CHK(covariance_tail(ctx, N, sdim, n_pad, di));
         CHK(run_inverse(ctx));
         double *S0 = S_dev + (size_t)k0 * S_stride;
         CHK(run_score(ctx, contact_target(p[k0].score, p[k0].apc, S0)));
@@ -1981,19 +1978,9 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
                 continue;
             }
             double *Sk = S_dev + (size_t)k * S_stride;
-            ctx->pend.fn_timed = false;
-            HIPCHK(hipMemsetAsync(&sc->di_noconv, 0, sizeof(int), s));
-            if (timed) CHK(mark(ctx, 11));
-            CHK(score_stage(ctx, N, sdim, n_pad, contact_target(p[k].score, p[k].apc, Sk), timed));
-            if (timed) CHK(mark(ctx, 5));
-            CHK(fetch_scalars(ctx));
-            if (timed) {
-                bool tfail = false;
-                st[k].ms_score = between(ctx, 11, 5, &tfail);
-                st[k].ms_total = between(ctx, 0, 5, &tfail);
-                if (ctx->pend.fn_timed && ctx->pend.at.refined == 0) st[k].ms_fn = between(ctx, 7, 8, &tfail);
-                if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
-            }
+            ctx->pend.target = contact_target(p[k].score, p[k].apc, Sk);
+            CHK(rescore(ctx, true));
+            CHK(score_times(ctx, &st[k]));
             if (ctx->sc_host->di_noconv != 0) {
                 st[k].info = -ctx->sc_host->di_noconv;
                 mst[k] = fail(ctx, GDCA_ENOCONV, "eigenvalue iteration of a DI block did not converge%s%s", "", "");
@@ -2140,7 +2127,7 @@ gdca_status gdca_pair_identity_sum_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
     CHK(validate(ctx, N, M, 2));
     if (!Z_dev || !out) return GDCA_EINVAL;
     CHK(begin(ctx));
-    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, -1.0, -1, true, -1));
+    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, -1.0, -1, true));
     CHK(fetch_scalars(ctx));
     *out = ctx->sc_host->pair_sum;
     return GDCA_OK;
@@ -2151,7 +2138,7 @@ gdca_status gdca_compute_theta_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N
     CHK(validate(ctx, N, M, 2));
     if (!Z_dev || !theta) return GDCA_EINVAL;
     CHK(begin(ctx));
-    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, -1.0, -1, true, -1));
+    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, -1.0, -1, true));
     CHK(fetch_scalars(ctx));
     *theta = ctx->sc_host->theta;
     return GDCA_OK;
@@ -2163,7 +2150,7 @@ gdca_status gdca_neighbour_counts_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_
     CHK(validate(ctx, N, M, 2));
     if (!Z_dev || !n_dev || thresh < 0) return GDCA_EINVAL;
     CHK(begin(ctx));
-    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, 0.0, thresh, false, -1));
+    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, 0.0, thresh, false));
     HIPCHK(hipMemcpyAsync(n_dev, ctx->nk.p, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
     CHK(fetch_scalars(ctx));
     return symbols_ok(ctx);
@@ -2175,7 +2162,7 @@ gdca_status gdca_compute_weights_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t
     CHK(validate(ctx, N, M, 2));
     if (!Z_dev || !W_dev || !Meff || !(theta <= 1.0)) return GDCA_EINVAL;
     CHK(begin(ctx));
-    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, theta, -1, false, -1));
+    CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, theta, -1, false));
     HIPCHK(hipMemcpyAsync(W_dev, ctx->W.p, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     CHK(fetch_scalars(ctx));
     *Meff = ctx->sc_host->Meff;
@@ -2262,8 +2249,7 @@ static gdca_status operator_inverse_once(gdca_ctx *ctx, double *A_dev, int n, in
     hipStream_t s = ctx->stream;
     CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
     gdca_launch_copy_in(s, A_dev, n, (double *)ctx->A.p, n_pad);
-    int n_upd = 0;
-    CHK(inverse_stage(ctx, n, n_pad, false, &n_upd, nullptr));
+    CHK(inverse_stage(ctx, n, n_pad, nullptr));
     CHK(operator_norms_and_refine(ctx, A_dev, n, n_pad));
     CHK(operator_fallback(ctx, A_dev, n, n_pad));
     if (ctx->sc_host->info == INT32_MIN) return GDCA_OK;  // (the watchdog: the caller's matrix stays as it is)
@@ -2335,7 +2321,6 @@ gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double 
         gdca_launch_copy_in(lead->stream, A_dev[k], n[k], (double *)m->A.p, n_pad);
         m->pend.n = n[k];
         m->pend.n_pad = n_pad;
-        m->pend.timed = false;
     }
     if (st == GDCA_OK) st = run_inverses(lead, ctxs, K);
     // kappa_1 and, where it is beyond the threshold, the Newton-Schulz step: member by member, as gdca_spd_inverse_dev does (the
@@ -2382,6 +2367,7 @@ gdca_status gdca_fn_dev(gdca_ctx *ctx, const double *mJ_dev, int32_t N, int32_t 
     if (!mJ_dev || !S_dev) return GDCA_EINVAL;
     CHK(not_pending(ctx));
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->pend.timed = false;  // (no scalars, so no begin(): the timeline of the context's last run is closed here)
     const int sdim = q - 1, n = N * sdim, n_pad = round_up(n, GDCA_TILE);
     CHK(stage_neg_mJ(ctx, mJ_dev, n, n_pad));
     return score_stage(ctx, N, sdim, n_pad, contact_target(GDCA_SCORE_FROB, 0, S_dev));
@@ -2804,17 +2790,18 @@ gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)
     hipStream_t s = ctx->stream;
     const int blocks = 256 * 2;  // 2 waves per SIMD, all resident at once
     CHK(ensure(ctx, ctx->scratch[6], (size_t)blocks * 256 * sizeof(double)));
-    CHK(need_events(ctx, 2));
+    CHK(open_timeline(ctx, true, false));
     gdca_launch_probe_mfma_f64(s, (double *)ctx->scratch[6].p, 16, blocks);  // warm-up
-    HIPCHK(hipEventRecord(ctx->ev[0], s));
+    CHK(mark(ctx, T_BEGIN));
     gdca_launch_probe_mfma_f64(s, (double *)ctx->scratch[6].p, iters, blocks);
-    HIPCHK(hipEventRecord(ctx->ev[1], s));
+    CHK(mark(ctx, T_END));
     CHK(check_launch(ctx, "probe"));
     HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    bool tfail = false;
+    const double ms = elapsed(ctx, T_BEGIN, T_END, &tfail);
+    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
     const double flops = (double)blocks * 4.0 * (double)((iters + 1) / 2) * 16.0 * 2.0 * 16 * 16 * 4;  // 16 MFMAs per trip
-    *tflops = flops / ((double)ms * 1e-3) / 1e12;
+    *tflops = flops / (ms * 1e-3) / 1e12;
     return GDCA_OK;
 }
 

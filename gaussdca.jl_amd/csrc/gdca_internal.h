@@ -9,7 +9,18 @@
 #define GDCA_TILE 128     // tile edge of the SPD-inverse kernels (f64 elements)
 #define GDCA_HTILE 128    // sequences per side of a Hamming tile
 #define GDCA_MAXQ 31
-#define GDCA_STAMPS 20
+
+// The timeline of a fused run: its stage boundaries in stream order.  A boundary is marked by one of two clocks -- a HIP event of the
+// context, or a 100 MHz device time stamp in gdca_dev_scalars::stamp -- and both are indexed by this enum (gdca_api.hip: mark, elapsed).
+enum gdca_boundary {
+    T_NONE = -1,
+    T_BEGIN, T_THETA, T_WEIGHTS,
+    T_TALLY_BEGIN, T_TALLY_END,                              // around k_pair_tally of the covariance's first build (gdca_stats.ms_pair_tally)
+    T_COV,
+    T_INV_BEGIN, T_SWEEP_BEGIN, T_SWEEP_END, T_INV_END,      // the run's turn on the MFMA pipe (behind any pipeline gate), and the sweep kernel alone in it
+    T_SCORE_BEGIN, T_FN_BEGIN, T_FN_END, T_END,              // the score stage, and k_fn alone in it (gdca_stats.ms_fn)
+    T_COUNT
+};
 
 // Scalars that live in HBM so the whole pipeline can be enqueued without a host round trip.
 struct gdca_dev_scalars {
@@ -31,9 +42,8 @@ struct gdca_dev_scalars {
                        // caller's matrix (operator-level inverse); 0: not measured
     double pi_max;     // max over the n single-site frequencies with pseudocount (k_pi_finalize): ||C||_1 <= 2 N pi_max
     // device time stamps (100 MHz wall clock) of a run whose kernels were issued as batched grids (gdca_run_dev_phased: no HIP events
-    // between them -- an event per member and stage was most of the host's work for a batch): slot = the index of the event a
-    // launch of its own would have recorded (gdca_api.hip: EV_*)
-    unsigned long long stamp[GDCA_STAMPS];
+    // between them -- an event per member and stage was most of the host's work for a batch)
+    unsigned long long stamp[T_COUNT];
     int ham_cand2;   // pairs of the sampled tiles the consensus form would list (D1 < thresh)
     int ham_cut;     // word at which the three-plane bound form goes from all pairs of a tile to the list of those still below the threshold
                      // (k_hamming_decide; >= NW: never)
@@ -195,13 +205,12 @@ struct gdca_inverse_job {
     bool doomed;  // tests (option SWEEP_DEBUG bit 5): this launch's watchdog fires at its first unsatisfied wait
 };
 size_t gdca_inverse_flag_bytes(int n_pad);
-// ONE persistent launch on stream s; upd_ev (optional, 2 events) are recorded around the launch.
-void gdca_launch_spd_inverse(hipStream_t s, const gdca_inverse_job &job, hipEvent_t *upd_ev, int max_upd_ev, int *n_upd_launch,
-                             double *upd_flops);
+// ONE persistent launch on stream s; sweep_begin / sweep_end (each may be null) are recorded around the sweep kernel, behind k_sweep_prep.
+void gdca_launch_spd_inverse(hipStream_t s, const gdca_inverse_job &job, hipEvent_t sweep_begin, hipEvent_t sweep_end, double *upd_flops);
 // K <= gdca_inverse_max_merge() independent inverses (single-block schedules: small matrices) carried by ONE persistent launch;
 // every member's arithmetic is that of a launch of its own.  upd_flops: K entries.
 int gdca_inverse_max_merge(void);
-void gdca_launch_spd_inverse_merged(hipStream_t s, const gdca_inverse_job *jobs, int K, hipEvent_t *upd_ev, int max_upd_ev,
+void gdca_launch_spd_inverse_merged(hipStream_t s, const gdca_inverse_job *jobs, int K, hipEvent_t sweep_begin, hipEvent_t sweep_end,
                                     double *upd_flops);
 // ---- k_rank.hip --------------------------------------------------------------------------
 // compute_ranking (src/GaussDCA.jl:88-99) of S_dev (N x N column-major): `len` = gdca_ranking_length(N, sep) > 0 entries, sorted,

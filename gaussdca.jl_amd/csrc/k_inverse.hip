@@ -2709,8 +2709,7 @@ static SweepPlan plan_sweep(hipStream_t s0, const gdca_inverse_job &job, bool me
 
 static void write_sweep_trace(const char *trace_path, const SweepPlan &P, unsigned grid, unsigned long long *dbg);
 
-void gdca_launch_spd_inverse(hipStream_t s0, const gdca_inverse_job &job, hipEvent_t *upd_ev, int max_upd_ev, int *n_upd_launch,
-                             double *upd_flops)
+void gdca_launch_spd_inverse(hipStream_t s0, const gdca_inverse_job &job, hipEvent_t sweep_begin, hipEvent_t sweep_end, double *upd_flops)
 {
     SweepPlan P = plan_sweep(s0, job, false, 1);
     {
@@ -2734,24 +2733,22 @@ void gdca_launch_spd_inverse(hipStream_t s0, const gdca_inverse_job &job, hipEve
     D.dbg_main = dbg ? dbg + 2 * (mpos + 1) : nullptr;
     D.dbg_items = dbg ? dbg + 2 * (mpos + 1) + 8 + 1024 + 19 * (size_t)ng : nullptr;
     const unsigned grid = (unsigned)(2 * job.ws.update_cus);  // two 256-VGPR workgroups per CU: every register file full
-    const bool tm = upd_ev && max_upd_ev >= 2;
-    if (tm) (void)hipEventRecord(upd_ev[0], s0);
+    if (sweep_begin) (void)hipEventRecord(sweep_begin, s0);
     if (P.g > 1)
         GDCA_LAUNCH_DIRECT((k_sweep<true>), dim3(grid), dim3(256), 0, s0, D);
     else
         GDCA_LAUNCH_DIRECT((k_sweep<false>), dim3(grid), dim3(256), 0, s0, D);
-    if (tm) (void)hipEventRecord(upd_ev[1], s0);
+    if (sweep_end) (void)hipEventRecord(sweep_end, s0);
     if (dbg) {
         (void)hipStreamSynchronize(s0);
         write_sweep_trace(trace_path, P, grid, dbg);
         (void)hipFree(dbg);
     }
-    if (n_upd_launch) *n_upd_launch = 1;
     if (upd_flops) *upd_flops = 2.0 * T * T * KC * P.chunks;
 }
 
 // K <= SWEEP_MAX_MERGE inverses as one launch of k_sweep_merged; upd_flops[k] receives member k's issued MFMA flops
-void gdca_launch_spd_inverse_merged(hipStream_t s0, const gdca_inverse_job *jobs, int K, hipEvent_t *upd_ev, int max_upd_ev,
+void gdca_launch_spd_inverse_merged(hipStream_t s0, const gdca_inverse_job *jobs, int K, hipEvent_t sweep_begin, hipEvent_t sweep_end,
                                     double *upd_flops)
 {
     SweepBatch B{};
@@ -2770,13 +2767,12 @@ void gdca_launch_spd_inverse_merged(hipStream_t s0, const gdca_inverse_job *jobs
     }
     GDCA_LAUNCH_DIRECT(k_sweep_prep, dim3(16, (unsigned)K), dim3(256), 0, s0, prep);
     const unsigned grid = (unsigned)(2 * cus);
-    const bool tm = upd_ev && max_upd_ev >= 2;
-    if (tm) (void)hipEventRecord(upd_ev[0], s0);
+    if (sweep_begin) (void)hipEventRecord(sweep_begin, s0);
     if (multi)
         GDCA_LAUNCH_DIRECT(k_sweep_merged<true>, dim3(grid), dim3(256), 0, s0, B);
     else
         GDCA_LAUNCH_DIRECT(k_sweep_merged<false>, dim3(grid), dim3(256), 0, s0, B);
-    if (tm) (void)hipEventRecord(upd_ev[1], s0);
+    if (sweep_end) (void)hipEventRecord(sweep_end, s0);
 }
 
 static void write_sweep_trace(const char *trace_path, const SweepPlan &P, unsigned grid, unsigned long long *dbg)

@@ -88,7 +88,9 @@ typedef struct gdca_stats {
                                    2: the sweep gave up (a non-positive pivot of its own, or the step above could not converge) and
                                    the inverse was computed again by blocked Cholesky (dpotrf + dpotri, as the reference does);
                                    `info` and the scores are those of that factorisation */
-    /* device time (HIP events on the ctx stream), milliseconds */
+    /* device time, milliseconds: between two boundaries of the run's timeline, both marked by one clock -- HIP events on the ctx
+       stream, or, for the members of a phase batch issued as batched grids, 100 MHz device time stamps written by kernels of the
+       batch (a launch of its own is bracketed by events there too).  0: the run did not mark that stage, or timing is off */
     double ms_total;            /* Z in HBM -> S in HBM                                     */
     double ms_theta;            /* column histograms + theta                                */
     double ms_weights;          /* bit-plane pack + all-pairs Hamming + W, Meff             */
@@ -124,7 +126,8 @@ typedef struct gdca_stats {
                                    compulsory HBM write: 8 n^2 bytes); 0 with option REFINE=0                      */
     int32_t sweep_retries;      /* 0.6: times this run's SPD inverse was run AGAIN because the sweep kernel's watchdog had ended
                                    its launch (normally 0; see "Contexts and the device's queues" below).  The result is that
-                                   of the last attempt, the ms_* of the inverse and of the score stage are the last attempt's */
+                                   of the last attempt; ms_inverse, ms_inverse_update, ms_score and ms_fn are the last attempt's
+                                   (its score stage ran alone: no share of a batch), and ms_total runs to the end of the last attempt */
     int32_t reserved0;          /* (keeps the struct a multiple of 8 bytes; 0) */
 } gdca_stats;
 
@@ -145,8 +148,10 @@ int32_t gdca_device_count(void);
  *   - what a program cannot rule out (another process starting on the GPU, a library of its own that makes a stream) is survived: the
  *     sweep notices that its waves were off the hardware and ends a launch that no longer moves after ~0.1 s instead of seconds, and
  *     gdca_run_collect / gdca_spd_inverse_dev run that inverse again -- up to option SWEEP_RETRIES (default 2) times, reported in
- *     gdca_stats.sweep_retries; the results are those of an undisturbed run, bit for bit.  Only an inverse that fails every attempt
- *     is GDCA_EHIP ("a dependency wait inside the sweep kernel timed out"). */
+ *     gdca_stats.sweep_retries; the results are those of an undisturbed run: bit for bit for launches of their own and for
+ *     members of a merged launch under option MERGE_GROUP=1, equal to rounding for a member of a merged launch with the library's own
+ *     grouping (the second attempt is a launch of its own, swept in the pivot groups of that size).  Only an inverse that fails every
+ *     attempt is GDCA_EHIP ("a dependency wait inside the sweep kernel timed out"). */
 gdca_status gdca_ctx_create(int32_t device_id, gdca_ctx **out);
 /* same, but enqueue on an existing hipStream_t (passed as void*); NULL = the null stream */
 gdca_status gdca_ctx_create_on_stream(int32_t device_id, void *hip_stream, gdca_ctx **out);

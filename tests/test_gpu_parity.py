@@ -711,6 +711,11 @@ def test_a_launch_the_watchdog_ended_gets_a_second_attempt(g):
             S, st = cs[0].run(Z, 21, 0.8, -1.0, 0)
             assert st["sweep_retries"] == 1 and st["info"] == 0
             assert np.array_equal(S, want[k][0])
+            # the stage times of a retried run are the last attempt's, every interval on one clock (gdca.h): its score stage is not
+            # the second covariance build and inverse as well -- shapes at which that shows: the undisturbed inverse outlasts the scores
+            assert want[k][1]["ms_score"] < want[k][1]["ms_inverse"], want[k][1]
+            assert st["ms_score"] < st["ms_inverse"], st
+            assert st["ms_inverse"] + st["ms_score"] <= st["ms_total"] + 1e-3, st
             ii, jj, sc, st2 = cs[0].run_ranked_ptr(Z.ctypes.data, Z.shape[0], Z.shape[1], 21, 0.8, -1.0, 0, 5)
             assert st2["sweep_retries"] == 1
             assert np.array_equal(ii, want_r[k][0]) and np.array_equal(jj, want_r[k][1]) and np.array_equal(sc, want_r[k][2])
@@ -724,6 +729,8 @@ def test_a_launch_the_watchdog_ended_gets_a_second_attempt(g):
         for k in range(4):
             assert sts[k]["sweep_retries"] == 1 and sts[k]["info"] == 0, (k, sts[k])
             assert np.array_equal(dS[k].cpu().numpy(), want[k][0]), k
+            # (a member's retry runs alone, marked in the member's own clock: the batch's time stamps)
+            assert 0.0 < sts[k]["ms_score"] and sts[k]["ms_inverse"] + sts[k]["ms_score"] <= sts[k]["ms_total"] + 1e-3, (k, sts[k])
         # ... and ranked, from host matrices
         g.run_ranked_phased_async(cs, [Z.ctypes.data for Z in Zf], [Z.shape[0] for Z in Zf], [Z.shape[1] for Z in Zf], [21] * 4, 0.8, -1.0, 0, 5)
         for k, c in enumerate(cs):
