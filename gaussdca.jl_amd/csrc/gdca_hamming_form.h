@@ -33,8 +33,9 @@
 // density x M^2 / 2.  The constants are fitted to the kernel times of forced forms at configs B, C, D and four families of E
 // (profiles/consensus_bound_sweep.log: both forms' kernels traced per family):
 //   three-plane loop, no cut   C 1.93e-3, D 1.76e-3, E 2.0 .. 2.5e-3 us per tile and word
-//   product                    E = 8: 7.9e-3, E = 16: 8.6 .. 10.1e-3, E = 32: 12.3e-3 us per tile -- mostly per tile: a chunk's loads
-//                              are not covered by its predecessor's MFMAs (k_hamming_fp4.hip), so a tile costs a latency, not its K
+//   product                    E = 8: 7.9e-3, E = 16: 8.6 .. 10.1e-3, E = 32: 12.3e-3 us per tile -- mostly per tile: the epilogue's
+//                              scan was 61 % of a tile.  That scan has since been cut (C: 8.3e-3 -> 6.4e-3); the
+//                              constants below are still this fit, which overstates the product and so chooses it later, never wrongly
 //   refine                     0.86e-4 (N = 129) .. 1.1e-4 (N = 500) .. 2.3e-4 (N = 1000) us per listed pair
 //   image                      0.9 .. 1.7e-5 us per row and entry, 4e-5 where N is not a multiple of four (bytes one by one)
 #define HAM_T_DENSE 1.9e-3     // us per tile and word of the three-plane loop

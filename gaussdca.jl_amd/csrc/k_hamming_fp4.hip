@@ -29,10 +29,15 @@
 // J of ONE tile row I of the upper triangle.  Operands are staged global -> registers -> LDS in chunks of four k steps; the stream
 // of chunks runs across the tiles of the walk, double-buffered, one barrier per chunk, so only the first chunk of a walk is waited
 // for with nothing to do.  Where a row strip is at most two chunks (N <= 512) the A strip is loaded once and stays in LDS for the
-// whole walk (ARES): the kernel is bound by what a compute unit can fetch (64 KB a chunk for both operands against 0.86 us of
-// MFMA time), and a resident A halves it.  Rows of the triangle are cut into walks of F4_SEG tiles, all about equally long, which
-// balances the triangle.  The epilogue, per tile, compares S with N - 2 thresh and lists the pairs (the three-plane form's list: one
-// LDS counter, one device-wide atomic per tile).
+// whole walk (ARES).  Rows of the triangle are cut into walks of F4_SEG tiles, all about equally long, which balances the triangle.
+// The epilogue, per tile, compares S with N - 2 thresh.  Shader-clock stamps (-DGDCA_F4_STAMPS, tools/fp4_stamps.py,
+// profiles/fp4_feed_stamps_C.txt) showed that it, not the loads, was 61 % of a tile's 16 200 clocks at C (the wait for the loads:
+// 4 %): its scan ran 64 compares with their validity tests in every wave that held a single candidate, then two barriers and the
+// wait for a device-wide atomic.  Now: one maximum per four accumulators and a wave-uniform branch, the validity tests only behind
+// a mask that is not empty; a wave's candidates go, by a prefix sum and one LDS atomic, to the tile's LDS list (two lists, tile
+// parity); the chunk's own barrier publishes it, and wave 0 flushes it to the global list under the NEXT chunk -- the one
+// device-wide atomic per tile is issued before that chunk's MFMAs and waited for behind them.  What a tile holds beyond its LDS list
+// goes straight to the global list with an atomic per wave.  The listed set is the same; its order is not.
 #include <algorithm>
 
 #include "gdca_internal.h"
@@ -179,7 +184,36 @@ struct k_hamming_fp4_args {
     int2 *cand_list;
     unsigned cand_cap;
 };
-__shared__ unsigned f4_tile_n[2], f4_tile_base;  // (f4_tile_n: tile t of a walk counts into slot t % 2)
+// A tile's candidates wait in LDS, behind the operands, for the chunk after the tile: two lists (tile t of a walk: list t % 2) of
+// F4_LCAP packed entries (row of the tile << 8 | column of the tile) and their two counters
+#define F4_LCAP 1536
+#define F4_LDS_ALL (F4_LDS + 2 * F4_LCAP * 4 + 16)  // 159 760 bytes of the 160 KB a workgroup may have
+
+#ifdef GDCA_F4_STAMPS
+// tools/fp4_stamps.py only: shader-clock stamps of one lane of eight workgroups (walk 1 of the tile rows 0, 16, .., 112),
+// [workgroup][chunk of the walk][phase]; phases: 0 top of the chunk, 1 after its MFMAs, 2 after the LDS stores, 3 / 4 the
+// epilogue's begin and end (last chunk of a tile; else 0), 5 behind the chunk's barrier, 6 / 7 begin and end of the flush of the
+// tile before (first chunk of a tile; else 0), 8 the epilogue's scan done, 9 the wave's run of the list taken (0: no candidate)
+#define F4_STAMP_WG 8
+#define F4_STAMP_IT 32
+#define F4_STAMP_PH 10
+__device__ long long g_f4_stamps[F4_STAMP_WG * F4_STAMP_IT * F4_STAMP_PH];
+extern "C" int gdca_fp4_stamps(long long *out, int clear)
+{
+    if (clear) {
+        static long long zero[F4_STAMP_WG * F4_STAMP_IT * F4_STAMP_PH];
+        return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_f4_stamps), zero, sizeof(zero));
+    }
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_f4_stamps), sizeof(g_f4_stamps));
+}
+#define F4_STAMP(it, ph)                                                                                                  \
+    do {                                                                                                                  \
+        if (f4_stamped && tid == 0 && (it) < F4_STAMP_IT)                                                                 \
+            g_f4_stamps[(((int)blockIdx.y >> 4) * F4_STAMP_IT + (it)) * F4_STAMP_PH + (ph)] = (long long)clock64();       \
+    } while (0)
+#else
+#define F4_STAMP(it, ph) do { } while (0)
+#endif
 // ARES: the A strip (at most two chunks) is loaded once and stays in LDS; else A is streamed beside B
 template <int CAP, bool ARES>
 __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_fp4_args, CAP> B_)
@@ -199,11 +233,15 @@ __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_
     const int I = (int)blockIdx.y, J0 = I + (int)blockIdx.x * F4_SEG;
     if (J0 >= Mt) return;
     const int J1 = min(Mt, J0 + F4_SEG);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv & 3, wc = wv >> 2;
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wv & 3, wc = wv >> 2;  // (wv: on the scalar side)
     const int l32 = lane & 31, lh = lane >> 5;
+#ifdef GDCA_F4_STAMPS
+    const bool f4_stamped = blockIdx.x == 1 && (blockIdx.y & 15) == 0 && (blockIdx.y >> 4) < F4_STAMP_WG && blockIdx.z == 0;
+#endif
+    unsigned *const f4_list = reinterpret_cast<unsigned *>(f4_lds + F4_LDS), *const f4_cnt = f4_list + 2 * F4_LCAP;
     if (tid == 0) {
-        f4_tile_n[0] = 0u;
-        f4_tile_n[1] = 0u;
+        f4_cnt[0] = 0u;
+        f4_cnt[1] = 0u;
     }
     const size_t rowbytes = (size_t)E * 16;
     const int nchunk = E / (2 * F4_KC);  // (rows hold whole chunks; ARES: 1 or 2)
@@ -213,22 +251,24 @@ __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_
     // id / 8, piece id % 8 (eight consecutive threads: 128 contiguous bytes of a row).  Named registers: as an array behind lambdas
     // the pieces lived in scratch.  LDS: regions 0, 1 = A (ARES: chunks 0, 1 of the strip; else two buffers), 2, 3 = B's two buffers.
     const int srow = tid >> 3, spc = tid & 7;  // (pieces t and t + 1024: rows srow and srow + 128)
-    const unsigned char *ga = img + ((size_t)I * F4_TILE + srow) * rowbytes + spc * 16;
-    const unsigned char *gb0 = img + (size_t)srow * rowbytes + spc * 16;  // (+ J F4_TILE rowbytes)
+    // (a lane's place inside a tile's rows as a 32-bit offset: the tile's and the chunk's address stay on the scalar side)
+    const unsigned goff = (unsigned)srow * (unsigned)rowbytes + (unsigned)spc * 16u;
     const size_t half = (size_t)128 * rowbytes, tilebytes = (size_t)F4_TILE * rowbytes;
+    const unsigned char *const ga = img + (size_t)I * tilebytes;
     unsigned char *la = f4_lds + srow * F4_ROW + spc * 16;
     uint4 s0, s1, s2, s3;
     s0 = s1 = make_uint4(0u, 0u, 0u, 0u);
 #define F4_LOAD_A(ch)                                                                     \
     do {                                                                                  \
-        s0 = *reinterpret_cast<const uint4 *>(ga + (size_t)(ch) * (32 * F4_KC));          \
-        s1 = *reinterpret_cast<const uint4 *>(ga + half + (size_t)(ch) * (32 * F4_KC));   \
+        const unsigned char *g_ = ga + (size_t)(ch) * (32 * F4_KC);                       \
+        s0 = *reinterpret_cast<const uint4 *>(g_ + goff);                                 \
+        s1 = *reinterpret_cast<const uint4 *>(g_ + half + goff);                          \
     } while (0)
 #define F4_LOAD_B(J, ch)                                                                                      \
     do {                                                                                                      \
-        const unsigned char *g_ = gb0 + (size_t)(J) * tilebytes + (size_t)(ch) * (32 * F4_KC);                \
-        s2 = *reinterpret_cast<const uint4 *>(g_);                                                            \
-        s3 = *reinterpret_cast<const uint4 *>(g_ + half);                                                     \
+        const unsigned char *g_ = img + (size_t)(J) * tilebytes + (size_t)(ch) * (32 * F4_KC);                \
+        s2 = *reinterpret_cast<const uint4 *>(g_ + goff);                                                     \
+        s3 = *reinterpret_cast<const uint4 *>(g_ + half + goff);                                              \
     } while (0)
 #define F4_STORE_A(region)                                                                \
     do {                                                                                  \
@@ -271,15 +311,42 @@ __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_
     F4_LOAD_B(J0, 0);
     F4_STORE_B(0);
     __syncthreads();
+    // The flush of a tile's LDS list to the global list (wave 0; n > 0 entries of list q, tile Jt; b64: what lane 0's device-wide atomic
+    // returned -- beyond the capacity nothing is written)
+#define F4_FLUSH_WRITE(q, Jt, n, b64)                                                                                          \
+    do {                                                                                                                       \
+        const unsigned lo_ = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((b64) & 0xffffffffull));                 \
+        const unsigned hi_ = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((b64) >> 32));                           \
+        const unsigned base_ = (hi_ != 0u || lo_ > cand_cap) ? cand_cap : lo_;                                                 \
+        const unsigned *lst_ = f4_list + (q) * F4_LCAP;                                                                        \
+        for (unsigned k_ = (unsigned)lane; k_ < (n); k_ += 64u) {                                                              \
+            const unsigned e_ = lst_[k_], slot_ = base_ + k_;                                                                  \
+            if (slot_ < cand_cap) cand_list[slot_] = make_int2(I * F4_TILE + (int)(e_ >> 8), (Jt) * F4_TILE + (int)(e_ & 255u)); \
+        }                                                                                                                      \
+    } while (0)
+    unsigned fl_n = 0u;               // wave 0: entries of the tile before in its LDS list, their place in the global list asked for
+    unsigned long long fl_base = 0ull;  // (lane 0) and not yet waited for
     int J = J0, ch = 0;  // the chunk being multiplied
     for (int it = 0; it < total; ++it) {
         const int buf = it & 1;
         const bool more = it + 1 < total;
         const bool last = ch + 1 == nchunk;  // (of tile J)
         const int Jn = last ? J + 1 : J, chn = last ? 0 : ch + 1;
+        F4_STAMP(it, 0);
         if (more) {  // in flight under this chunk's MFMAs
             if constexpr (!ARES) F4_LOAD_A(chn);
             F4_LOAD_B(Jn, chn);
+        }
+        if (wv == 0 && ch == 0 && it > 0) {
+            // the tile before is complete and the barrier behind it has published its list: ONE device-wide atomic asks for its place
+            // in the global list now; the answer is waited for behind this chunk's MFMAs.  The counter starts over: its next adds
+            // are the tile after this one's, behind this chunk's barrier.
+            const int q = (J - 1 - J0) & 1;
+            fl_n = min((unsigned)__builtin_amdgcn_readfirstlane((int)f4_cnt[q]), (unsigned)F4_LCAP);  // (on the scalar side)
+            if (lane == 0) {
+                f4_cnt[q] = 0u;
+                if (fl_n) fl_base = atomicAdd(&sc->ham_ncand, (unsigned long long)fl_n);
+            }
         }
         const unsigned char *As = abase + (size_t)(ARES ? ch : buf) * F4_OP, *Bs = bbase + (size_t)buf * F4_OP;
         // (one k step at a time: unrolled, the compiler hoists all sixteen 16-byte reads of the chunk in front of the first MFMA and the
@@ -303,77 +370,119 @@ __global__ __launch_bounds__(1024) void k_hamming_fp4(const BatchArgs<k_hamming_
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[i], b[j], acc[i][j], 4, 4, 0, one, 0, one);
         }
+        F4_STAMP(it, 1);
         if (more) {  // (the other buffers: their readers passed the barrier of the chunk before)
             if constexpr (!ARES) F4_STORE_A(buf ^ 1);
             F4_STORE_B(buf ^ 1);
         }
+        F4_STAMP(it, 2);
+        if (wv == 0 && fl_n != 0u) {  // (its readers here, the list's next writers behind this chunk's barrier)
+            F4_STAMP(it, 6);
+            F4_FLUSH_WRITE((J - 1 - J0) & 1, J - 1, fl_n, fl_base);
+            fl_n = 0u;
+            F4_STAMP(it, 7);
+        }
         if (last) {
-            // ---- tile J is complete: its candidates, then the accumulators start over ----
+            F4_STAMP(it, 3);
+            // ---- tile J is complete: its candidates go to its LDS list, then the accumulators start over.  No barrier and no device-wide
+            // atomic here: the chunk's barrier below publishes the list, wave 0 flushes it under the next chunk ----
             // accumulator element e of block (i, j): row 8 (e / 4) + 4 (lane / 32) + e % 4, column lane % 32
             const int slot_n = (J - J0) & 1;
             const bool diag = I == J;
-            unsigned mine = 0;
             unsigned long long cand[2] = {0ull, 0ull};  // bit 16 j + e of cand[i]: element e of block (i, j)
-            // (most lanes of most tiles hold nothing above the limit: one maximum over the 64 accumulators decides that)
-            float mx = acc[0][0][0];
+            // One compare per accumulator, its lane mask tested on the scalar side: a tile lists a few dozen of its 65 536 pairs, so
+            // nearly every mask is empty and the validity tests run for the few that are not.  (As one maximum per lane and then the
+            // whole scan wherever any lane of the wave held a candidate -- nearly every wave of every tile at C -- the scan's vector
+            // instructions were half of a tile's time: profiles/fp4_feed_stamps_C.txt.)
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, acc[i][j][e]);
-            if (mx > limit) {
+                    for (int e4 = 0; e4 < 16; e4 += 4) {
+                        // (four accumulators share the first test: a compare and a branch each cost a wave about 12 clocks)
+                        const float m4 = fmaxf(fmaxf(acc[i][j][e4], acc[i][j][e4 + 1]), fmaxf(acc[i][j][e4 + 2], acc[i][j][e4 + 3]));
+                        if (__builtin_amdgcn_ballot_w64(m4 > limit) != 0ull) {  // (wave-uniform)
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int gc = J * F4_TILE + wc * 64 + j * 32 + l32;
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) {
-                            const int gr = I * F4_TILE + wr * 64 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
-                            if (acc[i][j][e] > limit && gr < M && gc < M && (diag ? gr < gc : true)) {
-                                cand[i] |= 1ull << (16 * j + e);
-                                ++mine;
+                            for (int e = e4; e < e4 + 4; ++e) {
+                                const bool above = acc[i][j][e] > limit;
+                                if (__builtin_amdgcn_ballot_w64(above) != 0ull) {  // (wave-uniform)
+                                    // (the empty asm: without it the compiler keeps all 64 row indices in registers for the whole walk)
+                                    int rb = I * F4_TILE + wr * 64 + 4 * lh;
+                                    asm volatile("" : "+v"(rb));
+                                    const int gr = rb + i * 32 + 8 * (e >> 2) + (e & 3);
+                                    const int gc = J * F4_TILE + wc * 64 + j * 32 + l32;
+                                    if (above && gr < M && gc < M && (diag ? gr < gc : true)) cand[i] |= 1ull << (16 * j + e);
+                                }
                             }
                         }
+#pragma unroll
+                        for (int e = e4; e < e4 + 4; ++e) acc[i][j][e] = 0.f;
                     }
-            }
+            F4_STAMP(it, 8);
+            const unsigned mine = (unsigned)(__builtin_popcountll(cand[0]) + __builtin_popcountll(cand[1]));
+            if (__builtin_amdgcn_ballot_w64(mine != 0u) != 0ull) {  // (wave-uniform)
+                // the wave's candidates take one run of the list: a prefix sum over its lanes, one LDS atomic
+                unsigned incl = mine;
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-            const unsigned off = mine ? atomicAdd(&f4_tile_n[slot_n], mine) : 0u;
-            __syncthreads();
-            const unsigned ntile = f4_tile_n[slot_n];  // (uniform)
-            // (the other slot: its readers -- the tile before -- are all past this barrier, its next writers behind the chunk's barrier below)
-            if (tid == 0) f4_tile_n[slot_n ^ 1] = 0u;
-            if (ntile != 0u) {
-                if (tid == 0) {
-                    const unsigned long long base = atomicAdd(&sc->ham_ncand, (unsigned long long)ntile);
-                    f4_tile_base = base > (unsigned long long)cand_cap ? cand_cap : (unsigned)base;  // (beyond the capacity nothing is written)
+                for (int d = 1; d < 64; d <<= 1) {
+                    const unsigned v = __shfl_up(incl, d);
+                    if (lane >= d) incl += v;
                 }
-                __syncthreads();
-                unsigned slot = f4_tile_base + off;
+                const unsigned wtot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+                unsigned woff = 0u;
+                if (lane == 0) woff = atomicAdd(&f4_cnt[slot_n], wtot);
+                woff = (unsigned)__builtin_amdgcn_readfirstlane((int)woff);
+                // what of the run lies beyond the LDS list (a tile of a cluster may hold up to 65 536 candidates) goes straight to the
+                // global list, with an atomic of this wave's own
+                const unsigned spill0 = max(woff, (unsigned)F4_LCAP);
+                const unsigned nspill = woff + wtot > spill0 ? woff + wtot - spill0 : 0u;
+                unsigned gbase = 0u;
+                if (nspill != 0u) {
+                    unsigned long long b64 = 0ull;
+                    if (lane == 0) b64 = atomicAdd(&sc->ham_ncand, (unsigned long long)nspill);
+                    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 & 0xffffffffull));
+                    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b64 >> 32));
+                    gbase = (hi != 0u || lo > cand_cap) ? cand_cap : lo;  // (beyond the capacity nothing is written)
+                }
+                F4_STAMP(it, 9);
+                unsigned idx = woff + incl - mine;
+                unsigned *lst = f4_list + slot_n * F4_LCAP;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     unsigned long long c = cand[i];
                     while (c) {
                         const int bit = __builtin_ctzll(c), j = bit >> 4, e = bit & 15;
-                        const int gr = I * F4_TILE + wr * 64 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
-                        const int gc = J * F4_TILE + wc * 64 + j * 32 + l32;
-                        if (slot < cand_cap) cand_list[slot] = make_int2(gr, gc);
-                        ++slot;
+                        const int tr = wr * 64 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3), tc = wc * 64 + j * 32 + l32;
+                        if (idx < (unsigned)F4_LCAP) {
+                            lst[idx] = (unsigned)(tr << 8 | tc);
+                        } else {
+                            const unsigned slot = gbase + (idx - spill0);
+                            if (slot < cand_cap) cand_list[slot] = make_int2(I * F4_TILE + tr, J * F4_TILE + tc);
+                        }
+                        ++idx;
                         c &= c - 1;
                     }
                 }
             }
+            F4_STAMP(it, 4);
         }
         J = Jn;
         ch = chn;
         __syncthreads();
+        F4_STAMP(it, 5);
     }
+    // the walk's last tile: published by the loop's last barrier
+    if (wv == 0) {
+        const int q = (J1 - 1 - J0) & 1;
+        const unsigned n = min(f4_cnt[q], (unsigned)F4_LCAP);
+        if (n != 0u) {
+            unsigned long long b64 = 0ull;
+            if (lane == 0) b64 = atomicAdd(&sc->ham_ncand, (unsigned long long)n);
+            F4_FLUSH_WRITE(q, J1 - 1, n, b64);
+        }
+    }
+#undef F4_FLUSH_WRITE
 }
 
 // ---- how many pairs would this form list?  (a sample of 128 x 128 tiles, the very tiles k_hamming<3, PROBE> takes for the three-plane form) ------
@@ -472,7 +581,7 @@ void gdca_launch_hamming_fp4(hipStream_t s, const void *img, int N, int M, gdca_
     const dim3 grid((unsigned)((Mt + F4_SEG - 1) / F4_SEG), (unsigned)Mt);
     const k_hamming_fp4_args a{(const unsigned char *)img, E, M, Mt, N, sc, (int2 *)cand_list, cap};
     if (E <= 4 * F4_KC)
-        gdca_launch<k_hamming_fp4_args, k_hamming_fp4<1, true>, k_hamming_fp4<GDCA_MAXB, true>>(grid, dim3(1024), F4_LDS, s, a);
+        gdca_launch<k_hamming_fp4_args, k_hamming_fp4<1, true>, k_hamming_fp4<GDCA_MAXB, true>>(grid, dim3(1024), F4_LDS_ALL, s, a);
     else
-        gdca_launch<k_hamming_fp4_args, k_hamming_fp4<1, false>, k_hamming_fp4<GDCA_MAXB, false>>(grid, dim3(1024), F4_LDS, s, a);
+        gdca_launch<k_hamming_fp4_args, k_hamming_fp4<1, false>, k_hamming_fp4<GDCA_MAXB, false>>(grid, dim3(1024), F4_LDS_ALL, s, a);
 }
