@@ -170,6 +170,19 @@ SYMBOLS = {
                                              C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
     "gdca_run_pair_energies": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
                                          C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_pair_blocks_length": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "gdca_pair_energies_blocked_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_pair_energies_blocked": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_assign_blocks_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdca_assign_blocks": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdca_run_partner_match_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_partner_match": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "gdca_mutation_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_mutation_scan": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_run_mutation_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
@@ -210,6 +223,22 @@ def load() -> C.CDLL:
 
 def _p(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
+
+
+def species_offsets(off) -> np.ndarray:
+    """species offsets as the library takes them: a contiguous int32 vector of S + 1 >= 2 entries (its values are checked there)"""
+    a = np.asarray(off)
+    if a.ndim != 1 or a.size < 2 or not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < 0 or a.max() > 2**31 - 1)):
+        raise ArgumentError("species offsets must be a vector of S + 1 >= 2 non-negative integers")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def pair_blocks_length(offA, offB) -> int:
+    """gdca_pair_blocks_length: the doubles the packed blocked matrix of these species holds; -1 for invalid offsets"""
+    offA, offB = np.ascontiguousarray(offA, dtype=np.int32), np.ascontiguousarray(offB, dtype=np.int32)
+    if offA.ndim != 1 or offA.shape != offB.shape:
+        return -1
+    return int(load().gdca_pair_blocks_length(_p(offA), _p(offB), len(offA) - 1))
 
 
 class Context:
@@ -369,6 +398,46 @@ class Context:
         (KA x KB, column-major) are device pointers."""
         self.check(self.lib.gdca_pair_energies_dev(self.h, C.c_void_p(mJ_ptr), self._opt(Pi_ptr), int(N), int(q), int(split),
                                                    C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB), int(what), C.c_void_p(E_ptr)))
+
+    # ---- partner matching per species: blocked pair energies and the assignment (gdca_run_partner_match) ----
+    def pair_energies_blocked_dev(self, mJ_ptr: int, Pi_ptr: int | None, N: int, q: int, split: int, XA_ptr: int, KA: int, XB_ptr: int,
+                                  KB: int, offA, offB, what: int, E_ptr: int) -> None:
+        """gdca_pair_energies_blocked_dev: as pair_energies_dev for species-sorted sequences; offA / offB are HOST offsets (S + 1
+        each), E the packed blocks (pair_blocks_length(offA, offB) doubles, device)."""
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        self.check(self.lib.gdca_pair_energies_blocked_dev(self.h, C.c_void_p(mJ_ptr), self._opt(Pi_ptr), int(N), int(q), int(split),
+                                                           C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB), _p(offA), _p(offB),
+                                                           len(offA) - 1, int(what), C.c_void_p(E_ptr)))
+
+    def assign_blocks_dev(self, E_ptr: int, offA, offB, match_ptr: int, gap_ptr: int | None = None) -> None:
+        """gdca_assign_blocks_dev: the minimum-cost assignment inside every block of the packed cost matrix E (device); match (int32,
+        offA[-1] entries) and gap (float64, or None) are device pointers, offA / offB HOST offsets."""
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        self.check(self.lib.gdca_assign_blocks_dev(self.h, C.c_void_p(E_ptr), _p(offA), _p(offB), len(offA) - 1, C.c_void_p(match_ptr),
+                                                   self._opt(gap_ptr)))
+
+    def run_partner_match_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int, XA_ptr: int | None,
+                              KA: int, XB_ptr: int | None, KB: int, offA, offB, what: int = 1, want_blocks: bool = True):
+        """gdca_run_partner_match on HOST matrices given by address: the model is fitted on Z as run() fits it, then the blocked pair
+        energies of the species-sorted XA / XB (None: that half of Z's own sequences) and the assignment inside every species.
+        Returns ((E packed float64 or None, match int32[KA], gap float64[KA]), stats)."""
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        ka = int(KA) if XA_ptr is not None else int(M)
+        E = np.empty(max(pair_blocks_length(offA, offB), 0), dtype=np.float64) if want_blocks else None
+        match, gap = np.empty(max(ka, 0), dtype=np.int32), np.empty(max(ka, 0), dtype=np.float64)
+        st = self._run_readout(self.lib.gdca_run_partner_match, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr), int(KA),
+                               self._opt(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, int(what), None if E is None else _p(E),
+                               _p(match), _p(gap))
+        return (E, match, gap), st
+
+    def run_partner_match_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int, XA_ptr: int | None,
+                              KA: int, XB_ptr: int | None, KB: int, offA, offB, what: int, E_ptr: int | None, match_ptr: int,
+                              gap_ptr: int | None):
+        """Device-pointer form (Z, XA, XB, E, match and gap resident in HBM; E None: kept inside the context).  Returns the stats dict."""
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        return self._run_readout(self.lib.gdca_run_partner_match_dev, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr),
+                                 int(KA), self._opt(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, int(what), self._opt(E_ptr),
+                                 C.c_void_p(match_ptr), self._opt(gap_ptr))
 
     # ---- the energy change of every single substitution (gdca_run_mutation_scan) ----
     def run_mutation_scan_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None,

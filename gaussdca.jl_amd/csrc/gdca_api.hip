@@ -37,15 +37,29 @@ struct gdca_gate {
 // APC), or -- the fused energy entries -- the model scored on sequences X, on the pairings across a split, or scanned for every single
 // substitution of sequences X.  The enqueued run keeps
 // its own (gdca_pending::target): a second attempt, refinement or fallback at collect time scores the same thing again.
+// The species of a species-sorted pair problem as the blocked pair stage and the assignment take them (species_blocks makes it): the
+// species table and the gather's work list on the device (ctx->PBtab, ctx->PBitems), and what the host keeps of them.
+struct pair_blocks {
+    const long long *eoff;         // device [S + 1]: where block s starts in the packed matrix
+    const int32_t *offA, *offB;    // device [S + 1] each
+    const int32_t *items;          // device: the work list (gdca_pair_block_items), cut for chunks of Ac sequences a
+    const long long *first;        // HOST: the first item of every chunk of T, and the count behind the last (valid during the call)
+    int S, Ac, kmax;               // kmax: the largest kA_s or kB_s
+    long long total;               // doubles of the packed matrix
+};
+
 struct score_target {
-    enum { CONTACT, ENERGY, PAIR, MUTATION } kind;
-    double *out;                       // S (N x N), E (K), E (KA x KB) or D (q x N x K)
+    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION } kind;
+    double *out;                       // S (N x N), E (K), E (KA x KB), E (packed blocks) or D (q x N x K)
     int score, apc;                    // contact
     const int8_t *X;                   // energy (k_energy.hip) and mutation scan (k_mutation.hip, with `what`): N x K
     int K;
     const int8_t *XA, *XB;             // pair (k_pair_energy.hip): as pair_stage takes them
     size_t strideA, strideB;
     int KA, KB, split, what;
+    pair_blocks blocks;                // partner: the blocked pair stage, then the assignment (k_assign.hip) into match / gap
+    int32_t *match;
+    double *gap;
 };
 
 static score_target contact_target(int score, int apc, double *S_dev)
@@ -84,6 +98,17 @@ static score_target pair_target(const int8_t *Z, int N, int M, int split, const 
     t.XB = XB ? XB : Z + split;
     t.strideB = XB ? (size_t)(N - split) : (size_t)N;
     t.KB = XB ? KB : M;
+    return t;
+}
+
+// (the pair target's sequences; the species come sorted as blk describes them)
+static score_target partner_target(const score_target &pair, const pair_blocks &blk, int32_t *match_dev, double *gap_dev)
+{
+    score_target t = pair;
+    t.kind = score_target::PARTNER;
+    t.blocks = blk;
+    t.match = match_dev;
+    t.gap = gap_dev;
     return t;
 }
 
@@ -156,7 +181,10 @@ struct gdca_ctx {
     // pair energies (k_pair_energy.hip): the packed symbols of the A and the B halves, the gap-padded halves and their marginal energies,
     // the folded rows T of one chunk of A sequences
     gdca_buf PXa, PXb, PXpad, PEab, PT;
-    int ncu;                   // compute units of the device
+    // partner matching: the species table (eoff, offA, offB), the blocked gather's work list, and the packed matrix of a fused run
+    // whose caller does not want it
+    gdca_buf PBtab, PBitems, PBE;
+    int ncu;                  // compute units of the device
     int *item0_host;           // pinned staging of the sweep's item table
     int item0_cap;
     gdca_buf scratch[N_SCRATCH];
@@ -577,7 +605,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pipc, &ctx->A, &ctx->G, &ctx->H, &ctx->P, &ctx->Sg, &ctx->Dblk, &ctx->Ld,
                         &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg,
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
-                        &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT};
+                        &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < N_SCRATCH; ++i)
@@ -971,8 +999,10 @@ static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
 // site of sequence 0's half; sequence k's starts strideA / strideB bytes on (so the columns of an alignment serve as they lie).
 // what = GDCA_PAIR_ENERGY: the marginal energies through energy_stage on the gap-padded halves (m.Pi needed), combined in the gather
 // kernel's epilogue; GDCA_PAIR_COUPLING: R alone, no g.  Illegal bytes: sc->bad_symbol bit 2.
+// blk != nullptr: only the pairings inside the species of species-sorted sequences, E packed block by block (include/gdca.h, partner
+// matching) -- the pack, the pad, the marginal energies and the fold are the same calls; the gather goes by blk's work list.
 static gdca_status pair_stage(gdca_ctx *ctx, const gdca_model &m, int split, const int8_t *XA, size_t strideA, int KA, const int8_t *XB,
-                              size_t strideB, int KB, int what, double *E_dev)
+                              size_t strideB, int KB, int what, double *E_dev, const pair_blocks *blk = nullptr)
 {
     hipStream_t s = ctx->stream;
     const int N = m.N, q = m.q, sdim = q - 1, n = N * sdim, nB = (N - split) * sdim;
@@ -990,12 +1020,26 @@ static gdca_status pair_stage(gdca_ctx *ctx, const gdca_model &m, int split, con
         EAB = (const double *)ctx->PEab.p;
         c0 = (const double *)ctx->gvec.p + n;
     }
-    const int Ac = gdca_pair_chunk(nB, KA, ctx->tune.pair_chunk);
+    const int Ac = blk ? blk->Ac : gdca_pair_chunk(nB, KA, ctx->tune.pair_chunk);
     CHK(ensure(ctx, ctx->PT, (size_t)Ac * nB * sizeof(double)));
-    for (int a0 = 0; a0 < KA; a0 += Ac)
-        HIPCHK(gdca_launch_pair_chunk(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim, KA, KB,
-                                      a0, std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev, ctx->ncu));
-    return check_launch(ctx, "pair energies");
+    for (int a0 = 0, c = 0; a0 < KA; a0 += Ac, ++c) {
+        if (blk)
+            HIPCHK(gdca_launch_pair_chunk_blocked(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim,
+                                                  KA, KB, a0, std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev,
+                                                  blk->items + 4 * blk->first[c], blk->first[c + 1] - blk->first[c], blk->eoff, blk->offA,
+                                                  blk->offB, ctx->ncu));
+        else
+            HIPCHK(gdca_launch_pair_chunk(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim, KA, KB,
+                                          a0, std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev, ctx->ncu));
+    }
+    return check_launch(ctx, blk ? "blocked pair energies" : "pair energies");
+}
+
+// match / gap of the assignment inside every block of the packed cost matrix E_dev (k_assign.hip)
+static gdca_status assign_stage(gdca_ctx *ctx, const double *E_dev, const pair_blocks &blk, int32_t *match_dev, double *gap_dev)
+{
+    HIPCHK(gdca_launch_assign_blocks(ctx->stream, E_dev, blk.eoff, blk.offA, blk.offB, blk.S, blk.kmax, match_dev, gap_dev));
+    return check_launch(ctx, "assignment");
 }
 
 // D[(b - 1) + q (i + N k)]: the site potentials V (what = GDCA_MUT_POTENTIAL) or the energy changes dE (GDCA_MUT_DELTA) of every single
@@ -1017,6 +1061,9 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
     switch (t.kind) {
     case score_target::ENERGY: return energy_stage(ctx, m, t.X, t.K, t.out);
     case score_target::PAIR: return pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
+    case score_target::PARTNER:
+        CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out, &t.blocks));
+        return assign_stage(ctx, t.out, t.blocks, t.match, t.gap);
     case score_target::MUTATION: return mutation_stage(ctx, m, t.X, t.K, t.what, t.out);
     case score_target::CONTACT: break;
     }
@@ -2473,6 +2520,124 @@ gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
     return run_target(ctx, Z_dev, N, M, q, p, pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, what, E_dev), st);
 }
 
+// ---- partner matching per species: the blocked pair energies and the assignment ----
+// eoff[S] of valid species offsets (S + 1 host int32 each: from 0, non-decreasing), or -1; *kmax: the largest kA_s or kB_s
+static long long blocks_length(const int32_t *offA, const int32_t *offB, int S, int *kmax)
+{
+    if (!offA || !offB || S < 1 || offA[0] != 0 || offB[0] != 0) return -1;
+    long long total = 0;
+    int km = 0;
+    for (int s = 0; s < S; ++s) {
+        const long long ka = (long long)offA[s + 1] - offA[s], kb = (long long)offB[s + 1] - offB[s];
+        if (ka < 0 || kb < 0) return -1;
+        total += ka * kb;
+        km = std::max(km, (int)std::max(ka, kb));
+    }
+    if (kmax) *kmax = km;
+    return total;
+}
+
+int64_t gdca_pair_blocks_length(const int32_t *offA, const int32_t *offB, int32_t S)
+{
+    return blocks_length(offA, offB, S, nullptr);
+}
+
+// The species of a call: offsets checked against the counts (nothing has run when that fails), the table in ctx->PBtab and -- nB > 0:
+// the blocked gather will run over (N - split)(q - 1) = nB rows -- its work list in ctx->PBitems, cut at the chunks pair_stage will
+// make.  `first` is the caller's: blk->first points into it.
+static gdca_status species_blocks(gdca_ctx *ctx, const void *offA_, const void *offB_, int S, long long KA, long long KB, int nB, bool assign,
+                                  pair_blocks *blk, std::vector<long long> &first)
+{
+    const int32_t *offA = (const int32_t *)offA_, *offB = (const int32_t *)offB_;
+    int kmax = 0;
+    const long long total = blocks_length(offA, offB, S, &kmax);
+    if (total < 0 || offA[S] != KA || offB[S] != KB)
+        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
+    if (assign && kmax > GDCA_ASSIGN_MAX)
+        return fail(ctx, GDCA_EINVAL, "a species has more than GDCA_ASSIGN_MAX sequences on one side%s%s", "", "");
+    CHK(not_pending(ctx));
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t S1 = (size_t)S + 1;
+    std::vector<long long> eoff(S1, 0);
+    for (int s = 0; s < S; ++s) eoff[s + 1] = eoff[s] + ((long long)offA[s + 1] - offA[s]) * ((long long)offB[s + 1] - offB[s]);
+    CHK(ensure(ctx, ctx->PBtab, S1 * (sizeof(long long) + 2 * sizeof(int32_t))));
+    char *tab = (char *)ctx->PBtab.p;
+    HIPCHK(hipMemcpyAsync(tab, eoff.data(), S1 * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tab + S1 * sizeof(long long), offA, S1 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tab + S1 * (sizeof(long long) + sizeof(int32_t)), offB, S1 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    blk->eoff = (const long long *)tab;
+    blk->offA = (const int32_t *)(tab + S1 * sizeof(long long));
+    blk->offB = blk->offA + S1;
+    blk->items = nullptr;
+    blk->first = nullptr;
+    blk->S = S;
+    blk->Ac = 0;
+    blk->kmax = kmax;
+    blk->total = total;
+    std::vector<int32_t> items;
+    if (nB > 0) {
+        blk->Ac = gdca_pair_chunk(nB, (int)KA, ctx->tune.pair_chunk);
+        gdca_pair_block_items(offA, offB, S, blk->Ac, items, first);
+        CHK(ensure(ctx, ctx->PBitems, items.size() * sizeof(int32_t)));
+        if (!items.empty())
+            HIPCHK(hipMemcpyAsync(ctx->PBitems.p, items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        blk->items = (const int32_t *)ctx->PBitems.p;
+        blk->first = first.data();
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));  // (the host arrays of this frame have been read)
+    return GDCA_OK;
+}
+
+gdca_status gdca_pair_energies_blocked_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, int32_t split,
+                                           const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA,
+                                           const void *offB, int32_t S, int32_t what, double *E_dev)
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
+    if (!mJ_dev || !XA_dev || !XB_dev || !E_dev || !offA || !offB || (what == GDCA_PAIR_ENERGY && !Pi_dev))
+        return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    pair_blocks blk;
+    std::vector<long long> first;
+    CHK(species_blocks(ctx, offA, offB, S, KA, KB, (N - split) * (q - 1), false, &blk, first));
+    CHK(begin(ctx));
+    CHK(pair_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), split, XA_dev, (size_t)split, KA, XB_dev, (size_t)(N - split), KB, what, E_dev,
+                   &blk));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_assign_blocks_dev(gdca_ctx *ctx, const double *E_dev, const void *offA, const void *offB, int32_t S, int32_t *match_dev,
+                                   double *gap_dev)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (!E_dev || !offA || !offB || !match_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (S < 1) return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1)%s%s", "", "");
+    pair_blocks blk;
+    std::vector<long long> first;
+    CHK(species_blocks(ctx, offA, offB, S, ((const int32_t *)offA)[S], ((const int32_t *)offB)[S], 0, true, &blk, first));
+    CHK(assign_stage(ctx, E_dev, blk, match_dev, gap_dev));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GDCA_OK;
+}
+
+gdca_status gdca_run_partner_match_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                       const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA, const void *offB,
+                                       int32_t S, int32_t what, double *E_dev, int32_t *match_dev, double *gap_dev, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    const int ka = XA_dev ? KA : M, kb = XB_dev ? KB : M;
+    CHK(validate_pair(ctx, N, q, split, ka, kb, what));
+    if (!Z_dev || !match_dev || !offA || !offB || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_params(ctx, p));
+    pair_blocks blk;
+    std::vector<long long> first;
+    CHK(species_blocks(ctx, offA, offB, S, ka, kb, (N - split) * (q - 1), true, &blk, first));
+    if (!E_dev) {
+        CHK(ensure(ctx, ctx->PBE, (size_t)blk.total * sizeof(double)));
+        E_dev = (double *)ctx->PBE.p;
+    }
+    return run_target(ctx, Z_dev, N, M, q, p,
+                      partner_target(pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, what, E_dev), blk, match_dev, gap_dev), st);
+}
+
 // the argument checks the four mutation-scan entry points share (nothing has run when one fails); K as it will be used
 static gdca_status validate_mutation(gdca_ctx *ctx, int N, int q, long long K, int what)
 {
@@ -2747,6 +2912,83 @@ gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
     CHK(up);
     CHK(gdca_run_pair_energies_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, what, E_dev, st));
     return to_host(ctx, E_host, ctx->scratch[5], ne);
+}
+
+// the packed length of a host form's species, its offsets held against the counts (EINVAL with nothing uploaded)
+static gdca_status host_blocks_length(gdca_ctx *ctx, const void *offA, const void *offB, int S, long long KA, long long KB, long long *total)
+{
+    if (!offA || !offB) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    *total = blocks_length((const int32_t *)offA, (const int32_t *)offB, S, nullptr);
+    if (*total < 0 || ((const int32_t *)offA)[S] != KA || ((const int32_t *)offB)[S] != KB)
+        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
+    return GDCA_OK;
+}
+
+gdca_status gdca_pair_energies_blocked(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split, const int8_t *XA,
+                                       int32_t KA, const int8_t *XB, int32_t KB, const void *offA, const void *offB, int32_t S, int32_t what,
+                                       double *E)
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
+    if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    long long total = 0;
+    CHK(host_blocks_length(ctx, offA, offB, S, KA, KB, &total));
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)N * (q - 1), ne = (size_t)total * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
+    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 0, XA, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 3, XB, (size_t)(N - split) * KB, &up);
+    double *E_dev = staged_out(ctx, 5, ne, &up);
+    CHK(up);
+    CHK(gdca_pair_energies_blocked_dev(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, offA, offB, S, what, E_dev));
+    return ne ? to_host(ctx, E, ctx->scratch[5], ne) : GDCA_OK;
+}
+
+gdca_status gdca_assign_blocks(gdca_ctx *ctx, const double *E, const void *offA, const void *offB, int32_t S, int32_t *match, double *gap)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (!E || !match || !offA || !offB) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (S < 1) return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1)%s%s", "", "");
+    const long long KA = ((const int32_t *)offA)[S], KB = ((const int32_t *)offB)[S];
+    long long total = 0;
+    CHK(host_blocks_length(ctx, offA, offB, S, KA, KB, &total));
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nm = (size_t)KA * sizeof(int32_t), ng = (size_t)KA * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const double *E_dev = (const double *)upload(ctx, 5, E, (size_t)total * sizeof(double), &up);
+    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
+    double *gap_dev = gap ? staged_out(ctx, 7, ng, &up) : nullptr;
+    CHK(up);
+    CHK(gdca_assign_blocks_dev(ctx, E_dev, offA, offB, S, match_dev, gap_dev));
+    if (gap && ng) CHK(to_host(ctx, gap, ctx->scratch[7], ng));
+    return nm ? to_host(ctx, match, ctx->scratch[6], nm) : GDCA_OK;
+}
+
+gdca_status gdca_run_partner_match(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                   const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA, const void *offB,
+                                   int32_t S, int32_t what, double *E_host, int32_t *match_host, double *gap_host, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    const int ka = XA_host ? KA : M, kb = XB_host ? KB : M;
+    CHK(validate_pair(ctx, N, q, split, ka, kb, what));
+    if (!Z_host || !match_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    long long total = 0;
+    CHK(host_blocks_length(ctx, offA, offB, S, ka, kb, &total));
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ne = (size_t)total * sizeof(double), nm = (size_t)ka * sizeof(int32_t), ng = (size_t)ka * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
+    double *E_dev = E_host ? staged_out(ctx, 5, ne, &up) : nullptr;
+    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
+    double *gap_dev = gap_host ? staged_out(ctx, 7, ng, &up) : nullptr;
+    CHK(up);
+    CHK(gdca_run_partner_match_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, offA, offB, S, what, E_dev, match_dev, gap_dev, st));
+    if (E_host && ne) CHK(to_host(ctx, E_host, ctx->scratch[5], ne));
+    if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
+    return to_host(ctx, match_host, ctx->scratch[6], nm);
 }
 
 gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "gdca.h"
 
 #define GDCA_TILE 128     // tile edge of the SPD-inverse kernels (f64 elements)
@@ -284,6 +286,22 @@ void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const
 hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N,
                                   int split, int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E,
                                   int ncu);
+// The pairings inside the species of species-sorted sequences (include/gdca.h, partner matching).  The work list: 4 int32 an item
+// (species, first a, first b, na | nb << 8), a ascending, no group of a across a multiple of Ac; first[c] = the first item of chunk c
+// (one entry more than chunks).  offA / offB: S + 1 valid offsets
+void gdca_pair_block_items(const int32_t *offA, const int32_t *offB, int S, int Ac, std::vector<int32_t> &items, std::vector<long long> &first);
+// ... and the blocks of the packed E those items of one chunk cover (items, eoff [S + 1], offA, offB [S + 1]: device); the fold and every
+// other argument as gdca_launch_pair_chunk, every entry bit for bit its
+hipError_t gdca_launch_pair_chunk_blocked(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N,
+                                          int split, int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0,
+                                          double *E, const int32_t *items, long long nitems, const long long *eoff, const int32_t *offA,
+                                          const int32_t *offB, int ncu);
+
+// ---- k_assign.hip: the minimum-cost assignment inside every block of a blocked cost matrix -------------------------------------------------
+// match[KA] / gap[KA] (gap may be nullptr) of the S species (eoff, offA, offB: device, S + 1 entries each); kmax = the largest kA_s or
+// kB_s (<= GDCA_ASSIGN_MAX)
+hipError_t gdca_launch_assign_blocks(hipStream_t s, const double *E, const long long *eoff, const int32_t *offA, const int32_t *offB, int S,
+                                     int kmax, int32_t *match, double *gap);
 
 // ---- k_mutation.hip: V(x; i, c) / dE(x; i, b) of every single substitution of K sequences ------------------------------------------------
 // D[(b - 1) + q (i + N k)] (q = sdim + 1; what: GDCA_MUT_DELTA | GDCA_MUT_POTENTIAL) of the K sequences packed by gdca_launch_energy_pack

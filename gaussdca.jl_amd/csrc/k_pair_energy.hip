@@ -21,6 +21,11 @@
 //   k_pair_gather  R[a, b] = sum_{j in B} T[a][r_b(j)]: a workgroup keeps segments of the T rows of 8 sequences a in LDS, interleaved
 //                  [row][8] (64 B a row: one symbol decode serves eight pairings), for 256 x BU sequences b; and, `what` = energy, the
 //                  combination ((EA[a] + EB[b]) - c0 / 2) + R in its epilogue -- the K_A x K_B matrix is written once and never read.
+//   k_pair_gather_blocked  the same sum for the pairings INSIDE the species of a species-sorted problem (include/gdca.h, partner
+//                  matching): a work item = (species, up to 8 of its sequences a, up to 32 of its sequences b), built on the host;
+//                  the same LDS layout, segments and epilogue, but a lane owns ONE pairing (lane = (b, a of 8)) where k_pair_gather's
+//                  lane owns a sequence b against eight a -- a species of five would use five of its lanes.  The packed block of
+//                  species s is written once.  Every entry is bit for bit k_pair_gather's (the same additions in the same order).
 // T is chunked over a (gdca_pair_chunk: ~256 MB; option PAIR_CHUNK).
 // ORDER-FIXED: T[a][row] is summed by ONE thread over the sites i ascending, R[a, b] by ONE thread over the sites j ascending (the
 // segments in ascending order), gaps adding an exact zero in their place; the fold direction is always A.  No floating-point atomics.
@@ -36,6 +41,7 @@
 #define PGA 8         // sequences a whose T rows a workgroup of k_pair_gather holds
 #define PBU_WIDE 2    // sequences b per thread of k_pair_gather / where that would leave compute units without a workgroup
 #define PBU_NARROW 1
+#define PGB 32        // sequences b of one work item of k_pair_gather_blocked (x PGA sequences a: the workgroup's 256 lanes)
 #define PSEG_ROWS 1020  // T rows per LDS segment of k_pair_gather: (1020 + 1) x 8 doubles = 63.8 KB, two workgroups a compute unit
 
 // Xp (N x (KA + KB)): sequence k < KA = a_k (+) gaps, sequence KA + k = gaps (+) b_k (bytes copied as they are: the energy stage's own
@@ -190,6 +196,65 @@ __global__ __launch_bounds__(256) void k_pair_gather(const k_pair_gather_args p)
     }
 }
 
+// ---- gather B inside the species of a species-sorted problem ------------------------------------------------------------------------------
+struct k_pair_gather_blocked_args {
+    const double *T;      // [Ac][nB]
+    const uint32_t *XBg;  // [ceil(NB / 4)][KB]
+    const double *EAB;    // as k_pair_gather
+    const double *c0;
+    double *E;            // packed: block s at eoff[s], column-major kA_s x kB_s
+    const int4 *items;    // this launch's work items: x = species, y = first a (global), z = first b (global), w = na | nb << 8
+    const long long *eoff;  // [S + 1]
+    const int *offA, *offB;  // [S + 1] each
+    int NB, sdim, nB, SB, KA, KB, a0;
+};
+
+__global__ __launch_bounds__(256) void k_pair_gather_blocked(const k_pair_gather_blocked_args p)
+{
+    extern __shared__ double lds_[];  // as k_pair_gather: [SR + 1 rows][PGA], row SR = zeros (the gap)
+    const int sdim = p.sdim, SR = p.SB * sdim;
+    const int t = threadIdx.x, g = t & (PGA - 1), bl = t >> 3;
+    const int4 it = p.items[blockIdx.x];
+    const int na = it.w & 0xff, nb = it.w >> 8;
+    const int ag = it.y - p.a0;  // first sequence a, within the launch's Ac (the host cuts the groups at the chunk boundaries)
+    const bool live = g < na && bl < nb;
+    const long long bk = (long long)it.z + bl;
+    double acc = 0.0;
+    const uint32_t gapw = 0x01010101u * (uint32_t)sdim;
+
+    for (int j0 = 0; j0 < p.NB; j0 += p.SB) {
+        const int r0 = j0 * sdim;
+        const int nr = min(SR, p.nB - r0);
+        __syncthreads();  // (the previous segment has been read)
+        for (int idx = t; idx < nr * PGA; idx += 256) {
+            const int gg = idx & (PGA - 1), r = idx >> 3;
+            lds_[idx] = gg < na ? p.T[(size_t)(ag + gg) * p.nB + r0 + r] : 0.0;
+        }
+        if (t < PGA) lds_[SR * PGA + t] = 0.0;
+        __syncthreads();
+        const int nw = (min(p.SB, p.NB - j0) + PT - 1) / PT;
+        for (int jb = 0; jb < nw; ++jb) {
+            const uint32_t w = live ? p.XBg[(size_t)(j0 / PT + jb) * p.KB + bk] : gapw;
+#pragma unroll
+            for (int l = 0; l < PT; ++l) {
+                const int sym = (int)((w >> (8 * l)) & 0xffu);
+                const int r = sym < sdim ? (jb * PT + l) * sdim + sym : SR;
+                acc += lds_[r * PGA + g];
+            }
+        }
+    }
+    if (!live) return;
+    const int a = it.y + g, oa = p.offA[it.x];
+    const long long kA = p.offA[it.x + 1] - oa;
+    const size_t at = (size_t)(p.eoff[it.x] + (a - oa) + kA * (bk - p.offB[it.x]));
+    if (p.EAB) {
+        const double hc0 = 0.5 * *p.c0;
+        p.E[at] = ((p.EAB[a] + p.EAB[(size_t)p.KA + bk]) - hc0) + acc;
+    } else {
+        p.E[at] = acc;
+    }
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------
 // sequences a one launch of the fold / gather kernels takes: a multiple of the fold workgroup's 4 x PAU_WIDE whose T stays within
 // ~256 MB, at most 32768 (wanted > 0: option PAIR_CHUNK, any SMALLER count -- tests; it never raises the buffer beyond the rule)
@@ -211,27 +276,44 @@ void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const
     GDCA_LAUNCH_DIRECT(k_pair_pad, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, s, XA, strideA, XB, strideB, N, split, KA, KB, q, Xp);
 }
 
+// T[a0 .. a0 + Ac - 1][nB rows] from the block of A (ld, sign) and the packed symbols of the A halves
+static hipError_t launch_pair_fold(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, int NA, int NB, int sdim, int KA,
+                                   int a0, int Ac, double *T, int ncu)
+{
+    const int nA = NA * sdim, nB = NB * sdim;
+    const k_pair_fold_args a{A, ld, sign, XAg, T, NA, sdim, nA, nB, KA, a0, Ac};
+    const int rt = (nB + PROWS - 1) / PROWS;
+    // 128 sequences a workgroup -- or 16, where 128 would give fewer than two workgroups a compute unit
+    const bool wide = gdca_wide_instance(Ac, 4 * PAU_WIDE, rt, ncu);
+    const int per = 4 * (wide ? PAU_WIDE : PAU_NARROW);
+    const size_t lds = (size_t)PT * (sdim + 1) * PROWS * sizeof(double);
+    void (*kern)(k_pair_fold_args) = wide ? k_pair_fold<PAU_WIDE> : k_pair_fold<PAU_NARROW>;
+    const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    if (e != hipSuccess) return e;
+    GDCA_LAUNCH_DIRECT(kern, dim3(rt, (Ac + per - 1) / per), dim3(256), lds, s, a);
+    return hipSuccess;
+}
+
+// sites per LDS segment of the gather kernels: whole dwords of XBg (s <= 30: at least 32)
+static int pair_segment_sites(int NB, int sdim)
+{
+    int SB = (PSEG_ROWS / sdim) & ~(PT - 1);
+    if (SB > ((NB + PT - 1) & ~(PT - 1))) SB = (NB + PT - 1) & ~(PT - 1);
+    return SB;
+}
+
 // E[a0 .. a0 + Ac - 1][all b] from the block of A (ld, sign) and the packed symbols; T: Ac x nB doubles.  EAB == nullptr: the coupling R.
 // An error: the dynamic LDS limit could not be raised for a tile; the kernel it was for and those behind it were not launched
 hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N, int split,
                             int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E, int ncu)
 {
-    const int NA = split, NB = N - split, nA = NA * sdim, nB = NB * sdim;
+    const int NB = N - split, nB = NB * sdim;
     {
-        const k_pair_fold_args a{A, ld, sign, XAg, T, NA, sdim, nA, nB, KA, a0, Ac};
-        const int rt = (nB + PROWS - 1) / PROWS;
-        // 128 sequences a workgroup -- or 16, where 128 would give fewer than two workgroups a compute unit
-        const bool wide = gdca_wide_instance(Ac, 4 * PAU_WIDE, rt, ncu);
-        const int per = 4 * (wide ? PAU_WIDE : PAU_NARROW);
-        const size_t lds = (size_t)PT * (sdim + 1) * PROWS * sizeof(double);
-        void (*kern)(k_pair_fold_args) = wide ? k_pair_fold<PAU_WIDE> : k_pair_fold<PAU_NARROW>;
-        const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
+        const hipError_t e = launch_pair_fold(s, A, ld, sign, XAg, split, NB, sdim, KA, a0, Ac, T, ncu);
         if (e != hipSuccess) return e;
-        GDCA_LAUNCH_DIRECT(kern, dim3(rt, (Ac + per - 1) / per), dim3(256), lds, s, a);
     }
     {
-        int SB = (PSEG_ROWS / sdim) & ~(PT - 1);  // sites per segment: whole dwords of XBg (s <= 30: at least 32)
-        if (SB > ((NB + PT - 1) & ~(PT - 1))) SB = (NB + PT - 1) & ~(PT - 1);
+        const int SB = pair_segment_sites(NB, sdim);
         const size_t lds = ((size_t)SB * sdim + 1) * PGA * sizeof(double);
         const int ga = (Ac + PGA - 1) / PGA;
         const bool wide = gdca_wide_instance(KB, 256 * PBU_WIDE, ga, ncu);
@@ -245,6 +327,56 @@ hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, dou
             const k_pair_gather_args a{T, XBg, EAB, c0, E, NB, sdim, nB, SB, KA, KB, a0, Ac, (int)b0};
             GDCA_LAUNCH_DIRECT(kern, dim3(ga, (unsigned)((kb + per - 1) / per)), dim3(256), lds, s, a);
         }
+    }
+    return hipSuccess;
+}
+
+// The work list of the blocked gather for species-sorted sequences (offA / offB: S + 1 valid offsets): items (species, first a, first b,
+// na | nb << 8) of up to PGA sequences a and PGB sequences b of one species, a ascending; a group of a never crosses a multiple of
+// `Ac` (the chunks of T).  first[c] = the first item of chunk c, c = 0 .. ceil(KA / Ac) (the last entry: all).  Empty sides give none.
+void gdca_pair_block_items(const int32_t *offA, const int32_t *offB, int S, int Ac, std::vector<int32_t> &items, std::vector<long long> &first)
+{
+    items.clear();
+    first.assign(1, 0);
+    const int KA = offA[S];
+    int s = 0;
+    for (int c0 = 0; c0 < KA; c0 += Ac) {
+        const int c1 = KA - c0 < Ac ? KA : c0 + Ac;
+        while (s < S && offA[s + 1] <= c0) ++s;
+        for (int sp = s; sp < S && offA[sp] < c1; ++sp) {
+            const int lo = offA[sp] > c0 ? offA[sp] : c0, hi = offA[sp + 1] < c1 ? offA[sp + 1] : c1;
+            if (offB[sp + 1] == offB[sp]) continue;
+            for (int a = lo; a < hi; a += PGA)
+                for (int b = offB[sp]; b < offB[sp + 1]; b += PGB) {
+                    const int na = hi - a < PGA ? hi - a : PGA, nb = offB[sp + 1] - b < PGB ? offB[sp + 1] - b : PGB;
+                    const int32_t it[4] = {sp, a, b, na | nb << 8};
+                    items.insert(items.end(), it, it + 4);
+                }
+        }
+        first.push_back((long long)(items.size() / 4));
+    }
+}
+
+// The blocks of E of the species whose sequences a lie in a0 .. a0 + Ac - 1, from `nitems` work items of that chunk (device; eoff,
+// offA, offB: the species table on the device).  The fold is gdca_launch_pair_chunk's own.
+hipError_t gdca_launch_pair_chunk_blocked(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N,
+                                          int split, int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0,
+                                          double *E, const int32_t *items, long long nitems, const long long *eoff, const int32_t *offA,
+                                          const int32_t *offB, int ncu)
+{
+    const int NB = N - split, nB = NB * sdim;
+    if (nitems == 0) return hipSuccess;  // (no pairing of these sequences a is wanted: their rows need not be folded)
+    const hipError_t e = launch_pair_fold(s, A, ld, sign, XAg, split, NB, sdim, KA, a0, Ac, T, ncu);
+    if (e != hipSuccess) return e;
+    const int SB = pair_segment_sites(NB, sdim);
+    const size_t lds = ((size_t)SB * sdim + 1) * PGA * sizeof(double);
+    const hipError_t e2 = gdca_raise_lds_limit(reinterpret_cast<const void *>(k_pair_gather_blocked), lds);
+    if (e2 != hipSuccess) return e2;
+    const long long maxi = 1 << 30;  // items one launch's grid covers
+    for (long long i0 = 0; i0 < nitems; i0 += maxi) {
+        const long long ni = nitems - i0 < maxi ? nitems - i0 : maxi;
+        const k_pair_gather_blocked_args a{T, XBg, EAB, c0, E, reinterpret_cast<const int4 *>(items) + i0, eoff, offA, offB, NB, sdim, nB, SB, KA, KB, a0};
+        GDCA_LAUNCH_DIRECT(k_pair_gather_blocked, dim3((unsigned)ni), dim3(256), lds, s, a);
     }
     return hipSuccess;
 }

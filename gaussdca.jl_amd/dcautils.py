@@ -389,6 +389,91 @@ def pair_energies(mJ, Pi, XA, XB, q: int = 21, what="energy", ctx=None) -> np.nd
     return E
 
 
+def species_blocks(labels_a, labels_b):
+    """Sequences grouped by species, as the blocked entry points take them.  ``labels_a`` / ``labels_b``: one integer label per
+    sequence of A / of B.  Returns ``(perm_a, perm_b, offA, offB, labels)``: ``labels`` the sorted union of both sides' labels
+    (species s = labels[s]); ``perm_a`` the stable order that sorts A's sequences by species (``XA[:, perm_a]`` is species-sorted, and
+    inside a species the caller's order is kept), likewise ``perm_b``; ``offA`` / ``offB`` int32 offsets of S + 1 entries: species s
+    owns the sorted sequences offA[s] .. offA[s + 1] - 1 (none, where a label occurs on the other side only).  Pure numpy."""
+    la, lb = np.asarray(labels_a), np.asarray(labels_b)
+    for lab in (la, lb):
+        if lab.ndim != 1 or (lab.size and not np.issubdtype(lab.dtype, np.integer)):
+            raise ArgumentError("species labels must be a vector of integers, one per sequence")
+    la, lb = la.astype(np.int64), lb.astype(np.int64)
+    labels = np.union1d(la, lb)
+    if labels.size < 1:
+        raise ArgumentError("species labels hold no sequence")
+    perm_a, perm_b = np.argsort(la, kind="stable"), np.argsort(lb, kind="stable")
+    offA = np.concatenate(([0], np.searchsorted(la[perm_a], labels, side="right"))).astype(np.int32)
+    offB = np.concatenate(([0], np.searchsorted(lb[perm_b], labels, side="right"))).astype(np.int32)
+    return perm_a, perm_b, offA, offB, labels
+
+
+def _block_views(E, offA, offB):
+    """the per-species kA_s x kB_s matrices of a packed blocked array, as views of it"""
+    out, at = [], 0
+    for ka, kb in zip(np.diff(offA).tolist(), np.diff(offB).tolist()):
+        out.append(E[at:at + ka * kb].reshape((ka, kb), order="F"))
+        at += ka * kb
+    return out
+
+
+def pair_energies_blocked(mJ, Pi, XA, XB, species_a, species_b, q: int = 21, what="energy", ctx=None) -> list:
+    """``pair_energies`` for partner matching per species: only the pairings of sequences of A and of B that carry the same species
+    label are computed, in one pass (``species_a`` / ``species_b``: one integer label per column of XA / XB, in any order).  Returns a
+    list of matrices, one per species in ascending order of the labels (``species_blocks(species_a, species_b)[4]``): entry s is the
+    (kA_s, kB_s) matrix of that species' pairings, rows and columns in the caller's order of its sequences, a view of one packed
+    array.  Every entry is bit for bit the entry ``pair_energies`` gives that pairing."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    w = _what_arg(what)
+    Pi = None if (Pi is None and w == _lib.PAIR_COUPLING) else np.ascontiguousarray(Pi, dtype=np.float64)
+    XAf, XBf = _symbols(XA, "XA"), _symbols(XB, "XB")
+    split, KA = XAf.shape
+    NB, KB = XBf.shape
+    N = split + NB
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = N * (int(q) - 1)
+    if split < 1 or NB < 1 or mJ.shape != (n, n) or (Pi is not None and Pi.shape != (n,)):
+        raise ArgumentError(f"incompatible sizes: XA has {split} sites and XB {NB}, q = {q}, so mJ must be {n} x {n} and Pi have {n} "
+                            f"entries (got {mJ.shape} and {None if Pi is None else Pi.shape})")
+    if KA < 1 or KB < 1:
+        raise ArgumentError("XA or XB holds no sequence")
+    perm_a, perm_b, offA, offB, _ = species_blocks(species_a, species_b)
+    if len(perm_a) != KA or len(perm_b) != KB:
+        raise ArgumentError(f"species_a / species_b have {len(perm_a)} / {len(perm_b)} labels, XA / XB hold {KA} / {KB} sequences")
+    XAs, XBs = np.asfortranarray(XAf[:, perm_a]), np.asfortranarray(XBf[:, perm_b])
+    ctx = ctx or default_context()
+    E = np.empty(int(np.sum(np.diff(offA).astype(np.int64) * np.diff(offB))), dtype=np.float64)
+    ctx.check(ctx.lib.gdca_pair_energies_blocked(ctx.h, _lib._p(mJ), _lib._p(Pi) if Pi is not None else None, N, int(q), split, _lib._p(XAs),
+                                                 KA, _lib._p(XBs), KB, _lib._p(offA), _lib._p(offB), len(offA) - 1, w, _lib._p(E)))
+    return _block_views(E, offA, offB)
+
+
+def assign_blocks(blocks, ctx=None):
+    """The minimum-cost one-to-one assignment inside every matrix of ``blocks`` (a list of (kA_s, kB_s) float64 cost matrices: what
+    ``pair_energies_blocked`` returns, or any costs), on the device: min(kA_s, kB_s) pairs a species.  Returns ``(match, gap)``, two
+    lists with one vector of kA_s entries per species: ``match[s][a]`` the column matched to row a (-1: unmatched), ``gap[s][a]`` the
+    least other entry of row a minus the matched one (+inf with one column, 0.0 unmatched, negative where the assignment overrode
+    the row's own minimum).  No side may exceed 512."""
+    mats = [np.asarray(b, dtype=np.float64) for b in blocks]
+    if not mats or any(m.ndim != 2 for m in mats):
+        raise ArgumentError("blocks must be a non-empty list of matrices")
+    offA = np.concatenate(([0], np.cumsum([m.shape[0] for m in mats]))).astype(np.int32)
+    offB = np.concatenate(([0], np.cumsum([m.shape[1] for m in mats]))).astype(np.int32)
+    E = np.concatenate([m.ravel(order="F") for m in mats]) if mats else np.empty(0)
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    KA = int(offA[-1])
+    match, gap = np.empty(KA, dtype=np.int32), np.empty(KA, dtype=np.float64)
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.gdca_assign_blocks(ctx.h, _lib._p(E), _lib._p(offA), _lib._p(offB), len(mats), _lib._p(match), _lib._p(gap)))
+    local = np.where(match >= 0, match - np.repeat(offB[:-1], np.diff(offA)), -1).astype(np.int32)
+    cut = offA[1:-1]
+    return np.split(local, cut), np.split(gap, cut)
+
+
 def _mut_what_arg(what) -> int:
     w = str(what).lstrip(":")
     if w == "delta":

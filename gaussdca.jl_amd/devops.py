@@ -99,6 +99,27 @@ def pair_energies_dev(ctx: Context, dmJ, dPi, N: int, q: int, split: int, dXA, K
     return dE
 
 
+def pair_energies_blocked_dev(ctx: Context, dmJ, dPi, N: int, q: int, split: int, dXA, KA: int, dXB, KB: int, offA, offB, what: int = 1,
+                              dE=None):
+    """The pairings inside the species of species-sorted sequences with every array in HBM (gdca_pair_energies_blocked_dev): offA /
+    offB are HOST offsets (S + 1 each, dcautils.species_blocks); E is packed, block s column-major kA_s x kB_s behind the blocks
+    before it (_lib.pair_blocks_length(offA, offB) doubles); every entry bit for bit pair_energies_dev's"""
+    dE = dE or DeviceBuffer(ctx, 8 * max(_lib.pair_blocks_length(offA, offB), 1))
+    ctx.pair_energies_blocked_dev(_ptr(dmJ).value, None if dPi is None else _ptr(dPi).value, N, int(q), int(split), _ptr(dXA).value, int(KA),
+                                  _ptr(dXB).value, int(KB), offA, offB, int(what), _ptr(dE).value)
+    return dE
+
+
+def assign_blocks_dev(ctx: Context, dE, offA, offB, dmatch=None, dgap=None):
+    """The minimum-cost assignment inside every block of the packed cost matrix E with every array in HBM (gdca_assign_blocks_dev):
+    returns (match int32[KA], gap float64[KA]) as device buffers"""
+    KA = int(np.asarray(offA)[-1])
+    dmatch = dmatch or DeviceBuffer(ctx, 4 * KA)
+    dgap = dgap or DeviceBuffer(ctx, 8 * KA)
+    ctx.assign_blocks_dev(_ptr(dE).value, offA, offB, _ptr(dmatch).value, _ptr(dgap).value)
+    return dmatch, dgap
+
+
 def mutation_scan_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, what: int = 0, dD=None):
     """D[(b - 1) + q (i + N k)] of every single substitution of the K sequences X (N x K int8) with every array in HBM
     (gdca_mutation_scan_dev): what = _lib.MUT_DELTA (the energy change) or _lib.MUT_POTENTIAL (the site potentials)"""

@@ -5,6 +5,7 @@ and compute_ranking (:44) is one call into libgdca.so (gdca_run_ranked): Z goes 
 the sorted ranking comes back; text output stays on the host as in the reference."""
 from __future__ import annotations
 
+import ctypes as C
 import os
 from typing import List, Tuple
 
@@ -12,8 +13,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, default_context
-from .dcautils import (FastaAlignment, Ranking, _mut_what_arg, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
-                       remove_duplicate_sequences)
+from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
+                       remove_duplicate_sequences, species_blocks)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
 last_multi_stats = None  # gDCA_multi: one stats dict per setting of its most recent call, in the order of the settings
@@ -193,6 +194,66 @@ def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what
                            lambda c, ptr, N, M, q: c.run_pair_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split),
                                                                            *_ptr_count(XA), *_ptr_count(XB), w),
                            "energies")
+
+
+def gDCA_partner_match(filename: str, split: int, seqs_a=None, seqs_b=None, species_a=None, species_b=None, what="energy",
+                       pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None,
+                       return_blocks: bool = False, **kw):
+    """Partner matching per species under the Gaussian model gDCA fits to ``filename`` (an alignment of concatenated pairs A (+) B,
+    the first ``split`` sites protein A; the fit is ``gDCA_pair_energies``'): inside every species the sequences of A are matched one
+    to one with those of B at minimum total energy (``what="coupling"``: total coupling) -- min(kA_s, kB_s) pairs a species, on the
+    device, only the within-species pairings are ever computed.
+
+    ``seqs_a`` / ``seqs_b`` as for ``gDCA_pair_energies``; ``species_a`` / ``species_b``: one integer label per sequence of that
+    side, in any order.  ``None`` sequences take that half of the alignment's own sequences: the labels then go with the sequences
+    the reader keeps (``max_gap_fraction = 1.0`` keeps every record).  Returns ``(match, gap)`` in the caller's order: ``match[a]``
+    the index into ``seqs_b`` of a's partner, or -1 (its species has fewer sequences of B); ``gap[a]`` the least other energy of a
+    with a sequence of B of its species minus the matched one (+inf: the only candidate; 0.0: unmatched; negative: the assignment
+    overrode a's own best).  ``return_blocks=True`` adds the list of per-species energy matrices (``pair_energies_blocked``' form).
+    At most 512 sequences a side in one species.  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_partner_match() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    w = _what_arg(what)
+    XA, XB = _sequences_arg(seqs_a, "seqs_a", "a sites x K"), _sequences_arg(seqs_b, "seqs_b", "a sites x K")
+    if species_a is None or species_b is None:
+        raise ArgumentError("species_a and species_b are needed: one integer label per sequence")
+    perm_a, perm_b, offA, offB, _ = species_blocks(species_a, species_b)
+
+    def check(N):
+        if not isinstance(split, (int, np.integer)) or not 1 <= split <= N - 1:
+            raise ArgumentError(f"invalid split value: {split} (must be between 1 and N - 1 = {N - 1})")
+        if XA is not None and XA.shape[0] != split:
+            raise ArgumentError(f"seqs_a have {XA.shape[0]} sites, protein A has {split}")
+        if XB is not None and XB.shape[0] != N - split:
+            raise ArgumentError(f"seqs_b have {XB.shape[0]} sites, protein B has {N - split}")
+        if (XA is not None and XA.shape[1] < 1) or (XB is not None and XB.shape[1] < 1):
+            raise ArgumentError("seqs_a or seqs_b holds no sequence")
+
+    def run(c, ptr, N, M, q):
+        def half(X, perm, lo, hi, name):
+            """that side's sequences sorted by species; None: the alignment's own already are"""
+            count = M if X is None else X.shape[1]
+            if len(perm) != count:
+                raise ArgumentError(f"{name} has {len(perm)} labels for {count} sequences")
+            if X is not None:
+                return np.asfortranarray(X[:, perm])
+            if np.array_equal(perm, np.arange(M)):
+                return None
+            Z = np.ctypeslib.as_array(C.cast(C.c_void_p(ptr), C.POINTER(C.c_int8)), shape=(M, N))  # (row k = sequence k)
+            return np.asfortranarray(Z[perm, lo:hi].T)
+
+        XAs, XBs = half(XA, perm_a, 0, int(split), "species_a"), half(XB, perm_b, int(split), N, "species_b")
+        (E, m, g), st = c.run_partner_match_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split), *_ptr_count(XAs),
+                                                *_ptr_count(XBs), offA, offB, w, want_blocks=return_blocks)
+        match, gap = np.empty_like(m), np.empty_like(g)
+        match[perm_a] = np.where(m >= 0, perm_b[np.maximum(m, 0)], -1)
+        gap[perm_a] = g
+        return ((match, gap, _block_views(E, offA, offB)) if return_blocks else (match, gap)), st
+
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, check, run, "matches")
 
 
 def gDCA_mutation_scan(filename: str, sequences=None, what="delta", pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,

@@ -344,6 +344,48 @@ gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                                        int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what,
                                        double *E_dev, gdca_stats *st);
 
+/* ---- partner matching per species: blocked pair energies and the assignment ---------------------------------------------------
+ * A matching problem has many species with a handful of paralogs each: wanted are the pairings WITHIN a species, sum_s kA_s kB_s
+ * entries, not K_A K_B.  The sequences of XA and of XB are SORTED BY SPECIES: species s = 0 .. S - 1 owns sequences offA[s] ..
+ * offA[s + 1] - 1 of XA and offB[s] .. offB[s + 1] - 1 of XB.  offA and offB are HOST arrays of S + 1 int32 in every form (declared
+ * const void * in the entry points), non-decreasing, offA[0] = offB[0] = 0, offA[S] = K_A, offB[S] = K_B; a species may be empty on
+ * either side; S >= 1.  A violation is GDCA_EINVAL with nothing run.
+ * The blocked matrix is packed: block s starts at eoff[s] = sum_{t < s} kA_t kB_t (64-bit) and is column-major kA_s x kB_s:
+ *     E[eoff[s] + (a - offA[s]) + kA_s (b - offB[s])].
+ * gdca_pair_blocks_length returns eoff[S], the doubles the packed matrix holds, or -1 for invalid offsets.
+ *
+ * gdca_pair_energies_blocked(_dev): `what` and every argument rule as gdca_pair_energies_dev (a bad symbol is detected on the
+ * device).  EVERY ENTRY IS BIT FOR BIT the entry E[a + K_A b] gdca_pair_energies_dev writes for the same model, a, b, split and
+ * `what`: the folded rows T[a][row] are summed over the A sites ascending by one thread, then gathered over the B sites ascending by
+ * one thread, segments in ascending order, no floating-point atomics -- the fold, the pack, the pad and the marginal energies are the
+ * full form's own; only the gather differs, spreading its lanes over the pairings of one species.  No limit on a species' size.
+ *
+ * gdca_assign_blocks(_dev): the minimum-cost one-to-one assignment inside every block of ANY blocked f64 cost matrix (energies or
+ * couplings): per species min(kA_s, kB_s) pairs, shortest augmenting paths (Jonker-Volgenant) in f64, one workgroup a species.
+ *     match[a] (int32, K_A entries)  the global index b of a's partner; -1 if a is unmatched (kA_s > kB_s, or kB_s = 0);
+ *     gap[a]   (f64, K_A entries; may be NULL)  min_{b' != match(a)} E[a, b'] - E[a, match(a)], b' inside the species: ONE f64
+ *              subtraction of two entries of E; +inf where kB_s = 1; +0.0 for an unmatched a; negative where the assignment
+ *              overrode the row's own minimum.
+ * Among optima of equal cost which one comes back is unspecified, but fixed for given input bits: run to run, and whatever other
+ * species share the call.  Costs are meant to be finite: a species whose search runs out of finite entries (NaNs, infinities) comes
+ * back unmatched as a whole (-1, +0.0).  GDCA_ASSIGN_MAX is the largest
+ * kA_s or kB_s the assignment accepts: a larger species is GDCA_EINVAL with nothing run.  Synchronous. */
+#define GDCA_ASSIGN_MAX 512
+int64_t gdca_pair_blocks_length(const int32_t *offA, const int32_t *offB, int32_t S);
+gdca_status gdca_pair_energies_blocked_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, int32_t split,
+                                           const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA,
+                                           const void *offB, int32_t S, int32_t what, double *E_dev);
+gdca_status gdca_assign_blocks_dev(gdca_ctx *ctx, const double *E_dev, const void *offA, const void *offB, int32_t S, int32_t *match_dev,
+                                   double *gap_dev);
+/* Fused: fits the model on Z exactly as gdca_run_pair_energies_dev does (the same code, the same conditioning screen), then the
+ * blocked pair stage and the assignment on it.  XA == NULL or XB == NULL takes that half of Z's own sequences (the count is then M
+ * and the offsets index Z).  E_dev == NULL keeps the blocked matrix in a grow-only buffer of the context.  Stats as
+ * gdca_run_pair_energies: ms_score is the blocked pair stage plus the assignment. */
+gdca_status gdca_run_partner_match_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                       int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB,
+                                       const void *offA, const void *offB, int32_t S, int32_t what, double *E_dev, int32_t *match_dev,
+                                       double *gap_dev, gdca_stats *st);
+
 /* ---- mutation scan: the energy change of every single substitution ---------------------------------------------------------
  * The mutational landscape of a sequence under the model (what is compared with deep mutational scans).  Conventions as for the
  * energies above: s = q - 1, n = N s, r(i, c) = i s + c - 1 for symbol c in 1..s at 0-based site i, the gap q has no row, Pi is
@@ -417,6 +459,17 @@ gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi
 gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                    int32_t split, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, int32_t what,
                                    double *E_host, gdca_stats *st);
+
+/* partner matching with host pointers: upload, the _dev form, download (E_host of gdca_run_partner_match may be NULL: only the
+ * matching comes back) */
+gdca_status gdca_pair_energies_blocked(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split,
+                                       const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, const void *offA, const void *offB,
+                                       int32_t S, int32_t what, double *E);
+gdca_status gdca_assign_blocks(gdca_ctx *ctx, const double *E, const void *offA, const void *offB, int32_t S, int32_t *match, double *gap);
+gdca_status gdca_run_partner_match(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                   int32_t split, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA,
+                                   const void *offB, int32_t S, int32_t what, double *E_host, int32_t *match_host, double *gap_host,
+                                   gdca_stats *st);
 
 /* mutation scan with host pointers: upload, the _dev form, download */
 gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,

@@ -15,7 +15,8 @@
 module GaussDCAHip
 
 export gDCA, gDCA_stepwise, printrank, compute_weights, compute_weighted_frequencies, add_pseudocount,
-       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, pair_energies, mutation_scan, gDCA_mutation_scan
+       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, pair_energies, mutation_scan, gDCA_mutation_scan,
+       species_blocks, pair_energies_blocked_dev, assign_blocks_dev, run_partner_match_dev, gDCA_partner_match
 
 using LinearAlgebra
 import DCAUtils                                   # host-side I/O only: read_fasta_alignment, remove_duplicate_sequences
@@ -197,6 +198,101 @@ function pair_energies(mJ::Matrix{Float64}, Pi::Union{Vector{Float64}, Nothing},
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ptr{Int8}, Int32, Ptr{Int8}, Int32, Int32, Ptr{Float64}),
         ctx(), mJ, Pp, N, q, split, XA, KA, XB, KB, what == :energy ? 1 : 0, E))
     return E
+end
+
+# ---- partner matching per species (include/gdca.h, "partner matching per species") ----
+# Sequences grouped by species: (perm_a, perm_b, offA, offB, labels) -- labels the sorted union of both sides' integer labels, perm_* the
+# stable orders that sort each side by species (1-based), offA / offB the 0-based Int32 offsets (S + 1 each) the library takes
+function species_blocks(labels_a::AbstractVector{<:Integer}, labels_b::AbstractVector{<:Integer})
+    labels = sort(union(labels_a, labels_b))
+    isempty(labels) && throw(ArgumentError("species labels hold no sequence"))
+    perm_a = sortperm(labels_a; alg = MergeSort); perm_b = sortperm(labels_b; alg = MergeSort)
+    offs(l) = Int32[0; [count(<=(s), l) for s in labels]]
+    return perm_a, perm_b, offs(labels_a), offs(labels_b), labels
+end
+
+# device pointers (Ptr{Cvoid} into HBM) for the model, the species-sorted sequences and the packed result; offA / offB on the host
+function pair_energies_blocked_dev(mJ::Ptr{Cvoid}, Pi::Ptr{Cvoid}, N::Integer, q::Integer, split::Integer, XA::Ptr{Cvoid}, KA::Integer,
+                                   XB::Ptr{Cvoid}, KB::Integer, offA::Vector{Int32}, offB::Vector{Int32}, what::Symbol, E::Ptr{Cvoid})
+    what in (:energy, :coupling) || throw(ArgumentError("invalid what value: $what (must be either :energy or :coupling)"))
+    length(offA) == length(offB) || throw(ArgumentError("offA and offB must have S + 1 entries each"))
+    GC.@preserve offA offB check(ccall((:gdca_pair_energies_blocked_dev, libgdca), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32,
+         Ptr{Cvoid}),
+        ctx(), mJ, Pi, N, q, split, XA, KA, XB, KB, pointer(offA), pointer(offB), length(offA) - 1, what == :energy ? 1 : 0, E))
+    return E
+end
+
+# the minimum-cost assignment inside every block of a packed cost matrix in HBM: match (Int32, offA[end] entries) and gap (Float64, or
+# C_NULL) are device pointers
+function assign_blocks_dev(E::Ptr{Cvoid}, offA::Vector{Int32}, offB::Vector{Int32}, match::Ptr{Cvoid}, gap::Ptr{Cvoid} = C_NULL)
+    length(offA) == length(offB) || throw(ArgumentError("offA and offB must have S + 1 entries each"))
+    GC.@preserve offA offB check(ccall((:gdca_assign_blocks_dev, libgdca), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+        ctx(), E, pointer(offA), pointer(offB), length(offA) - 1, match, gap))
+    return match, gap
+end
+
+# the fused form on device pointers: Z (N x M), the species-sorted XA / XB (C_NULL: that half of Z's own sequences), E (C_NULL: kept
+# inside the context), match and gap in HBM.  Returns the stats.
+function run_partner_match_dev(Z::Ptr{Cvoid}, N::Integer, M::Integer, q::Integer, pseudocount::Real, θ, split::Integer, XA::Ptr{Cvoid},
+                               KA::Integer, XB::Ptr{Cvoid}, KB::Integer, offA::Vector{Int32}, offB::Vector{Int32}, what::Symbol,
+                               E::Ptr{Cvoid}, match::Ptr{Cvoid}, gap::Ptr{Cvoid})
+    what in (:energy, :coupling) || throw(ArgumentError("invalid what value: $what (must be either :energy or :coupling)"))
+    length(offA) == length(offB) || throw(ArgumentError("offA and offB must have S + 1 entries each"))
+    p = Ref(GdcaParams(Float64(pseudocount), theta_arg(θ), 0, 0))
+    st = GdcaStats()
+    GC.@preserve offA offB begin
+        rc = ccall((:gdca_run_partner_match_dev, libgdca), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, Ref{GdcaParams}, Int32, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Ptr{Cvoid},
+                    Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{GdcaStats}),
+                   ctx(), Z, N, M, q, p, split, XA, KA, XB, KB, pointer(offA), pointer(offB), length(offA) - 1, what == :energy ? 1 : 0,
+                   E, match, gap, st)
+    end
+    check(rc, st.info)
+    return st
+end
+
+# gDCA's fit, then inside every species the one-to-one matching of the sequences of A (split x K_A) with those of B ((N - split) x K_B)
+# at minimum total energy.  species_a / species_b: one integer label per sequence, in any order.  Returns (match, gap) in the caller's
+# order: match[a] the 1-based column of seqs_b matched to a (0: unmatched), gap[a] the least other energy of a inside its species
+# minus the matched one.
+function gDCA_partner_match(filename::AbstractString, split::Integer, seqs_a::Matrix{Int8}, seqs_b::Matrix{Int8},
+                            species_a::AbstractVector{<:Integer}, species_b::AbstractVector{<:Integer}; what::Symbol = :energy,
+                            pseudocount::Real = 0.8, θ = :auto, max_gap_fraction::Real = 0.9, remove_dups::Bool = false)
+    check_arguments(filename, pseudocount, θ, max_gap_fraction, :frob, 1)
+    what in (:energy, :coupling) || throw(ArgumentError("invalid what value: $what (must be either :energy or :coupling)"))
+    Z = DCAUtils.read_fasta_alignment(filename, max_gap_fraction)
+    if remove_dups
+        Z, _ = DCAUtils.remove_duplicate_sequences(Z)
+    end
+    q = Int(maximum(Z))
+    q ≥ 32 && error("parameter q=$q is too big (max 31 is allowed)")
+    N, M = size(Z)
+    1 ≤ split ≤ N - 1 || throw(ArgumentError("invalid split value: $split (must be between 1 and N - 1 = $(N - 1))"))
+    (size(seqs_a, 1) == split && size(seqs_b, 1) == N - split) || throw(ArgumentError("seqs_a / seqs_b do not have the sites of protein A / B"))
+    KA = size(seqs_a, 2); KB = size(seqs_b, 2)
+    (length(species_a) == KA && length(species_b) == KB) || throw(ArgumentError("one species label per sequence is needed"))
+    perm_a, perm_b, offA, offB, _ = species_blocks(species_a, species_b)
+    XA = seqs_a[:, perm_a]; XB = seqs_b[:, perm_b]
+    m = Vector{Int32}(undef, KA); g = Vector{Float64}(undef, KA)
+    p = Ref(GdcaParams(Float64(pseudocount), theta_arg(θ), 0, 0))
+    st = GdcaStats()
+    GC.@preserve Z XA XB offA offB m g begin
+        rc = ccall((:gdca_run_partner_match, libgdca), Cint,
+                   (Ptr{Cvoid}, Ptr{Int8}, Int32, Int32, Int32, Ref{GdcaParams}, Int32, Ptr{Int8}, Int32, Ptr{Int8}, Int32, Ptr{Cvoid},
+                    Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ref{GdcaStats}),
+                   ctx(), Z, N, M, q, p, split, XA, KA, XB, KB, pointer(offA), pointer(offB), length(offA) - 1, what == :energy ? 1 : 0,
+                   Ptr{Float64}(C_NULL), m, g, st)
+    end
+    check(rc, st.info)
+    st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: matches are unreliable" pseudocount
+    match = Vector{Int}(undef, KA); gap = Vector{Float64}(undef, KA)
+    for i in 1:KA
+        match[perm_a[i]] = m[i] < 0 ? 0 : perm_b[m[i] + 1]
+        gap[perm_a[i]] = g[i]
+    end
+    return match, gap
 end
 
 # gDCA's fit (same keywords, minus score and min_separation), then the energies of `sequences` under it: nothing = the alignment's
