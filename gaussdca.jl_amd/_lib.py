@@ -162,6 +162,13 @@ SYMBOLS = {
                                         C.c_void_p, C.POINTER(Stats)]),
     "gdca_run_energies": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
                                     C.c_void_p, C.POINTER(Stats)]),
+    "gdca_last_logdet": (C.c_int, [_ctx, C.c_int32, _f64p, _i32p]),
+    "gdca_spd_inverse_logdet_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _i32p, _f64p]),
+    "gdca_spd_inverse_logdet": (C.c_int, [_ctx, C.c_void_p, C.c_int32, _i32p, _f64p]),
+    "gdca_run_loglik_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                      C.c_void_p, _f64p, C.POINTER(Stats)]),
+    "gdca_run_loglik": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                  C.c_void_p, _f64p, C.POINTER(Stats)]),
     "gdca_pair_energies_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_pair_energies": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
@@ -368,6 +375,57 @@ class Context:
         """Device-pointer form (Z, X and E resident in HBM).  Returns the stats dict."""
         return self._run_readout(self.lib.gdca_run_energies_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
                                  C.c_void_p(E_ptr))
+
+    # ---- log-likelihoods: log det C from the pivots of the inverse (include/gdca.h, "log-likelihoods") ----
+    def last_logdet(self, k: int = 0, return_source: bool = False):
+        """log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet); k: the member index after
+        run_multi.  NaN where that inverse was not positive definite.  return_source: (logdet, source), source 0 = the sweep's
+        pivots, 1 = the Cholesky fallback's diagonal."""
+        v = C.c_double(float("nan"))
+        src = C.c_int32(0)
+        self.check(self.lib.gdca_last_logdet(self.h, int(k), C.byref(v), C.byref(src)))
+        return (v.value, src.value) if return_source else v.value
+
+    def spd_inverse_logdet(self, A: np.ndarray):
+        """gdca_spd_inverse_logdet on a host matrix (n x n float64; symmetric, so either memory order): returns (inverse, logdet).
+        PosDefException as spd_inverse raises it."""
+        A = np.array(A, dtype=np.float64, order="F")
+        n = A.shape[0]
+        info = C.c_int32(0)
+        v = C.c_double(float("nan"))
+        self.check(self.lib.gdca_spd_inverse_logdet(self.h, _p(A), int(n), C.byref(info), C.byref(v)), info.value)
+        return A, v.value
+
+    def spd_inverse_logdet_dev(self, A_ptr: int, n: int) -> float:
+        """Device-pointer form: A (n x n, ld n) is inverted in place; returns logdet."""
+        info = C.c_int32(0)
+        v = C.c_double(float("nan"))
+        self.check(self.lib.gdca_spd_inverse_logdet_dev(self.h, C.c_void_p(A_ptr), int(n), C.byref(info), C.byref(v)), info.value)
+        return v.value
+
+    def run_loglik_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None, K: int = 0):
+        """gdca_run_loglik on HOST matrices given by address (as run_energies_ptr): log p(x) = -E(x) - 1/2 (n log 2 pi + log det C)
+        of the K sequences X (None: Z's own M).  Returns (L float64[K], logdet, stats)."""
+        Ke = int(K) if X_ptr is not None else int(M)
+        L = np.empty(max(Ke, 0), dtype=np.float64)
+        v = C.c_double(float("nan"))
+        st = self._run_readout(self.lib.gdca_run_loglik, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), _p(L), C.byref(v))
+        return L, v.value, st
+
+    def run_loglik(self, Zf: np.ndarray, q: int, pseudocount: float, theta: float, X: np.ndarray | None = None):
+        """run_loglik_ptr on arrays: Zf int8 (N, M) Fortran-contiguous, X int8 (N, K) likewise or None."""
+        N, M = Zf.shape
+        if X is None:
+            return self.run_loglik_ptr(Zf.ctypes.data, N, M, q, pseudocount, theta)
+        X = np.asfortranarray(X, dtype=np.int8)
+        return self.run_loglik_ptr(Zf.ctypes.data, N, M, q, pseudocount, theta, X.ctypes.data, X.shape[1])
+
+    def run_loglik_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int, L_ptr: int):
+        """Device-pointer form (Z, X and L resident in HBM).  Returns (logdet, stats)."""
+        v = C.c_double(float("nan"))
+        st = self._run_readout(self.lib.gdca_run_loglik_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                               C.c_void_p(L_ptr), C.byref(v))
+        return v.value, st
 
     def energies_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int, K: int, E_ptr: int) -> None:
         """gdca_energies_dev: mJ (n x n), Pi (n), X (N x K int8) and E (K) are device pointers."""

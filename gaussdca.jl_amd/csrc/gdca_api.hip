@@ -35,7 +35,8 @@ struct gdca_gate {
 
 // What the score stage of a run computes, handed to score_stage by whoever calls it: the contact score (FN or DI, with or without
 // APC), or -- the fused energy entries -- the model scored on sequences X, on the pairings across a split, or scanned for every single
-// substitution of sequences X.  The enqueued run keeps
+// substitution of sequences X; LOGLIK is the energy target whose E the collect turns into log-likelihoods once the run's log det is on
+// the host (loglik_epilogue).  The enqueued run keeps
 // its own (gdca_pending::target): a second attempt, refinement or fallback at collect time scores the same thing again.
 // The species of a species-sorted pair problem as the blocked pair stage and the assignment take them (species_blocks makes it): the
 // species table and the gather's work list on the device (ctx->PBtab, ctx->PBitems), and what the host keeps of them.
@@ -49,7 +50,7 @@ struct pair_blocks {
 };
 
 struct score_target {
-    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION } kind;
+    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK } kind;
     double *out;                       // S (N x N), E (K), E (KA x KB), E (packed blocks) or D (q x N x K)
     int score, apc;                    // contact
     const int8_t *X;                   // energy (k_energy.hip) and mutation scan (k_mutation.hip, with `what`): N x K
@@ -81,6 +82,14 @@ static score_target energy_target(const int8_t *Z, int M, const int8_t *X, int K
     t.out = E_dev;
     t.X = X ? X : Z;
     t.K = X ? K : M;
+    return t;
+}
+
+// (the energies of the same sequences; what the collect makes of them: gdca_run_collect)
+static score_target loglik_target(const int8_t *Z, int M, const int8_t *X, int K, double *L_dev)
+{
+    score_target t = energy_target(Z, M, X, K, L_dev);
+    t.kind = score_target::LOGLIK;
     return t;
 }
 
@@ -185,6 +194,16 @@ struct gdca_ctx {
     // whose caller does not want it
     gdca_buf PBtab, PBitems, PBE;
     int ncu;                  // compute units of the device
+    double *piv;              // the pivots of the context's last inverse, n_pad doubles inside Sg (inverse_job)
+    // log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet): kept on the host, so that entry points
+    // without an inverse of their own (their begin() clears the device scalars) leave it alone.  count: 0 = none, K after gdca_run_multi;
+    // chol: the Cholesky fallback factored that matrix (its diagonal is what the pivot vector holds)
+    struct {
+        int count;
+        bool chol;
+        double val[GDCA_MULTI_MAX];
+        int src[GDCA_MULTI_MAX];
+    } ld;
     int *item0_host;           // pinned staging of the sweep's item table
     int item0_cap;
     gdca_buf scratch[N_SCRATCH];
@@ -902,7 +921,8 @@ static gdca_status inverse_job(gdca_ctx *ctx, int n, int n_pad, gdca_inverse_job
     CHK(ensure(ctx, ctx->G, (size_t)8 * pbytes));
     CHK(ensure(ctx, ctx->H, (size_t)8 * pbytes));
     CHK(ensure(ctx, ctx->P, (size_t)GDCA_TILE * GDCA_TILE * sizeof(double)));
-    CHK(ensure(ctx, ctx->Sg, 4 * sg + fbytes + (size_t)3 * (nblk + 2) * sizeof(int)));
+    const size_t piv_off = (4 * sg + fbytes + (size_t)3 * (nblk + 2) * sizeof(int) + 15) & ~(size_t)15;
+    CHK(ensure(ctx, ctx->Sg, piv_off + (size_t)n_pad * sizeof(double)));
     if (ctx->item0_cap < 3 * (nblk + 2)) {
         if (ctx->item0_host) HIPCHK(hipHostFree(ctx->item0_host));
         ctx->item0_host = nullptr;
@@ -924,6 +944,9 @@ static gdca_status inverse_job(gdca_ctx *ctx, int n, int n_pad, gdca_inverse_job
     ws.flags_bytes = fbytes;
     ws.item0_dev = (int *)((char *)ctx->Sg.p + 4 * sg + fbytes);
     ws.item0_host = ctx->item0_host;
+    ws.piv = ctx->piv = (double *)((char *)ctx->Sg.p + piv_off);
+    ctx->ld.count = 0;  // (an inverse is on its way: the last one's log det is history)
+    ctx->ld.chol = false;
     {
         void *dp = nullptr;
         ws.item0_host_dev = hipHostGetDevicePointer(&dp, ctx->item0_host, 0) == hipSuccess ? (const int *)dp : nullptr;
@@ -965,6 +988,23 @@ static gdca_status inverse_stage(gdca_ctx *ctx, int n, int n_pad, double *upd_fl
     }
     gdca_launch_spd_inverse(ctx->stream, job, sweep_begin, sweep_end, upd_flops);
     return check_launch(ctx, "spd_inverse");
+}
+
+// log det of the matrix just inverted into sc->logdet, from the pivots the sweep (or the Cholesky fallback) left in ctx->piv: one small
+// launch behind the inverse on its stream (k_logdet.hip)
+static gdca_status logdet_stage(gdca_ctx *ctx, int n)
+{
+    gdca_launch_logdet(ctx->stream, ctx->piv, n, (gdca_dev_scalars *)ctx->sc.p);
+    return check_launch(ctx, "logdet");
+}
+
+// ... and, the scalars fetched, kept as the context's last (member k of a gdca_run_multi call; everything else has one member)
+static void note_logdet(gdca_ctx *ctx, int k = 0)
+{
+    const gdca_dev_scalars &h = *ctx->sc_host;
+    ctx->ld.val[k] = h.info == 0 && !h.bad_symbol ? h.logdet : (double)NAN;
+    ctx->ld.src[k] = ctx->ld.chol ? 1 : 0;
+    ctx->ld.count = k + 1;
 }
 
 // What the energies and the mutation scan open with: the K sequences X (N x K) packed into ctx->Xg (illegal bytes: sc->bad_symbol
@@ -1059,7 +1099,8 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
     // the model as the sweep left it, for the fused read-outs: scored on t's sequences in the place of the contact score
     const gdca_model m{(const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1};
     switch (t.kind) {
-    case score_target::ENERGY: return energy_stage(ctx, m, t.X, t.K, t.out);
+    case score_target::ENERGY:
+    case score_target::LOGLIK: return energy_stage(ctx, m, t.X, t.K, t.out);
     case score_target::PAIR: return pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
     case score_target::PARTNER:
         CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out, &t.blocks));
@@ -1165,7 +1206,8 @@ static gdca_status cholesky_stage(gdca_ctx *ctx, int n, int n_pad)
     CHK(ensure(ctx, ctx->Wd, (size_t)(n_pad / GDCA_TILE) * GDCA_TILE * GDCA_TILE * sizeof(double)));
     HIPCHK(hipMemsetAsync(&sc->info, 0, sizeof(int), ctx->stream));
     gdca_launch_cholesky_inverse(ctx->stream, (double *)ctx->C2.p, (double *)ctx->B0.p, (double *)ctx->Rt.p, (double *)ctx->Wd.p, (double *)ctx->A.p,
-                                 n_pad, n, sc);
+                                 n_pad, n, sc, ctx->piv);
+    ctx->ld.chol = true;  // (the pivot vector now holds the factor's L_ii^2)
     return check_launch(ctx, "cholesky_inverse");
 }
 
@@ -1210,6 +1252,7 @@ static gdca_status marked_score_stage(gdca_ctx *ctx)
     r.ev_marks &= ~fn;
     r.stamp_marks &= ~fn;
     CHK(mark(ctx, T_SCORE_BEGIN));
+    CHK(logdet_stage(ctx, r.n));  // (of the inverse the stage reads: a second attempt's and the fallback's come through here again)
     CHK(score_stage(ctx, r.N, r.q - 1, r.n_pad, r.target));
     return mark(ctx, T_END);
 }
@@ -1221,7 +1264,12 @@ static gdca_status rescore(gdca_ctx *ctx, bool again = false)
 {
     HIPCHK(hipMemsetAsync(&((gdca_dev_scalars *)ctx->sc.p)->di_noconv, 0, sizeof(int), ctx->stream));
     if (again) ctx->pend.score_batch = 1;
-    CHK(again ? marked_score_stage(ctx) : score_stage(ctx, ctx->pend.N, ctx->pend.q - 1, ctx->pend.n_pad, ctx->pend.target));
+    if (again)
+        CHK(marked_score_stage(ctx));
+    else {
+        CHK(logdet_stage(ctx, ctx->pend.n));
+        CHK(score_stage(ctx, ctx->pend.N, ctx->pend.q - 1, ctx->pend.n_pad, ctx->pend.target));
+    }
     return fetch_scalars(ctx);
 }
 
@@ -1238,6 +1286,28 @@ static gdca_status begin(gdca_ctx *ctx)
 
 static gdca_status run_inverse(gdca_ctx *ctx);
 static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st);
+
+// 1/2 (n log 2 pi + log det C), the constant between an energy and a log-likelihood: plain f64, one rounding per operation (one
+// multiplication, one addition, one multiplication -- the library is built without contraction), so that a caller who forms it from
+// gdca_last_logdet's value the same way gets the same bits
+static double loglik_constant(int n, double logdet)
+{
+    const double a = (double)n * GDCA_LOG_2PI;
+    const double b = a + logdet;
+    return 0.5 * b;
+}
+
+// How a LOGLIK run ends, every collect-time branch behind it: L = -(E + c) in place, c from the log det of the inverse finally used.
+// The run's score stage ends with this launch (T_END marked again: ms_score and ms_total include it).
+static gdca_status loglik_epilogue(gdca_ctx *ctx)
+{
+    const score_target &t = ctx->pend.target;
+    gdca_launch_loglik(ctx->stream, t.out, t.K, loglik_constant(ctx->pend.n, ctx->ld.val[0]));
+    CHK(check_launch(ctx, "loglik"));
+    CHK(mark(ctx, T_END));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GDCA_OK;
+}
 
 extern "C" {
 
@@ -1303,6 +1373,8 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
         CHK(rescore(ctx));
         ctx->pend.at.refined = 2;
     }
+    note_logdet(ctx);
+    if (ctx->pend.target.kind == score_target::LOGLIK && ctx->sc_host->info == 0 && !ctx->sc_host->bad_symbol) CHK(loglik_epilogue(ctx));
     if (st) CHK(fill_stats(ctx, st));
     const gdca_dev_scalars &h = *ctx->sc_host;
     if (h.bad_symbol & 4) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
@@ -1964,10 +2036,14 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
     const int sdim = q - 1, n = N * sdim, n_pad = round_up(n, GDCA_TILE);
     gdca_status mst[GDCA_MULTI_MAX];
     bool done[GDCA_MULTI_MAX];
+    double ldv[GDCA_MULTI_MAX];  // every member's log det (its group's) and where it came from: the context's record when the call returns
+    int lds[GDCA_MULTI_MAX];
     for (int k = 0; k < K; ++k) {
         memset(&st[k], 0, sizeof(st[k]));
         mst[k] = GDCA_OK;
         done[k] = false;
+        ldv[k] = (double)NAN;
+        lds[k] = 0;
     }
     // ---- the front end, once: theta, reweighting, Pi, Pij_true (ld = n) ----
     CHK(front_weights(ctx, Z_dev, N, M, q, p[0].theta, false));
@@ -2002,6 +2078,8 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
         if (gs == GDCA_EHIP || gs == GDCA_ENOMEM || gs == GDCA_EINVAL) return gs;  // (EINVAL here: a symbol outside 1..q)
         mst[k0] = gs;
         done[k0] = true;
+        ldv[k0] = ctx->ld.val[0];
+        lds[k0] = ctx->ld.src[0];
         if (first) {
             ms_theta = st[k0].ms_theta;
             ms_weights = st[k0].ms_weights;
@@ -2016,6 +2094,8 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
         for (int k = k0 + 1; k < K; ++k) {
             if (done[k] || p[k].pseudocount != pc) continue;
             done[k] = true;
+            ldv[k] = ldv[k0];
+            lds[k] = lds[k0];
             st[k] = st[k0];
             st[k].info = ginfo;
             st[k].ms_fn = 0.0;
@@ -2036,6 +2116,11 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
             if (rk) CHK(multi_rank_member(ctx, rk, k, Sk));
         }
     }
+    for (int k = 0; k < K; ++k) {
+        ctx->ld.val[k] = ldv[k];
+        ctx->ld.src[k] = lds[k];
+    }
+    ctx->ld.count = K;
     for (int k = 0; k < K; ++k)
         if (mst[k] != GDCA_OK) {
             char msg[sizeof(ctx->err)];
@@ -2286,6 +2371,7 @@ static gdca_status operator_fallback(gdca_ctx *ctx, const double *A_dev, int n, 
     CHK(ensure(ctx, ctx->C2, (size_t)n_pad * n_pad * sizeof(double)));
     gdca_launch_copy_in(ctx->stream, A_dev, n, (double *)ctx->C2.p, n_pad);
     CHK(cholesky_stage(ctx, n, n_pad));
+    CHK(logdet_stage(ctx, n));  // (of the factor's diagonal)
     return fetch_scalars(ctx);
 }
 
@@ -2297,6 +2383,7 @@ static gdca_status operator_inverse_once(gdca_ctx *ctx, double *A_dev, int n, in
     CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
     gdca_launch_copy_in(s, A_dev, n, (double *)ctx->A.p, n_pad);
     CHK(inverse_stage(ctx, n, n_pad, nullptr));
+    CHK(logdet_stage(ctx, n));
     CHK(operator_norms_and_refine(ctx, A_dev, n, n_pad));
     CHK(operator_fallback(ctx, A_dev, n, n_pad));
     if (ctx->sc_host->info == INT32_MIN) return GDCA_OK;  // (the watchdog: the caller's matrix stays as it is)
@@ -2324,6 +2411,7 @@ gdca_status gdca_spd_inverse_dev(gdca_ctx *ctx, double *A_dev, int32_t n, int32_
     const int n_pad = round_up(n, GDCA_TILE);
     CHK(operator_inverse_once(ctx, A_dev, n, n_pad));
     CHK(operator_inverse_retry(ctx, A_dev, n, n_pad));
+    note_logdet(ctx);
     if (ctx->sc_host->info == INT32_MIN) {
         if (info) *info = 0;
         return fail(ctx, GDCA_EHIP, "SPD inverse aborted: a dependency wait inside the sweep kernel timed out%s%s", "", "");
@@ -2370,6 +2458,7 @@ gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double 
         m->pend.n_pad = n_pad;
     }
     if (st == GDCA_OK) st = run_inverses(lead, ctxs, K);
+    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, logdet_stage(ctxs[k], n[k]));
     // kappa_1 and, where it is beyond the threshold, the Newton-Schulz step: member by member, as gdca_spd_inverse_dev does (the
     // caller's matrices are still intact; each member's switches are its own context's)
     for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_norms_and_refine(ctxs[k], A_dev[k], n[k], ctxs[k]->pend.n_pad));
@@ -2389,6 +2478,7 @@ gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double 
     gdca_status worst = GDCA_OK;
     for (int k = 0; k < K; ++k) {
         gdca_ctx *m = ctxs[k];
+        note_logdet(m);
         const int inf = m->sc_host->info;   // (fetched by operator_fallback)
         if (inf == INT32_MIN)
             worst = fail(lead, GDCA_EHIP, "SPD inverse aborted: a dependency wait inside the sweep kernel timed out%s%s", "", "");
@@ -2487,6 +2577,39 @@ gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N,
     if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     if (X_dev && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
     return run_target(ctx, Z_dev, N, M, q, p, energy_target(Z_dev, M, X_dev, K, E_dev), st);
+}
+
+gdca_status gdca_last_logdet(gdca_ctx *ctx, int32_t k, double *logdet, int32_t *source)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (!logdet) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(not_pending(ctx));
+    if (ctx->ld.count == 0) return fail(ctx, GDCA_EINVAL, "no SPD inverse has been completed on this context%s%s", "", "");
+    if (k < 0 || k >= ctx->ld.count) return fail(ctx, GDCA_EINVAL, "member index out of range%s%s", "", "");
+    *logdet = ctx->ld.val[k];
+    if (source) *source = ctx->ld.src[k];
+    return GDCA_OK;
+}
+
+gdca_status gdca_spd_inverse_logdet_dev(gdca_ctx *ctx, double *A_dev, int32_t n, int32_t *info, double *logdet)
+{
+    if (!ctx || !logdet) return GDCA_EINVAL;
+    *logdet = (double)NAN;
+    const gdca_status st = gdca_spd_inverse_dev(ctx, A_dev, n, info);
+    if (ctx->ld.count > 0 && !ctx->pending) *logdet = ctx->ld.val[0];
+    return st;
+}
+
+gdca_status gdca_run_loglik_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                const int8_t *X_dev, int32_t K, double *L_dev, double *logdet, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    if (!Z_dev || !L_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (X_dev && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (logdet) *logdet = (double)NAN;
+    const gdca_status rs = run_target(ctx, Z_dev, N, M, q, p, loglik_target(Z_dev, M, X_dev, K, L_dev), st);
+    if (logdet && ctx->ld.count > 0 && !ctx->pending) *logdet = ctx->ld.val[0];
+    return rs;
 }
 
 // the argument checks the four pair entry points share (nothing has run when one fails); KA / KB as they will be used
@@ -2793,6 +2916,16 @@ gdca_status gdca_spd_inverse(gdca_ctx *ctx, double *A, int32_t n, int32_t *info)
     return to_host(ctx, A, ctx->scratch[1], nn * nn * sizeof(double));
 }
 
+gdca_status gdca_spd_inverse_logdet(gdca_ctx *ctx, double *A, int32_t n, int32_t *info, double *logdet)
+{
+    if (!ctx || !A || !logdet || n < 1 || n > GDCA_MAX_N) return GDCA_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n;
+    CHK(to_dev(ctx, ctx->scratch[1], A, nn * nn * sizeof(double)));
+    CHK(gdca_spd_inverse_logdet_dev(ctx, (double *)ctx->scratch[1].p, n, info, logdet));
+    return to_host(ctx, A, ctx->scratch[1], nn * nn * sizeof(double));
+}
+
 gdca_status gdca_fn(gdca_ctx *ctx, const double *mJ, int32_t N, int32_t q, double *S)
 {
     CHK(validate(ctx, N, 1, q));
@@ -2875,6 +3008,23 @@ gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, in
     CHK(up);
     CHK(gdca_run_energies_dev(ctx, Z_dev, N, M, q, p, X_dev, K, E_dev, st));
     return to_host(ctx, E_host, ctx->scratch[5], ne);
+}
+
+gdca_status gdca_run_loglik(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, const int8_t *X_host,
+                            int32_t K, double *L_host, double *logdet, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    if (!Z_host || !L_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (X_host && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ne = (size_t)(X_host ? K : M) * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
+    double *L_dev = staged_out(ctx, 5, ne, &up);
+    CHK(up);
+    CHK(gdca_run_loglik_dev(ctx, Z_dev, N, M, q, p, X_dev, K, L_dev, logdet, st));
+    return to_host(ctx, L_host, ctx->scratch[5], ne);
 }
 
 gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split, const int8_t *XA,

@@ -50,6 +50,7 @@ struct gdca_dev_scalars {
     int ham_cut;     // word at which the three-plane bound form goes from all pairs of a tile to the list of those still below the threshold
                      // (k_hamming_decide; >= NW: never)
     unsigned ham_alive[64];  // k_hamming's probe: pairs of the sampled tiles still below the threshold after w + 1 words (HAM_ALIVE_SLOTS)
+    double logdet;   // log det of the matrix the last inverse was taken of: the sum of the logarithms of its pivots (k_logdet); NaN where info != 0
 };
 
 // Tuning switches of one context (gdca_ctx_set_option): initialised from the GDCA_* environment variables when the context is
@@ -186,6 +187,7 @@ struct gdca_inverse_ws {
     double *G[8];      // n_pad x 128 panels: [4 (p & 1) + w] = column block w of pivot group p (double-buffered by group parity)
     double *H[8];      // n_pad x 128 panels, -G * Pg
     double *P;         // 128 x 128 inverse of one pivot block
+    double *piv;       // n_pad pivots of the elimination, row by row (the sweep's side output; the Cholesky fallback writes its L_ii^2 there)
     double *Sg[2];     // 512 x 512 dense scratch copies of a group's diagonal super-block (ping-pong)
     double *Pg[2];     // 512 x 512: inverse of a group's diagonal super-block, by group parity
     unsigned *flags;   // dependency flags of the sweep (zeroed per inverse by the launcher)
@@ -223,8 +225,9 @@ void gdca_launch_probe_mfma_f64(hipStream_t s, double *out, int iters, int block
 // The reference's own way (dpotrf + dpotri) as a fallback for matrices the sweep cannot handle: C2 (n_pad x n_pad, identity
 // padding; overwritten by its Cholesky factor), U and Tm: n_pad x n_pad workspaces, Wd: (n_pad / 128) tiles of 128 x 128; Aout
 // receives -inverse in its lower block triangle (the sweep's storage); sc->info = dpotrf's index of a non-positive pivot
+// piv: n_pad doubles, L_ii^2 (the pivots: gdca_inverse_ws::piv)
 void gdca_launch_cholesky_inverse(hipStream_t s, double *C2, double *U, double *Tm, double *Wd, double *Aout, int n_pad, int n_real,
-                                  gdca_dev_scalars *sc);
+                                  gdca_dev_scalars *sc, double *piv);
 // *out = ||X||_1 of the symmetric matrix whose lower block triangle is A (= -X, the sweep's storage; first n rows / columns);
 // colsum_ws: n_pad doubles
 void gdca_launch_inverse_norm1(hipStream_t s, const double *A, int n_pad, int n, double *colsum_ws, double *out);
@@ -235,6 +238,12 @@ void gdca_launch_matrix_norm1(hipStream_t s, const double *C, size_t ld, int n, 
 // symmetric, n_pad x n_pad, identity padding), B0 and Rt: n_pad x n_pad workspaces
 // *resid (optional): max |I - X0 C|, the residual the step squares -- below one or the step cannot have converged
 void gdca_launch_newton_schulz(hipStream_t s, double *A, const double *C2, double *B0, double *Rt, int n_pad, double *resid);
+
+// ---- k_logdet.hip --------------------------------------------------------------------------
+// sc->logdet = sum_{i < n_real} log(piv[i]) in a fixed order (quiet NaN where sc->info != 0), behind the inverse on its stream
+void gdca_launch_logdet(hipStream_t s, const double *piv, int n_real, gdca_dev_scalars *sc);
+// L[k] <- -(L[k] + c), k < K: energies into log-likelihoods
+void gdca_launch_loglik(hipStream_t s, double *L, int K, double c);
 
 // ---- k_score.hip ---------------------------------------------------------------------------
 // S (N x N) from the lower triangle of A = -mJ (ld).  Diagonal 0.

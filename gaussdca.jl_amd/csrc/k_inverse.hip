@@ -29,6 +29,7 @@
 #include "gdca_launch.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
+typedef double double2_t __attribute__((ext_vector_type(2)));
 
 // threadIdx.x behind a volatile asm: inside the persistent loop of the update kernel the compiler would otherwise treat
 // every per-thread address offset of every path (hundreds of values) as loop-invariant, hoist them all and spill them
@@ -105,18 +106,21 @@ __device__ long long g_pivot_stamps[9 * 8 * 12];
 //      window 2 (after barrier 2):  chain: micro-pivot(K+1), -Pm(K+1) -> Pms         workers: 12 tile updates each, then column block
 //                                                                                     K+1 -> the OTHER Gs image, tile (K+2, K+2) -> Dt
 // Two barriers per micro-block; per micro-block the longer of (micro-pivot, 12 tile updates) instead of their sum plus the rest.
-// LDS (doubles): bufA = Gs image 0 | Ns rows kk < 8 | Pms | Dt | flag,  bufB = Gs image 1 | Ns rows kk >= 8  (two buffers of
+// LDS (doubles): bufA = Gs image 0 | Ns rows kk < 8 | Pms | Dt | flag | the block's pivots,  bufB = Gs image 1 | Ns rows kk >= 8  (two buffers of
 // 2 KC LDS_LD doubles: the staging arrays of the tile paths).
 #define PVC_NS_OFF (MB * PV_ROW)
 #define PVC_PMS_OFF (PVC_NS_OFF + (MB / 2) * PV_ROW)
 #define PVC_DT_OFF (PVC_PMS_OFF + MB * MB)
 #define PVC_FLAG_OFF (PVC_DT_OFF + MB * MB)
+#define PVC_PIV_OFF (PVC_FLAG_OFF + 2)  // the block's T pivots (behind the flag, 16-byte aligned): written by the chain wave, read by worker 0
 #define PVC_NT 12
 
-// One step of the 16 x 16 sweep as ONE MFMA, bad pivots remembered in a scalar (first one wins).
+// One step of the 16 x 16 sweep as ONE MFMA, bad pivots remembered in a scalar (first one wins).  dd[JJ]: the pivot d of step JJ, kept
+// where the step already has it -- in scalar registers -- until the sixteen steps are through (nothing of the chain reads it, no
+// instruction is added to a step): log det = sum log d (k_logdet).
 template <int JJ>
 struct ChainStep {
-    static __device__ __forceinline__ void run(double4_t &v, int l15, int lq, int index_base, int &bad)
+    static __device__ __forceinline__ void run(double4_t &v, int l15, int lq, int index_base, int &bad, double (&dd)[MB])
     {
         // lanes with lq == JJ & 3 hold column JJ, D[l15][JJ] (= D[JJ][l15] up to rounding), in register JJ >> 2: they are the
         // k = JJ & 3 slice of both operands, the other slices are zero:  v <- [row or column JJ ? 0 : v] - u w^T,
@@ -124,6 +128,7 @@ struct ChainStep {
         const double col = v[JJ >> 2];
         const double d = read_lane_f64<(JJ & 3) * 16 + JJ>(col);
         bad = (bad == 0 && !(d > 0.0)) ? index_base + JJ + 1 : bad;
+        dd[JJ] = d;
         double p = __builtin_amdgcn_rcp(d);
         p = fma(p, fma(-d, p, 1.0), p);
         p = fma(p, fma(-d, p, 1.0), p);
@@ -135,7 +140,7 @@ struct ChainStep {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) c[reg] = (l15 == JJ || (reg == (JJ >> 2) && sel)) ? 0.0 : v[reg];
         v = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-        if constexpr (JJ + 1 < MB) ChainStep<JJ + 1>::run(v, l15, lq, index_base, bad);
+        if constexpr (JJ + 1 < MB) ChainStep<JJ + 1>::run(v, l15, lq, index_base, bad, dd);
     }
 };
 
@@ -164,6 +169,7 @@ struct PivotBufs {
     }
     __device__ __forceinline__ double *pms() const { return A + PVC_PMS_OFF; }
     __device__ __forceinline__ double *dt() const { return A + PVC_DT_OFF; }
+    __device__ __forceinline__ double *piv() const { return A + PVC_PIV_OFF; }
 };
 
 __device__ __forceinline__ double4_t pvc_load_tile(const double *Ain, size_t ldin, int rb, int cb, int l15, int lq)
@@ -189,6 +195,7 @@ __device__ __forceinline__ void pivot_chain_wave(const double *Ain, size_t ldin,
     [[maybe_unused]] const int wv = 3;
     double *Pms = L.pms();
     const double *Dt = L.dt();
+    double *Pv = L.piv();
     double4_t v = (double4_t){0.0, 0.0, 0.0, 0.0};
     double4_t dt = pvc_load_tile(Ain, ldin, 0, 0, l15, lq);
     int bad = 0;
@@ -216,10 +223,19 @@ __device__ __forceinline__ void pivot_chain_wave(const double *Ain, size_t ldin,
             PV_STAMP(K, 3);
         }
         if (K + 1 < NMB) {
-            ChainStep<0>::run(dt, l15, lq, MB * (K + 1), bad);
+            double dd[MB];
+            ChainStep<0>::run(dt, l15, lq, MB * (K + 1), bad, dd);
             v = dt;
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) Pms[(lq + 4 * reg) * MB + l15] = v[reg];  // Pms[j][i] = -Pm(i, j)
+            // the sixteen pivots, behind everything the workers wait for (the chain wave has the shorter window): one lane writes
+            // them from their scalar pairs, two to a store -- LDS words nobody else touches; a worker takes them to memory once the
+            // chain is through
+            if (lane == 0) {
+                double2_t *pk = reinterpret_cast<double2_t *>(Pv + MB * (K + 1));
+#pragma unroll
+                for (int jj = 0; jj < MB; jj += 2) pk[jj >> 1] = (double2_t){dd[jj], dd[jj + 1]};
+            }
         }
         PV_STAMP(K, 4);
     }
@@ -232,7 +248,8 @@ __device__ __forceinline__ void store_wt(double *p, double v);
 
 template <int W, class Mid>
 __device__ __forceinline__ void pivot_worker(const double *Ain, size_t ldin, double *Aout, size_t ldout, double *__restrict__ P,
-                                             size_t pld, const PivotBufs L, int lane, Mid &mid, unsigned long long *ph = nullptr)
+                                             size_t pld, const PivotBufs L, int lane, Mid &mid, double *__restrict__ piv = nullptr,
+                                             unsigned long long *ph = nullptr)
 {
     const int l15 = lane & 15, lq = lane >> 4;
     [[maybe_unused]] const int wv = W;
@@ -367,25 +384,35 @@ __device__ __forceinline__ void pivot_worker(const double *Ain, size_t ldin, dou
     };
     emit(P, pld, -1.0);
     mid();
+    if (W == 0) {
+        // the block's T pivots, local rows lane and lane + 64, from where the chain wave left them (far above the waves' scratch X):
+        // behind the publication of P, which waits for nothing of this
+        const double *Pv = L.piv();
+        piv[lane] = Pv[lane];
+        piv[lane + 64] = Pv[lane + 64];
+    }
     emit(Aout, ldout, 1.0);
 }
 
 // Ain (ld = ldin) is read, Aout (ld = ldout) receives -P, P (ld = pld) the inverse; Ain and Aout may be the same tile.  buf:
 // 4 KC LDS_LD doubles of LDS; *bad_out (zeroed by the caller before a barrier) receives the 1-based local index of the first
 // non-positive pivot.  The caller puts a barrier behind the call before it reads *bad_out or reuses the buffers.  mid(): called once by
-// every wave, between the stores of P and those of the output tile (it may hold a barrier).
+// every wave, between the stores of P and those of the output tile (it may hold a barrier).  piv[0 .. T-1] receives the block's T
+// pivots -- the d of every elimination step, the squares of the Cholesky diagonal -- whatever their sign.
 template <class Mid>
 __device__ __forceinline__ void pivot_chain(const double *Ain, size_t ldin, double *Aout, size_t ldout, double *__restrict__ P,
-                                            size_t pld, double *buf, int *bad_out, Mid mid, unsigned long long *ph = nullptr)
+                                            size_t pld, double *buf, int *bad_out, double *__restrict__ piv, Mid mid,
+                                            unsigned long long *ph = nullptr)
 {
-    static_assert(PVC_FLAG_OFF < 2 * KC * LDS_LD && PVC_NS_OFF + (MB / 2) * PV_ROW <= 2 * KC * LDS_LD, "pivot images fit the staging buffers");
+    static_assert(PVC_PIV_OFF + T <= 2 * KC * LDS_LD && PVC_NS_OFF + (MB / 2) * PV_ROW <= 2 * KC * LDS_LD, "pivot images fit the staging buffers");
+    static_assert(3 * MB * (MB + 1) <= PVC_PIV_OFF, "the workers' transposition scratch ends below the pivots");
     const int tid = opaque_tid(), lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const PivotBufs L{buf};
     if (wv == 3)
         pivot_chain_wave(Ain, ldin, L, lane, bad_out, mid);
     else if (wv == 0)
-        pivot_worker<0>(Ain, ldin, Aout, ldout, P, pld, L, lane, mid, ph);
+        pivot_worker<0>(Ain, ldin, Aout, ldout, P, pld, L, lane, mid, piv, ph);
     else if (wv == 1)
         pivot_worker<1>(Ain, ldin, Aout, ldout, P, pld, L, lane, mid);
     else
@@ -969,6 +996,7 @@ struct SweepDesc {
     int n_real;
     int rl;                // real (non-padding) rows of the last block, rounded up to 16: 16 .. 128
     gdca_dev_scalars *sc;
+    double *piv;           // [n_pad] the pivots of the elimination, row by row (pivot_chain writes them, k_logdet sums their logarithms)
     unsigned long long *dbg;  // optional (GDCA_SWEEP_TRACE): 100 MHz wall-clock stamps, (start, end) per M-list item
     unsigned long long *dbg_main;  // optional: [0] ticks tile items waited, [1] panel items waited, [2..] ticks / counts by kind
     unsigned long long *dbg_items; // optional: per main-list item (kind, p, a, b, workgroup), taken, end of its wait, done (100 MHz stamps)
@@ -1280,14 +1308,14 @@ __device__ __forceinline__ MainItem main_decode(const SweepDesc &D, int &p, int 
 template <class Mid>
 __device__ __forceinline__ void sweep_pivot(const double *Ain, size_t ldin, double *Aout, size_t ldout, double *P,
                                                       double (*Gs)[KC][LDS_LD], double (*Hs)[KC][LDS_LD], int index0, int n_real,
-                                                      gdca_dev_scalars *sc, Mid mid, unsigned long long *ph = nullptr)
+                                                      gdca_dev_scalars *sc, double *piv, Mid mid, unsigned long long *ph = nullptr)
 {
     double *buf = &Gs[0][0][0];
     (void)Hs;
     int *badj = reinterpret_cast<int *>(buf + PVC_FLAG_OFF);
     if (threadIdx.x == 0) *badj = 0;
     __syncthreads();
-    pivot_chain(Ain, ldin, Aout, ldout, P, (size_t)T, buf, badj, mid, ph);
+    pivot_chain(Ain, ldin, Aout, ldout, P, (size_t)T, buf, badj, piv + index0, mid, ph);
     __syncthreads();
     if (threadIdx.x == 0 && *badj != 0) {
         // pivots run one after the other (each waits for the previous one's items): the first report is the smallest index
@@ -1482,7 +1510,7 @@ __device__ __forceinline__ void sweep_m_item(const SweepDesc &D, int q, int e, d
                 if (tid == 0) __hip_atomic_fetch_add(mc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         };
-        sweep_pivot(pin, pld_in, pout, pld_out, sz == 1 ? ring_pg(D, q) : D.Pw, Gs, Hs, (b0 + w) * T, D.n_real, D.sc, mid, D.dbg ? ph : nullptr);
+        sweep_pivot(pin, pld_in, pout, pld_out, sz == 1 ? ring_pg(D, q) : D.Pw, Gs, Hs, (b0 + w) * T, D.n_real, D.sc, D.piv, mid, D.dbg ? ph : nullptr);
         publish_wt_begin();  // the pivot's outputs are write-through stores
         if (tid == 0) {
             if (sz == 1)
@@ -2696,6 +2724,7 @@ static SweepPlan plan_sweep(hipStream_t s0, const gdca_inverse_job &job, bool me
     D.n_real = n_real;
     D.rl = rl;
     D.sc = job.sc;
+    D.piv = ws.piv;
     D.dbg = nullptr;
     D.dbg_main = nullptr;
     D.dbg_items = nullptr;
@@ -3048,8 +3077,9 @@ __device__ __forceinline__ void chol_tile_store(const double4_t (&acc)[4][4], do
 }
 
 // diagonal tile k: Cholesky in LDS (lower L written back, upper part zeroed), W = L^-1 to Wd (128 x 128, ld 128), U_kk = W^T (full tile)
+// piv[k T + j] = L_jj^2 of the tile, the pivot the sweep would have met at that row
 __global__ __launch_bounds__(256) void k_chol_diag(double *__restrict__ Lm, size_t ld, int k, double *__restrict__ Wd, double *__restrict__ U,
-                                                   int n_real, gdca_dev_scalars *sc)
+                                                   int n_real, gdca_dev_scalars *sc, double *__restrict__ piv)
 {
     extern __shared__ __attribute__((aligned(16))) double a[];  // [c][r], 128 x 128
     __shared__ int bad;
@@ -3060,6 +3090,7 @@ __global__ __launch_bounds__(256) void k_chol_diag(double *__restrict__ Lm, size
     for (int j = 0; j < T; ++j) {
         __syncthreads();
         double d = a[j + j * T];
+        if (tid == 0) piv[k * T + j] = d;
         if (!(d > 0.0)) {
             if (tid == 0 && bad == 0) bad = j + 1;
             d = 1.0;  // keep going with finite numbers: the result is discarded
@@ -3173,13 +3204,13 @@ __global__ __launch_bounds__(256, 2) void k_chol_uut(const double *__restrict__ 
 // C2: the matrix (full symmetric or lower block triangle, n_pad x n_pad, identity padding) -- overwritten by its Cholesky factor;
 // U, Tm: n_pad x n_pad workspaces; Wd: 128 x 128; Aout receives -inverse in its lower block triangle.  sc->info: dpotrf's index.
 void gdca_launch_cholesky_inverse(hipStream_t s, double *C2, double *U, double *Tm, double *Wd, double *Aout, int n_pad, int n_real,
-                                  gdca_dev_scalars *sc)
+                                  gdca_dev_scalars *sc, double *piv)
 {
     const int nblk = n_pad / T;
     const size_t ld = (size_t)n_pad;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_chol_diag), hipFuncAttributeMaxDynamicSharedMemorySize, T * T * (int)sizeof(double));
     for (int k = 0; k < nblk; ++k) {
-        GDCA_LAUNCH_DIRECT(k_chol_diag, dim3(1), dim3(256), T * T * sizeof(double), s, C2, ld, k, Wd + (size_t)k * T * T, U, n_real, sc);
+        GDCA_LAUNCH_DIRECT(k_chol_diag, dim3(1), dim3(256), T * T * sizeof(double), s, C2, ld, k, Wd + (size_t)k * T * T, U, n_real, sc, piv);
         const int below = nblk - k - 1;
         if (below > 0) {
             GDCA_LAUNCH_DIRECT(k_chol_panel, dim3((unsigned)below), dim3(256), 0, s, C2, ld, k, Wd + (size_t)k * T * T);

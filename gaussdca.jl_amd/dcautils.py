@@ -267,14 +267,21 @@ def compute_C(Pi, Pij, ctx=None) -> np.ndarray:
     return Cm
 
 
-def inv_cholesky(Cm, ctx=None) -> np.ndarray:
-    """mJ = inv(cholesky(C))   (src/GaussDCA.jl:34).  Raises PosDefException(info) like Julia."""
+def inv_cholesky(Cm, ctx=None, return_logdet: bool = False):
+    """mJ = inv(cholesky(C))   (src/GaussDCA.jl:34).  Raises PosDefException(info) like Julia.
+    return_logdet=True: (mJ, log det C) -- the sum of the logarithms of the pivots the inverse met on its way (2 sum log diag of the
+    Cholesky factor), the constant sequence_loglik needs; mJ is the same bits either way."""
     ctx = ctx or default_context()
     A = np.array(Cm, dtype=np.float64, order="C", copy=True)
     n = A.shape[0]
     if A.shape != (n, n) or not np.array_equal(A, A.T):
         raise PosDefException(-1)
     info = C.c_int32()
+    if return_logdet:
+        logdet = C.c_double(float("nan"))
+        rc = ctx.lib.gdca_spd_inverse_logdet(ctx.h, _lib._p(A), n, C.byref(info), C.byref(logdet))
+        ctx.check(rc, info.value)
+        return A, logdet.value
     rc = ctx.lib.gdca_spd_inverse(ctx.h, _lib._p(A), n, C.byref(info))
     ctx.check(rc, info.value)
     return A
@@ -312,7 +319,7 @@ def correct_APC(S, ctx=None) -> np.ndarray:
 def sequence_energies(mJ, Pi, X, q: int = 21, ctx=None) -> np.ndarray:
     """E[k] = 1/2 (x_k - Pi)' mJ (x_k - Pi) for the K columns of X (shape (N, K) like Z, symbols 1..q, q = the gap): minus the
     log-likelihood of each sequence under the Gaussian model with precision mJ = inv(cholesky(C)) (src/GaussDCA.jl:34) and mean
-    Pi (add_pseudocount's Pi, :30), up to the model's constant 1/2 log det(2 pi C), which is not included.  Lower = fits better.
+    Pi (add_pseudocount's Pi, :30), up to the model's constant 1/2 log det(2 pi C) (sequence_loglik adds it).  Lower = fits better.
     mJ must be symmetric (its lower triangle is read)."""
     mJ = np.ascontiguousarray(mJ, dtype=np.float64)
     Pi = np.ascontiguousarray(Pi, dtype=np.float64)
@@ -336,6 +343,22 @@ def sequence_energies(mJ, Pi, X, q: int = 21, ctx=None) -> np.ndarray:
     E = np.empty(K, dtype=np.float64)
     ctx.check(ctx.lib.gdca_energies(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xf), K, _lib._p(E)))
     return E
+
+
+LOG_2PI = 1.8378770664093453  # log(2 pi), GDCA_LOG_2PI of include/gdca.h
+
+
+def loglik_constant(n: int, logdet: float) -> float:
+    """c = 1/2 (n log 2 pi + log det C), rounded operation by operation as the library forms it (gdca_run_loglik)."""
+    return float(np.float64(0.5) * (np.float64(n) * np.float64(LOG_2PI) + np.float64(logdet)))
+
+
+def sequence_loglik(mJ, Pi, X, logdet: float, q: int = 21, ctx=None) -> np.ndarray:
+    """log p(x_k) = -E(x_k) - 1/2 (n log 2 pi + log det C) for the K columns of X: the density of the Gaussian model N(Pi, C) at the
+    one-hot point, comparable across models.  mJ, Pi, X, q as sequence_energies takes them; logdet = log det C, from
+    inv_cholesky(C, return_logdet=True).  Host arithmetic on sequence_energies: L = -(E + c)."""
+    E = sequence_energies(mJ, Pi, X, q=q, ctx=ctx)
+    return -(E + loglik_constant(np.asarray(Pi).shape[0], logdet))
 
 
 def _what_arg(what) -> int:

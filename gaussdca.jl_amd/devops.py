@@ -65,6 +65,11 @@ def inv_cholesky_dev(ctx: Context, dA, n: int):
     return dA
 
 
+def inv_cholesky_logdet_dev(ctx: Context, dA, n: int):
+    """inv_cholesky_dev and log det C in one call (gdca_spd_inverse_logdet_dev): (dA, logdet), the inverse bit for bit the same"""
+    return dA, ctx.spd_inverse_logdet_dev(_ptr(dA).value, int(n))
+
+
 def compute_FN_dev(ctx: Context, dmJ, N: int, q: int, dS=None):
     dS = dS or DeviceBuffer(ctx, 8 * N * N)
     ctx.check(ctx.lib.gdca_fn_dev(ctx.h, _ptr(dmJ), N, int(q), _ptr(dS)))

@@ -160,6 +160,28 @@ def gDCA_energies(filename: str, sequences=None, pseudocount: float = 0.8, theta
                            "energies")
 
 
+def gDCA_loglik(filename: str, sequences=None, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+                remove_dups: bool = False, ctx=None, **kw):
+    """Log-likelihoods of sequences under the Gaussian model gDCA fits to the alignment in ``filename`` (the fit and the arguments
+    are ``gDCA_energies``'): ``(L, logdet)`` with L[k] = log p(x_k) = -E(x_k) - 1/2 (n log 2 pi + log det C), the density of the
+    continuous Gaussian N(Pi, C) at the one-hot point, and logdet = log det C from the pivots of the very inverse the model comes
+    from.  Unlike the energies these are on one scale for every model: compare families, pseudocounts (a held-out likelihood) or
+    the halves of a paired alignment with them.  Higher = fits better.  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_loglik() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    X = _sequences_arg(sequences, "sequences", "an N x K")
+
+    def run(c, ptr, N, M, q):
+        L, logdet, st = c.run_loglik_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), *_ptr_count(X))
+        return (L, logdet), st
+
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N), run,
+                           "log-likelihoods")
+
+
 def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what="energy", pseudocount: float = 0.8, theta=":auto",
                        max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
     """Energies of every pairing across a split alignment under the Gaussian model gDCA fits to ``filename``, an alignment of

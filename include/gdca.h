@@ -297,8 +297,9 @@ gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N);
  * one-hot encoding x of a sequence (x[i*s + a - 1] = 1 for symbol a in 1..s at 0-based site i; symbol q, the gap, leaves the site's
  * block zero) and Pi the single-site frequencies WITH pseudocount (add_pseudocount's first result, :30):
  *     E(x) = 1/2 (x - Pi)' mJ (x - Pi)
- * i.e. minus the log-likelihood up to the model's constant 1/2 log det(2 pi C), which is NOT included (the block sweep does not
- * produce the Cholesky pivots; comparisons inside one model never need it).  Lower energy = better fit.
+ * i.e. minus the log-likelihood up to the model's constant 1/2 log det(2 pi C), which is not part of E: comparisons inside one model
+ * never need it.  Comparisons ACROSS models do -- see "log-likelihoods" below (gdca_last_logdet, gdca_run_loglik), which supply it from
+ * the pivots of the very inverse the model comes from.  Lower energy = better fit.
  * X is N x K int8 column-major like Z (sequence k = the N bytes X[k*N ..]), K >= 1; E has K entries.  mJ is n x n column-major,
  * leading dimension n, symmetric: only its lower triangle is read.  Every sum is taken in a fixed order in f64 (no floating-point
  * atomics): a sequence's energy is the same bits from run to run, whatever other sequences share the call and wherever it stands
@@ -314,6 +315,47 @@ gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double 
  * to the end of the energy stage. */
 gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                   const int8_t *X_dev, int32_t K, double *E_dev, gdca_stats *st);
+
+/* ---- log-likelihoods: log det C from the pivots of the inverse, normalised scores ---------------------------------------------------
+ * The energies stop one constant short of a likelihood.  With it, the density of the continuous Gaussian N(Pi, C) at the one-hot point x:
+ *     log p(x) = -E(x) - 1/2 (n log 2 pi + log det C),        n = N (q - 1)
+ * and that is what makes models comparable: which of several families a sequence belongs to, which pseudocount gives the higher held-out
+ * likelihood, how strongly the halves of a paired alignment co-vary (-1/2 (log det C - log det C_AA - log det C_BB)).
+ * log det C costs nothing extra: the block sweep eliminates symmetrically without pivoting, so the scalar pivot d_i of its every step is
+ * the square of the Cholesky diagonal, log det C = sum_i log d_i -- the quantity dpotrf would give.  Every SPD inverse of this library
+ * leaves its n pivots in a vector of the context's workspace (a side output: the inverse itself is bit for bit what it was), and one
+ * small kernel behind the inverse sums their logarithms in f64 in a fixed order (a fixed stride per thread, then a fixed tree; no
+ * floating-point atomics; the identity padding is not summed).
+ * Determinism: log det is the same bits from run to run for an inverse that has a launch of its own, and for the members of a merged
+ * launch under option MERGE_GROUP=1 (their arithmetic is then that of a launch of their own); between different groupings of the sweep
+ * (options GROUP, MERGE_GROUP, RAGGED) it agrees to rounding.  It does not depend on K or on X.
+ * The conditioning branches: a second attempt of the sweep (st->sweep_retries) writes the pivots again and the value is that attempt's --
+ * the undisturbed run's bits; after a Newton-Schulz step (st->refined = 1) the value stays that of the sweep's pivots: the step improves
+ * the inverse, the pivots are backward stable as they are; after the Cholesky fallback (st->refined = 2, or option CHOLESKY=2) the value
+ * is that of the fallback's diagonal, sum_i log L_ii^2, and `source` says so. */
+#define GDCA_LOG_2PI 1.8378770664093453  /* log(2 pi), the nearest double */
+/* log det of the matrix of the last SPD inverse this context completed: gdca_spd_inverse(_dev), a member of gdca_spd_inverse_batch_dev
+ * (ask that member's context), or any fused run once it has been collected (gdca_run*, _energies, _pair_energies, _partner_match,
+ * _mutation_scan, _loglik, the members of a phase batch).  k: after gdca_run_multi* the member index -- the value of the pseudocount group
+ * of p[k] --, 0 after everything else.  source (may be NULL): 0 = the sweep's pivots, 1 = the Cholesky fallback's diagonal.  Entry points
+ * that take no inverse leave the record alone.  GDCA_EINVAL: no inverse yet (or the last one did not complete: GDCA_EHIP), k out of
+ * range, a run outstanding on the context, a null pointer.  Where that inverse ended GDCA_ENOTPD the value is NaN, with GDCA_OK.  No device
+ * work: the value came back with the inverse's other scalars. */
+gdca_status gdca_last_logdet(gdca_ctx *ctx, int32_t k, double *logdet, int32_t *source);
+/* gdca_spd_inverse(_dev) and the value in one call (logdet: a host pointer; NaN on failure).  The inverse is bit for bit
+ * gdca_spd_inverse(_dev)'s, the status too. */
+gdca_status gdca_spd_inverse_logdet_dev(gdca_ctx *ctx, double *A_dev, int32_t n, int32_t *info, double *logdet);
+gdca_status gdca_spd_inverse_logdet(gdca_ctx *ctx, double *A, int32_t n, int32_t *info, double *logdet);
+/* Fused: gdca_run_energies(_dev) unchanged (X == NULL scores Z itself, M values), then L[k] = -(E[k] + c) with
+ *     c = 0.5 * (n * GDCA_LOG_2PI + logdet)
+ * formed once on the host in plain f64 -- one multiplication, one addition, one multiplication, no contraction -- from the log det of the
+ * inverse finally used (after a second attempt, refinement or fallback at collect time: see above), so L is bit for bit -(E + c) with E
+ * from gdca_run_energies and logdet from gdca_last_logdet.  logdet (host pointer, may be NULL) receives that value.  Status codes and
+ * stats as gdca_run_energies; ms_score includes the log det kernel and this epilogue.  On failure L is unspecified. */
+gdca_status gdca_run_loglik_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                const int8_t *X_dev, int32_t K, double *L_dev, double *logdet, gdca_stats *st);
+gdca_status gdca_run_loglik(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                            const int8_t *X_host, int32_t K, double *L_host, double *logdet, gdca_stats *st);
 
 /* ---- pair energies: every pairing across a split alignment -----------------------------------------------------------------
  * Partner matching (the paper's second use of the model) takes an alignment of concatenated pairs A (+) B and needs, per species, the

@@ -15,7 +15,7 @@
 module GaussDCAHip
 
 export gDCA, gDCA_stepwise, printrank, compute_weights, compute_weighted_frequencies, add_pseudocount,
-       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, pair_energies, mutation_scan, gDCA_mutation_scan,
+       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, inv_cholesky_logdet, gDCA_loglik, pair_energies, mutation_scan, gDCA_mutation_scan,
        species_blocks, pair_energies_blocked_dev, assign_blocks_dev, run_partner_match_dev, gDCA_partner_match
 
 using LinearAlgebra
@@ -163,6 +163,16 @@ function inv_cholesky(C::Matrix{Float64})   # mJ = inv(cholesky(C)), src/GaussDC
                               ctx(), A, n, info)
     check(rc, info[])
     return A
+end
+
+# (mJ, log det C): inv_cholesky and the sum of the logarithms of the pivots the inverse met (include/gdca.h, "log-likelihoods") --
+# the constant between sequence_energies and a log-likelihood; mJ is bit for bit inv_cholesky's
+function inv_cholesky_logdet(C::Matrix{Float64})
+    A = copy(C); n = size(A, 1); info = Ref{Int32}(0); logdet = Ref{Float64}(NaN)
+    rc = GC.@preserve A ccall((:gdca_spd_inverse_logdet, libgdca), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ref{Int32}, Ref{Float64}),
+                              ctx(), A, n, info, logdet)
+    check(rc, info[])
+    return A, logdet[]
 end
 
 function compute_FN(mJ::Matrix{Float64}, q::Integer = 21)
@@ -322,6 +332,36 @@ function gDCA_energies(filename::AbstractString; sequences = nothing, pseudocoun
     check(rc, st.info)
     st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: energies are unreliable" pseudocount
     return E
+end
+
+# gDCA's fit (the keywords of gDCA_energies), then (L, logdet): L[k] = log p(x_k) = -E(x_k) - 1/2 (n log 2 pi + log det C) of
+# `sequences` under it -- the density of the Gaussian N(Pi, C) at the one-hot point, on one scale for every model -- and log det C
+function gDCA_loglik(filename::AbstractString; sequences = nothing, pseudocount::Real = 0.8, θ = :auto,
+                     max_gap_fraction::Real = 0.9, remove_dups::Bool = false)
+    check_arguments(filename, pseudocount, θ, max_gap_fraction, :frob, 1)
+    Z = DCAUtils.read_fasta_alignment(filename, max_gap_fraction)
+    if remove_dups
+        Z, _ = DCAUtils.remove_duplicate_sequences(Z)
+    end
+    q = Int(maximum(Z))
+    q ≥ 32 && error("parameter q=$q is too big (max 31 is allowed)")
+    X = sequences isa AbstractString ? DCAUtils.read_fasta_alignment(sequences, 1.0) : sequences
+    N, M = size(Z)
+    (X === nothing || size(X, 1) == N) || throw(ArgumentError("sequences have $(size(X, 1)) sites, the alignment has $N"))
+    K = X === nothing ? M : size(X, 2)
+    L = Vector{Float64}(undef, K)
+    logdet = Ref{Float64}(NaN)
+    p = Ref(GdcaParams(Float64(pseudocount), theta_arg(θ), 0, 0))
+    st = GdcaStats()
+    Xp = X === nothing ? Ptr{Int8}(C_NULL) : pointer(X)
+    GC.@preserve Z X L begin
+        rc = ccall((:gdca_run_loglik, libgdca), Cint,
+                   (Ptr{Cvoid}, Ptr{Int8}, Int32, Int32, Int32, Ref{GdcaParams}, Ptr{Int8}, Int32, Ptr{Float64}, Ref{Float64}, Ref{GdcaStats}),
+                   ctx(), Z, N, M, q, p, Xp, K, L, logdet, st)
+    end
+    check(rc, st.info)
+    st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: log-likelihoods are unreliable" pseudocount
+    return L, logdet[]
 end
 
 # D[b, i, k] for every single substitution of the K columns of X (N x K like Z) under the model (include/gdca.h, "mutation scan"):

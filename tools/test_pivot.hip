@@ -8,6 +8,8 @@
 #define GDCA_PIVOT_STAMPS
 #include "../gaussdca.jl_amd/csrc/k_inverse.hip"
 
+__device__ double g_pivots[T];  // the block's pivots (pivot_chain's side output)
+
 // as the persistent sweep kernel runs it: one 256-thread workgroup of a two-workgroups-per-CU kernel
 __global__ __launch_bounds__(256, 2) void k_pivot4(const double *Ain, size_t ldin, double *Aout, size_t ldout, double *__restrict__ P,
                                                    size_t pld, int *bad)
@@ -15,7 +17,7 @@ __global__ __launch_bounds__(256, 2) void k_pivot4(const double *Ain, size_t ldi
     __shared__ __attribute__((aligned(16))) double buf[4 * KC * LDS_LD];
     if (threadIdx.x == 0) *bad = 0;
     __syncthreads();
-    pivot_chain(Ain, ldin, Aout, ldout, P, pld, buf, bad, [] {});
+    pivot_chain(Ain, ldin, Aout, ldout, P, pld, buf, bad, g_pivots, [] {});
 }
 
 static void print_stamps()
