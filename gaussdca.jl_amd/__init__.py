@@ -13,6 +13,6 @@ from .dcautils import (add_pseudocount, assign_blocks, compute_C, compute_DI_gau
                        inv_cholesky, mutation_scan, neighbour_counts, pair_energies, pair_energies_blocked, pair_identity_sum, printrank,
                        read_fasta_alignment, remove_duplicate_sequences, sequence_energies, sequence_loglik, species_blocks, Ranking)
 from .gdca import (check_arguments, gDCA, gDCA_energies, gDCA_loglik, gDCA_multi, gDCA_mutation_scan, gDCA_pair_energies,  # noqa: F401
-                   gDCA_partner_match)
+                   gDCA_partner_ipa, gDCA_partner_match)
 
 __all__ = ["gDCA", "printrank"]

@@ -47,6 +47,9 @@ class Params(C.Structure):
     _fields_ = [("pseudocount", C.c_double), ("theta", C.c_double), ("score", C.c_int32), ("apc", C.c_int32)]
 
 
+# the columns of a row of gdca_run_partner_ipa's rounds_out (GDCA_IPA_*), GDCA_IPA_FIELDS of them
+IPA_FIELDS = ("M_train", "candidates", "n_sel", "n_changed", "Meff", "theta", "logdet", "cost", "ms_fit", "ms_match", "ms_select", "reserved")
+
 MULTI_MAX = 16  # GDCA_MULTI_MAX: settings one gdca_run_multi call takes
 
 
@@ -190,6 +193,20 @@ SYMBOLS = {
     "gdca_run_partner_match": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
                                          C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_select_confident_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _i32p]),
+    "gdca_select_confident": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _i32p]),
+    "gdca_concat_pairs_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_int32]),
+    "gdca_concat_pairs": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p, C.c_int32]),
+    "gdca_run_partner_ipa_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32p,
+                                           C.POINTER(Stats)]),
+    "gdca_run_partner_ipa": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32p,
+                                       C.POINTER(Stats)]),
     "gdca_mutation_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_mutation_scan": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_run_mutation_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
@@ -496,6 +513,84 @@ class Context:
         return self._run_readout(self.lib.gdca_run_partner_match_dev, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr),
                                  int(KA), self._opt(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, int(what), self._opt(E_ptr),
                                  C.c_void_p(match_ptr), self._opt(gap_ptr))
+
+    # ---- iterative partner matching: the selection, the concatenation and the loop (gdca_run_partner_ipa) ----
+    def select_confident(self, match: np.ndarray, gap: np.ndarray, n_take: int):
+        """gdca_select_confident on host vectors (match int32[KA], gap float64[KA] as assign_blocks returns them): the first
+        min(n_take, candidates) candidates by gap descending, ties in ascending a.  Returns (sel int32[KA]: the selected a ascending,
+        then -1; n_sel)."""
+        match, gap = np.ascontiguousarray(match, dtype=np.int32), np.ascontiguousarray(gap, dtype=np.float64)
+        sel = np.empty(len(match), dtype=np.int32)
+        n = C.c_int32(0)
+        self.check(self.lib.gdca_select_confident(self.h, _p(match), _p(gap), len(match), int(n_take), _p(sel), C.byref(n)))
+        return sel, n.value
+
+    def select_confident_dev(self, match_ptr: int, gap_ptr: int, KA: int, n_take: int, sel_ptr: int) -> int:
+        """Device-pointer form (match, gap and sel resident in HBM).  Returns n_sel."""
+        n = C.c_int32(0)
+        self.check(self.lib.gdca_select_confident_dev(self.h, C.c_void_p(match_ptr), C.c_void_p(gap_ptr), int(KA), int(n_take),
+                                                      C.c_void_p(sel_ptr), C.byref(n)))
+        return n.value
+
+    def concat_pairs(self, XA: np.ndarray, XB: np.ndarray, selA, selB, Z: np.ndarray, col0: int = 0) -> None:
+        """gdca_concat_pairs on host arrays: column col0 + t of Z (int8 (N, M), Fortran-contiguous, written in place) becomes
+        XA[:, selA[t]] over XB[:, selB[t]]."""
+        XA, XB = np.asfortranarray(XA, dtype=np.int8), np.asfortranarray(XB, dtype=np.int8)
+        selA, selB = np.ascontiguousarray(selA, dtype=np.int32), np.ascontiguousarray(selB, dtype=np.int32)
+        if len(selA) != len(selB) or Z.dtype != np.int8 or not Z.flags.f_contiguous or Z.shape[0] != XA.shape[0] + XB.shape[0] \
+                or col0 < 0 or col0 + len(selA) > Z.shape[1]:
+            raise ArgumentError("Z must be an int8 Fortran-contiguous (N, M) array with M >= col0 + len(selA), and len(selA) == len(selB)")
+        self.check(self.lib.gdca_concat_pairs(self.h, _p(XA), XA.shape[1], _p(XB), XB.shape[1], Z.shape[0], XA.shape[0], _p(selA), _p(selB),
+                                              len(selA), _p(Z), int(col0)))
+
+    def concat_pairs_dev(self, XA_ptr: int, KA: int, XB_ptr: int, KB: int, N: int, split: int, selA_ptr: int, selB_ptr: int, n_sel: int,
+                         Z_ptr: int, col0: int = 0) -> None:
+        """Device-pointer form (the pools, the index vectors and Z resident in HBM)."""
+        self.check(self.lib.gdca_concat_pairs_dev(self.h, C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB), int(N), int(split),
+                                                  C.c_void_p(selA_ptr), C.c_void_p(selB_ptr), int(n_sel), C.c_void_p(Z_ptr), int(col0)))
+
+    def _ipa(self, fn, XA_ptr, KA, XB_ptr, KB, offA, offB, N, q, split, what, pseudocount, theta, Zfix_ptr, Mfix, seedA, seedB, n_inc,
+             max_rounds, match_p, gap_p, mt_p, gt_p):
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        seedA, seedB = np.ascontiguousarray(seedA, dtype=np.int32), np.ascontiguousarray(seedB, dtype=np.int32)
+        if seedA.ndim != 1 or seedA.shape != seedB.shape:
+            raise ArgumentError("the seed must be two index vectors of one length")
+        prm = Params(float(pseudocount), float(theta), SCORE_FROB, 0)
+        st = Stats()
+        rounds = np.zeros((max(int(max_rounds), 1), len(IPA_FIELDS)), dtype=np.float64)
+        done = C.c_int32(0)
+        rc = fn(self.h, self._opt(XA_ptr), int(KA), self._opt(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, int(N), int(q), int(split),
+                int(what), C.byref(prm), self._opt(Zfix_ptr), int(Mfix), _p(seedA), _p(seedB), len(seedA), int(n_inc), int(max_rounds),
+                match_p, gap_p, mt_p, gt_p, _p(rounds), C.byref(done), C.byref(st))
+        self.rounds_run = done.value   # (kept where the call raises: the completed rounds' results are in the caller's arrays)
+        self.check(rc, st.info)
+        return [dict(zip(IPA_FIELDS, row.tolist())) for row in rounds[:done.value]], st.as_dict()
+
+    def run_partner_ipa_ptr(self, XA_ptr: int, KA: int, XB_ptr: int, KB: int, offA, offB, N: int, q: int, split: int, pseudocount: float,
+                            theta: float, Zfix_ptr: int | None, Mfix: int, seedA, seedB, n_inc: int, max_rounds: int, what: int = 1,
+                            want_traces: bool = False):
+        """gdca_run_partner_ipa on HOST matrices given by address: the species-sorted pools XA (split x KA) and XB ((N - split) x KB),
+        Zfix (N x Mfix, or None) and the seed (index pairs into the pools).  Returns ((match int32[KA], gap float64[KA], match_trace,
+        gap_trace -- (rounds, KA) arrays or None), rounds: one dict a completed round (IPA_FIELDS), stats of the last fit)."""
+        ka = max(int(KA), 0)
+        match, gap = np.empty(ka, dtype=np.int32), np.empty(ka, dtype=np.float64)
+        mt = np.empty((max(int(max_rounds), 1), ka), dtype=np.int32) if want_traces else None
+        gt = np.empty((max(int(max_rounds), 1), ka), dtype=np.float64) if want_traces else None
+        rounds, st = self._ipa(self.lib.gdca_run_partner_ipa, XA_ptr, KA, XB_ptr, KB, offA, offB, N, q, split, what, pseudocount, theta, Zfix_ptr,
+                               Mfix, seedA, seedB, n_inc, max_rounds, _p(match), _p(gap), None if mt is None else _p(mt),
+                               None if gt is None else _p(gt))
+        if want_traces:
+            mt, gt = mt[:len(rounds)], gt[:len(rounds)]
+        return (match, gap, mt, gt), rounds, st
+
+    def run_partner_ipa_dev(self, XA_ptr: int, KA: int, XB_ptr: int, KB: int, offA, offB, N: int, q: int, split: int, pseudocount: float,
+                            theta: float, Zfix_ptr: int | None, Mfix: int, seedA, seedB, n_inc: int, max_rounds: int, what: int,
+                            match_ptr: int, gap_ptr: int | None, match_trace_ptr: int | None = None, gap_trace_ptr: int | None = None):
+        """Device-pointer form (the pools, Zfix, match, gap and the traces resident in HBM; the seed and the offsets are host arrays).
+        Returns (rounds, stats)."""
+        return self._ipa(self.lib.gdca_run_partner_ipa_dev, XA_ptr, KA, XB_ptr, KB, offA, offB, N, q, split, what, pseudocount, theta, Zfix_ptr,
+                         Mfix, seedA, seedB, n_inc, max_rounds, C.c_void_p(match_ptr), self._opt(gap_ptr), self._opt(match_trace_ptr),
+                         self._opt(gap_trace_ptr))
 
     # ---- the energy change of every single substitution (gdca_run_mutation_scan) ----
     def run_mutation_scan_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None,

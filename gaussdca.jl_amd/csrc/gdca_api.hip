@@ -61,6 +61,7 @@ struct score_target {
     pair_blocks blocks;                // partner: the blocked pair stage, then the assignment (k_assign.hip) into match / gap
     int32_t *match;
     double *gap;
+    bool packed;                       // partner: XA / XB lie packed and padded in the context already (pair_pack; the rounds of gdca_run_partner_ipa)
 };
 
 static score_target contact_target(int score, int apc, double *S_dev)
@@ -193,6 +194,10 @@ struct gdca_ctx {
     // partner matching: the species table (eoff, offA, offB), the blocked gather's work list, and the packed matrix of a fused run
     // whose caller does not want it
     gdca_buf PBtab, PBitems, PBE;
+    // iterative partner matching (k_ipa.hip): the selection's workspace (keys, values, histograms, flags), the counts a round hands to
+    // the host, the growing training alignment, the selection (and a seed's partners behind it), a round's match / gap, the match of
+    // the round before, and the species of every sequence a
+    gdca_buf IPAws, IPAcnt, IPAZ, IPAsel, IPAm, IPAg, IPAprev, IPAsp;
     int ncu;                  // compute units of the device
     double *piv;              // the pivots of the context's last inverse, n_pad doubles inside Sg (inverse_job)
     // log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet): kept on the host, so that entry points
@@ -624,7 +629,8 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pipc, &ctx->A, &ctx->G, &ctx->H, &ctx->P, &ctx->Sg, &ctx->Dblk, &ctx->Ld,
                         &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg,
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
-                        &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE};
+                        &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
+                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < N_SCRATCH; ++i)
@@ -1041,21 +1047,35 @@ static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
 // kernel's epilogue; GDCA_PAIR_COUPLING: R alone, no g.  Illegal bytes: sc->bad_symbol bit 2.
 // blk != nullptr: only the pairings inside the species of species-sorted sequences, E packed block by block (include/gdca.h, partner
 // matching) -- the pack, the pad, the marginal energies and the fold are the same calls; the gather goes by blk's work list.
-static gdca_status pair_stage(gdca_ctx *ctx, const gdca_model &m, int split, const int8_t *XA, size_t strideA, int KA, const int8_t *XB,
-                              size_t strideB, int KB, int what, double *E_dev, const pair_blocks *blk = nullptr)
+// what the pair stage makes of its sequences alone, whatever the model: the packed symbols of the two halves (ctx->PXa, ctx->PXb;
+// illegal bytes: sc->bad_symbol bit 2) and, for the energy, the gap-padded halves (ctx->PXpad)
+static gdca_status pair_pack(gdca_ctx *ctx, int N, int q, int split, const int8_t *XA, size_t strideA, int KA, const int8_t *XB, size_t strideB,
+                             int KB, int what)
 {
     hipStream_t s = ctx->stream;
-    const int N = m.N, q = m.q, sdim = q - 1, n = N * sdim, nB = (N - split) * sdim;
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
     CHK(ensure(ctx, ctx->PXa, (size_t)gdca_energy_blocks(split) * KA * sizeof(uint32_t)));
     CHK(ensure(ctx, ctx->PXb, (size_t)gdca_energy_blocks(N - split) * KB * sizeof(uint32_t)));
     gdca_launch_energy_pack(s, XA, strideA, split, KA, q, (uint32_t *)ctx->PXa.p, sc);
     gdca_launch_energy_pack(s, XB, strideB, N - split, KB, q, (uint32_t *)ctx->PXb.p, sc);
-    const double *EAB = nullptr, *c0 = nullptr;
     if (what == GDCA_PAIR_ENERGY) {
         CHK(ensure(ctx, ctx->PXpad, (size_t)N * ((size_t)KA + (size_t)KB)));
-        CHK(ensure(ctx, ctx->PEab, ((size_t)KA + (size_t)KB) * sizeof(double)));
         gdca_launch_pair_pad(s, XA, strideA, XB, strideB, N, split, KA, KB, q, (int8_t *)ctx->PXpad.p);
+    }
+    return GDCA_OK;
+}
+
+// packed: pair_pack has run on these sequences already and nothing has touched its three buffers since (the rounds of
+// gdca_run_partner_ipa: the pools do not change from round to round)
+static gdca_status pair_stage(gdca_ctx *ctx, const gdca_model &m, int split, const int8_t *XA, size_t strideA, int KA, const int8_t *XB,
+                              size_t strideB, int KB, int what, double *E_dev, const pair_blocks *blk = nullptr, bool packed = false)
+{
+    hipStream_t s = ctx->stream;
+    const int N = m.N, q = m.q, sdim = q - 1, n = N * sdim, nB = (N - split) * sdim;
+    if (!packed) CHK(pair_pack(ctx, N, q, split, XA, strideA, KA, XB, strideB, KB, what));
+    const double *EAB = nullptr, *c0 = nullptr;
+    if (what == GDCA_PAIR_ENERGY) {
+        CHK(ensure(ctx, ctx->PEab, ((size_t)KA + (size_t)KB) * sizeof(double)));
         CHK(energy_stage(ctx, m, (const int8_t *)ctx->PXpad.p, KA + KB, (double *)ctx->PEab.p));
         EAB = (const double *)ctx->PEab.p;
         c0 = (const double *)ctx->gvec.p + n;
@@ -1103,7 +1123,7 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
     case score_target::LOGLIK: return energy_stage(ctx, m, t.X, t.K, t.out);
     case score_target::PAIR: return pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
     case score_target::PARTNER:
-        CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out, &t.blocks));
+        CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out, &t.blocks, t.packed));
         return assign_stage(ctx, t.out, t.blocks, t.match, t.gap);
     case score_target::MUTATION: return mutation_stage(ctx, m, t.X, t.K, t.what, t.out);
     case score_target::CONTACT: break;
@@ -2761,6 +2781,224 @@ gdca_status gdca_run_partner_match_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                       partner_target(pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, what, E_dev), blk, match_dev, gap_dev), st);
 }
 
+// ---- iterative partner matching: the selection, the concatenation and the loop (k_ipa.hip) ----
+// the selection enqueued: sel_dev and the counts record (ctx->IPAcnt)
+static gdca_status select_stage(gdca_ctx *ctx, const int32_t *match_dev, const double *gap_dev, int KA, int n_take, int32_t *sel_dev)
+{
+    CHK(ensure(ctx, ctx->IPAws, gdca_ipa_select_ws_bytes(KA)));
+    CHK(ensure(ctx, ctx->IPAcnt, sizeof(gdca_ipa_counts)));
+    gdca_launch_ipa_select(ctx->stream, match_dev, gap_dev, KA, n_take, ctx->IPAws.p, sel_dev, (gdca_ipa_counts *)ctx->IPAcnt.p);
+    return check_launch(ctx, "selection");
+}
+
+// the counts record on the host (one copy of a few scalars, one synchronisation)
+static gdca_status fetch_counts(gdca_ctx *ctx, gdca_ipa_counts *h)
+{
+    HIPCHK(hipMemcpyAsync(h, ctx->IPAcnt.p, sizeof(*h), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GDCA_OK;
+}
+
+gdca_status gdca_select_confident_dev(gdca_ctx *ctx, const int32_t *match_dev, const double *gap_dev, int32_t KA, int32_t n_take, int32_t *sel_dev,
+                                      int32_t *n_sel)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (!match_dev || !gap_dev || !sel_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (KA < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    CHK(not_pending(ctx));
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(select_stage(ctx, match_dev, gap_dev, KA, n_take, sel_dev));
+    gdca_ipa_counts h;
+    CHK(fetch_counts(ctx, &h));
+    if (n_sel) *n_sel = h.n_sel;
+    return GDCA_OK;
+}
+
+// the argument checks of the two concatenation entry points (nothing has run when one fails)
+static gdca_status validate_concat(gdca_ctx *ctx, int KA, int KB, int N, int split, int n_sel, long long col0)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (N < 2 || split < 1 || split > N - 1) return fail(ctx, GDCA_EINVAL, "invalid split (must be between 1 and N - 1)%s%s", "", "");
+    if (KA < 1 || KB < 1 || n_sel < 0 || col0 < 0 || col0 + n_sel > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    return GDCA_OK;
+}
+
+gdca_status gdca_concat_pairs_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t N, int32_t split,
+                                  const int32_t *selA_dev, const int32_t *selB_dev, int32_t n_sel, int8_t *Z_dev, int32_t col0)
+{
+    CHK(validate_concat(ctx, KA, KB, N, split, n_sel, col0));
+    if (!XA_dev || !XB_dev || !Z_dev || (n_sel > 0 && (!selA_dev || !selB_dev))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(begin(ctx));
+    gdca_launch_ipa_concat(ctx->stream, XA_dev, KA, XB_dev, KB, N, split, selA_dev, selB_dev, nullptr, n_sel, Z_dev, (size_t)col0,
+                           (gdca_dev_scalars *)ctx->sc.p);
+    CHK(check_launch(ctx, "concatenation"));
+    CHK(fetch_scalars(ctx));
+    if (ctx->sc_host->bad_symbol & 8) return fail(ctx, GDCA_EINVAL, "a selected index is outside its pool%s%s", "", "");
+    return GDCA_OK;
+}
+
+// What gdca_run_partner_ipa(_dev) checks on the host before anything runs, and what the checks leave behind: the species of every a,
+// and the seed as pairs in ascending a.
+struct ipa_plan {
+    std::vector<int32_t> spA, seedA, seedB;
+};
+
+static gdca_status ipa_check(gdca_ctx *ctx, int32_t KA, int32_t KB, const void *offA_, const void *offB_, int32_t S, int32_t N, int32_t q,
+                             int32_t split, int32_t what, const gdca_params *p, int32_t Mfix, const int32_t *seedA, const int32_t *seedB,
+                             int32_t n_seed, int32_t n_inc, int32_t max_rounds, ipa_plan *plan)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (Mfix < 0 || n_seed < 0 || (long long)Mfix + n_seed < 1)
+        return fail(ctx, GDCA_EINVAL, "no training pairs: Zfix and the seed are both empty%s%s", "", "");
+    if (n_inc < 1 || max_rounds < 1) return fail(ctx, GDCA_EINVAL, "n_inc and max_rounds must be at least 1%s%s", "", "");
+    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
+    if ((long long)Mfix + KA > INT32_MAX || (long long)Mfix + n_seed > INT32_MAX)
+        return fail(ctx, GDCA_EINVAL, "invalid alignment size%s%s", "", "");
+    if (!offA_ || !offB_ || !p || (n_seed > 0 && (!seedA || !seedB))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_params(ctx, p));
+    const int32_t *offA = (const int32_t *)offA_, *offB = (const int32_t *)offB_;
+    int kmax = 0;
+    if (blocks_length(offA, offB, S, &kmax) < 0 || offA[S] != KA || offB[S] != KB)
+        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
+    if (kmax > GDCA_ASSIGN_MAX) return fail(ctx, GDCA_EINVAL, "a species has more than GDCA_ASSIGN_MAX sequences on one side%s%s", "", "");
+    plan->spA.assign((size_t)KA, 0);
+    std::vector<int32_t> spB((size_t)KB, 0);
+    for (int s = 0; s < S; ++s) {
+        std::fill(plan->spA.begin() + offA[s], plan->spA.begin() + offA[s + 1], s);
+        std::fill(spB.begin() + offB[s], spB.begin() + offB[s + 1], s);
+    }
+    std::vector<char> usedA((size_t)KA, 0), usedB((size_t)KB, 0);
+    std::vector<std::pair<int32_t, int32_t>> seed;
+    for (int t = 0; t < n_seed; ++t) {
+        const int32_t a = seedA[t], b = seedB[t];
+        if (a < 0 || a >= KA || b < 0 || b >= KB) return fail(ctx, GDCA_EINVAL, "a seed index is outside its pool%s%s", "", "");
+        if (plan->spA[(size_t)a] != spB[(size_t)b]) return fail(ctx, GDCA_EINVAL, "a seed pair joins two species%s%s", "", "");
+        if (usedA[(size_t)a] || usedB[(size_t)b]) return fail(ctx, GDCA_EINVAL, "a sequence appears twice in the seed%s%s", "", "");
+        usedA[(size_t)a] = usedB[(size_t)b] = 1;
+        seed.emplace_back(a, b);
+    }
+    std::sort(seed.begin(), seed.end());
+    for (const auto &ab : seed) {
+        plan->seedA.push_back(ab.first);
+        plan->seedB.push_back(ab.second);
+    }
+    return GDCA_OK;
+}
+
+gdca_status gdca_run_partner_ipa_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA,
+                                     const void *offB, int32_t S, int32_t N, int32_t q, int32_t split, int32_t what, const gdca_params *p,
+                                     const int8_t *Zfix_dev, int32_t Mfix, const int32_t *seedA, const int32_t *seedB, int32_t n_seed,
+                                     int32_t n_inc, int32_t max_rounds, int32_t *match_dev, double *gap_dev, int32_t *match_trace_dev,
+                                     double *gap_trace_dev, double *rounds_out, int32_t *rounds_run, gdca_stats *st)
+{
+    ipa_plan plan;
+    CHK(ipa_check(ctx, KA, KB, offA, offB, S, N, q, split, what, p, Mfix, seedA, seedB, n_seed, n_inc, max_rounds, &plan));
+    if (!XA_dev || !XB_dev || !match_dev || (Mfix > 0 && !Zfix_dev)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(not_pending(ctx));
+    if (rounds_run) *rounds_run = 0;
+    hipStream_t s = ctx->stream;
+    // ---- once per call: the species table and the gather's work list, the species of every a, the packed pools and their symbol check ----
+    pair_blocks blk;
+    std::vector<long long> first;
+    CHK(species_blocks(ctx, offA, offB, S, KA, KB, (N - split) * (q - 1), true, &blk, first));
+    const size_t ni = (size_t)KA * sizeof(int32_t), ng = (size_t)KA * sizeof(double);
+    CHK(ensure(ctx, ctx->IPAsp, ni));
+    CHK(ensure(ctx, ctx->IPAsel, 2 * ni));
+    CHK(ensure(ctx, ctx->IPAm, ni));
+    CHK(ensure(ctx, ctx->IPAg, ng));
+    CHK(ensure(ctx, ctx->IPAprev, ni));
+    CHK(ensure(ctx, ctx->IPAZ, (size_t)N * ((size_t)Mfix + (size_t)KA)));
+    CHK(ensure(ctx, ctx->PBE, (size_t)blk.total * sizeof(double)));
+    int32_t *sel = (int32_t *)ctx->IPAsel.p, *selB = sel + KA, *m_dev = (int32_t *)ctx->IPAm.p, *prev = (int32_t *)ctx->IPAprev.p;
+    double *g_dev = (double *)ctx->IPAg.p, *E_dev = (double *)ctx->PBE.p;
+    int8_t *Z = (int8_t *)ctx->IPAZ.p;
+    HIPCHK(hipMemcpyAsync(ctx->IPAsp.p, plan.spA.data(), ni, hipMemcpyHostToDevice, s));
+    if (n_seed > 0) {
+        HIPCHK(hipMemcpyAsync(sel, plan.seedA.data(), (size_t)n_seed * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(selB, plan.seedB.data(), (size_t)n_seed * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    CHK(begin(ctx));
+    CHK(pair_pack(ctx, N, q, split, XA_dev, (size_t)split, KA, XB_dev, (size_t)(N - split), KB, what));
+    CHK(sequences_checked(ctx));  // (a synchronisation: the host arrays above have been read as well)
+    // ---- the first training alignment: Zfix once, the seed behind it ----
+    if (Mfix > 0) HIPCHK(hipMemcpyAsync(Z, Zfix_dev, (size_t)N * Mfix, hipMemcpyDeviceToDevice, s));
+    gdca_launch_ipa_concat(s, XA_dev, KA, XB_dev, KB, N, split, sel, selB, nullptr, n_seed, Z, (size_t)Mfix, (gdca_dev_scalars *)ctx->sc.p);
+    CHK(check_launch(ctx, "concatenation"));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    const bool timed = ctx->timing && rounds_out;
+    if (timed && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) {
+        if (ev0) (void)hipEventDestroy(ev0);
+        return fail(ctx, GDCA_EHIP, "hipEventCreate%s%s", "", "");
+    }
+    gdca_status rs = GDCA_OK;
+    int M = Mfix + n_seed, sel_before = -1, cand_before = -2;
+    for (int r = 1; r <= max_rounds; ++r) {
+        // ---- fit and match: the fused partner match's own code on Z_r, the pools as packed above ----
+        score_target t = partner_target(pair_target(Z, N, M, split, XA_dev, KA, XB_dev, KB, what, E_dev), blk, m_dev, g_dev);
+        t.packed = true;
+        gdca_stats fit;
+        rs = run_target(ctx, Z, N, M, q, p, t, &fit);
+        if (st) *st = fit;
+        if (rs != GDCA_OK) break;
+        // ---- the round is complete: its figures, its results where the caller wants them, the selection ----
+        gdca_status gs = GDCA_OK;
+        auto step = [&](hipError_t e) {
+            if (e != hipSuccess && gs == GDCA_OK) gs = fail(ctx, GDCA_EHIP, "iterative partner matching: %s%s", hipGetErrorString(e), "");
+        };
+        if (timed) step(hipEventRecord(ev0, s));
+        gs = gs != GDCA_OK ? gs : ensure(ctx, ctx->IPAcnt, sizeof(gdca_ipa_counts));
+        if (gs == GDCA_OK) {
+            gdca_launch_ipa_round(s, E_dev, blk.eoff, blk.offA, blk.offB, (const int32_t *)ctx->IPAsp.p, m_dev, r > 1 ? prev : nullptr, KA,
+                                  (gdca_ipa_counts *)ctx->IPAcnt.p);
+            gs = check_launch(ctx, "round figures");
+        }
+        if (gs == GDCA_OK) {  // (behind the figures: they read the match of the round before)
+            gdca_launch_ipa_publish(s, m_dev, g_dev, KA, prev, match_dev, gap_dev, match_trace_dev ? match_trace_dev + (size_t)(r - 1) * KA : nullptr,
+                                    gap_trace_dev ? gap_trace_dev + (size_t)(r - 1) * KA : nullptr);
+            gs = check_launch(ctx, "round results");
+        }
+        const int n_take = (int)std::min<long long>((long long)r * n_inc, KA);
+        if (gs == GDCA_OK) gs = select_stage(ctx, m_dev, g_dev, KA, n_take, sel);
+        if (timed) step(hipEventRecord(ev1, s));
+        gdca_ipa_counts h{};
+        if (gs == GDCA_OK) gs = fetch_counts(ctx, &h);
+        if (gs != GDCA_OK) {
+            rs = gs;
+            break;
+        }
+        if (rounds_out) {
+            double *row = rounds_out + (size_t)(r - 1) * GDCA_IPA_FIELDS;
+            float ms = 0.0f;
+            if (timed) step(hipEventElapsedTime(&ms, ev0, ev1));
+            row[GDCA_IPA_M_TRAIN] = (double)M;
+            row[GDCA_IPA_CANDIDATES] = (double)h.ncand;
+            row[GDCA_IPA_N_SEL] = (double)h.n_sel;
+            row[GDCA_IPA_N_CHANGED] = (double)h.n_changed;
+            row[GDCA_IPA_MEFF] = fit.Meff;
+            row[GDCA_IPA_THETA] = fit.theta;
+            row[GDCA_IPA_LOGDET] = ctx->ld.count > 0 ? ctx->ld.val[0] : (double)NAN;
+            row[GDCA_IPA_COST] = h.cost;
+            row[GDCA_IPA_MS_FIT] = fit.ms_total - fit.ms_score;
+            row[GDCA_IPA_MS_MATCH] = fit.ms_score;
+            row[GDCA_IPA_MS_SELECT] = (double)ms;
+            row[GDCA_IPA_RESERVED] = 0.0;
+        }
+        if (rounds_run) *rounds_run = r;
+        // ---- the stop rule, else the next training alignment: Zfix stays, the selected pairs behind it in ascending a ----
+        if (r == max_rounds || (r >= 2 && sel_before == cand_before) || Mfix + h.n_sel < 1) break;
+        gdca_launch_ipa_concat(s, XA_dev, KA, XB_dev, KB, N, split, sel, nullptr, m_dev, h.n_sel, Z, (size_t)Mfix, (gdca_dev_scalars *)ctx->sc.p);
+        rs = check_launch(ctx, "concatenation");
+        if (rs != GDCA_OK) break;
+        M = Mfix + h.n_sel;
+        sel_before = h.n_sel;
+        cand_before = h.ncand;
+    }
+    (void)hipStreamSynchronize(s);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    return rs;
+}
+
 // the argument checks the four mutation-scan entry points share (nothing has run when one fails); K as it will be used
 static gdca_status validate_mutation(gdca_ctx *ctx, int N, int q, long long K, int what)
 {
@@ -3139,6 +3377,77 @@ gdca_status gdca_run_partner_match(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
     if (E_host && ne) CHK(to_host(ctx, E_host, ctx->scratch[5], ne));
     if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
     return to_host(ctx, match_host, ctx->scratch[6], nm);
+}
+
+gdca_status gdca_select_confident(gdca_ctx *ctx, const int32_t *match, const double *gap, int32_t KA, int32_t n_take, int32_t *sel, int32_t *n_sel)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (!match || !gap || !sel) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (KA < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ni = (size_t)KA * sizeof(int32_t);
+    gdca_status up = GDCA_OK;
+    const int32_t *match_dev = (const int32_t *)upload(ctx, 6, match, ni, &up);
+    const double *gap_dev = (const double *)upload(ctx, 7, gap, (size_t)KA * sizeof(double), &up);
+    int32_t *sel_dev = (int32_t *)staged_out(ctx, 8, ni, &up);
+    CHK(up);
+    CHK(gdca_select_confident_dev(ctx, match_dev, gap_dev, KA, n_take, sel_dev, n_sel));
+    return to_host(ctx, sel, ctx->scratch[8], ni);
+}
+
+// (Z is the caller's whole alignment: only the requested columns are staged on the device and written back, and none where an index is bad)
+gdca_status gdca_concat_pairs(gdca_ctx *ctx, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, int32_t N, int32_t split,
+                              const int32_t *selA, const int32_t *selB, int32_t n_sel, int8_t *Z, int32_t col0)
+{
+    CHK(validate_concat(ctx, KA, KB, N, split, n_sel, col0));
+    if (!XA || !XB || !Z || (n_sel > 0 && (!selA || !selB))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (n_sel == 0) return GDCA_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ni = (size_t)n_sel * sizeof(int32_t), nz = (size_t)N * n_sel;
+    gdca_status up = GDCA_OK;
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB, (size_t)(N - split) * KB, &up);
+    const int32_t *selA_dev = (const int32_t *)upload(ctx, 6, selA, ni, &up);
+    const int32_t *selB_dev = (const int32_t *)upload(ctx, 8, selB, ni, &up);
+    int8_t *Z_dev = (int8_t *)staged_out(ctx, 0, nz, &up);
+    CHK(up);
+    CHK(gdca_concat_pairs_dev(ctx, XA_dev, KA, XB_dev, KB, N, split, selA_dev, selB_dev, n_sel, Z_dev, 0));
+    return to_host(ctx, Z + (size_t)col0 * N, ctx->scratch[0], nz);
+}
+
+gdca_status gdca_run_partner_ipa(gdca_ctx *ctx, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA,
+                                 const void *offB, int32_t S, int32_t N, int32_t q, int32_t split, int32_t what, const gdca_params *p,
+                                 const int8_t *Zfix_host, int32_t Mfix, const int32_t *seedA, const int32_t *seedB, int32_t n_seed, int32_t n_inc,
+                                 int32_t max_rounds, int32_t *match_host, double *gap_host, int32_t *match_trace_host, double *gap_trace_host,
+                                 double *rounds_out, int32_t *rounds_run, gdca_stats *st)
+{
+    {
+        ipa_plan plan;  // (the same checks before anything is uploaded: the sizes below are the caller's)
+        CHK(ipa_check(ctx, KA, KB, offA, offB, S, N, q, split, what, p, Mfix, seedA, seedB, n_seed, n_inc, max_rounds, &plan));
+    }
+    if (!XA_host || !XB_host || !match_host || (Mfix > 0 && !Zfix_host)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nm = (size_t)KA * sizeof(int32_t), ng = (size_t)KA * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const int8_t *Zfix_dev = Mfix > 0 ? (const int8_t *)upload(ctx, 0, Zfix_host, (size_t)N * Mfix, &up) : nullptr;
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
+    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
+    double *gap_dev = staged_out(ctx, 7, ng, &up);
+    int32_t *mt_dev = match_trace_host ? (int32_t *)staged_out(ctx, 8, nm * max_rounds, &up) : nullptr;
+    double *gt_dev = gap_trace_host ? staged_out(ctx, 9, ng * max_rounds, &up) : nullptr;
+    CHK(up);
+    int32_t done = 0;
+    const gdca_status rs = gdca_run_partner_ipa_dev(ctx, XA_dev, KA, XB_dev, KB, offA, offB, S, N, q, split, what, p, Zfix_dev, Mfix, seedA, seedB,
+                                                    n_seed, n_inc, max_rounds, match_dev, gap_dev, mt_dev, gt_dev, rounds_out, &done, st);
+    if (rounds_run) *rounds_run = done;
+    if (done > 0) {  // (the last completed round's, also where a later round's fit failed)
+        if (match_trace_host) CHK(to_host(ctx, match_trace_host, ctx->scratch[8], nm * done));
+        if (gap_trace_host) CHK(to_host(ctx, gap_trace_host, ctx->scratch[9], ng * done));
+        if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
+        CHK(to_host(ctx, match_host, ctx->scratch[6], nm));
+    }
+    return rs;
 }
 
 gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,

@@ -31,7 +31,8 @@ struct gdca_dev_scalars {
     unsigned long long pair_sum;
     int thresh;
     int info;
-    int bad_symbol;  // bit 0: a byte of Z is outside 1..q; bit 1: a caller-given weight is outside [0, 1] (GDCA_EINVAL)
+    int bad_symbol;  // bit 0: a byte of Z is outside 1..q; bit 1: a caller-given weight is outside [0, 1]; bit 2: a byte of the scored sequences is
+                     // outside 1..q; bit 3: an index of gdca_concat_pairs is outside its pool (GDCA_EINVAL)
     int di_noconv;   // number of site pairs whose tridiagonal QL iteration did not converge (DI score)
     int ham_mode;    // all-pairs Hamming kernel chosen for this family: 0 = exact distances, 1 = three-plane lower bound + refinement, 2 = the consensus
                      // lower bound on the fp4 matrix pipe + refinement (k_hamming_fp4.hip)
@@ -221,6 +222,19 @@ void gdca_launch_spd_inverse_merged(hipStream_t s, const gdca_inverse_job *jobs,
 // left in three arrays inside the workspace `ws` (gdca_ranking_ws_bytes(len) bytes)
 size_t gdca_ranking_ws_bytes(long long len);
 void gdca_launch_ranking(hipStream_t s, const double *S_dev, int N, int sep, long long len, void *ws, int32_t **ii, int32_t **jj, double **sc);
+// the 64-bit key of the ranking's order (the host form's, gdca_host.cpp): ascending keys = descending scores under isless, NaN first,
+// 0.0 before -0.0
+__device__ __forceinline__ uint64_t gdca_rank_key(double x)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(x);
+    uint64_t asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // ascending in isless order: -0.0 < 0.0
+    if (x != x) asc = ~0ull;                                        // every NaN greatest, all equal
+    return ~asc;                                                    // descending
+}
+// The ranking's eight stable radix passes on given keys and values: n entries in key[0] / val[0], sorted ascending by key into key[0] /
+// val[0] again (equal keys keep their order); key[1] / val[1]: as large; hist: gdca_sort_hist_words(n) words
+size_t gdca_sort_hist_words(size_t n);
+void gdca_launch_sort_pairs(hipStream_t s, uint64_t *const key[2], uint32_t *const val[2], uint32_t *hist, size_t n);
 void gdca_launch_probe_mfma_f64(hipStream_t s, double *out, int iters, int blocks);
 // The reference's own way (dpotrf + dpotri) as a fallback for matrices the sweep cannot handle: C2 (n_pad x n_pad, identity
 // padding; overwritten by its Cholesky factor), U and Tm: n_pad x n_pad workspaces, Wd: (n_pad / 128) tiles of 128 x 128; Aout
@@ -311,6 +325,31 @@ hipError_t gdca_launch_pair_chunk_blocked(hipStream_t s, const double *A, size_t
 // kB_s (<= GDCA_ASSIGN_MAX)
 hipError_t gdca_launch_assign_blocks(hipStream_t s, const double *E, const long long *eoff, const int32_t *offA, const int32_t *offB, int S,
                                      int kmax, int32_t *match, double *gap);
+
+// ---- k_ipa.hip: the glue between two rounds of iterative partner matching ---------------------------------------------------------------
+// what a round hands to the host (device record; every field written by a kernel, nothing accumulated)
+struct gdca_ipa_counts {
+    double cost;     // sum over the candidates in ascending a of E[a, match[a]] (k_ipa_round)
+    int n_changed;   // a whose match differs from the round before; without a round before: the candidates (k_ipa_round)
+    int ncand;       // a with match[a] >= 0 (k_ipa_compact)
+    int n_sel;       // the selected (k_ipa_compact)
+    int pad_;
+};
+// The selection (include/gdca.h, gdca_select_confident_dev): sel[KA] = the first min(n_take, candidates) candidates by gap descending (the
+// ranking's order, ties in ascending a), in ascending a, then -1; out->ncand, out->n_sel.  ws: gdca_ipa_select_ws_bytes(KA) bytes
+size_t gdca_ipa_select_ws_bytes(int KA);
+void gdca_launch_ipa_select(hipStream_t s, const int32_t *match, const double *gap, int KA, int n_take, void *ws, int32_t *sel, gdca_ipa_counts *out);
+// Columns col0 .. col0 + n_sel - 1 of Z (N rows): XA[:, selA[t]] over XB[:, b], b = viaB ? viaB[selA[t]] : selB[t]; an index outside its
+// pool: bit 3 of sc->bad_symbol, that column left alone
+void gdca_launch_ipa_concat(hipStream_t s, const int8_t *XA, int KA, const int8_t *XB, int KB, int N, int split, const int32_t *selA,
+                            const int32_t *selB, const int32_t *viaB, int n_sel, int8_t *Z, size_t col0, gdca_dev_scalars *sc);
+// out->cost, out->n_changed of a round's match against the packed blocks E (eoff, offA, offB: the species table; spA[a]: a's species;
+// prev: the match of the round before, or nullptr)
+void gdca_launch_ipa_round(hipStream_t s, const double *E, const long long *eoff, const int32_t *offA, const int32_t *offB, const int32_t *spA,
+                           const int32_t *match, const int32_t *prev, int KA, gdca_ipa_counts *out);
+// a completed round's match / gap (KA entries) into prev, match_out and -- each may be nullptr -- gap_out, match_row, gap_row
+void gdca_launch_ipa_publish(hipStream_t s, const int32_t *match, const double *gap, int KA, int32_t *prev, int32_t *match_out, double *gap_out,
+                             int32_t *match_row, double *gap_row);
 
 // ---- k_mutation.hip: V(x; i, c) / dE(x; i, b) of every single substitution of K sequences ------------------------------------------------
 // D[(b - 1) + q (i + N k)] (q = sdim + 1; what: GDCA_MUT_DELTA | GDCA_MUT_POTENTIAL) of the K sequences packed by gdca_launch_energy_pack

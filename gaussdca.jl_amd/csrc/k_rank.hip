@@ -21,14 +21,6 @@ namespace {
 
 constexpr int RK_THREADS = 256, RK_E = 16, RK_CHUNK = RK_THREADS * RK_E, RK_ROW = 258;  // (row of 258 u16 = 129 words: equal digits of different threads fall into different banks)
 
-__device__ __forceinline__ uint64_t rank_key(double x)
-{
-    const uint64_t u = (uint64_t)__double_as_longlong(x);
-    uint64_t asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // ascending in isless order: -0.0 < 0.0
-    if (x != x) asc = ~0ull;                                        // every NaN greatest, all equal
-    return ~asc;                                                    // descending
-}
-
 // row i = blockIdx.x + 1 of the enumeration: entries (i, j), j = i + sep .. N, at offset (i-1)(N-sep) - (i-1)(i-2)/2
 struct k_rank_keys_args {
     const double *S;
@@ -55,7 +47,7 @@ __global__ __launch_bounds__(256) void k_rank_keys(const BatchArgs<k_rank_keys_a
     const long long off = (long long)(i - 1) * d - (long long)(i - 1) * (i - 2) / 2;
     for (int j = i + sep + (int)threadIdx.x; j <= N; j += 256) {
         const long long t = off + (j - i - sep);
-        key[t] = rank_key(S[(size_t)(j - 1) + (size_t)(i - 1) * N]);
+        key[t] = gdca_rank_key(S[(size_t)(j - 1) + (size_t)(i - 1) * N]);
         val[t] = ((uint32_t)i << 16) | (uint32_t)j;
     }
 }
@@ -249,6 +241,26 @@ size_t gdca_ranking_ws_bytes(long long len)
     return 2 * up256(n * 8) + 2 * up256(n * 4) + up256(256 * nchunk * 4) + 2 * up256(n * 4) + up256(n * 8);
 }
 
+// The eight radix passes on given keys and values: n entries in key[0] / val[0], sorted (stable, ascending by key) into key[0] / val[0]
+// again; key[1] / val[1]: as large, hist: 256 * ceil(n / 4096) words.  What the ranking and the selection of k_ipa.hip share.
+void gdca_launch_sort_pairs(hipStream_t s, uint64_t *const key[2], uint32_t *const val[2], uint32_t *hist, size_t n)
+{
+    const int nchunk = (int)((n + RK_CHUNK - 1) / RK_CHUNK);
+    const size_t lds = (size_t)RK_THREADS * RK_ROW * sizeof(uint16_t);
+    // (dynamic LDS beyond 48 KB: the launcher raises the kernel's limit, gdca_launch.h)
+    for (int pass = 0; pass < 8; ++pass) {
+        const int a = pass & 1, b = a ^ 1, shift = 8 * pass;
+        (gdca_launch<k_rank_hist_args, k_rank_hist<1>, k_rank_hist<GDCA_MAXB>>(dim3((unsigned)nchunk), dim3(256), 0, s, k_rank_hist_mk(key[a], n, shift, hist, nchunk)));
+        (gdca_launch<k_rank_scan_args, k_rank_scan<1>, k_rank_scan<GDCA_MAXB>>(dim3(1), dim3(256), 0, s, k_rank_scan_mk(hist, nchunk)));
+        (gdca_launch<k_rank_scatter_args, k_rank_scatter<1>, k_rank_scatter<GDCA_MAXB>>(dim3((unsigned)nchunk), dim3(256), lds, s, k_rank_scatter_mk(key[a], val[a], key[b], val[b], n, shift, hist, nchunk)));
+    }
+}
+
+size_t gdca_sort_hist_words(size_t n)
+{
+    return (size_t)256 * ((n + RK_CHUNK - 1) / RK_CHUNK);
+}
+
 void gdca_launch_ranking(hipStream_t s, const double *S_dev, int N, int sep, long long len, void *ws, int32_t **ii, int32_t **jj, double **sc)
 {
     const size_t n = (size_t)len;
@@ -265,14 +277,7 @@ void gdca_launch_ranking(hipStream_t s, const double *S_dev, int N, int sep, lon
     *ii = (int32_t *)p, p += up256(n * 4);
     *jj = (int32_t *)p, p += up256(n * 4);
     *sc = (double *)p;
-    const size_t lds = (size_t)RK_THREADS * RK_ROW * sizeof(uint16_t);
-    // (dynamic LDS beyond 48 KB: the launcher raises the kernel's limit, gdca_launch.h)
     (gdca_launch<k_rank_keys_args, k_rank_keys<1>, k_rank_keys<GDCA_MAXB>>(dim3((unsigned)(N - sep)), dim3(256), 0, s, k_rank_keys_mk(S_dev, N, sep, key[0], val[0])));
-    for (int pass = 0; pass < 8; ++pass) {
-        const int a = pass & 1, b = a ^ 1, shift = 8 * pass;
-        (gdca_launch<k_rank_hist_args, k_rank_hist<1>, k_rank_hist<GDCA_MAXB>>(dim3((unsigned)nchunk), dim3(256), 0, s, k_rank_hist_mk(key[a], n, shift, hist, nchunk)));
-        (gdca_launch<k_rank_scan_args, k_rank_scan<1>, k_rank_scan<GDCA_MAXB>>(dim3(1), dim3(256), 0, s, k_rank_scan_mk(hist, nchunk)));
-        (gdca_launch<k_rank_scatter_args, k_rank_scatter<1>, k_rank_scatter<GDCA_MAXB>>(dim3((unsigned)nchunk), dim3(256), lds, s, k_rank_scatter_mk(key[a], val[a], key[b], val[b], n, shift, hist, nchunk)));
-    }
+    gdca_launch_sort_pairs(s, key, val, hist, n);
     (gdca_launch<k_rank_emit_args, k_rank_emit<1>, k_rank_emit<GDCA_MAXB>>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, k_rank_emit_mk(val[0], n, S_dev, N, *ii, *jj, *sc)));
 }

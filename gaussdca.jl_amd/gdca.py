@@ -278,6 +278,80 @@ def gDCA_partner_match(filename: str, split: int, seqs_a=None, seqs_b=None, spec
     return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, check, run, "matches")
 
 
+def gDCA_partner_ipa(seqs_a, seqs_b, species_a, species_b, known_pairs=None, seed="singletons", n_inc: int = 6, max_rounds: int = 50,
+                     what="energy", pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9, q=None, ctx=None, **kw):
+    """Iterative partner matching (progressive paralog matching / the iterative pairing algorithm) for two alignments without a
+    trusted alignment of pairs: fit on the pairs trusted so far, match every species (``gDCA_partner_match``'s fit and assignment),
+    keep the ``r * n_inc`` most confident matches of round r as the next training set, repeat -- on the device, the pools and the
+    growing alignment resident from the first round to the last (``gdca_run_partner_ipa``).
+
+    ``seqs_a`` / ``seqs_b``: the two sides, ``(sites, K)`` int8 arrays (symbols 1..q) or FASTA files (every record kept);
+    ``species_a`` / ``species_b``: one integer label per sequence, in any order.  ``seed``: ``"singletons"`` -- the species with
+    exactly one sequence on each side -- or a list of ``(a, b)`` index pairs (the caller's indices; a pair lies inside one species);
+    it is the first training set and is replaced from round 1 on.  ``known_pairs``: an alignment file of concatenated pairs A (+) B
+    (read as gDCA reads its input, ``max_gap_fraction``) that is part of every round's training alignment.  The loop ends after
+    ``max_rounds`` rounds, or one round after the training set held every matched sequence.  ``q``: the alphabet (default: the
+    largest symbol present).
+
+    Returns ``(match, gap, rounds)``: match / gap of the last round in the caller's order, as ``gDCA_partner_match`` returns them;
+    ``rounds``: one dict a round (``M_train, candidates, n_sel, n_changed, Meff, theta, logdet, cost, ms_*``).  The last fit's stats
+    go to ``last_stats``."""
+    global last_stats
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_partner_ipa() got unexpected keyword arguments {sorted(kw)}")
+    if not (isinstance(pseudocount, (int, float, np.integer, np.floating)) and 0 <= pseudocount <= 1):
+        raise ArgumentError(f"invalid pseudocount value: {pseudocount} (must be between 0 and 1)")
+    th, w = _theta_arg(theta), _what_arg(what)
+    XA, XB = _sequences_arg(seqs_a, "seqs_a", "a sites x K"), _sequences_arg(seqs_b, "seqs_b", "a sites x K")
+    if XA is None or XB is None or species_a is None or species_b is None:
+        raise ArgumentError("seqs_a, seqs_b, species_a and species_b are all needed")
+    if XA.shape[1] < 1 or XB.shape[1] < 1:
+        raise ArgumentError("seqs_a or seqs_b holds no sequence")
+    for k, name in ((n_inc, "n_inc"), (max_rounds, "max_rounds")):
+        if not isinstance(k, (int, np.integer)) or k < 1:
+            raise ArgumentError(f"invalid {name} value: {k} (must be an integer >= 1)")
+    split, N = XA.shape[0], XA.shape[0] + XB.shape[0]
+    perm_a, perm_b, offA, offB, _ = species_blocks(species_a, species_b)
+    if len(perm_a) != XA.shape[1] or len(perm_b) != XB.shape[1]:
+        raise ArgumentError(f"species_a / species_b have {len(perm_a)} / {len(perm_b)} labels for {XA.shape[1]} / {XB.shape[1]} sequences")
+    Zfix = None
+    if known_pairs is not None:
+        if not os.path.isfile(known_pairs):
+            raise ArgumentError(f"cannot open file {known_pairs}")
+        Zfix = np.asfortranarray(read_fasta_alignment(os.fspath(known_pairs), max_gap_fraction), dtype=np.int8)
+        if Zfix.shape[0] != N:
+            raise ArgumentError(f"known_pairs has {Zfix.shape[0]} sites, the two sides have {N}")
+    # the seed in the species-sorted order the library works in
+    inv_a, inv_b = np.empty_like(perm_a), np.empty_like(perm_b)
+    inv_a[perm_a], inv_b[perm_b] = np.arange(len(perm_a)), np.arange(len(perm_b))
+    if isinstance(seed, str):
+        if seed.lstrip(":") != "singletons":
+            raise ArgumentError(f"invalid seed value: {seed} (must be singletons or a list of index pairs)")
+        one = np.nonzero((np.diff(offA) == 1) & (np.diff(offB) == 1))[0]
+        seedA, seedB = offA[one].astype(np.int32), offB[one].astype(np.int32)
+    else:
+        pairs = np.asarray(seed if seed is not None else [], dtype=np.int64).reshape(-1, 2)
+        if pairs.size and (pairs.min() < 0 or pairs[:, 0].max() >= len(perm_a) or pairs[:, 1].max() >= len(perm_b)):
+            raise ArgumentError("a seed index is outside its side")
+        seedA, seedB = inv_a[pairs[:, 0]].astype(np.int32), inv_b[pairs[:, 1]].astype(np.int32)
+    if len(seedA) + (0 if Zfix is None else Zfix.shape[1]) < 1:
+        raise ArgumentError("nothing to fit the first round on: no seed pair and no known_pairs")
+    qq = int(q) if q is not None else int(max(XA.max(), XB.max(), 0 if Zfix is None else Zfix.max()))
+    if qq >= 32:
+        raise RuntimeError(f"parameter q={qq} is too big (max 31 is allowed)")
+    XAs, XBs = np.asfortranarray(XA[:, perm_a]), np.asfortranarray(XB[:, perm_b])
+    c = ctx or default_context()
+    (m, g, _, _), rounds, last_stats = c.run_partner_ipa_ptr(XAs.ctypes.data, XAs.shape[1], XBs.ctypes.data, XBs.shape[1], offA, offB, N, qq, split,
+                                                             float(pseudocount), th, None if Zfix is None else Zfix.ctypes.data,
+                                                             0 if Zfix is None else Zfix.shape[1], seedA, seedB, int(n_inc), int(max_rounds), w)
+    match, gap = np.empty_like(m), np.empty_like(g)
+    match[perm_a] = np.where(m >= 0, perm_b[np.maximum(m, 0)], -1)
+    gap[perm_a] = g
+    return match, gap, rounds
+
+
 def gDCA_mutation_scan(filename: str, sequences=None, what="delta", pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
                        remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
     """The mutational landscape of sequences under the Gaussian model gDCA fits to the alignment in ``filename`` (same reading,

@@ -428,6 +428,66 @@ gdca_status gdca_run_partner_match_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                                        const void *offA, const void *offB, int32_t S, int32_t what, double *E_dev, int32_t *match_dev,
                                        double *gap_dev, gdca_stats *st);
 
+/* ---- iterative partner matching: grow the paired alignment on the device ----------------------------------------------------------
+ * Who wants to pair paralogs usually has no trusted alignment of pairs to fit on: two pools with species labels, and a few certain
+ * pairs.  The published procedure (progressive paralog matching, the iterative pairing algorithm) fits on the pairs trusted so far,
+ * matches every species, keeps the most confident matches as the next training set -- a few more each round -- and repeats.
+ * gdca_run_partner_ipa(_dev) is that loop, with the pools, the species table, the model and the growing alignment resident in HBM from
+ * the first round to the last; the two entry points below are what it runs between two rounds.
+ *
+ * gdca_select_confident(_dev): match / gap as gdca_assign_blocks(_dev) returns them for KA sequences a.  The CANDIDATES are the a with
+ * match[a] >= 0.  They are ordered by gap[a] descending under the total order of gdca_ranking (its 64-bit key: NaN first, then +inf,
+ * 0.0 before -0.0), equal keys in ascending a; the first min(n_take, #candidates) are SELECTED (n_take <= 0: none).  sel (int32, KA
+ * entries) receives the selected a in ASCENDING a and -1 from there on; *n_sel (host; may be NULL) their number.  Radix passes of the
+ * ranking, a flag per a by rank, an exclusive scan, a compaction: no order-dependent atomics, the result is a function of the input
+ * bits.  GDCA_EINVAL: KA < 1, a null pointer.  Synchronous.
+ *
+ * gdca_concat_pairs(_dev): writes columns col0 .. col0 + n_sel - 1 of Z (N x M int8, column-major, M >= col0 + n_sel: the caller's):
+ * column col0 + t is XA[:, selA[t]] (split symbols) over XB[:, selB[t]] (N - split symbols).  One pass, a byte a thread.  An index
+ * outside its pool is GDCA_EINVAL, detected on the device (nothing is read out of bounds for it; columns of valid indices may have
+ * been written, nothing outside the requested columns is).  GDCA_EINVAL with nothing run: split outside 1..N - 1, KA or KB < 1,
+ * n_sel or col0 < 0, a null pointer.  n_sel = 0 writes nothing.  Synchronous.
+ *
+ * gdca_run_partner_ipa(_dev): the pools XA (split x K_A) and XB ((N - split) x K_B) sorted by species, offA / offB / S exactly as for
+ * gdca_run_partner_match; Zfix (N x Mfix; NULL with Mfix = 0): pairs that are part of EVERY round's training alignment; seedA / seedB
+ * (n_seed HOST int32 each; may be empty): the first training set T_0 as index pairs into the pools.  Round r = 1, 2, ...:
+ *     Z_r = [Zfix | the pairs (a, b) of T_{r-1} in ascending a]  (a grow-only buffer of the context; Zfix is copied once);
+ *     fit on Z_r and match: gdca_run_partner_match's own code, so that ROUND r's match AND gap ARE BIT FOR BIT what
+ *         gdca_run_partner_match returns for Z_r, the same pools and the same parameters (collect-time branches included);
+ *     T_r = the selection of gdca_select_confident with n_take = r n_inc, each selected a paired with match[a].
+ * The pairs are chosen afresh every round, not accumulated: a pool seed is replaced from round 1 on (a pair that is to stay belongs
+ * into Zfix).  The loop ends after round max_rounds, after the first round r >= 2 whose training set already held every candidate of
+ * the round before (n_sel of round r - 1 equalled its candidates), or -- Mfix = 0 only -- after a round that selects nothing.  The
+ * offset checks, the species table, the gather's work list and the packed symbols of the pools with their symbol check are done once
+ * per call; between two rounds only scalars cross PCIe (the fit's status block, the round's counts).
+ *     match, gap (K_A entries; gap may be NULL)              the last completed round's
+ *     match_trace, gap_trace (max_rounds x K_A; may be NULL)  round r's at row r - 1
+ *     rounds_out (HOST f64, max_rounds x GDCA_IPA_FIELDS; may be NULL)  per round, by the GDCA_IPA_* indices: the columns of Z_r, the
+ *         candidates, n_sel, the a whose match differs from the round before (round 1: the candidates), the fit's Meff, theta and
+ *         log det C, the total cost sum over the candidates of E[a, match[a]] (f64, on the device: thread t takes a = t, t + 1024, ..
+ *         ascending, then a fixed binary tree), and -- 0 unless gdca_ctx_set_timing is on -- ms_fit (front end and inverse), ms_match
+ *         (blocked pair stage and assignment) and ms_select (the round's figures, its copies and the selection; the concatenation
+ *         goes with the next round's front end)
+ *     *rounds_run (HOST; may be NULL)  completed rounds;     st: the last fit's stats
+ * GDCA_EINVAL with nothing run and no output touched: the checks of gdca_run_partner_match; Mfix + n_seed < 1; a seed index outside
+ * its pool; a seed pair across two species; an a or a b twice in the seed; n_inc < 1 or max_rounds < 1; Mfix + K_A beyond INT32_MAX.
+ * A bad symbol in a pool is GDCA_EINVAL before the first round.  If a round's fit fails (GDCA_ENOTPD, ..) that status is returned,
+ * *rounds_run counts the completed rounds and match / gap are the last completed round's. */
+enum {
+    GDCA_IPA_M_TRAIN = 0, GDCA_IPA_CANDIDATES, GDCA_IPA_N_SEL, GDCA_IPA_N_CHANGED, GDCA_IPA_MEFF, GDCA_IPA_THETA, GDCA_IPA_LOGDET,
+    GDCA_IPA_COST, GDCA_IPA_MS_FIT, GDCA_IPA_MS_MATCH, GDCA_IPA_MS_SELECT, GDCA_IPA_RESERVED
+};
+#define GDCA_IPA_FIELDS 12
+gdca_status gdca_select_confident_dev(gdca_ctx *ctx, const int32_t *match_dev, const double *gap_dev, int32_t KA, int32_t n_take,
+                                      int32_t *sel_dev, int32_t *n_sel);
+gdca_status gdca_concat_pairs_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t N, int32_t split,
+                                  const int32_t *selA_dev, const int32_t *selB_dev, int32_t n_sel, int8_t *Z_dev, int32_t col0);
+gdca_status gdca_run_partner_ipa_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA,
+                                     const void *offB, int32_t S, int32_t N, int32_t q, int32_t split, int32_t what, const gdca_params *p,
+                                     const int8_t *Zfix_dev, int32_t Mfix, const int32_t *seedA, const int32_t *seedB, int32_t n_seed,
+                                     int32_t n_inc, int32_t max_rounds, int32_t *match_dev, double *gap_dev, int32_t *match_trace_dev,
+                                     double *gap_trace_dev, double *rounds_out, int32_t *rounds_run, gdca_stats *st);
+
 /* ---- mutation scan: the energy change of every single substitution ---------------------------------------------------------
  * The mutational landscape of a sequence under the model (what is compared with deep mutational scans).  Conventions as for the
  * energies above: s = q - 1, n = N s, r(i, c) = i s + c - 1 for symbol c in 1..s at 0-based site i, the gap q has no row, Pi is
@@ -512,6 +572,18 @@ gdca_status gdca_run_partner_match(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
                                    int32_t split, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA,
                                    const void *offB, int32_t S, int32_t what, double *E_host, int32_t *match_host, double *gap_host,
                                    gdca_stats *st);
+
+/* iterative partner matching with host pointers: upload, the _dev form, download (gdca_concat_pairs takes the caller's whole Z and
+ * touches the requested columns alone; after a failed round gdca_run_partner_ipa still brings back the completed rounds' results) */
+gdca_status gdca_select_confident(gdca_ctx *ctx, const int32_t *match, const double *gap, int32_t KA, int32_t n_take, int32_t *sel,
+                                  int32_t *n_sel);
+gdca_status gdca_concat_pairs(gdca_ctx *ctx, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, int32_t N, int32_t split,
+                              const int32_t *selA, const int32_t *selB, int32_t n_sel, int8_t *Z, int32_t col0);
+gdca_status gdca_run_partner_ipa(gdca_ctx *ctx, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA,
+                                 const void *offB, int32_t S, int32_t N, int32_t q, int32_t split, int32_t what, const gdca_params *p,
+                                 const int8_t *Zfix_host, int32_t Mfix, const int32_t *seedA, const int32_t *seedB, int32_t n_seed,
+                                 int32_t n_inc, int32_t max_rounds, int32_t *match_host, double *gap_host, int32_t *match_trace_host,
+                                 double *gap_trace_host, double *rounds_out, int32_t *rounds_run, gdca_stats *st);
 
 /* mutation scan with host pointers: upload, the _dev form, download */
 gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
