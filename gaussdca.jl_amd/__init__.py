@@ -10,9 +10,10 @@ from ._lib import (ArgumentError, Context, ConvergenceError, DeviceBuffer, GdcaE
                    default_context, load)
 from .dcautils import (add_pseudocount, assign_blocks, compute_C, compute_DI_gauss, compute_FN, compute_ranking,  # noqa: F401
                        compute_theta, compute_weighted_frequencies, compute_weights, correct_APC,
-                       inv_cholesky, mutation_scan, neighbour_counts, pair_energies, pair_energies_blocked, pair_identity_sum, printrank,
+                       inv_cholesky, logodds_information, mutation_scan, neighbour_counts, pair_energies, pair_energies_blocked, pair_identity_sum,
+                       pair_logodds, pair_logodds_blocked, printrank,
                        read_fasta_alignment, remove_duplicate_sequences, sequence_energies, sequence_loglik, species_blocks, Ranking)
 from .gdca import (check_arguments, gDCA, gDCA_energies, gDCA_loglik, gDCA_multi, gDCA_mutation_scan, gDCA_pair_energies,  # noqa: F401
-                   gDCA_partner_ipa, gDCA_partner_match)
+                   gDCA_pair_logodds, gDCA_partner_ipa, gDCA_partner_logodds, gDCA_partner_match)
 
 __all__ = ["gDCA", "printrank"]

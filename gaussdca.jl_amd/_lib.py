@@ -50,6 +50,9 @@ class Params(C.Structure):
 # the columns of a row of gdca_run_partner_ipa's rounds_out (GDCA_IPA_*), GDCA_IPA_FIELDS of them
 IPA_FIELDS = ("M_train", "candidates", "n_sel", "n_changed", "Meff", "theta", "logdet", "cost", "ms_fit", "ms_match", "ms_select", "reserved")
 
+# the entries of gdca_run_pair_logodds' / gdca_run_partner_logodds' info (GDCA_LOGODDS_*), GDCA_LOGODDS_FIELDS of them
+LOGODDS_FIELDS = ("logdet", "logdet_A", "logdet_B", "information", "refined_A", "refined_B", "ms_marginals", "reserved")
+
 MULTI_MAX = 16  # GDCA_MULTI_MAX: settings one gdca_run_multi call takes
 
 
@@ -193,6 +196,25 @@ SYMBOLS = {
     "gdca_run_partner_match": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
                                          C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_pair_logodds_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    "gdca_pair_logodds": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    "gdca_pair_logodds_blocked_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    "gdca_pair_logodds_blocked": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    "gdca_run_pair_logodds_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats)]),
+    "gdca_run_pair_logodds": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_partner_logodds_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                               C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_partner_logodds": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "gdca_select_confident_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _i32p]),
     "gdca_select_confident": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _i32p]),
     "gdca_concat_pairs_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -396,7 +418,7 @@ class Context:
     # ---- log-likelihoods: log det C from the pivots of the inverse (include/gdca.h, "log-likelihoods") ----
     def last_logdet(self, k: int = 0, return_source: bool = False):
         """log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet); k: the member index after
-        run_multi.  NaN where that inverse was not positive definite.  return_source: (logdet, source), source 0 = the sweep's
+        run_multi; after a fused log-odds run 0 = the joint C, 1 = C_AA, 2 = C_BB.  NaN where that inverse was not positive definite.  return_source: (logdet, source), source 0 = the sweep's
         pivots, 1 = the Cholesky fallback's diagonal."""
         v = C.c_double(float("nan"))
         src = C.c_int32(0)
@@ -513,6 +535,73 @@ class Context:
         return self._run_readout(self.lib.gdca_run_partner_match_dev, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr),
                                  int(KA), self._opt(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, int(what), self._opt(E_ptr),
                                  C.c_void_p(match_ptr), self._opt(gap_ptr))
+
+    # ---- pair log-odds: the joint model against the two marginal models (include/gdca.h, "pair log-odds") ----
+    def pair_logodds_dev(self, mJ_ptr: int, mJA_ptr: int, mJB_ptr: int, Pi_ptr: int, N: int, q: int, split: int, XA_ptr: int, KA: int,
+                         XB_ptr: int, KB: int, I: float, L_ptr: int) -> None:
+        """gdca_pair_logodds_dev: the three precisions (n x n, n_A x n_A, n_B x n_B), Pi (n), XA (split x KA int8), XB ((N - split) x KB
+        int8) and L (KA x KB, column-major) are device pointers; I the caller's -1/2 (log det C - log det C_AA - log det C_BB)."""
+        self.check(self.lib.gdca_pair_logodds_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(mJA_ptr), C.c_void_p(mJB_ptr), C.c_void_p(Pi_ptr),
+                                                  int(N), int(q), int(split), C.c_void_p(XA_ptr), int(KA), C.c_void_p(XB_ptr), int(KB),
+                                                  float(I), C.c_void_p(L_ptr)))
+
+    def pair_logodds_blocked_dev(self, mJ_ptr: int, mJA_ptr: int, mJB_ptr: int, Pi_ptr: int, N: int, q: int, split: int, XA_ptr: int,
+                                 KA: int, XB_ptr: int, KB: int, offA, offB, I: float, L_ptr: int) -> None:
+        """gdca_pair_logodds_blocked_dev: as pair_logodds_dev for species-sorted sequences; offA / offB are HOST offsets, L the packed
+        blocks (pair_blocks_length(offA, offB) doubles, device)."""
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        self.check(self.lib.gdca_pair_logodds_blocked_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(mJA_ptr), C.c_void_p(mJB_ptr),
+                                                          C.c_void_p(Pi_ptr), int(N), int(q), int(split), C.c_void_p(XA_ptr), int(KA),
+                                                          C.c_void_p(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, float(I),
+                                                          C.c_void_p(L_ptr)))
+
+    def run_pair_logodds_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int,
+                             XA_ptr: int | None = None, KA: int = 0, XB_ptr: int | None = None, KB: int = 0):
+        """gdca_run_pair_logodds on HOST matrices given by address: the joint model and the two marginal models are fitted on Z (one
+        front end, three inverses), then L[a, b] = log p_AB(a (+) b) - log p_A(a) - log p_B(b) of the pairings of XA (split x KA) with
+        XB ((N - split) x KB); None: the halves of Z's own M sequences.  Returns ((L float64 (KA, KB), EmA float64[KA], EmB
+        float64[KB], info dict by LOGODDS_FIELDS), stats of the joint fit)."""
+        ka = int(KA) if XA_ptr is not None else int(M)
+        kb = int(KB) if XB_ptr is not None else int(M)
+        L = np.empty((max(ka, 0), max(kb, 0)), dtype=np.float64, order="F")
+        EmA, EmB = np.empty(max(ka, 0), dtype=np.float64), np.empty(max(kb, 0), dtype=np.float64)
+        info = np.zeros(len(LOGODDS_FIELDS), dtype=np.float64)
+        st = self._run_readout(self.lib.gdca_run_pair_logodds, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr), int(KA),
+                               self._opt(XB_ptr), int(KB), _p(L), _p(EmA), _p(EmB), _p(info))
+        return (L, EmA, EmB, dict(zip(LOGODDS_FIELDS, info.tolist()))), st
+
+    def run_pair_logodds_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int, XA_ptr: int | None,
+                             KA: int, XB_ptr: int | None, KB: int, L_ptr: int, EmA_ptr: int | None = None, EmB_ptr: int | None = None):
+        """Device-pointer form (Z, XA, XB, L and the optional EmA / EmB resident in HBM).  Returns (info dict, stats)."""
+        info = np.zeros(len(LOGODDS_FIELDS), dtype=np.float64)
+        st = self._run_readout(self.lib.gdca_run_pair_logodds_dev, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr),
+                               int(KA), self._opt(XB_ptr), int(KB), C.c_void_p(L_ptr), self._opt(EmA_ptr), self._opt(EmB_ptr), _p(info))
+        return dict(zip(LOGODDS_FIELDS, info.tolist())), st
+
+    def run_partner_logodds_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int, XA_ptr: int | None,
+                                KA: int, XB_ptr: int | None, KB: int, offA, offB, want_blocks: bool = True):
+        """gdca_run_partner_logodds on HOST matrices given by address: run_pair_logodds_ptr's fits, then the blocked log-odds of the
+        species-sorted XA / XB and the assignment that MAXIMISES their total inside every species.  Returns ((L packed float64 or None,
+        match int32[KA], gap float64[KA], info dict), stats)."""
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        ka = int(KA) if XA_ptr is not None else int(M)
+        L = np.empty(max(pair_blocks_length(offA, offB), 0), dtype=np.float64) if want_blocks else None
+        match, gap = np.empty(max(ka, 0), dtype=np.int32), np.empty(max(ka, 0), dtype=np.float64)
+        info = np.zeros(len(LOGODDS_FIELDS), dtype=np.float64)
+        st = self._run_readout(self.lib.gdca_run_partner_logodds, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr), int(KA),
+                               self._opt(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, None if L is None else _p(L), _p(match),
+                               _p(gap), _p(info))
+        return (L, match, gap, dict(zip(LOGODDS_FIELDS, info.tolist()))), st
+
+    def run_partner_logodds_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, split: int, XA_ptr: int | None,
+                                KA: int, XB_ptr: int | None, KB: int, offA, offB, L_ptr: int | None, match_ptr: int, gap_ptr: int | None):
+        """Device-pointer form (L None: kept inside the context).  Returns (info dict, stats)."""
+        offA, offB = species_offsets(offA), species_offsets(offB)
+        info = np.zeros(len(LOGODDS_FIELDS), dtype=np.float64)
+        st = self._run_readout(self.lib.gdca_run_partner_logodds_dev, Z_ptr, N, M, q, pseudocount, theta, int(split), self._opt(XA_ptr),
+                               int(KA), self._opt(XB_ptr), int(KB), _p(offA), _p(offB), len(offA) - 1, self._opt(L_ptr),
+                               C.c_void_p(match_ptr), self._opt(gap_ptr), _p(info))
+        return dict(zip(LOGODDS_FIELDS, info.tolist())), st
 
     # ---- iterative partner matching: the selection, the concatenation and the loop (gdca_run_partner_ipa) ----
     def select_confident(self, match: np.ndarray, gap: np.ndarray, n_take: int):

@@ -62,6 +62,12 @@ struct score_target {
     int32_t *match;
     double *gap;
     bool packed;                       // partner: XA / XB lie packed and padded in the context already (pair_pack; the rounds of gdca_run_partner_ipa)
+    size_t strideX;                    // energy: bytes from one sequence of X to the next (0: N -- whole sequences)
+    // pair / partner of a log-odds run (run_logodds): the pair stage waits for the collect, which knows the joint log det (logodds_epilogue);
+    // lo.EmA / lo.EmB: the marginal fits' energies, ldA / ldB their log dets, lo.I what the collect makes of the three
+    bool logodds;
+    gdca_logodds_terms lo;
+    double ldA, ldB;
 };
 
 static score_target contact_target(int score, int apc, double *S_dev)
@@ -138,6 +144,7 @@ struct gdca_pending {
     int N, M, q, n, n_pad;
     const int8_t *Z;           // what a refinement at collect time needs to build C again
     const double *pij;         // ... or, a pseudocount group of gdca_run_multi, the stored Pij_true C is built again from (nullptr: the tallies)
+    int N_all, site0;          // a marginal fit of a log-odds run: N is a range of the sites of an alignment of N_all, from site0 on; pij the joint Pij_true (N_all 0: no range)
     gdca_params p;
     // the run's timeline (open_timeline, mark, elapsed): whether it is timed at all, its clock -- device time stamps for a member of a
     // batch issued as batched grids, HIP events otherwise --, and which boundaries have been marked so far, by which of the two clocks
@@ -194,6 +201,8 @@ struct gdca_ctx {
     // partner matching: the species table (eoff, offA, offB), the blocked gather's work list, and the packed matrix of a fused run
     // whose caller does not want it
     gdca_buf PBtab, PBitems, PBE;
+    // pair log-odds: the marginal models' energies of the A and of the B sequences, and -L in packed blocks for the assignment
+    gdca_buf LOa, LOb, PBN;
     // iterative partner matching (k_ipa.hip): the selection's workspace (keys, values, histograms, flags), the counts a round hands to
     // the host, the growing training alignment, the selection (and a seed's partners behind it), a round's match / gap, the match of
     // the round before, and the species of every sequence a
@@ -630,6 +639,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Tws, &ctx->colsum, &ctx->sc, &ctx->normws, &ctx->C2, &ctx->B0, &ctx->Rt, &ctx->Wd, &ctx->rankws, &ctx->hcand, &ctx->himg,
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
                         &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
+                        &ctx->LOa, &ctx->LOb, &ctx->PBN,
                         &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -1015,25 +1025,26 @@ static void note_logdet(gdca_ctx *ctx, int k = 0)
 
 // What the energies and the mutation scan open with: the K sequences X (N x K) packed into ctx->Xg (illegal bytes: sc->bad_symbol
 // bit 2), g = mJ Pi in ctx->gvec and c0 = Pi' g behind it.
-static gdca_status pack_and_g(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K)
+static gdca_status pack_and_g(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, size_t stride = 0)
 {
     const int n = m.N * (m.q - 1), nb = gdca_energy_gblocks(n);
     CHK(ensure(ctx, ctx->Xg, (size_t)gdca_energy_blocks(m.N) * K * sizeof(uint32_t)));
     CHK(ensure(ctx, ctx->gpart, (size_t)nb * nb * 64 * sizeof(double)));
     CHK(ensure(ctx, ctx->gvec, ((size_t)n + 1) * sizeof(double)));
     double *g = (double *)ctx->gvec.p;
-    gdca_launch_energy_pack(ctx->stream, X_dev, (size_t)m.N, m.N, K, m.q, (uint32_t *)ctx->Xg.p, (gdca_dev_scalars *)ctx->sc.p);
+    gdca_launch_energy_pack(ctx->stream, X_dev, stride ? stride : (size_t)m.N, m.N, K, m.q, (uint32_t *)ctx->Xg.p, (gdca_dev_scalars *)ctx->sc.p);
     gdca_launch_energy_g(ctx->stream, m.A, m.ld, m.sign, n, m.Pi, (double *)ctx->gpart.p, g, g + n);
     return GDCA_OK;
 }
 
 // E[K] = 1/2 (x - Pi)' mJ (x - Pi) of the K sequences X (N x K) under the model m.  Illegal bytes of X: sc->bad_symbol bit 2.
-static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, double *E_dev)
+// stride != 0: sequence k starts at X_dev + k * stride (a range of the sites of longer sequences)
+static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, double *E_dev, size_t stride = 0)
 {
     const int sdim = m.q - 1, n = m.N * sdim;
     const int Kc = gdca_energy_chunk(m.N, K, ctx->tune.energy_chunk);
     CHK(ensure(ctx, ctx->Epart, (size_t)gdca_energy_blocks(m.N) * Kc * sizeof(double)));
-    CHK(pack_and_g(ctx, m, X_dev, K));
+    CHK(pack_and_g(ctx, m, X_dev, K, stride));
     const double *g = (const double *)ctx->gvec.p;
     for (int k0 = 0; k0 < K; k0 += Kc)
         HIPCHK(gdca_launch_energy_rows(ctx->stream, m.A, m.ld, m.sign, g, g + n, (const uint32_t *)ctx->Xg.p, m.N, sdim, K, k0,
@@ -1045,6 +1056,7 @@ static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
 // site of sequence 0's half; sequence k's starts strideA / strideB bytes on (so the columns of an alignment serve as they lie).
 // what = GDCA_PAIR_ENERGY: the marginal energies through energy_stage on the gap-padded halves (m.Pi needed), combined in the gather
 // kernel's epilogue; GDCA_PAIR_COUPLING: R alone, no g.  Illegal bytes: sc->bad_symbol bit 2.
+// lo != nullptr (what = GDCA_PAIR_ENERGY): the log-odds ((EmA[a] + EmB[b]) - E[a, b]) + I in the place of the energy (the gather's LO instances).
 // blk != nullptr: only the pairings inside the species of species-sorted sequences, E packed block by block (include/gdca.h, partner
 // matching) -- the pack, the pad, the marginal energies and the fold are the same calls; the gather goes by blk's work list.
 // what the pair stage makes of its sequences alone, whatever the model: the packed symbols of the two halves (ctx->PXa, ctx->PXb;
@@ -1068,7 +1080,8 @@ static gdca_status pair_pack(gdca_ctx *ctx, int N, int q, int split, const int8_
 // packed: pair_pack has run on these sequences already and nothing has touched its three buffers since (the rounds of
 // gdca_run_partner_ipa: the pools do not change from round to round)
 static gdca_status pair_stage(gdca_ctx *ctx, const gdca_model &m, int split, const int8_t *XA, size_t strideA, int KA, const int8_t *XB,
-                              size_t strideB, int KB, int what, double *E_dev, const pair_blocks *blk = nullptr, bool packed = false)
+                              size_t strideB, int KB, int what, double *E_dev, const pair_blocks *blk = nullptr, bool packed = false,
+                              const gdca_logodds_terms *lo = nullptr)
 {
     hipStream_t s = ctx->stream;
     const int N = m.N, q = m.q, sdim = q - 1, n = N * sdim, nB = (N - split) * sdim;
@@ -1087,10 +1100,10 @@ static gdca_status pair_stage(gdca_ctx *ctx, const gdca_model &m, int split, con
             HIPCHK(gdca_launch_pair_chunk_blocked(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim,
                                                   KA, KB, a0, std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev,
                                                   blk->items + 4 * blk->first[c], blk->first[c + 1] - blk->first[c], blk->eoff, blk->offA,
-                                                  blk->offB, ctx->ncu));
+                                                  blk->offB, ctx->ncu, lo));
         else
             HIPCHK(gdca_launch_pair_chunk(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->PXa.p, (const uint32_t *)ctx->PXb.p, N, split, sdim, KA, KB,
-                                          a0, std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev, ctx->ncu));
+                                          a0, std::min(Ac, KA - a0), (double *)ctx->PT.p, EAB, c0, E_dev, ctx->ncu, lo));
     }
     return check_launch(ctx, blk ? "blocked pair energies" : "pair energies");
 }
@@ -1117,10 +1130,12 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
 {
     hipStream_t s = ctx->stream;
     // the model as the sweep left it, for the fused read-outs: scored on t's sequences in the place of the contact score
-    const gdca_model m{(const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p, N, sdim + 1};
+    // (a marginal fit of a log-odds run: its sites' range of Pi)
+    const gdca_model m{(const double *)ctx->A.p, (size_t)n_pad, -1.0, (const double *)ctx->Pipc.p + (size_t)ctx->pend.site0 * sdim, N, sdim + 1};
+    if (t.logodds) return GDCA_OK;  // (the pair stage of a log-odds run needs the joint log det: logodds_epilogue, at collect time)
     switch (t.kind) {
     case score_target::ENERGY:
-    case score_target::LOGLIK: return energy_stage(ctx, m, t.X, t.K, t.out);
+    case score_target::LOGLIK: return energy_stage(ctx, m, t.X, t.K, t.out, t.strideX);
     case score_target::PAIR: return pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out);
     case score_target::PARTNER:
         CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out, &t.blocks, t.packed));
@@ -1234,13 +1249,17 @@ static gdca_status cholesky_stage(gdca_ctx *ctx, int n, int n_pad)
 // gdca_run_multi: the covariance of pseudocount pc into dst (ld = n_pad; the padding is the caller's) from the stored Pij_true and the
 // kept single-site tallies Pifix -- Pi' of pc (k_pi_finalize), then k_cov_from_pij: bit for bit what tally_stage's mode 1 writes for
 // pc.  want_norm1: a group's first build -- sc->pi_max and, where the screen needs it, sc->mat_norm1, as the fused path's first build
-static gdca_status cov_from_pij_stage(gdca_ctx *ctx, int N, int M, int q, double pc, double *dst, size_t ld, bool want_norm1)
+// N_all != 0: the principal block of the N sites from site0 on of an alignment of N_all sites, whose Pij_true is the stored one -- Pi' is
+// that of all N_all sites (it does not depend on the block), and the block's entries are bit for bit the joint covariance's
+static gdca_status cov_from_pij_stage(gdca_ctx *ctx, int N, int M, int q, double pc, double *dst, size_t ld, bool want_norm1, int N_all = 0,
+                                      int site0 = 0)
 {
     hipStream_t s = ctx->stream;
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    gdca_launch_pi_finalize(s, (const unsigned long long *)ctx->Pifix.p, N, q, gdca_fix_shift(M), &sc->Meff, pc, nullptr, (double *)ctx->Pipc.p,
-                            want_norm1 ? &sc->pi_max : nullptr);
-    gdca_launch_cov_from_pij(s, (const double *)ctx->Pij.p, (const double *)ctx->Pipc.p, N, q, pc, dst, ld);
+    const size_t ldp = (size_t)(N_all ? N_all : N) * (q - 1), off = (size_t)site0 * (q - 1);
+    gdca_launch_pi_finalize(s, (const unsigned long long *)ctx->Pifix.p, N_all ? N_all : N, q, gdca_fix_shift(M), &sc->Meff, pc, nullptr,
+                            (double *)ctx->Pipc.p, want_norm1 ? &sc->pi_max : nullptr);
+    gdca_launch_cov_from_pij(s, (const double *)ctx->Pij.p + off * (ldp + 1), (const double *)ctx->Pipc.p + off, N, q, pc, dst, ld, ldp);
     if (want_norm1 && !norm1_settled(ctx, N, q, pc))
         gdca_launch_cov_norm1(s, dst, ld, N, q, pc, ctx->tune.refine_cond, sc, ctx->tune.refine == 1);
     return check_launch(ctx, "covariance from Pij_true");
@@ -1252,7 +1271,8 @@ static gdca_status rebuild_covariance(gdca_ctx *ctx, double *dst)
 {
     gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
     const int N = ctx->pend.N, M = ctx->pend.M, q = ctx->pend.q;
-    if (ctx->pend.pij) return cov_from_pij_stage(ctx, N, M, q, ctx->pend.p.pseudocount, dst, (size_t)ctx->pend.n_pad, false);
+    if (ctx->pend.pij)
+        return cov_from_pij_stage(ctx, N, M, q, ctx->pend.p.pseudocount, dst, (size_t)ctx->pend.n_pad, false, ctx->pend.N_all, ctx->pend.site0);
     return tally_stage(ctx, ctx->pend.Z, N, M, q, &sc->Meff, ctx->pend.p.pseudocount, 1, nullptr, dst, (size_t)ctx->pend.n_pad);
 }
 
@@ -1329,6 +1349,37 @@ static gdca_status loglik_epilogue(gdca_ctx *ctx)
     return GDCA_OK;
 }
 
+// I = -1/2 (log det C - log det C_AA - log det C_BB): plain f64, one rounding per operation (two subtractions, one multiplication), so
+// that a caller who forms it from gdca_last_logdet's three values the same way gets the same bits
+static double logodds_information(double ld, double ldA, double ldB)
+{
+    const double a = ld - ldA;
+    const double b = a - ldB;
+    return -0.5 * b;
+}
+
+// How a log-odds run ends, every collect-time branch of the joint fit behind it: the pair stage (full or blocked) on the inverse finally
+// used, its gather writing L = ((EmA[a] + EmB[b]) - E[a, b]) + I with I from the three log dets -- the joint one is on the host only
+// now --, and for a partner run the assignment on -L.  The run's score stage ends here (T_END marked again); the scalars are fetched
+// again: the pair stage's pack has looked at the sequences.
+static gdca_status logodds_epilogue(gdca_ctx *ctx)
+{
+    gdca_pending &r = ctx->pend;
+    score_target &t = r.target;
+    t.lo.I = logodds_information(ctx->ld.val[0], t.ldA, t.ldB);
+    const gdca_model m{(const double *)ctx->A.p, (size_t)r.n_pad, -1.0, (const double *)ctx->Pipc.p, r.N, r.q};
+    if (t.kind == score_target::PARTNER) {
+        CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, GDCA_PAIR_ENERGY, t.out, &t.blocks, t.packed, &t.lo));
+        CHK(ensure(ctx, ctx->PBN, (size_t)t.blocks.total * sizeof(double)));
+        gdca_launch_negate(ctx->stream, t.out, (double *)ctx->PBN.p, (size_t)t.blocks.total);
+        CHK(assign_stage(ctx, (const double *)ctx->PBN.p, t.blocks, t.match, t.gap));
+    } else {
+        CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, GDCA_PAIR_ENERGY, t.out, nullptr, false, &t.lo));
+    }
+    CHK(mark(ctx, T_END));
+    return fetch_scalars(ctx);
+}
+
 extern "C" {
 
 gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
@@ -1395,6 +1446,7 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
     }
     note_logdet(ctx);
     if (ctx->pend.target.kind == score_target::LOGLIK && ctx->sc_host->info == 0 && !ctx->sc_host->bad_symbol) CHK(loglik_epilogue(ctx));
+    if (ctx->pend.target.logodds && ctx->sc_host->info == 0 && !ctx->sc_host->bad_symbol) CHK(logodds_epilogue(ctx));
     if (st) CHK(fill_stats(ctx, st));
     const gdca_dev_scalars &h = *ctx->sc_host;
     if (h.bad_symbol & 4) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
@@ -1496,6 +1548,7 @@ static void pending_front(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int 
     r.n_pad = round_up(r.n, GDCA_TILE);
     r.Z = Z_dev;
     r.pij = pij;
+    r.N_all = r.site0 = 0;  // (run_logodds knows better)
     r.p = *p;
     r.front_batch = r.score_batch = 1;  // (run_phased knows better)
 }
@@ -2781,6 +2834,190 @@ gdca_status gdca_run_partner_match_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                       partner_target(pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, what, E_dev), blk, match_dev, gap_dev), st);
 }
 
+// ---- pair log-odds: the joint model against the two marginal models (include/gdca.h) ----
+// what the operator forms share: the marginal models' energies of XA and XB into ctx->LOa / ctx->LOb (the energy stage with N = split
+// and N - split, Pi's two ranges), then the pair stage's LO instances on the joint model
+static gdca_status logodds_operator(gdca_ctx *ctx, const double *mJ_dev, const double *mJA_dev, const double *mJB_dev, const double *Pi_dev, int N,
+                                    int q, int split, const int8_t *XA_dev, int KA, const int8_t *XB_dev, int KB, double I, double *L_dev,
+                                    const pair_blocks *blk)
+{
+    CHK(begin(ctx));
+    CHK(ensure(ctx, ctx->LOa, (size_t)KA * sizeof(double)));
+    CHK(ensure(ctx, ctx->LOb, (size_t)KB * sizeof(double)));
+    CHK(energy_stage(ctx, operator_model(mJA_dev, Pi_dev, split, q), XA_dev, KA, (double *)ctx->LOa.p));
+    CHK(energy_stage(ctx, operator_model(mJB_dev, Pi_dev + (size_t)split * (q - 1), N - split, q), XB_dev, KB, (double *)ctx->LOb.p));
+    const gdca_logodds_terms lo{(const double *)ctx->LOa.p, (const double *)ctx->LOb.p, I};
+    CHK(pair_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), split, XA_dev, (size_t)split, KA, XB_dev, (size_t)(N - split), KB, GDCA_PAIR_ENERGY,
+                   L_dev, blk, false, &lo));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_pair_logodds_dev(gdca_ctx *ctx, const double *mJ_dev, const double *mJA_dev, const double *mJB_dev, const double *Pi_dev, int32_t N,
+                                  int32_t q, int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, double I,
+                                  double *L_dev)
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
+    if (!mJ_dev || !mJA_dev || !mJB_dev || !Pi_dev || !XA_dev || !XB_dev || !L_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return logodds_operator(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, I, L_dev, nullptr);
+}
+
+gdca_status gdca_pair_logodds_blocked_dev(gdca_ctx *ctx, const double *mJ_dev, const double *mJA_dev, const double *mJB_dev, const double *Pi_dev,
+                                          int32_t N, int32_t q, int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB,
+                                          const void *offA, const void *offB, int32_t S, double I, double *L_dev)
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
+    if (!mJ_dev || !mJA_dev || !mJB_dev || !Pi_dev || !XA_dev || !XB_dev || !L_dev || !offA || !offB)
+        return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    pair_blocks blk;
+    std::vector<long long> first;
+    CHK(species_blocks(ctx, offA, offB, S, KA, KB, (N - split) * (q - 1), false, &blk, first));
+    return logodds_operator(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, I, L_dev, &blk);
+}
+
+// The fused form, arguments checked: the front end once into Pij_true (gdca_run_multi's way), then three fits one after the other on the
+// context's stream, each collected like a single run of its own size -- the block of sites 0 .. split - 1 with the energy stage on the A
+// sequences as its target, the block of the other sites with the B sequences, and the joint fit last, whose collect ends with the pair
+// stage `t` names (logodds_epilogue).  The blocks' covariances are entries of the joint one bit for bit (cov_from_pij_stage).
+// EmA / EmB: where the marginal energies go (nullptr: buffers of the context).  The status is the first failing fit's.
+static gdca_status run_logodds(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, int q, const gdca_params *p, score_target t, double *EmA_dev,
+                               double *EmB_dev, double *info, gdca_stats *st)
+{
+    CHK(check_params(ctx, p));
+    CHK(not_pending(ctx));
+    if (info) {
+        for (int i = 0; i < GDCA_LOGODDS_FIELDS; ++i) info[i] = 0.0;
+        info[GDCA_LOGODDS_LOGDET] = info[GDCA_LOGODDS_LOGDET_A] = info[GDCA_LOGODDS_LOGDET_B] = info[GDCA_LOGODDS_INFORMATION] = (double)NAN;
+    }
+    gdca_params pp = *p;  // (score and apc are ignored: no contact score is computed)
+    pp.score = GDCA_SCORE_FROB;
+    pp.apc = 0;
+    hipStream_t s = ctx->stream;
+    const int sdim = q - 1, n = N * sdim, n_pad = round_up(n, GDCA_TILE), split = t.split;
+    const double pc = pp.pseudocount;
+    if (!EmA_dev) {
+        CHK(ensure(ctx, ctx->LOa, (size_t)t.KA * sizeof(double)));
+        EmA_dev = (double *)ctx->LOa.p;
+    }
+    if (!EmB_dev) {
+        CHK(ensure(ctx, ctx->LOb, (size_t)t.KB * sizeof(double)));
+        EmB_dev = (double *)ctx->LOb.p;
+    }
+    // ---- the front end, once: theta, reweighting, Pi, Pij_true (ld = n) ----
+    CHK(front_weights(ctx, Z_dev, N, M, q, pp.theta, false));
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    CHK(ensure(ctx, ctx->Pij, (size_t)n * n * sizeof(double)));
+    CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
+    CHK(ensure(ctx, ctx->sc_front, sizeof(gdca_dev_scalars)));
+    CHK(mark(ctx, T_TALLY_BEGIN));  // (the tallies into Pij_true: gdca_stats.ms_pair_tally of this run, and where the first marginal fit begins)
+    CHK(tally_stage(ctx, Z_dev, N, M, q, &sc->Meff, pc, 0, nullptr, (double *)ctx->Pij.p, (size_t)n));
+    CHK(mark(ctx, T_TALLY_END));
+    HIPCHK(hipMemcpyAsync(ctx->sc_front.p, sc, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
+    double ldv[3] = {(double)NAN, (double)NAN, (double)NAN}, ms_theta = 0.0, ms_weights = 0.0, ms_marg = 0.0;
+    int lds[3] = {0, 0, 0};
+    gdca_stats own;
+    if (!st) st = &own;
+    // ---- the fits: 1 = block A, 2 = block B, 0 = the joint one (their indices in the log-det record) ----
+    const int order[3] = {1, 2, 0};
+    for (int f = 0; f < 3; ++f) {
+        const int k = order[f];
+        const int Nf = k == 1 ? split : k == 2 ? N - split : N, site0 = k == 2 ? split : 0;
+        const int nf_pad = round_up(Nf * sdim, GDCA_TILE);
+        if (f > 0) {
+            // (every fit starts from the scalars the front end left: theta, Meff, ...; its own -- pi_max, norms, info -- zero)
+            HIPCHK(hipMemcpyAsync(sc, ctx->sc_front.p, sizeof(gdca_dev_scalars), hipMemcpyDeviceToDevice, s));
+            ctx->pend.at = gdca_pending::progress{};
+            CHK(mark(ctx, T_WEIGHTS));
+        }
+        pending_front(ctx, Z_dev, Nf, M, q, &pp, (const double *)ctx->Pij.p);
+        if (k != 0) {
+            ctx->pend.N_all = N;
+            ctx->pend.site0 = site0;
+        }
+        CHK(cov_from_pij_stage(ctx, Nf, M, q, pc, (double *)ctx->A.p, (size_t)nf_pad, ctx->tune.refine != 0, ctx->pend.N_all, site0));
+        CHK(covariance_tail(ctx, Nf, sdim, nf_pad, false));
+        CHK(run_inverse(ctx));
+        score_target tf = t;
+        if (k == 0) {
+            tf.logodds = true;
+            tf.lo = gdca_logodds_terms{EmA_dev, EmB_dev, 0.0};
+            tf.ldA = ldv[1];
+            tf.ldB = ldv[2];
+        } else {
+            tf = score_target{};
+            tf.kind = score_target::ENERGY;
+            tf.out = k == 1 ? EmA_dev : EmB_dev;
+            tf.X = k == 1 ? t.XA : t.XB;
+            tf.strideX = k == 1 ? t.strideA : t.strideB;
+            tf.K = k == 1 ? t.KA : t.KB;
+        }
+        CHK(run_score(ctx, tf));
+        gdca_stats sf;
+        const gdca_status gs = gdca_run_collect(ctx, k == 0 ? st : &sf);
+        ctx->pend.N_all = ctx->pend.site0 = 0;  // (nothing of a block stays behind for the next run's stages)
+        ctx->pend.pij = nullptr;
+        if (gs != GDCA_OK) return gs;
+        ldv[k] = ctx->ld.val[0];
+        lds[k] = ctx->ld.src[0];
+        if (k != 0) {
+            bool tfail = false;
+            ms_marg += elapsed(ctx, f == 0 ? T_TALLY_END : T_WEIGHTS, T_END, &tfail);
+            if (f == 0) {
+                ms_theta = sf.ms_theta;
+                ms_weights = sf.ms_weights;
+            }
+            if (info) {
+                info[k == 1 ? GDCA_LOGODDS_LOGDET_A : GDCA_LOGODDS_LOGDET_B] = ldv[k];
+                info[k == 1 ? GDCA_LOGODDS_REFINED_A : GDCA_LOGODDS_REFINED_B] = (double)sf.refined;
+            }
+        }
+    }
+    st->ms_theta = ms_theta;
+    st->ms_weights = ms_weights;
+    for (int k = 0; k < 3; ++k) {
+        ctx->ld.val[k] = ldv[k];
+        ctx->ld.src[k] = lds[k];
+    }
+    ctx->ld.count = 3;
+    if (info) {
+        info[GDCA_LOGODDS_LOGDET] = ldv[0];
+        info[GDCA_LOGODDS_INFORMATION] = ctx->pend.target.lo.I;
+        info[GDCA_LOGODDS_MS_MARGINALS] = ms_marg;
+    }
+    return GDCA_OK;
+}
+
+gdca_status gdca_run_pair_logodds_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                      const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, double *L_dev, double *EmA_dev,
+                                      double *EmB_dev, double *info, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_pair(ctx, N, q, split, XA_dev ? KA : M, XB_dev ? KB : M, GDCA_PAIR_ENERGY));
+    if (!Z_dev || !L_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return run_logodds(ctx, Z_dev, N, M, q, p, pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, GDCA_PAIR_ENERGY, L_dev), EmA_dev, EmB_dev, info,
+                       st);
+}
+
+gdca_status gdca_run_partner_logodds_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                         const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA, const void *offB,
+                                         int32_t S, double *L_dev, int32_t *match_dev, double *gap_dev, double *info, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    const int ka = XA_dev ? KA : M, kb = XB_dev ? KB : M;
+    CHK(validate_pair(ctx, N, q, split, ka, kb, GDCA_PAIR_ENERGY));
+    if (!Z_dev || !match_dev || !offA || !offB || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_params(ctx, p));
+    pair_blocks blk;
+    std::vector<long long> first;
+    CHK(species_blocks(ctx, offA, offB, S, ka, kb, (N - split) * (q - 1), true, &blk, first));
+    if (!L_dev) {
+        CHK(ensure(ctx, ctx->PBE, (size_t)blk.total * sizeof(double)));
+        L_dev = (double *)ctx->PBE.p;
+    }
+    return run_logodds(ctx, Z_dev, N, M, q, p,
+                       partner_target(pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, GDCA_PAIR_ENERGY, L_dev), blk, match_dev, gap_dev),
+                       nullptr, nullptr, info, st);
+}
+
 // ---- iterative partner matching: the selection, the concatenation and the loop (k_ipa.hip) ----
 // the selection enqueued: sel_dev and the counts record (ctx->IPAcnt)
 static gdca_status select_stage(gdca_ctx *ctx, const int32_t *match_dev, const double *gap_dev, int KA, int n_take, int32_t *sel_dev)
@@ -3375,6 +3612,96 @@ gdca_status gdca_run_partner_match(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
     CHK(up);
     CHK(gdca_run_partner_match_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, offA, offB, S, what, E_dev, match_dev, gap_dev, st));
     if (E_host && ne) CHK(to_host(ctx, E_host, ctx->scratch[5], ne));
+    if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
+    return to_host(ctx, match_host, ctx->scratch[6], nm);
+}
+
+// pair log-odds with host pointers: upload, the _dev form, download (three matrices cross PCIe in the operator forms)
+static gdca_status logodds_operator_host(gdca_ctx *ctx, const double *mJ, const double *mJA, const double *mJB, const double *Pi, int32_t N, int32_t q,
+                                         int32_t split, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, const void *offA,
+                                         const void *offB, int32_t S, bool blocked, double I, double *L)
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
+    if (!mJ || !mJA || !mJB || !Pi || !XA || !XB || !L) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    long long total = (long long)KA * KB;
+    if (blocked) CHK(host_blocks_length(ctx, offA, offB, S, KA, KB, &total));
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t s = (size_t)(q - 1), n = (size_t)N * s, nA = (size_t)split * s, nB = n - nA, ne = (size_t)total * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
+    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 0, XA, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 3, XB, (size_t)(N - split) * KB, &up);
+    const double *mJA_dev = (const double *)upload(ctx, 4, mJA, nA * nA * sizeof(double), &up);
+    const double *mJB_dev = (const double *)upload(ctx, 6, mJB, nB * nB * sizeof(double), &up);
+    double *L_dev = staged_out(ctx, 5, ne, &up);
+    CHK(up);
+    if (blocked)
+        CHK(gdca_pair_logodds_blocked_dev(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, offA, offB, S, I, L_dev));
+    else
+        CHK(gdca_pair_logodds_dev(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, I, L_dev));
+    return ne ? to_host(ctx, L, ctx->scratch[5], ne) : GDCA_OK;
+}
+
+gdca_status gdca_pair_logodds(gdca_ctx *ctx, const double *mJ, const double *mJA, const double *mJB, const double *Pi, int32_t N, int32_t q,
+                              int32_t split, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, double I, double *L)
+{
+    return logodds_operator_host(ctx, mJ, mJA, mJB, Pi, N, q, split, XA, KA, XB, KB, nullptr, nullptr, 0, false, I, L);
+}
+
+gdca_status gdca_pair_logodds_blocked(gdca_ctx *ctx, const double *mJ, const double *mJA, const double *mJB, const double *Pi, int32_t N, int32_t q,
+                                      int32_t split, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, const void *offA, const void *offB,
+                                      int32_t S, double I, double *L)
+{
+    return logodds_operator_host(ctx, mJ, mJA, mJB, Pi, N, q, split, XA, KA, XB, KB, offA, offB, S, true, I, L);
+}
+
+gdca_status gdca_run_pair_logodds(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                  const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, double *L_host, double *EmA_host,
+                                  double *EmB_host, double *info, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    const int ka = XA_host ? KA : M, kb = XB_host ? KB : M;
+    CHK(validate_pair(ctx, N, q, split, ka, kb, GDCA_PAIR_ENERGY));
+    if (!Z_host || !L_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ne = (size_t)ka * (size_t)kb * sizeof(double), na = (size_t)ka * sizeof(double), nb = (size_t)kb * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
+    double *L_dev = staged_out(ctx, 5, ne, &up);
+    double *EmA_dev = EmA_host ? staged_out(ctx, 8, na, &up) : nullptr;
+    double *EmB_dev = EmB_host ? staged_out(ctx, 9, nb, &up) : nullptr;
+    CHK(up);
+    CHK(gdca_run_pair_logodds_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, L_dev, EmA_dev, EmB_dev, info, st));
+    if (EmA_host) CHK(to_host(ctx, EmA_host, ctx->scratch[8], na));
+    if (EmB_host) CHK(to_host(ctx, EmB_host, ctx->scratch[9], nb));
+    return to_host(ctx, L_host, ctx->scratch[5], ne);
+}
+
+gdca_status gdca_run_partner_logodds(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                     const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA, const void *offB,
+                                     int32_t S, double *L_host, int32_t *match_host, double *gap_host, double *info, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    const int ka = XA_host ? KA : M, kb = XB_host ? KB : M;
+    CHK(validate_pair(ctx, N, q, split, ka, kb, GDCA_PAIR_ENERGY));
+    if (!Z_host || !match_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    long long total = 0;
+    CHK(host_blocks_length(ctx, offA, offB, S, ka, kb, &total));
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ne = (size_t)total * sizeof(double), nm = (size_t)ka * sizeof(int32_t), ng = (size_t)ka * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
+    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
+    double *L_dev = L_host ? staged_out(ctx, 5, ne, &up) : nullptr;
+    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
+    double *gap_dev = gap_host ? staged_out(ctx, 7, ng, &up) : nullptr;
+    CHK(up);
+    CHK(gdca_run_partner_logodds_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, offA, offB, S, L_dev, match_dev, gap_dev, info, st));
+    if (L_host && ne) CHK(to_host(ctx, L_host, ctx->scratch[5], ne));
     if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
     return to_host(ctx, match_host, ctx->scratch[6], nm);
 }

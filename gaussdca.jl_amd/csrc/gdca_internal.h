@@ -163,8 +163,10 @@ void gdca_launch_pair_tally(hipStream_t s, const int8_t *Zc, const int8_t *Zt, c
                             const double *Pi_pc, int mode, double *out, size_t ld, int TJ, const uint32_t *keep = nullptr,
                             const int *keep_n = nullptr, const uint8_t *sigma = nullptr, const unsigned long long *Pifix = nullptr);
 // out (ld) = the covariance of pseudocount pc built from stored tallies: Pij (n x n, ld = n, mode 0's output) and that pc's Pi_pc --
-// bit for bit what mode 1 writes for pc (both triangles; the padding is the caller's: gdca_launch_pad_identity)
-void gdca_launch_cov_from_pij(hipStream_t s, const double *Pij, const double *Pi_pc, int N, int q, double pc, double *out, size_t ld);
+// bit for bit what mode 1 writes for pc (both triangles; the padding is the caller's: gdca_launch_pad_identity).  ldp != 0: Pij and
+// Pi_pc point at the first element of a principal block of N whole sites inside a Pij of leading dimension ldp (0: ldp = n)
+void gdca_launch_cov_from_pij(hipStream_t s, const double *Pij, const double *Pi_pc, int N, int q, double pc, double *out, size_t ld,
+                              size_t ldp = 0);
 
 // ---- k_elementwise.hip ---------------------------------------------------------------------
 void gdca_launch_add_pseudocount(hipStream_t s, const double *Pi_true, const double *Pij_true, int N, int q,
@@ -303,12 +305,18 @@ int gdca_pair_chunk(int nB, int KA, int wanted);    // sequences a one launch of
 // Xp (N x (KA + KB)): a (+) gaps for the KA sequences of XA (split sites each), then gaps (+) b for the KB of XB (N - split sites each)
 void gdca_launch_pair_pad(hipStream_t s, const int8_t *XA, size_t strideA, const int8_t *XB, size_t strideB, int N, int split, int KA, int KB,
                           int q, int8_t *Xp);
+// What carries a pair energy on to the log-odds of the pairing against the two marginal models (include/gdca.h, pair log-odds): the
+// marginal models' energies of the KA sequences a and of the KB sequences b (device), and I = -1/2 (log det C - log det C_AA - log det C_BB)
+struct gdca_logodds_terms {
+    const double *EmA, *EmB;
+    double I;
+};
 // E[a + KA * b], a0 <= a < a0 + Ac, all b, from the block rows >= split * sdim, columns < split * sdim of A (ld; sign -1: A holds -mJ);
 // XAg / XBg: the halves packed by gdca_launch_energy_pack; T: Ac x (N - split) * sdim doubles.  EAB (KA + KB marginal energies) and c0:
-// the energy; EAB == nullptr: the coupling R alone
+// the energy; EAB == nullptr: the coupling R alone.  lo != nullptr (with EAB): E receives ((EmA[a] + EmB[b]) - energy) + I instead
 hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N,
                                   int split, int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E,
-                                  int ncu);
+                                  int ncu, const gdca_logodds_terms *lo = nullptr);
 // The pairings inside the species of species-sorted sequences (include/gdca.h, partner matching).  The work list: 4 int32 an item
 // (species, first a, first b, na | nb << 8), a ascending, no group of a across a multiple of Ac; first[c] = the first item of chunk c
 // (one entry more than chunks).  offA / offB: S + 1 valid offsets
@@ -318,7 +326,9 @@ void gdca_pair_block_items(const int32_t *offA, const int32_t *offB, int S, int 
 hipError_t gdca_launch_pair_chunk_blocked(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N,
                                           int split, int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0,
                                           double *E, const int32_t *items, long long nitems, const long long *eoff, const int32_t *offA,
-                                          const int32_t *offB, int ncu);
+                                          const int32_t *offB, int ncu, const gdca_logodds_terms *lo = nullptr);
+// dst[i] = -src[i], i < len (the assignment on log-odds minimises -L)
+void gdca_launch_negate(hipStream_t s, const double *src, double *dst, size_t len);
 
 // ---- k_assign.hip: the minimum-cost assignment inside every block of a blocked cost matrix -------------------------------------------------
 // match[KA] / gap[KA] (gap may be nullptr) of the S species (eoff, offA, offB: device, S + 1 entries each); kmax = the largest kA_s or

@@ -21,6 +21,9 @@
 //   k_pair_gather  R[a, b] = sum_{j in B} T[a][r_b(j)]: a workgroup keeps segments of the T rows of 8 sequences a in LDS, interleaved
 //                  [row][8] (64 B a row: one symbol decode serves eight pairings), for 256 x BU sequences b; and, `what` = energy, the
 //                  combination ((EA[a] + EB[b]) - c0 / 2) + R in its epilogue -- the K_A x K_B matrix is written once and never read.
+//                  A third compile-time variant (LO) carries the energy on to the LOG-ODDS of the pairing against the two marginal
+//                  models (include/gdca.h, pair log-odds): e formed exactly as above, then ((EmA[a] + EmB[b]) - e) + I, with the
+//                  marginal energies read like EA / EB and I a kernel argument from the host; e is never stored.
 //   k_pair_gather_blocked  the same sum for the pairings INSIDE the species of a species-sorted problem (include/gdca.h, partner
 //                  matching): a work item = (species, up to 8 of its sequences a, up to 32 of its sequences b), built on the host;
 //                  the same LDS layout, segments and epilogue, but a lane owns ONE pairing (lane = (b, a of 8)) where k_pair_gather's
@@ -136,9 +139,10 @@ struct k_pair_gather_args {
     const double *c0;
     double *E;            // [KB][KA]: E[a + KA * b]
     int NB, sdim, nB, SB, KA, KB, a0, Ac, b0;
+    gdca_logodds_terms lo;  // the LO instances: the marginal models' energies EmA [KA], EmB [KB] and the constant I
 };
 
-template <int BU>
+template <int BU, bool LO>
 __global__ __launch_bounds__(256) void k_pair_gather(const k_pair_gather_args p)
 {
     extern __shared__ double lds_[];  // [SR + 1 rows][PGA]: a segment of the T rows of this workgroup's sequences a; row SR = zeros (the gap)
@@ -186,12 +190,18 @@ __global__ __launch_bounds__(256) void k_pair_gather(const k_pair_gather_args p)
     for (int u = 0; u < BU; ++u) {
         if (bk[u] >= p.KB) continue;
         const double eb = p.EAB ? p.EAB[(size_t)p.KA + bk[u]] : 0.0;
+        double emb = 0.0;
+        if constexpr (LO) emb = p.lo.EmB[bk[u]];
 #pragma unroll
         for (int g = 0; g < PGA; ++g) {
             if (ag + g >= p.Ac) continue;
             const int a = p.a0 + ag + g;
             const double r = acc[u][g];
-            p.E[(size_t)a + (size_t)p.KA * (size_t)bk[u]] = p.EAB ? ((p.EAB[a] + eb) - hc0) + r : r;
+            const double e = p.EAB ? ((p.EAB[a] + eb) - hc0) + r : r;
+            if constexpr (LO)
+                p.E[(size_t)a + (size_t)p.KA * (size_t)bk[u]] = ((p.lo.EmA[a] + emb) - e) + p.lo.I;
+            else
+                p.E[(size_t)a + (size_t)p.KA * (size_t)bk[u]] = e;
         }
     }
 }
@@ -207,8 +217,10 @@ struct k_pair_gather_blocked_args {
     const long long *eoff;  // [S + 1]
     const int *offA, *offB;  // [S + 1] each
     int NB, sdim, nB, SB, KA, KB, a0;
+    gdca_logodds_terms lo;  // as k_pair_gather
 };
 
+template <bool LO>
 __global__ __launch_bounds__(256) void k_pair_gather_blocked(const k_pair_gather_blocked_args p)
 {
     extern __shared__ double lds_[];  // as k_pair_gather: [SR + 1 rows][PGA], row SR = zeros (the gap)
@@ -249,7 +261,11 @@ __global__ __launch_bounds__(256) void k_pair_gather_blocked(const k_pair_gather
     const size_t at = (size_t)(p.eoff[it.x] + (a - oa) + kA * (bk - p.offB[it.x]));
     if (p.EAB) {
         const double hc0 = 0.5 * *p.c0;
-        p.E[at] = ((p.EAB[a] + p.EAB[(size_t)p.KA + bk]) - hc0) + acc;
+        const double e = ((p.EAB[a] + p.EAB[(size_t)p.KA + bk]) - hc0) + acc;
+        if constexpr (LO)
+            p.E[at] = ((p.lo.EmA[a] + p.lo.EmB[bk]) - e) + p.lo.I;
+        else
+            p.E[at] = e;
     } else {
         p.E[at] = acc;
     }
@@ -305,7 +321,8 @@ static int pair_segment_sites(int NB, int sdim)
 // E[a0 .. a0 + Ac - 1][all b] from the block of A (ld, sign) and the packed symbols; T: Ac x nB doubles.  EAB == nullptr: the coupling R.
 // An error: the dynamic LDS limit could not be raised for a tile; the kernel it was for and those behind it were not launched
 hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N, int split,
-                            int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E, int ncu)
+                            int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0, double *E, int ncu,
+                            const gdca_logodds_terms *lo)
 {
     const int NB = N - split, nB = NB * sdim;
     {
@@ -318,13 +335,14 @@ hipError_t gdca_launch_pair_chunk(hipStream_t s, const double *A, size_t ld, dou
         const int ga = (Ac + PGA - 1) / PGA;
         const bool wide = gdca_wide_instance(KB, 256 * PBU_WIDE, ga, ncu);
         const int per = 256 * (wide ? PBU_WIDE : PBU_NARROW);
-        void (*kern)(k_pair_gather_args) = wide ? k_pair_gather<PBU_WIDE> : k_pair_gather<PBU_NARROW>;
+        void (*kern)(k_pair_gather_args) = lo ? (wide ? k_pair_gather<PBU_WIDE, true> : k_pair_gather<PBU_NARROW, true>)
+                                              : (wide ? k_pair_gather<PBU_WIDE, false> : k_pair_gather<PBU_NARROW, false>);
         const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
         if (e != hipSuccess) return e;
         const long long maxb = (long long)65535 * per;  // sequences b one launch's grid covers
         for (long long b0 = 0; b0 < KB; b0 += maxb) {
             const long long kb = KB - b0 < maxb ? KB - b0 : maxb;
-            const k_pair_gather_args a{T, XBg, EAB, c0, E, NB, sdim, nB, SB, KA, KB, a0, Ac, (int)b0};
+            const k_pair_gather_args a{T, XBg, EAB, c0, E, NB, sdim, nB, SB, KA, KB, a0, Ac, (int)b0, lo ? *lo : gdca_logodds_terms{}};
             GDCA_LAUNCH_DIRECT(kern, dim3(ga, (unsigned)((kb + per - 1) / per)), dim3(256), lds, s, a);
         }
     }
@@ -362,7 +380,7 @@ void gdca_pair_block_items(const int32_t *offA, const int32_t *offB, int S, int 
 hipError_t gdca_launch_pair_chunk_blocked(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *XAg, const uint32_t *XBg, int N,
                                           int split, int sdim, int KA, int KB, int a0, int Ac, double *T, const double *EAB, const double *c0,
                                           double *E, const int32_t *items, long long nitems, const long long *eoff, const int32_t *offA,
-                                          const int32_t *offB, int ncu)
+                                          const int32_t *offB, int ncu, const gdca_logodds_terms *lo)
 {
     const int NB = N - split, nB = NB * sdim;
     if (nitems == 0) return hipSuccess;  // (no pairing of these sequences a is wanted: their rows need not be folded)
@@ -370,13 +388,30 @@ hipError_t gdca_launch_pair_chunk_blocked(hipStream_t s, const double *A, size_t
     if (e != hipSuccess) return e;
     const int SB = pair_segment_sites(NB, sdim);
     const size_t lds = ((size_t)SB * sdim + 1) * PGA * sizeof(double);
-    const hipError_t e2 = gdca_raise_lds_limit(reinterpret_cast<const void *>(k_pair_gather_blocked), lds);
+    void (*kern)(k_pair_gather_blocked_args) = lo ? k_pair_gather_blocked<true> : k_pair_gather_blocked<false>;
+    const hipError_t e2 = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e2 != hipSuccess) return e2;
     const long long maxi = 1 << 30;  // items one launch's grid covers
     for (long long i0 = 0; i0 < nitems; i0 += maxi) {
         const long long ni = nitems - i0 < maxi ? nitems - i0 : maxi;
-        const k_pair_gather_blocked_args a{T, XBg, EAB, c0, E, reinterpret_cast<const int4 *>(items) + i0, eoff, offA, offB, NB, sdim, nB, SB, KA, KB, a0};
-        GDCA_LAUNCH_DIRECT(k_pair_gather_blocked, dim3((unsigned)ni), dim3(256), lds, s, a);
+        const k_pair_gather_blocked_args a{T, XBg, EAB, c0, E, reinterpret_cast<const int4 *>(items) + i0, eoff, offA, offB, NB, sdim, nB, SB, KA, KB, a0,
+                                           lo ? *lo : gdca_logodds_terms{}};
+        GDCA_LAUNCH_DIRECT(kern, dim3((unsigned)ni), dim3(256), lds, s, a);
     }
     return hipSuccess;
+}
+
+// ---- the negation for the assignment on log-odds -------------------------------------------------------------------------------------------
+// dst[i] = -src[i] over the packed blocks: the assignment MAXIMISES the total log-odds of a species by minimising -L (exact)
+__global__ __launch_bounds__(256) void k_negate(const double *__restrict__ src, double *__restrict__ dst, size_t len)
+{
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < len; i += step) dst[i] = -src[i];
+}
+
+void gdca_launch_negate(hipStream_t s, const double *src, double *dst, size_t len)
+{
+    if (len == 0) return;
+    const size_t blocks = (len + 255) / 256;
+    GDCA_LAUNCH_DIRECT(k_negate, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, s, src, dst, len);
 }

@@ -658,10 +658,12 @@ struct k_cov_from_pij_args {
     double pc;
     double *out;
     size_t ld;
+    size_t ldp;  // leading dimension of Pij: n, or -- a principal block of whole sites (the marginal fits of the log-odds) -- the joint n
 };
-static inline k_cov_from_pij_args k_cov_from_pij_mk(const double *Pij, const double *Pi_pc, int n, int q, double pc, double *out, size_t ld)
+static inline k_cov_from_pij_args k_cov_from_pij_mk(const double *Pij, const double *Pi_pc, int n, int q, double pc, double *out, size_t ld,
+                                                    size_t ldp)
 {
-    return k_cov_from_pij_args{Pij, Pi_pc, n, q, pc, out, ld};
+    return k_cov_from_pij_args{Pij, Pi_pc, n, q, pc, out, ld, ldp};
 }
 template <int CAP>
 __global__ __launch_bounds__(256) void k_cov_from_pij(const BatchArgs<k_cov_from_pij_args, CAP> B_)
@@ -680,7 +682,7 @@ __global__ __launch_bounds__(256) void k_cov_from_pij(const BatchArgs<k_cov_from
     const double pcq = pc / (double)q;
     const double off_add = pcq / (double)q;
     const double pi_c = Pi_pc[c];
-    const double *__restrict__ src = Pij + (size_t)c * n;
+    const double *__restrict__ src = Pij + (size_t)c * a_.ldp;
     double *__restrict__ dst = out + (size_t)c * ld;
     const int r0 = blockIdx.x * (256 * COV_ROWS_PER_THREAD) + threadIdx.x;
     double pt[COV_ROWS_PER_THREAD], pr[COV_ROWS_PER_THREAD];
@@ -701,9 +703,12 @@ __global__ __launch_bounds__(256) void k_cov_from_pij(const BatchArgs<k_cov_from
     }
 }
 
-void gdca_launch_cov_from_pij(hipStream_t s, const double *Pij, const double *Pi_pc, int N, int q, double pc, double *out, size_t ld)
+// ldp != 0: the principal block of N whole sites whose first element Pij and Pi_pc point at, inside a Pij of leading dimension ldp -- an
+// element depends on its row and column only through their difference of sites and their equality, so the block's entries are bit for
+// bit the entries of the joint covariance
+void gdca_launch_cov_from_pij(hipStream_t s, const double *Pij, const double *Pi_pc, int N, int q, double pc, double *out, size_t ld, size_t ldp)
 {
     const int n = N * (q - 1);
     const int rows = 256 * COV_ROWS_PER_THREAD;
-    (gdca_launch<k_cov_from_pij_args, k_cov_from_pij<1>, k_cov_from_pij<GDCA_MAXB>>(dim3((n + rows - 1) / rows, n), dim3(256), 0, s, k_cov_from_pij_mk(Pij, Pi_pc, n, q, pc, out, ld)));
+    (gdca_launch<k_cov_from_pij_args, k_cov_from_pij<1>, k_cov_from_pij<GDCA_MAXB>>(dim3((n + rows - 1) / rows, n), dim3(256), 0, s, k_cov_from_pij_mk(Pij, Pi_pc, n, q, pc, out, ld, ldp ? ldp : (size_t)n)));
 }

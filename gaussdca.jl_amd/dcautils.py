@@ -475,6 +475,63 @@ def pair_energies_blocked(mJ, Pi, XA, XB, species_a, species_b, q: int = 21, wha
     return _block_views(E, offA, offB)
 
 
+def logodds_information(logdet: float, logdet_a: float, logdet_b: float) -> float:
+    """I = -1/2 (log det C - log det C_AA - log det C_BB), rounded operation by operation as the library forms it (gdca_run_pair_logodds):
+    the Gaussian mutual information of the halves, the expected log-odds of a native pair."""
+    return float(np.float64(-0.5) * ((np.float64(logdet) - np.float64(logdet_a)) - np.float64(logdet_b)))
+
+
+def _logodds_args(mJ, mJA, mJB, Pi, XA, XB, q):
+    """the operator log-odds' arrays as the library takes them, their sizes held against each other"""
+    mJ, mJA, mJB = (np.ascontiguousarray(m, dtype=np.float64) for m in (mJ, mJA, mJB))
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    XAf, XBf = _symbols(XA, "XA"), _symbols(XB, "XB")
+    split, KA = XAf.shape
+    NB, KB = XBf.shape
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    s = int(q) - 1
+    n, nA, nB = (split + NB) * s, split * s, NB * s
+    if split < 1 or NB < 1 or mJ.shape != (n, n) or mJA.shape != (nA, nA) or mJB.shape != (nB, nB) or Pi.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: XA has {split} sites and XB {NB}, q = {q}, so mJ, mJA, mJB must be {n} x {n}, {nA} x {nA}, "
+                            f"{nB} x {nB} and Pi have {n} entries (got {mJ.shape}, {mJA.shape}, {mJB.shape} and {Pi.shape})")
+    if KA < 1 or KB < 1:
+        raise ArgumentError("XA or XB holds no sequence")
+    return mJ, mJA, mJB, Pi, XAf, XBf, split + NB, split, KA, KB
+
+
+def pair_logodds(mJ, mJA, mJB, Pi, XA, XB, information: float, q: int = 21, ctx=None) -> np.ndarray:
+    """L[a, b] = log p_AB(a (+) b) - log p_A(a) - log p_B(b) for every pairing of the columns of XA with those of XB (as
+    ``pair_energies`` takes them) under the joint model (mJ = inv(C), Pi) and the two marginal models mJA = inv(C_AA), mJB =
+    inv(C_BB) -- the true marginals, not the diagonal blocks of mJ; ``information`` = ``logodds_information`` of the three log dets.
+    L = ((EmA[a] + EmB[b]) - E[a, b]) + I with the marginal and the joint energies.  Higher = more likely partners.  Returns a
+    (K_A, K_B) array.  The matrices must be symmetric (their lower triangles are read)."""
+    mJ, mJA, mJB, Pi, XAf, XBf, N, split, KA, KB = _logodds_args(mJ, mJA, mJB, Pi, XA, XB, q)
+    ctx = ctx or default_context()
+    L = np.empty((KA, KB), dtype=np.float64, order="F")
+    ctx.check(ctx.lib.gdca_pair_logodds(ctx.h, _lib._p(mJ), _lib._p(mJA), _lib._p(mJB), _lib._p(Pi), N, int(q), split, _lib._p(XAf), KA,
+                                        _lib._p(XBf), KB, float(information), _lib._p(L)))
+    return L
+
+
+def pair_logodds_blocked(mJ, mJA, mJB, Pi, XA, XB, species_a, species_b, information: float, q: int = 21, ctx=None) -> list:
+    """``pair_logodds`` inside the species only, in ``pair_energies_blocked``' form: a list of (kA_s, kB_s) matrices, one per species in
+    ascending order of the labels.  Every entry is bit for bit the entry ``pair_logodds`` gives that pairing."""
+    mJ, mJA, mJB, Pi, XAf, XBf, N, split, KA, KB = _logodds_args(mJ, mJA, mJB, Pi, XA, XB, q)
+    perm_a, perm_b, offA, offB, _ = species_blocks(species_a, species_b)
+    if len(perm_a) != KA or len(perm_b) != KB:
+        raise ArgumentError(f"species_a / species_b have {len(perm_a)} / {len(perm_b)} labels, XA / XB hold {KA} / {KB} sequences")
+    XAs, XBs = np.asfortranarray(XAf[:, perm_a]), np.asfortranarray(XBf[:, perm_b])
+    ctx = ctx or default_context()
+    L = np.empty(int(np.sum(np.diff(offA).astype(np.int64) * np.diff(offB))), dtype=np.float64)
+    ctx.check(ctx.lib.gdca_pair_logodds_blocked(ctx.h, _lib._p(mJ), _lib._p(mJA), _lib._p(mJB), _lib._p(Pi), N, int(q), split, _lib._p(XAs),
+                                                KA, _lib._p(XBs), KB, _lib._p(offA), _lib._p(offB), len(offA) - 1, float(information),
+                                                _lib._p(L)))
+    return _block_views(L, offA, offB)
+
+
 def assign_blocks(blocks, ctx=None):
     """The minimum-cost one-to-one assignment inside every matrix of ``blocks`` (a list of (kA_s, kB_s) float64 cost matrices: what
     ``pair_energies_blocked`` returns, or any costs), on the device: min(kA_s, kB_s) pairs a species.  Returns ``(match, gap)``, two

@@ -182,6 +182,35 @@ def gDCA_loglik(filename: str, sequences=None, pseudocount: float = 0.8, theta="
                            "log-likelihoods")
 
 
+def _split_check(split, XA, XB):
+    """check(N) of the entries that score pairings across a split: the split and the halves' sizes held against the alignment"""
+    def check(N):
+        if not isinstance(split, (int, np.integer)) or not 1 <= split <= N - 1:
+            raise ArgumentError(f"invalid split value: {split} (must be between 1 and N - 1 = {N - 1})")
+        if XA is not None and XA.shape[0] != split:
+            raise ArgumentError(f"seqs_a have {XA.shape[0]} sites, protein A has {split}")
+        if XB is not None and XB.shape[0] != N - split:
+            raise ArgumentError(f"seqs_b have {XB.shape[0]} sites, protein B has {N - split}")
+        if (XA is not None and XA.shape[1] < 1) or (XB is not None and XB.shape[1] < 1):
+            raise ArgumentError("seqs_a or seqs_b holds no sequence")
+
+    return check
+
+
+def _species_half(ptr, N, M, X, perm, lo, hi, name):
+    """one side's sequences sorted by species (sites lo .. hi - 1 of the alignment at ptr where X is None); None: the alignment's own
+    already are"""
+    count = M if X is None else X.shape[1]
+    if len(perm) != count:
+        raise ArgumentError(f"{name} has {len(perm)} labels for {count} sequences")
+    if X is not None:
+        return np.asfortranarray(X[:, perm])
+    if np.array_equal(perm, np.arange(M)):
+        return None
+    Z = np.ctypeslib.as_array(C.cast(C.c_void_p(ptr), C.POINTER(C.c_int8)), shape=(M, N))  # (row k = sequence k)
+    return np.asfortranarray(Z[perm, lo:hi].T)
+
+
 def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what="energy", pseudocount: float = 0.8, theta=":auto",
                        max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
     """Energies of every pairing across a split alignment under the Gaussian model gDCA fits to ``filename``, an alignment of
@@ -202,15 +231,7 @@ def gDCA_pair_energies(filename: str, split: int, seqs_a=None, seqs_b=None, what
     w = _what_arg(what)
     XA, XB = _sequences_arg(seqs_a, "seqs_a", "a sites x K"), _sequences_arg(seqs_b, "seqs_b", "a sites x K")
 
-    def check(N):
-        if not isinstance(split, (int, np.integer)) or not 1 <= split <= N - 1:
-            raise ArgumentError(f"invalid split value: {split} (must be between 1 and N - 1 = {N - 1})")
-        if XA is not None and XA.shape[0] != split:
-            raise ArgumentError(f"seqs_a have {XA.shape[0]} sites, protein A has {split}")
-        if XB is not None and XB.shape[0] != N - split:
-            raise ArgumentError(f"seqs_b have {XB.shape[0]} sites, protein B has {N - split}")
-        if (XA is not None and XA.shape[1] < 1) or (XB is not None and XB.shape[1] < 1):
-            raise ArgumentError("seqs_a or seqs_b holds no sequence")
+    check = _split_check(split, XA, XB)
 
     return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, check,
                            lambda c, ptr, N, M, q: c.run_pair_energies_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split),
@@ -244,30 +265,11 @@ def gDCA_partner_match(filename: str, split: int, seqs_a=None, seqs_b=None, spec
         raise ArgumentError("species_a and species_b are needed: one integer label per sequence")
     perm_a, perm_b, offA, offB, _ = species_blocks(species_a, species_b)
 
-    def check(N):
-        if not isinstance(split, (int, np.integer)) or not 1 <= split <= N - 1:
-            raise ArgumentError(f"invalid split value: {split} (must be between 1 and N - 1 = {N - 1})")
-        if XA is not None and XA.shape[0] != split:
-            raise ArgumentError(f"seqs_a have {XA.shape[0]} sites, protein A has {split}")
-        if XB is not None and XB.shape[0] != N - split:
-            raise ArgumentError(f"seqs_b have {XB.shape[0]} sites, protein B has {N - split}")
-        if (XA is not None and XA.shape[1] < 1) or (XB is not None and XB.shape[1] < 1):
-            raise ArgumentError("seqs_a or seqs_b holds no sequence")
+    check = _split_check(split, XA, XB)
 
     def run(c, ptr, N, M, q):
-        def half(X, perm, lo, hi, name):
-            """that side's sequences sorted by species; None: the alignment's own already are"""
-            count = M if X is None else X.shape[1]
-            if len(perm) != count:
-                raise ArgumentError(f"{name} has {len(perm)} labels for {count} sequences")
-            if X is not None:
-                return np.asfortranarray(X[:, perm])
-            if np.array_equal(perm, np.arange(M)):
-                return None
-            Z = np.ctypeslib.as_array(C.cast(C.c_void_p(ptr), C.POINTER(C.c_int8)), shape=(M, N))  # (row k = sequence k)
-            return np.asfortranarray(Z[perm, lo:hi].T)
-
-        XAs, XBs = half(XA, perm_a, 0, int(split), "species_a"), half(XB, perm_b, int(split), N, "species_b")
+        XAs = _species_half(ptr, N, M, XA, perm_a, 0, int(split), "species_a")
+        XBs = _species_half(ptr, N, M, XB, perm_b, int(split), N, "species_b")
         (E, m, g), st = c.run_partner_match_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split), *_ptr_count(XAs),
                                                 *_ptr_count(XBs), offA, offB, w, want_blocks=return_blocks)
         match, gap = np.empty_like(m), np.empty_like(g)
@@ -276,6 +278,63 @@ def gDCA_partner_match(filename: str, split: int, seqs_a=None, seqs_b=None, spec
         return ((match, gap, _block_views(E, offA, offB)) if return_blocks else (match, gap)), st
 
     return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, check, run, "matches")
+
+
+def gDCA_pair_logodds(filename: str, split: int, seqs_a=None, seqs_b=None, pseudocount: float = 0.8, theta=":auto",
+                      max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, return_info: bool = False, **kw):
+    """Log-odds of every pairing across a split alignment: L[a, b] = log p_AB(a (+) b) - log p_A(a) - log p_B(b), the joint Gaussian
+    model gDCA fits to ``filename`` against the two proteins modelled on their own -- the TRUE marginals N(Pi_A, C_AA), N(Pi_B, C_BB)
+    of that very fit (same weights, theta and pseudocount; two more inverses).  This is the method's partner score: where the joint
+    energy of ``gDCA_pair_energies`` ranks a pairing largely by how typical a and b each are, the log-odds removes exactly that part.
+    HIGHER = more likely partners.  Arguments as ``gDCA_pair_energies`` (without ``what``).  Returns the (K_A, K_B) matrix;
+    ``return_info=True``: ``(L, info)`` with the three log dets, the mutual information I of the halves (the expected log-odds of a
+    native pair), the marginal energies ``EmA`` / ``EmB`` and the marginal fits' ``refined``.  Stats of the joint fit go to
+    ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_pair_logodds() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    XA, XB = _sequences_arg(seqs_a, "seqs_a", "a sites x K"), _sequences_arg(seqs_b, "seqs_b", "a sites x K")
+
+    def run(c, ptr, N, M, q):
+        (L, EmA, EmB, info), st = c.run_pair_logodds_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split), *_ptr_count(XA),
+                                                         *_ptr_count(XB))
+        return ((L, dict(info, EmA=EmA, EmB=EmB)) if return_info else L), st
+
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, _split_check(split, XA, XB), run, "log-odds")
+
+
+def gDCA_partner_logodds(filename: str, split: int, seqs_a=None, seqs_b=None, species_a=None, species_b=None, pseudocount: float = 0.8,
+                         theta=":auto", max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, return_blocks: bool = False,
+                         return_info: bool = False, **kw):
+    """Partner matching per species on the log-odds of ``gDCA_pair_logodds``: inside every species the sequences of A are matched one
+    to one with those of B at MAXIMUM total log-odds.  Arguments and the returned ``(match, gap)`` as ``gDCA_partner_match`` (without
+    ``what``); ``gap[a]`` is the matched log-odds minus the greatest other one of a with a sequence of B of its species (+inf: the only
+    candidate; 0.0: unmatched; negative: the assignment overrode a's own best).  ``return_blocks=True`` adds the per-species log-odds
+    matrices, ``return_info=True`` the info dict (after them).  Stats of the joint fit go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_partner_logodds() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    XA, XB = _sequences_arg(seqs_a, "seqs_a", "a sites x K"), _sequences_arg(seqs_b, "seqs_b", "a sites x K")
+    if species_a is None or species_b is None:
+        raise ArgumentError("species_a and species_b are needed: one integer label per sequence")
+    perm_a, perm_b, offA, offB, _ = species_blocks(species_a, species_b)
+
+    def run(c, ptr, N, M, q):
+        XAs = _species_half(ptr, N, M, XA, perm_a, 0, int(split), "species_a")
+        XBs = _species_half(ptr, N, M, XB, perm_b, int(split), N, "species_b")
+        (L, m, g, info), st = c.run_partner_logodds_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), int(split), *_ptr_count(XAs),
+                                                        *_ptr_count(XBs), offA, offB, want_blocks=return_blocks)
+        match, gap = np.empty_like(m), np.empty_like(g)
+        match[perm_a] = np.where(m >= 0, perm_b[np.maximum(m, 0)], -1)
+        gap[perm_a] = g
+        out = (match, gap) + ((_block_views(L, offA, offB),) if return_blocks else ()) + ((info,) if return_info else ())
+        return out, st
+
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, _split_check(split, XA, XB), run, "matches")
 
 
 def gDCA_partner_ipa(seqs_a, seqs_b, species_a, species_b, known_pairs=None, seed="singletons", n_inc: int = 6, max_rounds: int = 50,

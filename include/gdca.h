@@ -337,7 +337,8 @@ gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N,
 /* log det of the matrix of the last SPD inverse this context completed: gdca_spd_inverse(_dev), a member of gdca_spd_inverse_batch_dev
  * (ask that member's context), or any fused run once it has been collected (gdca_run*, _energies, _pair_energies, _partner_match,
  * _mutation_scan, _loglik, the members of a phase batch).  k: after gdca_run_multi* the member index -- the value of the pseudocount group
- * of p[k] --, 0 after everything else.  source (may be NULL): 0 = the sweep's pivots, 1 = the Cholesky fallback's diagonal.  Entry points
+ * of p[k] --, after a fused log-odds run (gdca_run_pair_logodds, gdca_run_partner_logodds) 0 = the joint C, 1 = C_AA, 2 = C_BB --,
+ * 0 after everything else.  source (may be NULL): 0 = the sweep's pivots, 1 = the Cholesky fallback's diagonal.  Entry points
  * that take no inverse leave the record alone.  GDCA_EINVAL: no inverse yet (or the last one did not complete: GDCA_EHIP), k out of
  * range, a run outstanding on the context, a null pointer.  Where that inverse ended GDCA_ENOTPD the value is NaN, with GDCA_OK.  No device
  * work: the value came back with the inverse's other scalars. */
@@ -427,6 +428,71 @@ gdca_status gdca_run_partner_match_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                                        int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB,
                                        const void *offA, const void *offB, int32_t S, int32_t what, double *E_dev, int32_t *match_dev,
                                        double *gap_dev, gdca_stats *st);
+
+/* ---- pair log-odds: the joint model against the two marginal models, and matching on them ------------------------------------------
+ * The partner score of the method (the paper's "protein-interaction partners") is the log-odds of a pairing under the joint model
+ * against the two proteins modelled on their own:
+ *     L(a, b) = log p_AB(a (+) b) - log p_A(a) - log p_B(b),      p_AB = N(Pi, C),  p_A = N(Pi_A, C_AA),  p_B = N(Pi_B, C_BB).
+ * The joint energy ranks a pairing largely by how typical a and b each are; the log-odds removes exactly that part.
+ * s = q - 1, n_A = split s, n_B = (N - split) s, n = n_A + n_B.  C is the covariance the fused run builds, Pi add_pseudocount's first
+ * result, Pi_A = Pi[0 .. n_A), Pi_B = Pi[n_A .. n).  C_AA and C_BB are the diagonal blocks of THAT VERY C -- entry for entry its bits:
+ * they share the joint alignment's weights, theta, Meff and pseudocount; they are not a refit on half the columns (which would
+ * reweight differently).  The marginals' precisions are mJ_A = inv(C_AA), mJ_B = inv(C_BB): the TRUE marginals, not the diagonal
+ * blocks of mJ = inv(C).
+ *     EmA[a] = 1/2 (x_a - Pi_A)' mJ_A (x_a - Pi_A)     gdca_energies' rule with N = split and Pi_A; EmB[b] likewise with Pi_B
+ *     E[a, b]                                          the joint energy: bit for bit gdca_(run_)pair_energies' with GDCA_PAIR_ENERGY
+ *     ld, ldA, ldB                                     the three log dets, each from the pivots of its own inverse (or from the
+ *                                                      fallback's diagonal where that inverse took the fallback)
+ *     I = -0.5 * ((ld - ldA) - ldB)                    formed once, on the host, in plain f64, no contraction: the Gaussian mutual
+ *                                                      information of the halves = the expected log-odds of a native pair (n log 2 pi
+ *                                                      cancels).  Mathematically I >= 0; rounding can leave it a few ulps of ld
+ *                                                      below zero (pseudocount 1: C is block diagonal).  It is not clamped.
+ *     L[a, b] = ((EmA[a] + EmB[b]) - E[a, b]) + I      exactly these three f64 operations in this order: L[a, b] is bit for bit that
+ *                                                      expression of the four values.  HIGHER = more likely partners.
+ * The bits of L[a, b] depend only on the model, a, b and split -- not on K_A, K_B, positions in the batch, option PAIR_CHUNK or the
+ * full or blocked form.  The gather kernels of the pair stage carry the combination in their epilogue (a third compile-time variant):
+ * E is never stored, K_A K_B doubles are written once.
+ *
+ * gdca_pair_logodds(_dev): the operator form on the caller's three precisions (n x n, n_A x n_A, n_B x n_B: symmetric, lower triangle
+ * read), Pi (n) and I; writes L[a + KA b].  Argument rules and the bad-symbol rule as gdca_pair_energies_dev.
+ * gdca_pair_logodds_blocked(_dev): the same inside the species of species-sorted sequences; offA / offB / S and the packed layout as
+ * gdca_pair_energies_blocked; every entry bit for bit the full form's.
+ * gdca_run_pair_logodds(_dev): fused.  The front end runs once; then three fits one after the other -- C_AA, C_BB, C last -- each
+ * through the SPD inverse with its conditioning screen, refinement, Cholesky fallback and second attempt as a single run of its own
+ * size takes them; the marginal fits score their half's sequences, the joint fit the pairings.  XA == NULL or XB == NULL takes that
+ * half of Z's own sequences, as gdca_run_pair_energies.  EmA_dev (K_A) and EmB_dev (K_B) are optional outputs.  info: optional HOST
+ * array of GDCA_LOGODDS_FIELDS f64 by the GDCA_LOGODDS_* indices: the three log dets (NaN for a fit that did not complete), I, the
+ * marginal fits' `refined` (as gdca_stats.refined), and -- 0 unless gdca_ctx_set_timing is on -- the device time of the two marginal
+ * fits.  st: the joint fit's stats, exactly what gdca_run_pair_energies reports (ms_pair_tally: the tallies into Pij_true; ms_total
+ * includes the marginal fits).  Afterwards gdca_last_logdet(ctx, k): k = 0 joint, 1 C_AA, 2 C_BB.
+ * gdca_run_partner_logodds(_dev): the fused form, then the blocked form and the assignment.  Arguments as gdca_run_partner_match without
+ * `what`, plus info.  The assignment MAXIMISES the total L inside every species (the minimum-cost assignment on -L; negation is
+ * exact); gap[a] = L[a, match(a)] - max_{b' != match(a)} L[a, b'], ONE f64 subtraction of two entries of L, with gdca_assign_blocks'
+ * special values: +inf where kB_s = 1, +0.0 for an unmatched a, negative where the assignment overrode the row's own best.
+ * L_dev == NULL keeps the blocked matrix in a buffer of the context.  GDCA_ASSIGN_MAX applies.
+ * Status: argument failures are GDCA_EINVAL with nothing run; a bad symbol is found on the device; where a fit fails (GDCA_ENOTPD, ..)
+ * the call returns the status of the first failing fit in the order the fits run (A, B, joint) and L is unspecified.  A principal block
+ * of a positive-definite matrix is positive definite, so a marginal fit can only fail where the joint one would.
+ * The `what` values of the pair, partner and IPA entry points stay {0, 1}: the log-odds has entry points of its own. */
+enum {
+    GDCA_LOGODDS_LOGDET = 0, GDCA_LOGODDS_LOGDET_A, GDCA_LOGODDS_LOGDET_B, GDCA_LOGODDS_INFORMATION, GDCA_LOGODDS_REFINED_A,
+    GDCA_LOGODDS_REFINED_B, GDCA_LOGODDS_MS_MARGINALS, GDCA_LOGODDS_RESERVED
+};
+#define GDCA_LOGODDS_FIELDS 8
+gdca_status gdca_pair_logodds_dev(gdca_ctx *ctx, const double *mJ_dev, const double *mJA_dev, const double *mJB_dev, const double *Pi_dev,
+                                  int32_t N, int32_t q, int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB,
+                                  double I, double *L_dev);
+gdca_status gdca_pair_logodds_blocked_dev(gdca_ctx *ctx, const double *mJ_dev, const double *mJA_dev, const double *mJB_dev,
+                                          const double *Pi_dev, int32_t N, int32_t q, int32_t split, const int8_t *XA_dev, int32_t KA,
+                                          const int8_t *XB_dev, int32_t KB, const void *offA, const void *offB, int32_t S, double I,
+                                          double *L_dev);
+gdca_status gdca_run_pair_logodds_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                      int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, double *L_dev,
+                                      double *EmA_dev, double *EmB_dev, double *info, gdca_stats *st);
+gdca_status gdca_run_partner_logodds_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                         int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB,
+                                         const void *offA, const void *offB, int32_t S, double *L_dev, int32_t *match_dev,
+                                         double *gap_dev, double *info, gdca_stats *st);
 
 /* ---- iterative partner matching: grow the paired alignment on the device ----------------------------------------------------------
  * Who wants to pair paralogs usually has no trusted alignment of pairs to fit on: two pools with species labels, and a few certain
@@ -572,6 +638,20 @@ gdca_status gdca_run_partner_match(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
                                    int32_t split, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA,
                                    const void *offB, int32_t S, int32_t what, double *E_host, int32_t *match_host, double *gap_host,
                                    gdca_stats *st);
+
+/* pair log-odds with host pointers: upload, the _dev form, download (L_host of gdca_run_partner_logodds may be NULL) */
+gdca_status gdca_pair_logodds(gdca_ctx *ctx, const double *mJ, const double *mJA, const double *mJB, const double *Pi, int32_t N, int32_t q,
+                              int32_t split, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, double I, double *L);
+gdca_status gdca_pair_logodds_blocked(gdca_ctx *ctx, const double *mJ, const double *mJA, const double *mJB, const double *Pi, int32_t N,
+                                      int32_t q, int32_t split, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, const void *offA,
+                                      const void *offB, int32_t S, double I, double *L);
+gdca_status gdca_run_pair_logodds(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
+                                  const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, double *L_host, double *EmA_host,
+                                  double *EmB_host, double *info, gdca_stats *st);
+gdca_status gdca_run_partner_logodds(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                     int32_t split, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA,
+                                     const void *offB, int32_t S, double *L_host, int32_t *match_host, double *gap_host, double *info,
+                                     gdca_stats *st);
 
 /* iterative partner matching with host pointers: upload, the _dev form, download (gdca_concat_pairs takes the caller's whole Z and
  * touches the requested columns alone; after a failed round gdca_run_partner_ipa still brings back the completed rounds' results) */
