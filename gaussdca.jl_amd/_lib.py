@@ -235,6 +235,22 @@ SYMBOLS = {
                                              C.c_int32, C.c_void_p, C.POINTER(Stats)]),
     "gdca_run_mutation_scan": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
                                          C.c_int32, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_double_mutant_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "gdca_double_mutant_scan": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "gdca_double_mutants_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p]),
+    "gdca_double_mutants": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                      C.c_void_p]),
+    "gdca_run_double_mutant_scan_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_double_mutant_scan": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_double_mutants_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_double_mutants": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -702,6 +718,50 @@ class Context:
         """gdca_mutation_scan_dev: mJ (n x n), Pi (n), X (N x K int8) and D (q N K doubles, (K, N, q) row-major) are device pointers."""
         self.check(self.lib.gdca_mutation_scan_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), C.c_void_p(X_ptr), int(K),
                                                    int(what), C.c_void_p(D_ptr)))
+
+    # ---- double mutants: the best double substitution and the epistasis of every site pair, listed double mutants ----
+    def run_double_mutant_scan_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int, K: int):
+        """gdca_run_double_mutant_scan on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run()
+        fits it, then the three maps of the K sequences X (N x K, same layout; required).  Returns ((Emin float64 (K, N, N), code int32
+        (K, N, N), epi float64 (K, N, N)), stats); entry [k, j, i] of the row-major arrays is [i, j, k] of include/gdca.h."""
+        shape = (max(int(K), 0), int(N), int(N))
+        Emin, code, epi = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.float64)
+        st = self._run_readout(self.lib.gdca_run_double_mutant_scan, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), _p(Emin),
+                               _p(code), _p(epi))
+        return (Emin, code, epi), st
+
+    def run_double_mutant_scan_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int, K: int,
+                                   Emin_ptr: int | None, code_ptr: int | None, epi_ptr: int | None):
+        """Device-pointer form (Z, X and the maps resident in HBM; a map given as None is skipped).  Returns the stats dict."""
+        return self._run_readout(self.lib.gdca_run_double_mutant_scan_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                 self._opt(Emin_ptr), self._opt(code_ptr), self._opt(epi_ptr))
+
+    def run_double_mutants_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int, K: int,
+                               muts_ptr: int, L: int):
+        """gdca_run_double_mutants on HOST arrays given by address: muts holds L records (k, i, b, j, c) of int32, 5 x L column-major.
+        Returns (ddE float64 (L,), stats)."""
+        out = np.empty(max(int(L), 0), dtype=np.float64)
+        return out, self._run_readout(self.lib.gdca_run_double_mutants, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                      self._opt(muts_ptr), int(L), _p(out))
+
+    def run_double_mutants_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int, K: int,
+                               muts_ptr: int, L: int, out_ptr: int):
+        """Device-pointer form.  Returns the stats dict."""
+        return self._run_readout(self.lib.gdca_run_double_mutants_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                 self._opt(muts_ptr), int(L), self._opt(out_ptr))
+
+    def double_mutant_scan_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int | None, K: int, Emin_ptr: int | None,
+                               code_ptr: int | None, epi_ptr: int | None) -> None:
+        """gdca_double_mutant_scan_dev: mJ (n x n), Pi (n), X (N x K int8) and the maps (N N K entries each; None: skipped) are device
+        pointers."""
+        self.check(self.lib.gdca_double_mutant_scan_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), self._opt(X_ptr), int(K),
+                                                        self._opt(Emin_ptr), self._opt(code_ptr), self._opt(epi_ptr)))
+
+    def double_mutants_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int | None, K: int, muts_ptr: int | None, L: int,
+                           out_ptr: int | None) -> None:
+        """gdca_double_mutants_dev: muts (5 x L int32) and out (L doubles) are device pointers like the rest."""
+        self.check(self.lib.gdca_double_mutants_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), self._opt(X_ptr), int(K),
+                                                    self._opt(muts_ptr), int(L), self._opt(out_ptr)))
 
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):

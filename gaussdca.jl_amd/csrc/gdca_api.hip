@@ -50,8 +50,8 @@ struct pair_blocks {
 };
 
 struct score_target {
-    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK } kind;
-    double *out;                       // S (N x N), E (K), E (KA x KB), E (packed blocks) or D (q x N x K)
+    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK, DOUBLE_SCAN, DOUBLE_LIST } kind;
+    double *out;                       // S (N x N), E (K), E (KA x KB), E (packed blocks), D (q x N x K), Emin (N x N x K, may be null) or ddE (L)
     int score, apc;                    // contact
     const int8_t *X;                   // energy (k_energy.hip) and mutation scan (k_mutation.hip, with `what`): N x K
     int K;
@@ -63,6 +63,10 @@ struct score_target {
     double *gap;
     bool packed;                       // partner: XA / XB lie packed and padded in the context already (pair_pack; the rounds of gdca_run_partner_ipa)
     size_t strideX;                    // energy: bytes from one sequence of X to the next (0: N -- whole sequences)
+    int32_t *dcode;                    // double-mutant scan (k_epistasis.hip): the maps beside Emin (`out`), each may be null
+    double *depi;
+    const int32_t *muts;               // listed double mutants: 5 x L records
+    int L;
     // pair / partner of a log-odds run (run_logodds): the pair stage waits for the collect, which knows the joint log det (logodds_epilogue);
     // lo.EmA / lo.EmB: the marginal fits' energies, ldA / ldB their log dets, lo.I what the collect makes of the three
     bool logodds;
@@ -133,6 +137,31 @@ static score_target mutation_target(const int8_t *Z, int M, const int8_t *X, int
     score_target t = energy_target(Z, M, X, K, D_dev);
     t.kind = score_target::MUTATION;
     t.what = what;
+    return t;
+}
+
+// (X is never the alignment itself here: N^2 M outputs are not on offer)
+static score_target double_scan_target(const int8_t *X, int K, double *Emin_dev, int32_t *code_dev, double *epi_dev)
+{
+    score_target t{};
+    t.kind = score_target::DOUBLE_SCAN;
+    t.out = Emin_dev;
+    t.dcode = code_dev;
+    t.depi = epi_dev;
+    t.X = X;
+    t.K = K;
+    return t;
+}
+
+static score_target double_list_target(const int8_t *X, int K, const int32_t *muts_dev, int L, double *out_dev)
+{
+    score_target t{};
+    t.kind = score_target::DOUBLE_LIST;
+    t.out = out_dev;
+    t.muts = muts_dev;
+    t.L = L;
+    t.X = X;
+    t.K = K;
     return t;
 }
 
@@ -207,6 +236,7 @@ struct gdca_ctx {
     // the host, the growing training alignment, the selection (and a seed's partners behind it), a round's match / gap, the match of
     // the round before, and the species of every sequence a
     gdca_buf IPAws, IPAcnt, IPAZ, IPAsel, IPAm, IPAg, IPAprev, IPAsp;
+    gdca_buf DMd;             // double-mutant scan (k_epistasis.hip): dE of every single substitution of its sequences, q N K doubles
     int ncu;                  // compute units of the device
     double *piv;              // the pivots of the context's last inverse, n_pad doubles inside Sg (inverse_job)
     // log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet): kept on the host, so that entry points
@@ -384,6 +414,7 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         {"MERGE_MCUS", &t->merge_mcus, -1, 16},  {"MERGE_GROUP", &t->merge_group, -1, 4}, {"MERGE_TILES", &t->merge_tiles, 1, 1 << 20},
         {"CHOLESKY", &t->cholesky, 0, 2},  {"PHASED_FRONTS", &t->phased_fronts, 0, 1}, {"PHASED_GRIDS", &t->phased_grids, -1, 8}, {"PHASED_STREAMS", &t->phased_streams, 1, 64},
         {"ENERGY_CHUNK", &t->energy_chunk, 0, 1 << 30}, {"PAIR_CHUNK", &t->pair_chunk, 0, 1 << 30},
+        {"EPI_GENERIC", &t->epi_generic, 0, 1},
     };
     for (auto &e : ints)
         if (!strcmp(k, e.name)) {
@@ -443,7 +474,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
                                         "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
                                         "GDCA_HAMMING_MODE", "GDCA_HAM_CUT", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
-                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK"};
+                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK", "GDCA_EPI_GENERIC"};
     for (const char *nm : names)
         if (const char *v = getenv(nm)) (void)gdca_tuning_set(t, nm, v);  // an unusable value leaves the default
 }
@@ -640,7 +671,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
                         &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
                         &ctx->LOa, &ctx->LOb, &ctx->PBN,
-                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp};
+                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < N_SCRATCH; ++i)
@@ -1125,6 +1156,25 @@ static gdca_status mutation_stage(gdca_ctx *ctx, const gdca_model &m, const int8
     return check_launch(ctx, "mutation scan");
 }
 
+// The double-mutant read-outs (k_epistasis.hip) of the K sequences X (N x K) under the model m: dE of every single substitution into
+// ctx->DMd first (the mutation stage), then -- muts == nullptr -- the maps Emin / code / epi (N x N x K; each may be nullptr) over the
+// block lower triangle, or the L listed double mutants (5 x L records) into out.  Illegal bytes of X: sc->bad_symbol bit 2; a record
+// out of range: bit 4.
+static gdca_status double_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, double *Emin_dev, int32_t *code_dev,
+                                double *epi_dev, const int32_t *muts_dev, int L, double *out_dev)
+{
+    CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)K * sizeof(double)));
+    CHK(mutation_stage(ctx, m, X_dev, K, GDCA_MUT_DELTA, (double *)ctx->DMd.p));
+    if (muts_dev) {
+        gdca_launch_double_mutants(ctx->stream, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, (const double *)ctx->DMd.p, muts_dev, L, m.N,
+                                   m.q - 1, K, out_dev, (gdca_dev_scalars *)ctx->sc.p);
+        return check_launch(ctx, "double mutants");
+    }
+    HIPCHK(gdca_launch_double_mutant_scan(ctx->stream, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, (const double *)ctx->DMd.p, m.N, m.q - 1,
+                                          K, Emin_dev, code_dev, epi_dev, ctx->tune.epi_generic != 0));
+    return check_launch(ctx, "double-mutant scan");
+}
+
 // -mJ in ctx->A (ld = n_pad) -> what `t` asks for
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t)
 {
@@ -1141,6 +1191,8 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
         CHK(pair_stage(ctx, m, t.split, t.XA, t.strideA, t.KA, t.XB, t.strideB, t.KB, t.what, t.out, &t.blocks, t.packed));
         return assign_stage(ctx, t.out, t.blocks, t.match, t.gap);
     case score_target::MUTATION: return mutation_stage(ctx, m, t.X, t.K, t.what, t.out);
+    case score_target::DOUBLE_SCAN: return double_stage(ctx, m, t.X, t.K, t.out, t.dcode, t.depi, nullptr, 0, nullptr);
+    case score_target::DOUBLE_LIST: return double_stage(ctx, m, t.X, t.K, nullptr, nullptr, nullptr, t.muts, t.L, t.out);
     case score_target::CONTACT: break;
     }
     double *S_dev = t.out;
@@ -1450,6 +1502,7 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
     if (st) CHK(fill_stats(ctx, st));
     const gdca_dev_scalars &h = *ctx->sc_host;
     if (h.bad_symbol & 4) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
+    if (h.bad_symbol & 16) return fail(ctx, GDCA_EINVAL, "a double-mutant record is out of range%s%s", "", "");
     if (h.bad_symbol) return fail(ctx, GDCA_EINVAL, "alignment holds a symbol outside 1..q%s%s", "", "");
     if (h.info == INT32_MIN)  // the sweep kernel's watchdog (k_inverse.hip, spin_until): a dependency wait ran out of time
         return fail(ctx, GDCA_EHIP, "SPD inverse aborted: a dependency wait inside the sweep kernel timed out%s%s", "", "");
@@ -2613,6 +2666,7 @@ static gdca_model operator_model(const double *mJ_dev, const double *Pi_dev, int
 static gdca_status sequences_checked(gdca_ctx *ctx)
 {
     CHK(fetch_scalars(ctx));
+    if (ctx->sc_host->bad_symbol & 16) return fail(ctx, GDCA_EINVAL, "a double-mutant record is out of range%s%s", "", "");
     if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
     return GDCA_OK;
 }
@@ -3265,6 +3319,59 @@ gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
     return run_target(ctx, Z_dev, N, M, q, p, mutation_target(Z_dev, M, X_dev, K, what, D_dev), st);
 }
 
+// the argument checks the double-mutant entry points share (nothing has run when one fails)
+static gdca_status validate_double(gdca_ctx *ctx, int N, int q, long long K)
+{
+    CHK(validate(ctx, N, 1, q));
+    if (N < 2) return fail(ctx, GDCA_EINVAL, "a double mutant needs two sites%s%s", "", "");
+    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    const long long nT = (N + 3) / 4;
+    if ((K + 63) / 64 * (nT * (nT + 1) / 2) > GDCA_EPI_MAX_GROUPS) return fail(ctx, GDCA_EINVAL, "N^2 K is too large for one scan%s%s", "", "");
+    return GDCA_OK;
+}
+
+gdca_status gdca_double_mutant_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                        int32_t K, double *Emin_dev, int32_t *code_dev, double *epi_dev)
+{
+    CHK(validate_double(ctx, N, q, K));
+    if (!mJ_dev || !Pi_dev || !X_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Emin_dev && !code_dev && !epi_dev) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    CHK(begin(ctx));
+    CHK(double_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, Emin_dev, code_dev, epi_dev, nullptr, 0, nullptr));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_double_mutants_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                    int32_t K, const void *muts_dev, int32_t L, double *out_dev)
+{
+    CHK(validate_double(ctx, N, q, K));
+    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
+    if (!mJ_dev || !Pi_dev || !X_dev || !muts_dev || !out_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(begin(ctx));
+    CHK(double_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, nullptr, nullptr, nullptr, (const int32_t *)muts_dev, L, out_dev));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_run_double_mutant_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                            const int8_t *X_dev, int32_t K, double *Emin_dev, int32_t *code_dev, double *epi_dev, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_double(ctx, N, q, K));
+    if (!Z_dev || !X_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Emin_dev && !code_dev && !epi_dev) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    return run_target(ctx, Z_dev, N, M, q, p, double_scan_target(X_dev, K, Emin_dev, code_dev, epi_dev), st);
+}
+
+gdca_status gdca_run_double_mutants_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                        const int8_t *X_dev, int32_t K, const void *muts_dev, int32_t L, double *out_dev, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_double(ctx, N, q, K));
+    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
+    if (!Z_dev || !X_dev || !muts_dev || !out_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return run_target(ctx, Z_dev, N, M, q, p, double_list_target(X_dev, K, (const int32_t *)muts_dev, L, out_dev), st);
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -3809,6 +3916,105 @@ gdca_status gdca_run_mutation_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t 
     CHK(up);
     CHK(gdca_run_mutation_scan_dev(ctx, Z_dev, N, M, q, p, X_dev, K, what, D_dev, st));
     return to_host(ctx, D_host, ctx->scratch[5], nd);
+}
+
+// the three maps of a double-mutant scan staged in scratch slots 5, 6, 7 (an absent one: nullptr) ...
+struct double_maps {
+    double *Emin;
+    int32_t *code;
+    double *epi;
+    size_t nd, ni;
+};
+static double_maps stage_double_maps(gdca_ctx *ctx, int N, int K, const double *Emin, const int32_t *code, const double *epi, gdca_status *up)
+{
+    double_maps m{};
+    m.nd = (size_t)N * (size_t)N * (size_t)K * sizeof(double);
+    m.ni = (size_t)N * (size_t)N * (size_t)K * sizeof(int32_t);
+    if (Emin) m.Emin = staged_out(ctx, 5, m.nd, up);
+    if (code) m.code = (int32_t *)staged_out(ctx, 6, m.ni, up);
+    if (epi) m.epi = staged_out(ctx, 7, m.nd, up);
+    return m;
+}
+// ... and brought back
+static gdca_status fetch_double_maps(gdca_ctx *ctx, const double_maps &m, double *Emin, int32_t *code, double *epi)
+{
+    if (Emin) CHK(to_host(ctx, Emin, ctx->scratch[5], m.nd));
+    if (code) CHK(to_host(ctx, code, ctx->scratch[6], m.ni));
+    if (epi) CHK(to_host(ctx, epi, ctx->scratch[7], m.nd));
+    return GDCA_OK;
+}
+
+gdca_status gdca_double_mutant_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                                    double *Emin, int32_t *code, double *epi)
+{
+    CHK(validate_double(ctx, N, q, K));
+    if (!mJ || !Pi || !X) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Emin && !code && !epi) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)N * (q - 1);
+    gdca_status up = GDCA_OK;
+    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
+    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
+    const double_maps m = stage_double_maps(ctx, N, K, Emin, code, epi, &up);
+    CHK(up);
+    CHK(gdca_double_mutant_scan_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, m.Emin, m.code, m.epi));
+    return fetch_double_maps(ctx, m, Emin, code, epi);
+}
+
+gdca_status gdca_double_mutants(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                                const void *muts, int32_t L, double *out)
+{
+    CHK(validate_double(ctx, N, q, K));
+    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
+    if (!mJ || !Pi || !X || !muts || !out) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)N * (q - 1), no = (size_t)L * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
+    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
+    const void *muts_dev = upload(ctx, 4, muts, (size_t)L * 5 * sizeof(int32_t), &up);
+    double *out_dev = staged_out(ctx, 5, no, &up);
+    CHK(up);
+    CHK(gdca_double_mutants_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, muts_dev, L, out_dev));
+    return to_host(ctx, out, ctx->scratch[5], no);
+}
+
+gdca_status gdca_run_double_mutant_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                        const int8_t *X_host, int32_t K, double *Emin_host, int32_t *code_host, double *epi_host, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_double(ctx, N, q, K));
+    if (!Z_host || !X_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Emin_host && !code_host && !epi_host) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
+    const double_maps m = stage_double_maps(ctx, N, K, Emin_host, code_host, epi_host, &up);
+    CHK(up);
+    CHK(gdca_run_double_mutant_scan_dev(ctx, Z_dev, N, M, q, p, X_dev, K, m.Emin, m.code, m.epi, st));
+    return fetch_double_maps(ctx, m, Emin_host, code_host, epi_host);
+}
+
+gdca_status gdca_run_double_mutants(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                    const int8_t *X_host, int32_t K, const void *muts_host, int32_t L, double *out_host, gdca_stats *st)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_double(ctx, N, q, K));
+    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
+    if (!Z_host || !X_host || !muts_host || !out_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t no = (size_t)L * sizeof(double);
+    gdca_status up = GDCA_OK;
+    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
+    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
+    const void *muts_dev = upload(ctx, 4, muts_host, (size_t)L * 5 * sizeof(int32_t), &up);
+    double *out_dev = staged_out(ctx, 5, no, &up);
+    CHK(up);
+    CHK(gdca_run_double_mutants_dev(ctx, Z_dev, N, M, q, p, X_dev, K, muts_dev, L, out_dev, st));
+    return to_host(ctx, out_host, ctx->scratch[5], no);
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

@@ -32,7 +32,7 @@ struct gdca_dev_scalars {
     int thresh;
     int info;
     int bad_symbol;  // bit 0: a byte of Z is outside 1..q; bit 1: a caller-given weight is outside [0, 1]; bit 2: a byte of the scored sequences is
-                     // outside 1..q; bit 3: an index of gdca_concat_pairs is outside its pool (GDCA_EINVAL)
+                     // outside 1..q; bit 3: an index of gdca_concat_pairs is outside its pool; bit 4: a record of gdca_double_mutants is out of range (GDCA_EINVAL)
     int di_noconv;   // number of site pairs whose tridiagonal QL iteration did not converge (DI score)
     int ham_mode;    // all-pairs Hamming kernel chosen for this family: 0 = exact distances, 1 = three-plane lower bound + refinement, 2 = the consensus
                      // lower bound on the fp4 matrix pipe + refinement (k_hamming_fp4.hip)
@@ -88,6 +88,7 @@ struct gdca_tuning {
     int cholesky;           // GDCA_CHOLESKY: the blocked dpotrf + dpotri fallback: 0 = never, 1 = where the sweep gave up (default), 2 = always
     int energy_chunk;       // GDCA_ENERGY_CHUNK: sequences one launch of the energy gather kernel takes; 0 = as many as keep its partials within ~256 MB
     int pair_chunk;         // GDCA_PAIR_CHUNK: sequences of protein A one launch of the pair-energy fold / gather kernels takes; 0 = as many as keep their folded rows within ~256 MB (the rule), a smaller count is taken as given, a larger one is cut to the rule
+    int epi_generic;        // GDCA_EPI_GENERIC (tests, measurements): 1 = the double-mutant scan runs its generic instance (s at run time) at s = 20 too
     char sweep_trace[256];  // GDCA_SWEEP_TRACE: file the in-kernel trace of the next inverse is written to ("" = off)
 };
 void gdca_tuning_from_env(gdca_tuning *t);
@@ -366,3 +367,15 @@ void gdca_launch_ipa_publish(hipStream_t s, const int32_t *match, const double *
 // (Xg) from the element-wise lower triangle of A (ld; sign -1: A holds -mJ) and g = mJ Pi (gdca_launch_energy_g)
 hipError_t gdca_launch_mutation_scan(hipStream_t s, const double *A, size_t ld, double sign, const double *g, const uint32_t *Xg, int N, int sdim,
                                int K, int what, double *D, int ncu);
+
+// ---- k_epistasis.hip: the double-mutant scan -- best double substitution and epistasis strength of every site pair, listed double mutants ---
+// (include/gdca.h, double-mutant scan).  Xg: the K sequences packed by gdca_launch_energy_pack; D: dE [K][N][q] of
+// gdca_launch_mutation_scan (what = GDCA_MUT_DELTA); A, ld, sign as there.
+#define GDCA_EPI_MAX_GROUPS (1LL << 24)  // workgroups one launch of the map kernel may have: ceil(K / 64) * T (T + 1) / 2, T = ceil(N / 4)
+// Emin / code / epi [i + N (j + N k)], each may be nullptr.  generic: the instance with s at run time at s = 20 too.  An error: more
+// workgroups than GDCA_EPI_MAX_GROUPS, or the dynamic LDS limit could not be raised; nothing was launched
+hipError_t gdca_launch_double_mutant_scan(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, const double *D, int N,
+                                          int sdim, int K, double *Emin, int32_t *code, double *epi, bool generic);
+// out[r] = ddE of record r of muts (5 x L int32: k, i, b, j, c); a record out of range: bit 4 of sc->bad_symbol, nothing indexed with it
+void gdca_launch_double_mutants(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, const double *D,
+                                const int32_t *muts, long long L, int N, int sdim, int K, double *out, gdca_dev_scalars *sc);

@@ -590,6 +590,75 @@ def mutation_scan(mJ, Pi, X, q: int = 21, what="delta", ctx=None) -> np.ndarray:
     return D
 
 
+def _double_model_args(mJ, Pi, X, q):
+    """the model and the sequences of the double-mutant operators, checked: (mJ, Pi, Xf, N, K)"""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    Xf = _symbols(X, "X")
+    N, K = Xf.shape
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = N * (int(q) - 1)
+    if N < 2 or mJ.shape != (n, n) or Pi.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: X has N = {N} sites (at least 2 are needed), q = {q}, so mJ must be {n} x {n} and Pi "
+                            f"have {n} entries (got {mJ.shape} and {Pi.shape})")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    return mJ, Pi, Xf, N, K
+
+
+def decode_double_code(code, q: int):
+    """code = (b - 1) + q (c - 1) of a double-mutant map -> (sub_i, sub_j) int8, the symbols b and c; 0 where code < 0 (the diagonal)"""
+    code = np.asarray(code)
+    ok = code >= 0
+    return (np.where(ok, code % int(q) + 1, 0).astype(np.int8), np.where(ok, code // int(q) + 1, 0).astype(np.int8))
+
+
+def double_mutant_scan(mJ, Pi, X, q: int = 21, ctx=None):
+    """The double-mutant landscape of the K columns of X (shape (N, K) like Z, symbols 1..q, q = the gap) under the Gaussian model
+    (mJ, Pi), one entry a site pair: ``(ddE_min, sub_i, sub_j, epistasis)``, each of shape (K, N, N) and indexed [k, i, j].
+    ddE_min[k, i, j] is the lowest energy change, in the sense of ``sequence_energies``, over the true double substitutions of sites i and
+    j (both symbols changed; the gap q is a target, "delete"), sub_i / sub_j (int8) the symbols it puts at site i and at site j, and
+    epistasis[k, i, j] = sqrt(sum over all targets of eps^2) with eps the part of a double mutant's energy change that is not the sum of
+    the two single changes ``mutation_scan`` gives.  ddE_min and epistasis are symmetric; the diagonal holds 0.  No mutant is written
+    down.  mJ must be symmetric (its lower triangle is read)."""
+    mJ, Pi, Xf, N, K = _double_model_args(mJ, Pi, X, q)
+    ctx = ctx or default_context()
+    Emin, code, epi = (np.empty((K, N, N), dtype=np.float64), np.empty((K, N, N), dtype=np.int32), np.empty((K, N, N), dtype=np.float64))
+    ctx.check(ctx.lib.gdca_double_mutant_scan(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xf), K, _lib._p(Emin), _lib._p(code),
+                                              _lib._p(epi)))
+    # (the library's [i + N (j + N k)] is [k, j, i] here: Emin and epi are symmetric, the transposed code names sub_i first)
+    sub_i, sub_j = decode_double_code(code.transpose(0, 2, 1), q)
+    return Emin, sub_i, sub_j, epi
+
+
+def _mutations_arg(muts) -> np.ndarray:
+    """(L, 5) records (k, i, b, j, c) -> int32, one record after the other in memory (the library's 5 x L column-major)"""
+    m = np.asarray(muts)
+    if m.ndim != 2 or m.shape[1] != 5 or not np.issubdtype(m.dtype, np.integer):
+        raise ArgumentError("mutations must be an (L, 5) integer array of records (k, i, b, j, c)")
+    if m.shape[0] < 1:
+        raise ArgumentError("mutations holds no record")
+    if m.size and (m.min() < np.iinfo(np.int32).min or m.max() > np.iinfo(np.int32).max):
+        raise ArgumentError("mutations holds a value beyond int32")
+    return np.ascontiguousarray(m, dtype=np.int32)
+
+
+def double_mutant_energies(mJ, Pi, X, muts, q: int = 21, ctx=None) -> np.ndarray:
+    """The energy change of the listed double mutants: ``muts`` is an (L, 5) integer array of records (k, i, b, j, c) -- sequence k
+    (a column of X), 0-based sites i != j, the symbols b (put at i) and c (put at j) in 1..q -- and the result has L entries, E(x_k with
+    i -> b, j -> c) - E(x_k) in the sense of ``sequence_energies``.  Which substitution is named first does not matter; a target equal to
+    the sequence's own symbol is allowed (the result is then the single change of the other site)."""
+    mJ, Pi, Xf, N, K = _double_model_args(mJ, Pi, X, q)
+    m = _mutations_arg(muts)
+    ctx = ctx or default_context()
+    out = np.empty(m.shape[0], dtype=np.float64)
+    ctx.check(ctx.lib.gdca_double_mutants(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xf), K, _lib._p(m), m.shape[0], _lib._p(out)))
+    return out
+
+
 def printrank(io, R: Sequence[Tuple[int, int, float]] = None):
     """printrank(io, R) / printrank(filename, R): one "%i %i %e" line per entry
     (src/GaussDCA.jl:67-74).  printrank(R) alone writes to stdout (the reference's one-argument

@@ -133,6 +133,30 @@ def mutation_scan_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, what: 
     return dD
 
 
+def double_mutant_scan_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, dEmin=None, dcode=None, depi=None, maps=("Emin", "code", "epi")):
+    """The double-mutant maps of the K sequences X (N x K int8) with every array in HBM (gdca_double_mutant_scan_dev): Emin (f64), code
+    (int32) and epi (f64), N N K entries each at [i + N (j + N k)].  ``maps`` names the ones wanted; a buffer is made for each of them
+    that is not given, the others come back as None.  Returns (dEmin, dcode, depi)."""
+    if "Emin" in maps:
+        dEmin = dEmin or DeviceBuffer(ctx, 8 * N * N * K)
+    if "code" in maps:
+        dcode = dcode or DeviceBuffer(ctx, 4 * N * N * K)
+    if "epi" in maps:
+        depi = depi or DeviceBuffer(ctx, 8 * N * N * K)
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.double_mutant_scan_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), opt(dX), int(K), opt(dEmin), opt(dcode), opt(depi))
+    return dEmin, dcode, depi
+
+
+def double_mutants_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, dmuts, L: int, dout=None):
+    """ddE of the L listed double mutants (dmuts: 5 x L int32 records (k, i, b, j, c), sites 0-based, symbols 1..q) of the K sequences
+    X with every array in HBM (gdca_double_mutants_dev).  Returns dout (L doubles)."""
+    dout = dout or DeviceBuffer(ctx, 8 * max(int(L), 1))
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.double_mutants_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), opt(dX), int(K), opt(dmuts), int(L), _ptr(dout).value)
+    return dout
+
+
 def scores_stepwise(Z, q: int, pseudocount: float = 0.8, theta=":auto", score: str = "frob", ctx: Context = None
                     ) -> Tuple[np.ndarray, dict]:
     """The six statements of src/GaussDCA.jl:28-42 one by one, arrays resident in HBM.  Z: (N, M) int8.

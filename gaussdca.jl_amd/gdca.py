@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, default_context
-from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
+from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _mutations_arg, decode_double_code, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
                        remove_duplicate_sequences, species_blocks)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
@@ -432,6 +432,59 @@ def gDCA_mutation_scan(filename: str, sequences=None, what="delta", pseudocount:
     return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N),
                            lambda c, ptr, N, M, q: c.run_mutation_scan_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta),
                                                                            *_ptr_count(X), w),
+                           "energy changes")
+
+
+def _required_sequences(sequences, name):
+    X = _sequences_arg(sequences, "sequences", "an N x K")
+    if X is None:
+        raise ArgumentError(f"{name}() needs sequences: the alignment's own are not scanned (N^2 M outputs)")
+    return X
+
+
+def gDCA_double_mutant_scan(filename: str, sequences, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+                            remove_dups: bool = False, ctx=None, **kw):
+    """The double-mutant landscape of sequences under the Gaussian model gDCA fits to the alignment in ``filename`` (the fit and its
+    arguments are ``gDCA_mutation_scan``'s): ``(ddE_min, sub_i, sub_j, epistasis)``, each (K, N, N) and indexed [k, i, j], as
+    ``dcautils.double_mutant_scan`` returns them -- the lowest energy change over the true double substitutions of every site pair, the
+    two symbols that reach it, and the pair's epistasis strength in that sequence.
+
+    ``sequences``: an ``(N, K)`` int8 array (symbols 1..q like ``Z``) or a string naming a FASTA file (read with
+    ``max_gap_fraction = 1.0``); required.  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_double_mutant_scan() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    X = _required_sequences(sequences, "gDCA_double_mutant_scan")
+    qbox = []
+
+    def run(c, ptr, N, M, q):
+        qbox.append(q)
+        return c.run_double_mutant_scan_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), *_ptr_count(X))
+
+    Emin, code, epi = _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N), run,
+                                      "energy changes")
+    sub_i, sub_j = decode_double_code(code.transpose(0, 2, 1), qbox[0])
+    return Emin, sub_i, sub_j, epi
+
+
+def gDCA_double_mutants(filename: str, sequences, mutations, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+                        remove_dups: bool = False, ctx=None, **kw) -> np.ndarray:
+    """The energy change of listed double mutants under the Gaussian model gDCA fits to the alignment in ``filename``: ``mutations``
+    is an (L, 5) integer array of records (k, i, b, j, c) as ``dcautils.double_mutant_energies`` takes them, ``sequences`` as for
+    ``gDCA_double_mutant_scan``.  Returns L energy changes -- what one holds against an experimental double-mutant library.  Stats go
+    to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_double_mutants() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    X = _required_sequences(sequences, "gDCA_double_mutants")
+    m = _mutations_arg(mutations)
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N),
+                           lambda c, ptr, N, M, q: c.run_double_mutants_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta),
+                                                                            *_ptr_count(X), m.ctypes.data, m.shape[0]),
                            "energy changes")
 
 

@@ -582,6 +582,50 @@ gdca_status gdca_mutation_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const do
 gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                        const int8_t *X_dev, int32_t K, int32_t what, double *D_dev, gdca_stats *st);
 
+/* ---- double-mutant scan: epistasis and the best double substitution of every site pair ------------------------------------
+ * The double-mutant landscape of a sequence under the model (what is compared with double-mutant libraries; which second
+ * substitution rescues a first one).  Conventions as in the mutation-scan section above: s, n, r(i, c), the gap q has no row, only the
+ * lower triangle of mJ is read.  No double mutant is written down: for a wild type x, sites i != j and targets b (at i), c (at j)
+ *     E(x with i -> b, j -> c) - E(x) = dE(x; i, b) + dE(x; j, c) + eps(x; i, b; j, c),
+ *     eps(x; i, b; j, c) = K(i,b; j,c) - K(i,x_i; j,c) - K(i,b; j,x_j) + K(i,x_i; j,x_j),      K(i,b; j,c) = mJ[r(i,b), r(j,c)],
+ * K = 0 where b or c is the gap.  eps is the EPISTASIS of the two substitutions in the background x.
+ * DEFINITIONS (everything below refers to these).  Orientation: i < j, a = x_i, a' = x_j.  B[b,c] = mJ[r(i,b), r(j,c)], exactly +0.0
+ * where b == q or c == q.  dE denotes the bits gdca_mutation_scan(.., GDCA_MUT_DELTA) returns for x.  The fixed f64 expressions:
+ *     eps[b,c] = (B[b,c] - B[a,c]) - (B[b,a'] - B[a,a'])
+ *     ddE[b,c] = (dE[i,b] + dE[j,c]) + eps[b,c]
+ * With this grouping eps is exactly 0 when b == a or c == a'.  (The fused forms read -mJ; every difference negates exactly, so they
+ * return the same bits as the operator forms on the same model.)
+ * MAPS, per sequence k: N x N x K entries each, column-major, index i + N (j + N k) (64-bit), both triangles filled:
+ *     Emin (f64)    min of ddE[b,c] over the admissible targets b != x_i, c != x_j, b and c in 1..q: the gap target ("delete") is
+ *                   included, a gap site may receive any residue -- the most stabilising true double substitution of the pair;
+ *     code (int32)  its minimiser as (b - 1) + q (c - 1) in the orientation i < j; ties go to the smallest code (ONE thread walks the
+ *                   codes in ascending order with a strict <); entry [j,i,k] holds the same pair transposed, (c - 1) + q (b - 1);
+ *     epi (f64)     the epistasis strength of the pair in this background, sqrt(sum over all q^2 targets of eps[b,c]^2), summed by one
+ *                   thread in ascending code order (a rounded product and a rounded sum a code).
+ * Emin[j,i,k] and epi[j,i,k] are the bits of [i,j,k].  Diagonal entries: Emin = +0.0, code = -1, epi = +0.0.  Any of the three
+ * pointers may be NULL: that map is skipped; all three NULL is GDCA_EINVAL.
+ * LISTED DOUBLE MUTANTS (the form one compares with an experimental library): muts holds L records of five int32 (k, i, b, j, c),
+ * column-major 5 x L, sites 0-based, symbols in 1..q; out[l] = ddE[b,c] of record l once it is put into the orientation i < j -- it
+ * does not matter which substitution is named first.  b == x_i or c == x_j is allowed: the result is then bit for bit the dE of the
+ * other site (+0.0 if both match).
+ * X is N x K int8 column-major, K >= 1, and must be given (there is no "scan Z itself" form: N^2 M outputs).  The bits of every
+ * output entry depend only on the model and x_k -- not on K, on where x_k stands in the batch, on the kernel instance or on fused /
+ * operator.  The stage keeps dE of all K sequences in a context workspace of q N K doubles.
+ * GDCA_EINVAL: N < 2, q outside 2..31, K < 1 or K > INT32_MAX - 256, ceil(K / 64) T (T + 1) / 2 > 2^24 with T = ceil(N / 4), L < 1,
+ * a null pointer (X included) -- nothing is run -- or, detected on the device with nothing indexed by it: a byte of X outside 1..q,
+ * a record with i == j or with k, i, j, b or c out of range.  On failure the outputs are unspecified.  Synchronous. */
+gdca_status gdca_double_mutant_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                        int32_t K, double *Emin_dev, int32_t *code_dev, double *epi_dev);
+gdca_status gdca_double_mutants_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                    int32_t K, const void *muts_dev, int32_t L, double *out_dev);
+/* Fused, exactly as gdca_run_mutation_scan (the fit, the conditioning screen, a refinement or fallback at collect time runs the stage
+ * again) but X must be given.  Stats: ms_score is the stage (the single-substitution scan and the double-mutant kernel), ms_fn 0. */
+gdca_status gdca_run_double_mutant_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                            const int8_t *X_dev, int32_t K, double *Emin_dev, int32_t *code_dev, double *epi_dev,
+                                            gdca_stats *st);
+gdca_status gdca_run_double_mutants_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                        const int8_t *X_dev, int32_t K, const void *muts_dev, int32_t L, double *out_dev, gdca_stats *st);
+
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* compute_theta's all-pairs identity sum (inside compute_weighted_frequencies, :28) */
 gdca_status gdca_pair_identity_sum(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, uint64_t *out);
@@ -670,6 +714,17 @@ gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi
                                int32_t what, double *D);
 gdca_status gdca_run_mutation_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                    const int8_t *X_host, int32_t K, int32_t what, double *D_host, gdca_stats *st);
+
+/* double-mutant scan with host pointers: upload, the _dev form, download */
+gdca_status gdca_double_mutant_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                                    double *Emin, int32_t *code, double *epi);
+gdca_status gdca_double_mutants(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                                const void *muts, int32_t L, double *out);
+gdca_status gdca_run_double_mutant_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                        const int8_t *X_host, int32_t K, double *Emin_host, int32_t *code_host, double *epi_host,
+                                        gdca_stats *st);
+gdca_status gdca_run_double_mutants(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                    const int8_t *X_host, int32_t K, const void *muts_host, int32_t L, double *out_host, gdca_stats *st);
 
 /* ---- host-side utilities around the hot path (plain C++, no GPU): the reference's callers of the path -------- */
 /* CPUs this process can really use: hardware threads capped by the cgroup CPU quota (a container may see 256 threads and be given

@@ -15,7 +15,7 @@
 module GaussDCAHip
 
 export gDCA, gDCA_stepwise, printrank, compute_weights, compute_weighted_frequencies, add_pseudocount,
-       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, inv_cholesky_logdet, gDCA_loglik, pair_energies, mutation_scan, gDCA_mutation_scan,
+       compute_FN, compute_DI_gauss, sequence_energies, gDCA_energies, inv_cholesky_logdet, gDCA_loglik, pair_energies, mutation_scan, gDCA_mutation_scan, double_mutant_scan, double_mutant_energies, gDCA_double_mutant_scan, gDCA_double_mutants,
        species_blocks, pair_energies_blocked_dev, assign_blocks_dev, run_partner_match_dev, gDCA_partner_match
 
 using LinearAlgebra
@@ -407,6 +407,101 @@ function gDCA_mutation_scan(filename::AbstractString; sequences = nothing, what:
     check(rc, st.info)
     st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: energy changes are unreliable" pseudocount
     return D
+end
+
+# The double-mutant landscape of the K columns of X under the model (include/gdca.h, "double-mutant scan"), an entry a site pair:
+# (ddE_min, sub_i, sub_j, epistasis), each N x N x K and indexed [i, j, k] -- the lowest energy change over the true double
+# substitutions of sites i and j (the gap q is a target), the symbols it puts at i and at j (0 on the diagonal), and the pair's
+# epistasis strength sqrt(sum eps^2) in that sequence.  No mutant is written down.
+function decode_double_code(code::Array{Int32, 3}, q::Integer)
+    sub_i = map(c -> c < 0 ? Int8(0) : Int8(c % q + 1), code)
+    sub_j = map(c -> c < 0 ? Int8(0) : Int8(c ÷ q + 1), code)
+    return sub_i, sub_j
+end
+
+function double_mutant_scan(mJ::Matrix{Float64}, Pi::Vector{Float64}, X::Matrix{Int8}, q::Integer = 21)
+    N, K = size(X); n = N * (q - 1)
+    (N ≥ 2 && size(mJ) == (n, n) && length(Pi) == n) || throw(ArgumentError("incompatible sizes of mJ, Pi, X and q"))
+    Emin = Array{Float64, 3}(undef, N, N, K); code = Array{Int32, 3}(undef, N, N, K); epi = Array{Float64, 3}(undef, N, N, K)
+    GC.@preserve mJ Pi X Emin code epi check(ccall((:gdca_double_mutant_scan, libgdca), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int8}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+        ctx(), mJ, Pi, N, q, X, K, Emin, code, epi))
+    sub_i, sub_j = decode_double_code(code, q)
+    return Emin, sub_i, sub_j, epi
+end
+
+# records (k, i, b, j, c) as a 5 x L integer matrix, k and the sites 1-based as everything in Julia -> the library's 0-based int32
+function double_mutant_records(muts::AbstractMatrix{<:Integer})
+    size(muts, 1) == 5 || throw(ArgumentError("mutations must be a 5 x L matrix of records (k, i, b, j, c)"))
+    size(muts, 2) ≥ 1 || throw(ArgumentError("mutations holds no record"))
+    m = Matrix{Int32}(muts)
+    m[1, :] .-= Int32(1); m[2, :] .-= Int32(1); m[4, :] .-= Int32(1)
+    return m
+end
+
+# The energy change of the listed double mutants: column l of muts = (k, i, b, j, c) -- sequence k (a column of X), sites i != j,
+# the symbols b (put at i) and c (put at j) in 1..q.  L entries; which substitution is named first does not matter.
+function double_mutant_energies(mJ::Matrix{Float64}, Pi::Vector{Float64}, X::Matrix{Int8}, muts::AbstractMatrix{<:Integer}, q::Integer = 21)
+    N, K = size(X); n = N * (q - 1)
+    (N ≥ 2 && size(mJ) == (n, n) && length(Pi) == n) || throw(ArgumentError("incompatible sizes of mJ, Pi, X and q"))
+    m = double_mutant_records(muts); L = size(m, 2)
+    out = Vector{Float64}(undef, L)
+    GC.@preserve mJ Pi X m out check(ccall((:gdca_double_mutants, libgdca), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int8}, Int32, Ptr{Cvoid}, Int32, Ptr{Float64}),
+        ctx(), mJ, Pi, N, q, X, K, m, L, out))
+    return out
+end
+
+# what the two fused double-mutant entries share: gDCA's reading of the alignment and of `sequences` (required: a Matrix{Int8}, N x K,
+# or the name of a FASTA file read with max_gap_fraction = 1)
+function double_mutant_inputs(filename, sequences, pseudocount, θ, max_gap_fraction, remove_dups)
+    check_arguments(filename, pseudocount, θ, max_gap_fraction, :frob, 1)
+    Z = DCAUtils.read_fasta_alignment(filename, max_gap_fraction)
+    if remove_dups
+        Z, _ = DCAUtils.remove_duplicate_sequences(Z)
+    end
+    q = Int(maximum(Z))
+    q ≥ 32 && error("parameter q=$q is too big (max 31 is allowed)")
+    X = sequences isa AbstractString ? DCAUtils.read_fasta_alignment(sequences, 1.0) : sequences
+    X isa Matrix{Int8} || throw(ArgumentError("sequences must be a Matrix{Int8} of symbols 1..q or a FASTA file name"))
+    size(X, 1) == size(Z, 1) || throw(ArgumentError("sequences have $(size(X, 1)) sites, the alignment has $(size(Z, 1))"))
+    return Z, X, q
+end
+
+function gDCA_double_mutant_scan(filename::AbstractString, sequences; pseudocount::Real = 0.8, θ = :auto, max_gap_fraction::Real = 0.9,
+                                 remove_dups::Bool = false)
+    Z, X, q = double_mutant_inputs(filename, sequences, pseudocount, θ, max_gap_fraction, remove_dups)
+    N, M = size(Z); K = size(X, 2)
+    Emin = Array{Float64, 3}(undef, N, N, K); code = Array{Int32, 3}(undef, N, N, K); epi = Array{Float64, 3}(undef, N, N, K)
+    p = Ref(GdcaParams(Float64(pseudocount), theta_arg(θ), 0, 0))
+    st = GdcaStats()
+    GC.@preserve Z X Emin code epi begin
+        rc = ccall((:gdca_run_double_mutant_scan, libgdca), Cint,
+                   (Ptr{Cvoid}, Ptr{Int8}, Int32, Int32, Int32, Ref{GdcaParams}, Ptr{Int8}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ref{GdcaStats}),
+                   ctx(), Z, N, M, q, p, X, K, Emin, code, epi, st)
+    end
+    check(rc, st.info)
+    st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: energy changes are unreliable" pseudocount
+    sub_i, sub_j = decode_double_code(code, q)
+    return Emin, sub_i, sub_j, epi
+end
+
+function gDCA_double_mutants(filename::AbstractString, sequences, mutations::AbstractMatrix{<:Integer}; pseudocount::Real = 0.8, θ = :auto,
+                             max_gap_fraction::Real = 0.9, remove_dups::Bool = false)
+    Z, X, q = double_mutant_inputs(filename, sequences, pseudocount, θ, max_gap_fraction, remove_dups)
+    N, M = size(Z); K = size(X, 2)
+    m = double_mutant_records(mutations); L = size(m, 2)
+    out = Vector{Float64}(undef, L)
+    p = Ref(GdcaParams(Float64(pseudocount), theta_arg(θ), 0, 0))
+    st = GdcaStats()
+    GC.@preserve Z X m out begin
+        rc = ccall((:gdca_run_double_mutants, libgdca), Cint,
+                   (Ptr{Cvoid}, Ptr{Int8}, Int32, Int32, Int32, Ref{GdcaParams}, Ptr{Int8}, Int32, Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{GdcaStats}),
+                   ctx(), Z, N, M, q, p, X, K, m, L, out, st)
+    end
+    check(rc, st.info)
+    st.refined < 0 && @warn "covariance too ill-conditioned for the refinement step and option CHOLESKY=0: energy changes are unreliable" pseudocount
+    return out
 end
 
 function compute_DI_gauss(mJ::Matrix{Float64}, C::Matrix{Float64}, q::Integer = 21)
