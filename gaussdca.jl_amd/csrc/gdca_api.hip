@@ -13,11 +13,24 @@
 #include "gdca_internal.h"
 #include "gdca_launch.h"
 
-#define N_SCRATCH 10
-
 struct gdca_buf {
     void *p;
     size_t cap;
+};
+
+// The device buffers behind the arrays of a host-pointer call (host_stage, below): the context's, grow-only, one per array in the order
+// a call asks for them.  Only host_stage can name them; gdca_ctx_destroy frees them through release().
+class stage_pool {
+    friend class host_stage;
+    static const int MAX_ARRAYS = 10;
+    gdca_buf buf[MAX_ARRAYS];
+
+public:
+    void release()
+    {
+        for (gdca_buf &b : buf)
+            if (b.p) (void)hipFree(b.p);
+    }
 };
 
 // Shared by the contexts of one pipeline (gdca_ctx_create_peer): orders their SPD-inverse stages one after
@@ -250,7 +263,7 @@ struct gdca_ctx {
     } ld;
     int *item0_host;           // pinned staging of the sweep's item table
     int item0_cap;
-    gdca_buf scratch[N_SCRATCH];
+    stage_pool staging;        // the arrays of a host-pointer call (host_stage)
     gdca_dev_scalars *sc_host;  // pinned
     gdca_dev_scalars *sc_host_dev;  // ... as the device addresses it (k_publish_scalars)
     hipEvent_t ev[T_COUNT];    // the stage boundaries of a timed run (made when the first one opens its timeline)
@@ -674,8 +687,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
-    for (int i = 0; i < N_SCRATCH; ++i)
-        if (ctx->scratch[i].p) (void)hipFree(ctx->scratch[i].p);
+    ctx->staging.release();
     if (ctx->gate && --ctx->gate->refs == 0) {
         for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ctx->gate->ev[i]);
         if (ctx->gate->batch_stream) {
@@ -1236,6 +1248,65 @@ static gdca_status not_pending(gdca_ctx *ctx)
         return fail(ctx, GDCA_EINVAL, "a run is still enqueued on this context: call gdca_run_collect first%s%s", "", "");
     return GDCA_OK;
 }
+
+// The arrays of one host-pointer call, staged on the device: made on the context once the call's arguments have been checked, asked for
+// one array at a time, and finished with the status of the `_dev` form.  It does not open on a context with an enqueued run (nothing of
+// the context is touched then); the first error sticks, every later request does nothing and yields nullptr, so a caller checks
+// status() once.  An absent optional array (host pointer nullptr) stages nothing and yields nullptr.  Each array has a buffer of the
+// context's stage_pool to itself, so it starts where hipMalloc put it, and growing the buffer of a later array leaves the earlier
+// pointers of the call valid.
+// INVARIANT: what is staged for an enqueued run (gdca_run_ranked_async, gdca_run_ranked_phased_async: the alignment gdca_pending::Z
+// points at, and the score matrix) stays valid and unchanged until the run's collect -- no host_stage opens on a pending context, and
+// nothing else can name the pool's buffers.
+class host_stage {
+    gdca_ctx *ctx;
+    gdca_status st;
+    int n = 0;  // arrays staged so far
+    struct {
+        void *host;
+        size_t bytes;
+    } back[stage_pool::MAX_ARRAYS];  // where finish() copies array i (host nullptr: nowhere)
+
+    gdca_status hip(hipError_t e) { return e == hipSuccess ? GDCA_OK : fail(ctx, GDCA_EHIP, "staging a host array: %s%s", hipGetErrorString(e), ""); }
+    void *stage(const void *from, void *to, size_t bytes)
+    {
+        if (st == GDCA_OK && n == stage_pool::MAX_ARRAYS) st = fail(ctx, GDCA_EINVAL, "more staged arrays than a call may have%s%s", "", "");
+        if (st != GDCA_OK) return nullptr;
+        gdca_buf &b = ctx->staging.buf[n];
+        st = ensure(ctx, b, bytes);
+        if (st == GDCA_OK && from) st = hip(hipMemcpyAsync(b.p, from, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (st != GDCA_OK) return nullptr;
+        back[n].host = to;
+        back[n++].bytes = bytes;
+        return b.p;
+    }
+
+public:
+    explicit host_stage(gdca_ctx *c) : ctx(c), st(not_pending(c))
+    {
+        if (st == GDCA_OK) st = hip(hipSetDevice(c->device));
+    }
+    gdca_status status() const { return st; }
+    // an input, uploaded on the context's stream; an output, which finish() copies to `host` (its size is stated here only); an array
+    // the device works on in place, `from` uploaded and the result copied to `to` (the same array, or another); device-only room
+    template <class T> const T *in(const T *host, size_t bytes) { return host ? (const T *)stage(host, nullptr, bytes) : nullptr; }
+    template <class T> T *out(T *host, size_t bytes) { return host ? (T *)stage(nullptr, host, bytes) : nullptr; }
+    template <class T> T *inout(const T *from, T *to, size_t bytes) { return (T *)stage(from, to, bytes); }
+    void *room(size_t bytes) { return stage(nullptr, nullptr, bytes); }
+    // the first `bytes` of a staged array to the host, enqueued only: finish() waits for it
+    void fetch(void *host, const void *dev, size_t bytes)
+    {
+        if (host && bytes && st == GDCA_OK) st = hip(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // how a call ends, given the status of its `_dev` form: a failure is returned and nothing copied; otherwise every output comes
+    // back (none of zero bytes), with one synchronisation behind the last copy
+    gdca_status finish(gdca_status rs)
+    {
+        if (st != GDCA_OK || rs != GDCA_OK) return st != GDCA_OK ? st : rs;
+        for (int i = 0; i < n; ++i) fetch(back[i].host, ctx->staging.buf[i].p, back[i].bytes);
+        return st != GDCA_OK ? st : hip(hipStreamSynchronize(ctx->stream));
+    }
+};
 
 // ||X||_1 of the inverse the sweep has just left in ctx->A (sc->inv_norm1): what the collect decides a refinement on
 static gdca_status inverse_norm_stage(gdca_ctx *ctx, int n, int n_pad)
@@ -1960,17 +2031,6 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
     return st;
 }
 
-// a host alignment on its way into a fused run: Z into scratch[0] (enqueued on the context's stream), room for n_scores score
-// matrices in scratch[1]
-static gdca_status upload_alignment(gdca_ctx *ctx, const int8_t *Z_host, int N, int M, int n_scores = 1)
-{
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(ensure(ctx, ctx->scratch[0], (size_t)N * M));
-    CHK(ensure(ctx, ctx->scratch[1], (size_t)n_scores * N * N * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(ctx->scratch[0].p, Z_host, (size_t)N * M, hipMemcpyHostToDevice, ctx->stream));
-    return GDCA_OK;
-}
-
 gdca_status gdca_run_dev_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *const *Z_dev, const int32_t *N,
                                 const int32_t *M, const int32_t *q, const gdca_params *p, double *const *S_dev)
 {
@@ -1989,13 +2049,11 @@ gdca_status gdca_run(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, 
 {
     CHK(validate(ctx, N, M, q));
     if (!Z_host || !S_host) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    CHK(upload_alignment(ctx, Z_host, N, M));
-    gdca_status rs = gdca_run_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, (double *)ctx->scratch[1].p, st);
-    if (rs != GDCA_OK) return rs;
-    HIPCHK(hipMemcpyAsync(S_host, ctx->scratch[1].p, (size_t)N * N * sizeof(double), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return GDCA_OK;
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    double *S_dev = sg.out(S_host, (size_t)N * N * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_dev(ctx, Z_dev, N, M, q, p, S_dev, st));
 }
 
 // ---- compute_ranking on the device (src/GaussDCA.jl:88-99, call :44) ---------------------------------------
@@ -2033,14 +2091,15 @@ gdca_status gdca_ranking_dev(gdca_ctx *ctx, const double *S_dev, int32_t N, int3
 gdca_status gdca_run_ranked_async(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t min_separation)
 {
     CHK(validate(ctx, N, M, q));
-    CHK(not_pending(ctx));
     if (!Z_host || min_separation < 1) return fail(ctx, GDCA_EINVAL, "null pointer or min_separation < 1%s%s", "", "");
     // (from pageable memory this copy holds the calling thread until the last byte is staged -- and overlaps whatever another
     // context of the same device is computing meanwhile: the pipelined batch driver's upload of the NEXT family)
-    CHK(upload_alignment(ctx, Z_host, N, M));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    double *S_dev = (double *)sg.room((size_t)N * N * sizeof(double));  // (both stay the run's until its collect: host_stage)
+    CHK(sg.status());
     CHK(upload_done(ctx));  // Z_host is the caller's again when this call returns (gdca.h), pinned or not
-    double *S_dev = (double *)ctx->scratch[1].p;
-    CHK(gdca_run_dev_async(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, S_dev));
+    CHK(gdca_run_dev_async(ctx, Z_dev, N, M, q, p, S_dev));
     enqueue_ranking(ctx, S_dev, N, min_separation);
     return GDCA_OK;
 }
@@ -2065,15 +2124,12 @@ gdca_status gdca_run_ranked_phased_async(gdca_ctx *const *ctxs, int32_t K, const
     HIPCHK(hipSetDevice(lead->device));
     for (int k = 0; k < K; ++k) {
         gdca_ctx *m = ctxs[k];
-        gdca_status es = ensure(m, m->scratch[0], (size_t)N[k] * M[k]);
-        if (es == GDCA_OK) es = ensure(m, m->scratch[1], (size_t)N[k] * N[k] * sizeof(double));
-        if (es != GDCA_OK) return member_error(lead, m, k, es);
         // (each member's upload goes to its own stream; gdca_run_dev_phased waits for the members' streams before it enqueues
         // anything, and the leader's upload sits on the very stream the batch is enqueued on)
-        if (hipMemcpyAsync(m->scratch[0].p, Z_host[k], (size_t)N[k] * M[k], hipMemcpyHostToDevice, m->stream) != hipSuccess)
-            return fail(lead, GDCA_EHIP, "upload of a member's alignment%s%s", "", "");
-        Zd[k] = (const int8_t *)m->scratch[0].p;
-        Sd[k] = (double *)m->scratch[1].p;
+        host_stage sg(m);
+        Zd[k] = sg.in(Z_host[k], (size_t)N[k] * M[k]);
+        Sd[k] = (double *)sg.room((size_t)N[k] * N[k] * sizeof(double));
+        if (sg.status() != GDCA_OK) return member_error(lead, m, k, sg.status());
     }
     // Z_host may be released when this call returns (gdca.h): from pageable memory the copies above are complete by now, from
     // pinned or registered memory they are true DMAs still in flight -- wait for every one of them HERE, whatever path the call
@@ -2275,13 +2331,15 @@ gdca_status gdca_run_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32
     CHK(multi_check_args(ctx, Z_host, N, M, q, p, K, S_host));
     if (K == 1) return gdca_run(ctx, Z_host, N, M, q, p, S_host, st);
     const size_t mat = (size_t)N * N;
-    CHK(upload_alignment(ctx, Z_host, N, M, K));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    double *S_dev = sg.out(S_host, (size_t)K * mat * sizeof(double));
+    CHK(sg.status());
     gdca_stats own[GDCA_MULTI_MAX];
-    const gdca_status rs = run_multi(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, K, (double *)ctx->scratch[1].p, mat, st ? st : own, nullptr);
+    const gdca_status rs = run_multi(ctx, Z_dev, N, M, q, p, K, S_dev, mat, st ? st : own, nullptr);
     if (rs != GDCA_OK && rs != GDCA_ENOTPD && rs != GDCA_ENOCONV) return rs;
     // (the members that did not fail are results: all K blocks come back)
-    HIPCHK(hipMemcpyAsync(S_host, ctx->scratch[1].p, (size_t)K * mat * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(sg.finish(GDCA_OK));
     return rs;
 }
 
@@ -2295,10 +2353,13 @@ gdca_status gdca_run_ranked_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N
     const long long len = gdca_ranking_length(N, min_separation);
     if (len > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     if (K == 1) return gdca_run_ranked(ctx, Z_host, N, M, q, p, min_separation, i_out, j_out, score_out, st);
-    CHK(upload_alignment(ctx, Z_host, N, M));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    double *S_dev = (double *)sg.room((size_t)N * N * sizeof(double));  // (the one matrix the members share)
+    CHK(sg.status());
     const multi_rank rk{min_separation, len, i_out, j_out, score_out};
     gdca_stats own[GDCA_MULTI_MAX];
-    return run_multi(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, p, K, (double *)ctx->scratch[1].p, 0, st ? st : own, &rk);
+    return run_multi(ctx, Z_dev, N, M, q, p, K, S_dev, 0, st ? st : own, &rk);
 }
 
 // ---- caller-visible device buffers ----------------------------------------------------------------------
@@ -2687,11 +2748,29 @@ static gdca_status run_target(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int
     return gdca_run_collect(ctx, st);
 }
 
+// The argument checks of an entry point with more to check than one condition: one text for its `_dev` form and its host-pointer form
+// (a pointer is only compared with nullptr, so device and host pointers are checked alike) -- the check_* functions here and further
+// down, beside validate_concat and ipa_check.  Nothing has run, and nothing is staged, when one fails.
+static gdca_status check_energies(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *X, int K, const void *E)
+{
+    CHK(validate(ctx, N, K, q));
+    if (!mJ || !Pi || !X || !E) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
+static gdca_status check_run_energies(gdca_ctx *ctx, const void *Z, int N, int M, int q, const void *p, const void *X, int K,
+                                      const void *E)  // ... and gdca_run_loglik
+{
+    CHK(validate(ctx, N, M, q));
+    if (!Z || !E || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (X && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    return GDCA_OK;
+}
+
 gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev, int32_t K,
                               double *E_dev)
 {
-    CHK(validate(ctx, N, K, q));
-    if (!mJ_dev || !Pi_dev || !X_dev || !E_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_energies(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, E_dev));
     CHK(begin(ctx));
     CHK(energy_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, E_dev));
     return sequences_checked(ctx);
@@ -2700,9 +2779,7 @@ gdca_status gdca_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double 
 gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                   const int8_t *X_dev, int32_t K, double *E_dev, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (X_dev && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    CHK(check_run_energies(ctx, Z_dev, N, M, q, p, X_dev, K, E_dev));
     return run_target(ctx, Z_dev, N, M, q, p, energy_target(Z_dev, M, X_dev, K, E_dev), st);
 }
 
@@ -2730,9 +2807,7 @@ gdca_status gdca_spd_inverse_logdet_dev(gdca_ctx *ctx, double *A_dev, int32_t n,
 gdca_status gdca_run_loglik_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                 const int8_t *X_dev, int32_t K, double *L_dev, double *logdet, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    if (!Z_dev || !L_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (X_dev && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    CHK(check_run_energies(ctx, Z_dev, N, M, q, p, X_dev, K, L_dev));
     if (logdet) *logdet = (double)NAN;
     const gdca_status rs = run_target(ctx, Z_dev, N, M, q, p, loglik_target(Z_dev, M, X_dev, K, L_dev), st);
     if (logdet && ctx->ld.count > 0 && !ctx->pending) *logdet = ctx->ld.val[0];
@@ -2749,12 +2824,28 @@ static gdca_status validate_pair(gdca_ctx *ctx, int N, int q, int split, long lo
     return GDCA_OK;
 }
 
+static gdca_status check_pair_energies(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, int split, const void *XA, int KA,
+                                       const void *XB, int KB, int what, const void *E)  // ... and the blocked form, before its species
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
+    if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
+// a fused pair form: gdca_run_pair_energies, gdca_run_pair_logodds (what: GDCA_PAIR_ENERGY)
+static gdca_status check_run_pair(gdca_ctx *ctx, const void *Z, int N, int M, int q, const void *p, int split, const void *XA, int KA,
+                                  const void *XB, int KB, int what, const void *out)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_pair(ctx, N, q, split, XA ? KA : M, XB ? KB : M, what));
+    if (!Z || !out || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
 gdca_status gdca_pair_energies_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, int32_t split,
                                    const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what, double *E_dev)
 {
-    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
-    if (!mJ_dev || !XA_dev || !XB_dev || !E_dev || (what == GDCA_PAIR_ENERGY && !Pi_dev))
-        return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_pair_energies(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, what, E_dev));
     CHK(begin(ctx));
     CHK(pair_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), split, XA_dev, (size_t)split, KA, XB_dev, (size_t)(N - split), KB, what, E_dev));
     return sequences_checked(ctx);
@@ -2764,9 +2855,7 @@ gdca_status gdca_run_pair_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                                        const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t what, double *E_dev,
                                        gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_pair(ctx, N, q, split, XA_dev ? KA : M, XB_dev ? KB : M, what));
-    if (!Z_dev || !E_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_run_pair(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, what, E_dev));
     return run_target(ctx, Z_dev, N, M, q, p, pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, what, E_dev), st);
 }
 
@@ -2792,6 +2881,35 @@ int64_t gdca_pair_blocks_length(const int32_t *offA, const int32_t *offB, int32_
     return blocks_length(offA, offB, S, nullptr);
 }
 
+// the species offsets of a call (host arrays in both forms of an entry) held against its counts; *total: the packed length
+static gdca_status check_blocks(gdca_ctx *ctx, const void *offA, const void *offB, int S, long long KA, long long KB, long long *total,
+                                int *kmax = nullptr)
+{
+    if (!offA || !offB) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    *total = blocks_length((const int32_t *)offA, (const int32_t *)offB, S, kmax);
+    if (*total < 0 || ((const int32_t *)offA)[S] != KA || ((const int32_t *)offB)[S] != KB)
+        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
+    return GDCA_OK;
+}
+
+static gdca_status check_assign_blocks(gdca_ctx *ctx, const void *E, const void *offA, const void *offB, int S, const void *match)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (!E || !offA || !offB || !match) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (S < 1) return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1)%s%s", "", "");
+    return GDCA_OK;
+}
+
+// a fused partner form: gdca_run_partner_match, gdca_run_partner_logodds (what: GDCA_PAIR_ENERGY); ka / kb: the pools as they will be used
+static gdca_status check_run_partner(gdca_ctx *ctx, const void *Z, int N, int M, int q, const void *p, int split, int ka, int kb,
+                                     const void *offA, const void *offB, int what, const void *match)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_pair(ctx, N, q, split, ka, kb, what));
+    if (!Z || !match || !offA || !offB || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
 // The species of a call: offsets checked against the counts (nothing has run when that fails), the table in ctx->PBtab and -- nB > 0:
 // the blocked gather will run over (N - split)(q - 1) = nB rows -- its work list in ctx->PBitems, cut at the chunks pair_stage will
 // make.  `first` is the caller's: blk->first points into it.
@@ -2800,9 +2918,8 @@ static gdca_status species_blocks(gdca_ctx *ctx, const void *offA_, const void *
 {
     const int32_t *offA = (const int32_t *)offA_, *offB = (const int32_t *)offB_;
     int kmax = 0;
-    const long long total = blocks_length(offA, offB, S, &kmax);
-    if (total < 0 || offA[S] != KA || offB[S] != KB)
-        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
+    long long total = 0;
+    CHK(check_blocks(ctx, offA, offB, S, KA, KB, &total, &kmax));
     if (assign && kmax > GDCA_ASSIGN_MAX)
         return fail(ctx, GDCA_EINVAL, "a species has more than GDCA_ASSIGN_MAX sequences on one side%s%s", "", "");
     CHK(not_pending(ctx));
@@ -2842,9 +2959,7 @@ gdca_status gdca_pair_energies_blocked_dev(gdca_ctx *ctx, const double *mJ_dev, 
                                            const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA,
                                            const void *offB, int32_t S, int32_t what, double *E_dev)
 {
-    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
-    if (!mJ_dev || !XA_dev || !XB_dev || !E_dev || !offA || !offB || (what == GDCA_PAIR_ENERGY && !Pi_dev))
-        return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_pair_energies(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, what, E_dev));
     pair_blocks blk;
     std::vector<long long> first;
     CHK(species_blocks(ctx, offA, offB, S, KA, KB, (N - split) * (q - 1), false, &blk, first));
@@ -2857,9 +2972,7 @@ gdca_status gdca_pair_energies_blocked_dev(gdca_ctx *ctx, const double *mJ_dev, 
 gdca_status gdca_assign_blocks_dev(gdca_ctx *ctx, const double *E_dev, const void *offA, const void *offB, int32_t S, int32_t *match_dev,
                                    double *gap_dev)
 {
-    if (!ctx) return GDCA_EINVAL;
-    if (!E_dev || !offA || !offB || !match_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (S < 1) return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1)%s%s", "", "");
+    CHK(check_assign_blocks(ctx, E_dev, offA, offB, S, match_dev));
     pair_blocks blk;
     std::vector<long long> first;
     CHK(species_blocks(ctx, offA, offB, S, ((const int32_t *)offA)[S], ((const int32_t *)offB)[S], 0, true, &blk, first));
@@ -2872,10 +2985,8 @@ gdca_status gdca_run_partner_match_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
                                        const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA, const void *offB,
                                        int32_t S, int32_t what, double *E_dev, int32_t *match_dev, double *gap_dev, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
     const int ka = XA_dev ? KA : M, kb = XB_dev ? KB : M;
-    CHK(validate_pair(ctx, N, q, split, ka, kb, what));
-    if (!Z_dev || !match_dev || !offA || !offB || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_run_partner(ctx, Z_dev, N, M, q, p, split, ka, kb, offA, offB, what, match_dev));
     CHK(check_params(ctx, p));
     pair_blocks blk;
     std::vector<long long> first;
@@ -2906,12 +3017,19 @@ static gdca_status logodds_operator(gdca_ctx *ctx, const double *mJ_dev, const d
     return sequences_checked(ctx);
 }
 
+static gdca_status check_pair_logodds(gdca_ctx *ctx, const void *mJ, const void *mJA, const void *mJB, const void *Pi, int N, int q, int split,
+                                      const void *XA, int KA, const void *XB, int KB, const void *L)  // ... and the blocked form, before its species
+{
+    CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
+    if (!mJ || !mJA || !mJB || !Pi || !XA || !XB || !L) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
 gdca_status gdca_pair_logodds_dev(gdca_ctx *ctx, const double *mJ_dev, const double *mJA_dev, const double *mJB_dev, const double *Pi_dev, int32_t N,
                                   int32_t q, int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, double I,
                                   double *L_dev)
 {
-    CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
-    if (!mJ_dev || !mJA_dev || !mJB_dev || !Pi_dev || !XA_dev || !XB_dev || !L_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_pair_logodds(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, L_dev));
     return logodds_operator(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, I, L_dev, nullptr);
 }
 
@@ -2919,9 +3037,7 @@ gdca_status gdca_pair_logodds_blocked_dev(gdca_ctx *ctx, const double *mJ_dev, c
                                           int32_t N, int32_t q, int32_t split, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB,
                                           const void *offA, const void *offB, int32_t S, double I, double *L_dev)
 {
-    CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
-    if (!mJ_dev || !mJA_dev || !mJB_dev || !Pi_dev || !XA_dev || !XB_dev || !L_dev || !offA || !offB)
-        return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_pair_logodds(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, L_dev));
     pair_blocks blk;
     std::vector<long long> first;
     CHK(species_blocks(ctx, offA, offB, S, KA, KB, (N - split) * (q - 1), false, &blk, first));
@@ -3044,9 +3160,7 @@ gdca_status gdca_run_pair_logodds_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_
                                       const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, double *L_dev, double *EmA_dev,
                                       double *EmB_dev, double *info, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_pair(ctx, N, q, split, XA_dev ? KA : M, XB_dev ? KB : M, GDCA_PAIR_ENERGY));
-    if (!Z_dev || !L_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_run_pair(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, GDCA_PAIR_ENERGY, L_dev));
     return run_logodds(ctx, Z_dev, N, M, q, p, pair_target(Z_dev, N, M, split, XA_dev, KA, XB_dev, KB, GDCA_PAIR_ENERGY, L_dev), EmA_dev, EmB_dev, info,
                        st);
 }
@@ -3055,10 +3169,8 @@ gdca_status gdca_run_partner_logodds_dev(gdca_ctx *ctx, const int8_t *Z_dev, int
                                          const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, const void *offA, const void *offB,
                                          int32_t S, double *L_dev, int32_t *match_dev, double *gap_dev, double *info, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
     const int ka = XA_dev ? KA : M, kb = XB_dev ? KB : M;
-    CHK(validate_pair(ctx, N, q, split, ka, kb, GDCA_PAIR_ENERGY));
-    if (!Z_dev || !match_dev || !offA || !offB || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_run_partner(ctx, Z_dev, N, M, q, p, split, ka, kb, offA, offB, GDCA_PAIR_ENERGY, match_dev));
     CHK(check_params(ctx, p));
     pair_blocks blk;
     std::vector<long long> first;
@@ -3090,12 +3202,18 @@ static gdca_status fetch_counts(gdca_ctx *ctx, gdca_ipa_counts *h)
     return GDCA_OK;
 }
 
+static gdca_status check_select_confident(gdca_ctx *ctx, const void *match, const void *gap, int KA, const void *sel)
+{
+    if (!ctx) return GDCA_EINVAL;
+    if (!match || !gap || !sel) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (KA < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    return GDCA_OK;
+}
+
 gdca_status gdca_select_confident_dev(gdca_ctx *ctx, const int32_t *match_dev, const double *gap_dev, int32_t KA, int32_t n_take, int32_t *sel_dev,
                                       int32_t *n_sel)
 {
-    if (!ctx) return GDCA_EINVAL;
-    if (!match_dev || !gap_dev || !sel_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (KA < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    CHK(check_select_confident(ctx, match_dev, gap_dev, KA, sel_dev));
     CHK(not_pending(ctx));
     HIPCHK(hipSetDevice(ctx->device));
     CHK(select_stage(ctx, match_dev, gap_dev, KA, n_take, sel_dev));
@@ -3106,19 +3224,20 @@ gdca_status gdca_select_confident_dev(gdca_ctx *ctx, const int32_t *match_dev, c
 }
 
 // the argument checks of the two concatenation entry points (nothing has run when one fails)
-static gdca_status validate_concat(gdca_ctx *ctx, int KA, int KB, int N, int split, int n_sel, long long col0)
+static gdca_status validate_concat(gdca_ctx *ctx, const void *XA, int KA, const void *XB, int KB, int N, int split, const void *selA,
+                                   const void *selB, int n_sel, const void *Z, long long col0)
 {
     if (!ctx) return GDCA_EINVAL;
     if (N < 2 || split < 1 || split > N - 1) return fail(ctx, GDCA_EINVAL, "invalid split (must be between 1 and N - 1)%s%s", "", "");
     if (KA < 1 || KB < 1 || n_sel < 0 || col0 < 0 || col0 + n_sel > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (!XA || !XB || !Z || (n_sel > 0 && (!selA || !selB))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     return GDCA_OK;
 }
 
 gdca_status gdca_concat_pairs_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_t KA, const int8_t *XB_dev, int32_t KB, int32_t N, int32_t split,
                                   const int32_t *selA_dev, const int32_t *selB_dev, int32_t n_sel, int8_t *Z_dev, int32_t col0)
 {
-    CHK(validate_concat(ctx, KA, KB, N, split, n_sel, col0));
-    if (!XA_dev || !XB_dev || !Z_dev || (n_sel > 0 && (!selA_dev || !selB_dev))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(validate_concat(ctx, XA_dev, KA, XB_dev, KB, N, split, selA_dev, selB_dev, n_sel, Z_dev, col0));
     CHK(begin(ctx));
     gdca_launch_ipa_concat(ctx->stream, XA_dev, KA, XB_dev, KB, N, split, selA_dev, selB_dev, nullptr, n_sel, Z_dev, (size_t)col0,
                            (gdca_dev_scalars *)ctx->sc.p);
@@ -3136,7 +3255,8 @@ struct ipa_plan {
 
 static gdca_status ipa_check(gdca_ctx *ctx, int32_t KA, int32_t KB, const void *offA_, const void *offB_, int32_t S, int32_t N, int32_t q,
                              int32_t split, int32_t what, const gdca_params *p, int32_t Mfix, const int32_t *seedA, const int32_t *seedB,
-                             int32_t n_seed, int32_t n_inc, int32_t max_rounds, ipa_plan *plan)
+                             int32_t n_seed, int32_t n_inc, int32_t max_rounds, const void *XA, const void *XB, const void *Zfix, const void *match,
+                             ipa_plan *plan)
 {
     if (!ctx) return GDCA_EINVAL;
     if (Mfix < 0 || n_seed < 0 || (long long)Mfix + n_seed < 1)
@@ -3173,6 +3293,7 @@ static gdca_status ipa_check(gdca_ctx *ctx, int32_t KA, int32_t KB, const void *
         plan->seedA.push_back(ab.first);
         plan->seedB.push_back(ab.second);
     }
+    if (!XA || !XB || !match || (Mfix > 0 && !Zfix)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
     return GDCA_OK;
 }
 
@@ -3183,8 +3304,8 @@ gdca_status gdca_run_partner_ipa_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_
                                      double *gap_trace_dev, double *rounds_out, int32_t *rounds_run, gdca_stats *st)
 {
     ipa_plan plan;
-    CHK(ipa_check(ctx, KA, KB, offA, offB, S, N, q, split, what, p, Mfix, seedA, seedB, n_seed, n_inc, max_rounds, &plan));
-    if (!XA_dev || !XB_dev || !match_dev || (Mfix > 0 && !Zfix_dev)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(ipa_check(ctx, KA, KB, offA, offB, S, N, q, split, what, p, Mfix, seedA, seedB, n_seed, n_inc, max_rounds, XA_dev, XB_dev, Zfix_dev, match_dev,
+                  &plan));
     CHK(not_pending(ctx));
     if (rounds_run) *rounds_run = 0;
     hipStream_t s = ctx->stream;
@@ -3300,11 +3421,26 @@ static gdca_status validate_mutation(gdca_ctx *ctx, int N, int q, long long K, i
     return GDCA_OK;
 }
 
+static gdca_status check_mutation_scan(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *X, int K, int what, const void *D)
+{
+    CHK(validate_mutation(ctx, N, q, K, what));
+    if (!mJ || !Pi || !X || !D) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
+static gdca_status check_run_mutation_scan(gdca_ctx *ctx, const void *Z, int N, int M, int q, const void *p, const void *X, int K, int what,
+                                           const void *D)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_mutation(ctx, N, q, X ? K : M, what));
+    if (!Z || !D || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
 gdca_status gdca_mutation_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
                                    int32_t K, int32_t what, double *D_dev)
 {
-    CHK(validate_mutation(ctx, N, q, K, what));
-    if (!mJ_dev || !Pi_dev || !X_dev || !D_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_mutation_scan(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, what, D_dev));
     CHK(begin(ctx));
     CHK(mutation_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, what, D_dev));
     return sequences_checked(ctx);
@@ -3313,9 +3449,7 @@ gdca_status gdca_mutation_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const do
 gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                        const int8_t *X_dev, int32_t K, int32_t what, double *D_dev, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_mutation(ctx, N, q, X_dev ? K : M, what));
-    if (!Z_dev || !D_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_run_mutation_scan(ctx, Z_dev, N, M, q, p, X_dev, K, what, D_dev));
     return run_target(ctx, Z_dev, N, M, q, p, mutation_target(Z_dev, M, X_dev, K, what, D_dev), st);
 }
 
@@ -3330,12 +3464,32 @@ static gdca_status validate_double(gdca_ctx *ctx, int N, int q, long long K)
     return GDCA_OK;
 }
 
+// the scan's and the listed form's: `a` and `b` are the model, mJ and Pi (M: 1), or -- a fused form -- the alignment of M sequences and
+// its parameters
+static gdca_status check_double_scan(gdca_ctx *ctx, const void *a, const void *b, int N, int M, int q, const void *X, int K, const void *Emin,
+                                     const void *code, const void *epi)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_double(ctx, N, q, K));
+    if (!a || !b || !X) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Emin && !code && !epi) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    return GDCA_OK;
+}
+
+static gdca_status check_double_list(gdca_ctx *ctx, const void *a, const void *b, int N, int M, int q, const void *X, int K, const void *muts, int L,
+                                     const void *out)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_double(ctx, N, q, K));
+    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
+    if (!a || !b || !X || !muts || !out) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    return GDCA_OK;
+}
+
 gdca_status gdca_double_mutant_scan_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
                                         int32_t K, double *Emin_dev, int32_t *code_dev, double *epi_dev)
 {
-    CHK(validate_double(ctx, N, q, K));
-    if (!mJ_dev || !Pi_dev || !X_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (!Emin_dev && !code_dev && !epi_dev) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    CHK(check_double_scan(ctx, mJ_dev, Pi_dev, N, 1, q, X_dev, K, Emin_dev, code_dev, epi_dev));
     CHK(begin(ctx));
     CHK(double_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, Emin_dev, code_dev, epi_dev, nullptr, 0, nullptr));
     return sequences_checked(ctx);
@@ -3344,9 +3498,7 @@ gdca_status gdca_double_mutant_scan_dev(gdca_ctx *ctx, const double *mJ_dev, con
 gdca_status gdca_double_mutants_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
                                     int32_t K, const void *muts_dev, int32_t L, double *out_dev)
 {
-    CHK(validate_double(ctx, N, q, K));
-    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
-    if (!mJ_dev || !Pi_dev || !X_dev || !muts_dev || !out_dev) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_double_list(ctx, mJ_dev, Pi_dev, N, 1, q, X_dev, K, muts_dev, L, out_dev));
     CHK(begin(ctx));
     CHK(double_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, nullptr, nullptr, nullptr, (const int32_t *)muts_dev, L, out_dev));
     return sequences_checked(ctx);
@@ -3355,20 +3507,14 @@ gdca_status gdca_double_mutants_dev(gdca_ctx *ctx, const double *mJ_dev, const d
 gdca_status gdca_run_double_mutant_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                             const int8_t *X_dev, int32_t K, double *Emin_dev, int32_t *code_dev, double *epi_dev, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_double(ctx, N, q, K));
-    if (!Z_dev || !X_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (!Emin_dev && !code_dev && !epi_dev) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    CHK(check_double_scan(ctx, Z_dev, p, N, M, q, X_dev, K, Emin_dev, code_dev, epi_dev));
     return run_target(ctx, Z_dev, N, M, q, p, double_scan_target(X_dev, K, Emin_dev, code_dev, epi_dev), st);
 }
 
 gdca_status gdca_run_double_mutants_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                         const int8_t *X_dev, int32_t K, const void *muts_dev, int32_t L, double *out_dev, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_double(ctx, N, q, K));
-    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
-    if (!Z_dev || !X_dev || !muts_dev || !out_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_double_list(ctx, Z_dev, p, N, M, q, X_dev, K, muts_dev, L, out_dev));
     return run_target(ctx, Z_dev, N, M, q, p, double_list_target(X_dev, K, (const int32_t *)muts_dev, L, out_dev), st);
 }
 
@@ -3385,37 +3531,26 @@ gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 // ---- operator level, host pointers: copy in, run the `_dev` form, copy out --------------------------------------
 // (what a statement-by-statement caller with ordinary Julia arrays binds; every n x n argument crosses PCIe, so a
 // caller who chains several operators should keep the matrices in gdca_dbuf buffers and use the `_dev` forms)
-
-static gdca_status to_dev(gdca_ctx *ctx, gdca_buf &b, const void *host, size_t bytes)
-{
-    CHK(ensure(ctx, b, bytes));
-    HIPCHK(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return GDCA_OK;
-}
-
-static gdca_status to_host(gdca_ctx *ctx, void *host, const gdca_buf &b, size_t bytes)
-{
-    HIPCHK(hipMemcpyAsync(host, b.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return GDCA_OK;
-}
+// Each is: the checks of its `_dev` form (nothing is staged for a bad argument), a host_stage, one line per array, the `_dev` form, finish.
 
 gdca_status gdca_pair_identity_sum(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, uint64_t *out)
 {
     CHK(validate(ctx, N, M, 2));
     if (!Z || !out) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(to_dev(ctx, ctx->scratch[0], Z, (size_t)N * M));
-    return gdca_pair_identity_sum_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, out);
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    CHK(sg.status());
+    return gdca_pair_identity_sum_dev(ctx, Z_dev, N, M, out);
 }
 
 gdca_status gdca_compute_theta(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, double *theta)
 {
     CHK(validate(ctx, N, M, 2));
     if (!Z || !theta) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(to_dev(ctx, ctx->scratch[0], Z, (size_t)N * M));
-    return gdca_compute_theta_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, theta);
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    CHK(sg.status());
+    return gdca_compute_theta_dev(ctx, Z_dev, N, M, theta);
 }
 
 gdca_status gdca_neighbour_counts(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, int32_t thresh,
@@ -3423,11 +3558,11 @@ gdca_status gdca_neighbour_counts(gdca_ctx *ctx, const int8_t *Z, int32_t N, int
 {
     CHK(validate(ctx, N, M, 2));
     if (!Z || !n_out || thresh < 0) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(to_dev(ctx, ctx->scratch[0], Z, (size_t)N * M));
-    CHK(ensure(ctx, ctx->scratch[2], (size_t)M * sizeof(int32_t)));
-    CHK(gdca_neighbour_counts_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, thresh, (int32_t *)ctx->scratch[2].p));
-    return to_host(ctx, n_out, ctx->scratch[2], (size_t)M * sizeof(int32_t));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    int32_t *n_dev = sg.out(n_out, (size_t)M * sizeof(int32_t));
+    CHK(sg.status());
+    return sg.finish(gdca_neighbour_counts_dev(ctx, Z_dev, N, M, thresh, n_dev));
 }
 
 gdca_status gdca_compute_weights(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, double theta, double *W,
@@ -3435,12 +3570,11 @@ gdca_status gdca_compute_weights(gdca_ctx *ctx, const int8_t *Z, int32_t N, int3
 {
     CHK(validate(ctx, N, M, 2));
     if (!Z || !W || !Meff || !(theta <= 1.0)) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(to_dev(ctx, ctx->scratch[0], Z, (size_t)N * M));
-    CHK(ensure(ctx, ctx->scratch[2], (size_t)M * sizeof(double)));
-    CHK(gdca_compute_weights_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, theta, (double *)ctx->scratch[2].p, Meff,
-                                 theta_used, thresh));
-    return to_host(ctx, W, ctx->scratch[2], (size_t)M * sizeof(double));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    double *W_dev = sg.out(W, (size_t)M * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_compute_weights_dev(ctx, Z_dev, N, M, theta, W_dev, Meff, theta_used, thresh));
 }
 
 gdca_status gdca_frequencies(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, int32_t q, const double *W,
@@ -3448,16 +3582,14 @@ gdca_status gdca_frequencies(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t 
 {
     CHK(validate(ctx, N, M, q));
     if (!Z || !W || !Pi || !Pij || !(Meff > 0.0)) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)N * (q - 1);
-    CHK(to_dev(ctx, ctx->scratch[0], Z, (size_t)N * M));
-    CHK(to_dev(ctx, ctx->W, W, (size_t)M * sizeof(double)));
-    CHK(ensure(ctx, ctx->scratch[1], n * n * sizeof(double)));
-    CHK(ensure(ctx, ctx->scratch[2], n * sizeof(double)));
-    CHK(gdca_frequencies_dev(ctx, (const int8_t *)ctx->scratch[0].p, N, M, q, (const double *)ctx->W.p, Meff,
-                             (double *)ctx->scratch[2].p, (double *)ctx->scratch[1].p));
-    CHK(to_host(ctx, Pi, ctx->scratch[2], n * sizeof(double)));
-    return to_host(ctx, Pij, ctx->scratch[1], n * n * sizeof(double));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    const double *W_dev = sg.in(W, (size_t)M * sizeof(double));
+    double *Pi_dev = sg.out(Pi, n * sizeof(double));
+    double *Pij_dev = sg.out(Pij, n * n * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_frequencies_dev(ctx, Z_dev, N, M, q, W_dev, Meff, Pi_dev, Pij_dev));
 }
 
 gdca_status gdca_add_pseudocount(gdca_ctx *ctx, const double *Pi_true, const double *Pij_true, int32_t N, int32_t q,
@@ -3465,289 +3597,218 @@ gdca_status gdca_add_pseudocount(gdca_ctx *ctx, const double *Pi_true, const dou
 {
     CHK(validate(ctx, N, 1, q));
     if (!Pi_true || !Pij_true || !Pi || !Pij || !(pc >= 0.0 && pc <= 1.0)) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)N * (q - 1);
-    CHK(to_dev(ctx, ctx->scratch[1], Pij_true, n * n * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[2], Pi_true, n * sizeof(double)));
+    host_stage sg(ctx);
     // elementwise: in place on the device
-    CHK(gdca_add_pseudocount_dev(ctx, (const double *)ctx->scratch[2].p, (const double *)ctx->scratch[1].p, N, q, pc,
-                                 (double *)ctx->scratch[2].p, (double *)ctx->scratch[1].p));
-    CHK(to_host(ctx, Pi, ctx->scratch[2], n * sizeof(double)));
-    return to_host(ctx, Pij, ctx->scratch[1], n * n * sizeof(double));
+    double *Pi_dev = sg.inout(Pi_true, Pi, n * sizeof(double));
+    double *Pij_dev = sg.inout(Pij_true, Pij, n * n * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_add_pseudocount_dev(ctx, Pi_dev, Pij_dev, N, q, pc, Pi_dev, Pij_dev));
 }
 
 gdca_status gdca_covariance(gdca_ctx *ctx, const double *Pi, const double *Pij, int32_t n, double *C)
 {
     if (!ctx || !Pi || !Pij || !C || n < 1 || n > GDCA_MAX_N) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n;
-    CHK(to_dev(ctx, ctx->scratch[1], Pij, nn * nn * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[2], Pi, nn * sizeof(double)));
-    CHK(gdca_covariance_dev(ctx, (const double *)ctx->scratch[2].p, (const double *)ctx->scratch[1].p, n,
-                            (double *)ctx->scratch[1].p));
-    return to_host(ctx, C, ctx->scratch[1], nn * nn * sizeof(double));
+    host_stage sg(ctx);
+    const double *Pi_dev = sg.in(Pi, nn * sizeof(double));
+    double *C_dev = sg.inout(Pij, C, nn * nn * sizeof(double));  // (C over Pij)
+    CHK(sg.status());
+    return sg.finish(gdca_covariance_dev(ctx, Pi_dev, C_dev, n, C_dev));
 }
 
 gdca_status gdca_spd_inverse(gdca_ctx *ctx, double *A, int32_t n, int32_t *info)
 {
     if (!ctx || !A || n < 1 || n > GDCA_MAX_N) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t nn = (size_t)n;
-    CHK(to_dev(ctx, ctx->scratch[1], A, nn * nn * sizeof(double)));
-    CHK(gdca_spd_inverse_dev(ctx, (double *)ctx->scratch[1].p, n, info));
-    return to_host(ctx, A, ctx->scratch[1], nn * nn * sizeof(double));
+    host_stage sg(ctx);
+    double *A_dev = sg.inout(A, A, (size_t)n * n * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_spd_inverse_dev(ctx, A_dev, n, info));
 }
 
 gdca_status gdca_spd_inverse_logdet(gdca_ctx *ctx, double *A, int32_t n, int32_t *info, double *logdet)
 {
     if (!ctx || !A || !logdet || n < 1 || n > GDCA_MAX_N) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t nn = (size_t)n;
-    CHK(to_dev(ctx, ctx->scratch[1], A, nn * nn * sizeof(double)));
-    CHK(gdca_spd_inverse_logdet_dev(ctx, (double *)ctx->scratch[1].p, n, info, logdet));
-    return to_host(ctx, A, ctx->scratch[1], nn * nn * sizeof(double));
+    host_stage sg(ctx);
+    double *A_dev = sg.inout(A, A, (size_t)n * n * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_spd_inverse_logdet_dev(ctx, A_dev, n, info, logdet));
 }
 
 gdca_status gdca_fn(gdca_ctx *ctx, const double *mJ, int32_t N, int32_t q, double *S)
 {
     CHK(validate(ctx, N, 1, q));
     if (!mJ || !S) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)N * (q - 1);
-    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
-    CHK(ensure(ctx, ctx->scratch[2], (size_t)N * N * sizeof(double)));
-    CHK(gdca_fn_dev(ctx, (const double *)ctx->scratch[1].p, N, q, (double *)ctx->scratch[2].p));
-    return to_host(ctx, S, ctx->scratch[2], (size_t)N * N * sizeof(double));
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    double *S_dev = sg.out(S, (size_t)N * N * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_fn_dev(ctx, mJ_dev, N, q, S_dev));
 }
 
 gdca_status gdca_di(gdca_ctx *ctx, const double *mJ, const double *C, int32_t N, int32_t q, double *S)
 {
     CHK(validate(ctx, N, 1, q));
     if (!mJ || !C || !S) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)N * (q - 1);
-    CHK(to_dev(ctx, ctx->scratch[1], mJ, n * n * sizeof(double)));
-    CHK(to_dev(ctx, ctx->scratch[4], C, n * n * sizeof(double)));
-    CHK(ensure(ctx, ctx->scratch[2], (size_t)N * N * sizeof(double)));
-    CHK(gdca_di_dev(ctx, (const double *)ctx->scratch[1].p, (const double *)ctx->scratch[4].p, N, q,
-                    (double *)ctx->scratch[2].p));
-    return to_host(ctx, S, ctx->scratch[2], (size_t)N * N * sizeof(double));
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *C_dev = sg.in(C, n * n * sizeof(double));
+    double *S_dev = sg.out(S, (size_t)N * N * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_di_dev(ctx, mJ_dev, C_dev, N, q, S_dev));
 }
 
 gdca_status gdca_apc(gdca_ctx *ctx, double *S, int32_t N)
 {
     if (!ctx || !S || N < 1) return GDCA_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
-    CHK(to_dev(ctx, ctx->scratch[2], S, (size_t)N * N * sizeof(double)));
-    CHK(gdca_apc_dev(ctx, (double *)ctx->scratch[2].p, N));
-    return to_host(ctx, S, ctx->scratch[2], (size_t)N * N * sizeof(double));
-}
-
-// The staging of the model read-outs' host-pointer forms: a host array into scratch slot `slot`, its device address returned; nullptr
-// for an absent optional one (host == nullptr), and where an upload has failed (*st then says why; later uploads do nothing)
-static const void *upload(gdca_ctx *ctx, int slot, const void *host, size_t bytes, gdca_status *st)
-{
-    if (!host || *st != GDCA_OK) return nullptr;
-    *st = to_dev(ctx, ctx->scratch[slot], host, bytes);
-    return *st == GDCA_OK ? ctx->scratch[slot].p : nullptr;
-}
-
-// ... and room for their result in scratch slot `slot` (nothing is done once *st holds an error)
-static double *staged_out(gdca_ctx *ctx, int slot, size_t bytes, gdca_status *st)
-{
-    if (*st == GDCA_OK) *st = ensure(ctx, ctx->scratch[slot], bytes);
-    return *st == GDCA_OK ? (double *)ctx->scratch[slot].p : nullptr;
+    host_stage sg(ctx);
+    double *S_dev = sg.inout(S, S, (size_t)N * N * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_apc_dev(ctx, S_dev, N));
 }
 
 gdca_status gdca_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K, double *E)
 {
-    CHK(validate(ctx, N, K, q));
-    if (!mJ || !Pi || !X || !E) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)N * (q - 1), ne = (size_t)K * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
-    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
-    double *E_dev = staged_out(ctx, 3, ne, &up);
-    CHK(up);
-    CHK(gdca_energies_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, E_dev));
-    return to_host(ctx, E, ctx->scratch[3], ne);
+    CHK(check_energies(ctx, mJ, Pi, N, q, X, K, E));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *X_dev = sg.in(X, (size_t)N * K);
+    double *E_dev = sg.out(E, (size_t)K * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_energies_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, E_dev));
 }
 
 gdca_status gdca_run_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, const int8_t *X_host,
                               int32_t K, double *E_host, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    if (!Z_host || !E_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (X_host && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ne = (size_t)(X_host ? K : M) * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
-    double *E_dev = staged_out(ctx, 5, ne, &up);
-    CHK(up);
-    CHK(gdca_run_energies_dev(ctx, Z_dev, N, M, q, p, X_dev, K, E_dev, st));
-    return to_host(ctx, E_host, ctx->scratch[5], ne);
+    CHK(check_run_energies(ctx, Z_host, N, M, q, p, X_host, K, E_host));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    double *E_dev = sg.out(E_host, (size_t)(X_host ? K : M) * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_energies_dev(ctx, Z_dev, N, M, q, p, X_dev, K, E_dev, st));
 }
 
 gdca_status gdca_run_loglik(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, const int8_t *X_host,
                             int32_t K, double *L_host, double *logdet, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    if (!Z_host || !L_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (X_host && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ne = (size_t)(X_host ? K : M) * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
-    double *L_dev = staged_out(ctx, 5, ne, &up);
-    CHK(up);
-    CHK(gdca_run_loglik_dev(ctx, Z_dev, N, M, q, p, X_dev, K, L_dev, logdet, st));
-    return to_host(ctx, L_host, ctx->scratch[5], ne);
+    CHK(check_run_energies(ctx, Z_host, N, M, q, p, X_host, K, L_host));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    double *L_dev = sg.out(L_host, (size_t)(X_host ? K : M) * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_loglik_dev(ctx, Z_dev, N, M, q, p, X_dev, K, L_dev, logdet, st));
 }
 
 gdca_status gdca_pair_energies(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split, const int8_t *XA,
                                int32_t KA, const int8_t *XB, int32_t KB, int32_t what, double *E)
 {
-    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
-    if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)N * (q - 1), ne = (size_t)KA * (size_t)KB * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
-    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 0, XA, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 3, XB, (size_t)(N - split) * KB, &up);
-    double *E_dev = staged_out(ctx, 5, ne, &up);
-    CHK(up);
-    CHK(gdca_pair_energies_dev(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, what, E_dev));
-    return to_host(ctx, E, ctx->scratch[5], ne);
+    CHK(check_pair_energies(ctx, mJ, Pi, N, q, split, XA, KA, XB, KB, what, E));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *XA_dev = sg.in(XA, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB, (size_t)(N - split) * KB);
+    double *E_dev = sg.out(E, (size_t)KA * (size_t)KB * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_pair_energies_dev(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, what, E_dev));
 }
 
 gdca_status gdca_run_pair_energies(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
                                    const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, int32_t what, double *E_host,
                                    gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_pair(ctx, N, q, split, XA_host ? KA : M, XB_host ? KB : M, what));
-    if (!Z_host || !E_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ne = (size_t)(XA_host ? KA : M) * (size_t)(XB_host ? KB : M) * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
-    double *E_dev = staged_out(ctx, 5, ne, &up);
-    CHK(up);
-    CHK(gdca_run_pair_energies_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, what, E_dev, st));
-    return to_host(ctx, E_host, ctx->scratch[5], ne);
-}
-
-// the packed length of a host form's species, its offsets held against the counts (EINVAL with nothing uploaded)
-static gdca_status host_blocks_length(gdca_ctx *ctx, const void *offA, const void *offB, int S, long long KA, long long KB, long long *total)
-{
-    if (!offA || !offB) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    *total = blocks_length((const int32_t *)offA, (const int32_t *)offB, S, nullptr);
-    if (*total < 0 || ((const int32_t *)offA)[S] != KA || ((const int32_t *)offB)[S] != KB)
-        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
-    return GDCA_OK;
+    CHK(check_run_pair(ctx, Z_host, N, M, q, p, split, XA_host, KA, XB_host, KB, what, E_host));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *XA_dev = sg.in(XA_host, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB_host, (size_t)(N - split) * KB);
+    double *E_dev = sg.out(E_host, (size_t)(XA_host ? KA : M) * (size_t)(XB_host ? KB : M) * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_pair_energies_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, what, E_dev, st));
 }
 
 gdca_status gdca_pair_energies_blocked(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, int32_t split, const int8_t *XA,
                                        int32_t KA, const int8_t *XB, int32_t KB, const void *offA, const void *offB, int32_t S, int32_t what,
                                        double *E)
 {
-    CHK(validate_pair(ctx, N, q, split, KA, KB, what));
-    if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_pair_energies(ctx, mJ, Pi, N, q, split, XA, KA, XB, KB, what, E));
     long long total = 0;
-    CHK(host_blocks_length(ctx, offA, offB, S, KA, KB, &total));
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)N * (q - 1), ne = (size_t)total * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
-    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 0, XA, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 3, XB, (size_t)(N - split) * KB, &up);
-    double *E_dev = staged_out(ctx, 5, ne, &up);
-    CHK(up);
-    CHK(gdca_pair_energies_blocked_dev(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, offA, offB, S, what, E_dev));
-    return ne ? to_host(ctx, E, ctx->scratch[5], ne) : GDCA_OK;
+    CHK(check_blocks(ctx, offA, offB, S, KA, KB, &total));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *XA_dev = sg.in(XA, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB, (size_t)(N - split) * KB);
+    double *E_dev = sg.out(E, (size_t)total * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_pair_energies_blocked_dev(ctx, mJ_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, offA, offB, S, what, E_dev));
 }
 
 gdca_status gdca_assign_blocks(gdca_ctx *ctx, const double *E, const void *offA, const void *offB, int32_t S, int32_t *match, double *gap)
 {
-    if (!ctx) return GDCA_EINVAL;
-    if (!E || !match || !offA || !offB) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (S < 1) return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1)%s%s", "", "");
+    CHK(check_assign_blocks(ctx, E, offA, offB, S, match));
     const long long KA = ((const int32_t *)offA)[S], KB = ((const int32_t *)offB)[S];
     long long total = 0;
-    CHK(host_blocks_length(ctx, offA, offB, S, KA, KB, &total));
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t nm = (size_t)KA * sizeof(int32_t), ng = (size_t)KA * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const double *E_dev = (const double *)upload(ctx, 5, E, (size_t)total * sizeof(double), &up);
-    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
-    double *gap_dev = gap ? staged_out(ctx, 7, ng, &up) : nullptr;
-    CHK(up);
-    CHK(gdca_assign_blocks_dev(ctx, E_dev, offA, offB, S, match_dev, gap_dev));
-    if (gap && ng) CHK(to_host(ctx, gap, ctx->scratch[7], ng));
-    return nm ? to_host(ctx, match, ctx->scratch[6], nm) : GDCA_OK;
+    CHK(check_blocks(ctx, offA, offB, S, KA, KB, &total));
+    host_stage sg(ctx);
+    const double *E_dev = sg.in(E, (size_t)total * sizeof(double));
+    int32_t *match_dev = sg.out(match, (size_t)KA * sizeof(int32_t));
+    double *gap_dev = sg.out(gap, (size_t)KA * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_assign_blocks_dev(ctx, E_dev, offA, offB, S, match_dev, gap_dev));
 }
 
 gdca_status gdca_run_partner_match(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
                                    const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA, const void *offB,
                                    int32_t S, int32_t what, double *E_host, int32_t *match_host, double *gap_host, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
     const int ka = XA_host ? KA : M, kb = XB_host ? KB : M;
-    CHK(validate_pair(ctx, N, q, split, ka, kb, what));
-    if (!Z_host || !match_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_run_partner(ctx, Z_host, N, M, q, p, split, ka, kb, offA, offB, what, match_host));
     long long total = 0;
-    CHK(host_blocks_length(ctx, offA, offB, S, ka, kb, &total));
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ne = (size_t)total * sizeof(double), nm = (size_t)ka * sizeof(int32_t), ng = (size_t)ka * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
-    double *E_dev = E_host ? staged_out(ctx, 5, ne, &up) : nullptr;
-    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
-    double *gap_dev = gap_host ? staged_out(ctx, 7, ng, &up) : nullptr;
-    CHK(up);
-    CHK(gdca_run_partner_match_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, offA, offB, S, what, E_dev, match_dev, gap_dev, st));
-    if (E_host && ne) CHK(to_host(ctx, E_host, ctx->scratch[5], ne));
-    if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
-    return to_host(ctx, match_host, ctx->scratch[6], nm);
+    CHK(check_blocks(ctx, offA, offB, S, ka, kb, &total));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *XA_dev = sg.in(XA_host, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB_host, (size_t)(N - split) * KB);
+    double *E_dev = sg.out(E_host, (size_t)total * sizeof(double));
+    int32_t *match_dev = sg.out(match_host, (size_t)ka * sizeof(int32_t));
+    double *gap_dev = sg.out(gap_host, (size_t)ka * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_partner_match_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, offA, offB, S, what, E_dev, match_dev, gap_dev,
+                                                st));
 }
 
-// pair log-odds with host pointers: upload, the _dev form, download (three matrices cross PCIe in the operator forms)
+// pair log-odds with host pointers (three matrices cross PCIe in the operator forms)
 static gdca_status logodds_operator_host(gdca_ctx *ctx, const double *mJ, const double *mJA, const double *mJB, const double *Pi, int32_t N, int32_t q,
                                          int32_t split, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, const void *offA,
                                          const void *offB, int32_t S, bool blocked, double I, double *L)
 {
-    CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
-    if (!mJ || !mJA || !mJB || !Pi || !XA || !XB || !L) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_pair_logodds(ctx, mJ, mJA, mJB, Pi, N, q, split, XA, KA, XB, KB, L));
     long long total = (long long)KA * KB;
-    if (blocked) CHK(host_blocks_length(ctx, offA, offB, S, KA, KB, &total));
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t s = (size_t)(q - 1), n = (size_t)N * s, nA = (size_t)split * s, nB = n - nA, ne = (size_t)total * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
-    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 0, XA, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 3, XB, (size_t)(N - split) * KB, &up);
-    const double *mJA_dev = (const double *)upload(ctx, 4, mJA, nA * nA * sizeof(double), &up);
-    const double *mJB_dev = (const double *)upload(ctx, 6, mJB, nB * nB * sizeof(double), &up);
-    double *L_dev = staged_out(ctx, 5, ne, &up);
-    CHK(up);
+    if (blocked) CHK(check_blocks(ctx, offA, offB, S, KA, KB, &total));
+    const size_t s = (size_t)(q - 1), n = (size_t)N * s, nA = (size_t)split * s, nB = n - nA;
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *XA_dev = sg.in(XA, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB, (size_t)(N - split) * KB);
+    const double *mJA_dev = sg.in(mJA, nA * nA * sizeof(double));
+    const double *mJB_dev = sg.in(mJB, nB * nB * sizeof(double));
+    double *L_dev = sg.out(L, (size_t)total * sizeof(double));
+    CHK(sg.status());
     if (blocked)
-        CHK(gdca_pair_logodds_blocked_dev(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, offA, offB, S, I, L_dev));
-    else
-        CHK(gdca_pair_logodds_dev(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, I, L_dev));
-    return ne ? to_host(ctx, L, ctx->scratch[5], ne) : GDCA_OK;
+        return sg.finish(
+            gdca_pair_logodds_blocked_dev(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, offA, offB, S, I, L_dev));
+    return sg.finish(gdca_pair_logodds_dev(ctx, mJ_dev, mJA_dev, mJB_dev, Pi_dev, N, q, split, XA_dev, KA, XB_dev, KB, I, L_dev));
 }
 
 gdca_status gdca_pair_logodds(gdca_ctx *ctx, const double *mJ, const double *mJA, const double *mJB, const double *Pi, int32_t N, int32_t q,
@@ -3767,86 +3828,64 @@ gdca_status gdca_run_pair_logodds(gdca_ctx *ctx, const int8_t *Z_host, int32_t N
                                   const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, double *L_host, double *EmA_host,
                                   double *EmB_host, double *info, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    const int ka = XA_host ? KA : M, kb = XB_host ? KB : M;
-    CHK(validate_pair(ctx, N, q, split, ka, kb, GDCA_PAIR_ENERGY));
-    if (!Z_host || !L_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ne = (size_t)ka * (size_t)kb * sizeof(double), na = (size_t)ka * sizeof(double), nb = (size_t)kb * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
-    double *L_dev = staged_out(ctx, 5, ne, &up);
-    double *EmA_dev = EmA_host ? staged_out(ctx, 8, na, &up) : nullptr;
-    double *EmB_dev = EmB_host ? staged_out(ctx, 9, nb, &up) : nullptr;
-    CHK(up);
-    CHK(gdca_run_pair_logodds_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, L_dev, EmA_dev, EmB_dev, info, st));
-    if (EmA_host) CHK(to_host(ctx, EmA_host, ctx->scratch[8], na));
-    if (EmB_host) CHK(to_host(ctx, EmB_host, ctx->scratch[9], nb));
-    return to_host(ctx, L_host, ctx->scratch[5], ne);
+    CHK(check_run_pair(ctx, Z_host, N, M, q, p, split, XA_host, KA, XB_host, KB, GDCA_PAIR_ENERGY, L_host));
+    const size_t ka = (size_t)(XA_host ? KA : M), kb = (size_t)(XB_host ? KB : M);
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *XA_dev = sg.in(XA_host, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB_host, (size_t)(N - split) * KB);
+    double *L_dev = sg.out(L_host, ka * kb * sizeof(double));
+    double *EmA_dev = sg.out(EmA_host, ka * sizeof(double));
+    double *EmB_dev = sg.out(EmB_host, kb * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_pair_logodds_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, L_dev, EmA_dev, EmB_dev, info, st));
 }
 
 gdca_status gdca_run_partner_logodds(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t split,
                                      const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA, const void *offB,
                                      int32_t S, double *L_host, int32_t *match_host, double *gap_host, double *info, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
     const int ka = XA_host ? KA : M, kb = XB_host ? KB : M;
-    CHK(validate_pair(ctx, N, q, split, ka, kb, GDCA_PAIR_ENERGY));
-    if (!Z_host || !match_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(check_run_partner(ctx, Z_host, N, M, q, p, split, ka, kb, offA, offB, GDCA_PAIR_ENERGY, match_host));
     long long total = 0;
-    CHK(host_blocks_length(ctx, offA, offB, S, ka, kb, &total));
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ne = (size_t)total * sizeof(double), nm = (size_t)ka * sizeof(int32_t), ng = (size_t)ka * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
-    double *L_dev = L_host ? staged_out(ctx, 5, ne, &up) : nullptr;
-    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
-    double *gap_dev = gap_host ? staged_out(ctx, 7, ng, &up) : nullptr;
-    CHK(up);
-    CHK(gdca_run_partner_logodds_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, offA, offB, S, L_dev, match_dev, gap_dev, info, st));
-    if (L_host && ne) CHK(to_host(ctx, L_host, ctx->scratch[5], ne));
-    if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
-    return to_host(ctx, match_host, ctx->scratch[6], nm);
+    CHK(check_blocks(ctx, offA, offB, S, ka, kb, &total));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *XA_dev = sg.in(XA_host, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB_host, (size_t)(N - split) * KB);
+    double *L_dev = sg.out(L_host, (size_t)total * sizeof(double));
+    int32_t *match_dev = sg.out(match_host, (size_t)ka * sizeof(int32_t));
+    double *gap_dev = sg.out(gap_host, (size_t)ka * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_partner_logodds_dev(ctx, Z_dev, N, M, q, p, split, XA_dev, KA, XB_dev, KB, offA, offB, S, L_dev, match_dev, gap_dev, info,
+                                                  st));
 }
 
 gdca_status gdca_select_confident(gdca_ctx *ctx, const int32_t *match, const double *gap, int32_t KA, int32_t n_take, int32_t *sel, int32_t *n_sel)
 {
-    if (!ctx) return GDCA_EINVAL;
-    if (!match || !gap || !sel) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (KA < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ni = (size_t)KA * sizeof(int32_t);
-    gdca_status up = GDCA_OK;
-    const int32_t *match_dev = (const int32_t *)upload(ctx, 6, match, ni, &up);
-    const double *gap_dev = (const double *)upload(ctx, 7, gap, (size_t)KA * sizeof(double), &up);
-    int32_t *sel_dev = (int32_t *)staged_out(ctx, 8, ni, &up);
-    CHK(up);
-    CHK(gdca_select_confident_dev(ctx, match_dev, gap_dev, KA, n_take, sel_dev, n_sel));
-    return to_host(ctx, sel, ctx->scratch[8], ni);
+    CHK(check_select_confident(ctx, match, gap, KA, sel));
+    host_stage sg(ctx);
+    const int32_t *match_dev = sg.in(match, (size_t)KA * sizeof(int32_t));
+    const double *gap_dev = sg.in(gap, (size_t)KA * sizeof(double));
+    int32_t *sel_dev = sg.out(sel, (size_t)KA * sizeof(int32_t));
+    CHK(sg.status());
+    return sg.finish(gdca_select_confident_dev(ctx, match_dev, gap_dev, KA, n_take, sel_dev, n_sel));
 }
 
 // (Z is the caller's whole alignment: only the requested columns are staged on the device and written back, and none where an index is bad)
 gdca_status gdca_concat_pairs(gdca_ctx *ctx, const int8_t *XA, int32_t KA, const int8_t *XB, int32_t KB, int32_t N, int32_t split,
                               const int32_t *selA, const int32_t *selB, int32_t n_sel, int8_t *Z, int32_t col0)
 {
-    CHK(validate_concat(ctx, KA, KB, N, split, n_sel, col0));
-    if (!XA || !XB || !Z || (n_sel > 0 && (!selA || !selB))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    CHK(validate_concat(ctx, XA, KA, XB, KB, N, split, selA, selB, n_sel, Z, col0));
     if (n_sel == 0) return GDCA_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t ni = (size_t)n_sel * sizeof(int32_t), nz = (size_t)N * n_sel;
-    gdca_status up = GDCA_OK;
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB, (size_t)(N - split) * KB, &up);
-    const int32_t *selA_dev = (const int32_t *)upload(ctx, 6, selA, ni, &up);
-    const int32_t *selB_dev = (const int32_t *)upload(ctx, 8, selB, ni, &up);
-    int8_t *Z_dev = (int8_t *)staged_out(ctx, 0, nz, &up);
-    CHK(up);
-    CHK(gdca_concat_pairs_dev(ctx, XA_dev, KA, XB_dev, KB, N, split, selA_dev, selB_dev, n_sel, Z_dev, 0));
-    return to_host(ctx, Z + (size_t)col0 * N, ctx->scratch[0], nz);
+    host_stage sg(ctx);
+    const int8_t *XA_dev = sg.in(XA, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB, (size_t)(N - split) * KB);
+    const int32_t *selA_dev = sg.in(selA, (size_t)n_sel * sizeof(int32_t));
+    const int32_t *selB_dev = sg.in(selB, (size_t)n_sel * sizeof(int32_t));
+    int8_t *Z_dev = sg.out(Z + (size_t)col0 * N, (size_t)N * n_sel);
+    CHK(sg.status());
+    return sg.finish(gdca_concat_pairs_dev(ctx, XA_dev, KA, XB_dev, KB, N, split, selA_dev, selB_dev, n_sel, Z_dev, 0));
 }
 
 gdca_status gdca_run_partner_ipa(gdca_ctx *ctx, const int8_t *XA_host, int32_t KA, const int8_t *XB_host, int32_t KB, const void *offA,
@@ -3856,30 +3895,31 @@ gdca_status gdca_run_partner_ipa(gdca_ctx *ctx, const int8_t *XA_host, int32_t K
                                  double *rounds_out, int32_t *rounds_run, gdca_stats *st)
 {
     {
-        ipa_plan plan;  // (the same checks before anything is uploaded: the sizes below are the caller's)
-        CHK(ipa_check(ctx, KA, KB, offA, offB, S, N, q, split, what, p, Mfix, seedA, seedB, n_seed, n_inc, max_rounds, &plan));
+        ipa_plan plan;  // (the same checks before anything is staged: the sizes below are the caller's)
+        CHK(ipa_check(ctx, KA, KB, offA, offB, S, N, q, split, what, p, Mfix, seedA, seedB, n_seed, n_inc, max_rounds, XA_host, XB_host, Zfix_host,
+                      match_host, &plan));
     }
-    if (!XA_host || !XB_host || !match_host || (Mfix > 0 && !Zfix_host)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t nm = (size_t)KA * sizeof(int32_t), ng = (size_t)KA * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Zfix_dev = Mfix > 0 ? (const int8_t *)upload(ctx, 0, Zfix_host, (size_t)N * Mfix, &up) : nullptr;
-    const int8_t *XA_dev = (const int8_t *)upload(ctx, 3, XA_host, (size_t)split * KA, &up);
-    const int8_t *XB_dev = (const int8_t *)upload(ctx, 4, XB_host, (size_t)(N - split) * KB, &up);
-    int32_t *match_dev = (int32_t *)staged_out(ctx, 6, nm, &up);
-    double *gap_dev = staged_out(ctx, 7, ng, &up);
-    int32_t *mt_dev = match_trace_host ? (int32_t *)staged_out(ctx, 8, nm * max_rounds, &up) : nullptr;
-    double *gt_dev = gap_trace_host ? staged_out(ctx, 9, ng * max_rounds, &up) : nullptr;
-    CHK(up);
+    host_stage sg(ctx);
+    const int8_t *Zfix_dev = Mfix > 0 ? sg.in(Zfix_host, (size_t)N * Mfix) : nullptr;
+    const int8_t *XA_dev = sg.in(XA_host, (size_t)split * KA);
+    const int8_t *XB_dev = sg.in(XB_host, (size_t)(N - split) * KB);
+    // (device-only room: what comes back is the explicit fetches below)
+    int32_t *match_dev = (int32_t *)sg.room(nm);
+    double *gap_dev = (double *)sg.room(ng);
+    int32_t *mt_dev = match_trace_host ? (int32_t *)sg.room(nm * max_rounds) : nullptr;
+    double *gt_dev = gap_trace_host ? (double *)sg.room(ng * max_rounds) : nullptr;
+    CHK(sg.status());
     int32_t done = 0;
     const gdca_status rs = gdca_run_partner_ipa_dev(ctx, XA_dev, KA, XB_dev, KB, offA, offB, S, N, q, split, what, p, Zfix_dev, Mfix, seedA, seedB,
                                                     n_seed, n_inc, max_rounds, match_dev, gap_dev, mt_dev, gt_dev, rounds_out, &done, st);
     if (rounds_run) *rounds_run = done;
     if (done > 0) {  // (the last completed round's, also where a later round's fit failed)
-        if (match_trace_host) CHK(to_host(ctx, match_trace_host, ctx->scratch[8], nm * done));
-        if (gap_trace_host) CHK(to_host(ctx, gap_trace_host, ctx->scratch[9], ng * done));
-        if (gap_host) CHK(to_host(ctx, gap_host, ctx->scratch[7], ng));
-        CHK(to_host(ctx, match_host, ctx->scratch[6], nm));
+        sg.fetch(match_trace_host, mt_dev, nm * done);
+        sg.fetch(gap_trace_host, gt_dev, ng * done);
+        sg.fetch(gap_host, gap_dev, ng);
+        sg.fetch(match_host, match_dev, nm);
+        CHK(sg.finish(GDCA_OK));
     }
     return rs;
 }
@@ -3887,134 +3927,86 @@ gdca_status gdca_run_partner_ipa(gdca_ctx *ctx, const int8_t *XA_host, int32_t K
 gdca_status gdca_mutation_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
                                int32_t what, double *D)
 {
-    CHK(validate_mutation(ctx, N, q, K, what));
-    if (!mJ || !Pi || !X || !D) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)N * (q - 1), nd = (size_t)q * (size_t)N * (size_t)K * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
-    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
-    double *D_dev = staged_out(ctx, 5, nd, &up);
-    CHK(up);
-    CHK(gdca_mutation_scan_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, what, D_dev));
-    return to_host(ctx, D, ctx->scratch[5], nd);
+    CHK(check_mutation_scan(ctx, mJ, Pi, N, q, X, K, what, D));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *X_dev = sg.in(X, (size_t)N * K);
+    double *D_dev = sg.out(D, (size_t)q * (size_t)N * (size_t)K * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_mutation_scan_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, what, D_dev));
 }
 
 gdca_status gdca_run_mutation_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                    const int8_t *X_host, int32_t K, int32_t what, double *D_host, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_mutation(ctx, N, q, X_host ? K : M, what));
-    if (!Z_host || !D_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t nd = (size_t)q * (size_t)N * (size_t)(X_host ? K : M) * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
-    double *D_dev = staged_out(ctx, 5, nd, &up);
-    CHK(up);
-    CHK(gdca_run_mutation_scan_dev(ctx, Z_dev, N, M, q, p, X_dev, K, what, D_dev, st));
-    return to_host(ctx, D_host, ctx->scratch[5], nd);
-}
-
-// the three maps of a double-mutant scan staged in scratch slots 5, 6, 7 (an absent one: nullptr) ...
-struct double_maps {
-    double *Emin;
-    int32_t *code;
-    double *epi;
-    size_t nd, ni;
-};
-static double_maps stage_double_maps(gdca_ctx *ctx, int N, int K, const double *Emin, const int32_t *code, const double *epi, gdca_status *up)
-{
-    double_maps m{};
-    m.nd = (size_t)N * (size_t)N * (size_t)K * sizeof(double);
-    m.ni = (size_t)N * (size_t)N * (size_t)K * sizeof(int32_t);
-    if (Emin) m.Emin = staged_out(ctx, 5, m.nd, up);
-    if (code) m.code = (int32_t *)staged_out(ctx, 6, m.ni, up);
-    if (epi) m.epi = staged_out(ctx, 7, m.nd, up);
-    return m;
-}
-// ... and brought back
-static gdca_status fetch_double_maps(gdca_ctx *ctx, const double_maps &m, double *Emin, int32_t *code, double *epi)
-{
-    if (Emin) CHK(to_host(ctx, Emin, ctx->scratch[5], m.nd));
-    if (code) CHK(to_host(ctx, code, ctx->scratch[6], m.ni));
-    if (epi) CHK(to_host(ctx, epi, ctx->scratch[7], m.nd));
-    return GDCA_OK;
+    CHK(check_run_mutation_scan(ctx, Z_host, N, M, q, p, X_host, K, what, D_host));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    double *D_dev = sg.out(D_host, (size_t)q * (size_t)N * (size_t)(X_host ? K : M) * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_mutation_scan_dev(ctx, Z_dev, N, M, q, p, X_dev, K, what, D_dev, st));
 }
 
 gdca_status gdca_double_mutant_scan(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
                                     double *Emin, int32_t *code, double *epi)
 {
-    CHK(validate_double(ctx, N, q, K));
-    if (!mJ || !Pi || !X) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (!Emin && !code && !epi) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)N * (q - 1);
-    gdca_status up = GDCA_OK;
-    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
-    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
-    const double_maps m = stage_double_maps(ctx, N, K, Emin, code, epi, &up);
-    CHK(up);
-    CHK(gdca_double_mutant_scan_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, m.Emin, m.code, m.epi));
-    return fetch_double_maps(ctx, m, Emin, code, epi);
+    CHK(check_double_scan(ctx, mJ, Pi, N, 1, q, X, K, Emin, code, epi));
+    const size_t n = (size_t)N * (q - 1), maps = (size_t)N * (size_t)N * (size_t)K;
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *X_dev = sg.in(X, (size_t)N * K);
+    double *Emin_dev = sg.out(Emin, maps * sizeof(double));
+    int32_t *code_dev = sg.out(code, maps * sizeof(int32_t));
+    double *epi_dev = sg.out(epi, maps * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_double_mutant_scan_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, Emin_dev, code_dev, epi_dev));
 }
 
 gdca_status gdca_double_mutants(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
                                 const void *muts, int32_t L, double *out)
 {
-    CHK(validate_double(ctx, N, q, K));
-    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
-    if (!mJ || !Pi || !X || !muts || !out) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)N * (q - 1), no = (size_t)L * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const double *mJ_dev = (const double *)upload(ctx, 1, mJ, n * n * sizeof(double), &up);
-    const double *Pi_dev = (const double *)upload(ctx, 2, Pi, n * sizeof(double), &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 0, X, (size_t)N * K, &up);
-    const void *muts_dev = upload(ctx, 4, muts, (size_t)L * 5 * sizeof(int32_t), &up);
-    double *out_dev = staged_out(ctx, 5, no, &up);
-    CHK(up);
-    CHK(gdca_double_mutants_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, muts_dev, L, out_dev));
-    return to_host(ctx, out, ctx->scratch[5], no);
+    CHK(check_double_list(ctx, mJ, Pi, N, 1, q, X, K, muts, L, out));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *X_dev = sg.in(X, (size_t)N * K);
+    const void *muts_dev = sg.in(muts, (size_t)L * 5 * sizeof(int32_t));
+    double *out_dev = sg.out(out, (size_t)L * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_double_mutants_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, muts_dev, L, out_dev));
 }
 
 gdca_status gdca_run_double_mutant_scan(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                         const int8_t *X_host, int32_t K, double *Emin_host, int32_t *code_host, double *epi_host, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_double(ctx, N, q, K));
-    if (!Z_host || !X_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (!Emin_host && !code_host && !epi_host) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
-    const double_maps m = stage_double_maps(ctx, N, K, Emin_host, code_host, epi_host, &up);
-    CHK(up);
-    CHK(gdca_run_double_mutant_scan_dev(ctx, Z_dev, N, M, q, p, X_dev, K, m.Emin, m.code, m.epi, st));
-    return fetch_double_maps(ctx, m, Emin_host, code_host, epi_host);
+    CHK(check_double_scan(ctx, Z_host, p, N, M, q, X_host, K, Emin_host, code_host, epi_host));
+    const size_t maps = (size_t)N * (size_t)N * (size_t)K;
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    double *Emin_dev = sg.out(Emin_host, maps * sizeof(double));
+    int32_t *code_dev = sg.out(code_host, maps * sizeof(int32_t));
+    double *epi_dev = sg.out(epi_host, maps * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_double_mutant_scan_dev(ctx, Z_dev, N, M, q, p, X_dev, K, Emin_dev, code_dev, epi_dev, st));
 }
 
 gdca_status gdca_run_double_mutants(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                     const int8_t *X_host, int32_t K, const void *muts_host, int32_t L, double *out_host, gdca_stats *st)
 {
-    CHK(validate(ctx, N, M, q));
-    CHK(validate_double(ctx, N, q, K));
-    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
-    if (!Z_host || !X_host || !muts_host || !out_host || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t no = (size_t)L * sizeof(double);
-    gdca_status up = GDCA_OK;
-    const int8_t *Z_dev = (const int8_t *)upload(ctx, 0, Z_host, (size_t)N * M, &up);
-    const int8_t *X_dev = (const int8_t *)upload(ctx, 3, X_host, (size_t)N * K, &up);
-    const void *muts_dev = upload(ctx, 4, muts_host, (size_t)L * 5 * sizeof(int32_t), &up);
-    double *out_dev = staged_out(ctx, 5, no, &up);
-    CHK(up);
-    CHK(gdca_run_double_mutants_dev(ctx, Z_dev, N, M, q, p, X_dev, K, muts_dev, L, out_dev, st));
-    return to_host(ctx, out_host, ctx->scratch[5], no);
+    CHK(check_double_list(ctx, Z_host, p, N, M, q, X_host, K, muts_host, L, out_host));
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    const void *muts_dev = sg.in(muts_host, (size_t)L * 5 * sizeof(int32_t));
+    double *out_dev = sg.out(out_host, (size_t)L * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_double_mutants_dev(ctx, Z_dev, N, M, q, p, X_dev, K, muts_dev, L, out_dev, st));
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)
@@ -4023,11 +4015,13 @@ gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)
     CHK(begin(ctx));
     hipStream_t s = ctx->stream;
     const int blocks = 256 * 2;  // 2 waves per SIMD, all resident at once
-    CHK(ensure(ctx, ctx->scratch[6], (size_t)blocks * 256 * sizeof(double)));
+    host_stage sg(ctx);
+    double *sink = (double *)sg.room((size_t)blocks * 256 * sizeof(double));
+    CHK(sg.status());
     CHK(open_timeline(ctx, true, false));
-    gdca_launch_probe_mfma_f64(s, (double *)ctx->scratch[6].p, 16, blocks);  // warm-up
+    gdca_launch_probe_mfma_f64(s, sink, 16, blocks);  // warm-up
     CHK(mark(ctx, T_BEGIN));
-    gdca_launch_probe_mfma_f64(s, (double *)ctx->scratch[6].p, iters, blocks);
+    gdca_launch_probe_mfma_f64(s, sink, iters, blocks);
     CHK(mark(ctx, T_END));
     CHK(check_launch(ctx, "probe"));
     HIPCHK(hipStreamSynchronize(s));

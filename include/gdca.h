@@ -627,6 +627,8 @@ gdca_status gdca_run_double_mutants_dev(gdca_ctx *ctx, const int8_t *Z_dev, int3
                                         const int8_t *X_dev, int32_t K, const void *muts_dev, int32_t L, double *out_dev, gdca_stats *st);
 
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
+/* A host-pointer form on a context with an enqueued run (gdca_run_dev_async, gdca_run_ranked_async, ...) is refused (GDCA_EINVAL)
+ * before it touches the context: nothing is uploaded or reallocated, and the enqueued run is unaffected. */
 /* compute_theta's all-pairs identity sum (inside compute_weighted_frequencies, :28) */
 gdca_status gdca_pair_identity_sum(gdca_ctx *ctx, const int8_t *Z, int32_t N, int32_t M, uint64_t *out);
 /* theta = min(0.5, 0.38*0.32 / mean pair identity) */
