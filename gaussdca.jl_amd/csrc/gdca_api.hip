@@ -179,8 +179,8 @@ static score_target double_list_target(const int8_t *X, int K, const int32_t *mu
 }
 
 // The enqueued, not yet collected run (gdca_run_dev_async / gdca_run_collect): all a collect needs to know, grouped by who writes it.
-// The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev, operator_inverse_retry) borrows n, n_pad, timed
-// (false: begin()) and at.attempt, so that it can go through run_inverses.
+// The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev) borrows n, n_pad, timed (false: begin()) and the
+// progress record `at` -- attempt and refined --, so that it can go through run_inverses and inverse_ladder.
 struct gdca_pending {
     // ---- the front end (pending_front) ----
     int N, M, q, n, n_pad;
@@ -205,7 +205,7 @@ struct gdca_pending {
     struct progress {
         int attempt;           // attempts the run's inverse has had so far (0: the first is enqueued); its watchdog may end a launch (k_inverse.hip, spin_until)
         bool rescored;         // ... and it was run again at collect time: the scores (and a ranking) are those of the last attempt
-        int refined;
+        int refined;           // what the ladder did to the inverse (gdca_stats.refined; the codes: gdca_refined_after_step)
     } at;
     // ---- a ranked run (gdca_run_ranked_async): where its ranking will be, and whether enqueueing it worked ----
     struct {
@@ -498,6 +498,20 @@ static gdca_status fail(gdca_ctx *ctx, gdca_status st, const char *fmt, const ch
     return st;
 }
 
+// ... with a fixed text
+static gdca_status fail(gdca_ctx *ctx, gdca_status st, const char *text)
+{
+    return fail(ctx, st, "%s%s", text, "");
+}
+
+// how a call that has the device scalars in sc_host ends: the verdict on them (gdca_inverse_outcome.h) as status and last error
+static gdca_status conclude(gdca_ctx *ctx, gdca_call_kind kind)
+{
+    const gdca_dev_scalars &h = *ctx->sc_host;
+    const gdca_verdict v = gdca_verdict_of(kind, h.bad_symbol, h.info, h.di_noconv);
+    return v.status == GDCA_OK ? GDCA_OK : fail(ctx, v.status, v.text);
+}
+
 #define HIPCHK(expr)                                                                      \
     do {                                                                                  \
         hipError_t e_ = (expr);                                                           \
@@ -615,7 +629,7 @@ static gdca_status warm_stream(gdca_ctx *ctx, hipStream_t s)
     gdca_fill_async(s, ctx->sc.p, 0, sizeof(gdca_dev_scalars));
     if (hipStreamSynchronize(s) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(ctx, GDCA_EHIP, "the context's stream could not be started%s%s", "", "");
+        return fail(ctx, GDCA_EHIP, "the context's stream could not be started");
     }
     return GDCA_OK;
 }
@@ -730,7 +744,7 @@ gdca_status gdca_ctx_set_timing(gdca_ctx *ctx, int32_t enabled)
 gdca_status gdca_ctx_set_option(gdca_ctx *ctx, const char *key, const char *value)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (!key || !value) return fail(ctx, GDCA_EINVAL, "null option key or value%s%s", "", "");
+    if (!key || !value) return fail(ctx, GDCA_EINVAL, "null option key or value");
     if (!gdca_tuning_set(&ctx->tune, key, value)) return fail(ctx, GDCA_EINVAL, "unknown option or unusable value: %s=%s", key, value);
     return GDCA_OK;
 }
@@ -923,14 +937,6 @@ static gdca_status weights_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, 
     return check_launch(ctx, "weights");
 }
 
-// true where the pseudocount alone bounds cond(C) below the refinement threshold whatever the alignment (pi_max <= (1 - pc) + pc / q):
-// then the first build of a covariance (tally_stage, gdca_run_multi) does not even launch k_cov_norm1
-static bool norm1_settled(const gdca_ctx *ctx, int N, int q, double pc)
-{
-    const double pi_cap = (1.0 - pc) + pc / (double)q;
-    return pc > 0.0 && 2.0 * (double)N * pi_cap * (double)q * (double)q / pc <= ctx->tune.refine_cond && ctx->tune.refine != 1;
-}
-
 // stage 3: Pi, pair tallies.  mode 0 -> Pij_true (ld) ; mode 1 -> covariance (ld)
 // want_norm1 (mode 1): the fused path's first build -- sc->pi_max, and sc->mat_norm1 = ||C||_1 where the screen needs it (k_cov_norm1)
 static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, int q, const double *Meff_dev, double pc,
@@ -964,7 +970,7 @@ static gdca_status tally_stage(gdca_ctx *ctx, const int8_t *Zd, int N, int M, in
     if (want_norm1) CHK(mark(ctx, T_TALLY_END));
     // ||C||_1 for the refinement screen, where the bound that costs nothing (2 N pi_max) does not settle it (k_cov_norm1)
     // (not even launched where the answer is known on the host: pi_max <= (1 - pc) + pc / q whatever the alignment)
-    if (want_norm1 && !norm1_settled(ctx, N, q, pc))
+    if (want_norm1 && !gdca_norm1_settled(N, q, pc, ctx->tune.refine, ctx->tune.refine_cond))
         gdca_launch_cov_norm1(s, out, ld, N, q, pc, ctx->tune.refine_cond, (gdca_dev_scalars *)ctx->sc.p, ctx->tune.refine == 1);
     return check_launch(ctx, "tally");
 }
@@ -1080,7 +1086,7 @@ static gdca_status pack_and_g(gdca_ctx *ctx, const gdca_model &m, const int8_t *
     return GDCA_OK;
 }
 
-// E[K] = 1/2 (x - Pi)' mJ (x - Pi) of the K sequences X (N x K) under the model m.  Illegal bytes of X: sc->bad_symbol bit 2.
+// E[K] = 1/2 (x - Pi)' mJ (x - Pi) of the K sequences X (N x K) under the model m.  Illegal bytes of X: sc->bad_symbol, GDCA_BAD_SEQUENCE.
 // stride != 0: sequence k starts at X_dev + k * stride (a range of the sites of longer sequences)
 static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, double *E_dev, size_t stride = 0)
 {
@@ -1098,12 +1104,12 @@ static gdca_status energy_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
 // E[a + KA * b] of the KA x KB pairings a (+) b across the split (k_pair_energy.hip) under the model m.  XA / XB point at the first
 // site of sequence 0's half; sequence k's starts strideA / strideB bytes on (so the columns of an alignment serve as they lie).
 // what = GDCA_PAIR_ENERGY: the marginal energies through energy_stage on the gap-padded halves (m.Pi needed), combined in the gather
-// kernel's epilogue; GDCA_PAIR_COUPLING: R alone, no g.  Illegal bytes: sc->bad_symbol bit 2.
+// kernel's epilogue; GDCA_PAIR_COUPLING: R alone, no g.  Illegal bytes: sc->bad_symbol, GDCA_BAD_SEQUENCE.
 // lo != nullptr (what = GDCA_PAIR_ENERGY): the log-odds ((EmA[a] + EmB[b]) - E[a, b]) + I in the place of the energy (the gather's LO instances).
 // blk != nullptr: only the pairings inside the species of species-sorted sequences, E packed block by block (include/gdca.h, partner
 // matching) -- the pack, the pad, the marginal energies and the fold are the same calls; the gather goes by blk's work list.
 // what the pair stage makes of its sequences alone, whatever the model: the packed symbols of the two halves (ctx->PXa, ctx->PXb;
-// illegal bytes: sc->bad_symbol bit 2) and, for the energy, the gap-padded halves (ctx->PXpad)
+// illegal bytes: sc->bad_symbol, GDCA_BAD_SEQUENCE) and, for the energy, the gap-padded halves (ctx->PXpad)
 static gdca_status pair_pack(gdca_ctx *ctx, int N, int q, int split, const int8_t *XA, size_t strideA, int KA, const int8_t *XB, size_t strideB,
                              int KB, int what)
 {
@@ -1159,7 +1165,7 @@ static gdca_status assign_stage(gdca_ctx *ctx, const double *E_dev, const pair_b
 }
 
 // D[(b - 1) + q (i + N k)]: the site potentials V (what = GDCA_MUT_POTENTIAL) or the energy changes dE (GDCA_MUT_DELTA) of every single
-// substitution of the K sequences X (N x K) (k_mutation.hip) under the model m.  Illegal bytes of X: sc->bad_symbol bit 2.
+// substitution of the K sequences X (N x K) (k_mutation.hip) under the model m.  Illegal bytes of X: sc->bad_symbol, GDCA_BAD_SEQUENCE.
 static gdca_status mutation_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, int what, double *D_dev)
 {
     CHK(pack_and_g(ctx, m, X_dev, K));
@@ -1170,7 +1176,7 @@ static gdca_status mutation_stage(gdca_ctx *ctx, const gdca_model &m, const int8
 
 // The double-mutant read-outs (k_epistasis.hip) of the K sequences X (N x K) under the model m: dE of every single substitution into
 // ctx->DMd first (the mutation stage), then -- muts == nullptr -- the maps Emin / code / epi (N x N x K; each may be nullptr) over the
-// block lower triangle, or the L listed double mutants (5 x L records) into out.  Illegal bytes of X: sc->bad_symbol bit 2; a record
+// block lower triangle, or the L listed double mutants (5 x L records) into out.  Illegal bytes of X: sc->bad_symbol, GDCA_BAD_SEQUENCE; a record
 // out of range: bit 4.
 static gdca_status double_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, double *Emin_dev, int32_t *code_dev,
                                 double *epi_dev, const int32_t *muts_dev, int L, double *out_dev)
@@ -1227,9 +1233,9 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
 static gdca_status validate(gdca_ctx *ctx, int N, int M, int q)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (N < 1 || M < 1) return fail(ctx, GDCA_EINVAL, "invalid alignment size%s%s", "", "");
-    if (q < 2 || q > GDCA_MAXQ) return fail(ctx, GDCA_EINVAL, "parameter q is too big (max 31 is allowed)%s%s", "", "");
-    if ((long long)N * (q - 1) > GDCA_MAX_N) return fail(ctx, GDCA_EINVAL, "N*(q-1) is larger than GDCA_MAX_N%s%s", "", "");
+    if (N < 1 || M < 1) return fail(ctx, GDCA_EINVAL, "invalid alignment size");
+    if (q < 2 || q > GDCA_MAXQ) return fail(ctx, GDCA_EINVAL, "parameter q is too big (max 31 is allowed)");
+    if ((long long)N * (q - 1) > GDCA_MAX_N) return fail(ctx, GDCA_EINVAL, "N*(q-1) is larger than GDCA_MAX_N");
     return GDCA_OK;
 }
 
@@ -1244,8 +1250,7 @@ static gdca_status fetch_scalars(gdca_ctx *ctx)
 // and the big buffers.  Every other entry point that touches the workspace refuses to run until it has been collected.
 static gdca_status not_pending(gdca_ctx *ctx)
 {
-    if (ctx->pending)
-        return fail(ctx, GDCA_EINVAL, "a run is still enqueued on this context: call gdca_run_collect first%s%s", "", "");
+    if (ctx->pending) return fail(ctx, GDCA_EINVAL, "a run is still enqueued on this context: call gdca_run_collect first");
     return GDCA_OK;
 }
 
@@ -1270,7 +1275,7 @@ class host_stage {
     gdca_status hip(hipError_t e) { return e == hipSuccess ? GDCA_OK : fail(ctx, GDCA_EHIP, "staging a host array: %s%s", hipGetErrorString(e), ""); }
     void *stage(const void *from, void *to, size_t bytes)
     {
-        if (st == GDCA_OK && n == stage_pool::MAX_ARRAYS) st = fail(ctx, GDCA_EINVAL, "more staged arrays than a call may have%s%s", "", "");
+        if (st == GDCA_OK && n == stage_pool::MAX_ARRAYS) st = fail(ctx, GDCA_EINVAL, "more staged arrays than a call may have");
         if (st != GDCA_OK) return nullptr;
         gdca_buf &b = ctx->staging.buf[n];
         st = ensure(ctx, b, bytes);
@@ -1318,41 +1323,6 @@ static gdca_status inverse_norm_stage(gdca_ctx *ctx, int n, int n_pad)
     return check_launch(ctx, "inverse_norm1");
 }
 
-// The screen of the fused path costs ordinary families nothing: the covariance with pseudocount pc is that of a MIXTURE -- weight 1 - pc
-// on the reweighted alignment, weight pc on independent uniform columns -- so  C >= pc Cov_uniform  in the positive-definite order, and
-// Cov_uniform = blockdiag(I / q - 1 1^T / q^2) (q - 1 states a column) has smallest eigenvalue 1 / q^2:
-//       lambda_min(C) >= pc / q^2,     cond_2(C) <= ||C||_1 q^2 / pc
-// (attained on every alignment tried: a column without gaps makes the bound sharp).  For ||C||_1 two figures: 2 N pi_max, which the
-// single-site frequencies give away (k_pi_finalize), and the measured norm (64 .. 94 on the reference's `large` data) where the first
-// is not enough -- k_cov_norm1 decides that on the device with this very formula, before the sweep overwrites C.  At the
-// pseudocounts gDCA is used with the bound is 1e4 .. 1e5 and the run pays nothing; beyond the threshold the collect measures ||X||_1
-// (one pass over the lower triangle) and decides on kappa_1 = ||C||_1 ||X||_1 like the operator-level entry.  +inf where there is no
-// bound (pc = 0).
-static double cond_bound(const gdca_dev_scalars &h, double pc, int q, int N)
-{
-    const double c1 = h.mat_norm1 > 0.0 ? h.mat_norm1 : 2.0 * (double)N * h.pi_max;
-    if (!(c1 > 0.0) || !(pc > 0.0)) return HUGE_VAL;
-    return c1 * (double)q * (double)q / pc;
-}
-
-static bool wants_refinement(const gdca_ctx *ctx, const gdca_dev_scalars &h)
-{
-    if (h.info != 0 || ctx->tune.refine == 0) return false;
-    if (ctx->tune.refine == 1) return true;
-    if (!(h.inv_norm1 > 0.0)) return false;  // not measured: the a-priori bound on cond(C) was below the threshold
-    // kappa_1 = ||C||_1 ||X||_1 (||C||_1: the covariance build's, or the caller's matrix at the operator-level entry)
-    return h.inv_norm1 * (h.mat_norm1 > 0.0 ? h.mat_norm1 : 1.0) > ctx->tune.refine_cond;
-}
-
-// The reference's own factorisation as the last resort (option CHOLESKY: 0 never, 1 where the sweep gave up, 2 always [tests]):
-// the sweep reported a non-positive pivot -- beyond cond ~1e10 that can be its own rounding, LAPACK's dpotrf still factors such
-// matrices -- or its Newton-Schulz step could not converge.  `h`: the scalars as fetched after the sweep / the refinement.
-static bool wants_cholesky(const gdca_ctx *ctx, const gdca_dev_scalars &h, int refined)
-{
-    if (ctx->tune.cholesky == 0 || h.bad_symbol || h.info == INT32_MIN) return false;
-    return ctx->tune.cholesky == 2 || h.info > 0 || refined < 0;
-}
-
 // ctx->C2 holds the matrix (n_pad x n_pad, identity padding, at least its lower block triangle): dpotrf + dpotri by blocks, -inverse
 // into ctx->A where the sweep would have left it; sc->info becomes dpotrf's
 static gdca_status cholesky_stage(gdca_ctx *ctx, int n, int n_pad)
@@ -1383,27 +1353,22 @@ static gdca_status cov_from_pij_stage(gdca_ctx *ctx, int N, int M, int q, double
     gdca_launch_pi_finalize(s, (const unsigned long long *)ctx->Pifix.p, N_all ? N_all : N, q, gdca_fix_shift(M), &sc->Meff, pc, nullptr,
                             (double *)ctx->Pipc.p, want_norm1 ? &sc->pi_max : nullptr);
     gdca_launch_cov_from_pij(s, (const double *)ctx->Pij.p + off * (ldp + 1), (const double *)ctx->Pipc.p + off, N, q, pc, dst, ld, ldp);
-    if (want_norm1 && !norm1_settled(ctx, N, q, pc))
+    if (want_norm1 && !gdca_norm1_settled(N, q, pc, ctx->tune.refine, ctx->tune.refine_cond))
         gdca_launch_cov_norm1(s, dst, ld, N, q, pc, ctx->tune.refine_cond, sc, ctx->tune.refine == 1);
     return check_launch(ctx, "covariance from Pij_true");
 }
 
-// The covariance of the enqueued run once more into dst (ld = n_pad), for the collect's second attempt, refinement and Cholesky
-// fallback (the sweep worked in place): from the tallies -- or, a pseudocount group of gdca_run_multi, from the stored Pij_true
-static gdca_status rebuild_covariance(gdca_ctx *ctx, double *dst)
-{
-    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    const int N = ctx->pend.N, M = ctx->pend.M, q = ctx->pend.q;
-    if (ctx->pend.pij)
-        return cov_from_pij_stage(ctx, N, M, q, ctx->pend.p.pseudocount, dst, (size_t)ctx->pend.n_pad, false, ctx->pend.N_all, ctx->pend.site0);
-    return tally_stage(ctx, ctx->pend.Z, N, M, q, &sc->Meff, ctx->pend.p.pseudocount, 1, nullptr, dst, (size_t)ctx->pend.n_pad);
-}
-
-// ... with its identity padding: what every recovery branch of the collect starts from
+// The covariance of the enqueued run once more into dst (n_pad x n_pad, identity padding), what every rung of the recovery ladder
+// starts from (the sweep worked in place): from the tallies -- or, a pseudocount group of gdca_run_multi, from the stored Pij_true
 static gdca_status rebuild_padded(gdca_ctx *ctx, void *dst)
 {
-    CHK(rebuild_covariance(ctx, (double *)dst));
-    gdca_launch_pad_identity(ctx->stream, (double *)dst, ctx->pend.n, ctx->pend.n_pad);
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    const gdca_pending &r = ctx->pend;
+    if (r.pij)
+        CHK(cov_from_pij_stage(ctx, r.N, r.M, r.q, r.p.pseudocount, (double *)dst, (size_t)r.n_pad, false, r.N_all, r.site0));
+    else
+        CHK(tally_stage(ctx, r.Z, r.N, r.M, r.q, &sc->Meff, r.p.pseudocount, 1, nullptr, (double *)dst, (size_t)r.n_pad));
+    gdca_launch_pad_identity(ctx->stream, (double *)dst, r.n, r.n_pad);
     return GDCA_OK;
 }
 
@@ -1503,12 +1468,112 @@ static gdca_status logodds_epilogue(gdca_ctx *ctx)
     return fetch_scalars(ctx);
 }
 
+// ---- the recovery ladder of an SPD inverse -------------------------------------------------------------------------
+// One walk for a fused run's collect and for the operator-level inverses: the decisions are gdca_inverse_outcome.h's, and what differs
+// between the two callers is this record and the three functions that read it.
+struct inverse_source {
+    gdca_inverse_form form;
+    const double *A_dev;  // an operator: the caller's matrix (n x n, ld n), still intact -- the sweep works on a copy
+};
+
+enum ladder_step { STEP_RETRY, STEP_NEWTON, STEP_FALLBACK };
+
+static gdca_inverse_state ladder_state(const gdca_ctx *ctx, const inverse_source &src, int retries)
+{
+    const gdca_dev_scalars &h = *ctx->sc_host;
+    const gdca_pending &r = ctx->pend;
+    const gdca_tuning &t = ctx->tune;
+    const bool run = src.form == GDCA_FORM_RUN;  // (an operator has no alignment: no a-priori bound)
+    return gdca_inverse_state{src.form, h.info, h.bad_symbol, h.inv_norm1, h.mat_norm1, h.ns_resid, h.pi_max, run ? r.p.pseudocount : 0.0,
+                              run ? r.N : 0, run ? r.q : 0, t.refine, t.cholesky, t.refine_cond, r.at.attempt, retries};
+}
+
+// the matrix once more into dst (n_pad x n_pad, identity padding): a run's covariance from the tallies or the stored Pij_true, an
+// operator's from the caller
+static gdca_status ladder_matrix(gdca_ctx *ctx, const inverse_source &src, void *dst)
+{
+    if (src.form == GDCA_FORM_RUN) return rebuild_padded(ctx, dst);
+    gdca_launch_copy_in(ctx->stream, src.A_dev, ctx->pend.n, (double *)dst, ctx->pend.n_pad);
+    return check_launch(ctx, "copy_in");
+}
+
+// ||X||_1 of the inverse in ctx->A into sc->inv_norm1; an operator measures ||C||_1 of the caller's matrix with it (a run's first
+// build of the covariance has done that where the screen needed it)
+static gdca_status ladder_norms(gdca_ctx *ctx, const inverse_source &src)
+{
+    if (src.form == GDCA_FORM_OPERATOR) {
+        CHK(ensure(ctx, ctx->normws, (size_t)ctx->pend.n_pad * sizeof(double)));
+        gdca_launch_matrix_norm1(ctx->stream, src.A_dev, (size_t)ctx->pend.n, ctx->pend.n, (double *)ctx->normws.p,
+                                 &((gdca_dev_scalars *)ctx->sc.p)->mat_norm1);
+    }
+    return inverse_norm_stage(ctx, ctx->pend.n, ctx->pend.n_pad);
+}
+
+// what follows an inverse that changed; the scalars are in sc_host afterwards.  A run scores again -- a second attempt as a stage of
+// its own on the run's timeline, and after the fallback gdca_stats.inverse_norm1 is that inverse's.  An operator takes the log det of
+// the new pivots; after a Newton-Schulz step its log det stays that of the sweep's pivots.
+static gdca_status ladder_changed(gdca_ctx *ctx, const inverse_source &src, ladder_step step)
+{
+    if (src.form == GDCA_FORM_OPERATOR) {
+        if (step != STEP_NEWTON) CHK(logdet_stage(ctx, ctx->pend.n));
+        return fetch_scalars(ctx);
+    }
+    if (step == STEP_FALLBACK) CHK(inverse_norm_stage(ctx, ctx->pend.n, ctx->pend.n_pad));
+    CHK(rescore(ctx, step == STEP_RETRY));
+    if (step == STEP_RETRY) ctx->pend.at.rescored = true;
+    return GDCA_OK;
+}
+
+// A first attempt has completed and its scalars are in sc_host: up to `retries` further attempts where the watchdog ended the launch,
+// the norm, the Newton-Schulz step and the Cholesky fallback, each where gdca_inverse_outcome.h says so -- on ordinary input every
+// answer is no and nothing is enqueued.  Synchronous and several times the cost of the inverse itself wherever a rung is taken: the
+// paths of rare inputs (pseudocounts far below the 0.2 .. 0.8 gDCA is used with), walked here so that the enqueue side stays lean.
+// The inverse finally arrived at is in ctx->A, its scalars in sc_host, what was done to it in pend.at.
+static gdca_status inverse_ladder(gdca_ctx *ctx, const inverse_source &src, int retries)
+{
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    const int n = ctx->pend.n, n_pad = ctx->pend.n_pad;
+    const size_t mat = (size_t)n_pad * n_pad * sizeof(double);
+    while (gdca_retry_due(ladder_state(ctx, src, retries))) {
+        // (a run's inverse again as a launch of its own behind the pipeline's gate, marked on the run's timeline)
+        ++ctx->pend.at.attempt;
+        CHK(ladder_matrix(ctx, src, ctx->A.p));
+        HIPCHK(hipMemsetAsync(&sc->info, 0, sizeof(int), ctx->stream));
+        CHK(src.form == GDCA_FORM_RUN ? run_inverse(ctx) : inverse_stage(ctx, n, n_pad, nullptr));
+        CHK(ladder_changed(ctx, src, STEP_RETRY));
+    }
+    if (gdca_norm_due(ladder_state(ctx, src, retries))) {
+        CHK(ladder_norms(ctx, src));
+        CHK(fetch_scalars(ctx));
+    }
+    if (gdca_wants_refinement(ladder_state(ctx, src, retries))) {
+        CHK(ensure(ctx, ctx->C2, mat));
+        CHK(ensure(ctx, ctx->B0, mat));
+        CHK(ensure(ctx, ctx->Rt, mat));
+        CHK(ladder_matrix(ctx, src, ctx->C2.p));
+        gdca_launch_newton_schulz(ctx->stream, (double *)ctx->A.p, (const double *)ctx->C2.p, (double *)ctx->B0.p, (double *)ctx->Rt.p, n_pad,
+                                  &sc->ns_resid);
+        CHK(check_launch(ctx, "newton_schulz"));
+        CHK(ladder_changed(ctx, src, STEP_NEWTON));
+        ctx->pend.at.refined = gdca_refined_after_step(ladder_state(ctx, src, retries));
+    }
+    if (gdca_wants_cholesky(ladder_state(ctx, src, retries), ctx->pend.at.refined)) {
+        // blocked dpotrf + dpotri of the matrix: its verdict on positive definiteness is LAPACK's
+        CHK(ensure(ctx, ctx->C2, mat));
+        CHK(ladder_matrix(ctx, src, ctx->C2.p));
+        CHK(cholesky_stage(ctx, n, n_pad));
+        CHK(ladder_changed(ctx, src, STEP_FALLBACK));
+        ctx->pend.at.refined = 2;
+    }
+    return GDCA_OK;
+}
+
 extern "C" {
 
 gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (!ctx->pending) return fail(ctx, GDCA_EINVAL, "no enqueued run to collect%s%s", "", "");
+    if (!ctx->pending) return fail(ctx, GDCA_EINVAL, "no enqueued run to collect");
     HIPCHK(hipSetDevice(ctx->device));
     ctx->pending = false;
     ctx->pend.rank.pending = false;  // (collected through this entry, a ranked run's ranking is given up: its arrays are scratch of the next run)
@@ -1519,70 +1584,14 @@ gdca_status gdca_run_collect(gdca_ctx *ctx, gdca_stats *st)
     } else {
         CHK(fetch_scalars(ctx));
     }
-    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    const int n_pad = ctx->pend.n_pad, n = ctx->pend.n;
-    while (ctx->sc_host->info == INT32_MIN && !ctx->sc_host->bad_symbol && ctx->pend.at.attempt < ctx->tune.sweep_retries) {
-        // The sweep's watchdog ended the launch (k_inverse.hip, spin_until: in practice a launch that did not get all its workgroups
-        // back after the driver had taken the device's queues off the hardware).  Nothing is wrong with the matrix: the covariance
-        // once more from the tallies -- the sweep works in place --, the inverse again as a launch of its own behind the pipeline's
-        // gate, the scores again.  A launch that fails option SWEEP_RETRIES times in a row (default 2) is reported as GDCA_EHIP.
-        ++ctx->pend.at.attempt;
-        CHK(rebuild_padded(ctx, ctx->A.p));
-        HIPCHK(hipMemsetAsync(&sc->info, 0, sizeof(int), ctx->stream));
-        CHK(run_inverse(ctx));
-        CHK(rescore(ctx, true));
-        ctx->pend.at.rescored = true;
-    }
-    if (ctx->tune.refine != 0 && ctx->sc_host->info == 0 && !ctx->sc_host->bad_symbol &&
-        (ctx->tune.refine == 1 || cond_bound(*ctx->sc_host, ctx->pend.p.pseudocount, ctx->pend.q, ctx->pend.N) > ctx->tune.refine_cond)) {
-        CHK(inverse_norm_stage(ctx, ctx->pend.n, ctx->pend.n_pad));   // cond(C) may be beyond the threshold: ||X||_1 itself
-        CHK(fetch_scalars(ctx));
-    }
-    if (wants_refinement(ctx, *ctx->sc_host) && !ctx->sc_host->bad_symbol) {
-        // The inverse looks ill-conditioned (||X||_1 beyond the threshold): the block sweep's error grows like cond^2, so it gets
-        // one Newton-Schulz step against the covariance -- built again from the tallies: the sweep worked in place -- and the
-        // scores are computed again from the refined inverse.  Synchronous and several times the cost of the run itself: a path
-        // for rare inputs (pseudocounts far below the 0.2 .. 0.8 gDCA is used with), taken here so that the enqueue side stays lean.
-        const size_t mat = (size_t)n_pad * n_pad * sizeof(double);
-        CHK(ensure(ctx, ctx->C2, mat));
-        CHK(ensure(ctx, ctx->B0, mat));
-        CHK(ensure(ctx, ctx->Rt, mat));
-        CHK(rebuild_padded(ctx, ctx->C2.p));
-        gdca_launch_newton_schulz(ctx->stream, (double *)ctx->A.p, (const double *)ctx->C2.p, (double *)ctx->B0.p, (double *)ctx->Rt.p, n_pad,
-                                  &sc->ns_resid);
-        CHK(check_launch(ctx, "newton_schulz"));
-        CHK(rescore(ctx));
-        // the step squares I - X0 C: with that residual at one or beyond (cond(C) past ~1e10: the sweep's own error is of order one
-        // there) it cannot have converged, and the caller is told so instead of being handed the result as if it were refined
-        ctx->pend.at.refined = ctx->sc_host->ns_resid < 1.0 ? 1 : -1;
-    }
-    if (wants_cholesky(ctx, *ctx->sc_host, ctx->pend.at.refined)) {
-        // the sweep gave up on this covariance (a non-positive pivot, or a refinement that cannot converge): once more the
-        // reference's way -- the covariance from the tallies again, blocked dpotrf + dpotri, the scores from that inverse.  Its
-        // verdict on positive definiteness is LAPACK's.
-        CHK(ensure(ctx, ctx->C2, (size_t)n_pad * n_pad * sizeof(double)));
-        CHK(rebuild_padded(ctx, ctx->C2.p));
-        CHK(cholesky_stage(ctx, n, n_pad));
-        CHK(inverse_norm_stage(ctx, n, n_pad));
-        CHK(rescore(ctx));
-        ctx->pend.at.refined = 2;
-    }
+    CHK(inverse_ladder(ctx, inverse_source{GDCA_FORM_RUN, nullptr}, ctx->tune.sweep_retries));
     note_logdet(ctx);
     if (ctx->pend.target.kind == score_target::LOGLIK && ctx->sc_host->info == 0 && !ctx->sc_host->bad_symbol) CHK(loglik_epilogue(ctx));
     if (ctx->pend.target.logodds && ctx->sc_host->info == 0 && !ctx->sc_host->bad_symbol) CHK(logodds_epilogue(ctx));
     if (st) CHK(fill_stats(ctx, st));
-    const gdca_dev_scalars &h = *ctx->sc_host;
-    if (h.bad_symbol & 4) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
-    if (h.bad_symbol & 16) return fail(ctx, GDCA_EINVAL, "a double-mutant record is out of range%s%s", "", "");
-    if (h.bad_symbol) return fail(ctx, GDCA_EINVAL, "alignment holds a symbol outside 1..q%s%s", "", "");
-    if (h.info == INT32_MIN)  // the sweep kernel's watchdog (k_inverse.hip, spin_until): a dependency wait ran out of time
-        return fail(ctx, GDCA_EHIP, "SPD inverse aborted: a dependency wait inside the sweep kernel timed out%s%s", "", "");
-    if (h.info != 0) return fail(ctx, GDCA_ENOTPD, "covariance matrix is not positive definite%s%s", "", "");
-    if (h.di_noconv != 0) {
-        if (st) st->info = -h.di_noconv;
-        return fail(ctx, GDCA_ENOCONV, "eigenvalue iteration of a DI block did not converge%s%s", "", "");
-    }
-    return GDCA_OK;
+    const gdca_status verdict = conclude(ctx, GDCA_ENDS_RUN);
+    if (verdict == GDCA_ENOCONV && st) st->info = -ctx->sc_host->di_noconv;
+    return verdict;
 }
 
 }  // extern "C"
@@ -1595,7 +1604,7 @@ static gdca_status score_times(gdca_ctx *ctx, gdca_stats *st)
     st->ms_total = elapsed(ctx, T_BEGIN, T_END, &tfail);
     st->ms_score = elapsed(ctx, T_SCORE_BEGIN, T_END, &tfail) / sbatch;
     st->ms_fn = ctx->pend.at.refined == 0 ? elapsed(ctx, T_FN_BEGIN, T_FN_END, &tfail) / sbatch : 0.0;
-    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
+    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime");
     return GDCA_OK;
 }
 
@@ -1620,7 +1629,7 @@ static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st)
     st->sweep_retries = ctx->pend.at.attempt;
     st->inverse_norm1 = h.inv_norm1;
     st->matrix_norm1 = h.mat_norm1;
-    st->cond_bound = ctx->tune.refine != 0 ? cond_bound(h, ctx->pend.p.pseudocount, ctx->pend.q, ctx->pend.N) : 0.0;
+    st->cond_bound = ctx->tune.refine != 0 ? gdca_cond_bound(h.mat_norm1, h.pi_max, ctx->pend.p.pseudocount, ctx->pend.q, ctx->pend.N) : 0.0;
     st->inverse_flops = inverse_flops_model((double)ctx->pend.n);
     st->update_flops = ctx->pend.upd_flops;
     st->sweep_ghz = h.sweep_ticks ? (double)h.sweep_cycles / (double)h.sweep_ticks * 0.1 : 0.0;
@@ -1636,7 +1645,7 @@ static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st)
     if (ctx->pend.at.refined == 0) st->ms_pair_tally = elapsed(ctx, T_TALLY_BEGIN, T_TALLY_END, &tfail) * fshare;
     st->ms_inverse = elapsed(ctx, T_INV_BEGIN, T_INV_END, &tfail) * share;
     st->ms_inverse_update = elapsed(ctx, T_SWEEP_BEGIN, T_SWEEP_END, &tfail) * share;
-    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
+    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime");
     return score_times(ctx, st);
 }
 
@@ -1644,9 +1653,8 @@ static gdca_status fill_stats(gdca_ctx *ctx, gdca_stats *st)
 // phase): front end (theta, reweighting, tallies, covariance), SPD inverse, scores.
 static gdca_status check_params(gdca_ctx *ctx, const gdca_params *p)
 {
-    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0))
-        return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)%s%s", "", "");
-    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value%s%s", "", "");
+    if (!(p->pseudocount >= 0.0 && p->pseudocount <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid pseudocount value (must be between 0 and 1)");
+    if (!(p->theta <= 1.0)) return fail(ctx, GDCA_EINVAL, "invalid theta value");
     return GDCA_OK;
 }
 
@@ -1654,10 +1662,9 @@ static gdca_status run_check_args(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N,
                                   double *S_dev)
 {
     CHK(validate(ctx, N, M, q));
-    if (!Z_dev || !S_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Z_dev || !S_dev || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
     CHK(check_params(ctx, p));
-    if (p->score != GDCA_SCORE_FROB && p->score != GDCA_SCORE_DI)
-        return fail(ctx, GDCA_EINVAL, "invalid score value%s%s", "", "");
+    if (p->score != GDCA_SCORE_FROB && p->score != GDCA_SCORE_DI) return fail(ctx, GDCA_EINVAL, "invalid score value");
     return GDCA_OK;
 }
 
@@ -1740,7 +1747,7 @@ static gdca_status run_inverse_merged(gdca_ctx *lead, gdca_ctx *const *mem, int 
     gdca_inverse_job jobs[8];
     gdca_tuning tun[8];  // a member's schedule switches are its own context's, the switches of the merged launch the leader's
     double flops[8];
-    if (K > gdca_inverse_max_merge() || K > 8) return fail(ctx, GDCA_EINVAL, "too many members in a merged inverse%s%s", "", "");
+    if (K > gdca_inverse_max_merge() || K > 8) return fail(ctx, GDCA_EINVAL, "too many members in a merged inverse");
     bool timed = true, stamps = true;
     // (the members of a batch are normally peers of ONE pipeline: one wait and one record per distinct gate, not per member)
     gdca_gate *gates[8];
@@ -1869,10 +1876,10 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
     gdca_ctx *lead = ctxs[0];
     if (!lead) return GDCA_EINVAL;
     for (int k = 0; k < K; ++k) {
-        if (!ctxs[k]) return fail(lead, GDCA_EINVAL, "null context in the batch%s%s", "", "");
+        if (!ctxs[k]) return fail(lead, GDCA_EINVAL, "null context in the batch");
         for (int j = 0; j < k; ++j)
-            if (ctxs[j] == ctxs[k]) return fail(lead, GDCA_EINVAL, "the same context twice in one batch%s%s", "", "");
-        if (ctxs[k]->device != lead->device) return fail(lead, GDCA_EINVAL, "contexts of one batch must share a device%s%s", "", "");
+            if (ctxs[j] == ctxs[k]) return fail(lead, GDCA_EINVAL, "the same context twice in one batch");
+        if (ctxs[k]->device != lead->device) return fail(lead, GDCA_EINVAL, "contexts of one batch must share a device");
         gdca_status vs = not_pending(ctxs[k]);
         if (vs == GDCA_OK) vs = run_check_args(ctxs[k], Z_dev[k], N[k], M[k], q[k], p, S_dev[k]);
         if (vs != GDCA_OK) return member_error(lead, ctxs[k], k, vs);
@@ -1884,7 +1891,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
     // on the leader's stream, as in round 4: 8 x 0.55 ms in front of 8 x 0.43 ms of merged inverses at config B).  The members keep
     // their own workspaces, scalars and timing events; their streams are restored before returning.
     hipStream_t own[64], use[64];
-    if (K > 64) return fail(lead, GDCA_EINVAL, "at most 64 families per batch%s%s", "", "");
+    if (K > 64) return fail(lead, GDCA_EINVAL, "at most 64 families per batch");
     // Round 6, the default (option PHASED_GRIDS != 0): the members' kernels of a KIND as ONE grid (gdca_launch.h).  The front ends are
     // recorded member by member, then issued in lockstep on the leader's stream -- ~25 launches per batch instead of ~25 per member,
     // every one with all members' workgroups on the chip at once --, then the inverses, then the score stages (and, for the ranked
@@ -1901,7 +1908,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         // the batch's stream: the pipeline's (gdca_gate) where the leader belongs to one, behind whatever its own stream holds
         hipStream_t bs = lead->gate && lead->gate->batch_stream ? lead->gate->batch_stream : lead->stream;
         if (bs != lead->stream && (hipEventRecord(lead->ev_upload, lead->stream) != hipSuccess || hipStreamWaitEvent(bs, lead->ev_upload, 0) != hipSuccess))
-            return fail(lead, GDCA_EHIP, "event chain of the batch%s%s", "", "");
+            return fail(lead, GDCA_EHIP, "event chain of the batch");
         // G groups of members (member k in group k mod G), each group's front ends as batched grids on a stream of its own -- the
         // leader's and the next members' --, the groups side by side: a VALU-bound reweighting of one group runs beside the
         // LDS-atomic-bound pair tallies of another.  One group (everything in lockstep) where the members are small: their kernels
@@ -1929,11 +1936,11 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
                 }
             }
             rec.member(-1);
-            if (rec.flush() != hipSuccess && st == GDCA_OK) st = fail(lead, GDCA_EHIP, "a batched front-end launch failed%s%s", "", "");
+            if (rec.flush() != hipSuccess && st == GDCA_OK) st = fail(lead, GDCA_EHIP, "a batched front-end launch failed");
             // the batch's stream goes on behind this group's front ends
             if (st == GDCA_OK && gi > 0 &&
                 (hipEventRecord(ctxs[gi]->ev_batch, sg) != hipSuccess || hipStreamWaitEvent(bs, ctxs[gi]->ev_batch, 0) != hipSuccess))
-                st = fail(lead, GDCA_EHIP, "event chain of the batch's front ends%s%s", "", "");
+                st = fail(lead, GDCA_EHIP, "event chain of the batch's front ends");
         }
         if (st != GDCA_OK) done_front = 0;  // (nothing of a batch that failed to enqueue is run any further; it is drained below)
         for (int k = 0; k < K; ++k) {
@@ -1950,7 +1957,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
             if (st != GDCA_OK) failed = k;
         }
         rec.member(-1);
-        if (rec.end() != hipSuccess && st == GDCA_OK) st = fail(lead, GDCA_EHIP, "a batched score launch failed%s%s", "", "");
+        if (rec.end() != hipSuccess && st == GDCA_OK) st = fail(lead, GDCA_EHIP, "a batched score launch failed");
         if (ranked && st == GDCA_OK && rank_sep > 0) *ranked = true;
         // the members' collects synchronise THEIR stream: every one of them waits for the batch (one event on the batch's stream)
         bool chained = st == GDCA_OK && hipEventRecord(lead->ev_batch, bs) == hipSuccess;
@@ -1967,7 +1974,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         }
         if (!chained) {
             (void)hipStreamSynchronize(bs);
-            return fail(lead, GDCA_EHIP, "event chain of the batch%s%s", "", "");
+            return fail(lead, GDCA_EHIP, "event chain of the batch");
         }
         return GDCA_OK;
     }
@@ -1990,7 +1997,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         if (st == GDCA_OK && use[k] != lead->stream) {
             // the batch's stream goes on behind this member's front end
             if (hipEventRecord(ctxs[k]->ev_batch, use[k]) != hipSuccess || hipStreamWaitEvent(lead->stream, ctxs[k]->ev_batch, 0) != hipSuccess)
-                st = fail(lead, GDCA_EHIP, "event chain of the batch's front ends%s%s", "", "");
+                st = fail(lead, GDCA_EHIP, "event chain of the batch's front ends");
         }
         if (st == GDCA_OK) ++done_front;
     }
@@ -1998,9 +2005,9 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
     if (st == GDCA_OK) st = run_inverses(lead, ctxs, done_front);
     if (st == GDCA_OK && side_by_side) {
         // ... and the score stages side by side again, each behind the batch's inverses on the stream its front end ran on
-        if (hipEventRecord(lead->ev_upload, lead->stream) != hipSuccess) st = fail(lead, GDCA_EHIP, "event chain of the batch's score stages%s%s", "", "");
+        if (hipEventRecord(lead->ev_upload, lead->stream) != hipSuccess) st = fail(lead, GDCA_EHIP, "event chain of the batch's score stages");
         for (int j = 1; j < W && st == GDCA_OK; ++j)
-            if (hipStreamWaitEvent(own[j], lead->ev_upload, 0) != hipSuccess) st = fail(lead, GDCA_EHIP, "event chain of the batch's score stages%s%s", "", "");
+            if (hipStreamWaitEvent(own[j], lead->ev_upload, 0) != hipSuccess) st = fail(lead, GDCA_EHIP, "event chain of the batch's score stages");
     }
     bool chained = true;  // every member's own stream waits for what was enqueued for it elsewhere
     for (int k = 0; k < done_front && st == GDCA_OK; ++k) {
@@ -2026,7 +2033,7 @@ static gdca_status run_phased(gdca_ctx *const *ctxs, int32_t K, const int8_t *co
         // the chain could not be built: the members' collects would not wait for the batch -- wait for it here instead
         (void)hipStreamSynchronize(lead->stream);
         for (int j = 1; j < W; ++j) (void)hipStreamSynchronize(own[j]);
-        return fail(lead, GDCA_EHIP, "event chain of the batch%s%s", "", "");
+        return fail(lead, GDCA_EHIP, "event chain of the batch");
     }
     return st;
 }
@@ -2048,7 +2055,7 @@ gdca_status gdca_run(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, 
                      double *S_host, gdca_stats *st)
 {
     CHK(validate(ctx, N, M, q));
-    if (!Z_host || !S_host) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Z_host || !S_host) return fail(ctx, GDCA_EINVAL, "null pointer");
     host_stage sg(ctx);
     const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
     double *S_dev = sg.out(S_host, (size_t)N * N * sizeof(double));
@@ -2091,7 +2098,7 @@ gdca_status gdca_ranking_dev(gdca_ctx *ctx, const double *S_dev, int32_t N, int3
 gdca_status gdca_run_ranked_async(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t min_separation)
 {
     CHK(validate(ctx, N, M, q));
-    if (!Z_host || min_separation < 1) return fail(ctx, GDCA_EINVAL, "null pointer or min_separation < 1%s%s", "", "");
+    if (!Z_host || min_separation < 1) return fail(ctx, GDCA_EINVAL, "null pointer or min_separation < 1");
     // (from pageable memory this copy holds the calling thread until the last byte is staged -- and overlaps whatever another
     // context of the same device is computing meanwhile: the pipelined batch driver's upload of the NEXT family)
     host_stage sg(ctx);
@@ -2111,12 +2118,12 @@ gdca_status gdca_run_ranked_phased_async(gdca_ctx *const *ctxs, int32_t K, const
     gdca_ctx *lead = ctxs[0];
     if (!lead) return GDCA_EINVAL;
     gdca_ctx *ctx = lead;  // (the error macros' context)
-    if (min_separation < 1) return fail(lead, GDCA_EINVAL, "min_separation < 1%s%s", "", "");
+    if (min_separation < 1) return fail(lead, GDCA_EINVAL, "min_separation < 1");
     const int8_t *Zd[64];
     double *Sd[64];
     for (int k = 0; k < K; ++k) {
         gdca_ctx *m = ctxs[k];
-        if (!m || !Z_host[k]) return fail(lead, GDCA_EINVAL, "null context or alignment in the batch%s%s", "", "");
+        if (!m || !Z_host[k]) return fail(lead, GDCA_EINVAL, "null context or alignment in the batch");
         gdca_status vs = validate(m, N[k], M[k], q[k]);
         if (vs == GDCA_OK) vs = not_pending(m);
         if (vs != GDCA_OK) return member_error(lead, m, k, vs);
@@ -2136,7 +2143,7 @@ gdca_status gdca_run_ranked_phased_async(gdca_ctx *const *ctxs, int32_t K, const
     // takes afterwards (gdca_run_dev_phased synchronises the members' streams too, but not on its early argument checks)
     CHK(upload_done(lead));
     for (int k = 1; k < K; ++k)
-        if (hipStreamSynchronize(ctxs[k]->stream) != hipSuccess) return fail(lead, GDCA_EHIP, "upload of a member's alignment%s%s", "", "");
+        if (hipStreamSynchronize(ctxs[k]->stream) != hipSuccess) return fail(lead, GDCA_EHIP, "upload of a member's alignment");
     bool ranked = false;  // (issued as batched grids, the rankings are part of the batch)
     CHK(run_phased(ctxs, K, Zd, N, M, q, p, Sd, min_separation, &ranked));
     // every member's ranking behind its scores, on the member's own stream (which now waits for the batch)
@@ -2148,13 +2155,13 @@ gdca_status gdca_run_ranked_collect(gdca_ctx *ctx, int32_t *i_out, int32_t *j_ou
 {
     if (!ctx) return GDCA_EINVAL;
     auto &r = ctx->pend.rank;
-    if (!r.pending) return fail(ctx, GDCA_EINVAL, "no enqueued ranked run to collect%s%s", "", "");
+    if (!r.pending) return fail(ctx, GDCA_EINVAL, "no enqueued ranked run to collect");
     r.pending = false;
     gdca_stats own;
     CHK(gdca_run_collect(ctx, st ? st : &own));
     if (r.status != GDCA_OK) return r.status;
     if (r.len == 0) return GDCA_OK;
-    if (!i_out || !j_out || !score_out) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!i_out || !j_out || !score_out) return fail(ctx, GDCA_EINVAL, "null pointer");
     // (a run whose inverse was refined, recomputed or run again at collect time has new scores: rank those)
     if (ctx->pend.at.refined != 0 || ctx->pend.at.rescored)
         CHK(ranking_stage(ctx, ctx->pend.target.out, ctx->pend.N, r.sep, r.len, &r.i, &r.j, &r.s));
@@ -2164,7 +2171,7 @@ gdca_status gdca_run_ranked_collect(gdca_ctx *ctx, int32_t *i_out, int32_t *j_ou
 gdca_status gdca_run_ranked(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t min_separation,
                             int32_t *i_out, int32_t *j_out, double *score_out, gdca_stats *st)
 {
-    if (ctx && gdca_ranking_length(N, min_separation) > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (ctx && gdca_ranking_length(N, min_separation) > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer");
     CHK(gdca_run_ranked_async(ctx, Z_host, N, M, q, p, min_separation));
     return gdca_run_ranked_collect(ctx, i_out, j_out, score_out, st);
 }
@@ -2176,7 +2183,7 @@ gdca_status gdca_run_ranked(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int3
 // tallies in their Pij_true form (k_pair_tally mode 0) into ctx->Pij.  Then for every distinct pseudocount, in order of first
 // appearance (a "group"): the covariance from Pij_true (k_cov_from_pij: bit for bit the fused build of that pseudocount), the DI
 // diagonal blocks if a member asks for DI, the inverse -- collected for the group's first member exactly like a single run (second
-// attempt, refinement, Cholesky fallback: each builds C again from Pij_true, rebuild_covariance) -- and every further member scored
+// attempt, refinement, Cholesky fallback: each builds C again from Pij_true, rebuild_padded) -- and every further member scored
 // from the inverse the collect left.  A single run of any member would compute the same C, the same inverse and the same scores.
 struct multi_rank {
     int sep;
@@ -2189,12 +2196,12 @@ struct multi_rank {
 static gdca_status multi_check_args(gdca_ctx *ctx, const void *Z, int32_t N, int32_t M, int32_t q, const gdca_params *p, int32_t K, double *S)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (K < 1 || K > GDCA_MULTI_MAX) return fail(ctx, GDCA_EINVAL, "number of settings must be between 1 and GDCA_MULTI_MAX%s%s", "", "");
-    if (!p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (K < 1 || K > GDCA_MULTI_MAX) return fail(ctx, GDCA_EINVAL, "number of settings must be between 1 and GDCA_MULTI_MAX");
+    if (!p) return fail(ctx, GDCA_EINVAL, "null pointer");
     for (int k = 0; k < K; ++k) {
         CHK(run_check_args(ctx, (const int8_t *)Z, N, M, q, &p[k], S));
         if (!(p[k].theta == p[0].theta || (p[k].theta < 0.0 && p[0].theta < 0.0)))
-            return fail(ctx, GDCA_EINVAL, "every setting of one call must have the same theta%s%s", "", "");
+            return fail(ctx, GDCA_EINVAL, "every setting of one call must have the same theta");
     }
     return not_pending(ctx);
 }
@@ -2292,7 +2299,7 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
             CHK(score_times(ctx, &st[k]));
             if (ctx->sc_host->di_noconv != 0) {
                 st[k].info = -ctx->sc_host->di_noconv;
-                mst[k] = fail(ctx, GDCA_ENOCONV, "eigenvalue iteration of a DI block did not converge%s%s", "", "");
+                mst[k] = fail(ctx, GDCA_ENOCONV, GDCA_TEXT_DI_NOCONV);
                 continue;
             }
             if (rk) CHK(multi_rank_member(ctx, rk, k, Sk));
@@ -2306,8 +2313,7 @@ static gdca_status run_multi(gdca_ctx *ctx, const int8_t *Z_dev, int N, int M, i
     for (int k = 0; k < K; ++k)
         if (mst[k] != GDCA_OK) {
             char msg[sizeof(ctx->err)];
-            snprintf(msg, sizeof(msg), "setting %d: %s", k, mst[k] == GDCA_ENOTPD ? "covariance matrix is not positive definite"
-                                                                               : "eigenvalue iteration of a DI block did not converge");
+            snprintf(msg, sizeof(msg), "setting %d: %s", k, mst[k] == GDCA_ENOTPD ? GDCA_TEXT_COV_NOT_PD : GDCA_TEXT_DI_NOCONV);
             memcpy(ctx->err, msg, sizeof(msg));
             return mst[k];
         }
@@ -2347,11 +2353,11 @@ gdca_status gdca_run_ranked_multi(gdca_ctx *ctx, const int8_t *Z_host, int32_t N
                                   int32_t min_separation, int32_t *i_out, int32_t *j_out, double *score_out, gdca_stats *st)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (min_separation < 1) return fail(ctx, GDCA_EINVAL, "min_separation < 1%s%s", "", "");
+    if (min_separation < 1) return fail(ctx, GDCA_EINVAL, "min_separation < 1");
     double placeholder = 0.0;  // (no score matrix crosses this ABI: the one the members share is the context's)
     CHK(multi_check_args(ctx, Z_host, N, M, q, p, K, &placeholder));
     const long long len = gdca_ranking_length(N, min_separation);
-    if (len > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (len > 0 && (!i_out || !j_out || !score_out)) return fail(ctx, GDCA_EINVAL, "null pointer");
     if (K == 1) return gdca_run_ranked(ctx, Z_host, N, M, q, p, min_separation, i_out, j_out, score_out, st);
     host_stage sg(ctx);
     const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
@@ -2434,13 +2440,6 @@ gdca_status gdca_dbuf_download(gdca_ctx *ctx, const gdca_dbuf *b, uint64_t offse
 // back (weights: Meff/theta/thresh; spd_inverse: info; di: convergence; frequencies: the symbol-range check); the
 // elementwise ones (add_pseudocount, covariance, fn, apc) return right after the launch.
 
-static gdca_status symbols_ok(gdca_ctx *ctx)
-{
-    if (ctx->sc_host->bad_symbol)
-        return fail(ctx, GDCA_EINVAL, "alignment holds a symbol outside 1..q%s%s", "", "");
-    return GDCA_OK;
-}
-
 gdca_status gdca_pair_identity_sum_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, uint64_t *out)
 {
     CHK(validate(ctx, N, M, 2));
@@ -2472,7 +2471,7 @@ gdca_status gdca_neighbour_counts_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_
     CHK(weights_stage(ctx, Z_dev, N, M, GDCA_MAXQ, 0.0, thresh, false));
     HIPCHK(hipMemcpyAsync(n_dev, ctx->nk.p, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
     CHK(fetch_scalars(ctx));
-    return symbols_ok(ctx);
+    return conclude(ctx, GDCA_ENDS_FRONT);
 }
 
 gdca_status gdca_compute_weights_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, double theta,
@@ -2487,7 +2486,7 @@ gdca_status gdca_compute_weights_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t
     *Meff = ctx->sc_host->Meff;
     if (theta_used) *theta_used = ctx->sc_host->theta;
     if (thresh) *thresh = ctx->sc_host->thresh;
-    return symbols_ok(ctx);
+    return conclude(ctx, GDCA_ENDS_FRONT);
 }
 
 gdca_status gdca_frequencies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q,
@@ -2506,8 +2505,8 @@ gdca_status gdca_frequencies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, 
     gdca_launch_fix_weights(s, W_dev, M, gdca_fix_shift(M), (unsigned long long *)ctx->Wfix.p, sc);
     CHK(tally_stage(ctx, Z_dev, N, M, q, &sc->Meff, 0.0, 0, Pi_dev, Pij_dev, (size_t)n));
     CHK(fetch_scalars(ctx));
-    if (ctx->sc_host->bad_symbol & 2) return fail(ctx, GDCA_EINVAL, "weights must lie in [0, 1]%s%s", "", "");
-    return symbols_ok(ctx);
+    if (ctx->sc_host->bad_symbol & GDCA_BAD_WEIGHT) return fail(ctx, GDCA_EINVAL, "weights must lie in [0, 1]");
+    return conclude(ctx, GDCA_ENDS_FRONT);
 }
 
 gdca_status gdca_add_pseudocount_dev(gdca_ctx *ctx, const double *Pi_true_dev, const double *Pij_true_dev, int32_t N,
@@ -2528,85 +2527,43 @@ gdca_status gdca_covariance_dev(gdca_ctx *ctx, const double *Pi_dev, const doubl
     return check_launch(ctx, "covariance");
 }
 
-// operator-level inverse: kappa_1 = ||C||_1 ||X||_1 (the caller's matrix is still in A_dev) and, beyond the threshold, one
-// Newton-Schulz step before the result is copied out.  Synchronises (the caller of an operator waits for `info` anyway).
-static gdca_status operator_norms_and_refine(gdca_ctx *ctx, const double *A_dev, int n, int n_pad)
+// The operator-level inverse of the caller's matrix: a first attempt is enqueued on the context's stream (its matrix copied into ctx->A,
+// pend.n / pend.n_pad set) -- the log det of its pivots behind it, the scalars fetched, the ladder with up to `retries` further
+// attempts, and the result copied out.  Not where the watchdog had the last word: the caller's matrix stays as it is.
+static gdca_status operator_ladder(gdca_ctx *ctx, double *A_dev, int retries, bool first)
 {
-    if (ctx->tune.refine == 0) return GDCA_OK;
-    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
-    CHK(ensure(ctx, ctx->normws, (size_t)n_pad * sizeof(double)));
-    gdca_launch_matrix_norm1(ctx->stream, A_dev, (size_t)n, n, (double *)ctx->normws.p, &sc->mat_norm1);
-    CHK(inverse_norm_stage(ctx, n, n_pad));
-    CHK(fetch_scalars(ctx));
-    if (!wants_refinement(ctx, *ctx->sc_host)) return GDCA_OK;
-    const size_t mat = (size_t)n_pad * n_pad * sizeof(double);
-    CHK(ensure(ctx, ctx->C2, mat));
-    CHK(ensure(ctx, ctx->B0, mat));
-    CHK(ensure(ctx, ctx->Rt, mat));
-    gdca_launch_copy_in(ctx->stream, A_dev, n, (double *)ctx->C2.p, n_pad);
-    gdca_launch_newton_schulz(ctx->stream, (double *)ctx->A.p, (const double *)ctx->C2.p, (double *)ctx->B0.p, (double *)ctx->Rt.p, n_pad,
-                              &sc->ns_resid);
-    return check_launch(ctx, "newton_schulz");
-}
-
-// ... and the Cholesky fallback where the sweep gave up (non-positive pivot) or the step above cannot have converged.  Leaves the
-// member's scalars fetched (sc_host) and its stream idle.
-static gdca_status operator_fallback(gdca_ctx *ctx, const double *A_dev, int n, int n_pad)
-{
-    CHK(fetch_scalars(ctx));
-    if (!wants_cholesky(ctx, *ctx->sc_host, ctx->sc_host->ns_resid >= 1.0 ? -1 : 0)) return GDCA_OK;
-    CHK(ensure(ctx, ctx->C2, (size_t)n_pad * n_pad * sizeof(double)));
-    gdca_launch_copy_in(ctx->stream, A_dev, n, (double *)ctx->C2.p, n_pad);
-    CHK(cholesky_stage(ctx, n, n_pad));
-    CHK(logdet_stage(ctx, n));  // (of the factor's diagonal)
-    return fetch_scalars(ctx);
-}
-
-// the operator-level inverse of the caller's matrix (still intact: the sweep works on a copy), start to finish on the context's stream;
-// the context's scalars are in sc_host afterwards
-static gdca_status operator_inverse_once(gdca_ctx *ctx, double *A_dev, int n, int n_pad)
-{
-    hipStream_t s = ctx->stream;
-    CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
-    gdca_launch_copy_in(s, A_dev, n, (double *)ctx->A.p, n_pad);
-    CHK(inverse_stage(ctx, n, n_pad, nullptr));
-    CHK(logdet_stage(ctx, n));
-    CHK(operator_norms_and_refine(ctx, A_dev, n, n_pad));
-    CHK(operator_fallback(ctx, A_dev, n, n_pad));
-    if (ctx->sc_host->info == INT32_MIN) return GDCA_OK;  // (the watchdog: the caller's matrix stays as it is)
-    gdca_launch_copy_out_neg_sym(s, (const double *)ctx->A.p, n_pad, A_dev, n);
+    if (first) {
+        CHK(logdet_stage(ctx, ctx->pend.n));
+        CHK(fetch_scalars(ctx));
+    }
+    CHK(inverse_ladder(ctx, inverse_source{GDCA_FORM_OPERATOR, A_dev}, retries));
+    if (ctx->sc_host->info == GDCA_INFO_WATCHDOG) return GDCA_OK;
+    gdca_launch_copy_out_neg_sym(ctx->stream, (const double *)ctx->A.p, ctx->pend.n_pad, A_dev, ctx->pend.n);
     CHK(check_launch(ctx, "copy_out"));
-    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return GDCA_OK;
 }
 
-// ... once more after a launch the watchdog ended (gdca_run_collect has the why), up to option SWEEP_RETRIES times
-static gdca_status operator_inverse_retry(gdca_ctx *ctx, double *A_dev, int n, int n_pad)
+static gdca_status operator_copy_in(gdca_ctx *ctx, const double *A_dev, int n)
 {
-    while (ctx->sc_host->info == INT32_MIN && ctx->pend.at.attempt < ctx->tune.sweep_retries) {
-        ++ctx->pend.at.attempt;
-        HIPCHK(hipMemsetAsync(&((gdca_dev_scalars *)ctx->sc.p)->info, 0, sizeof(int), ctx->stream));
-        CHK(operator_inverse_once(ctx, A_dev, n, n_pad));
-    }
+    const int n_pad = round_up(n, GDCA_TILE);
+    CHK(begin(ctx));
+    CHK(ensure(ctx, ctx->A, (size_t)n_pad * n_pad * sizeof(double)));
+    gdca_launch_copy_in(ctx->stream, A_dev, n, (double *)ctx->A.p, n_pad);
+    ctx->pend.n = n;
+    ctx->pend.n_pad = n_pad;
     return GDCA_OK;
 }
 
 gdca_status gdca_spd_inverse_dev(gdca_ctx *ctx, double *A_dev, int32_t n, int32_t *info)
 {
     if (!ctx || !A_dev || n < 1 || n > GDCA_MAX_N) return GDCA_EINVAL;
-    CHK(begin(ctx));
-    const int n_pad = round_up(n, GDCA_TILE);
-    CHK(operator_inverse_once(ctx, A_dev, n, n_pad));
-    CHK(operator_inverse_retry(ctx, A_dev, n, n_pad));
+    CHK(operator_copy_in(ctx, A_dev, n));
+    CHK(inverse_stage(ctx, n, ctx->pend.n_pad, nullptr));
+    CHK(operator_ladder(ctx, A_dev, ctx->tune.sweep_retries, true));
     note_logdet(ctx);
-    if (ctx->sc_host->info == INT32_MIN) {
-        if (info) *info = 0;
-        return fail(ctx, GDCA_EHIP, "SPD inverse aborted: a dependency wait inside the sweep kernel timed out%s%s", "", "");
-    }
-    if (info) *info = ctx->sc_host->info;
-    if (ctx->sc_host->info != 0)
-        return fail(ctx, GDCA_ENOTPD, "matrix is not positive definite; Cholesky factorization failed%s%s", "", "");
-    return GDCA_OK;
+    if (info) *info = ctx->sc_host->info == GDCA_INFO_WATCHDOG ? 0 : ctx->sc_host->info;
+    return conclude(ctx, GDCA_ENDS_INVERSE);
 }
 
 gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double *const *A_dev, const int32_t *n, int32_t *info)
@@ -2616,10 +2573,10 @@ gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double 
     if (!lead) return GDCA_EINVAL;
     gdca_ctx *ctx = lead;
     for (int k = 0; k < K; ++k) {
-        if (!ctxs[k] || !A_dev[k] || n[k] < 1 || n[k] > GDCA_MAX_N) return fail(lead, GDCA_EINVAL, "invalid member of the batch%s%s", "", "");
+        if (!ctxs[k] || !A_dev[k] || n[k] < 1 || n[k] > GDCA_MAX_N) return fail(lead, GDCA_EINVAL, "invalid member of the batch");
         for (int j = 0; j < k; ++j)
-            if (ctxs[j] == ctxs[k]) return fail(lead, GDCA_EINVAL, "the same context twice in one batch%s%s", "", "");
-        if (ctxs[k]->device != lead->device) return fail(lead, GDCA_EINVAL, "contexts of one batch must share a device%s%s", "", "");
+            if (ctxs[j] == ctxs[k]) return fail(lead, GDCA_EINVAL, "the same context twice in one batch");
+        if (ctxs[k]->device != lead->device) return fail(lead, GDCA_EINVAL, "contexts of one batch must share a device");
         CHK(not_pending(ctxs[k]));
         if (info) info[k] = 0;
     }
@@ -2631,50 +2588,28 @@ gdca_status gdca_spd_inverse_batch_dev(gdca_ctx *const *ctxs, int32_t K, double 
         ctxs[k]->stream = lead->stream;
     }
     gdca_status st = GDCA_OK;
-    for (int k = 0; k < K && st == GDCA_OK; ++k) {
-        gdca_ctx *m = ctxs[k];
-        const int n_pad = round_up(n[k], GDCA_TILE);
-        st = begin(m);
-        if (st == GDCA_OK) st = ensure(m, m->A, (size_t)n_pad * n_pad * sizeof(double));
-        if (st != GDCA_OK) {
-            member_error(lead, m, k, st);
-            break;
-        }
-        gdca_launch_copy_in(lead->stream, A_dev[k], n[k], (double *)m->A.p, n_pad);
-        m->pend.n = n[k];
-        m->pend.n_pad = n_pad;
-    }
+    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_copy_in(ctxs[k], A_dev[k], n[k]));
     if (st == GDCA_OK) st = run_inverses(lead, ctxs, K);
-    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, logdet_stage(ctxs[k], n[k]));
-    // kappa_1 and, where it is beyond the threshold, the Newton-Schulz step: member by member, as gdca_spd_inverse_dev does (the
-    // caller's matrices are still intact; each member's switches are its own context's)
-    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_norms_and_refine(ctxs[k], A_dev[k], n[k], ctxs[k]->pend.n_pad));
-    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_fallback(ctxs[k], A_dev[k], n[k], ctxs[k]->pend.n_pad));
-    for (int k = 0; k < K && st == GDCA_OK; ++k) {
-        if (ctxs[k]->sc_host->info == INT32_MIN) continue;  // (the watchdog ended this member's launch: see below)
-        gdca_launch_copy_out_neg_sym(lead->stream, (const double *)ctxs[k]->A.p, ctxs[k]->pend.n_pad, A_dev[k], n[k]);
-        st = check_launch(lead, "copy_out");
-    }
+    // the ladder member by member on the leader's stream, as gdca_spd_inverse_dev walks it (the caller's matrices are still intact; each
+    // member's switches are its own context's) -- but for the further attempts of a launch the watchdog ended: see below
+    for (int k = 0; k < K && st == GDCA_OK; ++k) st = member_error(lead, ctxs[k], k, operator_ladder(ctxs[k], A_dev[k], 0, true));
     (void)hipStreamSynchronize(lead->stream);
     for (int k = 0; k < K; ++k) ctxs[k]->stream = own[k];
-    if (st != GDCA_OK) return st;
-    // members whose launch the watchdog ended (all members of a merged launch share that fate): once more, one by one
-    for (int k = 0; k < K && st == GDCA_OK; ++k)
-        if (ctxs[k]->sc_host->info == INT32_MIN) st = member_error(lead, ctxs[k], k, operator_inverse_retry(ctxs[k], A_dev[k], n[k], ctxs[k]->pend.n_pad));
-    if (st != GDCA_OK) return st;
-    gdca_status worst = GDCA_OK;
-    for (int k = 0; k < K; ++k) {
+    // members whose launch the watchdog ended (all members of a merged launch share that fate): once more, one by one, each on its own stream
+    for (int k = 0; k < K && st == GDCA_OK; ++k) {
         gdca_ctx *m = ctxs[k];
-        note_logdet(m);
-        const int inf = m->sc_host->info;   // (fetched by operator_fallback)
-        if (inf == INT32_MIN)
-            worst = fail(lead, GDCA_EHIP, "SPD inverse aborted: a dependency wait inside the sweep kernel timed out%s%s", "", "");
-        else if (inf != 0) {
-            if (info) info[k] = inf;
-            if (worst == GDCA_OK) worst = fail(lead, GDCA_ENOTPD, "matrix is not positive definite; Cholesky factorization failed%s%s", "", "");
-        }
+        if (m->sc_host->info == GDCA_INFO_WATCHDOG) st = member_error(lead, m, k, operator_ladder(m, A_dev[k], m->tune.sweep_retries, false));
     }
-    return worst;
+    if (st != GDCA_OK) return st;
+    gdca_verdict worst{GDCA_OK, nullptr};
+    for (int k = 0; k < K; ++k) {
+        note_logdet(ctxs[k]);
+        const int inf = ctxs[k]->sc_host->info;
+        const gdca_verdict v = gdca_verdict_of(GDCA_ENDS_INVERSE, 0, inf, 0);
+        if (v.status == GDCA_ENOTPD && info) info[k] = inf;
+        worst = gdca_worse_verdict(worst, v);
+    }
+    return worst.status == GDCA_OK ? GDCA_OK : fail(lead, worst.status, worst.text);
 }
 
 // mJ (device, n x n full, ld n) -> ctx->A as "-mJ" with ld = n_pad (the score kernels read its lower triangle)
@@ -2712,7 +2647,7 @@ gdca_status gdca_di_dev(gdca_ctx *ctx, const double *mJ_dev, const double *C_dev
     CHK(score_stage(ctx, N, sdim, n_pad, contact_target(GDCA_SCORE_DI, 0, S_dev)));
     CHK(fetch_scalars(ctx));
     if (ctx->sc_host->di_noconv)
-        return fail(ctx, GDCA_ENOCONV, "eigenvalue iteration of a DI block did not converge%s%s", "", "");
+        return fail(ctx, GDCA_ENOCONV, GDCA_TEXT_DI_NOCONV);
     return GDCA_OK;
 }
 
@@ -2727,9 +2662,7 @@ static gdca_model operator_model(const double *mJ_dev, const double *Pi_dev, int
 static gdca_status sequences_checked(gdca_ctx *ctx)
 {
     CHK(fetch_scalars(ctx));
-    if (ctx->sc_host->bad_symbol & 16) return fail(ctx, GDCA_EINVAL, "a double-mutant record is out of range%s%s", "", "");
-    if (ctx->sc_host->bad_symbol) return fail(ctx, GDCA_EINVAL, "sequences hold a symbol outside 1..q%s%s", "", "");
-    return GDCA_OK;
+    return conclude(ctx, GDCA_ENDS_READOUT);
 }
 
 // the fused form of the energy entries, their own arguments checked: gdca_run's front end and inverse, then the stage `t` names in
@@ -2754,7 +2687,7 @@ static gdca_status run_target(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int
 static gdca_status check_energies(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *X, int K, const void *E)
 {
     CHK(validate(ctx, N, K, q));
-    if (!mJ || !Pi || !X || !E) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!mJ || !Pi || !X || !E) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -2762,8 +2695,8 @@ static gdca_status check_run_energies(gdca_ctx *ctx, const void *Z, int N, int M
                                       const void *E)  // ... and gdca_run_loglik
 {
     CHK(validate(ctx, N, M, q));
-    if (!Z || !E || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (X && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (!Z || !E || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (X && K < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
     return GDCA_OK;
 }
 
@@ -2786,10 +2719,10 @@ gdca_status gdca_run_energies_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N,
 gdca_status gdca_last_logdet(gdca_ctx *ctx, int32_t k, double *logdet, int32_t *source)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (!logdet) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!logdet) return fail(ctx, GDCA_EINVAL, "null pointer");
     CHK(not_pending(ctx));
-    if (ctx->ld.count == 0) return fail(ctx, GDCA_EINVAL, "no SPD inverse has been completed on this context%s%s", "", "");
-    if (k < 0 || k >= ctx->ld.count) return fail(ctx, GDCA_EINVAL, "member index out of range%s%s", "", "");
+    if (ctx->ld.count == 0) return fail(ctx, GDCA_EINVAL, "no SPD inverse has been completed on this context");
+    if (k < 0 || k >= ctx->ld.count) return fail(ctx, GDCA_EINVAL, "member index out of range");
     *logdet = ctx->ld.val[k];
     if (source) *source = ctx->ld.src[k];
     return GDCA_OK;
@@ -2818,9 +2751,9 @@ gdca_status gdca_run_loglik_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, i
 static gdca_status validate_pair(gdca_ctx *ctx, int N, int q, int split, long long KA, long long KB, int what)
 {
     CHK(validate(ctx, N, 1, q));
-    if (split < 1 || split > N - 1) return fail(ctx, GDCA_EINVAL, "invalid split (must be between 1 and N - 1)%s%s", "", "");
-    if (KA < 1 || KB < 1 || KA + KB > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    if (what != GDCA_PAIR_COUPLING && what != GDCA_PAIR_ENERGY) return fail(ctx, GDCA_EINVAL, "invalid value of `what`%s%s", "", "");
+    if (split < 1 || split > N - 1) return fail(ctx, GDCA_EINVAL, "invalid split (must be between 1 and N - 1)");
+    if (KA < 1 || KB < 1 || KA + KB > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
+    if (what != GDCA_PAIR_COUPLING && what != GDCA_PAIR_ENERGY) return fail(ctx, GDCA_EINVAL, "invalid value of `what`");
     return GDCA_OK;
 }
 
@@ -2828,7 +2761,7 @@ static gdca_status check_pair_energies(gdca_ctx *ctx, const void *mJ, const void
                                        const void *XB, int KB, int what, const void *E)  // ... and the blocked form, before its species
 {
     CHK(validate_pair(ctx, N, q, split, KA, KB, what));
-    if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!mJ || !XA || !XB || !E || (what == GDCA_PAIR_ENERGY && !Pi)) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -2838,7 +2771,7 @@ static gdca_status check_run_pair(gdca_ctx *ctx, const void *Z, int N, int M, in
 {
     CHK(validate(ctx, N, M, q));
     CHK(validate_pair(ctx, N, q, split, XA ? KA : M, XB ? KB : M, what));
-    if (!Z || !out || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Z || !out || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -2885,18 +2818,18 @@ int64_t gdca_pair_blocks_length(const int32_t *offA, const int32_t *offB, int32_
 static gdca_status check_blocks(gdca_ctx *ctx, const void *offA, const void *offB, int S, long long KA, long long KB, long long *total,
                                 int *kmax = nullptr)
 {
-    if (!offA || !offB) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!offA || !offB) return fail(ctx, GDCA_EINVAL, "null pointer");
     *total = blocks_length((const int32_t *)offA, (const int32_t *)offB, S, kmax);
     if (*total < 0 || ((const int32_t *)offA)[S] != KA || ((const int32_t *)offB)[S] != KB)
-        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
+        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)");
     return GDCA_OK;
 }
 
 static gdca_status check_assign_blocks(gdca_ctx *ctx, const void *E, const void *offA, const void *offB, int S, const void *match)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (!E || !offA || !offB || !match) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (S < 1) return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1)%s%s", "", "");
+    if (!E || !offA || !offB || !match) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (S < 1) return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1)");
     return GDCA_OK;
 }
 
@@ -2906,7 +2839,7 @@ static gdca_status check_run_partner(gdca_ctx *ctx, const void *Z, int N, int M,
 {
     CHK(validate(ctx, N, M, q));
     CHK(validate_pair(ctx, N, q, split, ka, kb, what));
-    if (!Z || !match || !offA || !offB || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Z || !match || !offA || !offB || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -2920,8 +2853,7 @@ static gdca_status species_blocks(gdca_ctx *ctx, const void *offA_, const void *
     int kmax = 0;
     long long total = 0;
     CHK(check_blocks(ctx, offA, offB, S, KA, KB, &total, &kmax));
-    if (assign && kmax > GDCA_ASSIGN_MAX)
-        return fail(ctx, GDCA_EINVAL, "a species has more than GDCA_ASSIGN_MAX sequences on one side%s%s", "", "");
+    if (assign && kmax > GDCA_ASSIGN_MAX) return fail(ctx, GDCA_EINVAL, "a species has more than GDCA_ASSIGN_MAX sequences on one side");
     CHK(not_pending(ctx));
     HIPCHK(hipSetDevice(ctx->device));
     const size_t S1 = (size_t)S + 1;
@@ -3021,7 +2953,7 @@ static gdca_status check_pair_logodds(gdca_ctx *ctx, const void *mJ, const void 
                                       const void *XA, int KA, const void *XB, int KB, const void *L)  // ... and the blocked form, before its species
 {
     CHK(validate_pair(ctx, N, q, split, KA, KB, GDCA_PAIR_ENERGY));
-    if (!mJ || !mJA || !mJB || !Pi || !XA || !XB || !L) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!mJ || !mJA || !mJB || !Pi || !XA || !XB || !L) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -3205,8 +3137,8 @@ static gdca_status fetch_counts(gdca_ctx *ctx, gdca_ipa_counts *h)
 static gdca_status check_select_confident(gdca_ctx *ctx, const void *match, const void *gap, int KA, const void *sel)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (!match || !gap || !sel) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (KA < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (!match || !gap || !sel) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (KA < 1) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
     return GDCA_OK;
 }
 
@@ -3228,9 +3160,9 @@ static gdca_status validate_concat(gdca_ctx *ctx, const void *XA, int KA, const 
                                    const void *selB, int n_sel, const void *Z, long long col0)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (N < 2 || split < 1 || split > N - 1) return fail(ctx, GDCA_EINVAL, "invalid split (must be between 1 and N - 1)%s%s", "", "");
-    if (KA < 1 || KB < 1 || n_sel < 0 || col0 < 0 || col0 + n_sel > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    if (!XA || !XB || !Z || (n_sel > 0 && (!selA || !selB))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (N < 2 || split < 1 || split > N - 1) return fail(ctx, GDCA_EINVAL, "invalid split (must be between 1 and N - 1)");
+    if (KA < 1 || KB < 1 || n_sel < 0 || col0 < 0 || col0 + n_sel > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
+    if (!XA || !XB || !Z || (n_sel > 0 && (!selA || !selB))) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -3243,7 +3175,7 @@ gdca_status gdca_concat_pairs_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_t K
                            (gdca_dev_scalars *)ctx->sc.p);
     CHK(check_launch(ctx, "concatenation"));
     CHK(fetch_scalars(ctx));
-    if (ctx->sc_host->bad_symbol & 8) return fail(ctx, GDCA_EINVAL, "a selected index is outside its pool%s%s", "", "");
+    if (ctx->sc_host->bad_symbol & GDCA_BAD_INDEX) return fail(ctx, GDCA_EINVAL, "a selected index is outside its pool");
     return GDCA_OK;
 }
 
@@ -3259,19 +3191,17 @@ static gdca_status ipa_check(gdca_ctx *ctx, int32_t KA, int32_t KB, const void *
                              ipa_plan *plan)
 {
     if (!ctx) return GDCA_EINVAL;
-    if (Mfix < 0 || n_seed < 0 || (long long)Mfix + n_seed < 1)
-        return fail(ctx, GDCA_EINVAL, "no training pairs: Zfix and the seed are both empty%s%s", "", "");
-    if (n_inc < 1 || max_rounds < 1) return fail(ctx, GDCA_EINVAL, "n_inc and max_rounds must be at least 1%s%s", "", "");
+    if (Mfix < 0 || n_seed < 0 || (long long)Mfix + n_seed < 1) return fail(ctx, GDCA_EINVAL, "no training pairs: Zfix and the seed are both empty");
+    if (n_inc < 1 || max_rounds < 1) return fail(ctx, GDCA_EINVAL, "n_inc and max_rounds must be at least 1");
     CHK(validate_pair(ctx, N, q, split, KA, KB, what));
-    if ((long long)Mfix + KA > INT32_MAX || (long long)Mfix + n_seed > INT32_MAX)
-        return fail(ctx, GDCA_EINVAL, "invalid alignment size%s%s", "", "");
-    if (!offA_ || !offB_ || !p || (n_seed > 0 && (!seedA || !seedB))) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if ((long long)Mfix + KA > INT32_MAX || (long long)Mfix + n_seed > INT32_MAX) return fail(ctx, GDCA_EINVAL, "invalid alignment size");
+    if (!offA_ || !offB_ || !p || (n_seed > 0 && (!seedA || !seedB))) return fail(ctx, GDCA_EINVAL, "null pointer");
     CHK(check_params(ctx, p));
     const int32_t *offA = (const int32_t *)offA_, *offB = (const int32_t *)offB_;
     int kmax = 0;
     if (blocks_length(offA, offB, S, &kmax) < 0 || offA[S] != KA || offB[S] != KB)
-        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)%s%s", "", "");
-    if (kmax > GDCA_ASSIGN_MAX) return fail(ctx, GDCA_EINVAL, "a species has more than GDCA_ASSIGN_MAX sequences on one side%s%s", "", "");
+        return fail(ctx, GDCA_EINVAL, "invalid species offsets (S >= 1; from 0, non-decreasing, up to the number of sequences)");
+    if (kmax > GDCA_ASSIGN_MAX) return fail(ctx, GDCA_EINVAL, "a species has more than GDCA_ASSIGN_MAX sequences on one side");
     plan->spA.assign((size_t)KA, 0);
     std::vector<int32_t> spB((size_t)KB, 0);
     for (int s = 0; s < S; ++s) {
@@ -3282,9 +3212,9 @@ static gdca_status ipa_check(gdca_ctx *ctx, int32_t KA, int32_t KB, const void *
     std::vector<std::pair<int32_t, int32_t>> seed;
     for (int t = 0; t < n_seed; ++t) {
         const int32_t a = seedA[t], b = seedB[t];
-        if (a < 0 || a >= KA || b < 0 || b >= KB) return fail(ctx, GDCA_EINVAL, "a seed index is outside its pool%s%s", "", "");
-        if (plan->spA[(size_t)a] != spB[(size_t)b]) return fail(ctx, GDCA_EINVAL, "a seed pair joins two species%s%s", "", "");
-        if (usedA[(size_t)a] || usedB[(size_t)b]) return fail(ctx, GDCA_EINVAL, "a sequence appears twice in the seed%s%s", "", "");
+        if (a < 0 || a >= KA || b < 0 || b >= KB) return fail(ctx, GDCA_EINVAL, "a seed index is outside its pool");
+        if (plan->spA[(size_t)a] != spB[(size_t)b]) return fail(ctx, GDCA_EINVAL, "a seed pair joins two species");
+        if (usedA[(size_t)a] || usedB[(size_t)b]) return fail(ctx, GDCA_EINVAL, "a sequence appears twice in the seed");
         usedA[(size_t)a] = usedB[(size_t)b] = 1;
         seed.emplace_back(a, b);
     }
@@ -3293,7 +3223,7 @@ static gdca_status ipa_check(gdca_ctx *ctx, int32_t KA, int32_t KB, const void *
         plan->seedA.push_back(ab.first);
         plan->seedB.push_back(ab.second);
     }
-    if (!XA || !XB || !match || (Mfix > 0 && !Zfix)) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!XA || !XB || !match || (Mfix > 0 && !Zfix)) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -3340,7 +3270,7 @@ gdca_status gdca_run_partner_ipa_dev(gdca_ctx *ctx, const int8_t *XA_dev, int32_
     const bool timed = ctx->timing && rounds_out;
     if (timed && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) {
         if (ev0) (void)hipEventDestroy(ev0);
-        return fail(ctx, GDCA_EHIP, "hipEventCreate%s%s", "", "");
+        return fail(ctx, GDCA_EHIP, "hipEventCreate");
     }
     gdca_status rs = GDCA_OK;
     int M = Mfix + n_seed, sel_before = -1, cand_before = -2;
@@ -3416,15 +3346,15 @@ static gdca_status validate_mutation(gdca_ctx *ctx, int N, int q, long long K, i
 {
     CHK(validate(ctx, N, 1, q));
     // (the grids round K up to whole workgroups of 256 sequences in 32-bit arithmetic)
-    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
-    if (what != GDCA_MUT_DELTA && what != GDCA_MUT_POTENTIAL) return fail(ctx, GDCA_EINVAL, "invalid value of `what`%s%s", "", "");
+    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
+    if (what != GDCA_MUT_DELTA && what != GDCA_MUT_POTENTIAL) return fail(ctx, GDCA_EINVAL, "invalid value of `what`");
     return GDCA_OK;
 }
 
 static gdca_status check_mutation_scan(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *X, int K, int what, const void *D)
 {
     CHK(validate_mutation(ctx, N, q, K, what));
-    if (!mJ || !Pi || !X || !D) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!mJ || !Pi || !X || !D) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -3433,7 +3363,7 @@ static gdca_status check_run_mutation_scan(gdca_ctx *ctx, const void *Z, int N, 
 {
     CHK(validate(ctx, N, M, q));
     CHK(validate_mutation(ctx, N, q, X ? K : M, what));
-    if (!Z || !D || !p) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (!Z || !D || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -3457,10 +3387,10 @@ gdca_status gdca_run_mutation_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32
 static gdca_status validate_double(gdca_ctx *ctx, int N, int q, long long K)
 {
     CHK(validate(ctx, N, 1, q));
-    if (N < 2) return fail(ctx, GDCA_EINVAL, "a double mutant needs two sites%s%s", "", "");
-    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences%s%s", "", "");
+    if (N < 2) return fail(ctx, GDCA_EINVAL, "a double mutant needs two sites");
+    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
     const long long nT = (N + 3) / 4;
-    if ((K + 63) / 64 * (nT * (nT + 1) / 2) > GDCA_EPI_MAX_GROUPS) return fail(ctx, GDCA_EINVAL, "N^2 K is too large for one scan%s%s", "", "");
+    if ((K + 63) / 64 * (nT * (nT + 1) / 2) > GDCA_EPI_MAX_GROUPS) return fail(ctx, GDCA_EINVAL, "N^2 K is too large for one scan");
     return GDCA_OK;
 }
 
@@ -3471,8 +3401,8 @@ static gdca_status check_double_scan(gdca_ctx *ctx, const void *a, const void *b
 {
     CHK(validate(ctx, N, M, q));
     CHK(validate_double(ctx, N, q, K));
-    if (!a || !b || !X) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
-    if (!Emin && !code && !epi) return fail(ctx, GDCA_EINVAL, "no output requested%s%s", "", "");
+    if (!a || !b || !X) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (!Emin && !code && !epi) return fail(ctx, GDCA_EINVAL, "no output requested");
     return GDCA_OK;
 }
 
@@ -3481,8 +3411,8 @@ static gdca_status check_double_list(gdca_ctx *ctx, const void *a, const void *b
 {
     CHK(validate(ctx, N, M, q));
     CHK(validate_double(ctx, N, q, K));
-    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants%s%s", "", "");
-    if (!a || !b || !X || !muts || !out) return fail(ctx, GDCA_EINVAL, "null pointer%s%s", "", "");
+    if (L < 1) return fail(ctx, GDCA_EINVAL, "invalid number of double mutants");
+    if (!a || !b || !X || !muts || !out) return fail(ctx, GDCA_EINVAL, "null pointer");
     return GDCA_OK;
 }
 
@@ -4027,7 +3957,7 @@ gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)
     HIPCHK(hipStreamSynchronize(s));
     bool tfail = false;
     const double ms = elapsed(ctx, T_BEGIN, T_END, &tfail);
-    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime%s%s", "", "");
+    if (tfail) return fail(ctx, GDCA_EHIP, "hipEventElapsedTime");
     const double flops = (double)blocks * 4.0 * (double)((iters + 1) / 2) * 16.0 * 2.0 * 16 * 16 * 4;  // 16 MFMAs per trip
     *tflops = flops / (ms * 1e-3) / 1e12;
     return GDCA_OK;

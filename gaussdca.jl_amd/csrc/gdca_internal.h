@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gdca.h"
+#include "gdca_inverse_outcome.h"
 
 #define GDCA_TILE 128     // tile edge of the SPD-inverse kernels (f64 elements)
 #define GDCA_HTILE 128    // sequences per side of a Hamming tile
@@ -31,8 +32,7 @@ struct gdca_dev_scalars {
     unsigned long long pair_sum;
     int thresh;
     int info;
-    int bad_symbol;  // bit 0: a byte of Z is outside 1..q; bit 1: a caller-given weight is outside [0, 1]; bit 2: a byte of the scored sequences is
-                     // outside 1..q; bit 3: an index of gdca_concat_pairs is outside its pool; bit 4: a record of gdca_double_mutants is out of range (GDCA_EINVAL)
+    int bad_symbol;  // what the kernels found wrong with the caller's data, one bit a kind: the GDCA_BAD_* of gdca_inverse_outcome.h (GDCA_EINVAL)
     int di_noconv;   // number of site pairs whose tridiagonal QL iteration did not converge (DI score)
     int ham_mode;    // all-pairs Hamming kernel chosen for this family: 0 = exact distances, 1 = three-plane lower bound + refinement, 2 = the consensus
                      // lower bound on the fp4 matrix pipe + refinement (k_hamming_fp4.hip)
@@ -139,7 +139,7 @@ void gdca_launch_fix_weights(hipStream_t s, const double *W, int M, int fix_shif
 int gdca_fix_shift(int M);
 
 // ---- k_tally.hip -------------------------------------------------------------------------
-// Pifix: u64 [N][32], every entry written: sum_k Wfix[k] [Z[i,k] & 31 == z] at [i][z] (bytes outside 1..q set bit 0 of sc->bad_symbol).
+// Pifix: u64 [N][32], every entry written: sum_k Wfix[k] [Z[i,k] & 31 == z] at [i][z] (bytes outside 1..q raise GDCA_BAD_ALIGNMENT in sc->bad_symbol).
 // Zt: Z transposed (N rows of M; 4-byte aligned, 3 bytes of slack behind it).  keep != nullptr (TALLY_SKIP): also keep (uint32
 // [N][M]; per column i: keep_n[i] entries (k << 5) | Z[i,k], ascending k, every sequence whose Z[i,k] is a legal symbol other than
 // sigma[i] = the argmax of Pifix[i][1..q], ties to the smallest), keep_n and sigma
@@ -202,7 +202,7 @@ struct gdca_inverse_ws {
     int update_cus;    // compute units of the device
 };
 // One inverse: in place on A (n_pad x n_pad, ld = n_pad, lower triangle + full diagonal tiles authoritative): A <- -inverse(A) by
-// the block symmetric sweep.  sc->info gets the 1-based index of the first non-positive pivot, if any (INT_MIN: the kernel's
+// the block symmetric sweep.  sc->info gets the 1-based index of the first non-positive pivot, if any (GDCA_INFO_WATCHDOG: the kernel's
 // watchdog abandoned a dependency wait).
 struct gdca_inverse_job {
     double *A;
@@ -290,7 +290,7 @@ int gdca_energy_blocks(int Ns);       // site blocks (of four sites = one packed
 int gdca_energy_gblocks(int n);       // 64-blocks of the g pass
 int gdca_energy_chunk(int N, int K, int wanted);  // sequences one launch of the gather kernel takes (wanted > 0: that many)
 // Xg: uint32 [gdca_energy_blocks(Ns)][K] from the Ns sites X points at (sequence k: X + k * stride; whole sequences: stride = Ns = N);
-// bytes outside 1..q set bit 2 of sc->bad_symbol (and count as gaps)
+// bytes outside 1..q raise GDCA_BAD_SEQUENCE in sc->bad_symbol (and count as gaps)
 void gdca_launch_energy_pack(hipStream_t s, const int8_t *X, size_t stride, int Ns, int K, int q, uint32_t *Xg, gdca_dev_scalars *sc);
 // g = mJ Pi (n entries) and c0 = Pi' g from the element-wise lower triangle of A (ld; sign -1: A holds -mJ, the sweep's storage);
 // part: nb x (nb * 64) doubles, nb = gdca_energy_gblocks(n)
@@ -351,7 +351,7 @@ struct gdca_ipa_counts {
 size_t gdca_ipa_select_ws_bytes(int KA);
 void gdca_launch_ipa_select(hipStream_t s, const int32_t *match, const double *gap, int KA, int n_take, void *ws, int32_t *sel, gdca_ipa_counts *out);
 // Columns col0 .. col0 + n_sel - 1 of Z (N rows): XA[:, selA[t]] over XB[:, b], b = viaB ? viaB[selA[t]] : selB[t]; an index outside its
-// pool: bit 3 of sc->bad_symbol, that column left alone
+// pool: GDCA_BAD_INDEX in sc->bad_symbol, that column left alone
 void gdca_launch_ipa_concat(hipStream_t s, const int8_t *XA, int KA, const int8_t *XB, int KB, int N, int split, const int32_t *selA,
                             const int32_t *selB, const int32_t *viaB, int n_sel, int8_t *Z, size_t col0, gdca_dev_scalars *sc);
 // out->cost, out->n_changed of a round's match against the packed blocks E (eoff, offA, offB: the species table; spA[a]: a's species;
@@ -376,6 +376,6 @@ hipError_t gdca_launch_mutation_scan(hipStream_t s, const double *A, size_t ld, 
 // workgroups than GDCA_EPI_MAX_GROUPS, or the dynamic LDS limit could not be raised; nothing was launched
 hipError_t gdca_launch_double_mutant_scan(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, const double *D, int N,
                                           int sdim, int K, double *Emin, int32_t *code, double *epi, bool generic);
-// out[r] = ddE of record r of muts (5 x L int32: k, i, b, j, c); a record out of range: bit 4 of sc->bad_symbol, nothing indexed with it
+// out[r] = ddE of record r of muts (5 x L int32: k, i, b, j, c); a record out of range: GDCA_BAD_MUTANT in sc->bad_symbol, nothing indexed with it
 void gdca_launch_double_mutants(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, const double *D,
                                 const int32_t *muts, long long L, int N, int sdim, int K, double *out, gdca_dev_scalars *sc);

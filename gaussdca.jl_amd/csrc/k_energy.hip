@@ -14,7 +14,7 @@
 //
 // Per sequence that is a gather of N^2 / 2 doubles from a matrix that fits no cache, so the gathers are turned into LDS reads:
 //   k_energy_pack   X [K][N] -> Xg [ceil(N / 4)][K] dwords: the four symbols of a site block as LDS row indices a - 1 (gap, a site
-//                   beyond N and an illegal byte -> s, a row of zeros); illegal bytes are flagged (sc->bad_symbol bit 2) HERE, so
+//                   beyond N and an illegal byte -> s, a row of zeros); illegal bytes are flagged (sc->bad_symbol, GDCA_BAD_SEQUENCE) HERE, so
 //                   nothing downstream can index out of bounds (the one pack kernel: the pair energies and the mutation scan
 //                   pack with it too, the former a range of sites with a stride of its own);
 //   k_energy_gtile / _gfin / _c0   g and c0 in one streaming pass over the lower triangle (64 x 64 tiles, each giving its rows' and,
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_energy_pack(const int8_t *__restrict__ 
         w |= (uint32_t)idx << (8 * l);
     }
     Xg[(size_t)blk * K + k] = w;
-    if (bad) atomicOr(&sc->bad_symbol, 4);
+    if (bad) atomicOr(&sc->bad_symbol, GDCA_BAD_SEQUENCE);
 }
 
 // ---- g = mJ Pi from the lower triangle ----------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@
 //                 stores them together (32 bytes), stages them in LDS, and after a barrier the wave of ROW site i stores the four
 //                 mirror entries [j0 .. j0+3, i, k] together.  (One entry at a time, as first built, the partial lines left the L2
 //                 before their neighbours arrived.)  The diagonal entries come from the diagonal tiles.
-//   k_epi_list    one thread a record (k, i, b, j, c): checked (a bad record sets bit 4 of sc->bad_symbol and indexes nothing), put
+//   k_epi_list    one thread a record (k, i, b, j, c): checked (a bad record raises GDCA_BAD_MUTANT in sc->bad_symbol and indexes nothing), put
 //                 into the orientation i < j, then the same two expressions on five gathers from A and two from dE.
 // dE comes from k_mut_rows in a workspace of q N K doubles (gdca_api.hip).
 // ORDER-FIXED: every entry is computed by ONE thread, the codes ascending, the minimiser the first code that reaches the minimum (what a
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void k_epi_list(const double *__restrict__ A, 
     const int k = m[0], q = sdim + 1;
     int i = m[1], b = m[2], j = m[3], c = m[4];
     if (k < 0 || k >= K || i < 0 || i >= N || j < 0 || j >= N || i == j || b < 1 || b > q || c < 1 || c > q) {
-        atomicOr(&sc->bad_symbol, 16);
+        atomicOr(&sc->bad_symbol, GDCA_BAD_MUTANT);
         out[r] = 0.0;
         return;
     }

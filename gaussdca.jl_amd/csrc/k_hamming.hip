@@ -101,7 +101,7 @@ __global__ __launch_bounds__(128) void k_bitplane_pack(const BatchArgs<k_bitplan
 #pragma unroll
     for (int p = 0; p < NPLANES; ++p)
         Zb[(((size_t)tile * NPLANES + p) * NW + w) * GDCA_HTILE + kl] = pl[p];
-    if (bad) atomicOr(&sc->bad_symbol, 1);
+    if (bad) atomicOr(&sc->bad_symbol, GDCA_BAD_ALIGNMENT);
 }
 
 void gdca_launch_bitplane_pack(hipStream_t s, const int8_t *Z, uint32_t *Zb, int N, int M, int q, gdca_dev_scalars *sc)
@@ -820,7 +820,7 @@ __global__ __launch_bounds__(256) void k_fix_weights(const BatchArgs<k_fix_weigh
     // a weight outside [0, 1] (or NaN) does not fit the 59-bit field of the tally's packed word: flagged (bit 1 of
     // bad_symbol), staged as 0
     const bool ok = w >= 0.0 && w <= 1.0;
-    if (!ok) atomicOr(&sc->bad_symbol, 2);
+    if (!ok) atomicOr(&sc->bad_symbol, GDCA_BAD_WEIGHT);
     Wfix[k] = ok ? (unsigned long long)rint(ldexp(w, fix_shift)) : 0ull;
 }
 

@@ -1137,7 +1137,7 @@ __device__ __forceinline__ void publish_wt_begin()
 // Every dependency wait of the kernel is thread 0 polling a few flags (s_sleep between polls).  A wait that never ends -- a
 // bug in the item order, a workgroup of the launch that was never scheduled, a device fault elsewhere -- would hang the whole
 // GPU behind a C-ABI that promises to return a status.  So a wait is bounded (D.timeout_ticks of the 100 MHz wall clock, seconds:
-// a healthy wait is microseconds): the workgroup that runs out of time sets the device-wide abort word and sc->info = INT_MIN,
+// a healthy wait is microseconds): the workgroup that runs out of time sets the device-wide abort word and sc->info = GDCA_INFO_WATCHDOG,
 // every poll loop also looks at that word, and everybody leaves; the host runs the inverse once more (gdca_run_collect) and maps
 // a second failure to GDCA_EHIP.  The fast path (flags already set) costs nothing; a poll iteration costs one more load.
 //
@@ -1193,7 +1193,7 @@ __device__ __forceinline__ bool spin_until(const SweepDesc &D, F ready)
             if (now - prev > SWEEP_HOLE_TICKS && now - t0 + D.hole_timeout_ticks < limit) limit = now - t0 + D.hole_timeout_ticks;
             if (now - t0 > limit) {
                 __hip_atomic_store(D.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&D.sc->info, (int)0x80000000, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&D.sc->info, GDCA_INFO_WATCHDOG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 return false;
             }
         }
@@ -2496,7 +2496,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep_merged(const SweepBatch Barg)
             // a wait of ANY member ran out of time: this workgroup has dropped its items, so no member's result can be trusted
             if (aborted) {
                 __hip_atomic_store(Dk.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&Dk.sc->info, (int)0x80000000, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&Dk.sc->info, GDCA_INFO_WATCHDOG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }

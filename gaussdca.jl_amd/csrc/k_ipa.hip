@@ -9,7 +9,7 @@
 //               k_ipa_compact   one workgroup: an exclusive scan of the flags (thread t owns a fixed stretch of a, then a fixed scan over
 //                               the 1024 counts), the selected a written in ascending order, -1 behind them; the counts for the host
 //   concat      k_ipa_concat    one thread a byte of the new columns: column col0 + t = XA[:, selA[t]] over XB[:, selB[t]], consecutive
-//                               threads store consecutive bytes; an index outside its pool sets bit 3 of sc->bad_symbol and its column is
+//                               threads store consecutive bytes; an index outside its pool raises GDCA_BAD_INDEX in sc->bad_symbol and its column is
 //                               left alone (nothing is read out of bounds)
 //   a round's   k_ipa_round     one workgroup: the total cost sum_a E[a, match[a]] in f64 -- thread t takes a = t, t + 1024, ... in
 //   figures                     ascending order, then a fixed binary tree, as k_logdet does -- and the number of a whose match changed
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void k_ipa_concat(const int8_t *__restrict__ X
     const bool a_ok = a >= 0 && a < KA;
     const int32_t b = viaB ? (a_ok ? viaB[a] : -1) : selB[t];
     if (!a_ok || b < 0 || b >= KB) {
-        if (i == 0) atomicOr(&sc->bad_symbol, 8);
+        if (i == 0) atomicOr(&sc->bad_symbol, GDCA_BAD_INDEX);
         return;
     }
     Z[(col0 + t) * (size_t)N + i] = i < split ? XA[(size_t)a * split + i] : XB[(size_t)b * (N - split) + (i - split)];

@@ -31,7 +31,7 @@ typedef unsigned long long u64;
 // neighbouring rows and those bytes are masked by their sequence index, so Zt needs 4-byte alignment and 3 bytes of slack.
 //
 // Pass one: Pifix[i][z] = sum_k Wfix[k] [Zt[i][k] & 31 == z] in u64, all 32 of them (bytes outside 1..q land where their low five
-// bits say and set bit 0 of sc->bad_symbol).  The sums are taken in bins[z][lane] in LDS: the lane index makes the 64 lanes of an
+// bits say and raise GDCA_BAD_ALIGNMENT in sc->bad_symbol).  The sums are taken in bins[z][lane] in LDS: the lane index makes the 64 lanes of an
 // ds_add_u64 conflict-free whatever the symbols are, the workgroup's waves share the bins, and nothing waits for an add.  The 64
 // partial sums of a symbol are then added in a fixed order (integers: any order gives these bits) and stored -- one owner per sum.
 //
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(PIK_THREADS) void k_pi_keep(const BatchArgs<k_pi_ke
             }
         }
     }
-    if (bad) atomicOr(&sc->bad_symbol, 1);
+    if (bad) atomicOr(&sc->bad_symbol, GDCA_BAD_ALIGNMENT);
     __syncthreads();
     if (t < 256) {  // eight threads fold the 64 partial sums of one symbol
         const int z = t >> 3, part = t & 7;
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void k_pi_finalize(const BatchArgs<k_pi_finali
 }
 
 // ||C||_1 of the covariance the pair tally has just written (full symmetric, ld) -- but only where it is NEEDED: the refinement
-// screen of the fused path (gdca_api.hip, cond_bound) is  cond_2(C) <= ||C||_1 q^2 / pc,  and  ||C||_1 <= 2 N pi_max  is at hand for
+// screen of the fused path (gdca_inverse_outcome.h, gdca_cond_bound) is  cond_2(C) <= ||C||_1 q^2 / pc,  and  ||C||_1 <= 2 N pi_max  is at hand for
 // nothing (a column of C sums, in absolute value, to at most  sum_j sum_b [Pij(jb, ia) + Pi(jb) Pi(ia)] <= 2 N Pi(ia)).  At the
 // pseudocounts gDCA is used with that cheap bound already settles the question and every workgroup leaves at once; where it does
 // not (pc = 0.2 with a conserved column; small pc), the columns are summed -- one pass over C before the sweep overwrites it.

@@ -159,7 +159,7 @@ def test_pseudocount_and_covariance_rules():
 
 @pytest.mark.parametrize("pc", [0.8, 0.2, 0.02, 0.001])
 def test_pseudocount_bounds_the_smallest_eigenvalue_of_the_covariance(refdata, pc):
-    """What the device path's refinement screen rests on (gdca_api.hip, cond_bound): with pseudocount pc the covariance is that of a
+    """What the device path's refinement screen rests on (gdca_inverse_outcome.h, gdca_cond_bound): with pseudocount pc the covariance is that of a
     mixture with weight pc on independent uniform columns, so lambda_min(C) >= pc / q^2 and cond_2(C) <= ||C||_1 q^2 / pc -- on the
     reference's own alignment, with and without gaps in every column (q = 21 and a gap-free q = 20 one), and on a random one."""
     Zs = [o.remove_duplicate_sequences(o.read_fasta_alignment(os.path.join(refdata, "small.fasta.gz"), 0.9))[0]]
