@@ -15,6 +15,8 @@ GDCA_OK, GDCA_EINVAL, GDCA_ENOTPD, GDCA_EHIP, GDCA_ENOMEM, GDCA_ENOCONV = 0, 1, 
 SCORE_FROB, SCORE_DI = 0, 1
 PAIR_COUPLING, PAIR_ENERGY = 0, 1  # `what` of gdca_pair_energies: the cross-term matrix R alone, or the energy of every concatenation
 MUT_DELTA, MUT_POTENTIAL = 0, 1  # `what` of gdca_mutation_scan: the energy change of every substitution, or the site potentials themselves
+WALK_GAP_TARGET, WALK_FILL_GAPS = 1, 2  # `flags` of gdca_greedy_walk: the gap is a target ("delete"); a gap site may receive a residue
+WALK_MAX_STEPS = 65535  # GDCA_WALK_MAX_STEPS
 ABI_VERSION = 6  # GDCA_VERSION_MAJOR * 1000 + GDCA_VERSION_MINOR of the header this binding mirrors
 
 
@@ -251,6 +253,16 @@ SYMBOLS = {
                                               C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
     "gdca_run_double_mutants": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_greedy_walk_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                       C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdca_greedy_walk": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                   C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdca_run_greedy_walk_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_greedy_walk": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -762,6 +774,56 @@ class Context:
         """gdca_double_mutants_dev: muts (5 x L int32) and out (L doubles) are device pointers like the rest."""
         self.check(self.lib.gdca_double_mutants_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), self._opt(X_ptr), int(K),
                                                     self._opt(muts_ptr), int(L), self._opt(out_ptr)))
+
+    # ---- greedy walk: every sequence descends to a local energy minimum (gdca_greedy_walk*, gdca_run_greedy_walk*) ----
+    def greedy_walk_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int | None, K: int, mask_ptr: int | None, flags: int,
+                        min_gain: float, max_steps: int, Xout_ptr: int | None, steps_ptr: int | None, dE_sum_ptr: int | None = None,
+                        path_ptr: int | None = None, dE_path_ptr: int | None = None, V_ptr: int | None = None) -> None:
+        """gdca_greedy_walk_dev: mJ (n x n), Pi (n), X (N x K int8), mask (N int8 or None) and the outputs -- Xout (N x K int8), steps
+        (K int32), dE_sum (K f64), path (2 x max_steps x K int32), dE_path (max_steps x K f64), V (q N K f64); the last four may be
+        None -- are device pointers."""
+        self.check(self.lib.gdca_greedy_walk_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), self._opt(X_ptr), int(K),
+                                                 self._opt(mask_ptr), int(flags), float(min_gain), int(max_steps), self._opt(Xout_ptr),
+                                                 self._opt(steps_ptr), self._opt(dE_sum_ptr), self._opt(path_ptr), self._opt(dE_path_ptr),
+                                                 self._opt(V_ptr)))
+
+    def run_greedy_walk_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int,
+                            mask_ptr: int | None, flags: int, min_gain: float, max_steps: int, Xout_ptr: int | None, steps_ptr: int | None,
+                            dE_sum_ptr: int | None = None, path_ptr: int | None = None, dE_path_ptr: int | None = None,
+                            V_ptr: int | None = None):
+        """gdca_run_greedy_walk_dev: the model is fitted on Z (N x M int8 in HBM) as run() fits it, then the walk of X (None: Z's own M
+        sequences); the outputs as greedy_walk_dev's.  Returns the stats dict."""
+        return self._run_readout(self.lib.gdca_run_greedy_walk_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                 self._opt(mask_ptr), int(flags), float(min_gain), int(max_steps), self._opt(Xout_ptr), self._opt(steps_ptr),
+                                 self._opt(dE_sum_ptr), self._opt(path_ptr), self._opt(dE_path_ptr), self._opt(V_ptr))
+
+    @staticmethod
+    def walk_outputs(N: int, K: int, q: int, max_steps: int, path: bool, table: bool):
+        """the host arrays a walk of K sequences fills, in the library's memory order: (Xout (N, K) Fortran int8, steps, dE_sum,
+        path (K, max_steps, 2) int32 or None, dE_path (K, max_steps) or None, V (K, N, q) or None)"""
+        K, T = max(int(K), 0), max(int(max_steps), 0)
+        return (np.empty((int(N), K), dtype=np.int8, order="F"), np.empty(K, dtype=np.int32), np.empty(K, dtype=np.float64),
+                np.empty((K, T, 2), dtype=np.int32) if path else None, np.empty((K, T), dtype=np.float64) if path else None,
+                np.empty((K, int(N), int(q)), dtype=np.float64) if table else None)
+
+    @staticmethod
+    def walk_result(out):
+        """(Xout, steps, dE_sum[, path, dE_path][, V]): the arrays of walk_outputs that were asked for"""
+        Xout, steps, dE_sum, pth, dpth, V = out
+        return (Xout, steps, dE_sum) + ((pth, dpth) if pth is not None else ()) + ((V,) if V is not None else ())
+
+    def run_greedy_walk_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None, K: int = 0,
+                            mask: np.ndarray | None = None, flags: int = 0, min_gain: float = 0.0, max_steps: int = 1, path: bool = False,
+                            table: bool = False):
+        """gdca_run_greedy_walk on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run() fits it,
+        then the K sequences X (N x K, same layout; None: Z's own M sequences) walk to their local minima.  mask: N int8 or None.
+        Returns ((Xout (N, K), steps (K,), dE_sum (K,)[, path (K, max_steps, 2), dE_path (K, max_steps)][, V (K, N, q)]), stats)."""
+        Ke = int(K) if X_ptr is not None else int(M)
+        out = self.walk_outputs(N, Ke, q, max_steps, path, table)
+        opt = lambda a: None if a is None else _p(a)  # noqa: E731
+        st = self._run_readout(self.lib.gdca_run_greedy_walk, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), opt(mask), int(flags),
+                               float(min_gain), int(max_steps), *[opt(a) for a in out])
+        return self.walk_result(out), st
 
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):

@@ -62,8 +62,22 @@ struct pair_blocks {
     long long total;               // doubles of the packed matrix
 };
 
+// What a greedy walk takes beside its sequences and returns (include/gdca.h, greedy walk): device pointers, each but Xout and steps
+// may be nullptr
+struct walk_request {
+    const int8_t *mask;
+    int flags, max_steps;
+    double min_gain;
+    int8_t *Xout;
+    int32_t *steps;
+    double *dE_sum;
+    int32_t *path;
+    double *dE_path;
+    double *V;
+};
+
 struct score_target {
-    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK, DOUBLE_SCAN, DOUBLE_LIST } kind;
+    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK, DOUBLE_SCAN, DOUBLE_LIST, WALK } kind;
     double *out;                       // S (N x N), E (K), E (KA x KB), E (packed blocks), D (q x N x K), Emin (N x N x K, may be null) or ddE (L)
     int score, apc;                    // contact
     const int8_t *X;                   // energy (k_energy.hip) and mutation scan (k_mutation.hip, with `what`): N x K
@@ -80,6 +94,7 @@ struct score_target {
     double *depi;
     const int32_t *muts;               // listed double mutants: 5 x L records
     int L;
+    walk_request walk;                 // greedy walk (k_walk.hip) of the sequences X: the rule's parameters and the outputs
     // pair / partner of a log-odds run (run_logodds): the pair stage waits for the collect, which knows the joint log det (logodds_epilogue);
     // lo.EmA / lo.EmB: the marginal fits' energies, ldA / ldB their log dets, lo.I what the collect makes of the three
     bool logodds;
@@ -175,6 +190,15 @@ static score_target double_list_target(const int8_t *X, int K, const int32_t *mu
     t.L = L;
     t.X = X;
     t.K = K;
+    return t;
+}
+
+// (X == NULL: the alignment's own M sequences)
+static score_target walk_target(const int8_t *Z, int M, const int8_t *X, int K, const walk_request &w)
+{
+    score_target t = energy_target(Z, M, X, K, nullptr);
+    t.kind = score_target::WALK;
+    t.walk = w;
     return t;
 }
 
@@ -413,6 +437,12 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         t->hamming_mode = c == 'f' ? 0 : (c == 'b' ? 1 : (c == 'm' ? 2 : -1));
         return c == 'f' || c == 'b' || c == 'm' || c == 'a' || c == 0;  // full | bound | mfma | auto
     }
+    if (!strcmp(k, "WALK_TABLE")) {  // auto | lds | hbm
+        const int v = !strcasecmp(value, "auto") ? 0 : (!strcasecmp(value, "lds") ? 1 : (!strcasecmp(value, "hbm") ? 2 : -1));
+        if (v < 0) return false;
+        t->walk_table = v;
+        return true;
+    }
     if (!strcmp(k, "FORCE_FALLBACK")) {  // any value but "" and "0" switches it on (as DCAUTILS_FORCE_FALLBACK in the reference's tests)
         t->force_fallback = (*value && strcmp(value, "0") != 0) ? 1 : 0;
         return true;
@@ -487,7 +517,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
                                         "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
                                         "GDCA_HAMMING_MODE", "GDCA_HAM_CUT", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
-                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK", "GDCA_EPI_GENERIC"};
+                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK", "GDCA_EPI_GENERIC", "GDCA_WALK_TABLE"};
     for (const char *nm : names)
         if (const char *v = getenv(nm)) (void)gdca_tuning_set(t, nm, v);  // an unusable value leaves the default
 }
@@ -1193,6 +1223,33 @@ static gdca_status double_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
     return check_launch(ctx, "double-mutant scan");
 }
 
+// Where the walk keeps a sequence's table (option WALK_TABLE): in LDS where it fits, unless HBM is asked for; false: LDS asked for
+// and the table does not fit
+static bool walk_placement(const gdca_ctx *ctx, int N, int q, bool *in_lds)
+{
+    const bool fits = gdca_walk_table_fits(N, q);
+    *in_lds = ctx->tune.walk_table == 2 ? false : fits;
+    return fits || ctx->tune.walk_table != 1;
+}
+
+// The greedy walk (k_walk.hip) of the K sequences X (N x K) under the model m: their site potentials through the mutation stage into
+// w.V -- or, where the caller does not want the final tables, into ctx->DMd --, then one workgroup a sequence walks its table, in LDS
+// or in place.  Illegal bytes of X: sc->bad_symbol, GDCA_BAD_SEQUENCE (they count as gaps: nothing is indexed with them).
+static gdca_status walk_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, const walk_request &w)
+{
+    bool in_lds = false;
+    if (!walk_placement(ctx, m.N, m.q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    double *V = w.V;
+    if (!V) {
+        CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)K * sizeof(double)));
+        V = (double *)ctx->DMd.p;
+    }
+    CHK(mutation_stage(ctx, m, X_dev, K, GDCA_MUT_POTENTIAL, V));
+    HIPCHK(gdca_launch_greedy_walk(ctx->stream, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K, w.mask, w.flags, w.min_gain,
+                                   w.max_steps, V, in_lds, w.V != nullptr, w.Xout, w.steps, w.dE_sum, w.path, w.dE_path));
+    return check_launch(ctx, "greedy walk");
+}
+
 // -mJ in ctx->A (ld = n_pad) -> what `t` asks for
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t)
 {
@@ -1211,6 +1268,7 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
     case score_target::MUTATION: return mutation_stage(ctx, m, t.X, t.K, t.what, t.out);
     case score_target::DOUBLE_SCAN: return double_stage(ctx, m, t.X, t.K, t.out, t.dcode, t.depi, nullptr, 0, nullptr);
     case score_target::DOUBLE_LIST: return double_stage(ctx, m, t.X, t.K, nullptr, nullptr, nullptr, t.muts, t.L, t.out);
+    case score_target::WALK: return walk_stage(ctx, m, t.X, t.K, t.walk);
     case score_target::CONTACT: break;
     }
     double *S_dev = t.out;
@@ -3448,6 +3506,59 @@ gdca_status gdca_run_double_mutants_dev(gdca_ctx *ctx, const int8_t *Z_dev, int3
     return run_target(ctx, Z_dev, N, M, q, p, double_list_target(X_dev, K, (const int32_t *)muts_dev, L, out_dev), st);
 }
 
+// the argument checks the four greedy-walk entry points share (nothing has run when one fails); K as it will be used
+static gdca_status validate_walk(gdca_ctx *ctx, int N, int q, long long K, int flags, double min_gain, int max_steps, const void *Xout,
+                                 const void *steps)
+{
+    CHK(validate(ctx, N, 1, q));
+    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
+    if (max_steps < 1 || max_steps > GDCA_WALK_MAX_STEPS) return fail(ctx, GDCA_EINVAL, "invalid max_steps");
+    if (!(min_gain >= 0.0)) return fail(ctx, GDCA_EINVAL, "invalid min_gain");
+    if (flags & ~(GDCA_WALK_GAP_TARGET | GDCA_WALK_FILL_GAPS)) return fail(ctx, GDCA_EINVAL, "invalid flags");
+    if (!Xout || !steps) return fail(ctx, GDCA_EINVAL, "null pointer");
+    bool in_lds = false;
+    if (!walk_placement(ctx, N, q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    return GDCA_OK;
+}
+
+static gdca_status check_greedy_walk(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *X, int K, int flags, double min_gain,
+                                     int max_steps, const void *Xout, const void *steps)
+{
+    CHK(validate_walk(ctx, N, q, K, flags, min_gain, max_steps, Xout, steps));
+    if (!mJ || !Pi || !X) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+static gdca_status check_run_greedy_walk(gdca_ctx *ctx, const void *Z, int N, int M, int q, const void *p, const void *X, int K, int flags,
+                                         double min_gain, int max_steps, const void *Xout, const void *steps)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_walk(ctx, N, q, X ? K : M, flags, min_gain, max_steps, Xout, steps));
+    if (!Z || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+gdca_status gdca_greedy_walk_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                 int32_t K, const int8_t *mask_dev, int32_t flags, double min_gain, int32_t max_steps, int8_t *Xout_dev,
+                                 int32_t *steps_dev, double *dE_sum_dev, int32_t *path_dev, double *dE_path_dev, double *V_dev)
+{
+    CHK(check_greedy_walk(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, flags, min_gain, max_steps, Xout_dev, steps_dev));
+    CHK(begin(ctx));
+    const walk_request w{mask_dev, flags, max_steps, min_gain, Xout_dev, steps_dev, dE_sum_dev, path_dev, dE_path_dev, V_dev};
+    CHK(walk_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, w));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_run_greedy_walk_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                     const int8_t *X_dev, int32_t K, const int8_t *mask_dev, int32_t flags, double min_gain,
+                                     int32_t max_steps, int8_t *Xout_dev, int32_t *steps_dev, double *dE_sum_dev, int32_t *path_dev,
+                                     double *dE_path_dev, double *V_dev, gdca_stats *st)
+{
+    CHK(check_run_greedy_walk(ctx, Z_dev, N, M, q, p, X_dev, K, flags, min_gain, max_steps, Xout_dev, steps_dev));
+    const walk_request w{mask_dev, flags, max_steps, min_gain, Xout_dev, steps_dev, dE_sum_dev, path_dev, dE_path_dev, V_dev};
+    return run_target(ctx, Z_dev, N, M, q, p, walk_target(Z_dev, M, X_dev, K, w), st);
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -3937,6 +4048,49 @@ gdca_status gdca_run_double_mutants(gdca_ctx *ctx, const int8_t *Z_host, int32_t
     double *out_dev = sg.out(out_host, (size_t)L * sizeof(double));
     CHK(sg.status());
     return sg.finish(gdca_run_double_mutants_dev(ctx, Z_dev, N, M, q, p, X_dev, K, muts_dev, L, out_dev, st));
+}
+
+gdca_status gdca_greedy_walk(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                             const int8_t *mask, int32_t flags, double min_gain, int32_t max_steps, int8_t *Xout, int32_t *steps,
+                             double *dE_sum, int32_t *path, double *dE_path, double *V)
+{
+    CHK(check_greedy_walk(ctx, mJ, Pi, N, q, X, K, flags, min_gain, max_steps, Xout, steps));
+    const size_t n = (size_t)N * (q - 1), k = (size_t)K, rows = (size_t)max_steps * k;
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *X_dev = sg.in(X, (size_t)N * k);
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    int8_t *Xout_dev = sg.out(Xout, (size_t)N * k);
+    int32_t *steps_dev = sg.out(steps, k * sizeof(int32_t));
+    double *dE_sum_dev = sg.out(dE_sum, k * sizeof(double));
+    int32_t *path_dev = sg.out(path, 2 * rows * sizeof(int32_t));
+    double *dE_path_dev = sg.out(dE_path, rows * sizeof(double));
+    double *V_dev = sg.out(V, (size_t)q * (size_t)N * k * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_greedy_walk_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, mask_dev, flags, min_gain, max_steps, Xout_dev, steps_dev, dE_sum_dev,
+                                          path_dev, dE_path_dev, V_dev));
+}
+
+gdca_status gdca_run_greedy_walk(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                 const int8_t *X_host, int32_t K, const int8_t *mask, int32_t flags, double min_gain, int32_t max_steps,
+                                 int8_t *Xout, int32_t *steps, double *dE_sum, int32_t *path, double *dE_path, double *V, gdca_stats *st)
+{
+    CHK(check_run_greedy_walk(ctx, Z_host, N, M, q, p, X_host, K, flags, min_gain, max_steps, Xout, steps));
+    const size_t k = (size_t)(X_host ? K : M), rows = (size_t)max_steps * k;
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    int8_t *Xout_dev = sg.out(Xout, (size_t)N * k);
+    int32_t *steps_dev = sg.out(steps, k * sizeof(int32_t));
+    double *dE_sum_dev = sg.out(dE_sum, k * sizeof(double));
+    int32_t *path_dev = sg.out(path, 2 * rows * sizeof(int32_t));
+    double *dE_path_dev = sg.out(dE_path, rows * sizeof(double));
+    double *V_dev = sg.out(V, (size_t)q * (size_t)N * k * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_greedy_walk_dev(ctx, Z_dev, N, M, q, p, X_dev, K, mask_dev, flags, min_gain, max_steps, Xout_dev, steps_dev,
+                                              dE_sum_dev, path_dev, dE_path_dev, V_dev, st));
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

@@ -89,6 +89,7 @@ struct gdca_tuning {
     int energy_chunk;       // GDCA_ENERGY_CHUNK: sequences one launch of the energy gather kernel takes; 0 = as many as keep its partials within ~256 MB
     int pair_chunk;         // GDCA_PAIR_CHUNK: sequences of protein A one launch of the pair-energy fold / gather kernels takes; 0 = as many as keep their folded rows within ~256 MB (the rule), a smaller count is taken as given, a larger one is cut to the rule
     int epi_generic;        // GDCA_EPI_GENERIC (tests, measurements): 1 = the double-mutant scan runs its generic instance (s at run time) at s = 20 too
+    int walk_table;         // GDCA_WALK_TABLE: where the greedy walk keeps a sequence's table of site potentials: 0 = in LDS where it fits, else in HBM (auto, default), 1 = LDS (a table that does not fit: GDCA_EINVAL), 2 = HBM; the same bits wherever it is
     char sweep_trace[256];  // GDCA_SWEEP_TRACE: file the in-kernel trace of the next inverse is written to ("" = off)
 };
 void gdca_tuning_from_env(gdca_tuning *t);
@@ -379,3 +380,16 @@ hipError_t gdca_launch_double_mutant_scan(hipStream_t s, const double *A, size_t
 // out[r] = ddE of record r of muts (5 x L int32: k, i, b, j, c); a record out of range: GDCA_BAD_MUTANT in sc->bad_symbol, nothing indexed with it
 void gdca_launch_double_mutants(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, const double *D,
                                 const int32_t *muts, long long L, int N, int sdim, int K, double *out, gdca_dev_scalars *sc);
+
+// ---- k_walk.hip: the greedy walk -- every sequence descends to a local energy minimum, one substitution a step ------------------------------
+// (include/gdca.h, greedy walk).  Xg: the K sequences packed by gdca_launch_energy_pack; V: the site potentials [K][N][q] of
+// gdca_launch_mutation_scan (what = GDCA_MUT_POTENTIAL); A, ld, sign as there.
+#define GDCA_WALK_LDS_LIMIT (160 * 1024)  // LDS of a compute unit: what the table, the symbols and the reduction's slots may take together
+size_t gdca_walk_lds_bytes(int N, int q, bool table_in_lds);
+bool gdca_walk_table_fits(int N, int q);  // the instance with the table in LDS can run
+// One workgroup a sequence.  table_in_lds: the table is copied to LDS, walked there and -- write_table -- written back to V at the end;
+// else it is walked in place in V.  mask (N bytes), dE_sum, path, dE_path may be nullptr.  An error: the table does not fit, or the
+// dynamic LDS limit could not be raised; nothing was launched
+hipError_t gdca_launch_greedy_walk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
+                                   const int8_t *mask, int flags, double min_gain, int max_steps, double *V, bool table_in_lds, bool write_table,
+                                   int8_t *Xout, int32_t *steps, double *dE_sum, int32_t *path, double *dE_path);

@@ -590,6 +590,66 @@ def mutation_scan(mJ, Pi, X, q: int = 21, what="delta", ctx=None) -> np.ndarray:
     return D
 
 
+def _walk_args(N, max_steps, min_gain, mask, gap_target, fill_gaps):
+    """the rule's parameters of a greedy walk, checked: (max_steps, min_gain, mask int8 (N,) or None, flags)"""
+    if max_steps is None:
+        max_steps = min(4 * N, _lib.WALK_MAX_STEPS)
+    if not isinstance(max_steps, (int, np.integer)) or not 1 <= max_steps <= _lib.WALK_MAX_STEPS:
+        raise ArgumentError(f"invalid max_steps value: {max_steps} (must be an integer between 1 and {_lib.WALK_MAX_STEPS})")
+    try:
+        min_gain = float(min_gain)
+    except (TypeError, ValueError):
+        raise ArgumentError(f"invalid min_gain value: {min_gain} (must be a number >= 0)") from None
+    if not min_gain >= 0.0:
+        raise ArgumentError(f"invalid min_gain value: {min_gain} (must be a number >= 0)")
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.shape != (N,) or not (m.dtype == np.bool_ or np.issubdtype(m.dtype, np.integer)):
+            raise ArgumentError(f"mask must be a vector of {N} booleans or integers, one per site")
+        mask = np.ascontiguousarray(m != 0, dtype=np.int8)
+    return int(max_steps), min_gain, mask, (_lib.WALK_GAP_TARGET if gap_target else 0) | (_lib.WALK_FILL_GAPS if fill_gaps else 0)
+
+
+def greedy_walk(mJ, Pi, X, q: int = 21, max_steps=None, min_gain: float = 0.0, mask=None, gap_target: bool = False, fill_gaps: bool = False,
+                path: bool = False, table: bool = False, ctx=None):
+    """Every one of the K columns of X (shape (N, K) like Z, symbols 1..q, q = the gap) descends the energy of the Gaussian model
+    (mJ, Pi) greedily: at each step the single substitution with the lowest energy change ``mutation_scan`` would give for the CURRENT
+    sequence is taken (ties: the smallest site, then the smallest symbol), until no admissible substitution lowers the energy by more
+    than ``min_gain`` or ``max_steps`` (default min(4 N, 65535)) steps are done -- the greedy k-fold mutant, the local minimum the
+    sequence drains to, and how far above it the sequence sits.  ``mask``: N booleans, the sites that may change (default all);
+    ``gap_target``: a residue may be deleted (the gap is a target); ``fill_gaps``: a gap may receive a residue.  By default residues
+    change into residues and gaps stay gaps.
+
+    Returns ``(Xout (N, K) int8, steps (K,) int32, dE_sum (K,))`` -- the final sequences, the steps taken and the sum of the steps'
+    energy changes --; with ``path=True`` also ``path (K, max_steps, 2)`` int32, row t = (site, 0-based; symbol, 1..q) of step t and -1
+    beyond ``steps[k]``, and ``dE_path (K, max_steps)``, the steps' energy changes and 0 beyond; with ``table=True`` also
+    ``V (K, N, q)``, the site potentials as the walk left them (``mutation_scan(.., what="potential")`` of Xout up to the rounding
+    of one subtraction and one addition a step).  With ``min_gain = 0`` a pair of moves worth about 1e-16 could in principle alternate
+    until max_steps; a min_gain above the table's drift (1e-9 is far above it) rules that out.  mJ must be symmetric (its lower triangle
+    is read)."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    Xf = _symbols(X, "X")
+    N, K = Xf.shape
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = N * (int(q) - 1)
+    if N < 1 or mJ.shape != (n, n) or Pi.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: X has N = {N} sites, q = {q}, so mJ must be {n} x {n} and Pi have {n} entries "
+                            f"(got {mJ.shape} and {Pi.shape})")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    T, min_gain, m, flags = _walk_args(N, max_steps, min_gain, mask, gap_target, fill_gaps)
+    ctx = ctx or default_context()
+    out = ctx.walk_outputs(N, K, q, T, path, table)
+    opt = lambda a: None if a is None else _lib._p(a)  # noqa: E731
+    ctx.check(ctx.lib.gdca_greedy_walk(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xf), K, opt(m), flags, min_gain, T,
+                                       *[opt(a) for a in out]))
+    return ctx.walk_result(out)
+
+
 def _double_model_args(mJ, Pi, X, q):
     """the model and the sequences of the double-mutant operators, checked: (mJ, Pi, Xf, N, K)"""
     mJ = np.ascontiguousarray(mJ, dtype=np.float64)

@@ -157,6 +157,30 @@ def double_mutants_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, dmuts
     return dout
 
 
+def greedy_walk_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, max_steps: int, min_gain: float = 0.0, dmask=None, flags: int = 0,
+                    dXout=None, dsteps=None, ddE_sum=None, dpath=None, ddE_path=None, dV=None, want=("dE_sum",)):
+    """The greedy walk of the K sequences X (N x K int8) to their local energy minima with every array in HBM (gdca_greedy_walk_dev):
+    flags = _lib.WALK_GAP_TARGET | _lib.WALK_FILL_GAPS, dmask N int8 or None.  Xout (N x K int8) and steps (K int32) are always
+    made; ``want`` names the optional outputs a buffer is made for where none is given: "dE_sum" (K f64), "path" (2 x max_steps x K
+    int32), "dE_path" (max_steps x K f64), "V" (q N K f64: the final tables).  Returns (dXout, dsteps, ddE_sum, dpath, ddE_path, dV),
+    None for what was not wanted."""
+    K, T = int(K), int(max_steps)
+    dXout = dXout or DeviceBuffer(ctx, max(N * K, 1))
+    dsteps = dsteps or DeviceBuffer(ctx, 4 * max(K, 1))
+    if "dE_sum" in want:
+        ddE_sum = ddE_sum or DeviceBuffer(ctx, 8 * max(K, 1))
+    if "path" in want:
+        dpath = dpath or DeviceBuffer(ctx, 8 * max(T * K, 1))
+    if "dE_path" in want:
+        ddE_path = ddE_path or DeviceBuffer(ctx, 8 * max(T * K, 1))
+    if "V" in want:
+        dV = dV or DeviceBuffer(ctx, 8 * int(q) * N * max(K, 1))
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.greedy_walk_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), opt(dX), K, opt(dmask), int(flags), float(min_gain), T, opt(dXout),
+                        opt(dsteps), opt(ddE_sum), opt(dpath), opt(ddE_path), opt(dV))
+    return dXout, dsteps, ddE_sum, dpath, ddE_path, dV
+
+
 def scores_stepwise(Z, q: int, pseudocount: float = 0.8, theta=":auto", score: str = "frob", ctx: Context = None
                     ) -> Tuple[np.ndarray, dict]:
     """The six statements of src/GaussDCA.jl:28-42 one by one, arrays resident in HBM.  Z: (N, M) int8.

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, default_context
-from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _mutations_arg, decode_double_code, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
+from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _walk_args, _mutations_arg, decode_double_code, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
                        remove_duplicate_sequences, species_blocks)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
@@ -433,6 +433,33 @@ def gDCA_mutation_scan(filename: str, sequences=None, what="delta", pseudocount:
                            lambda c, ptr, N, M, q: c.run_mutation_scan_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta),
                                                                            *_ptr_count(X), w),
                            "energy changes")
+
+
+def gDCA_greedy_walk(filename: str, sequences=None, max_steps=None, min_gain: float = 0.0, mask=None, gap_target: bool = False,
+                     fill_gaps: bool = False, path: bool = False, table: bool = False, pseudocount: float = 0.8, theta=":auto",
+                     max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, **kw):
+    """Greedy walks under the Gaussian model gDCA fits to the alignment in ``filename`` (the fit and its arguments are
+    ``gDCA_mutation_scan``'s): every sequence takes the single substitution that lowers its energy most, again and again, until none
+    lowers it by more than ``min_gain`` or ``max_steps`` (default min(4 N, 65535)) steps are done.  The walk's arguments and what is
+    returned -- ``(Xout, steps, dE_sum[, path, dE_path][, V])`` -- are ``dcautils.greedy_walk``'s.
+
+    ``sequences`` as for ``gDCA_energies``: ``None`` walks the alignment's own sequences (after the gap filter and the optional
+    deduplication); an ``(N, K)`` int8 array (symbols 1..q like ``Z``) walks its columns; a string names a second FASTA file, read
+    with ``max_gap_fraction = 1.0`` so every record is kept.  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_greedy_walk() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    X = _sequences_arg(sequences, "sequences", "an N x K")
+
+    def run(c, ptr, N, M, q):
+        T, mg, m, flags = _walk_args(N, max_steps, min_gain, mask, gap_target, fill_gaps)
+        return c.run_greedy_walk_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), *_ptr_count(X), mask=m, flags=flags, min_gain=mg,
+                                     max_steps=T, path=path, table=table)
+
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N), run,
+                           "walks")
 
 
 def _required_sequences(sequences, name):

@@ -183,7 +183,9 @@ gdca_status gdca_ctx_set_timing(gdca_ctx *ctx, int32_t enabled);
  * ill-conditioned / never / always) and REFINE_COND (the threshold of auto, default 1e6); CHOLESKY (0 | 1 | 2: the blocked
  * dpotrf + dpotri fallback never / where the sweep gave up [default] / for every inverse); ENERGY_CHUNK (sequences one launch of the energy gather
  * kernel takes, 0 = the rule [default]: the same bits whatever it is); PAIR_CHUNK (sequences of protein A one launch of the pair-energy
- * kernels takes, 0 = the rule [default: a ~256 MB buffer]; a count above the rule's is cut to it: the same bits whatever it is).  The schedule switches change results
+ * kernels takes, 0 = the rule [default: a ~256 MB buffer]; a count above the rule's is cut to it: the same bits whatever it is); WALK_TABLE (auto | lds | hbm: where the greedy walk keeps a
+ * sequence's table of site potentials -- auto [default]: in LDS where it fits, else in HBM; lds with a table that does not fit makes the
+ * walk fail with GDCA_EINVAL; the same bits wherever it is).  The schedule switches change results
  * at rounding level at most (another summation order); REFINE improves an ill-conditioned inverse.  GDCA_EINVAL: unknown key
  * or unusable value. */
 gdca_status gdca_ctx_set_option(gdca_ctx *ctx, const char *key, const char *value);
@@ -626,6 +628,54 @@ gdca_status gdca_run_double_mutant_scan_dev(gdca_ctx *ctx, const int8_t *Z_dev, 
 gdca_status gdca_run_double_mutants_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                         const int8_t *X_dev, int32_t K, const void *muts_dev, int32_t L, double *out_dev, gdca_stats *st);
 
+/* ---- greedy walk: every sequence descends to a local energy minimum, one substitution a step -------------------------------
+ * From a wild type take the most stabilising single substitution, update the landscape, repeat -- for max_steps steps or until no
+ * substitution lowers the energy: the greedy k-fold mutant, the local minimum a sequence drains to, and how far above it the
+ * sequence sits.  Conventions as in the mutation-scan section above: s, n, r(i, c), the gap q has no row, only the lower triangle of
+ * mJ is read; K(j,c; i,b) = mJ[r(j,c), r(i,b)], exactly +0.0 where b == q.  (The fused forms read -mJ; every expression below negates
+ * exactly, so they return the same bits as the operator forms on the same model.)
+ * STATE per sequence: the current symbols x (N) and a table V[i][c], c in 1..q; V[i][q] is +0.0 and never written.  Start:
+ * x = X[:, k] and V = the bits gdca_mutation_scan(.., GDCA_MUT_POTENTIAL) returns for that sequence.
+ * ADMISSIBLE MOVES in state x: site i if mask == NULL or mask[i] != 0 -- and, where x_i == q, only with GDCA_WALK_FILL_GAPS --, to a
+ * target b in 1..q, b != x_i; b == q only with GDCA_WALK_GAP_TARGET.  flags = 0: residues change into residues, gaps stay gaps.
+ * STEP: dE(i, b) = V[i][b] - V[i][x_i], ONE f64 subtraction of two table entries.  The step takes the admissible (i, b) that minimises
+ * dE, ties to the smallest code i q + (b - 1) (the total order on (dE, code): any reduction tree gives the same result; a NaN dE is
+ * never chosen).  The walk stops if there is no admissible move, if the best move does not satisfy dE < -min_gain, or after
+ * max_steps steps.  Otherwise it records (i, b, dE), sets x_i = b (a the old symbol), and for every site j != i and every c in 1..s
+ *     V[j][c] = V[j][c] + (K(j,c; i,b) - K(j,c; i,a))                         (one subtraction, then one addition);
+ * site i's own row is not touched: V(x; i, .) does not depend on x_i.
+ * In exact arithmetic the energy falls strictly, so a walk ends.  The table is updated in f64 and drifts from the potentials of the
+ * current sequence by about one unit roundoff of its entries a step; with min_gain = 0 two moves worth about 1e-16 could in
+ * principle alternate.  max_steps bounds that, and a min_gain above the drift (1e-9 is far above it for |V| ~ 1e2) rules it out.
+ * OUTPUTS (K sequences, X N x K int8 column-major):
+ *     Xout     N x K int8: the final sequences; must not overlap X or Z;
+ *     steps    K int32: the steps taken;
+ *     dE_sum   K f64: the sum of the recorded dE in step order (one thread); may be NULL;
+ *     path     2 x max_steps x K int32, column-major: record t of sequence k is (i, b), i 0-based, b in 1..q; the rows from steps[k]
+ *              on hold -1; may be NULL;
+ *     dE_path  max_steps x K f64; the rows from steps[k] on hold +0.0; may be NULL;
+ *     V        q x N x K f64 in gdca_mutation_scan's layout: the FINAL table as the walk left it; may be NULL.
+ * mask: N int8 shared by all sequences, NULL = every site may change.  The bits of everything a walk returns depend on the initial
+ * table's bits, the model, x_k, mask, flags, min_gain and max_steps -- not on K, on where x_k stands in the batch, on the kernel
+ * instance or on where the table lives (context option WALK_TABLE).  No floating-point atomics.  Without V the stage keeps the tables
+ * in the double-mutant scan's context workspace of q N K doubles.
+ * GDCA_EINVAL: K < 1 or K > INT32_MAX - 256, q outside 2..31, max_steps outside 1..GDCA_WALK_MAX_STEPS, min_gain < 0 or NaN, a
+ * flags bit other than the two, a null X (operator form), Xout or steps, WALK_TABLE = lds with a table that does not fit -- nothing
+ * is run -- or a byte of X outside 1..q (detected on the device before anything is indexed with it).  On failure the outputs are
+ * unspecified.  Synchronous. */
+enum { GDCA_WALK_GAP_TARGET = 1, GDCA_WALK_FILL_GAPS = 2 };
+#define GDCA_WALK_MAX_STEPS 65535
+gdca_status gdca_greedy_walk_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev,
+                                 int32_t K, const int8_t *mask_dev, int32_t flags, double min_gain, int32_t max_steps, int8_t *Xout_dev,
+                                 int32_t *steps_dev, double *dE_sum_dev, int32_t *path_dev, double *dE_path_dev, double *V_dev);
+/* Fused, exactly as gdca_run_mutation_scan (the fit, the conditioning screen; a refinement or fallback at collect time runs the stage
+ * again).  X == NULL walks Z's own M sequences (K is then ignored).  p->score and p->apc are ignored.  Stats: ms_score is the stage
+ * (the scan and the walk), ms_fn 0. */
+gdca_status gdca_run_greedy_walk_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                     const int8_t *X_dev, int32_t K, const int8_t *mask_dev, int32_t flags, double min_gain,
+                                     int32_t max_steps, int8_t *Xout_dev, int32_t *steps_dev, double *dE_sum_dev, int32_t *path_dev,
+                                     double *dE_path_dev, double *V_dev, gdca_stats *st);
+
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* A host-pointer form on a context with an enqueued run (gdca_run_dev_async, gdca_run_ranked_async, ...) is refused (GDCA_EINVAL)
  * before it touches the context: nothing is uploaded or reallocated, and the enqueued run is unaffected. */
@@ -727,6 +777,14 @@ gdca_status gdca_run_double_mutant_scan(gdca_ctx *ctx, const int8_t *Z_host, int
                                         gdca_stats *st);
 gdca_status gdca_run_double_mutants(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                     const int8_t *X_host, int32_t K, const void *muts_host, int32_t L, double *out_host, gdca_stats *st);
+
+/* greedy walk with host pointers: upload, the _dev form, download */
+gdca_status gdca_greedy_walk(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                             const int8_t *mask, int32_t flags, double min_gain, int32_t max_steps, int8_t *Xout, int32_t *steps,
+                             double *dE_sum, int32_t *path, double *dE_path, double *V);
+gdca_status gdca_run_greedy_walk(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                 const int8_t *X_host, int32_t K, const int8_t *mask, int32_t flags, double min_gain, int32_t max_steps,
+                                 int8_t *Xout, int32_t *steps, double *dE_sum, int32_t *path, double *dE_path, double *V, gdca_stats *st);
 
 /* ---- host-side utilities around the hot path (plain C++, no GPU): the reference's callers of the path -------- */
 /* CPUs this process can really use: hardware threads capped by the cgroup CPU quota (a container may see 256 threads and be given
