@@ -12,6 +12,8 @@ from .dcautils import double_mutant_energies, double_mutant_scan  # noqa: F401
 from .gdca import gDCA_double_mutant_scan, gDCA_double_mutants  # noqa: F401
 from .dcautils import greedy_walk  # noqa: F401
 from .gdca import gDCA_greedy_walk  # noqa: F401
+from .dcautils import sample  # noqa: F401
+from .gdca import gDCA_sample  # noqa: F401
 from .dcautils import (add_pseudocount, assign_blocks, compute_C, compute_DI_gauss, compute_FN, compute_ranking,  # noqa: F401
                        compute_theta, compute_weighted_frequencies, compute_weights, correct_APC,
                        inv_cholesky, logodds_information, mutation_scan, neighbour_counts, pair_energies, pair_energies_blocked, pair_identity_sum,

@@ -17,6 +17,7 @@ PAIR_COUPLING, PAIR_ENERGY = 0, 1  # `what` of gdca_pair_energies: the cross-ter
 MUT_DELTA, MUT_POTENTIAL = 0, 1  # `what` of gdca_mutation_scan: the energy change of every substitution, or the site potentials themselves
 WALK_GAP_TARGET, WALK_FILL_GAPS = 1, 2  # `flags` of gdca_greedy_walk: the gap is a target ("delete"); a gap site may receive a residue
 WALK_MAX_STEPS = 65535  # GDCA_WALK_MAX_STEPS
+SAMPLE_GAPS = 1  # `flags` of gdca_sample: the gap is a symbol like any other (default: residues change into residues, gaps stay gaps)
 ABI_VERSION = 6  # GDCA_VERSION_MAJOR * 1000 + GDCA_VERSION_MINOR of the header this binding mirrors
 
 
@@ -263,6 +264,18 @@ SYMBOLS = {
     "gdca_run_greedy_walk": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_sample_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                                  C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "gdca_sample": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                              C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p]),
+    "gdca_run_sample_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_sample": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -824,6 +837,59 @@ class Context:
         st = self._run_readout(self.lib.gdca_run_greedy_walk, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), opt(mask), int(flags),
                                float(min_gain), int(max_steps), *[opt(a) for a in out])
         return self.walk_result(out), st
+
+    # ---- Metropolis chains: sequences drawn from the model at an inverse temperature (gdca_sample*, gdca_run_sample*) ----
+    def sample_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, X_ptr: int | None, K: int, mask_ptr: int | None, flags: int, beta: float,
+                   seed: int, stream0: int, burn: int, stride: int, n_samples: int, Xs_ptr: int | None, accepted_ptr: int | None,
+                   dE_s_ptr: int | None = None, thr_ptr: int | None = None, moves_ptr: int | None = None, V_ptr: int | None = None) -> None:
+        """gdca_sample_dev: mJ (n x n), Pi (n), X (N x K int8), mask (N int8 or None) and the outputs -- Xs (N x n_samples x K int8),
+        accepted (K int32), dE_s (n_samples x K f64), thr (n_steps x K f64), moves (n_steps x K int32), V (q N K f64); the last four
+        may be None -- are device pointers."""
+        self.check(self.lib.gdca_sample_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), self._opt(X_ptr), int(K),
+                                            self._opt(mask_ptr), int(flags), float(beta), int(seed), int(stream0), int(burn), int(stride),
+                                            int(n_samples), self._opt(Xs_ptr), self._opt(dE_s_ptr), self._opt(accepted_ptr),
+                                            self._opt(thr_ptr), self._opt(moves_ptr), self._opt(V_ptr)))
+
+    def run_sample_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int,
+                       mask_ptr: int | None, flags: int, beta: float, seed: int, stream0: int, burn: int, stride: int, n_samples: int,
+                       Xs_ptr: int | None, accepted_ptr: int | None, dE_s_ptr: int | None = None, thr_ptr: int | None = None,
+                       moves_ptr: int | None = None, V_ptr: int | None = None):
+        """gdca_run_sample_dev: the model is fitted on Z (N x M int8 in HBM) as run() fits it, then the chains from X (None: one from
+        each of Z's own M sequences); the outputs as sample_dev's.  Returns the stats dict."""
+        return self._run_readout(self.lib.gdca_run_sample_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                 self._opt(mask_ptr), int(flags), float(beta), int(seed), int(stream0), int(burn), int(stride),
+                                 int(n_samples), self._opt(Xs_ptr), self._opt(dE_s_ptr), self._opt(accepted_ptr), self._opt(thr_ptr),
+                                 self._opt(moves_ptr), self._opt(V_ptr))
+
+    @staticmethod
+    def sample_outputs(N: int, K: int, q: int, burn: int, stride: int, n_samples: int, trace: bool, table: bool):
+        """the host arrays the chains of K start sequences fill, in the library's memory order: (Xs (N, n_samples, K) Fortran int8, dE_s
+        (K, n_samples), accepted (K,) int32, thr (K, n_steps) or None, moves (K, n_steps) int32 or None, V (K, N, q) or None)"""
+        K, S = max(int(K), 0), max(int(n_samples), 0)
+        T = max(int(burn) + S * int(stride), 0)
+        return (np.empty((int(N), S, K), dtype=np.int8, order="F"), np.empty((K, S), dtype=np.float64), np.empty(K, dtype=np.int32),
+                np.empty((K, T), dtype=np.float64) if trace else None, np.empty((K, T), dtype=np.int32) if trace else None,
+                np.empty((K, int(N), int(q)), dtype=np.float64) if table else None)
+
+    @staticmethod
+    def sample_result(out):
+        """(Xs, dE_s, accepted[, thr, moves][, V]): the arrays of sample_outputs that were asked for"""
+        Xs, dE_s, acc, thr, moves, V = out
+        return (Xs, dE_s, acc) + ((thr, moves) if thr is not None else ()) + ((V,) if V is not None else ())
+
+    def run_sample_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None, K: int = 0,
+                       mask: np.ndarray | None = None, flags: int = 0, beta: float = 1.0, seed: int = 0, stream0: int = 0, burn: int = 0,
+                       stride: int = 1, n_samples: int = 1, trace: bool = False, table: bool = False):
+        """gdca_run_sample on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run() fits it, then
+        one Metropolis chain starts from each of the K sequences X (N x K, same layout; None: Z's own M sequences).  mask: N int8 or
+        None.  Returns ((Xs (N, n_samples, K), dE_s (K, n_samples), accepted (K,)[, thr (K, n_steps), moves (K, n_steps)][, V (K, N, q)]),
+        stats)."""
+        Ke = int(K) if X_ptr is not None else int(M)
+        out = self.sample_outputs(N, Ke, q, burn, stride, n_samples, trace, table)
+        opt = lambda a: None if a is None else _p(a)  # noqa: E731
+        st = self._run_readout(self.lib.gdca_run_sample, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), opt(mask), int(flags),
+                               float(beta), int(seed), int(stream0), int(burn), int(stride), int(n_samples), *[opt(a) for a in out])
+        return self.sample_result(out), st
 
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):

@@ -76,8 +76,15 @@ struct walk_request {
     double *V;
 };
 
+// What the Metropolis chains take beside their start sequences and return (include/gdca.h, Metropolis chains): the kernel's plan and
+// the final tables; device pointers, dE_s, thr, moves and V may be nullptr
+struct sample_request {
+    gdca_sample_plan plan;
+    double *V;
+};
+
 struct score_target {
-    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK, DOUBLE_SCAN, DOUBLE_LIST, WALK } kind;
+    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK, DOUBLE_SCAN, DOUBLE_LIST, WALK, SAMPLE } kind;
     double *out;                       // S (N x N), E (K), E (KA x KB), E (packed blocks), D (q x N x K), Emin (N x N x K, may be null) or ddE (L)
     int score, apc;                    // contact
     const int8_t *X;                   // energy (k_energy.hip) and mutation scan (k_mutation.hip, with `what`): N x K
@@ -95,6 +102,7 @@ struct score_target {
     const int32_t *muts;               // listed double mutants: 5 x L records
     int L;
     walk_request walk;                 // greedy walk (k_walk.hip) of the sequences X: the rule's parameters and the outputs
+    sample_request sample;             // Metropolis chains (k_sample.hip) from the sequences X: the rule's parameters and the outputs
     // pair / partner of a log-odds run (run_logodds): the pair stage waits for the collect, which knows the joint log det (logodds_epilogue);
     // lo.EmA / lo.EmB: the marginal fits' energies, ldA / ldB their log dets, lo.I what the collect makes of the three
     bool logodds;
@@ -202,6 +210,15 @@ static score_target walk_target(const int8_t *Z, int M, const int8_t *X, int K, 
     return t;
 }
 
+// (X == NULL: one chain from each of the alignment's own M sequences)
+static score_target sample_target(const int8_t *Z, int M, const int8_t *X, int K, const sample_request &r)
+{
+    score_target t = energy_target(Z, M, X, K, nullptr);
+    t.kind = score_target::SAMPLE;
+    t.sample = r;
+    return t;
+}
+
 // The enqueued, not yet collected run (gdca_run_dev_async / gdca_run_collect): all a collect needs to know, grouped by who writes it.
 // The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev) borrows n, n_pad, timed (false: begin()) and the
 // progress record `at` -- attempt and refined --, so that it can go through run_inverses and inverse_ladder.
@@ -274,6 +291,7 @@ struct gdca_ctx {
     // the round before, and the species of every sequence a
     gdca_buf IPAws, IPAcnt, IPAZ, IPAsel, IPAm, IPAg, IPAprev, IPAsp;
     gdca_buf DMd;             // double-mutant scan (k_epistasis.hip): dE of every single substitution of its sequences, q N K doubles
+    gdca_buf SMst;            // Metropolis chains (k_sample.hip): what a chain keeps between two launches, gdca_sample_state_bytes
     int ncu;                  // compute units of the device
     double *piv;              // the pivots of the context's last inverse, n_pad doubles inside Sg (inverse_job)
     // log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet): kept on the host, so that entry points
@@ -457,7 +475,7 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         {"MERGE_MCUS", &t->merge_mcus, -1, 16},  {"MERGE_GROUP", &t->merge_group, -1, 4}, {"MERGE_TILES", &t->merge_tiles, 1, 1 << 20},
         {"CHOLESKY", &t->cholesky, 0, 2},  {"PHASED_FRONTS", &t->phased_fronts, 0, 1}, {"PHASED_GRIDS", &t->phased_grids, -1, 8}, {"PHASED_STREAMS", &t->phased_streams, 1, 64},
         {"ENERGY_CHUNK", &t->energy_chunk, 0, 1 << 30}, {"PAIR_CHUNK", &t->pair_chunk, 0, 1 << 30},
-        {"EPI_GENERIC", &t->epi_generic, 0, 1},
+        {"EPI_GENERIC", &t->epi_generic, 0, 1}, {"SAMPLE_CHUNK", &t->sample_chunk, 0, INT32_MAX},
     };
     for (auto &e : ints)
         if (!strcmp(k, e.name)) {
@@ -517,7 +535,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
                                         "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
                                         "GDCA_HAMMING_MODE", "GDCA_HAM_CUT", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
-                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK", "GDCA_EPI_GENERIC", "GDCA_WALK_TABLE"};
+                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK", "GDCA_EPI_GENERIC", "GDCA_WALK_TABLE", "GDCA_SAMPLE_CHUNK"};
     for (const char *nm : names)
         if (const char *v = getenv(nm)) (void)gdca_tuning_set(t, nm, v);  // an unusable value leaves the default
 }
@@ -728,7 +746,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
                         &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
                         &ctx->LOa, &ctx->LOb, &ctx->PBN,
-                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd};
+                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     ctx->staging.release();
@@ -1250,6 +1268,31 @@ static gdca_status walk_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *
     return check_launch(ctx, "greedy walk");
 }
 
+// The Metropolis chains (k_sample.hip) from the K sequences X (N x K) under the model m: the start tables through the mutation stage
+// into r.V -- or into ctx->DMd --, placed as the walk places them, then the proposals in launches of at most SAMPLE_CHUNK; between two
+// launches a chain lives in its table, in ctx->SMst and in `accepted`.  Illegal bytes of X: as the walk's.
+static gdca_status sample_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, const sample_request &r)
+{
+    bool in_lds = false;
+    if (!walk_placement(ctx, m.N, m.q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    double *V = r.V;
+    if (!V) {
+        CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)K * sizeof(double)));
+        V = (double *)ctx->DMd.p;
+    }
+    CHK(ensure(ctx, ctx->SMst, gdca_sample_state_bytes(m.N, K)));
+    CHK(mutation_stage(ctx, m, X_dev, K, GDCA_MUT_POTENTIAL, V));
+    const int n_steps = r.plan.burn + r.plan.n_samples * r.plan.stride;
+    const int chunk = ctx->tune.sample_chunk > 0 ? ctx->tune.sample_chunk : GDCA_SAMPLE_CHUNK_RULE;
+    for (int t0 = 0; t0 < n_steps;) {
+        const int t1 = n_steps - t0 > chunk ? t0 + chunk : n_steps;
+        HIPCHK(gdca_launch_sample(ctx->stream, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K, r.plan, t0, t1, V, in_lds,
+                                  ctx->SMst.p));
+        t0 = t1;
+    }
+    return check_launch(ctx, "Metropolis chains");
+}
+
 // -mJ in ctx->A (ld = n_pad) -> what `t` asks for
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t)
 {
@@ -1269,6 +1312,7 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
     case score_target::DOUBLE_SCAN: return double_stage(ctx, m, t.X, t.K, t.out, t.dcode, t.depi, nullptr, 0, nullptr);
     case score_target::DOUBLE_LIST: return double_stage(ctx, m, t.X, t.K, nullptr, nullptr, nullptr, t.muts, t.L, t.out);
     case score_target::WALK: return walk_stage(ctx, m, t.X, t.K, t.walk);
+    case score_target::SAMPLE: return sample_stage(ctx, m, t.X, t.K, t.sample);
     case score_target::CONTACT: break;
     }
     double *S_dev = t.out;
@@ -3559,6 +3603,65 @@ gdca_status gdca_run_greedy_walk_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t
     return run_target(ctx, Z_dev, N, M, q, p, walk_target(Z_dev, M, X_dev, K, w), st);
 }
 
+// the argument checks the four Metropolis entry points share (nothing has run when one fails); K as it will be used
+static gdca_status validate_sample(gdca_ctx *ctx, int N, int q, long long K, int flags, double beta, int burn, int stride, int n_samples,
+                                   const void *Xs, const void *accepted)
+{
+    CHK(validate(ctx, N, 1, q));
+    if (K < 1 || K > INT32_MAX - 256) return fail(ctx, GDCA_EINVAL, "invalid number of sequences");
+    if (flags & ~GDCA_SAMPLE_GAPS) return fail(ctx, GDCA_EINVAL, "invalid flags");
+    if ((flags & GDCA_SAMPLE_GAPS ? q : q - 1) < 2) return fail(ctx, GDCA_EINVAL, "fewer than two target symbols");
+    if (!(beta >= 0.0) || !std::isfinite(beta)) return fail(ctx, GDCA_EINVAL, "invalid beta");
+    if (burn < 0 || stride < 1 || n_samples < 1 || (long long)burn + (long long)n_samples * stride > INT32_MAX)
+        return fail(ctx, GDCA_EINVAL, "invalid burn, stride or n_samples");
+    if (!Xs || !accepted) return fail(ctx, GDCA_EINVAL, "null pointer");
+    bool in_lds = false;
+    if (!walk_placement(ctx, N, q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    if (N > GDCA_SAMPLE_MAX_SITES) return fail(ctx, GDCA_EINVAL, "N is larger than GDCA_SAMPLE_MAX_SITES");
+    return GDCA_OK;
+}
+
+static gdca_status check_sample(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *X, int K, int flags, double beta,
+                                int burn, int stride, int n_samples, const void *Xs, const void *accepted)
+{
+    CHK(validate_sample(ctx, N, q, K, flags, beta, burn, stride, n_samples, Xs, accepted));
+    if (!mJ || !Pi || !X) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+static gdca_status check_run_sample(gdca_ctx *ctx, const void *Z, int N, int M, int q, const void *p, const void *X, int K, int flags,
+                                    double beta, int burn, int stride, int n_samples, const void *Xs, const void *accepted)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_sample(ctx, N, q, X ? K : M, flags, beta, burn, stride, n_samples, Xs, accepted));
+    if (!Z || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+gdca_status gdca_sample_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev, int32_t K,
+                            const int8_t *mask_dev, int32_t flags, double beta, uint64_t seed, uint64_t stream0, int32_t burn,
+                            int32_t stride, int32_t n_samples, int8_t *Xs_dev, double *dE_s_dev, int32_t *accepted_dev, double *thr_dev,
+                            int32_t *moves_dev, double *V_dev)
+{
+    CHK(check_sample(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, flags, beta, burn, stride, n_samples, Xs_dev, accepted_dev));
+    CHK(begin(ctx));
+    const sample_request r{{mask_dev, flags, beta, seed, stream0, burn, stride, n_samples, Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev},
+                           V_dev};
+    CHK(sample_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, r));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                const int8_t *X_dev, int32_t K, const int8_t *mask_dev, int32_t flags, double beta, uint64_t seed,
+                                uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs_dev, double *dE_s_dev,
+                                int32_t *accepted_dev, double *thr_dev, int32_t *moves_dev, double *V_dev, gdca_stats *st)
+{
+    CHK(check_run_sample(ctx, Z_dev, N, M, q, p, X_dev, K, flags, beta, burn, stride, n_samples, Xs_dev, accepted_dev));
+    const sample_request r{{mask_dev, flags, beta, seed, stream0, burn, stride, n_samples, Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev},
+                           V_dev};
+    return run_target(ctx, Z_dev, N, M, q, p, sample_target(Z_dev, M, X_dev, K, r), st);
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -4091,6 +4194,50 @@ gdca_status gdca_run_greedy_walk(gdca_ctx *ctx, const int8_t *Z_host, int32_t N,
     CHK(sg.status());
     return sg.finish(gdca_run_greedy_walk_dev(ctx, Z_dev, N, M, q, p, X_dev, K, mask_dev, flags, min_gain, max_steps, Xout_dev, steps_dev,
                                               dE_sum_dev, path_dev, dE_path_dev, V_dev, st));
+}
+
+gdca_status gdca_sample(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                        const int8_t *mask, int32_t flags, double beta, uint64_t seed, uint64_t stream0, int32_t burn, int32_t stride,
+                        int32_t n_samples, int8_t *Xs, double *dE_s, int32_t *accepted, double *thr, int32_t *moves, double *V)
+{
+    CHK(check_sample(ctx, mJ, Pi, N, q, X, K, flags, beta, burn, stride, n_samples, Xs, accepted));
+    const size_t n = (size_t)N * (q - 1), k = (size_t)K, rows = ((size_t)burn + (size_t)n_samples * stride) * k;
+    host_stage sg(ctx);  // (ten arrays: the pool's limit)
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *X_dev = sg.in(X, (size_t)N * k);
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    int8_t *Xs_dev = sg.out(Xs, (size_t)N * n_samples * k);
+    double *dE_s_dev = sg.out(dE_s, (size_t)n_samples * k * sizeof(double));
+    int32_t *accepted_dev = sg.out(accepted, k * sizeof(int32_t));
+    double *thr_dev = sg.out(thr, rows * sizeof(double));
+    int32_t *moves_dev = sg.out(moves, rows * sizeof(int32_t));
+    double *V_dev = sg.out(V, (size_t)q * (size_t)N * k * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_sample_dev(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, mask_dev, flags, beta, seed, stream0, burn, stride, n_samples, Xs_dev,
+                                     dE_s_dev, accepted_dev, thr_dev, moves_dev, V_dev));
+}
+
+gdca_status gdca_run_sample(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                            const int8_t *X_host, int32_t K, const int8_t *mask, int32_t flags, double beta, uint64_t seed,
+                            uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs, double *dE_s, int32_t *accepted,
+                            double *thr, int32_t *moves, double *V, gdca_stats *st)
+{
+    CHK(check_run_sample(ctx, Z_host, N, M, q, p, X_host, K, flags, beta, burn, stride, n_samples, Xs, accepted));
+    const size_t k = (size_t)(X_host ? K : M), rows = ((size_t)burn + (size_t)n_samples * stride) * k;
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    int8_t *Xs_dev = sg.out(Xs, (size_t)N * n_samples * k);
+    double *dE_s_dev = sg.out(dE_s, (size_t)n_samples * k * sizeof(double));
+    int32_t *accepted_dev = sg.out(accepted, k * sizeof(int32_t));
+    double *thr_dev = sg.out(thr, rows * sizeof(double));
+    int32_t *moves_dev = sg.out(moves, rows * sizeof(int32_t));
+    double *V_dev = sg.out(V, (size_t)q * (size_t)N * k * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_run_sample_dev(ctx, Z_dev, N, M, q, p, X_dev, K, mask_dev, flags, beta, seed, stream0, burn, stride, n_samples,
+                                         Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev, V_dev, st));
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

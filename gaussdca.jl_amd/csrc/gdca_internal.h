@@ -89,7 +89,8 @@ struct gdca_tuning {
     int energy_chunk;       // GDCA_ENERGY_CHUNK: sequences one launch of the energy gather kernel takes; 0 = as many as keep its partials within ~256 MB
     int pair_chunk;         // GDCA_PAIR_CHUNK: sequences of protein A one launch of the pair-energy fold / gather kernels takes; 0 = as many as keep their folded rows within ~256 MB (the rule), a smaller count is taken as given, a larger one is cut to the rule
     int epi_generic;        // GDCA_EPI_GENERIC (tests, measurements): 1 = the double-mutant scan runs its generic instance (s at run time) at s = 20 too
-    int walk_table;         // GDCA_WALK_TABLE: where the greedy walk keeps a sequence's table of site potentials: 0 = in LDS where it fits, else in HBM (auto, default), 1 = LDS (a table that does not fit: GDCA_EINVAL), 2 = HBM; the same bits wherever it is
+    int walk_table;         // GDCA_WALK_TABLE: where the greedy walk keeps a sequence's table of site potentials: 0 = in LDS where it fits, else in HBM (auto, default), 1 = LDS (a table that does not fit: GDCA_EINVAL), 2 = HBM; the same bits wherever it is (the Metropolis chains share it)
+    int sample_chunk;       // GDCA_SAMPLE_CHUNK: proposals one launch of the Metropolis kernel takes; 0 = GDCA_SAMPLE_CHUNK_RULE; the same bits whatever it is
     char sweep_trace[256];  // GDCA_SWEEP_TRACE: file the in-kernel trace of the next inverse is written to ("" = off)
 };
 void gdca_tuning_from_env(gdca_tuning *t);
@@ -393,3 +394,28 @@ bool gdca_walk_table_fits(int N, int q);  // the instance with the table in LDS 
 hipError_t gdca_launch_greedy_walk(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
                                    const int8_t *mask, int flags, double min_gain, int max_steps, double *V, bool table_in_lds, bool write_table,
                                    int8_t *Xout, int32_t *steps, double *dE_sum, int32_t *path, double *dE_path);
+
+// ---- k_sample.hip: Metropolis chains -- one workgroup a chain proposes single substitutions and accepts them at inverse temperature beta ---
+// (include/gdca.h, Metropolis chains).  Xg, V, A, ld, sign as the walk's; the table is placed by the walk's rule (gdca_walk_table_fits:
+// the LDS instance keeps the N s residue entries only, the gap's +0.0 is in the code, so what fits there fits here).
+#define GDCA_SAMPLE_CHUNK_RULE 65536  // proposals a launch
+struct gdca_sample_plan {
+    const int8_t *mask;           // [N] or nullptr
+    int flags;
+    double beta;
+    unsigned long long seed, stream0;
+    int burn, stride, n_samples;  // n_steps = burn + n_samples * stride
+    int8_t *Xs;                   // [K][n_samples][N]
+    double *dE_s;                 // [K][n_samples] or nullptr
+    int32_t *accepted;            // [K]: the count so far between two launches
+    double *thr;                  // [K][n_steps] or nullptr
+    int32_t *moves;               // [K][n_steps] or nullptr
+};
+size_t gdca_sample_lds_bytes(int N, int q, bool table_in_lds);
+// what a chain keeps in HBM between two launches beside its table and `accepted`: the running sums (K doubles), then the symbols (K N bytes)
+size_t gdca_sample_state_bytes(int N, int K);
+// The proposals t0 .. t1 - 1 of every chain; t0 == 0 starts from Xg, a later launch from `state`.  table_in_lds: the table is copied
+// to LDS and written back to V at the end of the launch, else it is updated in place.  An error: the table or the site list does not
+// fit, or the dynamic LDS limit could not be raised; nothing was launched
+hipError_t gdca_launch_sample(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
+                              const gdca_sample_plan &plan, int t0, int t1, double *V, bool table_in_lds, void *state);

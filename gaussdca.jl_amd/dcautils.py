@@ -650,6 +650,74 @@ def greedy_walk(mJ, Pi, X, q: int = 21, max_steps=None, min_gain: float = 0.0, m
     return ctx.walk_result(out)
 
 
+def _sample_args(N, q, beta, burn, stride, n_samples, seed, stream0, mask, gaps):
+    """the rule's parameters of the Metropolis chains, checked: (beta, burn, stride, n_samples, seed, stream0, mask int8 (N,) or None,
+    flags); burn None: 10 sweeps, stride None: one sweep (a sweep is N proposals)"""
+    try:
+        beta = float(beta)
+    except (TypeError, ValueError):
+        raise ArgumentError(f"invalid beta value: {beta} (must be a finite number >= 0)") from None
+    if not (beta >= 0.0 and np.isfinite(beta)):
+        raise ArgumentError(f"invalid beta value: {beta} (must be a finite number >= 0)")
+    burn = 10 * N if burn is None else burn
+    stride = N if stride is None else stride
+    for v, name, lo in ((burn, "burn", 0), (stride, "stride", 1), (n_samples, "n_samples", 1)):
+        if not isinstance(v, (int, np.integer)) or v < lo:
+            raise ArgumentError(f"invalid {name} value: {v} (must be an integer >= {lo})")
+    if int(burn) + int(n_samples) * int(stride) > 2**31 - 1:
+        raise ArgumentError(f"burn + n_samples * stride = {int(burn) + int(n_samples) * int(stride)} proposals are more than 2^31 - 1")
+    for v, name in ((seed, "seed"), (stream0, "stream0")):
+        if not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2**64:
+            raise ArgumentError(f"invalid {name} value: {v} (must be an integer between 0 and 2^64 - 1)")
+    if (int(q) if gaps else int(q) - 1) < 2:
+        raise ArgumentError(f"q = {q} leaves fewer than two target symbols")
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.shape != (N,) or not (m.dtype == np.bool_ or np.issubdtype(m.dtype, np.integer)):
+            raise ArgumentError(f"mask must be a vector of {N} booleans or integers, one per site")
+        mask = np.ascontiguousarray(m != 0, dtype=np.int8)
+    return beta, int(burn), int(stride), int(n_samples), int(seed), int(stream0), mask, (_lib.SAMPLE_GAPS if gaps else 0)
+
+
+def sample(mJ, Pi, X, q: int = 21, beta: float = 1.0, burn=None, stride=None, n_samples: int = 1, seed: int = 0, stream0: int = 0, mask=None,
+           gaps: bool = False, trace: bool = False, table: bool = False, ctx=None):
+    """Metropolis chains under the Gaussian model (mJ, Pi): one chain starts from each of the K columns of X (shape (N, K) like Z,
+    symbols 1..q, q = the gap) and draws sequences from exp(-beta E(x)) / Z.  A proposal picks a site that may change and another
+    symbol for it, both uniformly; with dE the energy change ``mutation_scan`` would give for the CURRENT sequence it is accepted iff
+    ``beta * dE <= -log(u)``, u uniform in (0, 1].  ONE SWEEP IS N PROPOSALS: a chain runs ``burn`` proposals (default 10 N) and then
+    returns its state after every ``stride`` (default N) more, ``n_samples`` times.  ``mask``: N booleans, the sites that may change
+    (default all); ``gaps``: the gap is a symbol like any other (default: residues change into residues, gaps stay gaps).  The random
+    numbers are a function of ``(seed, stream0 + k, proposal)``: chain k of a call is the chain a call with ``stream0 + k`` alone runs.
+
+    Returns ``(Xs (N, n_samples, K) int8, dE_s (K, n_samples), accepted (K,) int32)`` -- ``Xs.reshape(N, -1, order="F")`` is an
+    alignment of the n_samples K samples, chain by chain; ``dE_s`` the energy of each sample minus its chain's start's (the running sum
+    of the accepted dE); ``accepted`` the accepted proposals of each chain --; with ``trace=True`` also ``thr (K, n_steps)``, the
+    thresholds -log(u), and ``moves (K, n_steps)`` int32, the proposal's code ``site * q + symbol`` (both 0-based) if accepted and
+    ``-1 - code`` if not; with ``table=True`` also ``V (K, N, q)``, the site potentials as the chain left them.  mJ must be symmetric
+    (its lower triangle is read)."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    Xf = _symbols(X, "X")
+    N, K = Xf.shape
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = N * (int(q) - 1)
+    if N < 1 or mJ.shape != (n, n) or Pi.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: X has N = {N} sites, q = {q}, so mJ must be {n} x {n} and Pi have {n} entries "
+                            f"(got {mJ.shape} and {Pi.shape})")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    beta, burn, stride, S, seed, stream0, m, flags = _sample_args(N, q, beta, burn, stride, n_samples, seed, stream0, mask, gaps)
+    ctx = ctx or default_context()
+    out = ctx.sample_outputs(N, K, q, burn, stride, S, trace, table)
+    opt = lambda a: None if a is None else _lib._p(a)  # noqa: E731
+    ctx.check(ctx.lib.gdca_sample(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xf), K, opt(m), flags, beta, seed, stream0, burn, stride,
+                                  S, *[opt(a) for a in out]))
+    return ctx.sample_result(out)
+
+
 def _double_model_args(mJ, Pi, X, q):
     """the model and the sequences of the double-mutant operators, checked: (mJ, Pi, Xf, N, K)"""
     mJ = np.ascontiguousarray(mJ, dtype=np.float64)

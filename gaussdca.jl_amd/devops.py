@@ -181,6 +181,32 @@ def greedy_walk_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, max_step
     return dXout, dsteps, ddE_sum, dpath, ddE_path, dV
 
 
+def sample_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, beta: float, burn: int, stride: int, n_samples: int, seed: int = 0,
+               stream0: int = 0, dmask=None, flags: int = 0, dXs=None, daccepted=None, ddE_s=None, dthr=None, dmoves=None, dV=None,
+               want=("dE_s",)):
+    """Metropolis chains from the K sequences X (N x K int8) with every array in HBM (gdca_sample_dev): n_steps = burn + n_samples *
+    stride proposals a chain, accepted iff beta * dE <= -log(u); flags = _lib.SAMPLE_GAPS or 0, dmask N int8 or None.  Xs (N x n_samples
+    x K int8) and accepted (K int32) are always made; ``want`` names the optional outputs a buffer is made for where none is given:
+    "dE_s" (n_samples x K f64), "thr" (n_steps x K f64), "moves" (n_steps x K int32), "V" (q N K f64: the final tables).  Returns
+    (dXs, daccepted, ddE_s, dthr, dmoves, dV), None for what was not wanted."""
+    K, S = int(K), int(n_samples)
+    T = int(burn) + S * int(stride)
+    dXs = dXs or DeviceBuffer(ctx, max(N * S * K, 1))
+    daccepted = daccepted or DeviceBuffer(ctx, 4 * max(K, 1))
+    if "dE_s" in want:
+        ddE_s = ddE_s or DeviceBuffer(ctx, 8 * max(S * K, 1))
+    if "thr" in want:
+        dthr = dthr or DeviceBuffer(ctx, 8 * max(T * K, 1))
+    if "moves" in want:
+        dmoves = dmoves or DeviceBuffer(ctx, 4 * max(T * K, 1))
+    if "V" in want:
+        dV = dV or DeviceBuffer(ctx, 8 * int(q) * N * max(K, 1))
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.sample_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), opt(dX), K, opt(dmask), int(flags), float(beta), int(seed), int(stream0),
+                   int(burn), int(stride), S, opt(dXs), opt(daccepted), opt(ddE_s), opt(dthr), opt(dmoves), opt(dV))
+    return dXs, daccepted, ddE_s, dthr, dmoves, dV
+
+
 def scores_stepwise(Z, q: int, pseudocount: float = 0.8, theta=":auto", score: str = "frob", ctx: Context = None
                     ) -> Tuple[np.ndarray, dict]:
     """The six statements of src/GaussDCA.jl:28-42 one by one, arrays resident in HBM.  Z: (N, M) int8.

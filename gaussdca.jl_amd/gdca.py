@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, default_context
-from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _walk_args, _mutations_arg, decode_double_code, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
+from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _walk_args, _sample_args, _mutations_arg, decode_double_code, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
                        remove_duplicate_sequences, species_blocks)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
@@ -460,6 +460,38 @@ def gDCA_greedy_walk(filename: str, sequences=None, max_steps=None, min_gain: fl
 
     return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N), run,
                            "walks")
+
+
+def gDCA_sample(filename: str, starts=None, beta: float = 1.0, burn=None, stride=None, n_samples: int = 1, seed: int = 0, stream0: int = 0,
+                mask=None, gaps: bool = False, trace: bool = False, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+                remove_dups: bool = False, ctx=None, **kw):
+    """Sequences drawn from the Gaussian model gDCA fits to the alignment in ``filename`` (the fit and its arguments are
+    ``gDCA_mutation_scan``'s): one Metropolis chain starts from each sequence of ``starts`` and samples exp(-beta E(x)) / Z.  A
+    proposal picks a site and another symbol for it, both uniformly, and is accepted iff ``beta * dE <= -log(u)`` with dE its energy
+    change and u uniform in (0, 1].  ONE SWEEP IS N PROPOSALS: a chain runs ``burn`` proposals (default 10 N), then returns its state
+    after every ``stride`` (default N) more, ``n_samples`` times.  ``mask``, ``gaps``, ``seed``, ``stream0`` as ``dcautils.sample``.
+
+    ``starts`` as ``sequences`` for ``gDCA_energies``: ``None`` starts a chain from each of the alignment's own sequences (after the
+    gap filter and the optional deduplication); an ``(N, K)`` int8 array (symbols 1..q like ``Z``) from its columns; a string names a
+    second FASTA file, read with ``max_gap_fraction = 1.0`` so every record is kept.
+
+    Returns ``(Xs (N, n_samples, K) int8, dE_s (K, n_samples), accepted (K,))``; with ``trace=True`` also ``thr, moves`` (K, n_steps)
+    each.  ``Xs.reshape(N, -1, order="F")`` is an alignment (N x n_samples K, chain by chain) that can be handed to ``gDCA_energies`` or
+    ``compute_weighted_frequencies`` as it lies; ``dE_s`` is each sample's energy minus its start's.  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_sample() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    X = _sequences_arg(starts, "starts", "an N x K")
+
+    def run(c, ptr, N, M, q):
+        b, bu, sd, S, sd0, st0, m, flags = _sample_args(N, q, beta, burn, stride, n_samples, seed, stream0, mask, gaps)
+        return c.run_sample_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), *_ptr_count(X), mask=m, flags=flags, beta=b, seed=sd0,
+                                stream0=st0, burn=bu, stride=sd, n_samples=S, trace=trace)
+
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N), run,
+                           "samples")
 
 
 def _required_sequences(sequences, name):

@@ -185,7 +185,8 @@ gdca_status gdca_ctx_set_timing(gdca_ctx *ctx, int32_t enabled);
  * kernel takes, 0 = the rule [default]: the same bits whatever it is); PAIR_CHUNK (sequences of protein A one launch of the pair-energy
  * kernels takes, 0 = the rule [default: a ~256 MB buffer]; a count above the rule's is cut to it: the same bits whatever it is); WALK_TABLE (auto | lds | hbm: where the greedy walk keeps a
  * sequence's table of site potentials -- auto [default]: in LDS where it fits, else in HBM; lds with a table that does not fit makes the
- * walk fail with GDCA_EINVAL; the same bits wherever it is).  The schedule switches change results
+ * walk fail with GDCA_EINVAL; the same bits wherever it is; the Metropolis chains place their table by the same rule and the same option);
+ * SAMPLE_CHUNK (proposals one launch of the Metropolis kernel takes, 0 = the rule [default]: 65536; the same bits whatever it is).  The schedule switches change results
  * at rounding level at most (another summation order); REFINE improves an ill-conditioned inverse.  GDCA_EINVAL: unknown key
  * or unusable value. */
 gdca_status gdca_ctx_set_option(gdca_ctx *ctx, const char *key, const char *value);
@@ -676,6 +677,68 @@ gdca_status gdca_run_greedy_walk_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t
                                      int32_t max_steps, int8_t *Xout_dev, int32_t *steps_dev, double *dE_sum_dev, int32_t *path_dev,
                                      double *dE_path_dev, double *V_dev, gdca_stats *st);
 
+/* ---- Metropolis chains: sequences drawn from the model at an inverse temperature beta ------------------------------------------
+ * K chains, each a Markov chain of single substitutions whose stationary distribution is exp(-beta E(x)) / Z over its state space:
+ * artificial homologues, a thermal ensemble around a wild type, an annealing step (a caller chains calls with the final table V).
+ * Conventions as in the greedy-walk section: s = q - 1, r(i, c), the gap q has no row and V[i][q] = +0.0, only the lower triangle of
+ * mJ is read, K(j,c; i,b) = mJ[r(j,c), r(i,b)] and +0.0 where b == q; the fused forms read -mJ and negate exactly.
+ * STATE per chain: the current symbols x (N) and the table V, which starts as the bits gdca_mutation_scan(.., GDCA_MUT_POTENTIAL)
+ * returns for the start sequence X[:, k].
+ * STATE SPACE.  flags = 0: residues change into residues, gaps stay gaps.  GDCA_SAMPLE_GAPS: the gap is a symbol like any other.  No
+ * other flag bit exists (the walk's two one-way flags would break detailed balance).  T = the number of target symbols: s without
+ * the flag, q with it.  sites = the ascending list of the sites i with mask == NULL or mask[i] != 0 and -- without the flag --
+ * x_i != q; it cannot change along a chain.  n_sites == 0: nothing is ever accepted and every sample is the start.
+ * RANDOM NUMBERS: counter-based SplitMix64 with random access, all arithmetic mod 2^64, G = 0x9E3779B97F4A7C15:
+ *     mix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  return z ^ z >> 31
+ *     key(seed, stream) = mix64(mix64(seed + G) + (stream + 1) * G)
+ *     draw(key, c)      = mix64(key + (c + 1) * G),  c = 0, 1, 2, ...
+ * Chain k of a call uses stream = stream0 + k; proposal t (0-based, counted over the whole chain) uses r0 = draw(key, 2 t) and
+ * r1 = draw(key, 2 t + 1).  Known answers: key(0, 0) = 0xa706dd2f4d197e6f with the draws 0x238275bc38fcbe91, 0xf89a2566b5822c54,
+ * 0x47200e1d9780fa44; key(1, 0) = 0x5e41ab087439611e with 0xb18a02f46d8d86c3, 0xf8c5b62c83f707e8; key(1, 5) = 0xc63f062c5c30e3d4
+ * with 0xfdba48dbc8c4fa9a; key(2^64 - 1, 2^63) = 0xf7f1454e6a8a1fa6 with 0xe447897adec0a36e.
+ * A PROPOSAL: m = ((r0 >> 32) * n_sites) >> 32 and i = sites[m]; v = ((r0 & 0xffffffff) * (T - 1)) >> 32; a = the 0-based symbol of
+ * x_i; the target is b = v + (v >= a), uniform over the T - 1 other symbols (the bias of either multiply-shift is below
+ * 2^-32 max(n_sites, T)).  u = ((r1 >> 11) + 1) * 2^-53, in (0, 1]; thr = -log(u), the one transcendental of a step.
+ * dE = V[i][b] - V[i][a], ONE f64 subtraction as in the walk.  ACCEPT iff beta * dE <= thr: one f64 multiplication, one comparison; a
+ * NaN on the left never accepts; at beta = 0 every finite dE accepts.  On acceptance x_i = b, dE is added to the chain's running sum
+ * (one thread, step order), and every other site's potentials are updated with the walk's two operations,
+ *     V[j][c] = V[j][c] + (K(j,c; i,b) - K(j,c; i,a)),  j != i, c in 1..s;                 site i's own row is not touched.
+ * LENGTH: n_steps = burn + n_samples * stride proposals, burn >= 0, stride >= 1, n_samples >= 1, n_steps <= INT32_MAX.  Sample j
+ * is the state after proposal burn + (j + 1) * stride - 1.
+ * OUTPUTS (K chains, X N x K int8 column-major):
+ *     Xs        N x n_samples x K int8, column-major: sample j of chain k is the N bytes at ((k * n_samples) + j) * N -- itself an
+ *               N x (n_samples K) alignment, as gdca_energies or gdca_frequencies take one; must not overlap X or Z;
+ *     dE_s      n_samples x K f64: the running sum of the accepted dE at the moment of the sample, so E(sample) ~ E(start) + dE_s;
+ *               may be NULL;
+ *     accepted  K int32: the accepted proposals over all n_steps;
+ *     thr       n_steps x K f64: the thresholds as the device computed them; may be NULL;
+ *     moves     n_steps x K int32: the proposal's code i q + b (b 0-based, the walk's code) if accepted, -1 - code if rejected,
+ *               INT32_MIN where n_sites == 0; may be NULL;
+ *     V         q x N x K f64 in gdca_mutation_scan's layout: the final table; may be NULL.
+ * ORDER: one thread updates an entry, one thread keeps the sum, the random numbers are functions of (seed, stream, t), no
+ * floating-point atomics.  The bits of everything a chain returns depend on the initial table's bits, the model, x_k, mask, flags,
+ * beta, seed, the chain's stream number, burn, stride, n_samples and the values of thr -- not on K or where the chain stands in the
+ * batch (a batch stream0 .. stream0 + K - 1 is its chains run one at a time with stream0 + k), on where the table lives (context
+ * option WALK_TABLE, shared with the walk), or on how the chain is cut into launches (context option SAMPLE_CHUNK).  Without V the
+ * stage keeps the tables in the double-mutant scan's context workspace of q N K doubles.
+ * GDCA_EINVAL, nothing run: K < 1 or K > INT32_MAX - 256, q outside 2..31, T < 2 (q = 2 without the flag), beta < 0, NaN or
+ * infinite, burn < 0, stride < 1, n_samples < 1, n_steps > INT32_MAX, a flags bit other than GDCA_SAMPLE_GAPS, a null X (operator
+ * form), Xs or accepted, WALK_TABLE = lds with a table that does not fit, N > GDCA_SAMPLE_MAX_SITES (the site list is kept in LDS).  A byte of X
+ * outside 1..q is detected on the device before anything is indexed with it.  On failure the outputs are unspecified.  Synchronous. */
+enum { GDCA_SAMPLE_GAPS = 1 };
+#define GDCA_SAMPLE_MAX_SITES 54000
+gdca_status gdca_sample_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *X_dev, int32_t K,
+                            const int8_t *mask_dev, int32_t flags, double beta, uint64_t seed, uint64_t stream0, int32_t burn,
+                            int32_t stride, int32_t n_samples, int8_t *Xs_dev, double *dE_s_dev, int32_t *accepted_dev, double *thr_dev,
+                            int32_t *moves_dev, double *V_dev);
+/* Fused, exactly as gdca_run_greedy_walk_dev (a refinement or fallback at collect time samples again on the inverse finally used).
+ * X == NULL starts one chain from each of Z's own M sequences (K is then ignored).  Stats: ms_score is the stage (the scan and the
+ * chains), ms_fn 0. */
+gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                const int8_t *X_dev, int32_t K, const int8_t *mask_dev, int32_t flags, double beta, uint64_t seed,
+                                uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs_dev, double *dE_s_dev,
+                                int32_t *accepted_dev, double *thr_dev, int32_t *moves_dev, double *V_dev, gdca_stats *st);
+
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* A host-pointer form on a context with an enqueued run (gdca_run_dev_async, gdca_run_ranked_async, ...) is refused (GDCA_EINVAL)
  * before it touches the context: nothing is uploaded or reallocated, and the enqueued run is unaffected. */
@@ -785,6 +848,15 @@ gdca_status gdca_greedy_walk(gdca_ctx *ctx, const double *mJ, const double *Pi, 
 gdca_status gdca_run_greedy_walk(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
                                  const int8_t *X_host, int32_t K, const int8_t *mask, int32_t flags, double min_gain, int32_t max_steps,
                                  int8_t *Xout, int32_t *steps, double *dE_sum, int32_t *path, double *dE_path, double *V, gdca_stats *st);
+
+/* Metropolis chains with host pointers: upload, the _dev form, download */
+gdca_status gdca_sample(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *X, int32_t K,
+                        const int8_t *mask, int32_t flags, double beta, uint64_t seed, uint64_t stream0, int32_t burn, int32_t stride,
+                        int32_t n_samples, int8_t *Xs, double *dE_s, int32_t *accepted, double *thr, int32_t *moves, double *V);
+gdca_status gdca_run_sample(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                            const int8_t *X_host, int32_t K, const int8_t *mask, int32_t flags, double beta, uint64_t seed,
+                            uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs, double *dE_s, int32_t *accepted,
+                            double *thr, int32_t *moves, double *V, gdca_stats *st);
 
 /* ---- host-side utilities around the hot path (plain C++, no GPU): the reference's callers of the path -------- */
 /* CPUs this process can really use: hardware threads capped by the cgroup CPU quota (a container may see 256 threads and be given
