@@ -276,6 +276,20 @@ SYMBOLS = {
     "gdca_run_sample": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_potts_from_gaussian_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_potts_from_gaussian": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_bm_update_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
+                                     C.c_double]),
+    "gdca_bm_update": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
+                                 C.c_double]),
+    "gdca_bm_readout_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_bm_readout": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gdca_bm_learn_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                    C.c_void_p, C.c_void_p]),
+    "gdca_bm_learn": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                C.c_void_p, C.c_void_p]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -890,6 +904,32 @@ class Context:
         st = self._run_readout(self.lib.gdca_run_sample, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), opt(mask), int(flags),
                                float(beta), int(seed), int(stream0), int(burn), int(stride), int(n_samples), *[opt(a) for a in out])
         return self.sample_result(out), st
+
+    # ---- Boltzmann-machine refinement of the Potts model (W, zeros) the chains draw from (gdca_potts_from_gaussian*, gdca_bm_*) ----
+    def potts_from_gaussian_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, W_ptr: int) -> None:
+        """gdca_potts_from_gaussian_dev: mJ (n x n), Pi (n) -> W (n x n; not mJ), device pointers"""
+        self.check(self.lib.gdca_potts_from_gaussian_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), C.c_void_p(W_ptr)))
+
+    def bm_update_dev(self, W_ptr: int, Pij_d_ptr: int, Pij_m_ptr: int, N: int, q: int, eta: float, lam: float = 0.0,
+                      Pi_d_ptr: int | None = None, Pi_m_ptr: int | None = None) -> None:
+        """gdca_bm_update_dev: one gradient step on W (n x n) in place from the data's and the model's Pij (n x n), device pointers"""
+        self.check(self.lib.gdca_bm_update_dev(self.h, C.c_void_p(W_ptr), self._opt(Pi_d_ptr), C.c_void_p(Pij_d_ptr), self._opt(Pi_m_ptr),
+                                               C.c_void_p(Pij_m_ptr), int(N), int(q), float(eta), float(lam)))
+
+    def bm_readout_dev(self, Pi_d_ptr: int, Pij_d_ptr: int, Pi_m_ptr: int, Pij_m_ptr: int, N: int, q: int, out4_ptr: int) -> None:
+        """gdca_bm_readout_dev: the fit of the model's tallies to the data's in four f64 at out4 (a device pointer like the rest)"""
+        self.check(self.lib.gdca_bm_readout_dev(self.h, C.c_void_p(Pi_d_ptr), C.c_void_p(Pij_d_ptr), C.c_void_p(Pi_m_ptr),
+                                                C.c_void_p(Pij_m_ptr), int(N), int(q), C.c_void_p(out4_ptr)))
+
+    def bm_learn_dev(self, W_ptr: int, Pi_d_ptr: int, Pij_d_ptr: int, N: int, q: int, X_ptr: int, K: int, mask_ptr: int | None, flags: int,
+                     beta: float, seed: int, iter0: int, n_iter: int, burn: int, stride: int, n_samples: int, eta: float, lam: float,
+                     trace_ptr: int, Xs_last_ptr: int | None = None) -> None:
+        """gdca_bm_learn_dev: n_iter iterations of sample, tally, read out, update on W (n x n) and the chains X (N x K int8), both
+        in place; trace (4 x n_iter f64) and the optional Xs_last (N x n_samples x K int8) are device pointers like the rest."""
+        self.check(self.lib.gdca_bm_learn_dev(self.h, C.c_void_p(W_ptr), C.c_void_p(Pi_d_ptr), C.c_void_p(Pij_d_ptr), int(N), int(q),
+                                              self._opt(X_ptr), int(K), self._opt(mask_ptr), int(flags), float(beta), int(seed), int(iter0),
+                                              int(n_iter), int(burn), int(stride), int(n_samples), float(eta), float(lam),
+                                              self._opt(trace_ptr), self._opt(Xs_last_ptr)))
 
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):

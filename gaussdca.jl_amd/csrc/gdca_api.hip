@@ -292,6 +292,9 @@ struct gdca_ctx {
     gdca_buf IPAws, IPAcnt, IPAZ, IPAsel, IPAm, IPAg, IPAprev, IPAsp;
     gdca_buf DMd;             // double-mutant scan (k_epistasis.hip): dE of every single substitution of its sequences, q N K doubles
     gdca_buf SMst;            // Metropolis chains (k_sample.hip): what a chain keeps between two launches, gdca_sample_state_bytes
+    // Boltzmann-machine refinement (k_bm.hip): the loop's workspace (bm_plan: the model's tallies, the zero Pi, the unit weights, the
+    // counts, the samples), and the read-out's column partials
+    gdca_buf BMws, BMred;
     int ncu;                  // compute units of the device
     double *piv;              // the pivots of the context's last inverse, n_pad doubles inside Sg (inverse_job)
     // log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet): kept on the host, so that entry points
@@ -746,7 +749,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
                         &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
                         &ctx->LOa, &ctx->LOb, &ctx->PBN,
-                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst};
+                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst, &ctx->BMws, &ctx->BMred};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     ctx->staging.release();
@@ -1122,15 +1125,28 @@ static void note_logdet(gdca_ctx *ctx, int k = 0)
 
 // What the energies and the mutation scan open with: the K sequences X (N x K) packed into ctx->Xg (illegal bytes: sc->bad_symbol
 // bit 2), g = mJ Pi in ctx->gvec and c0 = Pi' g behind it.
+static gdca_status g_room(gdca_ctx *ctx, int n)
+{
+    const int nb = gdca_energy_gblocks(n);
+    CHK(ensure(ctx, ctx->gpart, (size_t)nb * nb * 64 * sizeof(double)));
+    return ensure(ctx, ctx->gvec, ((size_t)n + 1) * sizeof(double));
+}
+
+// g = mJ Pi of the model m into ctx->gvec, c0 behind it (g_room first): the one g of the library -- the energies', the mutation
+// stage's and the Potts warm start's (gdca_potts_from_gaussian_dev)
+static void g_launch(gdca_ctx *ctx, const gdca_model &m)
+{
+    const int n = m.N * (m.q - 1);
+    double *g = (double *)ctx->gvec.p;
+    gdca_launch_energy_g(ctx->stream, m.A, m.ld, m.sign, n, m.Pi, (double *)ctx->gpart.p, g, g + n);
+}
+
 static gdca_status pack_and_g(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, size_t stride = 0)
 {
-    const int n = m.N * (m.q - 1), nb = gdca_energy_gblocks(n);
     CHK(ensure(ctx, ctx->Xg, (size_t)gdca_energy_blocks(m.N) * K * sizeof(uint32_t)));
-    CHK(ensure(ctx, ctx->gpart, (size_t)nb * nb * 64 * sizeof(double)));
-    CHK(ensure(ctx, ctx->gvec, ((size_t)n + 1) * sizeof(double)));
-    double *g = (double *)ctx->gvec.p;
+    CHK(g_room(ctx, m.N * (m.q - 1)));
     gdca_launch_energy_pack(ctx->stream, X_dev, stride ? stride : (size_t)m.N, m.N, K, m.q, (uint32_t *)ctx->Xg.p, (gdca_dev_scalars *)ctx->sc.p);
-    gdca_launch_energy_g(ctx->stream, m.A, m.ld, m.sign, n, m.Pi, (double *)ctx->gpart.p, g, g + n);
+    g_launch(ctx, m);
     return GDCA_OK;
 }
 
@@ -3662,6 +3678,158 @@ gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, i
     return run_target(ctx, Z_dev, N, M, q, p, sample_target(Z_dev, M, X_dev, K, r), st);
 }
 
+// ---- Boltzmann-machine refinement (k_bm.hip; include/gdca.h): the warm start, the update, the read-out and the loop ----
+static gdca_status check_potts(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *W)
+{
+    CHK(validate(ctx, N, 1, q));
+    if (!mJ || !Pi || !W) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (mJ == W) return fail(ctx, GDCA_EINVAL, "W may not alias mJ");
+    return GDCA_OK;
+}
+
+static gdca_status check_bm_rates(gdca_ctx *ctx, double eta, double lambda)
+{
+    if (!(eta > 0.0) || !std::isfinite(eta)) return fail(ctx, GDCA_EINVAL, "invalid eta");
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(ctx, GDCA_EINVAL, "invalid lambda");
+    return GDCA_OK;
+}
+
+static gdca_status check_bm_update(gdca_ctx *ctx, const void *W, const void *Pij_d, const void *Pij_m, int N, int q, double eta, double lambda)
+{
+    CHK(validate(ctx, N, 1, q));
+    if (!W || !Pij_d || !Pij_m) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return check_bm_rates(ctx, eta, lambda);
+}
+
+static gdca_status check_bm_readout(gdca_ctx *ctx, const void *Pi_d, const void *Pij_d, const void *Pi_m, const void *Pij_m, int N, int q,
+                                    const void *out)
+{
+    CHK(validate(ctx, N, 1, q));
+    if (!Pi_d || !Pij_d || !Pi_m || !Pij_m || !out) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+// the loop's arguments: validate_sample's, the rates, the iteration range; nothing has run when one fails
+static gdca_status check_bm_learn(gdca_ctx *ctx, const void *W, const void *Pi_d, const void *Pij_d, int N, int q, const void *X, int K,
+                                  int flags, double beta, uint64_t iter0, int n_iter, int burn, int stride, int n_samples, double eta,
+                                  double lambda, const void *trace)
+{
+    CHK(validate_sample(ctx, N, q, K, flags, beta, burn, stride, n_samples, W, W));  // (Xs and accepted are the loop's own)
+    if (!W || !Pi_d || !Pij_d || !X || !trace) return fail(ctx, GDCA_EINVAL, "null pointer");
+    CHK(check_bm_rates(ctx, eta, lambda));
+    if (n_iter < 1) return fail(ctx, GDCA_EINVAL, "invalid n_iter");
+    if ((long long)K * n_samples > INT32_MAX) return fail(ctx, GDCA_EINVAL, "K n_samples is larger than INT32_MAX");
+    // iteration t draws from the streams t K .. t K + K - 1
+    if (((unsigned __int128)iter0 + (unsigned)n_iter) * (unsigned __int128)(unsigned)K > (unsigned __int128)UINT64_MAX)
+        return fail(ctx, GDCA_EINVAL, "(iter0 + n_iter) K overflows the stream numbers");
+    return GDCA_OK;
+}
+
+gdca_status gdca_potts_from_gaussian_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, double *W_dev)
+{
+    CHK(check_potts(ctx, mJ_dev, Pi_dev, N, q, W_dev));
+    CHK(not_pending(ctx));
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(g_room(ctx, N * (q - 1)));
+    g_launch(ctx, operator_model(mJ_dev, Pi_dev, N, q));
+    gdca_launch_bm_from_gaussian(ctx->stream, mJ_dev, (const double *)ctx->gvec.p, N, q - 1, W_dev);
+    return check_launch(ctx, "Potts warm start");
+}
+
+gdca_status gdca_bm_update_dev(gdca_ctx *ctx, double *W_dev, const double *Pi_d_dev, const double *Pij_d_dev, const double *Pi_m_dev,
+                               const double *Pij_m_dev, int32_t N, int32_t q, double eta, double lambda)
+{
+    (void)Pi_d_dev, (void)Pi_m_dev;  // (the diagonal works through Pij alone)
+    CHK(check_bm_update(ctx, W_dev, Pij_d_dev, Pij_m_dev, N, q, eta, lambda));
+    CHK(not_pending(ctx));
+    HIPCHK(hipSetDevice(ctx->device));
+    gdca_launch_bm_update(ctx->stream, W_dev, Pij_d_dev, Pij_m_dev, N, q - 1, eta, lambda);
+    return check_launch(ctx, "Boltzmann-machine update");
+}
+
+static gdca_status bm_readout_stage(gdca_ctx *ctx, const double *Pi_d, const double *Pij_d, const double *Pi_m, const double *Pij_m, int N, int q,
+                                    double *out, bool zero3)
+{
+    CHK(ensure(ctx, ctx->BMred, gdca_bm_readout_bytes(N * (q - 1))));
+    gdca_launch_bm_readout(ctx->stream, Pi_d, Pij_d, Pi_m, Pij_m, N, q - 1, (double *)ctx->BMred.p, out, zero3);
+    return check_launch(ctx, "Boltzmann-machine read-out");
+}
+
+gdca_status gdca_bm_readout_dev(gdca_ctx *ctx, const double *Pi_d_dev, const double *Pij_d_dev, const double *Pi_m_dev,
+                                const double *Pij_m_dev, int32_t N, int32_t q, double *out4_dev)
+{
+    CHK(check_bm_readout(ctx, Pi_d_dev, Pij_d_dev, Pi_m_dev, Pij_m_dev, N, q, out4_dev));
+    CHK(not_pending(ctx));
+    HIPCHK(hipSetDevice(ctx->device));
+    return bm_readout_stage(ctx, Pi_d_dev, Pij_d_dev, Pi_m_dev, Pij_m_dev, N, q, out4_dev, true);
+}
+
+// where the loop's arrays lie in ctx->BMws (each at a multiple of 256 bytes): the model's tallies Pij_m (n x n) and Pi_m (n), the zero
+// Pi of the container (n), the unit weights (K n_samples), the chains' counts (K), the samples (N x n_samples x K; not where the caller
+// gives Xs_last)
+struct bm_plan {
+    size_t pij, pi, zero, ones, acc, xs, bytes;
+    bm_plan(int n, int N, int K, int S, bool own_xs)
+    {
+        size_t at = 0;
+        auto take = [&](size_t b) {
+            const size_t here = at;
+            at += (b + 255) & ~(size_t)255;
+            return here;
+        };
+        pij = take((size_t)n * n * sizeof(double));
+        pi = take((size_t)n * sizeof(double));
+        zero = take((size_t)n * sizeof(double));
+        ones = take((size_t)K * S * sizeof(double));
+        acc = take((size_t)K * sizeof(int32_t));
+        xs = take(own_xs ? (size_t)N * S * K : 0);
+        bytes = at;
+    }
+};
+
+gdca_status gdca_bm_learn_dev(gdca_ctx *ctx, double *W_dev, const double *Pi_d_dev, const double *Pij_d_dev, int32_t N, int32_t q,
+                              int8_t *X_dev, int32_t K, const int8_t *mask_dev, int32_t flags, double beta, uint64_t seed, uint64_t iter0,
+                              int32_t n_iter, int32_t burn, int32_t stride, int32_t n_samples, double eta, double lambda, double *trace_dev,
+                              int8_t *Xs_last_dev)
+{
+    CHK(check_bm_learn(ctx, W_dev, Pi_d_dev, Pij_d_dev, N, q, X_dev, K, flags, beta, iter0, n_iter, burn, stride, n_samples, eta, lambda,
+                       trace_dev));
+    CHK(begin(ctx));
+    hipStream_t s = ctx->stream;
+    const int sdim = q - 1, n = N * sdim, M = K * n_samples;
+    const long long n_steps = (long long)burn + (long long)n_samples * stride;
+    const bm_plan at(n, N, K, n_samples, Xs_last_dev == nullptr);
+    CHK(ensure(ctx, ctx->BMws, at.bytes));
+    CHK(ensure(ctx, ctx->Wfix, (size_t)M * sizeof(unsigned long long)));
+    char *ws = (char *)ctx->BMws.p;
+    double *Pij_m = (double *)(ws + at.pij), *Pi_m = (double *)(ws + at.pi), *zero = (double *)(ws + at.zero), *ones = (double *)(ws + at.ones);
+    int32_t *accepted = (int32_t *)(ws + at.acc);
+    int8_t *Xs = Xs_last_dev ? Xs_last_dev : (int8_t *)(ws + at.xs);
+    gdca_dev_scalars *sc = (gdca_dev_scalars *)ctx->sc.p;
+    // what does not change over the loop: the zero Pi, the unit weights in the tally's fixed point, Meff = K n_samples
+    // (gdca_frequencies_dev's own calls, so the tallies are its bits)
+    const double Meff = (double)M;
+    gdca_launch_bm_fill(s, zero, (size_t)n, 0.0);
+    gdca_launch_bm_fill(s, ones, (size_t)M, 1.0);
+    HIPCHK(hipMemcpyAsync(&sc->Meff, &Meff, sizeof(double), hipMemcpyHostToDevice, s));
+    gdca_launch_fix_weights(s, ones, M, gdca_fix_shift(M), (unsigned long long *)ctx->Wfix.p, sc);
+    const gdca_model model = operator_model(W_dev, zero, N, q);
+    for (int it = 0; it < n_iter; ++it) {
+        const uint64_t t = iter0 + (uint64_t)it;
+        const sample_request r{{mask_dev, flags, beta, seed, t * (uint64_t)K, burn, stride, n_samples, Xs, nullptr, accepted, nullptr, nullptr},
+                               nullptr};
+        CHK(sample_stage(ctx, model, X_dev, K, r));
+        gdca_launch_bm_last_sample(s, Xs, N, K, n_samples, X_dev);
+        CHK(tally_stage(ctx, Xs, N, M, q, &sc->Meff, 0.0, 0, Pi_m, Pij_m, (size_t)n));
+        double *out = trace_dev + 4 * (size_t)it;
+        CHK(bm_readout_stage(ctx, Pi_d_dev, Pij_d_dev, Pi_m, Pij_m, N, q, out, false));
+        gdca_launch_bm_accept(s, accepted, K, n_steps, out + 3);
+        gdca_launch_bm_update(s, W_dev, Pij_d_dev, Pij_m, N, sdim, eta, lambda);
+        CHK(check_launch(ctx, "Boltzmann-machine iteration"));
+    }
+    return sequences_checked(ctx);  // (the one round trip of the call: the device's flags)
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -4238,6 +4406,67 @@ gdca_status gdca_run_sample(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int3
     CHK(sg.status());
     return sg.finish(gdca_run_sample_dev(ctx, Z_dev, N, M, q, p, X_dev, K, mask_dev, flags, beta, seed, stream0, burn, stride, n_samples,
                                          Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev, V_dev, st));
+}
+
+/* Boltzmann-machine refinement with host pointers */
+gdca_status gdca_potts_from_gaussian(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, double *W)
+{
+    CHK(check_potts(ctx, mJ, Pi, N, q, W));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    double *W_dev = sg.out(W, n * n * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_potts_from_gaussian_dev(ctx, mJ_dev, Pi_dev, N, q, W_dev));
+}
+
+gdca_status gdca_bm_update(gdca_ctx *ctx, double *W, const double *Pi_d, const double *Pij_d, const double *Pi_m, const double *Pij_m, int32_t N,
+                           int32_t q, double eta, double lambda)
+{
+    (void)Pi_d, (void)Pi_m;
+    CHK(check_bm_update(ctx, W, Pij_d, Pij_m, N, q, eta, lambda));
+    const size_t nn = (size_t)N * (q - 1) * (size_t)N * (q - 1) * sizeof(double);
+    host_stage sg(ctx);
+    double *W_dev = sg.inout(W, W, nn);
+    const double *Pij_d_dev = sg.in(Pij_d, nn);
+    const double *Pij_m_dev = sg.in(Pij_m, nn);
+    CHK(sg.status());
+    return sg.finish(gdca_bm_update_dev(ctx, W_dev, nullptr, Pij_d_dev, nullptr, Pij_m_dev, N, q, eta, lambda));
+}
+
+gdca_status gdca_bm_readout(gdca_ctx *ctx, const double *Pi_d, const double *Pij_d, const double *Pi_m, const double *Pij_m, int32_t N, int32_t q,
+                            double *out4)
+{
+    CHK(check_bm_readout(ctx, Pi_d, Pij_d, Pi_m, Pij_m, N, q, out4));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *Pi_d_dev = sg.in(Pi_d, n * sizeof(double));
+    const double *Pij_d_dev = sg.in(Pij_d, n * n * sizeof(double));
+    const double *Pi_m_dev = sg.in(Pi_m, n * sizeof(double));
+    const double *Pij_m_dev = sg.in(Pij_m, n * n * sizeof(double));
+    double *out_dev = sg.out(out4, 4 * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_bm_readout_dev(ctx, Pi_d_dev, Pij_d_dev, Pi_m_dev, Pij_m_dev, N, q, out_dev));
+}
+
+gdca_status gdca_bm_learn(gdca_ctx *ctx, double *W, const double *Pi_d, const double *Pij_d, int32_t N, int32_t q, int8_t *X, int32_t K,
+                          const int8_t *mask, int32_t flags, double beta, uint64_t seed, uint64_t iter0, int32_t n_iter, int32_t burn,
+                          int32_t stride, int32_t n_samples, double eta, double lambda, double *trace, int8_t *Xs_last)
+{
+    CHK(check_bm_learn(ctx, W, Pi_d, Pij_d, N, q, X, K, flags, beta, iter0, n_iter, burn, stride, n_samples, eta, lambda, trace));
+    const size_t n = (size_t)N * (q - 1), k = (size_t)K;
+    host_stage sg(ctx);
+    double *W_dev = sg.inout(W, W, n * n * sizeof(double));
+    const double *Pi_d_dev = sg.in(Pi_d, n * sizeof(double));
+    const double *Pij_d_dev = sg.in(Pij_d, n * n * sizeof(double));
+    int8_t *X_dev = sg.inout(X, X, (size_t)N * k);
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    double *trace_dev = sg.out(trace, 4 * (size_t)n_iter * sizeof(double));
+    int8_t *Xs_dev = sg.out(Xs_last, (size_t)N * n_samples * k);
+    CHK(sg.status());
+    return sg.finish(gdca_bm_learn_dev(ctx, W_dev, Pi_d_dev, Pij_d_dev, N, q, X_dev, K, mask_dev, flags, beta, seed, iter0, n_iter, burn, stride,
+                                       n_samples, eta, lambda, trace_dev, Xs_dev));
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

@@ -419,3 +419,19 @@ size_t gdca_sample_state_bytes(int N, int K);
 // fit, or the dynamic LDS limit could not be raised; nothing was launched
 hipError_t gdca_launch_sample(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
                               const gdca_sample_plan &plan, int t0, int t1, double *V, bool table_in_lds, void *state);
+
+// ---- k_bm.hip: Boltzmann-machine refinement -- the warm start, the parameter update and the fit read-out of the Potts model (W, 0) ------
+// (include/gdca.h, Boltzmann-machine refinement).  Every matrix is n x n column-major with ld = n, n = N sdim.
+// W from the lower triangle of mJ and g = mJ Pi (gdca_launch_energy_g); W may not alias mJ
+void gdca_launch_bm_from_gaussian(hipStream_t s, const double *mJ, const double *g, int N, int sdim, double *W);
+// one pass over W in place: W = W + eta (m (Pij_m - Pij_d) - [m == 1] lambda W), entry by entry
+void gdca_launch_bm_update(hipStream_t s, double *W, const double *Pij_d, const double *Pij_m, int N, int sdim, double eta, double lambda);
+// out[0 .. 2] (out[3] = +0.0 where zero3) through `part`, gdca_bm_readout_bytes(n) bytes of workspace
+size_t gdca_bm_readout_bytes(int n);
+void gdca_launch_bm_readout(hipStream_t s, const double *Pi_d, const double *Pij_d, const double *Pi_m, const double *Pij_m, int N, int sdim,
+                            double *part, double *out, bool zero3);
+// *out = (sum of accepted[0 .. K - 1]) / (K n_steps)
+void gdca_launch_bm_accept(hipStream_t s, const int32_t *accepted, int K, long long n_steps, double *out);
+// X (N x K) <- the last of the n_samples samples of every chain in Xs (k_sample's layout)
+void gdca_launch_bm_last_sample(hipStream_t s, const int8_t *Xs, int N, int K, int n_samples, int8_t *X);
+void gdca_launch_bm_fill(hipStream_t s, double *v, size_t count, double value);

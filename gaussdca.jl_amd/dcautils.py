@@ -718,6 +718,63 @@ def sample(mJ, Pi, X, q: int = 21, beta: float = 1.0, burn=None, stride=None, n_
     return ctx.sample_result(out)
 
 
+def potts_independent(Pi, N: int, q: int = 21):
+    """The independent-site Potts model (W, zeros) of the single-site frequencies Pi (n = N (q - 1) entries, all and every site's gap
+    frequency 1 - sum positive): couplings zero, W[r, r] = -2 log(Pi[r] / Pi_gap(site)) -- the start of ``gDCA_bm(init="independent")``."""
+    P = np.asarray(Pi, dtype=np.float64).reshape(int(N), int(q) - 1)
+    return np.asfortranarray(np.diag((-2.0 * np.log(P / (1.0 - P.sum(axis=1))[:, None])).ravel()))
+
+
+def potts_from_gaussian(mJ, Pi, q: int = 21, ctx=None):
+    """The Gaussian model (mJ, Pi) as a Potts model in mJ's layout (gdca_potts_from_gaussian): returns W (n, n) with the couplings of
+    mJ in its off-diagonal blocks, W[r, r] = mJ[r, r] - 2 (mJ Pi)[r] and +0.0 elsewhere in a diagonal block.  (W, zeros) is a model
+    every read-out of this module takes in the place of (mJ, Pi): the same energy differences, and what ``bm_learn`` refines."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    n = Pi.shape[0] if Pi.ndim == 1 else -1
+    if not isinstance(q, (int, np.integer)) or not 2 <= q <= 31 or n < 1 or n % (int(q) - 1) or mJ.shape != (n, n):
+        raise ArgumentError(f"incompatible sizes: q = {q}, mJ {mJ.shape}, Pi {Pi.shape} (mJ must be n x n, Pi have n = N (q - 1) entries)")
+    ctx = ctx or default_context()
+    W = np.empty((n, n), dtype=np.float64, order="F")
+    ctx.check(ctx.lib.gdca_potts_from_gaussian(ctx.h, _lib._p(mJ), _lib._p(Pi), n // (int(q) - 1), int(q), _lib._p(W)))
+    return W
+
+
+def bm_learn(W, Pi_d, Pij_d, X, n_iter: int, q: int = 21, eta: float = 1.0, lam: float = 0.0, beta: float = 1.0, burn=None, stride=None,
+             n_samples: int = 1, seed: int = 0, iter0: int = 0, mask=None, gaps: bool = True, ctx=None):
+    """n_iter iterations of Boltzmann-machine learning on host arrays (gdca_bm_learn): the Potts model W (n, n) -- from
+    ``potts_from_gaussian`` or ``potts_independent`` -- is moved towards the frequencies (Pi_d, Pij_d) by sampling K persistent
+    Metropolis chains from the columns of X (N, K), tallying the K n_samples samples and adding eta times the difference of the model's
+    and the data's frequencies; ``lam`` is an L2 penalty on the couplings.  ``burn`` (default 10 N), ``stride`` (default N), ``mask``,
+    ``gaps`` (default True: the gap is a symbol like any other) as ``sample``.  Returns (W, X, trace (n_iter, 4)): new arrays; trace
+    holds max |Pi_m - Pi_d|, max |c_m - c_d|, the Pearson correlation of the connected correlations and the acceptance rate of every
+    iteration.  A later call with ``iter0 + n_iter`` continues the same run bit for bit."""
+    W = np.array(W, dtype=np.float64, order="F")
+    Pi_d = np.ascontiguousarray(Pi_d, dtype=np.float64)
+    Pij_d = np.ascontiguousarray(Pij_d, dtype=np.float64)
+    Xf = np.array(_symbols(X, "X"), dtype=np.int8, order="F")
+    N, K = Xf.shape
+    if not isinstance(q, (int, np.integer)) or not 2 <= q <= 31:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    n = N * (int(q) - 1)
+    if N < 1 or W.shape != (n, n) or Pij_d.shape != (n, n) or Pi_d.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: X has N = {N} sites, q = {q}, so W and Pij_d must be {n} x {n} and Pi_d have {n} entries")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    for v, name in ((eta, "eta"), (lam, "lam")):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (name == "eta" and v == 0):
+            raise ArgumentError(f"invalid {name} value: {v}")
+    if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
+    beta, burn, stride, S, seed, iter0, m, flags = _sample_args(N, q, beta, burn, stride, n_samples, seed, iter0, mask, gaps)
+    ctx = ctx or default_context()
+    trace = np.empty((int(n_iter), 4), dtype=np.float64)
+    ctx.check(ctx.lib.gdca_bm_learn(ctx.h, _lib._p(W), _lib._p(Pi_d), _lib._p(Pij_d), N, int(q), _lib._p(Xf), K,
+                                    None if m is None else _lib._p(m), flags, beta, seed, iter0, int(n_iter), burn, stride, S, float(eta),
+                                    float(lam), _lib._p(trace), None))
+    return W, Xf, trace
+
+
 def _double_model_args(mJ, Pi, X, q):
     """the model and the sequences of the double-mutant operators, checked: (mJ, Pi, Xf, N, K)"""
     mJ = np.ascontiguousarray(mJ, dtype=np.float64)

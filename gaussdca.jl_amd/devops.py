@@ -207,6 +207,96 @@ def sample_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, beta: float, 
     return dXs, daccepted, ddE_s, dthr, dmoves, dV
 
 
+def potts_from_gaussian_dev(ctx: Context, dmJ, dPi, N: int, q: int, dW=None):
+    """The Gaussian model (mJ, Pi) as a Potts model (W, zeros) in mJ's layout, every array in HBM (gdca_potts_from_gaussian_dev):
+    off-diagonal blocks the bits of mJ, W[r, r] = mJ[r, r] - 2 (mJ Pi)[r], the rest of a diagonal block +0.0.  W may not be mJ."""
+    n = N * (int(q) - 1)
+    dW = dW or DeviceBuffer(ctx, 8 * n * n)
+    ctx.potts_from_gaussian_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), _ptr(dW).value)
+    return dW
+
+
+def bm_update_dev(ctx: Context, dW, dPij_d, dPij_m, N: int, q: int, eta: float, lam: float = 0.0, dPi_d=None, dPi_m=None):
+    """One Boltzmann-machine step on W in place (gdca_bm_update_dev): W += eta (m (Pij_m - Pij_d) - [m == 1] lam W), m = 2 on the
+    diagonal, 0 elsewhere inside a diagonal block, 1 outside.  The single-site tallies are not read."""
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.bm_update_dev(_ptr(dW).value, _ptr(dPij_d).value, _ptr(dPij_m).value, N, int(q), float(eta), float(lam), opt(dPi_d), opt(dPi_m))
+    return dW
+
+
+def bm_readout_dev(ctx: Context, dPi_d, dPij_d, dPi_m, dPij_m, N: int, q: int, dout=None):
+    """The fit of the model's tallies to the data's (gdca_bm_readout_dev) -> a buffer of four f64: max |Pi_m - Pi_d|, max |c_m - c_d|
+    and the Pearson correlation of c_m and c_d over the off-diagonal blocks (c = Pij - Pi Pi'), then +0.0."""
+    dout = dout or DeviceBuffer(ctx, 32)
+    ctx.bm_readout_dev(_ptr(dPi_d).value, _ptr(dPij_d).value, _ptr(dPi_m).value, _ptr(dPij_m).value, N, int(q), _ptr(dout).value)
+    return dout
+
+
+def bm_learn_dev(ctx: Context, dW, dPi_d, dPij_d, N: int, q: int, dX, K: int, n_iter: int, burn: int, stride: int, n_samples: int,
+                 eta: float, lam: float = 0.0, beta: float = 1.0, seed: int = 0, iter0: int = 0, dmask=None, flags: int = 0, dtrace=None,
+                 dXs_last=None):
+    """n_iter iterations of Boltzmann-machine learning with every array in HBM and no host round trip per iteration
+    (gdca_bm_learn_dev): sample K persistent chains under (W, zeros) from X (N x K int8), tally the K n_samples samples, read the
+    fit out into trace[4 i ..], update W.  W and X change in place; a later call continues with ``iter0 + n_iter``.  Returns dtrace
+    (4 x n_iter f64: max |dPi|, max |dc|, Pearson, acceptance rate per iteration)."""
+    dtrace = dtrace or DeviceBuffer(ctx, 32 * max(int(n_iter), 1))
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.bm_learn_dev(_ptr(dW).value, _ptr(dPi_d).value, _ptr(dPij_d).value, N, int(q), opt(dX), int(K), opt(dmask), int(flags), float(beta),
+                     int(seed), int(iter0), int(n_iter), int(burn), int(stride), int(n_samples), float(eta), float(lam), _ptr(dtrace).value,
+                     opt(dXs_last))
+    return dtrace
+
+
+def bm_fit(Z, q: int, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float = 0.0, pseudocount: float = 0.8,
+           target_pseudocount: float = 0.0, theta=":auto", init: str = "gaussian", burn=None, stride=None, n_samples: int = 1,
+           beta: float = 1.0, seed: int = 0, gaps: bool = True, scores: bool = False, ctx: Context = None):
+    """Boltzmann-machine refinement built like scores_stepwise from the device operators.  Z: (N, M) int8.  weights, frequencies,
+    pseudocount, covariance, inverse (the warm start, ``init="gaussian"``; "independent" skips the last two), then n_iter iterations
+    of bm_learn_dev towards the frequencies at ``target_pseudocount``.  The chains start from the first K sequences of Z (K <= M).
+    Returns (W (n, n), trace (n_iter, 4)) and, with ``scores=True``, S = APC(FN(W)) as a third entry."""
+    from .dcautils import potts_independent
+
+    ctx = ctx or default_context()
+    Zf = _zf(Z)
+    N, M = Zf.shape
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    if init not in ("gaussian", "independent"):
+        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\" or \"independent\")")
+    if not isinstance(K, (int, np.integer)) or not 1 <= K <= M:
+        raise ArgumentError(f"invalid K value: {K} (must be an integer between 1 and the number of sequences, {M})")
+    if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
+    n = N * (q - 1)
+    burn = 10 * N if burn is None else int(burn)
+    stride = N if stride is None else int(stride)
+    dZ = DeviceBuffer.from_array(ctx, Zf)
+    dW_, Meff, th, thr = compute_weights_dev(ctx, dZ, N, M, theta)
+    dPi_t, dPij_t = compute_weighted_frequencies_dev(ctx, dZ, N, M, q, dW_, Meff)
+    # the target: the family's frequencies at target_pseudocount
+    dPi_d, dPij_d = add_pseudocount_dev(ctx, dPi_t, dPij_t, N, q, target_pseudocount, DeviceBuffer(ctx, 8 * n), DeviceBuffer(ctx, 8 * n * n))
+    # the start
+    dPi, dPij = add_pseudocount_dev(ctx, dPi_t, dPij_t, N, q, pseudocount)
+    if init == "gaussian":
+        dmJ = compute_C_dev(ctx, dPi, dPij, n, dC=dPij)
+        inv_cholesky_dev(ctx, dmJ, n)
+        dW = potts_from_gaussian_dev(ctx, dmJ, dPi, N, q)
+    else:
+        dW = DeviceBuffer.from_array(ctx, potts_independent(dPi.download((n,)), N, q))
+    dX = DeviceBuffer.from_array(ctx, np.asfortranarray(Zf[:, :K]))
+    dtrace = bm_learn_dev(ctx, dW, dPi_d, dPij_d, N, q, dX, K, n_iter, burn, stride, n_samples, eta, lam, beta, seed,
+                          flags=_lib.SAMPLE_GAPS if gaps else 0)
+    W, trace = dW.download((n, n)), dtrace.download((int(n_iter), 4), order="C")
+    out = (W, trace)
+    if scores:
+        dS = correct_APC_dev(ctx, compute_FN_dev(ctx, dW, N, q), N)
+        out += (dS.download((N, N)),)
+        dS.free()
+    for b in (dZ, dW_, dPi_t, dPij_t, dPi_d, dPij_d, dW, dX, dtrace):
+        b.free()
+    return out
+
+
 def scores_stepwise(Z, q: int, pseudocount: float = 0.8, theta=":auto", score: str = "frob", ctx: Context = None
                     ) -> Tuple[np.ndarray, dict]:
     """The six statements of src/GaussDCA.jl:28-42 one by one, arrays resident in HBM.  Z: (N, M) int8.

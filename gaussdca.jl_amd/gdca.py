@@ -494,6 +494,54 @@ def gDCA_sample(filename: str, starts=None, beta: float = 1.0, burn=None, stride
                            "samples")
 
 
+def gDCA_bm(filename: str, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float = 0.0, target_pseudocount: float = 0.0,
+            init: str = "gaussian", burn=None, stride=None, n_samples: int = 1, beta: float = 1.0, seed: int = 0, gaps: bool = True,
+            scores: bool = False, min_separation: int = 5, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
+            remove_dups: bool = False, ctx=None, **kw):
+    """Boltzmann-machine refinement (bmDCA) of the model gDCA fits to the alignment in ``filename``: the Potts model the Metropolis
+    chains of ``gDCA_sample`` draw from is moved until the one- and two-site frequencies of its samples are the family's.  Built from
+    the device operators like ``gDCA_stepwise``: weights, frequencies, pseudocount, covariance, inverse -- the Gaussian warm start at
+    ``pseudocount`` (``init="gaussian"``; ``"independent"``: the independent-site model, no inverse) --, then ``n_iter`` iterations of
+    sample, tally, update (``devops.bm_learn_dev``: nothing crosses to the host inside the loop) towards the family's frequencies at
+    ``target_pseudocount``.  ``K`` persistent chains start from the first K sequences of the alignment (fewer if it has fewer);
+    ONE SWEEP IS N PROPOSALS: every iteration runs ``burn`` proposals (default 10 N) and tallies ``n_samples`` states ``stride`` (default
+    N) apart; ``eta`` is the step, ``lam`` an L2 penalty on the couplings; ``gaps`` (default True) lets the chains change gaps.
+
+    Returns ``(W, trace)``: W (n, n) is the model as the pair (W, zeros) that ``sequence_energies``, ``mutation_scan``,
+    ``greedy_walk``, ``sample``, ``compute_FN`` take in the place of (mJ, Pi); ``trace`` (n_iter, 4) holds max |Pi_m - Pi_d|,
+    max |c_m - c_d|, the Pearson correlation of the connected correlations and the acceptance rate per iteration.  With
+    ``scores=True`` a third entry: the ranking of APC(FN(W)) at ``min_separation``, the bmDCA contact score."""
+    from . import devops
+
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_bm() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", min_separation)
+    if not (0 <= target_pseudocount <= 1):
+        raise ArgumentError(f"invalid target_pseudocount value: {target_pseudocount} (must be between 0 and 1)")
+    if init not in ("gaussian", "independent"):
+        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\" or \"independent\")")
+    if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
+    if not isinstance(K, (int, np.integer)) or K < 1:
+        raise ArgumentError(f"invalid K value: {K} (must be an integer >= 1)")
+    Z = read_fasta_alignment(filename, max_gap_fraction)
+    if remove_dups:
+        Z, _ = remove_duplicate_sequences(Z)
+    q = int(Z.max())
+    if q >= 32:
+        raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+    out = devops.bm_fit(Z, q, int(n_iter), K=min(int(K), Z.shape[1]), eta=eta, lam=lam, pseudocount=float(pseudocount),
+                        target_pseudocount=float(target_pseudocount), theta=theta, init=init, burn=burn, stride=stride,
+                        n_samples=n_samples, beta=beta, seed=seed, gaps=gaps, scores=scores, ctx=ctx)
+    if scores:
+        from .dcautils import compute_ranking
+
+        return out[0], out[1], compute_ranking(out[2], int(min_separation))
+    return out
+
+
 def _required_sequences(sequences, name):
     X = _sequences_arg(sequences, "sequences", "an N x K")
     if X is None:

@@ -739,6 +739,78 @@ gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, i
                                 uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs_dev, double *dE_s_dev,
                                 int32_t *accepted_dev, double *thr_dev, int32_t *moves_dev, double *V_dev, gdca_stats *st);
 
+/* ---- Boltzmann-machine refinement: fit the Potts model the Metropolis chains draw from ----------------------------------------------
+ * The chains sample exp(-beta E) with E(x) = 1/2 (x - Pi)' mJ (x - Pi): read that way (mJ, Pi) IS a Potts model -- couplings the
+ * off-diagonal blocks of mJ, fields g - 1/2 diag(mJ), g = mJ Pi.  These entry points fit that model to a family's one- and two-site
+ * frequencies by Boltzmann-machine learning: sample, tally, move every parameter by the difference between the model's and the data's
+ * frequency, repeat.
+ * THE CONTAINER (no new format).  A Potts model in the gauge "the gap's row is zero" is the pair (W, 0) in mJ's layout: W n x n,
+ * n = N (q - 1), column-major, full symmetric; its off-diagonal blocks are the couplings in E's sign; W[r, r] = -2 h[r] holds the
+ * fields; the entries of a diagonal block off the diagonal are exactly +0.0; Pi is a vector of n zeros.  With Pi = 0 the formulas above
+ * reduce to E(x) = sum_{i<j} W[r_i, r_j] + 1/2 sum_i W[r_i, r_i] and V(x; i, c) = sum_{j != i} W[r(i,c), r_j] + 1/2 W[r(i,c), r(i,c)]
+ * (g = W 0 = +0.0), so gdca_energies*, gdca_mutation_scan*, gdca_double_mutant*, gdca_greedy_walk*, gdca_sample*, gdca_fn* and
+ * gdca_apc* take (W, zeros) AS THEY ARE: that is the whole interface between a learned model and the rest of the library.
+ *
+ * gdca_potts_from_gaussian_dev: the warm start, W from (mJ, Pi).  Only the lower triangle of mJ is read.  Outside the diagonal blocks
+ * W[r, c] = W[c, r] = the bits of mJ[max(r, c), min(r, c)]; inside one, off the diagonal, +0.0; W[r, r] = mJ[r, r] - 2 g[r] (2 g[r]
+ * is exact: one subtraction).  g = mJ Pi is the g of the energies and of the mutation scan (the same code), summed in this order: the
+ * columns are cut into blocks of 64 (c / 64); inside block o a partial p_o = the products mJ[r, c] Pi[c] (each rounded once, no FMA)
+ * added one by one to +0.0 with c ascending -- in r's own block first the columns c <= r, then apart the columns c > r, and the two
+ * partials added --; g[r] = the p_o added one by one to +0.0 with o ascending.  Columns beyond n in the last block add +0.0.  W may
+ * not alias mJ (GDCA_EINVAL).
+ *
+ * gdca_bm_update_dev: ONE gradient step on W in place.  For every entry (r, c), in f64, one rounding an operation, no FMA:
+ *     d = Pij_m[r, c] - Pij_d[r, c]
+ *     m = 2 if r == c, else 0 if r and c belong to the same site, else 1;          g = m d                              (exact)
+ *     where m == 1 and lambda != 0:  g = g - lambda W[r, c]                        (one product, one subtraction)
+ *     W[r, c] = W[r, c] + eta g                                                    (one product, one addition)
+ * Every entry is computed from its own three operands: tallies that are symmetric to the bit (gdca_frequencies*'s and
+ * gdca_add_pseudocount*'s are) give both triangles the same bits, and the +0.0 of the diagonal blocks stays +0.0.  This is gradient
+ * ascent on the log-likelihood in a gauge without redundant parameters (a concave problem); fields and couplings move at the same
+ * rate, the L2 penalty lambda acts on the couplings alone.  The diagonal works through Pij alone (Pij[r, r] = Pi[r] in both tallies,
+ * and add_pseudocount keeps that): Pi_d and Pi_m are not read here and may be NULL.  eta > 0 and lambda >= 0, both finite.
+ *
+ * gdca_bm_readout_dev: the fit in four f64.  Only the lower triangles of Pij_d and Pij_m are read.  With c_x[r, c] = Pij_x[r, c] -
+ * Pi_x[r] Pi_x[c] (one rounded product, one subtraction) and P = the entries (r, c) with site(r) > site(c) (T = s^2 N (N - 1) / 2):
+ *     out[0] = max_r |Pi_m[r] - Pi_d[r]|;    out[1] = max_P |c_m - c_d|  (one subtraction of the two c, 0 where P is empty);
+ *     out[2] = the Pearson correlation of c_m and c_d over P: (T Sab - Sa Sb) / (sqrt(T Saa - Sa Sa) sqrt(T Sbb - Sb Sb)), every
+ *              operation rounded once, from the five sums Sa, Sb, Saa, Sab, Sbb over P taken in a fixed order: a column's entries by
+ *              256 strided partial sums (partial t: the rows r0 + t, r0 + t + 256, .. ascending, r0 the first row below the column's
+ *              diagonal block) folded by a halving tree (t and t + 128, then t and t + 64, ..), the columns' sums the same way.  NaN
+ *              where P is empty or a variance is not positive;
+ *     out[3] = +0.0 in this form (the loop writes the acceptance rate there).
+ * The order is a function of N and q alone, there are no floating-point atomics: the same bits from run to run on any device.
+ *
+ * gdca_bm_learn_dev: the loop, enqueued without a host round trip per iteration (the device's validity flags are read once, at the
+ * end).  W and the chains' states X (N x K int8) are in/out: the chains are persistent.  For t = iter0 .. iter0 + n_iter - 1:
+ *     1. the sample stage (gdca_sample_dev's: the scan of X under (W, zeros), then the chains) with stream0 = t K, so every iteration
+ *        has streams of its own, n_steps = burn + n_samples stride;
+ *     2. X <- every chain's last sample;
+ *     3. Pi_m, Pij_m <- gdca_frequencies_dev of the K n_samples samples, unit weights, Meff = K n_samples;
+ *     4. the read-out into trace[4 (t - iter0) ..], with out[3] = (the iteration's accepted proposals, summed as integers) /
+ *        f64(K n_steps), one division;
+ *     5. the update.
+ * RULE: a call of n_iter iterations equals, bit for bit in W, X and trace, two calls of a and n_iter - a iterations chained through
+ * W, X and iter0 (the second with iter0 + a), and equals the caller doing the steps 1 - 5 with the operator forms.  There is no
+ * early stop inside a call: the caller reads trace and calls again.  Xs_last (N x n_samples x K int8, gdca_sample_dev's layout) is
+ * optional: the samples of the last iteration.  The workspaces are grow-only buffers of the context (n^2 + 2 n + K n_samples doubles
+ * beside the sample stage's and the tally's own).  The bits depend on the context options WALK_TABLE and SAMPLE_CHUNK as little as
+ * gdca_sample_dev's do.
+ * GDCA_EINVAL, nothing run, W and X untouched: whatever gdca_sample_dev refuses (K, q, flags, beta, burn, stride, n_samples, the
+ * table's placement, N); eta <= 0, lambda < 0, either NaN or infinite; n_iter < 1; K n_samples > INT32_MAX;
+ * (iter0 + n_iter) K > 2^64 - 1 (the stream numbers would wrap); a null W, Pi_d, Pij_d, X or trace.  A byte of X outside 1..q is
+ * reported as gdca_sample_dev reports it (W, X and trace are unspecified then).  All four are new symbols: gdca_stats and gdca_params
+ * are unchanged.  There is no fused gdca_run_* form (the inverse is only an initialiser here). */
+gdca_status gdca_potts_from_gaussian_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, double *W_dev);
+gdca_status gdca_bm_update_dev(gdca_ctx *ctx, double *W_dev, const double *Pi_d_dev, const double *Pij_d_dev, const double *Pi_m_dev,
+                               const double *Pij_m_dev, int32_t N, int32_t q, double eta, double lambda);
+gdca_status gdca_bm_readout_dev(gdca_ctx *ctx, const double *Pi_d_dev, const double *Pij_d_dev, const double *Pi_m_dev,
+                                const double *Pij_m_dev, int32_t N, int32_t q, double *out4_dev);
+gdca_status gdca_bm_learn_dev(gdca_ctx *ctx, double *W_dev, const double *Pi_d_dev, const double *Pij_d_dev, int32_t N, int32_t q,
+                              int8_t *X_dev, int32_t K, const int8_t *mask_dev, int32_t flags, double beta, uint64_t seed, uint64_t iter0,
+                              int32_t n_iter, int32_t burn, int32_t stride, int32_t n_samples, double eta, double lambda, double *trace_dev,
+                              int8_t *Xs_last_dev);
+
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* A host-pointer form on a context with an enqueued run (gdca_run_dev_async, gdca_run_ranked_async, ...) is refused (GDCA_EINVAL)
  * before it touches the context: nothing is uploaded or reallocated, and the enqueued run is unaffected. */
@@ -857,6 +929,16 @@ gdca_status gdca_run_sample(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int3
                             const int8_t *X_host, int32_t K, const int8_t *mask, int32_t flags, double beta, uint64_t seed,
                             uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs, double *dE_s, int32_t *accepted,
                             double *thr, int32_t *moves, double *V, gdca_stats *st);
+
+/* Boltzmann-machine refinement with host pointers: upload, the _dev form, download (W, X in place) */
+gdca_status gdca_potts_from_gaussian(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, double *W);
+gdca_status gdca_bm_update(gdca_ctx *ctx, double *W, const double *Pi_d, const double *Pij_d, const double *Pi_m, const double *Pij_m, int32_t N,
+                           int32_t q, double eta, double lambda);
+gdca_status gdca_bm_readout(gdca_ctx *ctx, const double *Pi_d, const double *Pij_d, const double *Pi_m, const double *Pij_m, int32_t N, int32_t q,
+                            double *out4);
+gdca_status gdca_bm_learn(gdca_ctx *ctx, double *W, const double *Pi_d, const double *Pij_d, int32_t N, int32_t q, int8_t *X, int32_t K,
+                          const int8_t *mask, int32_t flags, double beta, uint64_t seed, uint64_t iter0, int32_t n_iter, int32_t burn,
+                          int32_t stride, int32_t n_samples, double eta, double lambda, double *trace, int8_t *Xs_last);
 
 /* ---- host-side utilities around the hot path (plain C++, no GPU): the reference's callers of the path -------- */
 /* CPUs this process can really use: hardware threads capped by the cgroup CPU quota (a container may see 256 threads and be given
