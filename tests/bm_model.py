@@ -11,6 +11,7 @@ in a diagonal block, Pi = n zeros.  Then E(x) = sum_{i<j} W[r_i, r_j] + 1/2 sum_
   update / update_scalar   one step: d = Pij_m - Pij_d; g = m d; m == 1 and lam != 0: g = g - lam W; W = W + eta g;
   readout            out[0], out[1] bit for bit, out[2] from exactly rounded sums (math.fsum) with the bound below;
   learn / learn_scalar     the loop on sample_model.emulate_chains (emulate) and tally_model.frequencies;
+  add_pseudocount, fit     devops.bm_fit: tallies, targets and start from the same true tallies, the start model, the loop from iteration 0;
   exact_marginals    (Pi, Pij) of a model by enumeration (sample_model.boltzmann); kl, pair_deviation on them.
 
 THE BOUND OF out[2] (u = 2^-53).  The T terms a_k = c_m, b_k = c_d and their rounded products a_k a_k, a_k b_k, b_k b_k are the
@@ -156,8 +157,10 @@ def readout(Pi_d, Pij_d, Pi_m, Pij_m, N, q):
     return np.array([out0, out1, float(r)]), bound
 
 
-def iteration(W, Pi_d, Pij_d, X, q, t, flags, beta, seed, burn, stride, n_samples, eta, lam, mask=None, thr=None, V0=None, scalar=False):
-    """one iteration t of the loop from the chains' states X (N, K) -> (W, X, out (4,), Xs (K, n_samples, N), Pi_m, Pij_m).
+def iteration(W, Pi_d, Pij_d, X, q, t, flags, beta, seed, burn, stride, n_samples, eta, lam, mask=None, thr=None, V0=None, scalar=False,
+              with_bound=False):
+    """one iteration t of the loop from the chains' states X (N, K) -> (W, X, out (4,), Xs (K, n_samples, N), Pi_m, Pij_m), and with
+    with_bound readout's bound of out[2] behind them (the read-out's exact sums are the expensive part: taken once).
     thr (K, n_steps) and V0 (K, N, q): the device's thresholds and start tables, where the comparison is to be bit for bit;
     None: -np.log(u) and mutation_model.potentials_dense"""
     X = np.asarray(X)
@@ -174,10 +177,10 @@ def iteration(W, Pi_d, Pij_d, X, q, t, flags, beta, seed, burn, stride, n_sample
         Xs, _, acc, _ = sm.emulate_chains(V0, W, X, q, thr, mask, flags, beta, seed, t * K, burn, stride, n_samples)
     Z = np.ascontiguousarray(Xs.reshape(K * n_samples, N).T)  # (N, K n_samples), chain by chain
     Pi_m, Pij_m = tm.frequencies(Z, np.ones(K * n_samples), float(K * n_samples), q)
-    out3, _ = readout(Pi_d, Pij_d, Pi_m, Pij_m, N, q)
+    out3, bound = readout(Pi_d, Pij_d, Pi_m, Pij_m, N, q)
     rate = np.float64(int(np.asarray(acc, dtype=np.int64).sum())) / np.float64(K * n_steps)
     Wn = (update_scalar if scalar else update)(W, Pij_d, Pij_m, N, q, eta, lam)
-    return Wn, np.asfortranarray(Xs[:, -1].T.astype(np.int8)), np.append(out3, rate), Xs, Pi_m, Pij_m
+    return (Wn, np.asfortranarray(Xs[:, -1].T.astype(np.int8)), np.append(out3, rate), Xs, Pi_m, Pij_m) + ((bound,) if with_bound else ())
 
 
 def learn(W, Pi_d, Pij_d, X, q, n_iter, flags=GAPS, beta=1.0, seed=0, iter0=0, burn=0, stride=1, n_samples=1, eta=1.0, lam=0.0, mask=None,
@@ -192,6 +195,52 @@ def learn(W, Pi_d, Pij_d, X, q, n_iter, flags=GAPS, beta=1.0, seed=0, iter0=0, b
 
 def learn_scalar(*a, **kw):
     return learn(*a, scalar=True, **kw)
+
+
+# ---- the whole fit: devops.bm_fit stated in numpy ---------------------------------------------------------------------------------------
+def add_pseudocount(Pi_true, Pij_true, pc, q):
+    """add_pseudocount of src/GaussDCA.jl:30, one f64 operation after the other as the oracle writes them: off the diagonal blocks
+    (1 - pc) P + (pc / q) / q, on the diagonal (1 - pc) P + pc / q, elsewhere inside a diagonal block (1 - pc) P; Pi = (1 - pc) P + pc / q"""
+    Pi_true, Pij_true = np.asarray(Pi_true, dtype=np.float64), np.asarray(Pij_true, dtype=np.float64)
+    pc = np.float64(pc)
+    pcq = pc / np.float64(q)
+    m = multipliers(Pi_true.shape[0] // (q - 1), q)
+    scaled = (1.0 - pc) * Pij_true
+    Pij = np.where(m == 1.0, scaled + pcq / np.float64(q), np.where(m == 2.0, scaled + pcq, scaled))
+    return (1.0 - pc) * Pi_true + pcq, Pij
+
+
+def fit(Z, q, n_iter, weights, Meff, K, eta=1.0, lam=0.0, pseudocount=0.8, target_pseudocount=0.0, init="gaussian", burn=None, stride=None,
+        n_samples=1, beta=1.0, seed=0, flags=GAPS, inverse=None, thresholds=None, tables=None):
+    """devops.bm_fit on the alignment Z (N, M) with the sequence weights and Meff GIVEN (the reweighting has its own model): the true
+    tallies (tally_model.frequencies), the targets at target_pseudocount and the start at pseudocount from the SAME true tallies, the
+    start model -- init = "gaussian": potts_from_gaussian of the inverse of C = Pij - Pi Pi'; "independent": potts_independent of Pi --,
+    the chains from the first K sequences, burn = 10 N and stride = N unless given, then n_iter iterations from iteration 0.
+    inverse(C) -> mJ, thresholds(t) -> (K, n_steps) and tables(W, X) -> (K, N, q) let a test hand in the device's own inverse, thresholds
+    and start tables where the comparison is to be bit for bit; None: numpy's inverse, -np.log(u), mutation_model.potentials_dense.
+    -> dict(W, trace (n_iter, 4), bounds (n_iter,): readout's of trace[:, 2], Ws: W after every iteration, X (N, K), W0, Pi_d, Pij_d, Pi)"""
+    Z = np.asarray(Z)
+    N, M = Z.shape
+    assert 1 <= K <= M and n_iter >= 1 and init in ("gaussian", "independent")
+    burn = 10 * N if burn is None else int(burn)
+    stride = N if stride is None else int(stride)
+    Pi_t, Pij_t = tm.frequencies(Z, weights, Meff, q)
+    Pi_d, Pij_d = add_pseudocount(Pi_t, Pij_t, target_pseudocount, q)
+    Pi, Pij = add_pseudocount(Pi_t, Pij_t, pseudocount, q)
+    if init == "gaussian":
+        C = Pij - np.outer(Pi, Pi)
+        mJ = np.linalg.inv(C) if inverse is None else inverse(C)
+        W0 = potts_from_gaussian(mJ, Pi, q)
+    else:
+        W0 = potts_independent(Pi, N, q)
+    W, X = W0, np.asfortranarray(Z[:, :K].astype(np.int8))
+    trace, Ws, bounds = np.empty((n_iter, 4)), [], np.empty(n_iter)
+    for t in range(n_iter):
+        step = iteration(W, Pi_d, Pij_d, X, q, t, flags, beta, seed, burn, stride, n_samples, eta, lam,
+                         thr=None if thresholds is None else thresholds(t), V0=None if tables is None else tables(W, X), with_bound=True)
+        W, X, trace[t], bounds[t] = step[0], step[1], step[2], step[6]
+        Ws.append(W)
+    return dict(W=W, trace=trace, bounds=bounds, Ws=Ws, X=X, W0=W0, Pi_d=Pi_d, Pij_d=Pij_d, Pi=Pi)
 
 
 # ---- exact marginals of a small model ------------------------------------------------------------------------------------------------

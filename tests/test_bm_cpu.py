@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import bm_model as bm
+import mutation_model as mm
 import sample_model as sm
 import tally_model as tm
 from gdca_testutil import CSRC, FLAGS, HIPCC, ROOT, compiler_report
@@ -41,9 +42,14 @@ def learn_problem():
     return N, q, P1, P2, W0, X0, bm.pair_deviation(W0, P2, q, N)
 
 
-def small_problem(seed=3, N=3, q=4, K=6, M=40):
+def small_family(seed=3, N=3, q=4, M=40):
+    """(rng behind it, Z (N, M)): the alignment of small_problem"""
     rng = np.random.default_rng(seed)
-    Z = rng.integers(1, q + 1, size=(N, M)).astype(np.int8)
+    return rng, rng.integers(1, q + 1, size=(N, M)).astype(np.int8)
+
+
+def small_problem(seed=3, N=3, q=4, K=6, M=40):
+    rng, Z = small_family(seed, N, q, M)
     Pi_d, Pij_d = tm.frequencies(Z, np.ones(M), float(M), q)
     n = N * (q - 1)
     A = rng.normal(size=(n, n)) * 0.3
@@ -104,6 +110,49 @@ def test_the_container_and_the_readout_of_the_model():
     out, bound = bm.readout(P1, Pij_d, Pi_d, Pij_d, N, q)
     assert abs(out[2] - want) < 1e-12 and np.isfinite(bound)
     assert np.array_equal(bm.update(W, Pij_d, P2, N, q, 0.3, 0.1), bm.update_scalar(W, Pij_d, P2, N, q, 0.3, 0.1))
+
+
+def test_fit_is_the_composition_it_states():
+    """bm_model.fit on small_problem's alignment against its steps taken one by one: the oracle's weights and add_pseudocount on
+    tally_model's true tallies, numpy's inverse, then bm_model.learn from iteration 0 with burn = 10 N and stride = N"""
+    from oracle import gdca_oracle as o
+
+    N, q, K, M = 3, 4, 6, 40
+    _, Z = small_family()
+    Z[0, 0] = q
+    wts, Meff, _, _ = o.compute_weights(np.ascontiguousarray(Z.T), 0.7)
+    assert Meff < M  # (the weights are not all 1: a fit that dropped them would differ)
+    Pi_t, Pij_t = tm.frequencies(Z, wts, Meff, q)
+    for pc in (0.0, 0.1, 0.8):  # the pseudocount stated twice: the oracle's loop over the diagonal blocks, and the masks of bm_model
+        Pi_o, Pij_o = o.add_pseudocount(Pi_t, Pij_t, pc, q)
+        Pi_m, Pij_m = bm.add_pseudocount(Pi_t, Pij_t, pc, q)
+        assert np.array_equal(Pi_m, Pi_o) and np.array_equal(Pij_m, Pij_o), pc
+    kw = dict(eta=0.7, lam=0.05, n_samples=2, beta=0.9, seed=5)
+    out = {}
+    for init, tpc in (("gaussian", 0.0), ("gaussian", 0.1), ("independent", 0.1)):
+        f = out[init, tpc] = bm.fit(Z, q, 3, wts, Meff, K, pseudocount=0.8, target_pseudocount=tpc, init=init, **kw)
+        Pi_d, Pij_d = o.add_pseudocount(Pi_t, Pij_t, tpc, q)
+        Pi, Pij = o.add_pseudocount(Pi_t, Pij_t, 0.8, q)
+        assert np.array_equal(f["Pi_d"], Pi_d) and np.array_equal(f["Pij_d"], Pij_d) and np.array_equal(f["Pi"], Pi)
+        W0 = bm.potts_from_gaussian(np.linalg.inv(o.compute_C(Pi, Pij)), Pi, q) if init == "gaussian" else bm.potts_independent(Pi, N, q)
+        assert np.array_equal(f["W0"], W0)
+        W, X, trace = bm.learn(W0, Pi_d, Pij_d, np.asfortranarray(Z[:, :K]), q, 3, burn=10 * N, stride=N, **kw)
+        assert np.array_equal(f["W"], W) and np.array_equal(f["X"], X) and np.array_equal(f["trace"], trace)
+        assert len(f["Ws"]) == 3 and np.array_equal(f["Ws"][-1], W) and not np.array_equal(f["Ws"][0], f["Ws"][1])
+        # a shorter fit is a prefix, and the hooks are where the defaults come from
+        two = bm.fit(Z, q, 2, wts, Meff, K, pseudocount=0.8, target_pseudocount=tpc, init=init, **kw)
+        assert np.array_equal(two["trace"], trace[:2]) and np.array_equal(two["W"], f["Ws"][1])
+    n_steps = 10 * N + 2 * N
+    hooked = bm.fit(Z, q, 3, wts, Meff, K, pseudocount=0.8, target_pseudocount=0.1, init="gaussian", inverse=np.linalg.inv,
+                    thresholds=lambda t: np.stack([-np.log(sm.uniforms(5, t * K + k, n_steps)[1]) for k in range(K)]),
+                    tables=lambda W, X: mm.potentials_dense(bm.library_symmetric(W), np.zeros(N * (q - 1)), X, q), **kw)
+    assert np.array_equal(hooked["W"], out["gaussian", 0.1]["W"]) and np.array_equal(hooked["trace"], out["gaussian", 0.1]["trace"])
+    # what must matter does: the target's pseudocount, the start, and which K sequences the chains start from
+    assert not np.array_equal(out["gaussian", 0.0]["W"], out["gaussian", 0.1]["W"])
+    assert np.array_equal(out["gaussian", 0.0]["W0"], out["gaussian", 0.1]["W0"])
+    assert not np.array_equal(out["independent", 0.1]["W"], out["gaussian", 0.1]["W"])
+    assert np.all(out["independent", 0.1]["W0"][~np.eye(N * (q - 1), dtype=bool)] == 0.0)
+    assert not np.array_equal(bm.fit(Z, q, 3, wts, Meff, K - 1, target_pseudocount=0.1, **kw)["W"], out["gaussian", 0.1]["W"])
 
 
 # ---- 2. the sign of the gradient ----------------------------------------------------------------------------------------------------------------

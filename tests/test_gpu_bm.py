@@ -1,14 +1,18 @@
 """Boltzmann-machine refinement on the device (gdca_potts_from_gaussian*, gdca_bm_update*, gdca_bm_readout*, gdca_bm_learn*) against
 tests/bm_model.py: the update and the read-out bit for bit, the loop against the chain of the operator forms and against the numpy
 statement driven with the device's thresholds and start tables, the container (W, zeros) under the existing read-outs, and learning
-itself: the exact marginals of the learned model on a toy against the target's.  No tolerance is invented here: the bounds are
-bm_model's, mutation_model's and energy_model's, the learning bar is measured on the numpy loop alone (test_bm_cpu.py)."""
+itself: the exact marginals of the learned model on a toy against the target's; then the whole fit (gDCA_bm, devops.bm_fit) on a
+golden family against the chain of the operator forms and against bm_model.fit.  No tolerance is invented here: the bounds are
+bm_model's, mutation_model's, energy_model's and score_model's, the learning bar is measured on the numpy loop alone (test_bm_cpu.py)."""
+import os
+
 import numpy as np
 import pytest
 
 import bm_model as bm
 import energy_model as em
 import sample_model as sm
+import score_model
 import tally_model as tm
 from energy_model import U
 from gdca_testutil import ctx, g, golden_model, mixed_sequences, mutation_reference, synth_model  # noqa: F401 (g, ctx: fixtures)
@@ -132,22 +136,35 @@ def test_readout(g, ctx, refdata, which):
 
 # ---- 3. the loop against the chain of the operator forms, and against the numpy statement ---------------------------------------------------------
 LOOP = dict(K=33, n_iter=5, burn=14, stride=7, n_samples=3, eta=0.75, lam=0.01, beta=1.0, seed=11)
+# (q, N) -> the settings.  Beyond the toy, burn = N and stride = N // 2 + 1:
+#   q = 6, N = 257: n = 1285, odd -- the narrow update instance over six row blocks; the sampler's loops over sites one element into a
+#                   second pass; N % 4 = 1 for the packed symbols; 256 % s != 0 and 256 % q != 0, so the incremental (site, symbol) wrap
+#                   is taken; a tally of 99 sequences over 17 ragged column blocks
+#   q = 3, N = 300: n = 600, even -- the wide update instance over two row blocks; 256 % s = 0
+# Every clause of the two tests runs at every shape; only the number of iterations is smaller beyond the toy (2, split 1 + 1).
+LOOPS = {(5, 7): LOOP, (6, 257): dict(LOOP, n_iter=2, burn=257, stride=129), (3, 300): dict(LOOP, n_iter=2, burn=300, stride=151)}
+_loop_problems = {}
 
 
-def loop_problem(g, ctx):
-    """N = 7, q = 5: (N, q, W0, Pi_d, Pij_d, X0 (N, K), mask)"""
-    Zo, q, mJ, Pi = synth_model(5, 7)
-    N = Zo.shape[1]
-    Z = np.ascontiguousarray(Zo.T.astype(np.int8))
-    Pi_d, Pij_d = tm.frequencies(Z, np.ones(Z.shape[1]), float(Z.shape[1]), q)
-    X0 = np.asfortranarray(Z[:, :LOOP["K"]])
-    return N, q, g.potts_from_gaussian(mJ, Pi, q, ctx=ctx), Pi_d, Pij_d, X0, (np.arange(N) % 3 != 1).astype(np.int8)
+def loop_problem(g, ctx, q=5, N=7):
+    """(N, q, W0, Pi_d, Pij_d, X0 (N, K), mask, the settings), made once per shape and never written to"""
+    if (q, N) not in _loop_problems:
+        L = LOOPS[q, N]
+        Zo, q, mJ, Pi = synth_model(q, N)
+        assert Zo.shape[1] == N
+        Z = np.ascontiguousarray(Zo.T.astype(np.int8))
+        Pi_d, Pij_d = tm.frequencies(Z, np.ones(Z.shape[1]), float(Z.shape[1]), q)
+        X0 = np.asfortranarray(Z[:, :L["K"]])
+        out = (g.potts_from_gaussian(mJ, Pi, q, ctx=ctx), Pi_d, Pij_d, X0, (np.arange(N) % 3 != 1).astype(np.int8))
+        for a in out:
+            a.setflags(write=False)
+        _loop_problems[q, N] = (N, q) + out + (L,)
+    return _loop_problems[q, N]
 
 
-def device_loop(g, c, N, q, W, Pi_d, Pij_d, X, mask, flags, iter0, n_iter, want_last=False):
+def device_loop(g, c, L, N, q, W, Pi_d, Pij_d, X, mask, flags, iter0, n_iter, want_last=False):
     from gaussdca.jl_amd import devops
 
-    L = LOOP
     n = N * (q - 1)
     dW, dPi, dPij, dX = up(g, c, W), up(g, c, Pi_d), up(g, c, Pij_d), up(g, c, X)
     dmask = None if mask is None else up(g, c, mask)
@@ -157,70 +174,82 @@ def device_loop(g, c, N, q, W, Pi_d, Pij_d, X, mask, flags, iter0, n_iter, want_
     out = (dW.download((n, n)), dX.download((N, L["K"]), dtype=np.int8), dtr.download((n_iter, 4), order="C"))
     if want_last:
         out += (dXs.download((N, L["n_samples"], L["K"]), dtype=np.int8),)
+        dXs.free()
+    for b in (dW, dPi, dPij, dX, dtr) + (() if dmask is None else (dmask,)):
+        b.free()
     return out
 
 
-def operator_iteration(g, c, N, q, W, Pi_d, Pij_d, X, mask, flags, t, model=False):
+def operator_iteration(g, c, L, N, q, W, Pi_d, Pij_d, X, mask, flags, t, model=False):
     """the steps 1 - 5 of iteration t with the operator forms -> (W, X, out (4,), Xs); model: bm_model.iteration driven with the
     device's thresholds and start tables must give the same W, X and out"""
     from gaussdca.jl_amd import devops
 
-    L = LOOP
     K, S = L["K"], L["n_samples"]
     n, T = N * (q - 1), L["burn"] + L["n_samples"] * L["stride"]
-    dW, dZero, dX = up(g, c, W), up(g, c, np.zeros(n)), up(g, c, X)
+    M = K * S
+    dW, dZero, dX, dOnes = up(g, c, W), up(g, c, np.zeros(n)), up(g, c, X), up(g, c, np.ones(M))
     dmask = None if mask is None else up(g, c, mask)
     dXs, dacc, _, dthr, _, _ = devops.sample_dev(c, dW, dZero, N, q, dX, K, L["beta"], L["burn"], L["stride"], S, L["seed"], t * K, dmask, flags,
                                                  want=("thr",))
     Xs = dXs.download((N, S, K), dtype=np.int8)
     acc = dacc.download((K,), dtype=np.int32)
     Xn = np.asfortranarray(Xs[:, -1, :])
-    M = K * S
-    dPi_m, dPij_m = devops.compute_weighted_frequencies_dev(c, dXs, N, M, q, up(g, c, np.ones(M)), float(M))
+    dPi_m, dPij_m = devops.compute_weighted_frequencies_dev(c, dXs, N, M, q, dOnes, float(M))
     dPi_d, dPij_d = up(g, c, Pi_d), up(g, c, Pij_d)
-    out = devops.bm_readout_dev(c, dPi_d, dPij_d, dPi_m, dPij_m, N, q).download((4,))
+    dout = devops.bm_readout_dev(c, dPi_d, dPij_d, dPi_m, dPij_m, N, q)
+    out = dout.download((4,))
     assert out[3] == 0.0
     out[3] = np.float64(int(acc.astype(np.int64).sum())) / np.float64(K * T)
     devops.bm_update_dev(c, dW, dPij_d, dPij_m, N, q, L["eta"], L["lam"])
     Wn = dW.download((n, n))
     if model:
-        V0 = devops.mutation_scan_dev(c, up(g, c, W), dZero, N, q, dX, K, g._lib.MUT_POTENTIAL).download((K, N, q), order="C")
+        dW0 = up(g, c, W)
+        dV0 = devops.mutation_scan_dev(c, dW0, dZero, N, q, dX, K, g._lib.MUT_POTENTIAL)
+        V0 = dV0.download((K, N, q), order="C")
+        dW0.free(), dV0.free()
         thr = dthr.download((K, T), order="C")
-        Wm, Xm, om, Xsm, Pi_m, Pij_m = bm.iteration(W, Pi_d, Pij_d, X, q, t, flags, L["beta"], L["seed"], L["burn"], L["stride"], S, L["eta"],
-                                                    L["lam"], mask, thr=thr, V0=V0)
+        Wm, Xm, om, Xsm, Pi_m, Pij_m, bound = bm.iteration(W, Pi_d, Pij_d, X, q, t, flags, L["beta"], L["seed"], L["burn"], L["stride"], S,
+                                                           L["eta"], L["lam"], mask, thr=thr, V0=V0, with_bound=True)
         assert np.array_equal(Xsm, np.transpose(Xs, (2, 1, 0))), t
         assert same_bits(dPij_m.download((n, n)), Pij_m) and same_bits(dPi_m.download((n,)), Pi_m), t
         assert same_bits(Wn, Wm), (t, int((bits(Wn) != bits(Wm)).sum()))
         assert np.array_equal(Xn, Xm) and out[0] == om[0] and out[1] == om[1] and out[3] == om[3], t
-        _, bound = bm.readout(Pi_d, Pij_d, Pi_m, Pij_m, N, q)
         assert abs(out[2] - om[2]) <= bound, (t, out[2], om[2], bound)
+    for b in (dW, dZero, dX, dOnes, dXs, dacc, dthr, dPi_m, dPij_m, dPi_d, dPij_d, dout) + (() if dmask is None else (dmask,)):
+        b.free()
     return Wn, Xn, out, Xs
 
 
 STATE_SPACES = [(0, False), (sm.GAPS, False), (sm.GAPS, True)]
+# the toy keeps its three ids; the two wide shapes follow, each in the three state spaces
+LOOP_CASES = [(q, N, flags, masked) for (q, N) in LOOPS for flags, masked in STATE_SPACES]
+LOOP_IDS = [("" if (q, N) == (5, 7) else "q%d-N%d-" % (q, N)) + ("gaps-masked" if masked else "gaps" if flags else "residues")
+            for q, N, flags, masked in LOOP_CASES]
 
 
-@pytest.mark.parametrize("flags,masked", STATE_SPACES, ids=["residues", "gaps", "gaps-masked"])
-def test_loop_is_the_operator_chain(g, ctx, flags, masked):
-    N, q, W0, Pi_d, Pij_d, X0, mask = loop_problem(g, ctx)
+@pytest.mark.parametrize("q,N,flags,masked", LOOP_CASES, ids=LOOP_IDS)
+def test_loop_is_the_operator_chain(g, ctx, q, N, flags, masked):
+    N, q, W0, Pi_d, Pij_d, X0, mask, L = loop_problem(g, ctx, q, N)
     mask = mask if masked else None
-    n_iter = LOOP["n_iter"]
-    W, X, trace, last = device_loop(g, ctx, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 3, n_iter, want_last=True)
+    n_iter = L["n_iter"]
+    W, X, trace, last = device_loop(g, ctx, L, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 3, n_iter, want_last=True)
     assert_container(W, N, q)
     # the operator forms, iteration by iteration
     Wc, Xc, rows = W0, X0, []
     for it in range(n_iter):
-        Wc, Xc, out, Xs = operator_iteration(g, ctx, N, q, Wc, Pi_d, Pij_d, Xc, mask, flags, 3 + it)
+        Wc, Xc, out, Xs = operator_iteration(g, ctx, L, N, q, Wc, Pi_d, Pij_d, Xc, mask, flags, 3 + it)
         rows.append(out)
     assert same_bits(W, Wc) and np.array_equal(X, Xc) and same_bits(trace, np.stack(rows)) and np.array_equal(last, Xs)
     assert not np.array_equal(X, X0) and np.all((trace[:, 3] > 0) & (trace[:, 3] <= 1)) and np.all(np.abs(trace[:, 2]) <= 1)
     print("trace:\n%s" % trace)
-    # 5 = 2 + 3 through W, X and iter0
-    Wa, Xa, ta = device_loop(g, ctx, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 3, 2)
-    Wb, Xb, tb = device_loop(g, ctx, N, q, Wa, Pi_d, Pij_d, Xa, mask, flags, 5, 3)
+    # n_iter = a + b through W, X and iter0: 5 = 2 + 3 on the toy, 2 = 1 + 1 beyond it
+    a = max(1, 2 * n_iter // 5)
+    Wa, Xa, ta = device_loop(g, ctx, L, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 3, a)
+    Wb, Xb, tb = device_loop(g, ctx, L, N, q, Wa, Pi_d, Pij_d, Xa, mask, flags, 3 + a, n_iter - a)
     assert same_bits(W, Wb) and np.array_equal(X, Xb) and same_bits(trace, np.concatenate((ta, tb)))
     # another iter0: other streams, another run
-    assert not same_bits(device_loop(g, ctx, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 4, n_iter)[0], W)
+    assert not same_bits(device_loop(g, ctx, L, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 4, n_iter)[0], W)
     # however the chains are cut into launches and wherever the tables live
     for chunk in (1, 7, 0):
         for where in ("lds", "hbm"):
@@ -228,25 +257,25 @@ def test_loop_is_the_operator_chain(g, ctx, flags, masked):
             try:
                 c.set_option("SAMPLE_CHUNK", chunk)
                 c.set_option("WALK_TABLE", where)
-                Wo, Xo, to = device_loop(g, c, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 3, n_iter)
+                Wo, Xo, to = device_loop(g, c, L, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 3, n_iter)
             finally:
                 c.close()
             assert same_bits(W, Wo) and np.array_equal(X, Xo) and same_bits(trace, to), (chunk, where)
     # the host-pointer form
-    Wh, Xh, th = g.bm_learn(W0, Pi_d, Pij_d, X0, n_iter, q, eta=LOOP["eta"], lam=LOOP["lam"], burn=LOOP["burn"], stride=LOOP["stride"],
-                            n_samples=LOOP["n_samples"], seed=LOOP["seed"], iter0=3, mask=mask, gaps=bool(flags), ctx=ctx)
+    Wh, Xh, th = g.bm_learn(W0, Pi_d, Pij_d, X0, n_iter, q, eta=L["eta"], lam=L["lam"], burn=L["burn"], stride=L["stride"],
+                            n_samples=L["n_samples"], seed=L["seed"], iter0=3, mask=mask, gaps=bool(flags), ctx=ctx)
     assert same_bits(W, Wh) and np.array_equal(X, Xh) and same_bits(trace, th)
 
 
-@pytest.mark.parametrize("flags,masked", STATE_SPACES, ids=["residues", "gaps", "gaps-masked"])
-def test_loop_is_the_numpy_statement(g, ctx, flags, masked):
+@pytest.mark.parametrize("q,N,flags,masked", LOOP_CASES, ids=LOOP_IDS)
+def test_loop_is_the_numpy_statement(g, ctx, q, N, flags, masked):
     """the operator chain with the thresholds and the start tables asked from the device, fed to bm_model: W after EVERY iteration"""
-    N, q, W0, Pi_d, Pij_d, X0, mask = loop_problem(g, ctx)
+    N, q, W0, Pi_d, Pij_d, X0, mask, L = loop_problem(g, ctx, q, N)
     mask = mask if masked else None
     W, X = W0, X0
-    for it in range(LOOP["n_iter"]):
-        W, X, _, _ = operator_iteration(g, ctx, N, q, W, Pi_d, Pij_d, X, mask, flags, it, model=True)
-        Wl, Xl, _ = device_loop(g, ctx, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 0, it + 1)
+    for it in range(L["n_iter"]):
+        W, X, _, _ = operator_iteration(g, ctx, L, N, q, W, Pi_d, Pij_d, X, mask, flags, it, model=True)
+        Wl, Xl, _ = device_loop(g, ctx, L, N, q, W0, Pi_d, Pij_d, X0, mask, flags, 0, it + 1)
         assert same_bits(W, Wl) and np.array_equal(X, Xl), it
 
 
@@ -320,7 +349,7 @@ def test_learning_lowers_the_exact_deviation(g, ctx):
 
 # ---- 6. arguments -------------------------------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_model_and_the_chains_untouched(g, ctx):
-    N, q, W0, Pi_d, Pij_d, X0, _ = loop_problem(g, ctx)
+    N, q, W0, Pi_d, Pij_d, X0, _, _ = loop_problem(g, ctx)
     lib, p, EINVAL = ctx.lib, g._lib._p, g._lib.GDCA_EINVAL
     W, X = np.asfortranarray(W0.copy()), X0.copy(order="F")
     trace = np.full((5, 4), np.nan)
@@ -372,3 +401,190 @@ def test_refusals_leave_the_model_and_the_chains_untouched(g, ctx):
     # the context still works
     Wn, Xn, tr = g.bm_learn(W0, Pi_d, Pij_d, X0, 1, q, burn=2, stride=3, ctx=ctx)
     assert np.all(np.isfinite(tr)) and not same_bits(Wn, W0)
+
+
+# ---- 7. the whole fit: gDCA_bm and devops.bm_fit on a golden family ----------------------------------------------------------------------------
+# small.fasta.gz: N = 53, q = 21, n = 1060, M = 106 (98 without duplicates).  burn and stride are the defaults, 10 N and N: 636 proposals
+# a chain and iteration.  Every setting that has a default is given another value, so that one put into another's place shows.
+# beta = 0.1 because the chains must move for the test to see anything: at beta = 0.9 the Gaussian start of this family of 106
+# sequences accepts ONE of the first iteration's 10 176 proposals and none afterwards (MEASURED on an MI355X, and the same in
+# bm_model.fit), so three iterations tally the start sequences three times; at 0.1 bm_model.fit accepts 35 % to 77 %.
+FASTA = "small.fasta.gz"
+FIT_ITER = 3
+FIT = dict(K=16, n_samples=2, eta=0.5, lam=0.01, beta=0.1, seed=5, pseudocount=0.5)
+FIT_CASES = [dict(), dict(init="independent"), dict(target_pseudocount=0.1), dict(gaps=False), dict(remove_dups=True)]
+FIT_IDS = ["gaussian", "independent", "target-0.1", "residues", "dedup"]
+_fits, _chains = {}, {}
+
+
+def family(g, refdata, remove_dups=False):
+    """(Z (N, M) as gDCA_bm reads it, N, M, q)"""
+    Z = g.read_fasta_alignment(os.path.join(refdata, FASTA), 0.9)
+    if remove_dups:
+        Z, _ = g.remove_duplicate_sequences(Z)
+    return (Z,) + Z.shape + (int(Z.max()),)
+
+
+def fit_of(g, ctx, refdata, n_iter=FIT_ITER, **kw):
+    """gDCA_bm on the family with FIT's settings and kw on the module's context, called once per set of arguments"""
+    key = (n_iter,) + tuple(sorted(kw.items()))
+    if key not in _fits:
+        _fits[key] = g.gDCA_bm(os.path.join(refdata, FASTA), n_iter, ctx=ctx, **dict(FIT, **kw))
+    return _fits[key]
+
+
+def operator_chain(g, ctx, refdata, init="gaussian", target_pseudocount=0.0, gaps=True, remove_dups=False):
+    """What devops.bm_fit documents, step by step with the HOST operator forms the suite pins one by one: the weighted frequencies at
+    theta = :auto, add_pseudocount twice from the same true tallies, compute_C, inv_cholesky, potts_from_gaussian (or potts_independent
+    in numpy), then bm_learn from the first K sequences with burn = 10 N, stride = N and iter0 = 0 -> a dict, made once per case"""
+    key = (init, target_pseudocount, gaps, remove_dups)
+    if key not in _chains:
+        Z, N, M, q = family(g, refdata, remove_dups)
+        Pi_t, Pij_t, Meff, wts = g.compute_weighted_frequencies(Z, q, ":auto", ctx=ctx)
+        Pi_d, Pij_d = g.add_pseudocount(Pi_t, Pij_t, target_pseudocount, q, ctx=ctx)
+        Pi, Pij = g.add_pseudocount(Pi_t, Pij_t, FIT["pseudocount"], q, ctx=ctx)
+        mJ = g.inv_cholesky(g.compute_C(Pi, Pij, ctx=ctx), ctx=ctx) if init == "gaussian" else None
+        W0 = g.potts_from_gaussian(mJ, Pi, q, ctx=ctx) if init == "gaussian" else bm.potts_independent(Pi, N, q)
+        W, X, trace = g.bm_learn(W0, Pi_d, Pij_d, Z[:, :FIT["K"]], FIT_ITER, q, eta=FIT["eta"], lam=FIT["lam"], beta=FIT["beta"], burn=10 * N,
+                                 stride=N, n_samples=FIT["n_samples"], seed=FIT["seed"], iter0=0, gaps=gaps, ctx=ctx)
+        _chains[key] = dict(Z=Z, N=N, M=M, q=q, Meff=Meff, wts=wts, Pi_d=Pi_d, Pij_d=Pij_d, Pi=Pi, mJ=mJ, W0=W0, W=W, X=X, trace=trace)
+    return _chains[key]
+
+
+@pytest.mark.parametrize("kw", FIT_CASES, ids=FIT_IDS)
+def test_fit_is_the_chain_of_the_operators(g, ctx, refdata, kw):
+    """W and trace of gDCA_bm, and of devops.bm_fit on the alignment itself, are the bits of the chain of the host operator forms.
+    (Every step of it is: the host forms and the _dev forms bm_fit calls gave the same bits on an MI355X, the inverse in place over
+    the covariance included, so the reference is built from the host forms throughout.)"""
+    from gaussdca.jl_amd import devops
+
+    W, trace = fit_of(g, ctx, refdata, **kw)
+    ref = operator_chain(g, ctx, refdata, **kw)
+    Z, N, q = ref["Z"], ref["N"], ref["q"]
+    n = N * (q - 1)
+    assert (N, q, ref["M"]) == (53, 21, 98 if kw.get("remove_dups") else 106)
+    assert W.shape == (n, n) and trace.shape == (FIT_ITER, 4)
+    assert same_bits(trace, ref["trace"]), (trace, ref["trace"])
+    assert same_bits(W, ref["W"]), int((bits(W) != bits(ref["W"])).sum())
+    assert_container(W, N, q)
+    assert np.all(np.isfinite(trace)) and np.all((trace[:, 3] > 0) & (trace[:, 3] <= 1)) and not same_bits(W, ref["W0"])
+    print("%s: trace\n%s" % (kw, trace))
+    direct = devops.bm_fit(Z, q, FIT_ITER, ctx=ctx, **dict(FIT, **{k: v for k, v in kw.items() if k != "remove_dups"}))
+    assert len(direct) == 2 and same_bits(direct[0], W) and same_bits(direct[1], trace)
+    if kw:  # the case's argument matters: another W than the first case's
+        base = fit_of(g, ctx, refdata)
+        assert not same_bits(W, base[0]) and not same_bits(trace, base[1])
+    if "target_pseudocount" in kw:  # ... and it moves the targets alone: the same start
+        assert same_bits(ref["W0"], operator_chain(g, ctx, refdata)["W0"]) and not same_bits(ref["Pij_d"], operator_chain(g, ctx, refdata)["Pij_d"])
+
+
+@pytest.mark.parametrize("init,tpc", [("gaussian", 0.0), ("independent", 0.1)], ids=["gaussian", "independent-target-0.1"])
+def test_fit_is_the_numpy_statement(g, ctx, refdata, init, tpc):
+    """bm_model.fit with the oracle's weights, driven as operator_iteration(model=True) drives bm_model.iteration: the thresholds and
+    the start tables (and, for the Gaussian start, the inverse) asked from the device.  The targets are the model's bit for bit and
+    within test_operator_parity's bars of the oracle's; W after every iteration, the chains' last states and trace[:, (0, 1, 3)] are
+    the model's bits, trace[:, 2] is within bm_model.readout's bound."""
+    from oracle import gdca_oracle as o
+
+    kw = dict(init=init, target_pseudocount=tpc)
+    ref = operator_chain(g, ctx, refdata, **kw)
+    Z, N, q = ref["Z"], ref["N"], ref["q"]
+    K, S = FIT["K"], FIT["n_samples"]
+    zeros = np.zeros(N * (q - 1))
+    Zo = np.ascontiguousarray(Z.T)
+    wts, Meff, _, _ = o.compute_weights(Zo, "auto")
+
+    def thresholds(t):
+        return g.sample(ref["W0"], zeros, Z[:, :K], q, beta=FIT["beta"], burn=10 * N, stride=N, n_samples=S, seed=FIT["seed"], stream0=t * K,
+                        gaps=True, trace=True, ctx=ctx)[3]
+
+    f = bm.fit(Z, q, FIT_ITER, wts, Meff, K, eta=FIT["eta"], lam=FIT["lam"], pseudocount=FIT["pseudocount"], target_pseudocount=tpc, init=init,
+               n_samples=S, beta=FIT["beta"], seed=FIT["seed"], inverse=lambda C: ref["mJ"], thresholds=thresholds,
+               tables=lambda W, X: g.mutation_scan(W, zeros, X, q, what="potential", ctx=ctx))
+    # the targets: against the oracle's at the bars of test_operator_parity (frequencies 1e-12 of the largest, add_pseudocount the
+    # same bits from the same input), and the device's own are the model's
+    Pi_o, Pij_o = o.compute_frequencies(Zo, q, wts, Meff)
+    Pi_do, Pij_do = o.add_pseudocount(Pi_o, Pij_o, tpc, q)
+    assert np.max(np.abs(f["Pi_d"] - Pi_do)) <= 1e-12 * np.max(np.abs(Pi_do)) and np.max(np.abs(f["Pij_d"] - Pij_do)) <= 1e-12 * np.max(np.abs(Pij_do))
+    again = bm.add_pseudocount(Pi_o, Pij_o, tpc, q)
+    assert np.array_equal(again[0], Pi_do) and np.array_equal(again[1], Pij_do)
+    assert same_bits(ref["Pi_d"], f["Pi_d"]) and same_bits(ref["Pij_d"], f["Pij_d"]) and same_bits(ref["Pi"], f["Pi"])
+    assert same_bits(ref["W0"], f["W0"]), int((bits(ref["W0"]) != bits(f["W0"])).sum())
+    # the loop
+    for it in range(FIT_ITER):
+        Wd = fit_of(g, ctx, refdata, n_iter=it + 1, **kw)[0]
+        assert same_bits(Wd, f["Ws"][it]), (it, int((bits(Wd) != bits(f["Ws"][it])).sum()))
+    W, trace = fit_of(g, ctx, refdata, **kw)
+    assert same_bits(W, ref["W"]) and np.array_equal(ref["X"], f["X"])
+    assert same_bits(trace[:, (0, 1, 3)], f["trace"][:, (0, 1, 3)]), (trace, f["trace"])
+    err = np.abs(trace[:, 2] - f["trace"][:, 2])
+    print("%s: trace\n%s\n|trace[:, 2] - exact| %s, bound %s" % (kw, trace, err, f["bounds"]))
+    assert np.all(np.isfinite(f["bounds"])) and np.all(err <= f["bounds"])
+
+
+def test_what_the_fit_may_not_depend_on(g, ctx, refdata):
+    fasta = os.path.join(refdata, FASTA)
+    W, trace = fit_of(g, ctx, refdata)
+    M = family(g, refdata)[2]
+    # K beyond the family is the whole family (and not the K = 16 of the other tests)
+    every = g.gDCA_bm(fasta, 2, ctx=ctx, **dict(FIT, K=M))
+    beyond = g.gDCA_bm(fasta, 2, ctx=ctx, **dict(FIT, K=10 ** 6))
+    assert same_bits(every[0], beyond[0]) and same_bits(every[1], beyond[1]) and not same_bits(every[1], trace[:2])
+    # a shorter fit is the beginning of a longer one
+    two = fit_of(g, ctx, refdata, n_iter=2)
+    assert same_bits(two[1], trace[:2]) and not same_bits(two[0], W)
+    # a second call repeats the bits
+    again = g.gDCA_bm(fasta, FIT_ITER, ctx=ctx, **FIT)
+    assert same_bits(again[0], W) and same_bits(again[1], trace)
+    # the tables in HBM and the chains cut into launches of 97 proposals (636 = 6 x 97 + 54)
+    c = g.Context(0)
+    try:
+        c.set_option("WALK_TABLE", "hbm")
+        c.set_option("SAMPLE_CHUNK", 97)
+        other = g.gDCA_bm(fasta, FIT_ITER, ctx=c, **FIT)
+    finally:
+        c.close()
+    assert same_bits(other[0], W) and same_bits(other[1], trace)
+
+
+def test_scores_of_the_fit(g, ctx, refdata):
+    """scores=True: the third entry is the ranking of APC(FN(W)) of the host forms entry for entry; FN(W) is within score_model.fn_bound of
+    the extended-precision model; and the fields on W's diagonal blocks do not reach the contact score"""
+    sep = 4
+    W, trace, R = g.gDCA_bm(os.path.join(refdata, FASTA), FIT_ITER, scores=True, min_separation=sep, ctx=ctx, **FIT)
+    base = fit_of(g, ctx, refdata)
+    assert same_bits(W, base[0]) and same_bits(trace, base[1])
+    _, N, _, q = family(g, refdata)
+    s = q - 1
+    FN = g.compute_FN(W, q, ctx=ctx)
+    want = g.compute_ranking(g.correct_APC(FN, ctx=ctx), sep)
+    assert len(R) == len(want) == (N - sep) * (N - sep + 1) // 2
+    assert np.array_equal(R.i, want.i) and np.array_equal(R.j, want.j) and same_bits(R.score, want.score)
+    assert np.all(np.isfinite(R.score)) and np.all(np.diff(R.score) <= 0)
+    ref, scale = score_model.fn_model(W, q)
+    bound = score_model.fn_bound(s, ref, scale)
+    err = np.abs(FN - ref)
+    off = ~np.eye(N, dtype=bool)
+    print("FN(W): worst err / bound %.3g" % float(np.max(err[off] / bound[off])))
+    assert np.all(err <= bound) and np.all(ref[off] > 10 * bound[off])
+    junk = W.copy()
+    inside = bm.multipliers(N, q) != 1.0
+    junk[inside] = 1e3 * np.random.default_rng(1).normal(size=int(inside.sum()))
+    assert same_bits(g.compute_FN(junk, q, ctx=ctx), FN)
+    # and the other separation is another list of the same scores
+    R5 = g.gDCA_bm(os.path.join(refdata, FASTA), FIT_ITER, scores=True, ctx=ctx, **FIT)[2]
+    assert len(R5) == (N - 5) * (N - 4) // 2 and R5 == g.compute_ranking(g.correct_APC(FN, ctx=ctx), 5)
+
+
+def test_a_fit_leaves_nothing_behind(g, refdata):
+    fasta = os.path.join(refdata, FASTA)
+    used, fresh = g.Context(0), g.Context(0)
+    try:
+        out = g.gDCA_bm(fasta, 2, scores=True, ctx=used, **FIT)
+        assert np.all(np.isfinite(out[0])) and np.all(np.isfinite(out[1]))
+        R_used, R_fresh = g.gDCA(fasta, ctx=used), g.gDCA(fasta, ctx=fresh)
+    finally:
+        used.close()
+        fresh.close()
+    assert len(R_used) == len(R_fresh) > 0
+    assert np.array_equal(R_used.i, R_fresh.i) and np.array_equal(R_used.j, R_fresh.j) and same_bits(R_used.score, R_fresh.score)

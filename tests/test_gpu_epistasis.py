@@ -24,6 +24,9 @@ pytestmark = pytest.mark.gpu
 T, CHUNK = 4, 64
 # (q, N, K): N = T - 1, T, T + 1, 2 T + 1; K = 1, 3, one chunk, one chunk + 1; q = 21 is the compile-time instance, the others the generic one
 SHAPES = [(2, 2, 1), (5, 3, 3), (5, 4, 3), (5, 5, CHUNK + 1), (5, 9, CHUNK), (21, 7, CHUNK + 1), (31, 6, 3)]
+# at width: 65 tiles a side (2145 tiles) with a ragged last tile; the benchmarked width, 125 tiles a side (7875 tiles: the tile index
+# is recovered from a square root); a second sequence chunk with one live lane at a ragged width (11 tiles a side)
+SHAPES += [(6, 257, 3), (3, 500, 2), (6, 41, CHUNK + 1)]
 GOLD = [("small.fasta.gz", 0.8), ("small.fasta.gz", 0.2)]
 ALL = SHAPES + GOLD
 IDS = ["q%d-N%d-K%d" % c for c in SHAPES] + ["small-pc%g" % pc for _, pc in GOLD]

@@ -467,3 +467,30 @@ def test_a_big_table(g, ctx, refdata):
     V0 = g.mutation_scan(mJ, Pi, X, q, what="potential", ctx=ctx)
     d = assert_is_the_rule(g, ctx, mJ, Pi, X, q, V0, None, sm.GAPS, 1.0, seed=8, burn=100, stride=50, n_samples=2, tag="large")
     print("large: accepted", d["accepted"].tolist(), "of 200")
+    assert d["accepted"].max() >= 100
+    # the other instance and the other paths at this width (N > 256: every loop over the sites takes a second pass): the table asked
+    # into LDS and into HBM (k_sample<true>, k_sample<false>), a mask, and the 200 proposals cut into launches of 97, 97 and 6 -- each
+    # the rule from the same V0, and all of them the same bits
+    mask = (np.arange(N) % 3 == 0).astype(np.int8)
+    for m in (None, mask):
+        runs = {}
+        for where in ("lds", "hbm"):
+            for chunk in (0, 97):
+                c = g.Context(0)
+                try:
+                    c.set_option("WALK_TABLE", where)
+                    c.set_option("SAMPLE_CHUNK", chunk)
+                    runs[where, chunk] = assert_is_the_rule(g, c, mJ, Pi, X, q, V0, m, sm.GAPS, 1.0, seed=8, burn=100, stride=50, n_samples=2,
+                                                            tag="large mask %d %s chunk %d" % (m is not None, where, chunk))
+                finally:
+                    c.close()
+        for key, r in runs.items():
+            same(r, runs["lds", 0], "mask %d: %s / lds in one launch" % (m is not None, key))
+        a = runs["lds", 0]
+        print("large mask %d: accepted %s of 200" % (m is not None, a["accepted"].tolist()))
+        if m is None:
+            same(a, d, "default placement")
+        else:
+            code = np.where(a["moves"] >= 0, a["moves"], -1 - a["moves"])
+            assert np.all((code // q) % 3 == 0) and a["accepted"].max() >= 100
+            assert np.array_equal(a["Xs"][mask == 0], np.repeat(X[mask == 0][:, None, :], 2, axis=1))

@@ -209,6 +209,28 @@ def test_a_big_table(g, ctx, refdata):
     d = assert_is_the_rule(g, ctx, mJ, Pi, X, q, V0, tag="large")
     print("large: walk lengths", d["steps"].tolist())
     assert 300 <= d["steps"].max() < 4 * N
+    # the other instance and the other paths at this width (N > 256: every loop over the sites takes a second pass): the table asked
+    # into LDS and into HBM (k_walk<true>, k_walk<false>), a mask, both flags -- each the rule from the same V0, and the same bits
+    mask = (np.arange(N) % 3 == 0).astype(np.int8)
+    lds, hbm = g.Context(0), g.Context(0)
+    try:
+        lds.set_option("WALK_TABLE", "lds")
+        hbm.set_option("WALK_TABLE", "hbm")
+        for m, flags in ((None, 0), (mask, 0), (None, 3), (mask, 3)):
+            tag = "large mask %d flags %d" % (m is not None, flags)
+            a = assert_is_the_rule(g, lds, mJ, Pi, X, q, V0, mask=m, flags=flags, tag=tag + " lds")
+            b = assert_is_the_rule(g, hbm, mJ, Pi, X, q, V0, mask=m, flags=flags, tag=tag + " hbm")
+            same(a, b, tag + ": lds / hbm")
+            print("%s: walk lengths %s" % (tag, a["steps"].tolist()))
+            assert a["steps"].max() >= N // 4
+            if m is None and flags == 0:
+                same(a, d, "default placement")
+            if m is not None:
+                used = a["path"][:, :, 0]
+                assert np.all(used[used >= 0] % 3 == 0) and np.array_equal(a["Xout"][mask == 0], X[mask == 0])
+    finally:
+        lds.close()
+        hbm.close()
 
 
 # ---- 7. lower triangle only ------------------------------------------------------------------------------------------------------------------------
