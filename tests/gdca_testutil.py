@@ -124,6 +124,24 @@ def edge_family(M, N, q, seed):
     return np.asfortranarray(Z.T.astype(np.int8))
 
 
+# ---- the schedules of the SPD inverse that the tests force through a context's options (test_gpu_parity.py, test_gpu_inverse_exact.py) -------
+_SCHEDULES = [{"GDCA_GROUP": "1"}, {"GDCA_GROUP": "2"}, {"GDCA_GROUP": "3"}, {"GDCA_GROUP": "4"},
+              {"GDCA_GROUP": "3", "GDCA_MCUS": "1"}, {"GDCA_GROUP": "2", "GDCA_MCUS": "16"},
+              {"GDCA_GROUP": "4", "GDCA_MCUS": "3"}, {"GDCA_GROUP": "3", "GDCA_REM_TAIL": "0"},
+              {"GDCA_GROUP": "2", "GDCA_REM_TAIL": "7"}, {"GDCA_GROUP": "4", "GDCA_REM_TAIL": "100000"},
+              {"GDCA_GROUP": "3", "GDCA_PANEL_HALVES": "1"}, {"GDCA_GROUP": "2", "GDCA_PANEL_HALVES": "0"},
+              {"GDCA_GROUP": "1", "GDCA_PANEL_HALVES": "0"}, {"GDCA_GROUP": "3", "GDCA_RAMP": "0"},
+              {"GDCA_GROUP": "4", "GDCA_RAMP": "0"}, {"GDCA_GROUP": "2", "GDCA_RAMP": "0", "GDCA_MCUS": "2"},
+              {"GDCA_GROUP": "3", "GDCA_RAGGED": "0"}, {"GDCA_GROUP": "4", "GDCA_SWEEP_DEBUG": "1"},
+              {"GDCA_GROUP": "1", "GDCA_SWEEP_DEBUG": "1", "GDCA_MCUS": "16"},
+              {"GDCA_GROUP": "1", "GDCA_SLAB": "0"}, {"GDCA_GROUP": "1", "GDCA_SLAB": "0", "GDCA_RING": "2"},
+              {"GDCA_GROUP": "1", "GDCA_RING": "2"}, {"GDCA_GROUP": "1", "GDCA_RING": "3", "GDCA_MCUS": "2"},
+              {"GDCA_GROUP": "1", "GDCA_MCUS": "1"},
+              # the merged kernel (k_sweep_merged) carrying this one inverse (SWEEP_DEBUG bit 3), workspaces poisoned (bit 4)
+              {"GDCA_SWEEP_DEBUG": "24"}, {"GDCA_SWEEP_DEBUG": "24", "GDCA_SLAB": "0"}, {"GDCA_SWEEP_DEBUG": "25", "GDCA_RING": "2"},
+              {"GDCA_SWEEP_DEBUG": "24", "GDCA_MERGE_MCUS": "1"}, {"GDCA_SWEEP_DEBUG": "24", "GDCA_RAGGED": "0", "GDCA_MERGE_MCUS": "16"}]
+
+
 # ---- the model read-outs (energies, pair energies, mutation scan): what their GPU tests share ---------------------------------------------
 @pytest.fixture(scope="module")
 def g():

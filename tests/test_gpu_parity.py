@@ -11,7 +11,7 @@ import math
 import numpy as np
 import pytest
 
-from gdca_testutil import CASES, compare_with_golden, random_msa, score_close
+from gdca_testutil import _SCHEDULES, CASES, compare_with_golden, random_msa, score_close
 
 pytestmark = pytest.mark.gpu
 
@@ -540,23 +540,6 @@ def test_large_spd_inverse_residual(g, ctx, n):
     R = A @ (X @ V) - V
     assert np.max(np.abs(R)) <= 1e-9 * np.max(np.abs(V))
     assert np.array_equal(X, X.T)
-
-
-_SCHEDULES = [{"GDCA_GROUP": "1"}, {"GDCA_GROUP": "2"}, {"GDCA_GROUP": "3"}, {"GDCA_GROUP": "4"},
-              {"GDCA_GROUP": "3", "GDCA_MCUS": "1"}, {"GDCA_GROUP": "2", "GDCA_MCUS": "16"},
-              {"GDCA_GROUP": "4", "GDCA_MCUS": "3"}, {"GDCA_GROUP": "3", "GDCA_REM_TAIL": "0"},
-              {"GDCA_GROUP": "2", "GDCA_REM_TAIL": "7"}, {"GDCA_GROUP": "4", "GDCA_REM_TAIL": "100000"},
-              {"GDCA_GROUP": "3", "GDCA_PANEL_HALVES": "1"}, {"GDCA_GROUP": "2", "GDCA_PANEL_HALVES": "0"},
-              {"GDCA_GROUP": "1", "GDCA_PANEL_HALVES": "0"}, {"GDCA_GROUP": "3", "GDCA_RAMP": "0"},
-              {"GDCA_GROUP": "4", "GDCA_RAMP": "0"}, {"GDCA_GROUP": "2", "GDCA_RAMP": "0", "GDCA_MCUS": "2"},
-              {"GDCA_GROUP": "3", "GDCA_RAGGED": "0"}, {"GDCA_GROUP": "4", "GDCA_SWEEP_DEBUG": "1"},
-              {"GDCA_GROUP": "1", "GDCA_SWEEP_DEBUG": "1", "GDCA_MCUS": "16"},
-              {"GDCA_GROUP": "1", "GDCA_SLAB": "0"}, {"GDCA_GROUP": "1", "GDCA_SLAB": "0", "GDCA_RING": "2"},
-              {"GDCA_GROUP": "1", "GDCA_RING": "2"}, {"GDCA_GROUP": "1", "GDCA_RING": "3", "GDCA_MCUS": "2"},
-              {"GDCA_GROUP": "1", "GDCA_MCUS": "1"},
-              # the merged kernel (k_sweep_merged) carrying this one inverse (SWEEP_DEBUG bit 3), workspaces poisoned (bit 4)
-              {"GDCA_SWEEP_DEBUG": "24"}, {"GDCA_SWEEP_DEBUG": "24", "GDCA_SLAB": "0"}, {"GDCA_SWEEP_DEBUG": "25", "GDCA_RING": "2"},
-              {"GDCA_SWEEP_DEBUG": "24", "GDCA_MERGE_MCUS": "1"}, {"GDCA_SWEEP_DEBUG": "24", "GDCA_RAGGED": "0", "GDCA_MERGE_MCUS": "16"}]
 
 
 @pytest.mark.parametrize("opts", _SCHEDULES, ids=lambda o: ",".join("%s=%s" % (k[5:], v) for k, v in o.items()))
