@@ -11,6 +11,7 @@
 
 #include "gdca_hamming_form.h"
 #include "gdca_internal.h"
+#include "gdca_sweep_schedule.h"
 #include "gdca_launch.h"
 
 struct gdca_buf {
@@ -1037,14 +1038,15 @@ static gdca_status inverse_job(gdca_ctx *ctx, int n, int n_pad, gdca_inverse_job
     CHK(ensure(ctx, ctx->G, (size_t)8 * pbytes));
     CHK(ensure(ctx, ctx->H, (size_t)8 * pbytes));
     CHK(ensure(ctx, ctx->P, (size_t)GDCA_TILE * GDCA_TILE * sizeof(double)));
-    const size_t piv_off = (4 * sg + fbytes + (size_t)3 * (nblk + 2) * sizeof(int) + 15) & ~(size_t)15;
+    const int item_ints = gdca_sweep::table_ints_max(nblk);  // the sweep's item table, whatever groups it picks
+    const size_t piv_off = (4 * sg + fbytes + (size_t)item_ints * sizeof(int) + 15) & ~(size_t)15;
     CHK(ensure(ctx, ctx->Sg, piv_off + (size_t)n_pad * sizeof(double)));
-    if (ctx->item0_cap < 3 * (nblk + 2)) {
+    if (ctx->item0_cap < item_ints) {
         if (ctx->item0_host) HIPCHK(hipHostFree(ctx->item0_host));
         ctx->item0_host = nullptr;
         ctx->item0_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&ctx->item0_host, (size_t)3 * (nblk + 2) * sizeof(int), hipHostMallocDefault));
-        ctx->item0_cap = 3 * (nblk + 2);
+        HIPCHK(hipHostMalloc((void **)&ctx->item0_host, (size_t)item_ints * sizeof(int), hipHostMallocDefault));
+        ctx->item0_cap = item_ints;
     }
     gdca_inverse_ws &ws = job->ws;
     for (int w = 0; w < 8; ++w) {

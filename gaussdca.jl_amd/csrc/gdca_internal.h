@@ -198,7 +198,7 @@ struct gdca_inverse_ws {
     double *Pg[2];     // 512 x 512: inverse of a group's diagonal super-block, by group parity
     unsigned *flags;   // dependency flags of the sweep (zeroed per inverse by the launcher)
     size_t flags_bytes;
-    int *item0_host;   // pinned: first work item of every group's sequence in the main list and in the M list (2 x (n_pad / 128 + 2) entries)
+    int *item0_host;   // pinned: the sweep's item table -- three tables of ng + 1 entries (gdca_sweep_schedule.h: item0, mitem0, gs), room for gdca_sweep::table_ints_max(n_pad / 128)
     const int *item0_host_dev;  // item0_host as the device addresses it (nullptr: the table goes through hipMemcpyAsync)
     int *item0_dev;
     int update_cus;    // compute units of the device

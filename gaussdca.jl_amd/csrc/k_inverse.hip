@@ -27,6 +27,7 @@
 
 #include "gdca_internal.h"
 #include "gdca_launch.h"
+#include "gdca_sweep_schedule.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double double2_t __attribute__((ext_vector_type(2)));
@@ -40,8 +41,8 @@ __device__ __forceinline__ int opaque_tid()
     return t;
 }
 
-#define T 128          // tile edge
-#define KC 16          // k-chunk staged per pass
+#define T GDCA_SWEEP_TILE  // tile edge
+#define KC GDCA_SWEEP_KC   // k-chunk staged per pass
 #define LDS_LD (T + 16)  // f64 elements per k-row in LDS (128-byte pad)
 
 // -------------------------------------------------------------------------------------------------
@@ -68,7 +69,7 @@ __device__ __forceinline__ int opaque_tid()
 #define MB 16                      // micro-block edge
 #define NMB (T / MB)               // micro-blocks per side
 #define PV_ROW 160                 // doubles per kk-row of an operand image
-#define SLAB_ITEMS 8               // 16-row slabs of a 128-row block (the chain's row-slab items)
+#define SLAB_ITEMS GDCA_SWEEP_SLAB_ITEMS  // 16-row slabs of a 128-row block (the chain's row-slab items)
 #define SLAB_PD 4                  // their load pipeline: rounds of 16 k in flight (a round's MFMAs take 0.4 us, a load from L2 / HBM one to two)
 
 __device__ __forceinline__ int pv_off(int kk)
@@ -1067,28 +1068,8 @@ __device__ __forceinline__ const SweepDesc &launch_desc(int f)
 #endif
 }
 
-__device__ __forceinline__ int g_start(const SweepDesc &D, int p)
-{
-    return D.gs[p];
-}
-__device__ __forceinline__ int g_size(const SweepDesc &D, int p)
-{
-    return D.gs[p + 1] - D.gs[p];
-}
-// k-chunks (16 deep) of a tile item of update p: 8 per pivot block; the block at the ragged end of the matrix counts only the
-// chunks that hold real columns (rl of its 128; the padding columns of G and H are zero), rounded up to an even number
-__device__ __forceinline__ int g_chunks(const SweepDesc &D, int p)
-{
-    const int sz = g_size(D, p);
-    if (D.rl < T && D.gs[p + 1] == D.nblk && sz > 1) return (T / KC) * (sz - 1) + 2 * ((D.rl + 2 * KC - 1) / (2 * KC));
-    return (T / KC) * sz;
-}
-// tile and write-back items of group p (what done[p] counts up to)
-__device__ __forceinline__ unsigned g_done_total(const SweepDesc &D, int p)
-{
-    const int sz = g_size(D, p), pn = D.nblk - sz;
-    return (unsigned)(pn * sz + (long long)pn * (pn + 1) / 2);
-}
+// (the groups -- g_start, g_size, g_chunks, g_done_total -- and the decode of both lists: gdca_sweep_schedule.h)
+using namespace gdca_sweep;
 
 // Pg and the G / H panels of a group live in a ring of D.ring buffers indexed by the group number: 2 (parity; multi-block groups fill
 // the four panels of a slot) or, for single-block groups, 8 one-panel slots in the same memory -- the chain may then run that many
@@ -1213,94 +1194,6 @@ __device__ __forceinline__ bool acquire_end(bool ok)
     }
     __syncthreads();
     return *abort_lds() == 0;
-}
-
-// M(q): sz (sz+1) / 2 gather items (one lower tile each), per block w a pivot + 8 (sz-1) row-slab jobs, then
-// sz (sz+1) / 2 scatter items
-// (a group of ONE block needs no scratch copy: a single item, the pivot in place)
-__device__ __forceinline__ int m_items(int sz)
-{
-    return sz == 1 ? 1 : sz * (sz + 1) + sz * (1 + SLAB_ITEMS * (sz - 1));
-}
-
-// ---- the main list: item number -> what to do --------------------------------------------------------------------------
-// The first D.pro items are panel(0); then, group after group,
-//     diag2(p+2) | rest(p+1) | wb(p) | rem(p) but for its tail | panel(p+1) | the tail of rem(p)
-// (panel(p+1) covers the rows outside groups p+1 and p+2: Pg(p+1) comes from the chain, which runs a group ahead, and its
-// other inputs were produced early in this sequence -- so the panels are complete when the tile items of update p+1 are
-// handed out, instead of holding all of them up at the start of every group).
-// kind 0: panel item (group p, row block a, part b); 1: tile item (group p, tile (a, b)); 4: the same, one of the early ones the
-// chain of a later group waits for (diag2, rest); 2: write-back item (group p, index a); 3: nothing (a remainder slot that
-// belongs to diag2).  `p` is the caller's running group (items ascend).
-struct MainItem {
-    int kind, p, a, b;
-};
-__device__ __forceinline__ MainItem main_decode(const SweepDesc &D, int &p, int item)
-{
-    if (item < D.pro) {  // panel(0): nobody is ahead of it
-        const int sz0 = g_size(D, 0), nsz0 = D.ng > 1 ? g_size(D, 1) : 0;
-        const int i0 = sz0 + nsz0 + item / (D.ppb * sz0);
-        if (D.slab && i0 == 2) return MainItem{3, 0, 0, 0};  // row block b0 + 2: the chain's (sweep_slab_item, rowoff 2)
-        return MainItem{0, 0, i0, item % (D.ppb * sz0)};
-    }
-    while (item - D.pro >= D.item0[p + 1]) ++p;
-    int e = item - D.pro - D.item0[p];
-    const int b0 = g_start(D, p), sz = g_size(D, p), c0 = b0 + sz;
-    const int nsz = p + 1 < D.ng ? g_size(D, p + 1) : 0, d0 = c0 + nsz;
-    const int n2 = p + 2 < D.ng ? g_size(D, p + 2) : 0;
-    const int nrest = D.nblk - sz - nsz;  // blocks outside this group and the next
-    // (between single blocks the chain itself does tiles (b0+1, b0+1), (b0+2, b0+1), (b0+2, b0+2) and the panels of row blocks
-    // b0 + 1 and b0 + 2 -- sweep_slab_item, sweep_xslab_item -- and what it waits for a step later is row block b0 + 3: its tiles
-    // (b0+3, b0+2), (b0+3, b0+3) take the early slots here, (b0+3, b0+1) is among rest(p+1))
-    // ... and the tiles (i, b0+2), i > b0+3, follow them: column b0 + 2 is the next step's column b0 + 1, whose tiles must carry
-    // this update before they can take the next one early -- as ordinary remainder tiles they were what the chain ended up waiting for
-    const int n_diag2 = D.slab ? (b0 + 3 < D.nblk ? 2 : 0) + max(0, D.nblk - b0 - 4) : n2 * (n2 + 1) / 2;
-    if (e < n_diag2) {
-        if (D.slab) return e < 2 ? MainItem{4, p, b0 + 3, b0 + 2 + e} : MainItem{4, p, b0 + 2 + e, b0 + 2};
-        int mm = 0, first = 0;
-        while (e >= first + (n2 - mm)) {
-            first += n2 - mm;
-            ++mm;
-        }
-        return MainItem{4, p, d0 + mm + (e - first), d0 + mm};
-    }
-    e -= n_diag2;
-    if (e < nsz * nrest) {
-        const int mm = e / nrest, local = e % nrest;
-        const int b = local < b0 ? local : local - b0 + d0;
-        const int cb = c0 + mm;
-        if (D.slab && b == d0) return MainItem{3, p, 0, 0};  // tile (c0 + 1, c0): done on the chain (sweep_xslab_item)
-        return MainItem{4, p, b > cb ? b : cb, b > cb ? cb : b};
-    }
-    e -= nsz * nrest;
-    const int n_wb = (D.nblk - sz) * sz;
-    if (e < n_wb) return MainItem{2, p, e, 0};
-    e -= n_wb;
-    const int n_rem = nrest > 0 ? nrest * (nrest + 1) / 2 : 0;
-    const int n_head = n_rem - min(n_rem, D.rem_tail);
-    if (e >= n_head) {
-        const int n_pan = nsz > 0 ? (D.nblk - nsz - n2) * D.ppb * nsz : 0;
-        if (e - n_head < n_pan) {
-            const int ep = e - n_head;
-            int i = ep / (D.ppb * nsz);
-            if (i >= c0) i += nsz + n2;
-            if (D.slab && i == c0 + 2) return MainItem{3, p, 0, 0};  // row block b0' + 2 of group p + 1 (b0' = c0): the chain's
-            return MainItem{0, p + 1, i, ep % (D.ppb * nsz)};
-        }
-        e -= n_pan;
-    }
-    int ii = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-    while ((long long)ii * (ii + 1) / 2 > e) --ii;
-    while ((long long)(ii + 1) * (ii + 2) / 2 <= e) ++ii;
-    int jj = e - (int)((long long)ii * (ii + 1) / 2);
-    if (ii >= b0) ii += sz + nsz;
-    if (jj >= b0) jj += sz + nsz;
-    if (D.slab) {
-        // (b0+2, b0+2): the chain's; (b0+3, b0+3) and column b0 + 2 below the diagonal: early slots
-        if ((jj >= d0 && ii <= d0 + 1) || jj == d0) return MainItem{3, p, 0, 0};
-    } else if (jj >= d0 && ii < d0 + n2)
-        return MainItem{3, p, 0, 0};  // inside the diagonal super-block of group p+2: done as diag2
-    return MainItem{1, p, ii, jj};
 }
 
 // One 128 x 128 pivot by the calling 256-thread workgroup (LDS of the tile paths reused: Gs and Hs are the two halves of ONE array,
@@ -2111,6 +2004,8 @@ SWEEP_OUTLINE void sweep_chain_worker(int f_in)
         const int item = sw_item;
         __syncthreads();
         if (item >= D.total_m || *abort_lds()) break;
+        // (item number -> what to do: the walk of chain_decode, gdca_sweep_schedule.h, which the CPU test enumerates -- written out here,
+        // see there)
         while (item >= D.mitem0[q + 1]) ++q;
         int e = item - D.mitem0[q];
         if (D.dbg && threadIdx.x == 0) D.dbg[2 * item] = wall_clock64();
@@ -2395,9 +2290,9 @@ __global__ __launch_bounds__(256, 2) void k_sweep(const SweepDesc Darg)
 // Items of one family are still handed out in that family's list order, so the no-deadlock argument of k_sweep holds family by
 // family.  With the chains of K families side by side a member's chain no longer sets the pace -- it has the other members' tile
 // items to hide behind -- so a member of a merged launch takes the multi-block groups (tile items of depth K = 256 .. 512: a half
-// to a quarter of the C-tile traffic per flop) that pay only from 49 .. 58 blocks on when it runs alone (plan_sweep).  MULTI:
+// to a quarter of the C-tile traffic per flop) that pay only from 49 .. 58 blocks on when it runs alone (sweep_schedule).  MULTI:
 // some member has multi-block groups.
-#define SWEEP_MAX_MERGE 8
+#define SWEEP_MAX_MERGE GDCA_SWEEP_MAX_MERGE
 struct SweepBatch {
     SweepDesc fam[SWEEP_MAX_MERGE];
     int K;
@@ -2504,10 +2399,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep_merged(const SweepBatch Barg)
 
 size_t gdca_inverse_flag_bytes(int n_pad)
 {
-    const size_t nblk = (size_t)(n_pad / T);
-    // gen, rb (ng <= nblk), mc, done, sl | next, next_m, mxcc, arrived, mcu[32] | the abort word on a 128-byte line of its own (every wait
-    // of the kernel reads it; the line of the item counters is busy with atomics)
-    return (nblk * nblk + nblk * nblk + 5 * nblk + 96) * sizeof(unsigned);
+    return flag_words_max(n_pad / T) * sizeof(unsigned);
 }
 
 int gdca_inverse_max_merge(void)
@@ -2515,9 +2407,6 @@ int gdca_inverse_max_merge(void)
     return SWEEP_MAX_MERGE;
 }
 
-// Host side: the schedule of one inverse -- group sizes, the item table (written to the job's pinned staging buffer and sent to
-// the device on s0), the flags (zeroed on s0), the descriptor.  `merged`: the inverse is a member of a merged launch of
-// `members` families (single-block groups, chain CUs from the merge rule, no trace).
 // what a launch has to put in place for one inverse before its workgroups start: the flags zeroed, the item table on the device
 struct SweepPrepOne {
     unsigned *flags;
@@ -2547,114 +2436,37 @@ struct SweepPlan {
     long long mpos;
     double chunks;     // 128 x 128 x 16 MFMA chunk products issued (tile, panel and super-block items)
     bool slab;
-    std::vector<int> mit;
+    std::vector<int> table;  // the item table (item0 | mitem0 | gs) as the schedule wrote it
+    size_t mit_at;           // where mitem0 starts in there (the trace)
 };
 
+// Host side: the schedule of one inverse (sweep_schedule, gdca_sweep_schedule.h: group sizes, the item table, the rules' figures) bound
+// to the job's memory -- the table in the job's pinned staging buffer (and sent to the device on s0), the flags (zeroed on s0) at the
+// offsets of flag_layout, the descriptor.  `merged`: the inverse is a member of a merged launch of `members` families.
 static SweepPlan plan_sweep(hipStream_t s0, const gdca_inverse_job &job, bool merged, int members)
 {
     const gdca_tuning &tu = *job.tune;
     const gdca_inverse_ws &ws = job.ws;
-    const int n_pad = job.n_pad, n_real = job.n_real;
-    const int nblk = n_pad / T;
-    // pivot blocks per group: more blocks per pass raise the update's arithmetic intensity (K = 128 g) and amortise the per-item
-    // costs; the serial chain of a group grows with g (and has the group's whole update to hide behind).  Small matrices
-    // are bound by the chain itself, which is shortest with single blocks (no scratch copy, no tile jobs).  Measured on
-    // MI355X with the round-3 tile loop and chain (tools/sweep_groups.py, profiles/r03_sweep_groups*.log: inverse time over
-    // N x g x chain CUs): g = 1 is fastest up to 48 blocks (beyond, its K = 128 updates are bound by the traffic of the C tiles, not
-    // by the chain), 2 to 54, 3 to 57, 4 from 58 on (with the super-block inverse as row-slab jobs; as half-tile jobs its chain hid only
-    // from 71 blocks).
-    // A member of a merged launch: its chain hides behind the other members' tile items, so what counts is the traffic of the C
-    // tiles -- groups of four from 24 blocks, of two from 12 (option GDCA_MERGE_GROUP forces a size).
-    const int g_merged = tu.merge_group >= 1 ? std::min(tu.merge_group, 4) : (nblk >= 24 ? 4 : (nblk >= 12 ? 2 : 1));
-    // Round 5 measured the final kernel again, every block count from 44 to 77, the four sizes alternating inside one process, twice in
-    // opposite order (tools/option_probe.py, profiles/r05_group_rule.log; the two passes agree to 1 %): 1 up to 46 blocks, 2 up to 53, 3 up to
-    // 59, 4 from 60 (rounds 3-4: 2 from 49, 3 from 55, 4 from 58; 3-4 % at 47, 48, 54, 58 and 59 blocks) ...
-    // ... and once more with one chain worker per compute unit for groups of two and three (below, profiles/r05_group_rule.log, second
-    // part): 1 up to 44 blocks, 2 up to 52, 3 up to 60, 4 from 61.
-    const int g_rule = nblk >= 61 ? 4 : (nblk >= 53 ? 3 : (nblk >= 45 ? 2 : 1));
-    int g = merged ? g_merged : (tu.group >= 1 ? std::min(tu.group, 4) : g_rule);
-    if (nblk < 2 * g) g = 1;
-    // group sizes.  Before the first update there is nothing to hide the first chain behind: with full groups from the start
-    // every workgroup waits ~400 us (2 % of the inverse at n = 10 000) for the first super-block inverse.  So the sweep opens
-    // with a ramp 1, 2, .. g-1 (a single block is one in-place pivot item, ~70 us; each following chain is as long as the
-    // update before it), and the remainder of nblk / g joins the ramp instead of ending the sweep as a lone short group
-    // (measured at n = 10 000: 17.9-18.1 ms against 18.2-18.3 with the remainder last and 18.2 without the ramp).
-    // GDCA_RAMP=0: uniform groups, the remainder last.
-    std::vector<int> sizes;
-    {
-        const int ramp_sum = g * (g - 1) / 2;
-        if (tu.ramp && g > 1 && nblk >= ramp_sum + 2 * g) {
-            for (int k = 1; k < g; ++k) sizes.push_back(k);
-            const int rest = nblk - ramp_sum, rem = rest % g;
-            if (rem) sizes.insert(std::upper_bound(sizes.begin(), sizes.end(), rem), rem);
-            for (int k = 0; k < rest / g; ++k) sizes.push_back(g);
-        } else {
-            for (int b = 0; b < nblk; b += g) sizes.push_back(std::min(g, nblk - b));
-        }
-    }
-    const int ng = (int)sizes.size();
-    // item table on the host, then to the device (pinned staging buffer of the workspace)
-    int *it = ws.item0_host;
-    auto size = [&](int p) { return sizes[(size_t)p]; };
-    auto m_cnt = [&](int sz) { return sz == 1 ? 1 : sz * (sz + 1) + sz * (1 + SLAB_ITEMS * (sz - 1)); };
-    int *mit = it + (ng + 1);
-    int *gs = it + 2 * (ng + 1);
-    gs[0] = 0;
-    for (int p = 0; p < ng; ++p) gs[p + 1] = gs[p] + sizes[(size_t)p];
-    long long pos = 0, mpos = 0;
-    // real rows of the last block, in 16-row MFMA blocks: the sweep treats the matrix as n rounded up to 16, not to 128 -- the
-    // tile items of the last block row and the k loop over the last pivot block skip the rest of the padding (GDCA_RAGGED=0: off)
-    const int rl = tu.ragged ? std::min(T, ((n_real - (nblk - 1) * T + 15) / 16) * 16) : T;
-    double chunks = 0.0;
-    // remainder tiles of update p listed after panel(p+1): about one round of the workgroups, so that the panels are complete
-    // when the first tile items of update p+1 are handed out and the chain has had most of update p to produce Pg(p+1).
-    // Only where the update hides the chain (groups of three and four): on a chain-bound matrix Pg(p+1) is late anyway and
-    // workgroups parked on panel items are missing from update p (measured: config E 59.5 instead of 63.4 families/s).
-    const int rem_tail = tu.rem_tail >= 0 ? tu.rem_tail : (g >= 3 ? 2 * ws.update_cus : 0);
-    // main-list panel items: one 128 x 128 item per pivot block and row where the panels are throughput (multi-block groups of
-    // three and four), two 128 x 64 halves where their latency counts
-    const int ppb = tu.panel_halves >= 0 ? (tu.panel_halves ? 2 : 1) : (g >= 3 ? 1 : 2);
-    // single-block groups: the chain between two pivots as fused row-slab items (sweep_slab_item; GDCA_SLAB=0: panel and tile items)
-    bool slab = tu.slab != 0;
-    bool single = true;
-    for (int p = 0; p < ng; ++p) single = single && size(p) == 1;
-    slab = slab && single;
-    // buffers per kind (ring_panel): eight one-panel slots between single blocks (GDCA_RING=2: two, as for multi-block groups)
-    const int ring = single && tu.ring >= 3 ? std::min(tu.ring, 8) : 2;
-    const int pro = ng > 0 ? (nblk - size(0) - (ng > 1 ? size(1) : 0)) * ppb * size(0) : 0;  // panel(0)
-    for (int p = 0; p < ng; ++p) {
-        it[p] = (int)pos;
-        mit[p] = (int)mpos;
-        const int sz = size(p), nsz = p + 1 < ng ? size(p + 1) : 0, n2 = p + 2 < ng ? size(p + 2) : 0;
-        const int nrest = nblk - sz - nsz;
-        // M(p), then the next group's panel rows and its diagonal tiles -- or, between single blocks, the fused slab items
-        mpos += m_cnt(sz) + (slab ? (nsz ? SLAB_ITEMS : 0) + (n2 ? 2 * SLAB_ITEMS : 0) : nsz * 2 * sz + nsz * (nsz + 1) / 2);
-        pos += slab ? (gs[p] + 3 < nblk ? 2 : 0) + std::max(0, nblk - gs[p] - 4) : n2 * (n2 + 1) / 2;  // diag2 (between single blocks: (b0+3, b0+3) and column b0 + 2)
-        pos += (long long)nsz * nrest;                             // rest
-        pos += (long long)(nblk - sz) * sz;                        // wb
-        pos += nrest > 0 ? (long long)nrest * (nrest + 1) / 2 : 0; // rem (its diag2 tiles are empty items)
-        pos += nsz > 0 ? (long long)(nblk - nsz - n2) * ppb * nsz : 0;  // panel(p+1), the rows outside groups p+1 and p+2
-        const long long pn = nblk - sz;
-        const bool last = gs[p + 1] == nblk;
-        const int kch = (rl < T && last && sz > 1) ? 8 * (sz - 1) + 2 * ((rl + 31) / 32) : 8 * sz;  // = g_chunks()
-        const double nrag = (rl < T && !last) ? (double)pn : 0.0;  // tile items of the ragged block row: rl / 128 of the MFMAs
-        chunks += ((double)(pn * (pn + 1) / 2) - nrag + nrag * rl / T) * kch;  // tile items
-        chunks += (double)pn * sz * 8 * sz;                                    // panel items (K = 128 sz, 128 sz columns)
-        if (sz > 1) chunks += (double)sz * (sz - 1) * sz * 8;  // super-block inverse: per block and other row, sz products of 128 x 128 x 128
-    }
-    it[ng] = (int)pos;
-    mit[ng] = (int)mpos;
+    // 1. the schedule (gdca_sweep_schedule.h).  Its item table is built in ordinary memory -- the schedule reads its own group sizes back
+    // many times -- and goes to the job's pinned staging buffer in one copy
+    const Tuning st{tu.group, tu.ramp, tu.ragged, tu.rem_tail, tu.panel_halves, tu.slab, tu.ring, tu.mcus, tu.mcu_solo, tu.merge_group, tu.merge_mcus,
+                    tu.sweep_timeout_ms};
     SweepPlan P{};
-    P.prep = SweepPrepOne{ws.flags, (unsigned)(ws.flags_bytes / sizeof(unsigned)), ws.item0_host_dev, ws.item0_dev, 3 * (ng + 1)};
+    P.table.resize((size_t)table_ints_max(job.n_pad / T));
+    const Schedule S = sweep_schedule(job.n_pad / T, job.n_real, ws.update_cus, st, merged, members, P.table.data());
+    const int nblk = S.nblk, ng = S.ng;
+    std::copy(P.table.begin(), P.table.begin() + S.table_ints, ws.item0_host);
+    // 2. the pointers: the table on the device, the workspace, the flags, the scalars
+    P.prep = SweepPrepOne{ws.flags, (unsigned)(ws.flags_bytes / sizeof(unsigned)), ws.item0_host_dev, ws.item0_dev, S.table_ints};
     if (!ws.item0_host_dev) {  // (no device address for the pinned table: the runtime's copy, and the prep kernel only clears)
-        (void)hipMemcpyAsync(ws.item0_dev, it, (size_t)3 * (ng + 1) * sizeof(int), hipMemcpyHostToDevice, s0);
+        (void)hipMemcpyAsync(ws.item0_dev, ws.item0_host, (size_t)S.table_ints * sizeof(int), hipMemcpyHostToDevice, s0);
         P.prep.n_items = 0;
     }
     SweepDesc &D = P.D;
     D.A = job.A;
-    D.ld = (size_t)n_pad;
+    D.ld = (size_t)job.n_pad;
     D.nblk = nblk;
-    D.g = g;
+    D.g = S.g;
     D.ng = ng;
     D.G0 = ws.G[0];
     D.H0 = ws.H[0];
@@ -2664,75 +2476,46 @@ static SweepPlan plan_sweep(hipStream_t s0, const gdca_inverse_job &job, bool me
     D.Pg0 = ws.Pg[0];
     D.Pg1 = ws.Pg[1];
     D.Pw = ws.P;
-    unsigned *f = ws.flags;
-    D.gen = f;
-    f += (size_t)nblk * nblk;
-    D.rb = f;
-    f += (size_t)ng * nblk;
-    D.mc = f;
-    f += ng;
-    D.done = f;
-    f += ng;
-    D.sl = f;
-    f += 3 * ng;
-    D.next = f;
-    D.next_m = f + 1;
-    D.mxcc = f + 18;
-    D.arrived = f + 19;
-    D.mcu = f + 20;  // 32 slots
-    D.abort = f + 64;
-    // bound of one dependency wait (GDCA_SWEEP_TIMEOUT_MS; a healthy wait is microseconds).  By default it grows with the work the
-    // launch holds: the early workgroups of a launch that starts behind another one (two contexts in flight on one GPU, another
-    // tenant) wait for most of that launch's run time, and a slow but correct run must not be turned into GDCA_EHIP -- 4 s or
-    // eight times the modelled duration of everything this launch carries (n = 48 000: 1.8 s measured), whichever is longer
-    const double model_ms = 8.0 * members * ((double)n_pad * n_pad * n_pad / 50e12 * 1e3);
-    const long timeout_ms = tu.sweep_timeout_ms > 0 ? tu.sweep_timeout_ms : std::max(4000L, (long)model_ms);
-    D.timeout_ticks = (unsigned long long)std::max(1L, timeout_ms) * 100000ull;
-    // ... and once a polling wave has been off the hardware (spin_until): 50 ms or that modelled duration -- a launch that merely shares
-    // the device goes on within that; one that did not get all its workgroups back never does
-    D.hole_timeout_ticks = std::min(D.timeout_ticks, (unsigned long long)std::max(50L, (long)model_ms) * 100000ull);
+    const FlagLayout L = flag_layout(nblk, ng);
+    D.gen = ws.flags + L.gen;
+    D.rb = ws.flags + L.rb;
+    D.mc = ws.flags + L.mc;
+    D.done = ws.flags + L.done;
+    D.sl = ws.flags + L.sl;
+    D.next = ws.flags + L.next;
+    D.next_m = ws.flags + L.next_m;
+    D.mxcc = ws.flags + L.mxcc;
+    D.arrived = ws.flags + L.arrived;
+    D.mcu = ws.flags + L.mcu;
+    D.abort = ws.flags + L.abort;
+    D.timeout_ticks = S.timeout_ticks;
+    D.hole_timeout_ticks = S.hole_timeout_ticks;
     if (job.doomed) D.timeout_ticks = D.hole_timeout_ticks = 1ull;  // (tests: the first wait that has to poll twice gives up)
     D.debug = tu.sweep_debug;
-    D.item0 = ws.item0_dev;
-    D.mitem0 = ws.item0_dev + (ng + 1);
-    D.gs = ws.item0_dev + 2 * (ng + 1);
-    D.total = pro + (int)pos;
-    D.total_m = (int)mpos;
-    D.pro = pro;
-    D.rem_tail = rem_tail;
-    D.ppb = ppb;
-    D.slab = slab ? SLAB_ITEMS : 0;
-    D.ring = ring;
-    // compute units for the M list (same measurement): a chain-bound inverse wants every parallel item of the chain served at
-    // once -- the row-slab jobs of a level of a four-block group are 24 -- and once the update hides the chain the workers go
-    // back to the tiles: for multi-block groups 16 CUs up to 63 blocks, 12 up to 68, 10 up to 74, 6 up to 90 (n = 10 000: 16.5 ms
-    // with 6, 16.85 with 12, 20.8 with 4), 4 up to 120, 2 beyond (n = 20 000: 123.1 ms with 2, 123.75 with 4); between single blocks (a pivot and three times eight slab items per step) 12
-    // CUs below 28 blocks, 8 above
-    const int mcu_rule = g == 1 ? (nblk < 28 ? 12 : 8) : (nblk <= 63 ? 16 : (nblk <= 68 ? 12 : (nblk <= 74 ? 10 : (nblk <= 90 ? 6 : (nblk <= 120 ? 4 : 2)))));
-    // a member of a merged launch: its own rule unless that would hand more than an eighth of the chip to the chains
-    const int mcu_merged = tu.merge_mcus >= 1 ? tu.merge_mcus : std::min(mcu_rule, std::max(2, ws.update_cus / (8 * std::max(1, members))));
-    // One chain worker per elected compute unit (its second workgroup leaves the launch at once) for groups of two and three: there a
-    // pivot shared its SIMDs with a K = 256 / 384 panel or tile item of the M list on the unit's other workgroup.  Round 5, every block
-    // count from 47 to 76 with alternating settings (profiles/r05_mcu_solo.log): 12 such units for groups of two (47-53 blocks: 2-12 %
-    // faster than 16 units with two workers each), 16 for groups of three (54-56 blocks 3-8 %, 58-59 1 %); groups of four and the
-    // fused slab items between single blocks gain nothing (and lose workers), a merged launch's members keep both.
-    // (a merged launch's members: tried, no effect -- config B eight to a launch 0.444 against 0.448 ms per family)
-    const bool solo = !merged && (tu.mcu_solo >= 0 ? tu.mcu_solo != 0 : (g == 2 || g == 3));
-    D.mcu_solo = solo ? 1 : 0;
-    const int mcu_solo_rule = g == 2 ? 12 : 16;
-    D.n_mcu = merged ? std::min(mcu_merged, 16) : (tu.mcus >= 1 ? std::min(tu.mcus, solo ? 32 : 16) : (solo && tu.mcu_solo < 0 ? mcu_solo_rule : mcu_rule));
-    D.n_real = n_real;
-    D.rl = rl;
+    D.item0 = ws.item0_dev + (S.item0 - P.table.data());
+    D.mitem0 = ws.item0_dev + (S.mitem0 - P.table.data());
+    D.gs = ws.item0_dev + (S.gs - P.table.data());
+    D.total = S.total;
+    D.total_m = S.total_m;
+    D.pro = S.pro;
+    D.rem_tail = S.rem_tail;
+    D.ppb = S.ppb;
+    D.slab = S.slab;
+    D.ring = S.ring;
+    D.mcu_solo = S.mcu_solo;
+    D.n_mcu = S.n_mcu;
+    D.n_real = S.n_real;
+    D.rl = S.rl;
     D.sc = job.sc;
     D.piv = ws.piv;
     D.dbg = nullptr;
     D.dbg_main = nullptr;
     D.dbg_items = nullptr;
-    P.g = g;
-    P.mpos = mpos;
-    P.chunks = chunks;
-    P.slab = slab;
-    P.mit.assign(mit, mit + ng + 1);
+    P.g = S.g;
+    P.mpos = S.total_m;
+    P.chunks = S.chunks;
+    P.slab = S.slab != 0;
+    P.mit_at = (size_t)(S.mitem0 - P.table.data());
     return P;
 }
 
@@ -2809,7 +2592,7 @@ static void write_sweep_trace(const char *trace_path, const SweepPlan &P, unsign
     const int nblk = P.D.nblk, g = P.g, ng = P.D.ng;
     const long long mpos = P.mpos;
     const bool slab = P.slab;
-    const int *mit = P.mit.data();
+    const int *mit = P.table.data() + P.mit_at;
     {
         std::vector<unsigned long long> h((size_t)2 * mpos), hm(8 + 1024 + 19 * (size_t)ng);
         (void)hipMemcpy(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
