@@ -13,7 +13,9 @@ from .gdca import gDCA_double_mutant_scan, gDCA_double_mutants  # noqa: F401
 from .dcautils import greedy_walk  # noqa: F401
 from .gdca import gDCA_greedy_walk  # noqa: F401
 from .dcautils import sample  # noqa: F401
+from .dcautils import sample_tempered  # noqa: F401
 from .gdca import gDCA_sample  # noqa: F401
+from .gdca import gDCA_sample_tempered  # noqa: F401
 from .dcautils import bm_learn, potts_from_gaussian, potts_independent  # noqa: F401
 from .gdca import gDCA_bm  # noqa: F401
 from .dcautils import (add_pseudocount, assign_blocks, compute_C, compute_DI_gauss, compute_FN, compute_ranking,  # noqa: F401

@@ -17,6 +17,8 @@ PAIR_COUPLING, PAIR_ENERGY = 0, 1  # `what` of gdca_pair_energies: the cross-ter
 MUT_DELTA, MUT_POTENTIAL = 0, 1  # `what` of gdca_mutation_scan: the energy change of every substitution, or the site potentials themselves
 WALK_GAP_TARGET, WALK_FILL_GAPS = 1, 2  # `flags` of gdca_greedy_walk: the gap is a target ("delete"); a gap site may receive a residue
 WALK_MAX_STEPS = 65535  # GDCA_WALK_MAX_STEPS
+_NO_SWAPS = np.zeros(1, dtype=np.int32)  # what `swaps` points at where a chain has one replica (never written)
+TEMPER_MAX = 64  # GDCA_TEMPER_MAX: the most replicas a chain of gdca_sample_tempered may have
 SAMPLE_GAPS = 1  # `flags` of gdca_sample: the gap is a symbol like any other (default: residues change into residues, gaps stay gaps)
 ABI_VERSION = 6  # GDCA_VERSION_MAJOR * 1000 + GDCA_VERSION_MINOR of the header this binding mirrors
 
@@ -276,6 +278,22 @@ SYMBOLS = {
     "gdca_run_sample": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32, C.c_void_p,
                                   C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_sample_tempered_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "gdca_sample_tempered": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "gdca_run_sample_tempered_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_run_sample_tempered": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params), C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "gdca_potts_from_gaussian_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_potts_from_gaussian": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_bm_update_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
@@ -904,6 +922,80 @@ class Context:
         st = self._run_readout(self.lib.gdca_run_sample, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), opt(mask), int(flags),
                                float(beta), int(seed), int(stream0), int(burn), int(stride), int(n_samples), *[opt(a) for a in out])
         return self.sample_result(out), st
+
+    # ---- replica-exchange chains: the Metropolis chains tempered over a ladder (gdca_sample_tempered*, gdca_run_sample_tempered*) ----
+    @staticmethod
+    def _betas(betas):
+        """the ladder as the library takes it: a HOST array of R f64 (kept alive by the caller for the call)"""
+        return np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+
+    def sample_tempered_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, Xr_ptr: int | None, slot0_ptr: int | None, K: int, betas,
+                            mask_ptr: int | None, flags: int, seed: int, stream0: int, swap_every: int, burn: int, stride: int, n_samples: int,
+                            Xs_ptr: int | None, accepted_ptr: int | None, swaps_ptr: int | None, Xr_out_ptr: int | None,
+                            slot_out_ptr: int | None, E_s_ptr: int | None = None, thr_ptr: int | None = None, moves_ptr: int | None = None,
+                            swap_thr_ptr: int | None = None, slot_path_ptr: int | None = None) -> None:
+        """gdca_sample_tempered_dev: mJ (n x n), Pi (n), Xr (N x R x K int8), slot0 (R x K int32 or None), mask (N int8 or None) and
+        the outputs -- Xs (N x n_samples x K int8), accepted (R x K int32), swaps ((R - 1) x K int32), Xr_out (N x R x K int8), slot_out
+        (R x K int32), E_s (n_samples x K f64), thr / moves (n_steps x R x K), swap_thr (n_rounds x (R - 1) x K f64), slot_path
+        (n_rounds x R x K int32); the last five may be None -- are device pointers; betas (R values, betas[0] the target) is a host
+        sequence."""
+        b = self._betas(betas)
+        self.check(self.lib.gdca_sample_tempered_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), self._opt(Xr_ptr),
+                                                     self._opt(slot0_ptr), int(K), int(b.size), _p(b), self._opt(mask_ptr), int(flags), int(seed),
+                                                     int(stream0), int(swap_every), int(burn), int(stride), int(n_samples), self._opt(Xs_ptr),
+                                                     self._opt(E_s_ptr), self._opt(accepted_ptr), self._opt(swaps_ptr), self._opt(Xr_out_ptr),
+                                                     self._opt(slot_out_ptr), self._opt(thr_ptr), self._opt(moves_ptr), self._opt(swap_thr_ptr),
+                                                     self._opt(slot_path_ptr)))
+
+    def run_sample_tempered_dev(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None, K: int, betas,
+                                mask_ptr: int | None, flags: int, seed: int, stream0: int, swap_every: int, burn: int, stride: int,
+                                n_samples: int, Xs_ptr: int | None, accepted_ptr: int | None, swaps_ptr: int | None, Xr_out_ptr: int | None,
+                                slot_out_ptr: int | None, E_s_ptr: int | None = None, thr_ptr: int | None = None,
+                                moves_ptr: int | None = None, swap_thr_ptr: int | None = None, slot_path_ptr: int | None = None):
+        """gdca_run_sample_tempered_dev: the model is fitted on Z (N x M int8 in HBM) as run() fits it, then the tempered chains from X
+        (N x K; None: one from each of Z's own M sequences), every replica of a chain at its chain's sequence; the outputs as
+        sample_tempered_dev's.  Returns the stats dict."""
+        b = self._betas(betas)
+        return self._run_readout(self.lib.gdca_run_sample_tempered_dev, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K),
+                                 int(b.size), _p(b), self._opt(mask_ptr), int(flags), int(seed), int(stream0), int(swap_every), int(burn),
+                                 int(stride), int(n_samples), self._opt(Xs_ptr), self._opt(E_s_ptr), self._opt(accepted_ptr),
+                                 self._opt(swaps_ptr), self._opt(Xr_out_ptr), self._opt(slot_out_ptr), self._opt(thr_ptr), self._opt(moves_ptr),
+                                 self._opt(swap_thr_ptr), self._opt(slot_path_ptr))
+
+    @staticmethod
+    def tempered_outputs(N: int, K: int, R: int, swap_every: int, burn: int, stride: int, n_samples: int, trace: bool):
+        """the host arrays K tempered chains of R replicas fill, in the library's memory order: (Xs (N, n_samples, K) Fortran int8, E_s
+        (K, n_samples), accepted (K, R) int32, swaps (K, R - 1) int32, Xr_out (N, R, K) Fortran int8, slot_out (K, R) int32, then -- or
+        None each -- thr (K, R, n_steps), moves (K, R, n_steps) int32, swap_thr (K, R - 1, n_rounds), slot_path (K, R, n_rounds) int32)"""
+        K, R, S = max(int(K), 0), max(int(R), 1), max(int(n_samples), 0)
+        T = max(int(burn) + S * int(stride), 0)
+        E = T // max(int(swap_every), 1)
+        return (np.empty((int(N), S, K), dtype=np.int8, order="F"), np.empty((K, S), dtype=np.float64), np.empty((K, R), dtype=np.int32),
+                np.empty((K, R - 1), dtype=np.int32), np.empty((int(N), R, K), dtype=np.int8, order="F"), np.empty((K, R), dtype=np.int32),
+                np.empty((K, R, T), dtype=np.float64) if trace else None, np.empty((K, R, T), dtype=np.int32) if trace else None,
+                np.empty((K, R - 1, E), dtype=np.float64) if trace else None, np.empty((K, R, E), dtype=np.int32) if trace else None)
+
+    @staticmethod
+    def _swaps_arg(swaps):
+        """swaps may not be NULL even where it is empty (R == 1)"""
+        return _p(swaps) if swaps.size else _p(_NO_SWAPS)
+
+    def run_sample_tempered_ptr(self, Z_ptr: int, N: int, M: int, q: int, pseudocount: float, theta: float, X_ptr: int | None = None, K: int = 0,
+                                betas=(1.0,), mask: np.ndarray | None = None, flags: int = 0, seed: int = 0, stream0: int = 0,
+                                swap_every: int = 1, burn: int = 0, stride: int = 1, n_samples: int = 1, trace: bool = False):
+        """gdca_run_sample_tempered on HOST matrices given by address: the model is fitted on Z (N x M int8, column-major) as run() fits
+        it, then K tempered chains start from the sequences X (N x K, same layout; None: Z's own M sequences).  Returns (the arrays of
+        tempered_outputs, without the four traces unless trace), stats)."""
+        Ke = int(K) if X_ptr is not None else int(M)
+        b = self._betas(betas)
+        out = self.tempered_outputs(N, Ke, b.size, swap_every, burn, stride, n_samples, trace)
+        opt = lambda a: None if a is None or a.size == 0 else _p(a)  # noqa: E731
+        ptrs = [opt(a) for a in out]
+        ptrs[3] = self._swaps_arg(out[3])
+        st = self._run_readout(self.lib.gdca_run_sample_tempered, Z_ptr, N, M, q, pseudocount, theta, self._opt(X_ptr), int(K), int(b.size),
+                               _p(b), None if mask is None else _p(mask), int(flags), int(seed), int(stream0), int(swap_every), int(burn),
+                               int(stride), int(n_samples), *ptrs)
+        return tuple(a for a in out if a is not None), st
 
     # ---- Boltzmann-machine refinement of the Potts model (W, zeros) the chains draw from (gdca_potts_from_gaussian*, gdca_bm_*) ----
     def potts_from_gaussian_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, W_ptr: int) -> None:

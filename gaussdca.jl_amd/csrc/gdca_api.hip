@@ -23,7 +23,7 @@ struct gdca_buf {
 // a call asks for them.  Only host_stage can name them; gdca_ctx_destroy frees them through release().
 class stage_pool {
     friend class host_stage;
-    static const int MAX_ARRAYS = 10;
+    static const int MAX_ARRAYS = 16;
     gdca_buf buf[MAX_ARRAYS];
 
 public:
@@ -84,8 +84,16 @@ struct sample_request {
     double *V;
 };
 
+// What the replica-exchange chains take beside their start sequences and return (include/gdca.h, Replica-exchange chains): the
+// kernels' plan, with the ladder by value (a collect that runs the stage again needs no array of the caller's).  fused: the start
+// sequences are N x K and every replica of a chain starts at its chain's; else they are N x R x K
+struct temper_request {
+    gdca_temper_plan plan;
+    bool fused;
+};
+
 struct score_target {
-    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK, DOUBLE_SCAN, DOUBLE_LIST, WALK, SAMPLE } kind;
+    enum { CONTACT, ENERGY, PAIR, PARTNER, MUTATION, LOGLIK, DOUBLE_SCAN, DOUBLE_LIST, WALK, SAMPLE, TEMPER } kind;
     double *out;                       // S (N x N), E (K), E (KA x KB), E (packed blocks), D (q x N x K), Emin (N x N x K, may be null) or ddE (L)
     int score, apc;                    // contact
     const int8_t *X;                   // energy (k_energy.hip) and mutation scan (k_mutation.hip, with `what`): N x K
@@ -104,6 +112,7 @@ struct score_target {
     int L;
     walk_request walk;                 // greedy walk (k_walk.hip) of the sequences X: the rule's parameters and the outputs
     sample_request sample;             // Metropolis chains (k_sample.hip) from the sequences X: the rule's parameters and the outputs
+    temper_request temper;             // replica-exchange chains (k_temper.hip) from the sequences X
     // pair / partner of a log-odds run (run_logodds): the pair stage waits for the collect, which knows the joint log det (logodds_epilogue);
     // lo.EmA / lo.EmB: the marginal fits' energies, ldA / ldB their log dets, lo.I what the collect makes of the three
     bool logodds;
@@ -220,6 +229,15 @@ static score_target sample_target(const int8_t *Z, int M, const int8_t *X, int K
     return t;
 }
 
+// (X == NULL: one chain from each of the alignment's own M sequences)
+static score_target temper_target(const int8_t *Z, int M, const int8_t *X, int K, const temper_request &r)
+{
+    score_target t = energy_target(Z, M, X, K, nullptr);
+    t.kind = score_target::TEMPER;
+    t.temper = r;
+    return t;
+}
+
 // The enqueued, not yet collected run (gdca_run_dev_async / gdca_run_collect): all a collect needs to know, grouped by who writes it.
 // The operator-level inverse (gdca_spd_inverse_dev, gdca_spd_inverse_batch_dev) borrows n, n_pad, timed (false: begin()) and the
 // progress record `at` -- attempt and refined --, so that it can go through run_inverses and inverse_ladder.
@@ -295,6 +313,7 @@ struct gdca_ctx {
     gdca_buf SMst;            // Metropolis chains (k_sample.hip): what a chain keeps between two launches, gdca_sample_state_bytes
     // Boltzmann-machine refinement (k_bm.hip): the loop's workspace (bm_plan: the model's tallies, the zero Pi, the unit weights, the
     // counts, the samples), and the read-out's column partials
+    gdca_buf TMst, TMx;       // replica-exchange chains (k_temper.hip): gdca_temper_state_bytes, and the fused form's N x R x K starts
     gdca_buf BMws, BMred;
     int ncu;                  // compute units of the device
     double *piv;              // the pivots of the context's last inverse, n_pad doubles inside Sg (inverse_job)
@@ -750,7 +769,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
                         &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
                         &ctx->LOa, &ctx->LOb, &ctx->PBN,
-                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst, &ctx->BMws, &ctx->BMred};
+                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst, &ctx->TMst, &ctx->TMx, &ctx->BMws, &ctx->BMred};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     ctx->staging.release();
@@ -1311,6 +1330,47 @@ static gdca_status sample_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
     return check_launch(ctx, "Metropolis chains");
 }
 
+// The replica-exchange chains (k_temper.hip) of K chains of R replicas under the model m, from X_dev: N x R x K, or -- r.fused -- N x K
+// replicated into ctx->TMx.  The start tables (the mutation stage, into ctx->DMd: q N K R doubles) and the start energies (the energy
+// stage) of the K R replicas as of so many sequences, the maps, then launch by launch: the proposals up to the next round or
+// SAMPLE_CHUNK boundary, the round.  The only coupling between replicas is the order of the launches on the stream.
+static gdca_status temper_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, const temper_request &r)
+{
+    bool in_lds = false;
+    if (!walk_placement(ctx, m.N, m.q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    const gdca_temper_plan &plan = r.plan;
+    const int R = plan.R, G = K * R;
+    hipStream_t s = ctx->stream;
+    const int8_t *Xr = X_dev;
+    if (r.fused) {
+        CHK(ensure(ctx, ctx->TMx, (size_t)m.N * (size_t)G));
+        gdca_launch_temper_replicate(s, X_dev, m.N, K, R, (int8_t *)ctx->TMx.p);
+        Xr = (const int8_t *)ctx->TMx.p;
+    }
+    CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)G * sizeof(double)));
+    CHK(ensure(ctx, ctx->TMst, gdca_temper_state_bytes(m.N, G)));
+    double *V = (double *)ctx->DMd.p;
+    void *state = ctx->TMst.p;
+    CHK(energy_stage(ctx, m, Xr, G, gdca_temper_E0(state, G)));
+    CHK(mutation_stage(ctx, m, Xr, G, GDCA_MUT_POTENTIAL, V));  // (ctx->Xg: the G starts packed, as the first launch reads them)
+    gdca_launch_temper_init(s, plan, K, state, (gdca_dev_scalars *)ctx->sc.p);
+    const int n_steps = plan.burn + plan.n_samples * plan.stride, every = plan.swap_every;
+    const int chunk = ctx->tune.sample_chunk > 0 ? ctx->tune.sample_chunk : GDCA_SAMPLE_CHUNK_RULE;
+    for (int t0 = 0; t0 < n_steps;) {
+        const int round_end = (t0 / every + 1) * every;  // (every divides n_steps)
+        const int t1 = std::min(round_end, n_steps - t0 > chunk ? t0 + chunk : n_steps);
+        HIPCHK(gdca_launch_temper_chain(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K, plan, t0, t1, V, in_lds, state));
+        if (t1 == round_end) {
+            const int past = t1 - plan.burn;  // a sample point: t1 = burn + (j + 1) stride
+            const int js = past > 0 && past % plan.stride == 0 ? past / plan.stride - 1 : -1;
+            gdca_launch_temper_round(s, m.N, K, plan, t1 / every - 1, js, state);
+        }
+        t0 = t1;
+    }
+    gdca_launch_temper_finish(s, m.N, K, plan, state);
+    return check_launch(ctx, "replica-exchange chains");
+}
+
 // -mJ in ctx->A (ld = n_pad) -> what `t` asks for
 static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const score_target &t)
 {
@@ -1331,6 +1391,7 @@ static gdca_status score_stage(gdca_ctx *ctx, int N, int sdim, int n_pad, const 
     case score_target::DOUBLE_LIST: return double_stage(ctx, m, t.X, t.K, nullptr, nullptr, nullptr, t.muts, t.L, t.out);
     case score_target::WALK: return walk_stage(ctx, m, t.X, t.K, t.walk);
     case score_target::SAMPLE: return sample_stage(ctx, m, t.X, t.K, t.sample);
+    case score_target::TEMPER: return temper_stage(ctx, m, t.X, t.K, t.temper);
     case score_target::CONTACT: break;
     }
     double *S_dev = t.out;
@@ -3680,6 +3741,90 @@ gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, i
     return run_target(ctx, Z_dev, N, M, q, p, sample_target(Z_dev, M, X_dev, K, r), st);
 }
 
+// the argument checks the four replica-exchange entry points share (nothing has run when one fails); K chains as they will be used
+static gdca_status validate_temper(gdca_ctx *ctx, int N, int q, long long K, int R, const double *betas, int flags, int swap_every, int burn,
+                                   int stride, int n_samples, const void *Xs, const void *accepted, const void *swaps, const void *Xr_out,
+                                   const void *slot_out)
+{
+    if (R < 1 || R > GDCA_TEMPER_MAX) return fail(ctx, GDCA_EINVAL, "invalid number of replicas");
+    if (!betas) return fail(ctx, GDCA_EINVAL, "null pointer");
+    for (int r = 0; r < R; ++r) CHK(validate_sample(ctx, N, q, K < 1 ? K : K * R, flags, betas[r], burn, stride, n_samples, Xs, accepted));
+    if (!swaps || !Xr_out || !slot_out) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (swap_every < 1 || burn % swap_every != 0 || stride % swap_every != 0)
+        return fail(ctx, GDCA_EINVAL, "invalid swap_every: it must be at least 1 and divide burn and stride");
+    return GDCA_OK;
+}
+
+static temper_request temper_request_of(int R, const double *betas, const int8_t *mask, int flags, uint64_t seed, uint64_t stream0, int swap_every,
+                                        int burn, int stride, int n_samples, const int32_t *slot0, int8_t *Xs, double *E_s, int32_t *accepted,
+                                        int32_t *swaps, int8_t *Xr_out, int32_t *slot_out, double *thr, int32_t *moves, double *swap_thr,
+                                        int32_t *slot_path, bool fused)
+{
+    temper_request r{};
+    r.plan.mask = mask, r.plan.flags = flags, r.plan.R = R, r.plan.swap_every = swap_every;
+    for (int i = 0; i < R; ++i) r.plan.betas[i] = betas[i];
+    r.plan.seed = seed, r.plan.stream0 = stream0;
+    r.plan.burn = burn, r.plan.stride = stride, r.plan.n_samples = n_samples;
+    r.plan.slot0 = slot0, r.plan.Xs = Xs, r.plan.E_s = E_s, r.plan.accepted = accepted, r.plan.swaps = swaps, r.plan.Xr_out = Xr_out;
+    r.plan.slot_out = slot_out, r.plan.thr = thr, r.plan.moves = moves, r.plan.swap_thr = swap_thr, r.plan.slot_path = slot_path;
+    r.fused = fused;
+    return r;
+}
+
+static gdca_status check_sample_tempered(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *Xr, int K, int R,
+                                         const double *betas, int flags, int swap_every, int burn, int stride, int n_samples, const void *Xs,
+                                         const void *accepted, const void *swaps, const void *Xr_out, const void *slot_out)
+{
+    CHK(validate_temper(ctx, N, q, K, R, betas, flags, swap_every, burn, stride, n_samples, Xs, accepted, swaps, Xr_out, slot_out));
+    if (!mJ || !Pi || !Xr) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+static gdca_status check_run_sample_tempered(gdca_ctx *ctx, const void *Z, int N, int M, int q, const void *p, const void *X, int K, int R,
+                                             const double *betas, int flags, int swap_every, int burn, int stride, int n_samples,
+                                             const void *Xs, const void *accepted, const void *swaps, const void *Xr_out,
+                                             const void *slot_out)
+{
+    CHK(validate(ctx, N, M, q));
+    CHK(validate_temper(ctx, N, q, X ? K : M, R, betas, flags, swap_every, burn, stride, n_samples, Xs, accepted, swaps, Xr_out, slot_out));
+    if (!Z || !p) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+gdca_status gdca_sample_tempered_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *Xr_dev,
+                                     const int32_t *slot0_dev, int32_t K, int32_t R, const double *betas, const int8_t *mask_dev,
+                                     int32_t flags, uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride,
+                                     int32_t n_samples, int8_t *Xs_dev, double *E_s_dev, int32_t *accepted_dev, int32_t *swaps_dev,
+                                     int8_t *Xr_out_dev, int32_t *slot_out_dev, double *thr_dev, int32_t *moves_dev, double *swap_thr_dev,
+                                     int32_t *slot_path_dev)
+{
+    CHK(check_sample_tempered(ctx, mJ_dev, Pi_dev, N, q, Xr_dev, K, R, betas, flags, swap_every, burn, stride, n_samples, Xs_dev, accepted_dev,
+                              swaps_dev, Xr_out_dev, slot_out_dev));
+    CHK(begin(ctx));
+    const temper_request r = temper_request_of(R, betas, mask_dev, flags, seed, stream0, swap_every, burn, stride, n_samples, slot0_dev, Xs_dev,
+                                               E_s_dev, accepted_dev, swaps_dev, Xr_out_dev, slot_out_dev, thr_dev, moves_dev, swap_thr_dev,
+                                               slot_path_dev, false);
+    CHK(temper_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), Xr_dev, K, r));
+    CHK(fetch_scalars(ctx));
+    if (ctx->sc_host->bad_symbol & GDCA_BAD_SLOTS) return fail(ctx, GDCA_EINVAL, "a column of slot0 is not a permutation of 0 .. R - 1");
+    return conclude(ctx, GDCA_ENDS_READOUT);
+}
+
+gdca_status gdca_run_sample_tempered_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                         const int8_t *X_dev, int32_t K, int32_t R, const double *betas, const int8_t *mask_dev,
+                                         int32_t flags, uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride,
+                                         int32_t n_samples, int8_t *Xs_dev, double *E_s_dev, int32_t *accepted_dev, int32_t *swaps_dev,
+                                         int8_t *Xr_out_dev, int32_t *slot_out_dev, double *thr_dev, int32_t *moves_dev,
+                                         double *swap_thr_dev, int32_t *slot_path_dev, gdca_stats *st)
+{
+    CHK(check_run_sample_tempered(ctx, Z_dev, N, M, q, p, X_dev, K, R, betas, flags, swap_every, burn, stride, n_samples, Xs_dev, accepted_dev,
+                                  swaps_dev, Xr_out_dev, slot_out_dev));
+    const temper_request r = temper_request_of(R, betas, mask_dev, flags, seed, stream0, swap_every, burn, stride, n_samples, nullptr, Xs_dev,
+                                               E_s_dev, accepted_dev, swaps_dev, Xr_out_dev, slot_out_dev, thr_dev, moves_dev, swap_thr_dev,
+                                               slot_path_dev, true);
+    return run_target(ctx, Z_dev, N, M, q, p, temper_target(Z_dev, M, X_dev, K, r), st);
+}
+
 // ---- Boltzmann-machine refinement (k_bm.hip; include/gdca.h): the warm start, the update, the read-out and the loop ----
 static gdca_status check_potts(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *W)
 {
@@ -4372,7 +4517,7 @@ gdca_status gdca_sample(gdca_ctx *ctx, const double *mJ, const double *Pi, int32
 {
     CHK(check_sample(ctx, mJ, Pi, N, q, X, K, flags, beta, burn, stride, n_samples, Xs, accepted));
     const size_t n = (size_t)N * (q - 1), k = (size_t)K, rows = ((size_t)burn + (size_t)n_samples * stride) * k;
-    host_stage sg(ctx);  // (ten arrays: the pool's limit)
+    host_stage sg(ctx);
     const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
     const double *Pi_dev = sg.in(Pi, n * sizeof(double));
     const int8_t *X_dev = sg.in(X, (size_t)N * k);
@@ -4408,6 +4553,69 @@ gdca_status gdca_run_sample(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int3
     CHK(sg.status());
     return sg.finish(gdca_run_sample_dev(ctx, Z_dev, N, M, q, p, X_dev, K, mask_dev, flags, beta, seed, stream0, burn, stride, n_samples,
                                          Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev, V_dev, st));
+}
+
+/* Replica-exchange chains with host pointers (fifteen arrays at the most: the pool has sixteen) */
+gdca_status gdca_sample_tempered(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *Xr,
+                                 const int32_t *slot0, int32_t K, int32_t R, const double *betas, const int8_t *mask, int32_t flags,
+                                 uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride, int32_t n_samples,
+                                 int8_t *Xs, double *E_s, int32_t *accepted, int32_t *swaps, int8_t *Xr_out, int32_t *slot_out, double *thr,
+                                 int32_t *moves, double *swap_thr, int32_t *slot_path)
+{
+    CHK(check_sample_tempered(ctx, mJ, Pi, N, q, Xr, K, R, betas, flags, swap_every, burn, stride, n_samples, Xs, accepted, swaps, Xr_out,
+                              slot_out));
+    const size_t n = (size_t)N * (q - 1), k = (size_t)K, g = k * (size_t)R, n_steps = (size_t)burn + (size_t)n_samples * stride;
+    const size_t pairs = k * (size_t)(R - 1), n_rounds = n_steps / (size_t)swap_every;
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *Xr_dev = sg.in(Xr, (size_t)N * g);
+    const int32_t *slot0_dev = sg.in(slot0, g * sizeof(int32_t));
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    int8_t *Xs_dev = sg.out(Xs, (size_t)N * n_samples * k);
+    double *E_s_dev = sg.out(E_s, (size_t)n_samples * k * sizeof(double));
+    int32_t *accepted_dev = sg.out(accepted, g * sizeof(int32_t));
+    int32_t *swaps_dev = pairs ? sg.out(swaps, pairs * sizeof(int32_t)) : (int32_t *)sg.room(sizeof(int32_t));  // (R == 1: nothing comes back)
+    int8_t *Xr_out_dev = sg.out(Xr_out, (size_t)N * g);
+    int32_t *slot_out_dev = sg.out(slot_out, g * sizeof(int32_t));
+    double *thr_dev = sg.out(thr, n_steps * g * sizeof(double));
+    int32_t *moves_dev = sg.out(moves, n_steps * g * sizeof(int32_t));
+    double *swap_thr_dev = pairs && n_rounds ? sg.out(swap_thr, n_rounds * pairs * sizeof(double)) : nullptr;
+    int32_t *slot_path_dev = n_rounds ? sg.out(slot_path, n_rounds * g * sizeof(int32_t)) : nullptr;
+    CHK(sg.status());
+    return sg.finish(gdca_sample_tempered_dev(ctx, mJ_dev, Pi_dev, N, q, Xr_dev, slot0_dev, K, R, betas, mask_dev, flags, seed, stream0, swap_every,
+                                              burn, stride, n_samples, Xs_dev, E_s_dev, accepted_dev, swaps_dev, Xr_out_dev, slot_out_dev, thr_dev,
+                                              moves_dev, swap_thr_dev, slot_path_dev));
+}
+
+gdca_status gdca_run_sample_tempered(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                     const int8_t *X_host, int32_t K, int32_t R, const double *betas, const int8_t *mask, int32_t flags,
+                                     uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride, int32_t n_samples,
+                                     int8_t *Xs, double *E_s, int32_t *accepted, int32_t *swaps, int8_t *Xr_out, int32_t *slot_out,
+                                     double *thr, int32_t *moves, double *swap_thr, int32_t *slot_path, gdca_stats *st)
+{
+    CHK(check_run_sample_tempered(ctx, Z_host, N, M, q, p, X_host, K, R, betas, flags, swap_every, burn, stride, n_samples, Xs, accepted, swaps,
+                                  Xr_out, slot_out));
+    const size_t k = (size_t)(X_host ? K : M), g = k * (size_t)R, n_steps = (size_t)burn + (size_t)n_samples * stride;
+    const size_t pairs = k * (size_t)(R - 1), n_rounds = n_steps / (size_t)swap_every;
+    host_stage sg(ctx);
+    const int8_t *Z_dev = sg.in(Z_host, (size_t)N * M);
+    const int8_t *X_dev = sg.in(X_host, (size_t)N * K);
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    int8_t *Xs_dev = sg.out(Xs, (size_t)N * n_samples * k);
+    double *E_s_dev = sg.out(E_s, (size_t)n_samples * k * sizeof(double));
+    int32_t *accepted_dev = sg.out(accepted, g * sizeof(int32_t));
+    int32_t *swaps_dev = pairs ? sg.out(swaps, pairs * sizeof(int32_t)) : (int32_t *)sg.room(sizeof(int32_t));
+    int8_t *Xr_out_dev = sg.out(Xr_out, (size_t)N * g);
+    int32_t *slot_out_dev = sg.out(slot_out, g * sizeof(int32_t));
+    double *thr_dev = sg.out(thr, n_steps * g * sizeof(double));
+    int32_t *moves_dev = sg.out(moves, n_steps * g * sizeof(int32_t));
+    double *swap_thr_dev = pairs && n_rounds ? sg.out(swap_thr, n_rounds * pairs * sizeof(double)) : nullptr;
+    int32_t *slot_path_dev = n_rounds ? sg.out(slot_path, n_rounds * g * sizeof(int32_t)) : nullptr;
+    CHK(sg.status());
+    return sg.finish(gdca_run_sample_tempered_dev(ctx, Z_dev, N, M, q, p, X_dev, K, R, betas, mask_dev, flags, seed, stream0, swap_every, burn,
+                                                  stride, n_samples, Xs_dev, E_s_dev, accepted_dev, swaps_dev, Xr_out_dev, slot_out_dev, thr_dev,
+                                                  moves_dev, swap_thr_dev, slot_path_dev, st));
 }
 
 /* Boltzmann-machine refinement with host pointers */

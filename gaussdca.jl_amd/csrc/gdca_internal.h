@@ -420,6 +420,40 @@ size_t gdca_sample_state_bytes(int N, int K);
 hipError_t gdca_launch_sample(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
                               const gdca_sample_plan &plan, int t0, int t1, double *V, bool table_in_lds, void *state);
 
+// ---- k_temper.hip: replica exchange over the Metropolis chains -- R replicas a chain, one workgroup a replica, swap rounds between launches --
+// (include/gdca.h, Replica-exchange chains).  G = K R replicas; Xg, V, A, ld, sign, the table's placement and the LDS layout as k_sample's.
+struct gdca_temper_plan {
+    const int8_t *mask;           // [N] or nullptr
+    int flags, R, swap_every;
+    double betas[GDCA_TEMPER_MAX];  // HOST values, by slot; they travel as kernel arguments
+    unsigned long long seed, stream0;
+    int burn, stride, n_samples;  // n_steps = burn + n_samples * stride, n_rounds = n_steps / swap_every
+    const int32_t *slot0;         // [K][R] or nullptr
+    int8_t *Xs;                   // [K][n_samples][N]
+    double *E_s;                  // [K][n_samples] or nullptr
+    int32_t *accepted;            // [K][R], by slot
+    int32_t *swaps;               // [K][R - 1]
+    int8_t *Xr_out;               // [K][R][N]
+    int32_t *slot_out;            // [K][R]
+    double *thr;                  // [K][R][n_steps] or nullptr
+    int32_t *moves;               // [K][R][n_steps] or nullptr
+    double *swap_thr;             // [K][R - 1][n_rounds] or nullptr
+    int32_t *slot_path;           // [K][R][n_rounds] or nullptr
+};
+// what the replicas keep in HBM beside their tables: the running sums, E0, the maps slot_of and holder, the symbols
+size_t gdca_temper_state_bytes(int N, int G);
+double *gdca_temper_E0(void *state, int G);  // where the stage writes the start energies (G doubles)
+void gdca_launch_temper_replicate(hipStream_t s, const int8_t *X, int N, int K, int R, int8_t *Xr);
+// the maps from slot0 (checked: GDCA_BAD_SLOTS in sc->bad_symbol, the identity in its place), accepted and swaps zeroed
+void gdca_launch_temper_init(hipStream_t s, const gdca_temper_plan &plan, int K, void *state, gdca_dev_scalars *sc);
+// The proposals t0 .. t1 - 1 of every replica, which may not cross a round (t0 / swap_every == (t1 - 1) / swap_every); errors as
+// gdca_launch_sample's
+hipError_t gdca_launch_temper_chain(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
+                                    const gdca_temper_plan &plan, int t0, int t1, double *V, bool table_in_lds, void *state);
+// round e of every chain; js >= 0: the round is the point of sample js
+void gdca_launch_temper_round(hipStream_t s, int N, int K, const gdca_temper_plan &plan, int e, int js, void *state);
+void gdca_launch_temper_finish(hipStream_t s, int N, int K, const gdca_temper_plan &plan, void *state);
+
 // ---- k_bm.hip: Boltzmann-machine refinement -- the warm start, the parameter update and the fit read-out of the Potts model (W, 0) ------
 // (include/gdca.h, Boltzmann-machine refinement).  Every matrix is n x n column-major with ld = n, n = N sdim.
 // W from the lower triangle of mJ and g = mJ Pi (gdca_launch_energy_g); W may not alias mJ

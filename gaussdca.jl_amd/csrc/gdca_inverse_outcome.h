@@ -17,6 +17,7 @@ enum : int {
     GDCA_BAD_SEQUENCE = 4,    // a byte of the scored sequences is outside 1..q (k_energy_pack)
     GDCA_BAD_INDEX = 8,       // an index of gdca_concat_pairs is outside its pool (k_ipa.hip)
     GDCA_BAD_MUTANT = 16,     // a record of gdca_double_mutants is out of range (k_epi_list)
+    GDCA_BAD_SLOTS = 32,      // a column of slot0 is no permutation of 0 .. R - 1 (k_temper_init)
 };
 // info: 0, the 1-based index of the first non-positive pivot, or -- the sweep kernel's watchdog (k_inverse.hip, spin_until) ended the
 // launch: a dependency wait ran out of time, nothing is known about the matrix --

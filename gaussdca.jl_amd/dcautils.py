@@ -718,6 +718,77 @@ def sample(mJ, Pi, X, q: int = 21, beta: float = 1.0, burn=None, stride=None, n_
     return ctx.sample_result(out)
 
 
+def _temper_args(N, betas, swap_every, burn, stride):
+    """the ladder and the round schedule of the replica-exchange chains, checked: (betas f64 (R,), swap_every); swap_every None: one sweep"""
+    try:
+        b = np.asarray(betas, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ArgumentError(f"invalid betas: {betas} (must be 1 to {_lib.TEMPER_MAX} finite numbers >= 0, the target first)") from None
+    if not 1 <= b.size <= _lib.TEMPER_MAX:
+        raise ArgumentError(f"invalid betas: {b.size} replicas (must be 1 to {_lib.TEMPER_MAX} finite numbers >= 0, the target first)")
+    if not np.all(np.isfinite(b) & (b >= 0.0)):
+        raise ArgumentError(f"invalid betas: {betas} (every beta must be a finite number >= 0)")
+    swap_every = N if swap_every is None else swap_every
+    if not isinstance(swap_every, (int, np.integer)) or swap_every < 1:
+        raise ArgumentError(f"invalid swap_every value: {swap_every} (must be an integer >= 1)")
+    if burn % int(swap_every) or stride % int(swap_every):
+        raise ArgumentError(f"invalid swap_every value: {swap_every} (must divide burn = {burn} and stride = {stride})")
+    return np.ascontiguousarray(b), int(swap_every)
+
+
+def sample_tempered(mJ, Pi, X, q: int = 21, betas=(1.0,), swap_every=None, burn=None, stride=None, n_samples: int = 1, seed: int = 0,
+                    stream0: int = 0, mask=None, gaps: bool = False, slot0=None, trace: bool = False, ctx=None):
+    """Replica-exchange (parallel tempering) Metropolis chains under the Gaussian model (mJ, Pi).  Every one of K chains runs
+    R = len(betas) replicas; a replica is a chain of ``sample`` on a stream of its own (``stream0 + k R + r``) at the inverse
+    temperature ``betas[slot]`` of the slot it holds, accepting a proposal iff ``beta * dE <= -log(u)``.  After every ``swap_every``
+    proposals (default N, one sweep; it must divide ``burn`` and ``stride``) round e lets the holders a, b of the slots p, p + 1 with
+    p % 2 == e % 2 exchange their slots iff ``(betas[p] - betas[p + 1]) * (E_b - E_a) <= -log(u)``.  ``betas[0]`` is the target
+    temperature: only the holder of slot 0 is sampled, after ``burn`` proposals (default 10 N) and every ``stride`` (default N) more.
+    X is (N, K) -- every replica of chain k starts at X[:, k] -- or (N, R, K); ``slot0`` (K, R): the slot every replica holds at the
+    start (default: replica r holds slot r).  ``mask``, ``gaps``, ``seed`` as ``sample``.
+
+    Returns ``(Xs (N, n_samples, K) int8, E_s (K, n_samples), accepted (K, R) int32, swaps (K, R - 1) int32, Xr_out (N, R, K) int8,
+    slot_out (K, R) int32)``: the samples, their energies, the accepted proposals by SLOT, the accepted swaps by pair, and the final
+    states and slots (hand them back as X and slot0 to continue); with ``trace=True`` also ``thr, moves (K, R, n_steps)``, ``swap_thr
+    (K, R - 1, n_rounds)`` and ``slot_path (K, R, n_rounds)``."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    Xa = np.asarray(X)
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    if Xa.ndim not in (2, 3):
+        raise ArgumentError("X must be an (N, K) or an (N, R, K) array of symbols")
+    N, K = Xa.shape[0], Xa.shape[-1]
+    n = N * (int(q) - 1)
+    if N < 1 or mJ.shape != (n, n) or Pi.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: X has N = {N} sites, q = {q}, so mJ must be {n} x {n} and Pi have {n} entries "
+                            f"(got {mJ.shape} and {Pi.shape})")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    _, burn, stride, S, seed, stream0, m, flags = _sample_args(N, q, 1.0, burn, stride, n_samples, seed, stream0, mask, gaps)
+    b, swap_every = _temper_args(N, betas, swap_every, burn, stride)
+    R = b.size
+    if Xa.ndim == 3 and Xa.shape[1] != R:
+        raise ArgumentError(f"incompatible sizes: X has {Xa.shape[1]} replicas a chain, betas has {R}")
+    Xr = _symbols(np.repeat(Xa[:, None, :], R, axis=1).reshape(N, R * K, order="F") if Xa.ndim == 2 else Xa.reshape(N, R * K, order="F"), "X")
+    s0 = None
+    if slot0 is not None:
+        s0 = np.asarray(slot0)
+        if s0.shape != (K, R) or not np.issubdtype(s0.dtype, np.integer) or not np.all(np.sort(s0, axis=1) == np.arange(R)):
+            raise ArgumentError(f"slot0 must be {K} x {R} integers, every row a permutation of 0 .. {R - 1}")
+        s0 = np.ascontiguousarray(s0, dtype=np.int32)
+    ctx = ctx or default_context()
+    out = ctx.tempered_outputs(N, K, R, swap_every, burn, stride, S, trace)
+    opt = lambda a: None if a is None or a.size == 0 else _lib._p(a)  # noqa: E731
+    ptrs = [opt(a) for a in out]
+    ptrs[3] = ctx._swaps_arg(out[3])
+    ctx.check(ctx.lib.gdca_sample_tempered(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), _lib._p(Xr), opt(s0), K, R, _lib._p(b), opt(m), flags,
+                                           seed, stream0, swap_every, burn, stride, S, *ptrs))
+    return tuple(a for a in out if a is not None)
+
+
 def potts_independent(Pi, N: int, q: int = 21):
     """The independent-site Potts model (W, zeros) of the single-site frequencies Pi (n = N (q - 1) entries, all and every site's gap
     frequency 1 - sum positive): couplings zero, W[r, r] = -2 log(Pi[r] / Pi_gap(site)) -- the start of ``gDCA_bm(init="independent")``."""
@@ -741,18 +812,34 @@ def potts_from_gaussian(mJ, Pi, q: int = 21, ctx=None):
 
 
 def bm_learn(W, Pi_d, Pij_d, X, n_iter: int, q: int = 21, eta: float = 1.0, lam: float = 0.0, beta: float = 1.0, burn=None, stride=None,
-             n_samples: int = 1, seed: int = 0, iter0: int = 0, mask=None, gaps: bool = True, ctx=None):
+             n_samples: int = 1, seed: int = 0, iter0: int = 0, mask=None, gaps: bool = True, ctx=None, betas=None, swap_every=None,
+             slot0=None):
     """n_iter iterations of Boltzmann-machine learning on host arrays (gdca_bm_learn): the Potts model W (n, n) -- from
     ``potts_from_gaussian`` or ``potts_independent`` -- is moved towards the frequencies (Pi_d, Pij_d) by sampling K persistent
     Metropolis chains from the columns of X (N, K), tallying the K n_samples samples and adding eta times the difference of the model's
     and the data's frequencies; ``lam`` is an L2 penalty on the couplings.  ``burn`` (default 10 N), ``stride`` (default N), ``mask``,
     ``gaps`` (default True: the gap is a symbol like any other) as ``sample``.  Returns (W, X, trace (n_iter, 4)): new arrays; trace
     holds max |Pi_m - Pi_d|, max |c_m - c_d|, the Pearson correlation of the connected correlations and the acceptance rate of every
-    iteration.  A later call with ``iter0 + n_iter`` continues the same run bit for bit."""
+    iteration.  A later call with ``iter0 + n_iter`` continues the same run bit for bit.
+
+    ``betas`` (a ladder of inverse temperatures, the target first; ``beta`` is then not used): replica-exchange chains in the place of
+    the plain ones (``devops.bm_learn_tempered_dev``, driven from Python; ``swap_every`` default N).  X is (N, K) -- every replica of
+    chain k starts at X[:, k] -- or (N, R, K) with ``slot0`` (K, R) to continue a run.  Returns (W, Xr (N, R, K), trace, slot (K, R),
+    swap_rates (n_iter, R - 1)); with ``betas=(beta,)`` W, Xr[:, 0, :] and trace are the plain loop's bit for bit."""
     W = np.array(W, dtype=np.float64, order="F")
     Pi_d = np.ascontiguousarray(Pi_d, dtype=np.float64)
     Pij_d = np.ascontiguousarray(Pij_d, dtype=np.float64)
-    Xf = np.array(_symbols(X, "X"), dtype=np.int8, order="F")
+    Xa = np.asarray(X)
+    R = None
+    if betas is not None:
+        if Xa.ndim not in (2, 3):
+            raise ArgumentError("X must be an (N, K) or an (N, R, K) array of symbols")
+        R = len(np.atleast_1d(np.asarray(betas, dtype=object)))
+        if Xa.ndim == 3 and Xa.shape[1] != R:
+            raise ArgumentError(f"incompatible sizes: X has {Xa.shape[1]} replicas a chain, betas has {R}")
+        Xr = np.repeat(Xa[:, None, :], R, axis=1) if Xa.ndim == 2 else Xa
+        Xa = Xr.reshape(Xr.shape[0], -1, order="F")[:, ::R] if R else Xa  # (one column a chain: the checks below)
+    Xf = np.array(_symbols(Xa, "X"), dtype=np.int8, order="F")
     N, K = Xf.shape
     if not isinstance(q, (int, np.integer)) or not 2 <= q <= 31:
         raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
@@ -768,6 +855,27 @@ def bm_learn(W, Pi_d, Pij_d, X, n_iter: int, q: int = 21, eta: float = 1.0, lam:
         raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
     beta, burn, stride, S, seed, iter0, m, flags = _sample_args(N, q, beta, burn, stride, n_samples, seed, iter0, mask, gaps)
     ctx = ctx or default_context()
+    if betas is not None:
+        from . import devops
+
+        b, every = _temper_args(N, betas, swap_every, burn, stride)
+        Xrf = _symbols(Xr.reshape(N, R * K, order="F"), "X")
+        s0 = None
+        if slot0 is not None:
+            s0 = np.asarray(slot0)
+            if s0.shape != (K, R) or not np.issubdtype(s0.dtype, np.integer) or not np.all(np.sort(s0, axis=1) == np.arange(R)):
+                raise ArgumentError(f"slot0 must be {K} x {R} integers, every row a permutation of 0 .. {R - 1}")
+        up = lambda a: _lib.DeviceBuffer.from_array(ctx, a)  # noqa: E731
+        dW, dPi, dPij, dXr = up(W), up(Pi_d), up(Pij_d), up(Xrf)
+        dslot = None if s0 is None else up(np.ascontiguousarray(s0, dtype=np.int32))
+        dmask = None if m is None else up(m)
+        dXo, dso, trace, rates = devops.bm_learn_tempered_dev(ctx, dW, dPi, dPij, N, int(q), dXr, dslot, K, b, int(n_iter), burn, stride, S,
+                                                              float(eta), float(lam), every, seed, iter0, dmask, flags)
+        out = (dW.download((n, n)), dXo.download((N, R, K), np.int8), trace, dso.download((K, R), np.int32, order="C"), rates)
+        for d in (dW, dPi, dPij, dXr, dslot, dmask, dXo, dso):
+            if d is not None:
+                d.free()
+        return out
     trace = np.empty((int(n_iter), 4), dtype=np.float64)
     ctx.check(ctx.lib.gdca_bm_learn(ctx.h, _lib._p(W), _lib._p(Pi_d), _lib._p(Pij_d), N, int(q), _lib._p(Xf), K,
                                     None if m is None else _lib._p(m), flags, beta, seed, iter0, int(n_iter), burn, stride, S, float(eta),

@@ -207,6 +207,41 @@ def sample_dev(ctx: Context, dmJ, dPi, N: int, q: int, dX, K: int, beta: float, 
     return dXs, daccepted, ddE_s, dthr, dmoves, dV
 
 
+def sample_tempered_dev(ctx: Context, dmJ, dPi, N: int, q: int, dXr, K: int, betas, swap_every: int, burn: int, stride: int, n_samples: int,
+                        seed: int = 0, stream0: int = 0, dslot0=None, dmask=None, flags: int = 0, dXs=None, daccepted=None, dswaps=None,
+                        dXr_out=None, dslot_out=None, dE_s=None, dthr=None, dmoves=None, dswap_thr=None, dslot_path=None, want=("E_s",)):
+    """Replica-exchange chains with every array in HBM (gdca_sample_tempered_dev): K chains of R = len(betas) replicas from Xr (N x R x K
+    int8; replica r of chain k holds slot dslot0[r + R k], or slot r), each replica a Metropolis chain on stream stream0 + k R + r at
+    betas[its slot]; after every swap_every proposals the holders of the slots p, p + 1 (p % 2 == round % 2) exchange slots iff
+    (betas[p] - betas[p + 1]) * (E_b - E_a) <= -log(u).  Slot 0 is sampled.  Xs, accepted (R x K, by slot), swaps ((R - 1) x K), Xr_out
+    and slot_out are always made; ``want`` names the optional outputs a buffer is made for where none is given: "E_s", "thr", "moves",
+    "swap_thr", "slot_path".  Returns (dXs, daccepted, dswaps, dXr_out, dslot_out, dE_s, dthr, dmoves, dswap_thr, dslot_path)."""
+    K, S, R = int(K), int(n_samples), len(betas)
+    T = int(burn) + S * int(stride)
+    E = T // max(int(swap_every), 1)
+    G = max(K * R, 1)
+    dXs = dXs or DeviceBuffer(ctx, max(N * S * K, 1))
+    daccepted = daccepted or DeviceBuffer(ctx, 4 * G)
+    dswaps = dswaps or DeviceBuffer(ctx, 4 * max(K * (R - 1), 1))
+    dXr_out = dXr_out or DeviceBuffer(ctx, N * G)
+    dslot_out = dslot_out or DeviceBuffer(ctx, 4 * G)
+    if "E_s" in want:
+        dE_s = dE_s or DeviceBuffer(ctx, 8 * max(S * K, 1))
+    if "thr" in want:
+        dthr = dthr or DeviceBuffer(ctx, 8 * max(T, 1) * G)
+    if "moves" in want:
+        dmoves = dmoves or DeviceBuffer(ctx, 4 * max(T, 1) * G)
+    if "swap_thr" in want:
+        dswap_thr = dswap_thr or DeviceBuffer(ctx, 8 * max(E * K * (R - 1), 1))
+    if "slot_path" in want:
+        dslot_path = dslot_path or DeviceBuffer(ctx, 4 * max(E, 1) * G)
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.sample_tempered_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), opt(dXr), opt(dslot0), K, betas, opt(dmask), int(flags), int(seed),
+                            int(stream0), int(swap_every), int(burn), int(stride), S, opt(dXs), opt(daccepted), opt(dswaps), opt(dXr_out),
+                            opt(dslot_out), opt(dE_s), opt(dthr), opt(dmoves), opt(dswap_thr), opt(dslot_path))
+    return dXs, daccepted, dswaps, dXr_out, dslot_out, dE_s, dthr, dmoves, dswap_thr, dslot_path
+
+
 def potts_from_gaussian_dev(ctx: Context, dmJ, dPi, N: int, q: int, dW=None):
     """The Gaussian model (mJ, Pi) as a Potts model (W, zeros) in mJ's layout, every array in HBM (gdca_potts_from_gaussian_dev):
     off-diagonal blocks the bits of mJ, W[r, r] = mJ[r, r] - 2 (mJ Pi)[r], the rest of a diagonal block +0.0.  W may not be mJ."""
@@ -247,13 +282,58 @@ def bm_learn_dev(ctx: Context, dW, dPi_d, dPij_d, N: int, q: int, dX, K: int, n_
     return dtrace
 
 
+def bm_learn_tempered_dev(ctx: Context, dW, dPi_d, dPij_d, N: int, q: int, dXr, dslot, K: int, betas, n_iter: int, burn: int, stride: int,
+                          n_samples: int, eta: float, lam: float = 0.0, swap_every=None, seed: int = 0, iter0: int = 0, dmask=None,
+                          flags: int = 0):
+    """n_iter iterations of Boltzmann-machine learning with REPLICA-EXCHANGE chains, driven from the host over the operator forms with
+    every array in HBM: iteration t runs sample_tempered_dev under (W, zeros) with stream0 = t K R from the persistent replicas dXr
+    (N x R x K int8) and their slots dslot (R x K int32, or None: replica r holds slot r), keeps Xr_out / slot_out as the next
+    iteration's start, tallies the K n_samples samples of slot 0 (betas[0], the target temperature), reads the fit out and updates W in
+    place.  One download of R K counts an iteration is the loop's only host round trip.  With betas = (beta,) the model, the chains
+    and the trace are bm_learn_dev's bit for bit.  Returns (dXr, dslot, trace (n_iter, 4), swap_rates (n_iter, R - 1)): the final
+    replicas and slots (new buffers), trace as bm_learn_dev's with the acceptance rate of slot 0 in column 3, and the accepted
+    fraction of every pair's attempted swaps per iteration."""
+    K, S, R, n_iter = int(K), int(n_samples), len(betas), int(n_iter)
+    n, T, M = N * (int(q) - 1), int(burn) + S * int(stride), K * S
+    every = N if swap_every is None else int(swap_every)
+    E = T // max(every, 1)
+    att = np.array([(E - p % 2 + 1) // 2 for p in range(R - 1)], dtype=np.float64)  # the rounds e < E with e % 2 == p % 2
+    dZero, dOnes = DeviceBuffer.from_array(ctx, np.zeros(n)), DeviceBuffer.from_array(ctx, np.ones(M))
+    dPi_m, dPij_m, dout = DeviceBuffer(ctx, 8 * n), DeviceBuffer(ctx, 8 * n * n), DeviceBuffer(ctx, 32)
+    G = K * R
+    pairs = [(DeviceBuffer(ctx, N * G), DeviceBuffer(ctx, 4 * G)) for _ in range(2)]  # (Xr_out may alias nothing that is read)
+    src = (dXr, dslot)
+    dXs, dacc, dsw = DeviceBuffer(ctx, max(N * M, 1)), DeviceBuffer(ctx, 4 * G), DeviceBuffer(ctx, 4 * max(K * (R - 1), 1))
+    trace, rates = np.empty((n_iter, 4)), np.empty((n_iter, R - 1))
+    for it in range(n_iter):
+        t = int(iter0) + it
+        dst = pairs[it % 2]
+        sample_tempered_dev(ctx, dW, dZero, N, q, src[0], K, betas, every, burn, stride, S, seed, t * G, dslot0=src[1], dmask=dmask,
+                            flags=flags, dXs=dXs, daccepted=dacc, dswaps=dsw, dXr_out=dst[0], dslot_out=dst[1], want=())
+        src = dst  # (the caller's buffers are never written)
+        compute_weighted_frequencies_dev(ctx, dXs, N, M, q, dOnes, float(M), dPi_m, dPij_m)
+        bm_readout_dev(ctx, dPi_d, dPij_d, dPi_m, dPij_m, N, q, dout)
+        trace[it] = dout.download((4,))
+        acc = dacc.download((K, R), np.int32, order="C")
+        trace[it, 3] = np.float64(int(acc[:, 0].astype(np.int64).sum())) / np.float64(K * T)
+        if R > 1:
+            rates[it] = dsw.download((K, R - 1), np.int32, order="C").astype(np.int64).sum(axis=0) / (K * att)
+        bm_update_dev(ctx, dW, dPij_d, dPij_m, N, q, eta, lam)
+    for b in (dZero, dOnes, dPi_m, dPij_m, dout, dXs, dacc, dsw) + pairs[n_iter % 2]:
+        b.free()
+    return src[0], src[1], trace, rates
+
+
 def bm_fit(Z, q: int, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float = 0.0, pseudocount: float = 0.8,
            target_pseudocount: float = 0.0, theta=":auto", init: str = "gaussian", burn=None, stride=None, n_samples: int = 1,
-           beta: float = 1.0, seed: int = 0, gaps: bool = True, scores: bool = False, ctx: Context = None):
+           beta: float = 1.0, seed: int = 0, gaps: bool = True, scores: bool = False, ctx: Context = None, betas=None, swap_every=None):
     """Boltzmann-machine refinement built like scores_stepwise from the device operators.  Z: (N, M) int8.  weights, frequencies,
     pseudocount, covariance, inverse (the warm start, ``init="gaussian"``; "independent" skips the last two), then n_iter iterations
     of bm_learn_dev towards the frequencies at ``target_pseudocount``.  The chains start from the first K sequences of Z (K <= M).
-    Returns (W (n, n), trace (n_iter, 4)) and, with ``scores=True``, S = APC(FN(W)) as a third entry."""
+    Returns (W (n, n), trace (n_iter, 4)) and, with ``scores=True``, S = APC(FN(W)) as a third entry.
+    ``betas`` (a ladder, the target temperature first; ``beta`` is then not used): the iterations are bm_learn_tempered_dev's, every
+    replica of chain k starting at sequence k, swaps every ``swap_every`` proposals (default N); the swap rates (n_iter, R - 1) come
+    back as a third entry, before S."""
     from .dcautils import potts_independent
 
     ctx = ctx or default_context()
@@ -284,10 +364,19 @@ def bm_fit(Z, q: int, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float =
     else:
         dW = DeviceBuffer.from_array(ctx, potts_independent(dPi.download((n,)), N, q))
     dX = DeviceBuffer.from_array(ctx, np.asfortranarray(Zf[:, :K]))
-    dtrace = bm_learn_dev(ctx, dW, dPi_d, dPij_d, N, q, dX, K, n_iter, burn, stride, n_samples, eta, lam, beta, seed,
-                          flags=_lib.SAMPLE_GAPS if gaps else 0)
-    W, trace = dW.download((n, n)), dtrace.download((int(n_iter), 4), order="C")
-    out = (W, trace)
+    if betas is None:
+        dtrace = bm_learn_dev(ctx, dW, dPi_d, dPij_d, N, q, dX, K, n_iter, burn, stride, n_samples, eta, lam, beta, seed,
+                              flags=_lib.SAMPLE_GAPS if gaps else 0)
+        W, trace = dW.download((n, n)), dtrace.download((int(n_iter), 4), order="C")
+        out = (W, trace)
+    else:
+        R = len(betas)
+        dXr0 = DeviceBuffer.from_array(ctx, np.asfortranarray(np.repeat(Zf[:, None, :K], R, axis=1)))  # (N, R, K): the replicas' starts
+        dXr, dslot, trace, rates = bm_learn_tempered_dev(ctx, dW, dPi_d, dPij_d, N, q, dXr0, None, K, betas, n_iter, burn, stride, n_samples,
+                                                         eta, lam, swap_every, seed, flags=_lib.SAMPLE_GAPS if gaps else 0)
+        dtrace = dXr0  # (freed with the rest below)
+        dXr.free(), dslot.free()
+        out = (dW.download((n, n)), trace, rates)
     if scores:
         dS = correct_APC_dev(ctx, compute_FN_dev(ctx, dW, N, q), N)
         out += (dS.download((N, N)),)

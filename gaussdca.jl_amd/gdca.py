@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, default_context
-from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _walk_args, _sample_args, _mutations_arg, decode_double_code, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
+from .dcautils import (FastaAlignment, Ranking, _block_views, _mut_what_arg, _walk_args, _sample_args, _temper_args, _mutations_arg, decode_double_code, _symbols, _theta_arg, _what_arg, read_fasta_alignment,
                        remove_duplicate_sequences, species_blocks)
 
 last_stats = None  # stats of the most recent gDCA call (theta, threshold, Meff, device timings)
@@ -494,10 +494,44 @@ def gDCA_sample(filename: str, starts=None, beta: float = 1.0, burn=None, stride
                            "samples")
 
 
+def gDCA_sample_tempered(filename: str, starts=None, betas=(1.0,), swap_every=None, burn: int = 10, stride: int = 1, n_samples: int = 1,
+                         seed: int = 0, stream0: int = 0, mask=None, gaps: bool = False, pseudocount: float = 0.8, theta=":auto",
+                         max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, **kw):
+    """Sequences drawn from the Gaussian model gDCA fits to the alignment in ``filename`` by replica-exchange (parallel tempering)
+    Metropolis chains (the fit and its arguments are ``gDCA_mutation_scan``'s, ``starts`` is ``gDCA_sample``'s).  Every chain runs
+    R = len(betas) replicas from its start sequence; a replica is a chain of ``gDCA_sample`` on a stream of its own at ``betas[slot]``
+    of the slot it holds (a proposal is accepted iff ``beta * dE <= -log(u)``), and after every ``swap_every`` proposals (default N) the
+    holders a, b of neighbouring slots p, p + 1 (p % 2 == round % 2) exchange slots iff ``(betas[p] - betas[p + 1]) * (E_b - E_a) <=
+    -log(u)``; ``betas[0]`` is the target temperature and only its holder is sampled.  ``burn`` and ``stride`` are IN SWEEPS (one
+    sweep is N proposals); ``swap_every`` in proposals must divide a sweep's multiples ``burn N`` and ``stride N``.
+
+    Returns ``(Xs (N, n_samples, K) int8, E_s (K, n_samples), accepted (K, R), swaps (K, R - 1))``: the samples, their energies, the
+    accepted proposals by slot and the accepted swaps by pair (a pair is attempted every other round).  Stats go to ``last_stats``."""
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_sample_tempered() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", 1)
+    X = _sequences_arg(starts, "starts", "an N x K")
+    for v, name, lo in ((burn, "burn", 0), (stride, "stride", 1)):
+        if not isinstance(v, (int, np.integer)) or v < lo:
+            raise ArgumentError(f"invalid {name} value: {v} (must be an integer >= {lo}, in sweeps)")
+
+    def run(c, ptr, N, M, q):
+        _, bu, sd, S, sd0, st0, m, flags = _sample_args(N, q, 1.0, int(burn) * N, int(stride) * N, n_samples, seed, stream0, mask, gaps)
+        b, every = _temper_args(N, betas, swap_every, bu, sd)
+        out, st = c.run_sample_tempered_ptr(ptr, N, M, q, float(pseudocount), _theta_arg(theta), *_ptr_count(X), betas=b, mask=m, flags=flags,
+                                            seed=sd0, stream0=st0, swap_every=every, burn=bu, stride=sd, n_samples=S)
+        return out[:4], st
+
+    return _fit_then_score(filename, pseudocount, max_gap_fraction, remove_dups, ctx, lambda N: _check_whole_sequences(X, N), run,
+                           "samples")
+
+
 def gDCA_bm(filename: str, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float = 0.0, target_pseudocount: float = 0.0,
             init: str = "gaussian", burn=None, stride=None, n_samples: int = 1, beta: float = 1.0, seed: int = 0, gaps: bool = True,
             scores: bool = False, min_separation: int = 5, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
-            remove_dups: bool = False, ctx=None, **kw):
+            remove_dups: bool = False, ctx=None, betas=None, swap_every=None, **kw):
     """Boltzmann-machine refinement (bmDCA) of the model gDCA fits to the alignment in ``filename``: the Potts model the Metropolis
     chains of ``gDCA_sample`` draw from is moved until the one- and two-site frequencies of its samples are the family's.  Built from
     the device operators like ``gDCA_stepwise``: weights, frequencies, pseudocount, covariance, inverse -- the Gaussian warm start at
@@ -510,7 +544,13 @@ def gDCA_bm(filename: str, n_iter: int, K: int = 1024, eta: float = 1.0, lam: fl
     Returns ``(W, trace)``: W (n, n) is the model as the pair (W, zeros) that ``sequence_energies``, ``mutation_scan``,
     ``greedy_walk``, ``sample``, ``compute_FN`` take in the place of (mJ, Pi); ``trace`` (n_iter, 4) holds max |Pi_m - Pi_d|,
     max |c_m - c_d|, the Pearson correlation of the connected correlations and the acceptance rate per iteration.  With
-    ``scores=True`` a third entry: the ranking of APC(FN(W)) at ``min_separation``, the bmDCA contact score."""
+    ``scores=True`` a third entry: the ranking of APC(FN(W)) at ``min_separation``, the bmDCA contact score.
+
+    ``betas`` (default None: the plain chains at ``beta``): a ladder of inverse temperatures, the target first -- every chain becomes
+    R = len(betas) replicas that swap neighbouring temperatures every ``swap_every`` proposals (default N) as in
+    ``gDCA_sample_tempered``, the samples of the target temperature are tallied, and the loop is driven from Python over the operator
+    forms (``devops.bm_learn_tempered_dev``).  ``trace[:, 3]`` is then the acceptance at the target temperature, and the accepted
+    fraction of every pair's swaps per iteration, (n_iter, R - 1), comes back as a third entry (before the ranking)."""
     from . import devops
 
     if "θ" in kw:
@@ -532,13 +572,16 @@ def gDCA_bm(filename: str, n_iter: int, K: int = 1024, eta: float = 1.0, lam: fl
     q = int(Z.max())
     if q >= 32:
         raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+    if betas is not None:
+        N = Z.shape[0]
+        betas, swap_every = _temper_args(N, betas, swap_every, 10 * N if burn is None else int(burn), N if stride is None else int(stride))
     out = devops.bm_fit(Z, q, int(n_iter), K=min(int(K), Z.shape[1]), eta=eta, lam=lam, pseudocount=float(pseudocount),
                         target_pseudocount=float(target_pseudocount), theta=theta, init=init, burn=burn, stride=stride,
-                        n_samples=n_samples, beta=beta, seed=seed, gaps=gaps, scores=scores, ctx=ctx)
+                        n_samples=n_samples, beta=beta, seed=seed, gaps=gaps, scores=scores, ctx=ctx, betas=betas, swap_every=swap_every)
     if scores:
         from .dcautils import compute_ranking
 
-        return out[0], out[1], compute_ranking(out[2], int(min_separation))
+        return out[:-1] + (compute_ranking(out[-1], int(min_separation)),)
     return out
 
 

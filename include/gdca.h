@@ -739,6 +739,68 @@ gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, i
                                 uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs_dev, double *dE_s_dev,
                                 int32_t *accepted_dev, double *thr_dev, int32_t *moves_dev, double *V_dev, gdca_stats *st);
 
+/* ---- Replica-exchange chains: the Metropolis chains tempered over a ladder of inverse temperatures --------------------------------
+ * Single-substitution chains at beta = 1 mix slowly on a fitted model.  Replica exchange (parallel tempering) runs R copies of every
+ * chain at a ladder of inverse temperatures and lets neighbouring temperatures swap by a Metropolis rule: the hot copies cross
+ * barriers, the swaps carry their states down, only the copy at the target temperature is sampled.  Conventions, state space,
+ * flags, mask, proposal, `beta * dE <= thr`, table update and generator (mix64, key, draw) are the Metropolis-chain section's.
+ * REPLICAS.  Chain k (0 .. K - 1) has R replicas, 1 <= R <= GDCA_TEMPER_MAX.  betas: a HOST array of R f64, each finite and >= 0, in
+ * any order; betas[0] is the target temperature and the only one sampled; the slots p and p + 1 are swap partners.  A replica HOLDS a
+ * slot; the states and tables never move, a swap exchanges the slots of two replicas.
+ * START.  Xr is N x R x K int8: replica (k, r) is the N bytes at (k R + r) N.  slot0 is R x K int32 (slot0[r + R k] = the slot replica
+ * r holds) or NULL: replica r holds slot r.  Every column of slot0 must be a permutation of 0 .. R - 1; that is checked on the device
+ * before anything is indexed with it (GDCA_EINVAL).  A replica's table starts as the bits gdca_mutation_scan(.., GDCA_MUT_POTENTIAL)
+ * returns for its start, E0[k, r] is the bits gdca_energies_dev returns for it, its site list is that of its own start.
+ * STREAMS.  Replica (k, r) draws its proposals from stream0 + k R + r exactly as a plain chain on that stream would: the stream belongs
+ * to the replica (the state), not to the temperature.  K R and the stream range obey gdca_sample_dev's limits for K.
+ * PROPOSALS.  Proposal t of a replica is the Metropolis section's proposal t with beta = betas[the slot held]; the running sum S of
+ * its accepted dE is one thread's, in step order.
+ * SWAP ROUND e (e = 0, 1, ..) takes place after proposal t of every replica whenever (t + 1) % swap_every == 0, swap_every >= 1.  It
+ * attempts the pairs p in 0 .. R - 2 with p % 2 == e % 2 (disjoint).  For pair p: a = the replica holding slot p, b = the one holding
+ * p + 1; Ea = E0[a] + S[a], Eb = E0[b] + S[b] (one addition each); d = (betas[p] - betas[p + 1]) * (Eb - Ea): two subtractions, one
+ * multiplication, no contraction; u = ((draw(skey_k, e R + p) >> 11) + 1) * 2^-53 with skey_k = mix64(~key(seed, stream0 + k R));
+ * thr_s = -log(u).  ACCEPT iff d <= thr_s: a NaN never accepts, equal betas accept every finite d.  On acceptance a and b exchange
+ * slots.  Known answers: skey of (seed, stream0, k, R) = (0, 0, 0, 3) is 0x1c44fab6a246bae2 with draw(skey, 0) = 0x3dc548297666b4b4
+ * (round 0, pair 0) and draw(skey, 4) = 0xace4d333b149e3d1 (round 1, pair 1); of (1, 5, 2, 4) it is 0x56a6a56ca201d633 with
+ * 0x9faf955cbe491e47 and draw(skey, 5) = 0xf81e54a1e15977ed.
+ * SAMPLES.  burn % swap_every == 0 and stride % swap_every == 0, so that every sample point coincides with a round: sample j is the
+ * state of slot 0's holder after the round at proposal burn + (j + 1) stride - 1.  n_steps = burn + n_samples stride,
+ * n_rounds = n_steps / swap_every.
+ * OUTPUTS (column-major):
+ *     Xs         N x n_samples x K int8, gdca_sample_dev's layout;
+ *     E_s        n_samples x K f64: E0 + S of the holder at the sample (one addition); may be NULL;
+ *     accepted   R x K int32: accepted proposals, counted BY THE SLOT held when proposed;
+ *     swaps      (R - 1) x K int32: accepted swaps per pair (the attempts are a function of e alone); not NULL even where R == 1;
+ *     Xr_out     N x R x K int8: the final states; may alias nothing that is read;
+ *     slot_out   R x K int32: the final slots (Xr_out and slot_out continue a run as Xr and slot0);
+ *     thr, moves n_steps x R x K, by replica, gdca_sample_dev's meaning; each may be NULL;
+ *     swap_thr   n_rounds x (R - 1) x K f64: thr_s, +0.0 for a pair not attempted in that round; may be NULL;
+ *     slot_path  n_rounds x R x K int32: the slot of every replica after the round; may be NULL.
+ * ORDER: no floating-point atomics, no reduction whose order depends on the launch.  The bits of everything returned for chain k
+ * depend on the model, its starts, slot0, mask, flags, betas, seed, its stream numbers, burn, stride, n_samples, swap_every and the
+ * values of thr and swap_thr -- not on K, on where the chain stands in the batch, on WALK_TABLE or on SAMPLE_CHUNK.
+ * R = 1 is gdca_sample_dev on stream stream0 + k, bit for bit: Xs, accepted, thr, moves equal, E_s = E0 + dE_s (one addition),
+ * whatever swap_every divides burn and stride.
+ * GDCA_EINVAL, nothing run: everything gdca_sample_dev refuses with K R in the place of K; R outside 1 .. GDCA_TEMPER_MAX; a beta
+ * negative, NaN or infinite; swap_every < 1 or one that does not divide burn and stride; a null Xr (operator form), Xs, accepted,
+ * swaps, Xr_out, slot_out or betas.  A byte of Xr outside 1..q is detected on the device as in the chains.  The tables live in the
+ * context's workspace of q N K R doubles.  Synchronous. */
+#define GDCA_TEMPER_MAX 64
+gdca_status gdca_sample_tempered_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *Xr_dev,
+                                     const int32_t *slot0_dev, int32_t K, int32_t R, const double *betas, const int8_t *mask_dev,
+                                     int32_t flags, uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride,
+                                     int32_t n_samples, int8_t *Xs_dev, double *E_s_dev, int32_t *accepted_dev, int32_t *swaps_dev,
+                                     int8_t *Xr_out_dev, int32_t *slot_out_dev, double *thr_dev, int32_t *moves_dev, double *swap_thr_dev,
+                                     int32_t *slot_path_dev);
+/* Fused, exactly as gdca_run_sample_dev: X is N x K, or NULL for Z's own M sequences (K is then ignored); every replica of a chain
+ * starts at that chain's sequence and replica r holds slot r. */
+gdca_status gdca_run_sample_tempered_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                         const int8_t *X_dev, int32_t K, int32_t R, const double *betas, const int8_t *mask_dev,
+                                         int32_t flags, uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride,
+                                         int32_t n_samples, int8_t *Xs_dev, double *E_s_dev, int32_t *accepted_dev, int32_t *swaps_dev,
+                                         int8_t *Xr_out_dev, int32_t *slot_out_dev, double *thr_dev, int32_t *moves_dev,
+                                         double *swap_thr_dev, int32_t *slot_path_dev, gdca_stats *st);
+
 /* ---- Boltzmann-machine refinement: fit the Potts model the Metropolis chains draw from ----------------------------------------------
  * The chains sample exp(-beta E) with E(x) = 1/2 (x - Pi)' mJ (x - Pi): read that way (mJ, Pi) IS a Potts model -- couplings the
  * off-diagonal blocks of mJ, fields g - 1/2 diag(mJ), g = mJ Pi.  These entry points fit that model to a family's one- and two-site
@@ -929,6 +991,18 @@ gdca_status gdca_run_sample(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int3
                             const int8_t *X_host, int32_t K, const int8_t *mask, int32_t flags, double beta, uint64_t seed,
                             uint64_t stream0, int32_t burn, int32_t stride, int32_t n_samples, int8_t *Xs, double *dE_s, int32_t *accepted,
                             double *thr, int32_t *moves, double *V, gdca_stats *st);
+
+/* Replica-exchange chains with host pointers: upload, the _dev form, download */
+gdca_status gdca_sample_tempered(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *Xr,
+                                 const int32_t *slot0, int32_t K, int32_t R, const double *betas, const int8_t *mask, int32_t flags,
+                                 uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride, int32_t n_samples,
+                                 int8_t *Xs, double *E_s, int32_t *accepted, int32_t *swaps, int8_t *Xr_out, int32_t *slot_out, double *thr,
+                                 int32_t *moves, double *swap_thr, int32_t *slot_path);
+gdca_status gdca_run_sample_tempered(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int32_t M, int32_t q, const gdca_params *p,
+                                     const int8_t *X_host, int32_t K, int32_t R, const double *betas, const int8_t *mask, int32_t flags,
+                                     uint64_t seed, uint64_t stream0, int32_t swap_every, int32_t burn, int32_t stride, int32_t n_samples,
+                                     int8_t *Xs, double *E_s, int32_t *accepted, int32_t *swaps, int8_t *Xr_out, int32_t *slot_out,
+                                     double *thr, int32_t *moves, double *swap_thr, int32_t *slot_path, gdca_stats *st);
 
 /* Boltzmann-machine refinement with host pointers: upload, the _dev form, download (W, X in place) */
 gdca_status gdca_potts_from_gaussian(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, double *W);
