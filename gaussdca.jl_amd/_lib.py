@@ -119,6 +119,7 @@ SYMBOLS = {
     "gdca_dbuf_bytes": (C.c_uint64, [C.c_void_p]),
     "gdca_dbuf_upload": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "gdca_dbuf_download": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "gdca_dbuf_copy": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "gdca_pair_identity_sum_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, _u64p]),
     "gdca_compute_theta_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, _f64p]),
     "gdca_neighbour_counts_dev": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -308,6 +309,20 @@ SYMBOLS = {
     "gdca_bm_learn": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                 C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                 C.c_void_p, C.c_void_p]),
+    "gdca_plm_conditionals_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdca_plm_conditionals": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdca_plm_tally_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p]),
+    "gdca_plm_tally": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                 C.c_void_p]),
+    "gdca_plm_tallies_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "gdca_plm_tallies": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "gdca_plm_learn_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p]),
+    "gdca_plm_learn": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p]),
     "gdca_write_rank": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gdca_synth_family": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
     "gdca_write_fasta": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
@@ -1023,6 +1038,30 @@ class Context:
                                               int(n_iter), int(burn), int(stride), int(n_samples), float(eta), float(lam),
                                               self._opt(trace_ptr), self._opt(Xs_last_ptr)))
 
+    # ---- pseudo-likelihood fit of the Potts model (W, zeros) (gdca_plm_*): every argument a device pointer ----
+    def plm_conditionals_dev(self, W_ptr: int, Z_ptr: int, N: int, M: int, q: int, p_ptr: int, nll_k_ptr: int) -> None:
+        """gdca_plm_conditionals_dev: W (n x n), Z (N x M int8) -> p (q N M f64, the scan's layout) and nll_k (M)"""
+        self.check(self.lib.gdca_plm_conditionals_dev(self.h, self._opt(W_ptr), self._opt(Z_ptr), int(N), int(M), int(q), self._opt(p_ptr),
+                                                      self._opt(nll_k_ptr)))
+
+    def plm_tally_dev(self, p_ptr: int, Z_ptr: int, w_ptr: int, Meff: float, N: int, M: int, q: int, Pi_c_ptr: int, Pij_c_ptr: int) -> None:
+        """gdca_plm_tally_dev: the conditionals p, Z and the weights w (M) -> the conditional tallies Pi_c (n), Pij_c (n x n)"""
+        self.check(self.lib.gdca_plm_tally_dev(self.h, self._opt(p_ptr), self._opt(Z_ptr), self._opt(w_ptr), float(Meff), int(N), int(M), int(q),
+                                               self._opt(Pi_c_ptr), self._opt(Pij_c_ptr)))
+
+    def plm_tallies_dev(self, W_ptr: int, Z_ptr: int, w_ptr: int, Meff: float, N: int, M: int, q: int, Pi_c_ptr: int, Pij_c_ptr: int,
+                        nll_ptr: int) -> None:
+        """gdca_plm_tallies_dev: the two above fused over slabs -> Pi_c, Pij_c and nll (one f64)"""
+        self.check(self.lib.gdca_plm_tallies_dev(self.h, self._opt(W_ptr), self._opt(Z_ptr), self._opt(w_ptr), float(Meff), int(N), int(M),
+                                                 int(q), self._opt(Pi_c_ptr), self._opt(Pij_c_ptr), self._opt(nll_ptr)))
+
+    def plm_learn_dev(self, W_ptr: int, Z_ptr: int, w_ptr: int, Meff: float, Pi_d_ptr: int, Pij_d_ptr: int, N: int, M: int, q: int,
+                      n_iter: int, eta: float, lam: float, trace_ptr: int) -> None:
+        """gdca_plm_learn_dev: n_iter iterations of tallies, read-out (trace, 4 x n_iter f64, the fourth nll), step on W in place"""
+        self.check(self.lib.gdca_plm_learn_dev(self.h, self._opt(W_ptr), self._opt(Z_ptr), self._opt(w_ptr), float(Meff), self._opt(Pi_d_ptr),
+                                               self._opt(Pij_d_ptr), int(N), int(M), int(q), int(n_iter), float(eta), float(lam),
+                                               self._opt(trace_ptr)))
+
     # ---- several settings of one alignment (gdca_run_multi): one front end, a covariance + inverse per distinct pseudocount ----
     def _check_multi(self, rc: int, sts, results):
         """Raise as check() does for the first failing member (its info); the exception carries every member's result in
@@ -1204,6 +1243,12 @@ class DeviceBuffer:
         out = np.empty(shape, dtype=dtype, order=order)
         self.ctx.check(self.ctx.lib.gdca_dbuf_download(self.ctx.h, self.h, int(offset), _p(out), out.nbytes))
         return out
+
+    def copy_from(self, src: "DeviceBuffer", nbytes: int | None = None) -> "DeviceBuffer":
+        """The first nbytes (default: all of src) of another buffer into this one, device to device, on the context's stream
+        (gdca_dbuf_copy): ordered with every call on the context, nothing crosses to the host."""
+        self.ctx.check(self.ctx.lib.gdca_dbuf_copy(self.ctx.h, self.h, src.h, int(src.nbytes if nbytes is None else nbytes)))
+        return self
 
     def free(self):
         if getattr(self, "h", None):

@@ -315,6 +315,8 @@ struct gdca_ctx {
     // counts, the samples), and the read-out's column partials
     gdca_buf TMst, TMx;       // replica-exchange chains (k_temper.hip): gdca_temper_state_bytes, and the fused form's N x R x K starts
     gdca_buf BMws, BMred;
+    // pseudo-likelihood fit (k_plm.hip): the slab's table of potentials / conditionals, and plm_plan's arrays
+    gdca_buf PLMv, PLMws;
     int ncu;                  // compute units of the device
     double *piv;              // the pivots of the context's last inverse, n_pad doubles inside Sg (inverse_job)
     // log det of the matrix of the last SPD inverse this context completed (gdca_last_logdet): kept on the host, so that entry points
@@ -499,6 +501,7 @@ bool gdca_tuning_set(gdca_tuning *t, const char *key, const char *value)
         {"CHOLESKY", &t->cholesky, 0, 2},  {"PHASED_FRONTS", &t->phased_fronts, 0, 1}, {"PHASED_GRIDS", &t->phased_grids, -1, 8}, {"PHASED_STREAMS", &t->phased_streams, 1, 64},
         {"ENERGY_CHUNK", &t->energy_chunk, 0, 1 << 30}, {"PAIR_CHUNK", &t->pair_chunk, 0, 1 << 30},
         {"EPI_GENERIC", &t->epi_generic, 0, 1}, {"SAMPLE_CHUNK", &t->sample_chunk, 0, INT32_MAX},
+        {"PLM_CHUNK", &t->plm_chunk, 0, 1 << 20}, {"PLM_SLAB", &t->plm_slab, 0, INT32_MAX},
     };
     for (auto &e : ints)
         if (!strcmp(k, e.name)) {
@@ -558,7 +561,7 @@ void gdca_tuning_from_env(gdca_tuning *t)
     static const char *const names[] = {"GDCA_GROUP", "GDCA_RAMP", "GDCA_RAGGED", "GDCA_REM_TAIL", "GDCA_PANEL_HALVES", "GDCA_SLAB",
                                         "GDCA_RING", "GDCA_MCUS", "GDCA_SWEEP_DEBUG", "GDCA_SWEEP_TIMEOUT_MS", "GDCA_SWEEP_RETRIES", "GDCA_TALLY_TJ", "GDCA_TALLY_SKIP",
                                         "GDCA_HAMMING_MODE", "GDCA_HAM_CUT", "GDCA_FORCE_FALLBACK", "GDCA_MERGE", "GDCA_MERGE_BLOCKS",
-                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK", "GDCA_EPI_GENERIC", "GDCA_WALK_TABLE", "GDCA_SAMPLE_CHUNK"};
+                                        "GDCA_MERGE_MCUS", "GDCA_MERGE_GROUP", "GDCA_MERGE_TILES", "GDCA_REFINE", "GDCA_REFINE_COND", "GDCA_CHOLESKY", "GDCA_SWEEP_TRACE", "GDCA_PHASED_FRONTS", "GDCA_PHASED_GRIDS", "GDCA_PHASED_STREAMS", "GDCA_MCU_SOLO", "GDCA_ENERGY_CHUNK", "GDCA_PAIR_CHUNK", "GDCA_EPI_GENERIC", "GDCA_WALK_TABLE", "GDCA_SAMPLE_CHUNK", "GDCA_PLM_CHUNK", "GDCA_PLM_SLAB"};
     for (const char *nm : names)
         if (const char *v = getenv(nm)) (void)gdca_tuning_set(t, nm, v);  // an unusable value leaves the default
 }
@@ -769,7 +772,7 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
                         &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
                         &ctx->LOa, &ctx->LOb, &ctx->PBN,
-                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst, &ctx->TMst, &ctx->TMx, &ctx->BMws, &ctx->BMred};
+                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst, &ctx->TMst, &ctx->TMx, &ctx->BMws, &ctx->BMred, &ctx->PLMv, &ctx->PLMws};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     ctx->staging.release();
@@ -2616,6 +2619,14 @@ gdca_status gdca_dbuf_download(gdca_ctx *ctx, const gdca_dbuf *b, uint64_t offse
     return GDCA_OK;
 }
 
+gdca_status gdca_dbuf_copy(gdca_ctx *ctx, gdca_dbuf *dst, const gdca_dbuf *src, uint64_t bytes)
+{
+    if (!ctx || !dst || !src || bytes > dst->bytes || bytes > src->bytes) return GDCA_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (bytes && dst->p != src->p) HIPCHK(hipMemcpyAsync(dst->p, src->p, (size_t)bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return GDCA_OK;
+}
+
 // ---- operator level, device-resident (`_dev`): every matrix argument is a device pointer ----------------------
 // Each call enqueues on the ctx stream and returns after the stream has drained only where a host scalar comes
 // back (weights: Meff/theta/thresh; spd_inverse: info; di: convergence; frequencies: the symbol-range check); the
@@ -3977,6 +3988,212 @@ gdca_status gdca_bm_learn_dev(gdca_ctx *ctx, double *W_dev, const double *Pi_d_d
     return sequences_checked(ctx);  // (the one round trip of the call: the device's flags)
 }
 
+// ---- pseudo-likelihood fit (k_plm.hip; include/gdca.h): the conditionals, their tally, the two fused over slabs, the loop ----
+// The sequences go through the mutation stage in SLABS of whole blocks of PLM_CHUNK, so the table [slab][N][q] stays bounded: 256 MB
+// where PLM_SLAB does not say otherwise.  A block never straddles two slabs, so the order of every sum is the same whatever the slab.
+struct plm_geometry {
+    int chunk, slab;
+    plm_geometry(const gdca_ctx *ctx, int N, int M, int q)
+    {
+        chunk = ctx->tune.plm_chunk > 0 ? ctx->tune.plm_chunk : GDCA_PLM_CHUNK_RULE;
+        long long want = ctx->tune.plm_slab > 0 ? ctx->tune.plm_slab : std::max(1LL, (256LL << 20) / ((long long)N * q * 8));
+        want = (want + chunk - 1) / chunk * chunk;
+        slab = (int)std::min<long long>(want, ((long long)M + chunk - 1) / chunk * chunk);
+    }
+};
+
+// where the arrays lie in ctx->PLMws (each at a multiple of 256 bytes): Q (n x n), S (n), the zero Pi of the container (n), nll_k (M),
+// l_ki of a slab (slab N), and the loop's own conditional tallies Pij_c (n x n), Pi_c (n) and nll (1)
+struct plm_plan {
+    size_t q, s, zero, nllk, l, pij, pi, nll, bytes;
+    plm_plan(int n, int N, int M, int slab, bool loop)
+    {
+        size_t at = 0;
+        auto take = [&](size_t b) {
+            const size_t here = at;
+            at += (b + 255) & ~(size_t)255;
+            return here;
+        };
+        q = take((size_t)n * n * sizeof(double));
+        s = take((size_t)n * sizeof(double));
+        zero = take((size_t)n * sizeof(double));
+        nllk = take((size_t)M * sizeof(double));
+        l = take((size_t)std::min(slab, M) * N * sizeof(double));
+        pij = take(loop ? (size_t)n * n * sizeof(double) : 0);
+        pi = take(loop ? (size_t)n * sizeof(double) : 0);
+        nll = take(sizeof(double));
+        bytes = at;
+    }
+};
+
+static gdca_status check_plm_model(gdca_ctx *ctx, const void *W, const void *Z, int N, int M, int q)
+{
+    CHK(validate(ctx, N, M, q));
+    if (!W || !Z) return fail(ctx, GDCA_EINVAL, "null pointer");
+    return GDCA_OK;
+}
+
+static gdca_status check_plm_weights(gdca_ctx *ctx, const void *w, double Meff)
+{
+    if (!w) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (!(Meff > 0.0) || !std::isfinite(Meff)) return fail(ctx, GDCA_EINVAL, "invalid Meff");
+    return GDCA_OK;
+}
+
+static gdca_status check_plm_tallies(gdca_ctx *ctx, const void *W, const void *Z, const void *w, double Meff, int N, int M, int q,
+                                     const void *Pi_c, const void *Pij_c, const void *nll)
+{
+    CHK(check_plm_model(ctx, W, Z, N, M, q));
+    CHK(check_plm_weights(ctx, w, Meff));
+    if (!Pi_c || !Pij_c || !nll) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (W == Pij_c || W == Pi_c || W == nll) return fail(ctx, GDCA_EINVAL, "W may not alias an output");
+    return GDCA_OK;
+}
+
+static gdca_status check_plm_learn(gdca_ctx *ctx, const void *W, const void *Z, const void *w, double Meff, const void *Pi_d, const void *Pij_d,
+                                   int N, int M, int q, int n_iter, double eta, double lambda, const void *trace)
+{
+    CHK(check_plm_model(ctx, W, Z, N, M, q));
+    CHK(check_plm_weights(ctx, w, Meff));
+    if (!Pi_d || !Pij_d || !trace) return fail(ctx, GDCA_EINVAL, "null pointer");
+    CHK(check_bm_rates(ctx, eta, lambda));
+    if (n_iter < 1) return fail(ctx, GDCA_EINVAL, "invalid n_iter");
+    if (W == trace || W == Pij_d || W == Pi_d) return fail(ctx, GDCA_EINVAL, "W may not alias an output or the data's frequencies");
+    return GDCA_OK;
+}
+
+// the weights' range, before anything is computed from them: one round trip
+static gdca_status plm_weights_checked(gdca_ctx *ctx, const double *w_dev, int M)
+{
+    gdca_launch_plm_check_weights(ctx->stream, w_dev, M, (gdca_dev_scalars *)ctx->sc.p);
+    CHK(check_launch(ctx, "weights check"));
+    CHK(fetch_scalars(ctx));
+    if (ctx->sc_host->bad_symbol & GDCA_BAD_WEIGHT) return fail(ctx, GDCA_EINVAL, "weights must lie in [0, 1]");
+    return GDCA_OK;
+}
+
+// One pass over the M sequences Z (N x M) under (W, zero) in slabs: the potentials of a slab through the mutation stage -- into the
+// caller's p where p_out is given, else into ctx->PLMv --, the softmax in place, l_ki into L, nll_k; and, where Q is given, the slab's
+// tally into Q and S (+0.0 before the first slab: the caller's fill).
+static gdca_status plm_pass(gdca_ctx *ctx, const double *W, const double *zero, const int8_t *Z, int N, int M, int q, const plm_geometry &g,
+                            double *p_out, double *L, double *nll_k, const double *w, double *Q, double *S)
+{
+    const gdca_model model = operator_model(W, zero, N, q);
+    const size_t seq = (size_t)N * q;
+    if (!p_out) CHK(ensure(ctx, ctx->PLMv, (size_t)std::min(g.slab, M) * seq * sizeof(double)));
+    for (int k0 = 0; k0 < M; k0 += g.slab) {
+        const int cnt = std::min(g.slab, M - k0);
+        double *D = p_out ? p_out + (size_t)k0 * seq : (double *)ctx->PLMv.p;
+        CHK(mutation_stage(ctx, model, Z + (size_t)k0 * N, cnt, GDCA_MUT_POTENTIAL, D));
+        gdca_launch_plm_softmax(ctx->stream, D, (const uint32_t *)ctx->Xg.p, N, cnt, q, L, nll_k + k0);
+        if (Q) HIPCHK(gdca_launch_plm_tally(ctx->stream, D, (const uint32_t *)ctx->Xg.p, w + k0, N, q - 1, cnt, g.chunk, Q, S));
+        CHK(check_launch(ctx, "pseudo-likelihood slab"));
+    }
+    return GDCA_OK;
+}
+
+// the conditional tallies and nll of (W, zero) into Pi_c, Pij_c, *nll: fill, the slabs, the finish, the weighted sum (ws: plm_plan's)
+static gdca_status plm_tallies_stage(gdca_ctx *ctx, const double *W, const int8_t *Z, const double *w, double Meff, int N, int M, int q,
+                                     const plm_geometry &g, const plm_plan &at, double *Pi_c, double *Pij_c, double *nll)
+{
+    hipStream_t s = ctx->stream;
+    const int n = N * (q - 1);
+    char *ws = (char *)ctx->PLMws.p;
+    double *Q = (double *)(ws + at.q), *S = (double *)(ws + at.s), *zero = (double *)(ws + at.zero), *nllk = (double *)(ws + at.nllk),
+           *L = (double *)(ws + at.l);
+    gdca_launch_bm_fill(s, Q, (size_t)n * n, 0.0);
+    gdca_launch_bm_fill(s, S, (size_t)n, 0.0);
+    CHK(plm_pass(ctx, W, zero, Z, N, M, q, g, nullptr, L, nllk, w, Q, S));
+    gdca_launch_plm_finish(s, Q, S, N, q - 1, Meff, Pi_c, Pij_c);
+    gdca_launch_plm_nll(s, w, nllk, M, Meff, nll);
+    return check_launch(ctx, "pseudo-likelihood tallies");
+}
+
+gdca_status gdca_plm_conditionals_dev(gdca_ctx *ctx, const double *W_dev, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, double *p_dev,
+                                      double *nll_k_dev)
+{
+    CHK(check_plm_model(ctx, W_dev, Z_dev, N, M, q));
+    if (!p_dev || !nll_k_dev) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if ((const void *)W_dev == p_dev || (const void *)W_dev == nll_k_dev) return fail(ctx, GDCA_EINVAL, "W may not alias an output");
+    CHK(begin(ctx));
+    const int n = N * (q - 1);
+    const plm_geometry g(ctx, N, M, q);
+    const plm_plan at(n, N, M, g.slab, false);
+    CHK(ensure(ctx, ctx->PLMws, at.bytes));
+    char *ws = (char *)ctx->PLMws.p;
+    double *zero = (double *)(ws + at.zero);
+    gdca_launch_bm_fill(ctx->stream, zero, (size_t)n, 0.0);
+    CHK(plm_pass(ctx, W_dev, zero, Z_dev, N, M, q, g, p_dev, (double *)(ws + at.l), nll_k_dev, nullptr, nullptr, nullptr));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_plm_tally_dev(gdca_ctx *ctx, const double *p_dev, const int8_t *Z_dev, const double *w_dev, double Meff, int32_t N, int32_t M,
+                               int32_t q, double *Pi_c_dev, double *Pij_c_dev)
+{
+    CHK(check_plm_model(ctx, p_dev, Z_dev, N, M, q));
+    CHK(check_plm_weights(ctx, w_dev, Meff));
+    if (!Pi_c_dev || !Pij_c_dev) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if ((const void *)p_dev == Pi_c_dev || (const void *)p_dev == Pij_c_dev) return fail(ctx, GDCA_EINVAL, "p may not alias an output");
+    CHK(begin(ctx));
+    CHK(plm_weights_checked(ctx, w_dev, M));
+    hipStream_t s = ctx->stream;
+    const int n = N * (q - 1);
+    const plm_geometry g(ctx, N, M, q);
+    const plm_plan at(n, N, M, g.slab, false);
+    CHK(ensure(ctx, ctx->PLMws, at.bytes));
+    CHK(ensure(ctx, ctx->Xg, (size_t)gdca_energy_blocks(N) * M * sizeof(uint32_t)));
+    char *ws = (char *)ctx->PLMws.p;
+    double *Q = (double *)(ws + at.q), *S = (double *)(ws + at.s);
+    gdca_launch_energy_pack(s, Z_dev, (size_t)N, N, M, q, (uint32_t *)ctx->Xg.p, (gdca_dev_scalars *)ctx->sc.p);
+    gdca_launch_bm_fill(s, Q, (size_t)n * n, 0.0);
+    gdca_launch_bm_fill(s, S, (size_t)n, 0.0);
+    HIPCHK(gdca_launch_plm_tally(s, p_dev, (const uint32_t *)ctx->Xg.p, w_dev, N, q - 1, M, g.chunk, Q, S));
+    gdca_launch_plm_finish(s, Q, S, N, q - 1, Meff, Pi_c_dev, Pij_c_dev);
+    CHK(check_launch(ctx, "pseudo-likelihood tally"));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_plm_tallies_dev(gdca_ctx *ctx, const double *W_dev, const int8_t *Z_dev, const double *w_dev, double Meff, int32_t N,
+                                 int32_t M, int32_t q, double *Pi_c_dev, double *Pij_c_dev, double *nll_dev)
+{
+    CHK(check_plm_tallies(ctx, W_dev, Z_dev, w_dev, Meff, N, M, q, Pi_c_dev, Pij_c_dev, nll_dev));
+    CHK(begin(ctx));
+    CHK(plm_weights_checked(ctx, w_dev, M));
+    const int n = N * (q - 1);
+    const plm_geometry g(ctx, N, M, q);
+    const plm_plan at(n, N, M, g.slab, false);
+    CHK(ensure(ctx, ctx->PLMws, at.bytes));
+    gdca_launch_bm_fill(ctx->stream, (double *)((char *)ctx->PLMws.p + at.zero), (size_t)n, 0.0);
+    CHK(plm_tallies_stage(ctx, W_dev, Z_dev, w_dev, Meff, N, M, q, g, at, Pi_c_dev, Pij_c_dev, nll_dev));
+    return sequences_checked(ctx);
+}
+
+gdca_status gdca_plm_learn_dev(gdca_ctx *ctx, double *W_dev, const int8_t *Z_dev, const double *w_dev, double Meff, const double *Pi_d_dev,
+                               const double *Pij_d_dev, int32_t N, int32_t M, int32_t q, int32_t n_iter, double eta, double lambda,
+                               double *trace_dev)
+{
+    CHK(check_plm_learn(ctx, W_dev, Z_dev, w_dev, Meff, Pi_d_dev, Pij_d_dev, N, M, q, n_iter, eta, lambda, trace_dev));
+    CHK(begin(ctx));
+    CHK(plm_weights_checked(ctx, w_dev, M));
+    hipStream_t s = ctx->stream;
+    const int n = N * (q - 1);
+    const plm_geometry g(ctx, N, M, q);
+    const plm_plan at(n, N, M, g.slab, true);
+    CHK(ensure(ctx, ctx->PLMws, at.bytes));
+    char *ws = (char *)ctx->PLMws.p;
+    double *Pij_c = (double *)(ws + at.pij), *Pi_c = (double *)(ws + at.pi), *nll = (double *)(ws + at.nll);
+    gdca_launch_bm_fill(s, (double *)(ws + at.zero), (size_t)n, 0.0);
+    for (int it = 0; it < n_iter; ++it) {
+        CHK(plm_tallies_stage(ctx, W_dev, Z_dev, w_dev, Meff, N, M, q, g, at, Pi_c, Pij_c, nll));
+        double *out = trace_dev + 4 * (size_t)it;
+        CHK(bm_readout_stage(ctx, Pi_d_dev, Pij_d_dev, Pi_c, Pij_c, N, q, out, false));
+        HIPCHK(hipMemcpyAsync(out + 3, nll, sizeof(double), hipMemcpyDeviceToDevice, s));
+        gdca_launch_bm_update(s, W_dev, Pij_d_dev, Pij_c, N, q - 1, eta, lambda);
+        CHK(check_launch(ctx, "pseudo-likelihood iteration"));
+    }
+    return sequences_checked(ctx);  // (the sequences' flags, read once at the end)
+}
+
 gdca_status gdca_apc_dev(gdca_ctx *ctx, double *S_dev, int32_t N)
 {
     if (!ctx || !S_dev || N < 1) return GDCA_EINVAL;
@@ -4677,6 +4894,70 @@ gdca_status gdca_bm_learn(gdca_ctx *ctx, double *W, const double *Pi_d, const do
     CHK(sg.status());
     return sg.finish(gdca_bm_learn_dev(ctx, W_dev, Pi_d_dev, Pij_d_dev, N, q, X_dev, K, mask_dev, flags, beta, seed, iter0, n_iter, burn, stride,
                                        n_samples, eta, lambda, trace_dev, Xs_dev));
+}
+
+/* pseudo-likelihood fit with host pointers */
+gdca_status gdca_plm_conditionals(gdca_ctx *ctx, const double *W, const int8_t *Z, int32_t N, int32_t M, int32_t q, double *p, double *nll_k)
+{
+    CHK(check_plm_model(ctx, W, Z, N, M, q));
+    if (!p || !nll_k) return fail(ctx, GDCA_EINVAL, "null pointer");
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *W_dev = sg.in(W, n * n * sizeof(double));
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    double *p_dev = sg.out(p, (size_t)M * N * q * sizeof(double));
+    double *nll_k_dev = sg.out(nll_k, (size_t)M * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_plm_conditionals_dev(ctx, W_dev, Z_dev, N, M, q, p_dev, nll_k_dev));
+}
+
+gdca_status gdca_plm_tally(gdca_ctx *ctx, const double *p, const int8_t *Z, const double *w, double Meff, int32_t N, int32_t M, int32_t q,
+                           double *Pi_c, double *Pij_c)
+{
+    CHK(check_plm_model(ctx, p, Z, N, M, q));
+    CHK(check_plm_weights(ctx, w, Meff));
+    if (!Pi_c || !Pij_c) return fail(ctx, GDCA_EINVAL, "null pointer");
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *p_dev = sg.in(p, (size_t)M * N * q * sizeof(double));
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    const double *w_dev = sg.in(w, (size_t)M * sizeof(double));
+    double *Pi_dev = sg.out(Pi_c, n * sizeof(double));
+    double *Pij_dev = sg.out(Pij_c, n * n * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_plm_tally_dev(ctx, p_dev, Z_dev, w_dev, Meff, N, M, q, Pi_dev, Pij_dev));
+}
+
+gdca_status gdca_plm_tallies(gdca_ctx *ctx, const double *W, const int8_t *Z, const double *w, double Meff, int32_t N, int32_t M, int32_t q,
+                             double *Pi_c, double *Pij_c, double *nll)
+{
+    CHK(check_plm_tallies(ctx, W, Z, w, Meff, N, M, q, Pi_c, Pij_c, nll));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    const double *W_dev = sg.in(W, n * n * sizeof(double));
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    const double *w_dev = sg.in(w, (size_t)M * sizeof(double));
+    double *Pi_dev = sg.out(Pi_c, n * sizeof(double));
+    double *Pij_dev = sg.out(Pij_c, n * n * sizeof(double));
+    double *nll_dev = sg.out(nll, sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_plm_tallies_dev(ctx, W_dev, Z_dev, w_dev, Meff, N, M, q, Pi_dev, Pij_dev, nll_dev));
+}
+
+gdca_status gdca_plm_learn(gdca_ctx *ctx, double *W, const int8_t *Z, const double *w, double Meff, const double *Pi_d, const double *Pij_d,
+                           int32_t N, int32_t M, int32_t q, int32_t n_iter, double eta, double lambda, double *trace)
+{
+    CHK(check_plm_learn(ctx, W, Z, w, Meff, Pi_d, Pij_d, N, M, q, n_iter, eta, lambda, trace));
+    const size_t n = (size_t)N * (q - 1);
+    host_stage sg(ctx);
+    double *W_dev = sg.inout(W, W, n * n * sizeof(double));
+    const int8_t *Z_dev = sg.in(Z, (size_t)N * M);
+    const double *w_dev = sg.in(w, (size_t)M * sizeof(double));
+    const double *Pi_d_dev = sg.in(Pi_d, n * sizeof(double));
+    const double *Pij_d_dev = sg.in(Pij_d, n * n * sizeof(double));
+    double *trace_dev = sg.out(trace, 4 * (size_t)n_iter * sizeof(double));
+    CHK(sg.status());
+    return sg.finish(gdca_plm_learn_dev(ctx, W_dev, Z_dev, w_dev, Meff, Pi_d_dev, Pij_d_dev, N, M, q, n_iter, eta, lambda, trace_dev));
 }
 
 gdca_status gdca_probe_mfma_f64(gdca_ctx *ctx, int32_t iters, double *tflops)

@@ -91,6 +91,8 @@ struct gdca_tuning {
     int epi_generic;        // GDCA_EPI_GENERIC (tests, measurements): 1 = the double-mutant scan runs its generic instance (s at run time) at s = 20 too
     int walk_table;         // GDCA_WALK_TABLE: where the greedy walk keeps a sequence's table of site potentials: 0 = in LDS where it fits, else in HBM (auto, default), 1 = LDS (a table that does not fit: GDCA_EINVAL), 2 = HBM; the same bits wherever it is (the Metropolis chains share it)
     int sample_chunk;       // GDCA_SAMPLE_CHUNK: proposals one launch of the Metropolis kernel takes; 0 = GDCA_SAMPLE_CHUNK_RULE; the same bits whatever it is
+    int plm_chunk;          // GDCA_PLM_CHUNK: sequences a block of the pseudo-likelihood tally sums in one go (k_plm.hip); 0 = GDCA_PLM_CHUNK_RULE; it fixes the order of the sums: another value, other bits
+    int plm_slab;           // GDCA_PLM_SLAB: sequences whose conditionals are held at a time (rounded up to whole blocks); 0 = as many as keep the table within ~256 MB; the same bits whatever it is
     char sweep_trace[256];  // GDCA_SWEEP_TRACE: file the in-kernel trace of the next inverse is written to ("" = off)
 };
 void gdca_tuning_from_env(gdca_tuning *t);
@@ -469,3 +471,17 @@ void gdca_launch_bm_accept(hipStream_t s, const int32_t *accepted, int K, long l
 // X (N x K) <- the last of the n_samples samples of every chain in Xs (k_sample's layout)
 void gdca_launch_bm_last_sample(hipStream_t s, const int8_t *Xs, int N, int K, int n_samples, int8_t *X);
 void gdca_launch_bm_fill(hipStream_t s, double *v, size_t count, double value);
+
+// ---- k_plm.hip: pseudo-likelihood fit of the Potts model (W, 0) -- the conditionals of the mutation stage's potentials, their tally against
+// the alignment, the finish (include/gdca.h, Pseudo-likelihood) -----------------------------------------------------------------------------
+#define GDCA_PLM_CHUNK_RULE 512  // sequences a block of the tally
+// D [K][N][q] from V to p in place, l_ki into L [K][N], nll_k [K]; Xg the K sequences' packed symbols
+void gdca_launch_plm_softmax(hipStream_t s, double *D, const uint32_t *Xg, int N, int K, int q, double *L, double *nll_k);
+// Q (n x n) and S (n), +0.0 before the first slab, take a slab of K sequences in, blocks of `chunk`; an error: nothing launched
+hipError_t gdca_launch_plm_tally(hipStream_t s, const double *p, const uint32_t *Xg, const double *w, int N, int sdim, int K, int chunk,
+                                 double *Q, double *S);
+void gdca_launch_plm_finish(hipStream_t s, const double *Q, const double *S, int N, int sdim, double Meff, double *Pi, double *Pij);
+// *out = (sum_k w_k nll_k) / Meff by one workgroup's fixed tree
+void gdca_launch_plm_nll(hipStream_t s, const double *w, const double *nll_k, int M, double Meff, double *out);
+// a weight outside [0, 1]: GDCA_BAD_WEIGHT in sc->bad_symbol
+void gdca_launch_plm_check_weights(hipStream_t s, const double *w, int M, gdca_dev_scalars *sc);

@@ -883,6 +883,72 @@ def bm_learn(W, Pi_d, Pij_d, X, n_iter: int, q: int = 21, eta: float = 1.0, lam:
     return W, Xf, trace
 
 
+def _plm_args(W, Z, q, w=None, Meff=None):
+    """the model, the sequences and the weights of the pseudo-likelihood operators, checked: (W, Zf, N, M, w)"""
+    W = np.asfortranarray(W, dtype=np.float64)
+    Zf = _symbols(Z, "Z", "an N x M")
+    N, M = Zf.shape
+    if not isinstance(q, (int, np.integer)) or not 2 <= q <= 31:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    n = N * (int(q) - 1)
+    if N < 1 or M < 1 or W.shape != (n, n):
+        raise ArgumentError(f"incompatible sizes: Z has N = {N} sites, q = {q}, so W must be {n} x {n}")
+    if w is not None:
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (M,) or not isinstance(Meff, (int, float, np.integer, np.floating)) or not Meff > 0:
+            raise ArgumentError(f"incompatible weights: w must have M = {M} entries and Meff be positive")
+    return W, Zf, N, M, w
+
+
+def plm_conditionals(W, Z, q: int = 21, ctx=None):
+    """The conditionals of the sequences Z (N, M) under the Potts model (W, zeros) on host arrays (gdca_plm_conditionals): returns
+    (p (M, N, q): p[k, i, c - 1] = P(x_i = c | the rest of sequence k), the gap last; nll_k (M,): -sum_i log P(x_ki | rest))."""
+    W, Zf, N, M, _ = _plm_args(W, Z, q)
+    ctx = ctx or default_context()
+    p, nll_k = np.empty((M, N, int(q)), dtype=np.float64), np.empty(M, dtype=np.float64)
+    ctx.check(ctx.lib.gdca_plm_conditionals(ctx.h, _lib._p(W), _lib._p(Zf), N, M, int(q), _lib._p(p), _lib._p(nll_k)))
+    return p, nll_k
+
+
+def plm_tallies(W, Z, w, Meff: float, q: int = 21, ctx=None):
+    """The conditional tallies of the pseudo-likelihood on host arrays (gdca_plm_tallies): returns (Pi_c (n,), Pij_c (n, n), nll) of
+    the sequences Z (N, M) with the weights w (M,) and Meff (``compute_weights``'s) under (W, zeros).  With (Pi_d, Pij_d) of
+    ``compute_weighted_frequencies``, 2 (Pij_c - Pij_d) is the gradient of the log pseudo-likelihood by the couplings and
+    1/2 (Pi_c - Pi_d) by W's diagonal."""
+    W, Zf, N, M, w = _plm_args(W, Z, q, w, Meff)
+    n = N * (int(q) - 1)
+    ctx = ctx or default_context()
+    Pi_c, Pij_c, nll = np.empty(n, dtype=np.float64), np.empty((n, n), dtype=np.float64, order="F"), np.empty(1, dtype=np.float64)
+    ctx.check(ctx.lib.gdca_plm_tallies(ctx.h, _lib._p(W), _lib._p(Zf), _lib._p(w), float(Meff), N, M, int(q), _lib._p(Pi_c), _lib._p(Pij_c),
+                                       _lib._p(nll)))
+    return Pi_c, Pij_c, float(nll[0])
+
+
+def plm_learn(W, Z, w, Meff: float, Pi_d, Pij_d, n_iter: int, q: int = 21, eta=None, lam: float = 0.01, ctx=None):
+    """n_iter iterations of pseudo-likelihood ascent on host arrays (gdca_plm_learn): W (n, n) is moved by ``bm_learn``'s step with the
+    conditional tallies of Z (N, M), w, Meff in the place of the sampler's.  ``eta=None`` is 1 / (N + 2 lam).  Returns (W, trace
+    (n_iter, 4)): new arrays; trace holds max |Pi_c - Pi_d|, max |c_c - c_d|, the Pearson correlation of the connected correlations and
+    nll per iteration.  A later call continues the same run bit for bit."""
+    W, Zf, N, M, w = _plm_args(W, Z, q, w, Meff)
+    W = np.array(W, dtype=np.float64, order="F")
+    n = N * (int(q) - 1)
+    Pi_d = np.ascontiguousarray(Pi_d, dtype=np.float64)
+    Pij_d = np.ascontiguousarray(Pij_d, dtype=np.float64)
+    if Pij_d.shape != (n, n) or Pi_d.shape != (n,):
+        raise ArgumentError(f"incompatible sizes: Pij_d must be {n} x {n} and Pi_d have {n} entries")
+    if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
+    eta = 1.0 / (N + 2.0 * float(lam)) if eta is None else eta
+    for v, name in ((eta, "eta"), (lam, "lam")):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (name == "eta" and v == 0):
+            raise ArgumentError(f"invalid {name} value: {v}")
+    ctx = ctx or default_context()
+    trace = np.empty((int(n_iter), 4), dtype=np.float64)
+    ctx.check(ctx.lib.gdca_plm_learn(ctx.h, _lib._p(W), _lib._p(Zf), _lib._p(w), float(Meff), _lib._p(Pi_d), _lib._p(Pij_d), N, M, int(q),
+                                     int(n_iter), float(eta), float(lam), _lib._p(trace)))
+    return W, trace
+
+
 def _double_model_args(mJ, Pi, X, q):
     """the model and the sequences of the double-mutant operators, checked: (mJ, Pi, Xf, N, K)"""
     mJ = np.ascontiguousarray(mJ, dtype=np.float64)

@@ -326,9 +326,12 @@ def bm_learn_tempered_dev(ctx: Context, dW, dPi_d, dPij_d, N: int, q: int, dXr, 
 
 def bm_fit(Z, q: int, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float = 0.0, pseudocount: float = 0.8,
            target_pseudocount: float = 0.0, theta=":auto", init: str = "gaussian", burn=None, stride=None, n_samples: int = 1,
-           beta: float = 1.0, seed: int = 0, gaps: bool = True, scores: bool = False, ctx: Context = None, betas=None, swap_every=None):
+           beta: float = 1.0, seed: int = 0, gaps: bool = True, scores: bool = False, ctx: Context = None, betas=None, swap_every=None,
+           plm_iter: int = 100, plm_lam: float = 0.01):
     """Boltzmann-machine refinement built like scores_stepwise from the device operators.  Z: (N, M) int8.  weights, frequencies,
-    pseudocount, covariance, inverse (the warm start, ``init="gaussian"``; "independent" skips the last two), then n_iter iterations
+    pseudocount, covariance, inverse (the warm start, ``init="gaussian"``; "independent" skips the last two; "plm": the
+    independent-site model moved by ``plm_iter`` pseudo-likelihood iterations, plm_learn_dev at its default step with the penalty
+    ``plm_lam``, towards the same target frequencies), then n_iter iterations
     of bm_learn_dev towards the frequencies at ``target_pseudocount``.  The chains start from the first K sequences of Z (K <= M).
     Returns (W (n, n), trace (n_iter, 4)) and, with ``scores=True``, S = APC(FN(W)) as a third entry.
     ``betas`` (a ladder, the target temperature first; ``beta`` is then not used): the iterations are bm_learn_tempered_dev's, every
@@ -341,8 +344,10 @@ def bm_fit(Z, q: int, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float =
     N, M = Zf.shape
     if q >= 32:
         raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
-    if init not in ("gaussian", "independent"):
-        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\" or \"independent\")")
+    if init not in ("gaussian", "independent", "plm"):
+        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\", \"independent\" or \"plm\")")
+    if init == "plm" and (not isinstance(plm_iter, (int, np.integer)) or plm_iter < 1):
+        raise ArgumentError(f"invalid plm_iter value: {plm_iter} (must be an integer >= 1)")
     if not isinstance(K, (int, np.integer)) or not 1 <= K <= M:
         raise ArgumentError(f"invalid K value: {K} (must be an integer between 1 and the number of sequences, {M})")
     if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
@@ -363,6 +368,9 @@ def bm_fit(Z, q: int, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float =
         dW = potts_from_gaussian_dev(ctx, dmJ, dPi, N, q)
     else:
         dW = DeviceBuffer.from_array(ctx, potts_independent(dPi.download((n,)), N, q))
+        if init == "plm":
+            plm_learn_dev(ctx, dW, dZ, dW_, Meff, dPi_d, dPij_d, N, M, q, int(plm_iter), 1.0 / (N + 2.0 * float(plm_lam)),
+                          float(plm_lam)).free()
     dX = DeviceBuffer.from_array(ctx, np.asfortranarray(Zf[:, :K]))
     if betas is None:
         dtrace = bm_learn_dev(ctx, dW, dPi_d, dPij_d, N, q, dX, K, n_iter, burn, stride, n_samples, eta, lam, beta, seed,
@@ -382,6 +390,150 @@ def bm_fit(Z, q: int, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float =
         out += (dS.download((N, N)),)
         dS.free()
     for b in (dZ, dW_, dPi_t, dPij_t, dPi_d, dPij_d, dW, dX, dtrace):
+        b.free()
+    return out
+
+
+def plm_conditionals_dev(ctx: Context, dW, dZ, N: int, M: int, q: int, dp=None, dnll_k=None):
+    """The conditionals of the M sequences Z (N x M int8) under the Potts model (W, zeros), every array in HBM
+    (gdca_plm_conditionals_dev) -> (dp, dnll_k): p[(c - 1) + q (i + N k)] = P(x_i = c | the rest of sequence k) (the scan's layout,
+    the gap last; q N M f64) and nll_k[k] = -sum_i log P(x_ki | rest)."""
+    dp = dp or DeviceBuffer(ctx, 8 * int(q) * N * M)
+    dnll_k = dnll_k or DeviceBuffer(ctx, 8 * M)
+    ctx.plm_conditionals_dev(_ptr(dW).value, _ptr(dZ).value, N, M, int(q), _ptr(dp).value, _ptr(dnll_k).value)
+    return dp, dnll_k
+
+
+def plm_tally_dev(ctx: Context, dp, dZ, dw, Meff: float, N: int, M: int, q: int, dPi_c=None, dPij_c=None):
+    """The conditional tallies (gdca_plm_tally_dev) of the conditionals p against Z with the weights w -> (dPi_c[n], dPij_c[n x n]),
+    in the frequencies' layout; summed in the fixed order include/gdca.h states (context option PLM_CHUNK)."""
+    n = N * (int(q) - 1)
+    dPi_c = dPi_c or DeviceBuffer(ctx, 8 * n)
+    dPij_c = dPij_c or DeviceBuffer(ctx, 8 * n * n)
+    ctx.plm_tally_dev(_ptr(dp).value, _ptr(dZ).value, _ptr(dw).value, float(Meff), N, M, int(q), _ptr(dPi_c).value, _ptr(dPij_c).value)
+    return dPi_c, dPij_c
+
+
+def plm_tallies_dev(ctx: Context, dW, dZ, dw, Meff: float, N: int, M: int, q: int, dPi_c=None, dPij_c=None, dnll=None):
+    """plm_conditionals_dev and plm_tally_dev fused over slabs of sequences (gdca_plm_tallies_dev; the same bits) ->
+    (dPi_c, dPij_c, dnll): dnll holds one f64, nll = (sum_k w_k nll_k) / Meff.  2 (Pij_c - Pij_d) is the gradient of the log
+    pseudo-likelihood by the couplings, 1/2 (Pi_c - Pi_d) by W's diagonal."""
+    n = N * (int(q) - 1)
+    dPi_c = dPi_c or DeviceBuffer(ctx, 8 * n)
+    dPij_c = dPij_c or DeviceBuffer(ctx, 8 * n * n)
+    dnll = dnll or DeviceBuffer(ctx, 8)
+    ctx.plm_tallies_dev(_ptr(dW).value, _ptr(dZ).value, _ptr(dw).value, float(Meff), N, M, int(q), _ptr(dPi_c).value, _ptr(dPij_c).value,
+                        _ptr(dnll).value)
+    return dPi_c, dPij_c, dnll
+
+
+def plm_learn_dev(ctx: Context, dW, dZ, dw, Meff: float, dPi_d, dPij_d, N: int, M: int, q: int, n_iter: int, eta: float, lam: float = 0.0,
+                  dtrace=None):
+    """n_iter iterations of pseudo-likelihood ascent on W in place with every array in HBM and no host round trip per iteration
+    (gdca_plm_learn_dev): tallies, read-out, bm_update_dev's step.  Returns dtrace (4 x n_iter f64: max |Pi_c - Pi_d|, max |dc|,
+    Pearson, nll per iteration, each of the W the iteration started from).  A later call continues the same run bit for bit."""
+    dtrace = dtrace or DeviceBuffer(ctx, 32 * max(int(n_iter), 1))
+    ctx.plm_learn_dev(_ptr(dW).value, _ptr(dZ).value, _ptr(dw).value, float(Meff), _ptr(dPi_d).value, _ptr(dPij_d).value, N, M, int(q),
+                      int(n_iter), float(eta), float(lam), _ptr(dtrace).value)
+    return dtrace
+
+
+PLM_GROW = 1.2  # the factor of plm_learn_adaptive_dev
+
+
+def plm_penalty(W, N: int, q: int) -> float:
+    """sum_{i<j} |W_ij|^2 of the couplings of W (n, n): the squares of the entries below the diagonal blocks, summed by numpy's
+    ``sum`` of the masked square (what the adaptive rule compares; tests/plm_model.py takes the same sum)."""
+    s = int(q) - 1
+    site = np.arange(N * s) // s
+    return float(np.sum(np.where(site[:, None] > site[None, :], np.asarray(W) ** 2, 0.0)))
+
+
+def plm_learn_adaptive_dev(ctx: Context, dW, dZ, dw, Meff: float, dPi_d, dPij_d, N: int, M: int, q: int, n_iter: int, eta: float,
+                           lam: float = 0.0, state=None):
+    """Pseudo-likelihood ascent with an adapted step, driven from the host over the operator forms (bm_learn_tempered_dev's pattern;
+    one download of W and of five f64 an iteration).  THE RULE, deterministic: every iteration evaluates the tallies and
+    f = nll + lam * plm_penalty(W) at the current W.  If there is no accepted point yet, or f < f_acc: the point is ACCEPTED -- eta
+    grows by PLM_GROW (not at the first point), f_acc = f, W is kept in a device copy --; f == f_acc: accepted, eta stays; then the
+    step bm_update_dev(eta).  If f > f_acc (a rise; a NaN counts as one): W is restored from the copy, eta is halved, nothing else --
+    the next iteration evaluates the restored point again.  So a step size is never kept after a rise.
+    Returns (trace (n_iter, 4) as plm_learn_dev's, etas (n_iter,): the eta each iteration stepped with, 0.0 where it restored,
+    state): ``state`` (eta, f_acc, the device copy) passed to a later call continues the run to the same bits."""
+    n = N * (int(q) - 1)
+    n_iter = int(n_iter)
+    eta, f_acc, dsave = (float(eta), None, DeviceBuffer(ctx, 8 * n * n)) if state is None else (state["eta"], state["f_acc"], state["dsave"])
+    dPi_c, dPij_c, dnll, dout = DeviceBuffer(ctx, 8 * n), DeviceBuffer(ctx, 8 * n * n), DeviceBuffer(ctx, 8), DeviceBuffer(ctx, 32)
+    trace, etas = np.empty((n_iter, 4)), np.zeros(n_iter)
+    for it in range(n_iter):
+        plm_tallies_dev(ctx, dW, dZ, dw, Meff, N, M, q, dPi_c, dPij_c, dnll)
+        bm_readout_dev(ctx, dPi_d, dPij_d, dPi_c, dPij_c, N, q, dout)
+        trace[it] = dout.download((4,))
+        nll = float(dnll.download((1,))[0])
+        trace[it, 3] = nll
+        f = nll + float(lam) * plm_penalty(dW.download((n, n)), N, q) if lam else nll
+        if f_acc is None or f <= f_acc:
+            if f_acc is not None and f < f_acc:
+                eta *= PLM_GROW
+            f_acc = f
+            dsave.copy_from(dW, 8 * n * n)
+            bm_update_dev(ctx, dW, dPij_d, dPij_c, N, q, eta, lam)
+            etas[it] = eta
+        else:
+            dW.copy_from(dsave, 8 * n * n)
+            eta *= 0.5
+    for b in (dPi_c, dPij_c, dnll, dout):
+        b.free()
+    return trace, etas, {"eta": eta, "f_acc": f_acc, "dsave": dsave}
+
+
+def plm_fit(Z, q: int, n_iter: int, lam: float = 0.01, eta=None, init: str = "independent", adapt: bool = False, pseudocount: float = 0.8,
+            target_pseudocount: float = 0.0, theta=":auto", scores: bool = False, ctx: Context = None):
+    """The pseudo-likelihood fit built like bm_fit from the device operators.  Z: (N, M) int8.  weights, frequencies, the start
+    (``init="independent"``: the independent-site model of the frequencies at ``pseudocount``; "gaussian": pseudocount, covariance,
+    inverse, potts_from_gaussian_dev), then n_iter iterations of plm_learn_dev -- ``adapt=True``: of plm_learn_adaptive_dev -- with the
+    family's frequencies at ``target_pseudocount`` as the data's side of the gradient.  ``eta=None`` is 1 / (N + 2 lam).
+    Returns (W (n, n), trace (n_iter, 4)) and, with ``scores=True``, S = APC(FN(W)) as a third entry."""
+    from .dcautils import potts_independent
+
+    Zf = _zf(Z)
+    N, M = Zf.shape
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    if init not in ("gaussian", "independent"):
+        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\" or \"independent\")")
+    if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
+    if not isinstance(lam, (int, float, np.integer, np.floating)) or not np.isfinite(lam) or lam < 0:
+        raise ArgumentError(f"invalid lam value: {lam}")
+    eta = 1.0 / (N + 2.0 * float(lam)) if eta is None else eta
+    if not isinstance(eta, (int, float, np.integer, np.floating)) or not np.isfinite(eta) or eta <= 0:
+        raise ArgumentError(f"invalid eta value: {eta}")
+    ctx = ctx or default_context()
+    n = N * (q - 1)
+    dZ = DeviceBuffer.from_array(ctx, Zf)
+    dw, Meff, th, thr = compute_weights_dev(ctx, dZ, N, M, theta)
+    dPi_t, dPij_t = compute_weighted_frequencies_dev(ctx, dZ, N, M, q, dw, Meff)
+    dPi_d, dPij_d = add_pseudocount_dev(ctx, dPi_t, dPij_t, N, q, target_pseudocount, DeviceBuffer(ctx, 8 * n), DeviceBuffer(ctx, 8 * n * n))
+    dPi, dPij = add_pseudocount_dev(ctx, dPi_t, dPij_t, N, q, pseudocount)
+    if init == "gaussian":
+        dmJ = compute_C_dev(ctx, dPi, dPij, n, dC=dPij)
+        inv_cholesky_dev(ctx, dmJ, n)
+        dW = potts_from_gaussian_dev(ctx, dmJ, dPi, N, q)
+    else:
+        dW = DeviceBuffer.from_array(ctx, potts_independent(dPi.download((n,)), N, q))
+    if adapt:
+        trace, _, state = plm_learn_adaptive_dev(ctx, dW, dZ, dw, Meff, dPi_d, dPij_d, N, M, q, n_iter, float(eta), float(lam))
+        state["dsave"].free()
+    else:
+        dtrace = plm_learn_dev(ctx, dW, dZ, dw, Meff, dPi_d, dPij_d, N, M, q, n_iter, float(eta), float(lam))
+        trace = dtrace.download((int(n_iter), 4), order="C")
+        dtrace.free()
+    out = (dW.download((n, n)), trace)
+    if scores:
+        dS = correct_APC_dev(ctx, compute_FN_dev(ctx, dW, N, q), N)
+        out += (dS.download((N, N)),)
+        dS.free()
+    for b in (dZ, dw, dPi_t, dPij_t, dPi_d, dPij_d, dW):
         b.free()
     return out
 

@@ -531,11 +531,12 @@ def gDCA_sample_tempered(filename: str, starts=None, betas=(1.0,), swap_every=No
 def gDCA_bm(filename: str, n_iter: int, K: int = 1024, eta: float = 1.0, lam: float = 0.0, target_pseudocount: float = 0.0,
             init: str = "gaussian", burn=None, stride=None, n_samples: int = 1, beta: float = 1.0, seed: int = 0, gaps: bool = True,
             scores: bool = False, min_separation: int = 5, pseudocount: float = 0.8, theta=":auto", max_gap_fraction: float = 0.9,
-            remove_dups: bool = False, ctx=None, betas=None, swap_every=None, **kw):
+            remove_dups: bool = False, ctx=None, betas=None, swap_every=None, plm_iter: int = 100, plm_lam: float = 0.01, **kw):
     """Boltzmann-machine refinement (bmDCA) of the model gDCA fits to the alignment in ``filename``: the Potts model the Metropolis
     chains of ``gDCA_sample`` draw from is moved until the one- and two-site frequencies of its samples are the family's.  Built from
     the device operators like ``gDCA_stepwise``: weights, frequencies, pseudocount, covariance, inverse -- the Gaussian warm start at
-    ``pseudocount`` (``init="gaussian"``; ``"independent"``: the independent-site model, no inverse) --, then ``n_iter`` iterations of
+    ``pseudocount`` (``init="gaussian"``; ``"independent"``: the independent-site model, no inverse; ``"plm"``: the independent-site
+    model after ``plm_iter`` pseudo-likelihood iterations with the penalty ``plm_lam``, ``gDCA_plm``'s loop) --, then ``n_iter`` iterations of
     sample, tally, update (``devops.bm_learn_dev``: nothing crosses to the host inside the loop) towards the family's frequencies at
     ``target_pseudocount``.  ``K`` persistent chains start from the first K sequences of the alignment (fewer if it has fewer);
     ONE SWEEP IS N PROPOSALS: every iteration runs ``burn`` proposals (default 10 N) and tallies ``n_samples`` states ``stride`` (default
@@ -560,8 +561,8 @@ def gDCA_bm(filename: str, n_iter: int, K: int = 1024, eta: float = 1.0, lam: fl
     check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", min_separation)
     if not (0 <= target_pseudocount <= 1):
         raise ArgumentError(f"invalid target_pseudocount value: {target_pseudocount} (must be between 0 and 1)")
-    if init not in ("gaussian", "independent"):
-        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\" or \"independent\")")
+    if init not in ("gaussian", "independent", "plm"):
+        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\", \"independent\" or \"plm\")")
     if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
         raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
     if not isinstance(K, (int, np.integer)) or K < 1:
@@ -577,11 +578,61 @@ def gDCA_bm(filename: str, n_iter: int, K: int = 1024, eta: float = 1.0, lam: fl
         betas, swap_every = _temper_args(N, betas, swap_every, 10 * N if burn is None else int(burn), N if stride is None else int(stride))
     out = devops.bm_fit(Z, q, int(n_iter), K=min(int(K), Z.shape[1]), eta=eta, lam=lam, pseudocount=float(pseudocount),
                         target_pseudocount=float(target_pseudocount), theta=theta, init=init, burn=burn, stride=stride,
-                        n_samples=n_samples, beta=beta, seed=seed, gaps=gaps, scores=scores, ctx=ctx, betas=betas, swap_every=swap_every)
+                        n_samples=n_samples, beta=beta, seed=seed, gaps=gaps, scores=scores, ctx=ctx, betas=betas, swap_every=swap_every,
+                        plm_iter=plm_iter, plm_lam=plm_lam)
     if scores:
         from .dcautils import compute_ranking
 
         return out[:-1] + (compute_ranking(out[-1], int(min_separation)),)
+    return out
+
+
+def gDCA_plm(filename: str, n_iter: int, lam: float = 0.01, eta=None, init: str = "independent", adapt: bool = False,
+             scores: bool = False, target_pseudocount: float = 0.0, min_separation: int = 5, pseudocount: float = 0.8, theta=":auto",
+             max_gap_fraction: float = 0.9, remove_dups: bool = False, ctx=None, **kw):
+    """Pseudo-likelihood fit (plmDCA) of a Potts model to the alignment in ``filename``: gradient ascent on the reweighted log
+    pseudo-likelihood (1 / Meff) sum_k w_k sum_i log P(x_ki | the rest of sequence k) minus ``lam`` times the squared couplings, with
+    no sampler -- the conditionals are the softmax of ``mutation_scan``'s site potentials, their tally against the alignment is the
+    model's side of the gradient (``devops.plm_learn_dev``: nothing crosses to the host inside the loop).  Built from the device
+    operators like ``gDCA_bm``: weights, frequencies, the start at ``pseudocount`` (``init="independent"``: the independent-site
+    model; ``"gaussian"``: the Gaussian fit read as a Potts model), then ``n_iter`` iterations towards the family's frequencies at
+    ``target_pseudocount`` (0: the true ones, the exact gradient).
+
+    ``eta=None`` selects 1 / (N + 2 lam), the step at which the penalised objective cannot rise in exact arithmetic.
+    ``adapt=True`` drives the loop from Python (``devops.plm_learn_adaptive_dev``) with this deterministic rule: every iteration
+    evaluates f = nll + lam sum_{i<j} |W_ij|^2 at the current W; where f fell below the last accepted value eta grows by 1.2, where
+    it is equal eta stays, and the step is taken; where f rose W is restored from a device copy and eta is halved, so no step size is
+    kept after a rise.
+
+    Returns ``(W, trace)``: W (n, n) is the model as the pair (W, zeros) every read-out takes in the place of (mJ, Pi); ``trace``
+    (n_iter, 4) holds max |Pi_c - Pi_d|, max |c_c - c_d|, the Pearson correlation of the connected correlations and nll, each at the
+    W the iteration started from.  With ``scores=True`` a third entry: the ranking of APC(FN(W)) at ``min_separation``, the plmDCA
+    contact score."""
+    from . import devops
+
+    if "θ" in kw:
+        theta = kw.pop("θ")
+    if kw:
+        raise TypeError(f"gDCA_plm() got unexpected keyword arguments {sorted(kw)}")
+    check_arguments(filename, pseudocount, theta, max_gap_fraction, ":frob", min_separation)
+    if not (0 <= target_pseudocount <= 1):
+        raise ArgumentError(f"invalid target_pseudocount value: {target_pseudocount} (must be between 0 and 1)")
+    if init not in ("gaussian", "independent"):
+        raise ArgumentError(f"invalid init value: {init} (must be \"gaussian\" or \"independent\")")
+    if not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ArgumentError(f"invalid n_iter value: {n_iter} (must be an integer >= 1)")
+    Z = read_fasta_alignment(filename, max_gap_fraction)
+    if remove_dups:
+        Z, _ = remove_duplicate_sequences(Z)
+    q = int(Z.max())
+    if q >= 32:
+        raise RuntimeError(f"parameter q={q} is too big (max 31 is allowed)")
+    out = devops.plm_fit(Z, q, int(n_iter), lam=lam, eta=eta, init=init, adapt=bool(adapt), pseudocount=float(pseudocount),
+                         target_pseudocount=float(target_pseudocount), theta=theta, scores=scores, ctx=ctx)
+    if scores:
+        from .dcautils import compute_ranking
+
+        return out[0], out[1], compute_ranking(out[2], int(min_separation))
     return out
 
 

@@ -186,7 +186,10 @@ gdca_status gdca_ctx_set_timing(gdca_ctx *ctx, int32_t enabled);
  * kernels takes, 0 = the rule [default: a ~256 MB buffer]; a count above the rule's is cut to it: the same bits whatever it is); WALK_TABLE (auto | lds | hbm: where the greedy walk keeps a
  * sequence's table of site potentials -- auto [default]: in LDS where it fits, else in HBM; lds with a table that does not fit makes the
  * walk fail with GDCA_EINVAL; the same bits wherever it is; the Metropolis chains place their table by the same rule and the same option);
- * SAMPLE_CHUNK (proposals one launch of the Metropolis kernel takes, 0 = the rule [default]: 65536; the same bits whatever it is).  The schedule switches change results
+ * SAMPLE_CHUNK (proposals one launch of the Metropolis kernel takes, 0 = the rule [default]: 65536; the same bits whatever it is);
+ * PLM_CHUNK (sequences a block of the pseudo-likelihood tally adds in one go, 0 = the rule [default]: 512; it FIXES THE ORDER of the tally's
+ * sums, so another value gives other bits); PLM_SLAB (sequences whose conditionals are held at a time, rounded up to whole blocks, 0 = the
+ * rule [default: a ~256 MB table]; the same bits whatever it is).  The schedule switches change results
  * at rounding level at most (another summation order); REFINE improves an ill-conditioned inverse.  GDCA_EINVAL: unknown key
  * or unusable value. */
 gdca_status gdca_ctx_set_option(gdca_ctx *ctx, const char *key, const char *value);
@@ -258,6 +261,8 @@ void *gdca_dbuf_ptr(const gdca_dbuf *buf);
 uint64_t gdca_dbuf_bytes(const gdca_dbuf *buf);
 gdca_status gdca_dbuf_upload(gdca_ctx *ctx, gdca_dbuf *buf, uint64_t offset, const void *host, uint64_t bytes);
 gdca_status gdca_dbuf_download(gdca_ctx *ctx, const gdca_dbuf *buf, uint64_t offset, void *host, uint64_t bytes);
+/* the first `bytes` bytes of src into dst, device to device, enqueued on ctx's stream behind what has been enqueued (not synchronous) */
+gdca_status gdca_dbuf_copy(gdca_ctx *ctx, gdca_dbuf *dst, const gdca_dbuf *src, uint64_t bytes);
 
 /* ---- operator level, device-resident: the statements of src/GaussDCA.jl:28-42 one by one with every array in HBM --
  * Same meaning as the host-pointer operators below (which are "upload, call the _dev form, download"); array
@@ -872,6 +877,62 @@ gdca_status gdca_bm_learn_dev(gdca_ctx *ctx, double *W_dev, const double *Pi_d_d
                               int8_t *X_dev, int32_t K, const int8_t *mask_dev, int32_t flags, double beta, uint64_t seed, uint64_t iter0,
                               int32_t n_iter, int32_t burn, int32_t stride, int32_t n_samples, double eta, double lambda, double *trace_dev,
                               int8_t *Xs_last_dev);
+
+/* ---- Pseudo-likelihood fit of the Potts model (plmDCA) --------------------------------------------------------------------------------
+ * The container is the Boltzmann machine's: (W, 0) in mJ's layout, the gap the reference state.  With s = q - 1, r(i, c) = i s + c - 1,
+ * weights w_k and Meff as gdca_compute_weights* returns them, the objective is
+ *     F(W) = (1 / Meff) sum_k w_k sum_i log P(x_ki | x_k,-i ; W),    nll = -F,
+ * P(x_i = c | rest) = exp(-V(x; i, c)) / sum_c' exp(-V(x; i, c')) with the mutation stage's site potentials V (GDCA_MUT_POTENTIAL, the
+ * gap's V = +0.0).  With p_k[r(i, a)] = P(x_i = a | x_k,-i) the CONDITIONAL TALLIES, in the frequencies' own layout, are
+ *     Q[r, c]     = sum_{k : x_k,site(c) = sym(c)} w_k p_k[r]                 Pi_c[r]     = (sum_k w_k p_k[r]) / Meff
+ *     Pij_c[r, c] = (Q[r, c] + Q[c, r]) / (2 Meff) outside the diagonal blocks, Pij_c[r, r] = Pi_c[r], +0.0 elsewhere inside one,
+ * and dF/dW[r, c] = 2 (Pij_c - Pij_d)[r, c] (the symmetric pair one parameter), dF/dW[r, r] = 1/2 (Pi_c - Pi_d)[r] with (Pi_d, Pij_d)
+ * gdca_frequencies*'s of the family.  So gdca_bm_update_dev(W, Pij_d, Pij_c, eta, lambda) IS an ascent step on F - lambda sum_{i<j}
+ * |W_ij|^2 (fields at rate eta, couplings at eta / 2 in natural parameters), and gdca_bm_readout_dev(Pi_d, Pij_d, Pi_c, Pij_c) the fit
+ * read-out.  eta <= 1 / (N + 2 lambda) keeps nll + lambda sum |W_ij|^2 from rising in exact arithmetic.
+ *
+ * gdca_plm_conditionals_dev: p (the scan's layout: p[(c - 1) + q (i + N k)], c = 1 .. q, the gap's probability last -- q N M doubles) and
+ * nll_k (M) of the M sequences Z (N x M int8) under (W, zeros).  The potentials are gdca_mutation_scan_dev's bits; then per (k, i), f64,
+ * one rounding an operation:  m = min_c V_c;  e_c = exp(m - V_c);  Zs = e_1 + .. + e_q added to +0.0 with c ascending;  p_c = e_c / Zs;
+ * l_ki = (V[x_ki] - m) + log(Zs);  nll_k = the l_ki added to +0.0 with i ascending BY ONE THREAD.  exp and log are the device library's:
+ * their bits are not pinned (the tests hold p and l to an ulp bar).  The largest e_c is 1, so nothing overflows whatever V spans.
+ *
+ * gdca_plm_tally_dev: (p, Z, w, Meff) -> (Pi_c, Pij_c).  ORDER-FIXED, no floating-point atomics: a = w_k p_k[r] is one rounded product;
+ * the sequences are cut into blocks of PLM_CHUNK (context option, default 512); inside a block an entry's terms are added to +0.0 with
+ * k ascending (only the sequences that select the entry: the others add nothing); the blocks' partials are added to +0.0 with the block
+ * index ascending; Pi_c's sum takes every sequence the same way.  Then one addition of Q and its transpose (it commutes: Pij_c is
+ * symmetric to the bit), 2 Meff exact, ONE division an entry.  The order depends on N, q, M and PLM_CHUNK alone: another PLM_CHUNK,
+ * other bits.
+ *
+ * gdca_plm_tallies_dev: the two fused over slabs of sequences (context option PLM_SLAB; a slab is whole blocks, so the bits do not
+ * depend on it), p never held beyond a slab.  nll = (sum_k w_k nll_k) / Meff: the rounded products w_k nll_k of k = t, t + 256, .. added
+ * to +0.0 ascending into partial t, the 256 partials folded by a halving tree (t and t + 128, t and t + 64, ..), one division.
+ *
+ * gdca_plm_learn_dev: per iteration t = 0 .. n_iter - 1 it enqueues the tallies; gdca_bm_readout_dev's read-out into trace[4 t ..] with
+ * out[3] = nll; gdca_bm_update_dev's step on W.  RULE: n_iter iterations equal a and n_iter - a iterations chained through W, and equal
+ * the caller's chain of the operator forms, bit for bit in W and trace, whatever PLM_SLAB.  The weights' range is checked before the
+ * first iteration (one round trip a call), the sequences' flags are read once at the end.
+ * GDCA_EINVAL, nothing run, every output and W untouched: a null pointer; q outside 2 .. 31; N or M < 1; Meff not positive and finite; a
+ * weight outside [0, 1]; eta <= 0, lambda < 0, either NaN or infinite; n_iter < 1; W (p for the tally) aliasing an output.  A byte of Z
+ * outside 1 .. q is reported as gdca_mutation_scan_dev reports it (the outputs are unspecified then).  New symbols only: gdca_stats and
+ * gdca_params are unchanged. */
+gdca_status gdca_plm_conditionals_dev(gdca_ctx *ctx, const double *W_dev, const int8_t *Z_dev, int32_t N, int32_t M, int32_t q, double *p_dev,
+                                      double *nll_k_dev);
+gdca_status gdca_plm_tally_dev(gdca_ctx *ctx, const double *p_dev, const int8_t *Z_dev, const double *w_dev, double Meff, int32_t N, int32_t M,
+                               int32_t q, double *Pi_c_dev, double *Pij_c_dev);
+gdca_status gdca_plm_tallies_dev(gdca_ctx *ctx, const double *W_dev, const int8_t *Z_dev, const double *w_dev, double Meff, int32_t N,
+                                 int32_t M, int32_t q, double *Pi_c_dev, double *Pij_c_dev, double *nll_dev);
+gdca_status gdca_plm_learn_dev(gdca_ctx *ctx, double *W_dev, const int8_t *Z_dev, const double *w_dev, double Meff, const double *Pi_d_dev,
+                               const double *Pij_d_dev, int32_t N, int32_t M, int32_t q, int32_t n_iter, double eta, double lambda,
+                               double *trace_dev);
+/* ... with host pointers: upload, the _dev form, download (W in place) */
+gdca_status gdca_plm_conditionals(gdca_ctx *ctx, const double *W, const int8_t *Z, int32_t N, int32_t M, int32_t q, double *p, double *nll_k);
+gdca_status gdca_plm_tally(gdca_ctx *ctx, const double *p, const int8_t *Z, const double *w, double Meff, int32_t N, int32_t M, int32_t q,
+                           double *Pi_c, double *Pij_c);
+gdca_status gdca_plm_tallies(gdca_ctx *ctx, const double *W, const int8_t *Z, const double *w, double Meff, int32_t N, int32_t M, int32_t q,
+                             double *Pi_c, double *Pij_c, double *nll);
+gdca_status gdca_plm_learn(gdca_ctx *ctx, double *W, const int8_t *Z, const double *w, double Meff, const double *Pi_d, const double *Pij_d,
+                           int32_t N, int32_t M, int32_t q, int32_t n_iter, double eta, double lambda, double *trace);
 
 /* ---- operator level (host pointers): what the DCAUtils-named wrappers bind -------------- */
 /* A host-pointer form on a context with an enqueued run (gdca_run_dev_async, gdca_run_ranked_async, ...) is refused (GDCA_EINVAL)
