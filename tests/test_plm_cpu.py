@@ -1,6 +1,7 @@
 """The pseudo-likelihood fit without a GPU: tests/plm_model.py against finite differences, against the exact toy (the gradient
 vanishes at the true parameters, L-BFGS lands on them), the loop's monotonicity at the default step, the adaptive rule, the measured
-softmax bars the GPU test uses, and the exported symbols and bindings."""
+softmax bars the GPU test uses, the inputs of the GPU tests at width with the conditions under which they can tell one order of
+summation from another, and the exported symbols and bindings."""
 import ctypes
 import os
 
@@ -220,7 +221,83 @@ def test_adaptive_rule_splits_and_never_keeps_a_step_after_a_rise():
     assert acc[-1] < acc[0]
 
 
-# ---- 5. exports and bindings ------------------------------------------------------------------------------------------------------------------------
+# ---- 5. the cases at width can tell one order from another (the GPU tests of test_gpu_plm_width.py run on these inputs) ----------------------------
+# (N, q, M, PLM_CHUNK; 0: the rule, blocks of pm.CHUNK_RULE): what each one reaches stands at test_gpu_plm_width.test_tally_at_width
+WIDTH_TALLY_CASES = [(5, 21, 1029, 0), (7, 5, 517, 0), (6, 2, 600, 0), (3, 31, 100, 24), (13, 21, 96, 32), (4, 5, 49, 16), (4, 5, 48, 16),
+                     (53, 21, 529, 0)]
+WIDTH_NLL_CASES = [(5, 21, 1029), (7, 5, 517), (5, 21, 257), (5, 21, 256)]
+WIDTH_FIT_FAMILY = (12, 1100, 5, 11)  # synth_family's (N, M, q, seed): three blocks of the rule
+
+
+def width_case(N, q, M):
+    """(W, Z, w, Meff) as test_gpu_plm.test_tally_bit_for_bit builds them: seed 100 N + q + M, weights 2^-40 apart (the order of the
+    additions shows in the last bits) with one zero and one 1"""
+    rng = np.random.default_rng(100 * N + q + M)
+    W = container(rng, N, q, 0.7)
+    Z, _, _ = family(rng, N, q, M)
+    w = 0.5 + np.arange(M) * 2.0 ** -40
+    w[1] = 0.0
+    w[M - 1] = 1.0
+    return W, Z, w, float(w.sum())
+
+
+def differing(a, b):
+    return int((np.ascontiguousarray(a).view(np.uint64) != np.ascontiguousarray(b).view(np.uint64)).sum())
+
+
+@pytest.mark.parametrize("N,q,M,chunk", WIDTH_TALLY_CASES)
+def test_width_cases_tell_the_blocks_from_one_block(N, q, M, chunk):
+    """With numpy's own p: the ordered tally cut into the case's blocks is not the bits of the same tally summed as ONE block, so a
+    device that added the blocks' partials in another place, or took another block length, would show."""
+    W, Z, w, Meff = width_case(N, q, M)
+    assert Z.shape == (N, M) and int(Z.max()) <= q and w.min() == 0.0 and w.max() == 1.0
+    p = pm.conditionals(W, Z, q, np.float64)[0]
+    Pi_b, Pij_b = pm.tallies_ordered(p, Z, w, Meff, q, chunk or pm.CHUNK_RULE)
+    Pi_1, Pij_1 = pm.tallies_ordered(p, Z, w, Meff, q, M)
+    d = differing(Pij_b, Pij_1)
+    print("N=%d q=%d M=%d chunk=%d: %d entries of Pij differ from the one-block sum's, %d of Pi" % (N, q, M, chunk, d, differing(Pi_b, Pi_1)))
+    assert d > 0
+    assert np.array_equal(Pij_b, Pij_b.T) and np.array_equal(np.diagonal(Pij_b), Pi_b)
+
+
+@pytest.mark.parametrize("N,q,M", WIDTH_NLL_CASES)
+def test_width_cases_tell_the_strided_sum_from_the_ascending_one(N, q, M):
+    """nll in the device's order (256 strided partials, the halving tree) is not the bits of the products added one by one with k
+    ascending: a wrong stride, start or tree would show."""
+    W, Z, w, Meff = width_case(N, q, M)
+    nll_k = pm.conditionals(W, Z, q, np.float64)[2]
+    prod = w * nll_k
+    asc = np.float64(0.0)
+    for v in prod:
+        asc = asc + v
+    ordered = float(pm.nll_ordered(w, nll_k, Meff))
+    print("M=%d: nll ordered %.17g, ascending %.17g" % (M, ordered, float(asc / np.float64(Meff))))
+    assert ordered != float(asc / np.float64(Meff))
+
+
+def test_width_fit_family_is_three_blocks_of_the_rule():
+    """synth_family(12, 1100, 5, 11): every symbol of the alphabet occurs (q is read off Z.max()), the sequences number more than two
+    blocks of the rule, plm_fit takes them as they are (it removes no duplicates: the chain of the operators gets the same M), and
+    the reweighting has neighbours to count: weights below 1."""
+    from gaussdca.jl_amd.dcautils import remove_duplicate_sequences
+    from gaussdca.jl_amd.synth import synth_family
+    from oracle import gdca_oracle as o
+
+    N, M, q, seed = WIDTH_FIT_FAMILY
+    Zo = synth_family(N, M, q, seed)
+    Z = np.asfortranarray(Zo.T)
+    assert Z.shape == (N, M) and int(Z.max()) == q and int(Z.min()) == 1 and M > 2 * pm.CHUNK_RULE
+    Zu, _ = remove_duplicate_sequences(Z)
+    wts, Meff, _, _ = o.compute_weights(np.ascontiguousarray(Zo), "auto")
+    print("synth family: %d sequences, %d distinct, Meff %.2f, %d weights below 1" % (M, Zu.shape[1], Meff, int((wts < 1).sum())))
+    assert Zu.shape[1] <= M and (wts < 1).any() and wts.max() <= 1 and Meff < M
+    # theta reaches the weights through floor(theta N) alone: :auto's theta and 0.3 are the same neighbourhood of 3 sites here (a fit
+    # at theta = 0.3 repeats the default's bits), 0.2 is another
+    thr = {th: o.compute_weights(np.ascontiguousarray(Zo), th)[3] for th in ("auto", 0.3, 0.2)}
+    assert thr == {"auto": 3, 0.3: 3, 0.2: 2}, thr
+
+
+# ---- 6. exports and bindings ------------------------------------------------------------------------------------------------------------------------
 def test_exports_and_bindings():
     import gaussdca.jl_amd as g
     from gaussdca.jl_amd import _lib, devops
