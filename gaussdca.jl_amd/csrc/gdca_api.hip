@@ -1281,13 +1281,34 @@ static gdca_status double_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
     return check_launch(ctx, "double-mutant scan");
 }
 
-// Where the walk keeps a sequence's table (option WALK_TABLE): in LDS where it fits, unless HBM is asked for; false: LDS asked for
+// Where the walk keeps a sequence's table (option WALK_TABLE): in LDS where it fits, unless HBM is asked for; an error: LDS asked for
 // and the table does not fit
-static bool walk_placement(const gdca_ctx *ctx, int N, int q, bool *in_lds)
+static gdca_status walk_placement(gdca_ctx *ctx, int N, int q, bool *in_lds)
 {
     const bool fits = gdca_walk_table_fits(N, q);
     *in_lds = ctx->tune.walk_table == 2 ? false : fits;
-    return fits || ctx->tune.walk_table != 1;
+    if (!fits && ctx->tune.walk_table == 1) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    return GDCA_OK;
+}
+
+// What the walk and the chains open with: the tables' placement, their room -- *V as the caller gave it or, where that is nullptr,
+// ctx->DMd sized for the K sequences X (N x K) --, and the sequences' site potentials in it through the mutation stage (ctx->Xg: the
+// K starts packed, as the first launch reads them)
+static gdca_status table_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, double **V, bool *in_lds)
+{
+    CHK(walk_placement(ctx, m.N, m.q, in_lds));
+    if (!*V) {
+        CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)K * sizeof(double)));
+        *V = (double *)ctx->DMd.p;
+    }
+    return mutation_stage(ctx, m, X_dev, K, GDCA_MUT_POTENTIAL, *V);
+}
+
+// the end of the chains' launch that starts at proposal t0: at most SAMPLE_CHUNK proposals
+static int chunk_end(const gdca_ctx *ctx, int t0, int n_steps)
+{
+    const int chunk = ctx->tune.sample_chunk > 0 ? ctx->tune.sample_chunk : GDCA_SAMPLE_CHUNK_RULE;
+    return n_steps - t0 > chunk ? t0 + chunk : n_steps;
 }
 
 // The greedy walk (k_walk.hip) of the K sequences X (N x K) under the model m: their site potentials through the mutation stage into
@@ -1296,13 +1317,8 @@ static bool walk_placement(const gdca_ctx *ctx, int N, int q, bool *in_lds)
 static gdca_status walk_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, const walk_request &w)
 {
     bool in_lds = false;
-    if (!walk_placement(ctx, m.N, m.q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
     double *V = w.V;
-    if (!V) {
-        CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)K * sizeof(double)));
-        V = (double *)ctx->DMd.p;
-    }
-    CHK(mutation_stage(ctx, m, X_dev, K, GDCA_MUT_POTENTIAL, V));
+    CHK(table_stage(ctx, m, X_dev, K, &V, &in_lds));
     HIPCHK(gdca_launch_greedy_walk(ctx->stream, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K, w.mask, w.flags, w.min_gain,
                                    w.max_steps, V, in_lds, w.V != nullptr, w.Xout, w.steps, w.dE_sum, w.path, w.dE_path));
     return check_launch(ctx, "greedy walk");
@@ -1314,18 +1330,12 @@ static gdca_status walk_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *
 static gdca_status sample_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, const sample_request &r)
 {
     bool in_lds = false;
-    if (!walk_placement(ctx, m.N, m.q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
     double *V = r.V;
-    if (!V) {
-        CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)K * sizeof(double)));
-        V = (double *)ctx->DMd.p;
-    }
     CHK(ensure(ctx, ctx->SMst, gdca_sample_state_bytes(m.N, K)));
-    CHK(mutation_stage(ctx, m, X_dev, K, GDCA_MUT_POTENTIAL, V));
-    const int n_steps = r.plan.burn + r.plan.n_samples * r.plan.stride;
-    const int chunk = ctx->tune.sample_chunk > 0 ? ctx->tune.sample_chunk : GDCA_SAMPLE_CHUNK_RULE;
+    CHK(table_stage(ctx, m, X_dev, K, &V, &in_lds));
+    const int n_steps = r.plan.chain.n_steps();
     for (int t0 = 0; t0 < n_steps;) {
-        const int t1 = n_steps - t0 > chunk ? t0 + chunk : n_steps;
+        const int t1 = chunk_end(ctx, t0, n_steps);
         HIPCHK(gdca_launch_sample(ctx->stream, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K, r.plan, t0, t1, V, in_lds,
                                   ctx->SMst.p));
         t0 = t1;
@@ -1340,7 +1350,7 @@ static gdca_status sample_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
 static gdca_status temper_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *X_dev, int K, const temper_request &r)
 {
     bool in_lds = false;
-    if (!walk_placement(ctx, m.N, m.q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    CHK(walk_placement(ctx, m.N, m.q, &in_lds));  // (before anything is enqueued; table_stage asks again)
     const gdca_temper_plan &plan = r.plan;
     const int R = plan.R, G = K * R;
     hipStream_t s = ctx->stream;
@@ -1350,22 +1360,20 @@ static gdca_status temper_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
         gdca_launch_temper_replicate(s, X_dev, m.N, K, R, (int8_t *)ctx->TMx.p);
         Xr = (const int8_t *)ctx->TMx.p;
     }
-    CHK(ensure(ctx, ctx->DMd, (size_t)m.q * (size_t)m.N * (size_t)G * sizeof(double)));
     CHK(ensure(ctx, ctx->TMst, gdca_temper_state_bytes(m.N, G)));
-    double *V = (double *)ctx->DMd.p;
     void *state = ctx->TMst.p;
     CHK(energy_stage(ctx, m, Xr, G, gdca_temper_E0(state, G)));
-    CHK(mutation_stage(ctx, m, Xr, G, GDCA_MUT_POTENTIAL, V));  // (ctx->Xg: the G starts packed, as the first launch reads them)
+    double *V = nullptr;  // (ctx->DMd: q N K R doubles)
+    CHK(table_stage(ctx, m, Xr, G, &V, &in_lds));
     gdca_launch_temper_init(s, plan, K, state, (gdca_dev_scalars *)ctx->sc.p);
-    const int n_steps = plan.burn + plan.n_samples * plan.stride, every = plan.swap_every;
-    const int chunk = ctx->tune.sample_chunk > 0 ? ctx->tune.sample_chunk : GDCA_SAMPLE_CHUNK_RULE;
+    const int n_steps = plan.chain.n_steps(), every = plan.swap_every;
     for (int t0 = 0; t0 < n_steps;) {
         const int round_end = (t0 / every + 1) * every;  // (every divides n_steps)
-        const int t1 = std::min(round_end, n_steps - t0 > chunk ? t0 + chunk : n_steps);
+        const int t1 = std::min(round_end, chunk_end(ctx, t0, n_steps));
         HIPCHK(gdca_launch_temper_chain(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K, plan, t0, t1, V, in_lds, state));
         if (t1 == round_end) {
-            const int past = t1 - plan.burn;  // a sample point: t1 = burn + (j + 1) stride
-            const int js = past > 0 && past % plan.stride == 0 ? past / plan.stride - 1 : -1;
+            const int past = t1 - plan.chain.burn;  // a sample point: t1 = burn + (j + 1) stride
+            const int js = past > 0 && past % plan.chain.stride == 0 ? past / plan.chain.stride - 1 : -1;
             gdca_launch_temper_round(s, m.N, K, plan, t1 / every - 1, js, state);
         }
         t0 = t1;
@@ -3651,7 +3659,7 @@ static gdca_status validate_walk(gdca_ctx *ctx, int N, int q, long long K, int f
     if (flags & ~(GDCA_WALK_GAP_TARGET | GDCA_WALK_FILL_GAPS)) return fail(ctx, GDCA_EINVAL, "invalid flags");
     if (!Xout || !steps) return fail(ctx, GDCA_EINVAL, "null pointer");
     bool in_lds = false;
-    if (!walk_placement(ctx, N, q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    CHK(walk_placement(ctx, N, q, &in_lds));
     return GDCA_OK;
 }
 
@@ -3706,7 +3714,7 @@ static gdca_status validate_sample(gdca_ctx *ctx, int N, int q, long long K, int
         return fail(ctx, GDCA_EINVAL, "invalid burn, stride or n_samples");
     if (!Xs || !accepted) return fail(ctx, GDCA_EINVAL, "null pointer");
     bool in_lds = false;
-    if (!walk_placement(ctx, N, q, &in_lds)) return fail(ctx, GDCA_EINVAL, "WALK_TABLE = lds: the table does not fit into LDS");
+    CHK(walk_placement(ctx, N, q, &in_lds));
     if (N > GDCA_SAMPLE_MAX_SITES) return fail(ctx, GDCA_EINVAL, "N is larger than GDCA_SAMPLE_MAX_SITES");
     return GDCA_OK;
 }
@@ -3735,7 +3743,7 @@ gdca_status gdca_sample_dev(gdca_ctx *ctx, const double *mJ_dev, const double *P
 {
     CHK(check_sample(ctx, mJ_dev, Pi_dev, N, q, X_dev, K, flags, beta, burn, stride, n_samples, Xs_dev, accepted_dev));
     CHK(begin(ctx));
-    const sample_request r{{mask_dev, flags, beta, seed, stream0, burn, stride, n_samples, Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev},
+    const sample_request r{{{mask_dev, flags, seed, stream0, burn, stride, n_samples, thr_dev, moves_dev}, beta, Xs_dev, dE_s_dev, accepted_dev},
                            V_dev};
     CHK(sample_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), X_dev, K, r));
     return sequences_checked(ctx);
@@ -3747,7 +3755,7 @@ gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, i
                                 int32_t *accepted_dev, double *thr_dev, int32_t *moves_dev, double *V_dev, gdca_stats *st)
 {
     CHK(check_run_sample(ctx, Z_dev, N, M, q, p, X_dev, K, flags, beta, burn, stride, n_samples, Xs_dev, accepted_dev));
-    const sample_request r{{mask_dev, flags, beta, seed, stream0, burn, stride, n_samples, Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev},
+    const sample_request r{{{mask_dev, flags, seed, stream0, burn, stride, n_samples, thr_dev, moves_dev}, beta, Xs_dev, dE_s_dev, accepted_dev},
                            V_dev};
     return run_target(ctx, Z_dev, N, M, q, p, sample_target(Z_dev, M, X_dev, K, r), st);
 }
@@ -3772,12 +3780,11 @@ static temper_request temper_request_of(int R, const double *betas, const int8_t
                                         int32_t *slot_path, bool fused)
 {
     temper_request r{};
-    r.plan.mask = mask, r.plan.flags = flags, r.plan.R = R, r.plan.swap_every = swap_every;
+    r.plan.chain = gdca_chain_plan{mask, flags, seed, stream0, burn, stride, n_samples, thr, moves};
+    r.plan.R = R, r.plan.swap_every = swap_every;
     for (int i = 0; i < R; ++i) r.plan.betas[i] = betas[i];
-    r.plan.seed = seed, r.plan.stream0 = stream0;
-    r.plan.burn = burn, r.plan.stride = stride, r.plan.n_samples = n_samples;
     r.plan.slot0 = slot0, r.plan.Xs = Xs, r.plan.E_s = E_s, r.plan.accepted = accepted, r.plan.swaps = swaps, r.plan.Xr_out = Xr_out;
-    r.plan.slot_out = slot_out, r.plan.thr = thr, r.plan.moves = moves, r.plan.swap_thr = swap_thr, r.plan.slot_path = slot_path;
+    r.plan.slot_out = slot_out, r.plan.swap_thr = swap_thr, r.plan.slot_path = slot_path;
     r.fused = fused;
     return r;
 }
@@ -3974,7 +3981,7 @@ gdca_status gdca_bm_learn_dev(gdca_ctx *ctx, double *W_dev, const double *Pi_d_d
     const gdca_model model = operator_model(W_dev, zero, N, q);
     for (int it = 0; it < n_iter; ++it) {
         const uint64_t t = iter0 + (uint64_t)it;
-        const sample_request r{{mask_dev, flags, beta, seed, t * (uint64_t)K, burn, stride, n_samples, Xs, nullptr, accepted, nullptr, nullptr},
+        const sample_request r{{{mask_dev, flags, seed, t * (uint64_t)K, burn, stride, n_samples, nullptr, nullptr}, beta, Xs, nullptr, accepted},
                                nullptr};
         CHK(sample_stage(ctx, model, X_dev, K, r));
         gdca_launch_bm_last_sample(s, Xs, N, K, n_samples, X_dev);

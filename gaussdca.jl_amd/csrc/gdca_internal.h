@@ -401,19 +401,25 @@ hipError_t gdca_launch_greedy_walk(hipStream_t s, const double *A, size_t ld, do
 // (include/gdca.h, Metropolis chains).  Xg, V, A, ld, sign as the walk's; the table is placed by the walk's rule (gdca_walk_table_fits:
 // the LDS instance keeps the N s residue entries only, the gap's +0.0 is in the code, so what fits there fits here).
 #define GDCA_SAMPLE_CHUNK_RULE 65536  // proposals a launch
-struct gdca_sample_plan {
-    const int8_t *mask;           // [N] or nullptr
+// what a plain chain and a replica take alike (csrc/gdca_chain.h runs it)
+struct gdca_chain_plan {
+    const int8_t *mask;  // [N] or nullptr
     int flags;
-    double beta;
     unsigned long long seed, stream0;
-    int burn, stride, n_samples;  // n_steps = burn + n_samples * stride
-    int8_t *Xs;                   // [K][n_samples][N]
-    double *dE_s;                 // [K][n_samples] or nullptr
-    int32_t *accepted;            // [K]: the count so far between two launches
-    double *thr;                  // [K][n_steps] or nullptr
-    int32_t *moves;               // [K][n_steps] or nullptr
+    int burn, stride, n_samples;
+    double *thr;     // [chains][n_steps] or nullptr (a replica is a chain here)
+    int32_t *moves;  // [chains][n_steps] or nullptr
+    int n_steps() const { return burn + n_samples * stride; }
 };
-size_t gdca_sample_lds_bytes(int N, int q, bool table_in_lds);
+struct gdca_sample_plan {
+    gdca_chain_plan chain;
+    double beta;
+    int8_t *Xs;         // [K][n_samples][N]
+    double *dE_s;       // [K][n_samples] or nullptr
+    int32_t *accepted;  // [K]: the count so far between two launches
+};
+// what both chain launchers check before they launch: the fit, the LDS limit, N, 0 <= t0 < t1 <= n_steps; *lds: the launch's dynamic LDS
+hipError_t gdca_chain_launch_check(int N, int sdim, bool table_in_lds, const gdca_chain_plan &c, int t0, int t1, size_t *lds);
 // what a chain keeps in HBM between two launches beside its table and `accepted`: the running sums (K doubles), then the symbols (K N bytes)
 size_t gdca_sample_state_bytes(int N, int K);
 // The proposals t0 .. t1 - 1 of every chain; t0 == 0 starts from Xg, a later launch from `state`.  table_in_lds: the table is copied
@@ -423,24 +429,20 @@ hipError_t gdca_launch_sample(hipStream_t s, const double *A, size_t ld, double 
                               const gdca_sample_plan &plan, int t0, int t1, double *V, bool table_in_lds, void *state);
 
 // ---- k_temper.hip: replica exchange over the Metropolis chains -- R replicas a chain, one workgroup a replica, swap rounds between launches --
-// (include/gdca.h, Replica-exchange chains).  G = K R replicas; Xg, V, A, ld, sign, the table's placement and the LDS layout as k_sample's.
+// (include/gdca.h, Replica-exchange chains).  G = K R replicas; Xg, V, A, ld, sign and the table's placement as k_sample's.
 struct gdca_temper_plan {
-    const int8_t *mask;           // [N] or nullptr
-    int flags, R, swap_every;
+    gdca_chain_plan chain;          // thr, moves: [K][R][n_steps]; n_rounds = n_steps / swap_every
+    int R, swap_every;
     double betas[GDCA_TEMPER_MAX];  // HOST values, by slot; they travel as kernel arguments
-    unsigned long long seed, stream0;
-    int burn, stride, n_samples;  // n_steps = burn + n_samples * stride, n_rounds = n_steps / swap_every
-    const int32_t *slot0;         // [K][R] or nullptr
-    int8_t *Xs;                   // [K][n_samples][N]
-    double *E_s;                  // [K][n_samples] or nullptr
-    int32_t *accepted;            // [K][R], by slot
-    int32_t *swaps;               // [K][R - 1]
-    int8_t *Xr_out;               // [K][R][N]
-    int32_t *slot_out;            // [K][R]
-    double *thr;                  // [K][R][n_steps] or nullptr
-    int32_t *moves;               // [K][R][n_steps] or nullptr
-    double *swap_thr;             // [K][R - 1][n_rounds] or nullptr
-    int32_t *slot_path;           // [K][R][n_rounds] or nullptr
+    const int32_t *slot0;           // [K][R] or nullptr
+    int8_t *Xs;                     // [K][n_samples][N]
+    double *E_s;                    // [K][n_samples] or nullptr
+    int32_t *accepted;              // [K][R], by slot
+    int32_t *swaps;                 // [K][R - 1]
+    int8_t *Xr_out;                 // [K][R][N]
+    int32_t *slot_out;              // [K][R]
+    double *swap_thr;               // [K][R - 1][n_rounds] or nullptr
+    int32_t *slot_path;             // [K][R][n_rounds] or nullptr
 };
 // what the replicas keep in HBM beside their tables: the running sums, E0, the maps slot_of and holder, the symbols
 size_t gdca_temper_state_bytes(int N, int G);

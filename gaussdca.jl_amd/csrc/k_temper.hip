@@ -6,13 +6,13 @@
 //   k_temper_init     one wave a chain: slot0 checked (a column that is no permutation of 0 .. R - 1 raises GDCA_BAD_SLOTS and the chain
 //                     goes on with the identity, so nothing is ever indexed with a bad slot), the maps slot_of (replica -> slot) and
 //                     holder (slot -> replica) written, the counts zeroed.
-//   k_temper_chain    ONE workgroup a replica, k_sample's structure line for line: the proposal computed by every wave for itself on
-//                     workgroup-uniform values, no barrier and no write on a rejected proposal, two barriers and the two-column update
-//                     on an accepted one, the table in LDS (TL = true) or in place in HBM by the walk's placement rule.  What differs:
-//                     beta is betas[slot_of[replica]] (fixed for the launch: slots change between launches only), the accepted
-//                     proposals are added to the SLOT's count at the end of the launch (one replica holds a slot, so one thread
-//                     writes a count), and no sample is written here.  A launch runs the proposals t0 .. t1 - 1, which never cross
-//                     a round; between two launches the replica lives in HBM exactly as a plain chain does.
+//   k_temper_chain    ONE workgroup a replica: csrc/gdca_chain.h's chain_run, the body k_sample runs -- no barrier and no write on a
+//                     rejected proposal, two barriers and the two-column update on an accepted one, the table in LDS (TL = true) or in
+//                     place in HBM by the walk's placement rule.  Its own: beta is betas[slot_of[replica]] (fixed for the launch: slots
+//                     change between launches only), the accepted proposals are added to the SLOT's count at the end of the launch
+//                     (one replica holds a slot, so one thread writes a count), and no sample is written here.  A launch runs the
+//                     proposals t0 .. t1 - 1, which never cross a round; between two launches the replica lives in HBM exactly as a
+//                     plain chain does.
 //   k_temper_round    one wave a chain, round e: thread p owns the pair (p, p + 1) where p % 2 == e % 2 -- the pairs of a round are
 //                     disjoint, so each owner writes its two entries of either map and its own count --, then every thread r writes
 //                     slot_path, and at a sample point the wave copies the symbols of slot 0's holder and its E0 + S out.  Integer
@@ -20,164 +20,33 @@
 //   k_temper_finish   the final symbols (1-based) and slots of every replica.
 // COUPLING: replicas meet at launch boundaries only.  No persistent kernel, no flag between workgroups, nothing spins: a dependency
 // that cannot hang is worth more than the microseconds a launch costs.
-// ORDER-FIXED as k_sample: one thread an entry, one thread a sum, one thread a count, one thread a pair; the random numbers are
+// ORDER-FIXED as the chain body: one thread an entry, one thread a sum, one thread a count, one thread a pair; the random numbers are
 // functions of (seed, stream, counter).  No read-modify-write is shared between threads.
-#include "gdca_internal.h"
+#include "gdca_chain.h"
 #include "gdca_launch.h"
-
-#include <climits>
 
 struct k_temper_betas {
     double b[GDCA_TEMPER_MAX];
 };
 
 struct k_temper_args {
-    const double *A;  // element (row, col), row >= col, at A[col * ld + row]
-    size_t ld;
-    double sign;
-    const uint32_t *Xg;      // [ceil(N / 4)][G]: the start symbols of the G = K R replicas (t0 == 0)
-    double *V;               // [G][N][q]: the tables between two launches (the first: k_mut_rows', what = potential)
-    const int8_t *mask;      // [N] or nullptr
+    chain_args c;            // G = K R replicas, the stream of replica g: stream0 + g
     const int32_t *slot_of;  // [G]: the slot every replica holds during this launch
     int32_t *accepted;       // [K][R]: by slot
-    double *thr;             // [G][n_steps] or nullptr
-    int32_t *moves;          // [G][n_steps] or nullptr
-    double *sum_state;       // [G]: the running sums between two launches
-    unsigned char *x_state;  // [G][N]: the symbols between two launches
-    unsigned long long seed, stream0;
-    int N, sdim, G, R, gaps, n_steps, t0, t1;
+    int R;
     k_temper_betas betas;
 };
-
-#define TEMPER_G 0x9E3779B97F4A7C15ull
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 template <bool TL>
 __global__ __launch_bounds__(256) void k_temper_chain(const k_temper_args p)
 {
-    extern __shared__ double lds_[];  // [TL ? N s : 0] the table's residue entries, then ints, shorts and bytes (k_sample's layout)
-    const int N = p.N, sdim = p.sdim, q = sdim + 1, n = N * sdim;
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    extern __shared__ double lds_[];  // chain_layout
     const size_t g = blockIdx.x;
-    double *tabL = lds_;
-    int *dec = reinterpret_cast<int *>(tabL + (TL ? n : 0));              // [4]: the length of the site list
-    unsigned short *sites = reinterpret_cast<unsigned short *>(dec + 4);  // [N]: the sites that may change, ascending
-    unsigned char *x = reinterpret_cast<unsigned char *>(sites + N);      // [N]
-    double *Vg = p.V + g * (size_t)N * q;
-    const bool first = p.t0 == 0;
-    const int dj = 256 / sdim, dr = 256 - dj * sdim;  // row r + 256: site + dj, symbol + dr (mod s)
     const int slot = __builtin_amdgcn_readfirstlane(p.slot_of[g]);  // (k_temper_init: inside 0 .. R - 1)
-
-    for (int i = t; i < N; i += 256)
-        x[i] = first ? (unsigned char)((p.Xg[(size_t)(i >> 2) * p.G + g] >> (8 * (i & 3))) & 0xffu) : p.x_state[g * (size_t)N + i];
-    if (TL) {
-        int j = t / sdim, c = t - j * sdim;
-        for (int r = t; r < n; r += 256) {
-            tabL[r] = Vg[j * q + c];
-            j += dj, c += dr;
-            if (c >= sdim) c -= sdim, ++j;
-        }
-    }
-    __syncthreads();
-    // ---- the site list: wave 0, 64 sites at a time.  It is the START's list: without the flag a gap stays a gap and a residue a
-    // residue, with it every site the mask lets change is listed, so the list of the current symbols is the list of the start
-    if (wave == 0) {
-        int cnt = 0;
-        for (int base = 0; base < N; base += 64) {
-            const int i = base + lane;
-            const bool e = i < N && (!p.mask || p.mask[i] != 0) && (p.gaps || x[i] != sdim);
-            const unsigned long long m = __ballot(e);
-            if (e) sites[cnt + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)i;
-            cnt += __popcll(m);
-        }
-        if (lane == 0) dec[0] = cnt;
-    }
-    __syncthreads();
-    const int n_sites = __builtin_amdgcn_readfirstlane(dec[0]);
-    auto ent = [&](int i, int c) -> double {
-        if (!TL) return Vg[i * q + c];
-        const double v = tabL[i * sdim + (c < sdim ? c : sdim - 1)];
-        return c < sdim ? v : 0.0;
-    };
-
-    const unsigned long long T1 = (unsigned long long)(p.gaps ? q : sdim) - 1ull;  // T - 1 targets
-    const unsigned long long key = mix64(mix64(p.seed + TEMPER_G) + (p.stream0 + g + 1ull) * TEMPER_G);  // the REPLICA's stream
-    unsigned long long ctr = key + (2ull * (unsigned long long)p.t0 + 1ull) * TEMPER_G;                 // key + (c + 1) G of draw c = 2 t0
-    const double *__restrict__ A = p.A;
-    const size_t ld = p.ld;
-    const double sign = p.sign, beta = p.betas.b[slot];
-    const size_t row = g * (size_t)p.n_steps;
-    int acc_n = 0;                               // this launch's accepted proposals (thread 0's is the one that is written)
-    double sum = first ? 0.0 : p.sum_state[g];   // the accepted dE in step order
-
-    for (int tt = p.t0; tt < p.t1; ++tt) {
-        // ---- propose: every wave for itself, on uniform values
-        const unsigned long long r0 = mix64(ctr), r1 = mix64(ctr + TEMPER_G);
-        ctr += 2ull * TEMPER_G;
-        const double u = (double)((r1 >> 11) + 1ull) * 0x1p-53;  // (0, 1], exact
-        const double thr = -log(u);
-        int code = INT_MIN, i = 0, a = 0, b = 0;
-        double dE = 0.0;
-        bool go = false;
-        if (n_sites > 0) {
-            i = sites[(int)(((r0 >> 32) * (unsigned long long)n_sites) >> 32)];
-            const int v = (int)(((r0 & 0xffffffffull) * T1) >> 32);
-            a = x[i];
-            b = v + (v >= a);
-            dE = ent(i, b) - ent(i, a);
-            go = beta * dE <= thr;  // (false for a NaN on the left)
-            code = i * q + b;
-        }
-        const int acc = __builtin_amdgcn_readfirstlane(go ? 1 : 0);
-        if (t == 0) {
-            if (p.thr) p.thr[row + tt] = thr;
-            if (p.moves) p.moves[row + tt] = n_sites > 0 && !acc ? -1 - code : code;
-        }
-        // ---- accept: x_i, then the two columns r(i,b), r(i,a) into every other site's potentials
-        if (acc) {
-            i = __builtin_amdgcn_readfirstlane(i), a = __builtin_amdgcn_readfirstlane(a), b = __builtin_amdgcn_readfirstlane(b);
-            sum = sum + dE;
-            ++acc_n;
-            __syncthreads();  // every wave has read the old state
-            if (t == 0) x[i] = (unsigned char)b;
-            const int rb = i * sdim + b, ra = i * sdim + a;  // (a gap has no column: not read)
-            int j = t / sdim, c = t - j * sdim;
-            for (int r = t; r < n; r += 256) {
-                if (j != i) {
-                    const double kb = b < sdim ? sign * A[r >= rb ? (size_t)rb * ld + r : (size_t)r * ld + rb] : 0.0;
-                    const double ka = a < sdim ? sign * A[r >= ra ? (size_t)ra * ld + r : (size_t)r * ld + ra] : 0.0;
-                    const double dk = kb - ka;
-                    double &v = TL ? tabL[r] : Vg[j * q + c];
-                    v = v + dk;
-                }
-                j += dj, c += dr;
-                if (c >= sdim) c -= sdim, ++j;
-            }
-            __syncthreads();
-        }
-    }
-
-    // ---- what the launch leaves for the next one and for the round: the symbols, the sum, the slot's count, the table
-    for (int i = t; i < N; i += 256) p.x_state[g * (size_t)N + i] = x[i];
-    if (t == 0) {
-        p.sum_state[g] = sum;
+    const int acc_n = chain_run<TL>(p.c, lds_, g, p.betas.b[slot], [](int, const unsigned char *, double) {});
+    if (threadIdx.x == 0) {
         int32_t *cnt = p.accepted + (g / (size_t)p.R) * (size_t)p.R + slot;  // (this replica alone holds the slot)
         *cnt = *cnt + acc_n;
-    }
-    if (TL) {
-        int j = t / sdim, c = t - j * sdim;
-        for (int r = t; r < n; r += 256) {  // (the rows this thread updated)
-            Vg[j * q + c] = tabL[r];
-            j += dj, c += dr;
-            if (c >= sdim) c -= sdim, ++j;
-        }
     }
 }
 
@@ -238,12 +107,9 @@ __global__ __launch_bounds__(64) void k_temper_round(const k_temper_round_args p
             const double Eb = p.E0[base + b] + p.sum_state[base + b];
             const double db = p.betas.b[t] - p.betas.b[t + 1], dEab = Eb - Ea;
             const double d = db * dEab;
-            const unsigned long long key = mix64(mix64(p.seed + TEMPER_G) + (p.stream0 + base + 1ull) * TEMPER_G);
-            const unsigned long long skey = mix64(~key);
+            const unsigned long long skey = chain_swap_key(chain_key(p.seed, p.stream0 + base));  // (the key of the chain's first replica)
             const unsigned long long c = (unsigned long long)e * (unsigned long long)R + (unsigned long long)t;
-            const unsigned long long r1 = mix64(skey + (c + 1ull) * TEMPER_G);
-            const double u = (double)((r1 >> 11) + 1ull) * 0x1p-53;
-            th = -log(u);
+            th = chain_threshold(chain_uniform(chain_mix64(chain_counter(skey, c))));
             if (d <= th) {  // (false for a NaN; the pairs of a round are disjoint: these five words are this thread's)
                 p.holder[base + t] = b;
                 p.holder[base + t + 1] = a;
@@ -330,19 +196,18 @@ void gdca_launch_temper_init(hipStream_t s, const gdca_temper_plan &plan, int K,
 hipError_t gdca_launch_temper_chain(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
                                     const gdca_temper_plan &plan, int t0, int t1, double *V, bool table_in_lds, void *state)
 {
-    const size_t lds = gdca_sample_lds_bytes(N, sdim + 1, table_in_lds);
-    // (gdca_api.hip checks before: walk_placement, validate_temper)
-    if ((table_in_lds && !gdca_walk_table_fits(N, sdim + 1)) || lds > GDCA_WALK_LDS_LIMIT || N > 65535) return hipErrorInvalidValue;
+    size_t lds = 0;
+    hipError_t e = gdca_chain_launch_check(N, sdim, table_in_lds, plan.chain, t0, t1, &lds);
+    if (e != hipSuccess) return e;
     if (plan.R < 1 || plan.R > GDCA_TEMPER_MAX || plan.swap_every < 1) return hipErrorInvalidValue;
-    const int n_steps = plan.burn + plan.n_samples * plan.stride;
     // a launch never crosses a round: the slots, and with them the temperatures, are fixed while it runs
-    if (t0 < 0 || t1 <= t0 || t1 > n_steps || (t1 - 1) / plan.swap_every != t0 / plan.swap_every) return hipErrorInvalidValue;
+    if ((t1 - 1) / plan.swap_every != t0 / plan.swap_every) return hipErrorInvalidValue;
     const int G = K * plan.R;
     const temper_state st(state, G);
-    const k_temper_args a{A, ld, sign, Xg, V, plan.mask, st.slot_of, plan.accepted, plan.thr, plan.moves, st.sum, st.x, plan.seed, plan.stream0,
-                          N, sdim, G, plan.R, (plan.flags & GDCA_SAMPLE_GAPS) != 0 ? 1 : 0, n_steps, t0, t1, betas_of(plan)};
+    const k_temper_args a{chain_args_of(A, ld, sign, Xg, V, plan.chain, st.sum, st.x, N, sdim, G, t0, t1), st.slot_of, plan.accepted, plan.R,
+                          betas_of(plan)};
     void (*kern)(k_temper_args) = table_in_lds ? k_temper_chain<true> : k_temper_chain<false>;
-    const hipError_t e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    e = gdca_raise_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     GDCA_LAUNCH_DIRECT(kern, dim3((unsigned)G), dim3(256), lds, s, a);
     return hipSuccess;
@@ -351,9 +216,9 @@ hipError_t gdca_launch_temper_chain(hipStream_t s, const double *A, size_t ld, d
 void gdca_launch_temper_round(hipStream_t s, int N, int K, const gdca_temper_plan &plan, int e, int js, void *state)
 {
     const temper_state st(state, K * plan.R);
-    const int n_rounds = (plan.burn + plan.n_samples * plan.stride) / plan.swap_every;
     const k_temper_round_args a{st.E0, st.sum, st.x, st.slot_of, st.holder, plan.swaps, plan.swap_thr, plan.slot_path, plan.Xs, plan.E_s,
-                                plan.seed, plan.stream0, N, K, plan.R, e, n_rounds, js, plan.n_samples, betas_of(plan)};
+                                plan.chain.seed, plan.chain.stream0, N, K, plan.R, e, plan.chain.n_steps() / plan.swap_every, js,
+                                plan.chain.n_samples, betas_of(plan)};
     GDCA_LAUNCH_DIRECT(k_temper_round, dim3((unsigned)K), dim3(64), 0, s, a);
 }
 

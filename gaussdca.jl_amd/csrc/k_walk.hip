@@ -21,20 +21,17 @@
 //              decide  thread 0 folds the four, tests dE < -min_gain, records (i, b, dE), adds dE to its running sum, sets x_i and
 //                      publishes (go, i, b, a) in LDS.  EVERY thread reads `go` there after the barrier (made a scalar: the loop's exit
 //                      is workgroup-uniform, no lane leaves on a view of its own).
-//              update  thread t takes the rows r = t, t + 256, .. of the two columns r(i,b), r(i,a) (the rows of site i left out).
-//                      mJ is symmetric and only its lower triangle is read: the rows below the column's diagonal element are contiguous,
-//                      the rows above it are a walk with stride ld along ROW r(i, .) -- the two columns of a step lie at most s doubles
-//                      apart there, so they share most of their cache lines.  (No mirrored copy of the triangle is kept: 8 n^2 bytes
-//                      of workspace for a read-side choice; DESIGN 3.8b has the measured cost of the strided half.)
+//              update  csrc/gdca_chain.h's chain_update: thread t takes the rows r = t, t + 256, .. of the two columns r(i,b), r(i,a)
+//                      (the rows of site i left out).  The two columns of a step lie at most s doubles apart in the strided half, so
+//                      they share most of their cache lines.  (No mirrored copy of the triangle is kept: 8 n^2 bytes of workspace for a
+//                      read-side choice.)
 //            Three barriers a step, none in a loop that lanes leave one by one.  A fused run's A holds -mJ (sign = -1): every load is
 //            negated, which is exact, so both forms compute on the same values.
 // ORDER-FIXED: every table entry is updated by one thread with the two operations above, the minimum is taken in a total order, the sum
 // of the recorded dE is thread 0's in step order.  No floating-point atomics.  So a walk's outputs are the same bits from run to run,
 // whatever K is, wherever x_k stands in the batch and wherever the table lives.
-#include "gdca_internal.h"
+#include "gdca_chain.h"
 #include "gdca_launch.h"
-
-#include <climits>
 
 struct k_walk_args {
     const double *A;  // element (row, col), row >= col, at A[col * ld + row]
@@ -87,7 +84,6 @@ __global__ __launch_bounds__(256) void k_walk(const k_walk_args p)
     const bool gap_target = (p.flags & GDCA_WALK_GAP_TARGET) != 0, fill_gaps = (p.flags & GDCA_WALK_FILL_GAPS) != 0;
     const double thresh = -p.min_gain;
     const int di = 256 / q, dc = 256 - di * q;  // entry idx + 256: site + di, symbol + dc (mod q)
-    const int dj = 256 / sdim, dr = 256 - dj * sdim;
     const double *__restrict__ A = p.A;
     const size_t ld = p.ld;
     const double sign = p.sign;
@@ -143,20 +139,7 @@ __global__ __launch_bounds__(256) void k_walk(const k_walk_args p)
         {
             const int i = __builtin_amdgcn_readfirstlane(dec[1]), b = __builtin_amdgcn_readfirstlane(dec[2]),
                       a = __builtin_amdgcn_readfirstlane(dec[3]);
-            const int rb = i * sdim + b, ra = i * sdim + a;  // (a gap has no column: not read)
-            int j = t / sdim, c = t - j * sdim;
-            for (int r = t; r < n; r += 256) {
-                if (j != i) {
-                    // (r, col) of the symmetric matrix from its lower triangle: below the diagonal as it lies, above it mirrored
-                    const double kb = b < sdim ? sign * A[r >= rb ? (size_t)rb * ld + r : (size_t)r * ld + rb] : 0.0;
-                    const double ka = a < sdim ? sign * A[r >= ra ? (size_t)ra * ld + r : (size_t)r * ld + ra] : 0.0;
-                    const double dk = kb - ka;
-                    double &v = tab(j * q + c);
-                    v = v + dk;
-                }
-                j += dj, c += dr;
-                if (c >= sdim) c -= sdim, ++j;
-            }
+            chain_update(A, ld, sign, n, sdim, i, a, b, t, [&](int, int j, int c) -> double & { return tab(j * q + c); });
         }
         __syncthreads();
     }

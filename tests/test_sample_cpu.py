@@ -186,6 +186,8 @@ def test_sample_kernels_do_not_spill_and_hold_no_barrier_in_a_divergent_loop(tmp
         assert field(r"LDS Size \[bytes/block\]") == 0  # (the table and the lists are the launch's dynamic LDS)
     # each instance: the proposal loop with the update loop in it, the loops of the prologue (symbols, table, site list) and the epilogue
     compiler_report(tmp_path, "k_sample.hip", min_loops=12)
-    code = "\n".join(ln.split("//")[0] for ln in open(os.path.join(CSRC, "k_sample.hip")).read().split("\n"))
-    # two barriers of the prologue, two of an accepted move -- none on the path of a rejected proposal
-    assert len(re.findall(r"__syncthreads\(\)", code)) == 4 and "atomic" not in code
+    code, chain = ("\n".join(ln.split("//")[0] for ln in open(os.path.join(CSRC, f)).read().split("\n")) for f in ("k_sample.hip", "gdca_chain.h"))
+    # the chain body (csrc/gdca_chain.h): two barriers of the prologue, two of an accepted move -- none on the path of a rejected
+    # proposal; the kernel adds none
+    assert len(re.findall(r"__syncthreads\(\)", chain)) == 4 and "atomic" not in chain
+    assert len(re.findall(r"__syncthreads\(\)", code)) == 0 and "atomic" not in code and "chain_run<TL>(" in code

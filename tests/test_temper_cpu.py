@@ -206,12 +206,18 @@ def test_temper_kernels_do_not_spill_and_hold_no_barrier_on_a_rejected_proposal(
     for name, field in report:
         assert field(r"LDS Size \[bytes/block\]") == 0  # (the table and the lists are the launch's dynamic LDS)
     compiler_report(tmp_path, "k_temper.hip", min_loops=12)
-    code = "\n".join(ln.split("//")[0] for ln in open(os.path.join(CSRC, "k_temper.hip")).read().split("\n"))
-    assert "atomic" not in code
-    chain = code[code.index("void k_temper_chain("):code.index("struct k_temper_init_args")]
+    code, hdr = ("\n".join(ln.split("//")[0] for ln in open(os.path.join(CSRC, f)).read().split("\n")) for f in ("k_temper.hip", "gdca_chain.h"))
+    assert "atomic" not in code and "atomic" not in hdr
+    # the chain body is csrc/gdca_chain.h's: k_temper_chain runs it and adds no barrier
+    kern = code[code.index("void k_temper_chain("):code.index("struct k_temper_init_args")]
+    assert "chain_run<TL>(" in kern and len(re.findall(r"__syncthreads\(\)", kern)) == 0
+    chain = hdr[hdr.index("int chain_run("):hdr.index("inline chain_args chain_args_of(")]
     # two barriers of the prologue, two of an accepted move -- none on the path of a rejected proposal
     assert len(re.findall(r"__syncthreads\(\)", chain)) == 4
     loop = chain[chain.index("for (int tt = p.t0;"):]
     assert len(re.findall(r"__syncthreads\(\)", loop)) == 2 and len(re.findall(r"__syncthreads\(\)", loop[loop.index("if (acc) {"):])) == 2
+    # the update the accepted move calls between its two barriers holds none of its own, nor does anything else of the header
+    assert len(re.findall(r"__syncthreads\(\)", hdr[hdr.index("void chain_rows("):hdr.index("struct chain_layout")])) == 0
+    assert len(re.findall(r"__syncthreads\(\)", hdr)) == 4
     # the round: one barrier, between the pairs' writes and the reads of the maps
-    assert len(re.findall(r"__syncthreads\(\)", code)) == 5
+    assert len(re.findall(r"__syncthreads\(\)", code)) == 1
