@@ -20,6 +20,7 @@ from .dcautils import bm_learn, potts_from_gaussian, potts_independent  # noqa: 
 from .gdca import gDCA_bm  # noqa: F401
 from .dcautils import plm_conditionals, plm_learn, plm_tallies  # noqa: F401
 from .gdca import gDCA_plm  # noqa: F401
+from .dcautils import log_partition, potts_loglik  # noqa: F401
 from .dcautils import (add_pseudocount, assign_blocks, compute_C, compute_DI_gauss, compute_FN, compute_ranking,  # noqa: F401
                        compute_theta, compute_weighted_frequencies, compute_weights, correct_APC,
                        inv_cholesky, logodds_information, mutation_scan, neighbour_counts, pair_energies, pair_energies_blocked, pair_identity_sum,

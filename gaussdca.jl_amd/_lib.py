@@ -295,6 +295,12 @@ SYMBOLS = {
                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "gdca_log_partition_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdca_log_partition": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdca_potts_from_gaussian_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_potts_from_gaussian": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gdca_bm_update_dev": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
@@ -1011,6 +1017,32 @@ class Context:
                                _p(b), None if mask is None else _p(mask), int(flags), int(seed), int(stream0), int(swap_every), int(burn),
                                int(stride), int(n_samples), *ptrs)
         return tuple(a for a in out if a is not None), st
+
+    # ---- log partition function by annealed importance sampling (gdca_log_partition*) ----
+    def log_partition_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, x_ptr: int | None, mask_ptr: int | None, flags: int, betas,
+                          sweep: int, K: int, seed: int, stream0: int, out4_ptr: int | None, logw_ptr: int | None,
+                          E_end_ptr: int | None = None, X0_ptr: int | None = None, Xout_ptr: int | None = None,
+                          accepted_ptr: int | None = None, thr_ptr: int | None = None, moves_ptr: int | None = None) -> None:
+        """gdca_log_partition_dev: mJ (n x n), Pi (n), the template x (N int8 or None: every site is free), mask (N int8 or None) and
+        the outputs -- out4 (4 f64: log Z, the effective sample size, max logw, log |Omega|), logw (K f64), E_end (K f64), X0 and Xout
+        (N x K int8), accepted (K int32), thr / moves (n_steps x K); the last six may be None -- are device pointers; betas (L + 1
+        values, betas[0] == 0, betas[L] the target) is a host sequence."""
+        b = self._betas(betas)
+        self.check(self.lib.gdca_log_partition_dev(self.h, C.c_void_p(mJ_ptr), C.c_void_p(Pi_ptr), int(N), int(q), self._opt(x_ptr),
+                                                   self._opt(mask_ptr), int(flags), _p(b), int(b.size) - 1, int(sweep), int(K), int(seed),
+                                                   int(stream0), self._opt(out4_ptr), self._opt(logw_ptr), self._opt(E_end_ptr),
+                                                   self._opt(X0_ptr), self._opt(Xout_ptr), self._opt(accepted_ptr), self._opt(thr_ptr),
+                                                   self._opt(moves_ptr)))
+
+    @staticmethod
+    def log_partition_outputs(N: int, K: int, n_steps: int, trace: bool):
+        """the host arrays the annealed chains fill, in the library's memory order: (out4 (4,), logw (K,), then -- or None each -- E_end
+        (K,), X0 (N, K) Fortran int8, Xout (N, K) Fortran int8, accepted (K,) int32, thr (K, n_steps), moves (K, n_steps) int32)"""
+        K, T = max(int(K), 0), max(int(n_steps), 0)
+        if not trace:
+            return (np.empty(4), np.empty(K)) + (None,) * 6
+        return (np.empty(4), np.empty(K), np.empty(K), np.empty((int(N), K), dtype=np.int8, order="F"),
+                np.empty((int(N), K), dtype=np.int8, order="F"), np.empty(K, dtype=np.int32), np.empty((K, T)), np.empty((K, T), dtype=np.int32))
 
     # ---- Boltzmann-machine refinement of the Potts model (W, zeros) the chains draw from (gdca_potts_from_gaussian*, gdca_bm_*) ----
     def potts_from_gaussian_dev(self, mJ_ptr: int, Pi_ptr: int, N: int, q: int, W_ptr: int) -> None:

@@ -315,6 +315,8 @@ struct gdca_ctx {
     // counts, the samples), and the read-out's column partials
     gdca_buf TMst, TMx;       // replica-exchange chains (k_temper.hip): gdca_temper_state_bytes, and the fused form's N x R x K starts
     gdca_buf BMws, BMred;
+    // log partition function (k_ais.hip): gdca_ais_state_bytes, the N x K starts, the ladder's L + 1 betas
+    gdca_buf AISst, AISx, AISb;
     // pseudo-likelihood fit (k_plm.hip): the slab's table of potentials / conditionals, and plm_plan's arrays
     gdca_buf PLMv, PLMws;
     int ncu;                  // compute units of the device
@@ -772,7 +774,8 @@ gdca_status gdca_ctx_destroy(gdca_ctx *ctx)
                         &ctx->Pij, &ctx->sc_front, &ctx->keep, &ctx->Xg, &ctx->Epart, &ctx->gpart, &ctx->gvec,
                         &ctx->PXa, &ctx->PXb, &ctx->PXpad, &ctx->PEab, &ctx->PT, &ctx->PBtab, &ctx->PBitems, &ctx->PBE,
                         &ctx->LOa, &ctx->LOb, &ctx->PBN,
-                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst, &ctx->TMst, &ctx->TMx, &ctx->BMws, &ctx->BMred, &ctx->PLMv, &ctx->PLMws};
+                        &ctx->IPAws, &ctx->IPAcnt, &ctx->IPAZ, &ctx->IPAsel, &ctx->IPAm, &ctx->IPAg, &ctx->IPAprev, &ctx->IPAsp, &ctx->DMd, &ctx->SMst, &ctx->TMst, &ctx->TMx, &ctx->BMws, &ctx->BMred, &ctx->PLMv, &ctx->PLMws,
+                        &ctx->AISst, &ctx->AISx, &ctx->AISb};
     for (gdca_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     ctx->staging.release();
@@ -1380,6 +1383,37 @@ static gdca_status temper_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t
     }
     gdca_launch_temper_finish(s, m.N, K, plan, state);
     return check_launch(ctx, "replica-exchange chains");
+}
+
+// The annealed chains (k_ais.hip) of K uniform starts over the state space of the template x_dev (nullptr: every site is free) under the
+// model m, along the HOST ladder betas[0 .. L]: the ladder into ctx->AISb, the starts into ctx->AISx, their energies (the energy stage)
+// and tables (the mutation stage, into ctx->DMd: q N K doubles) as of so many sequences -- temper_stage's pairing --, the proposals in
+// launches of at most SAMPLE_CHUNK, the reduction.  Between two launches a chain lives in its table and in ctx->AISst.
+static gdca_status ais_stage(gdca_ctx *ctx, const gdca_model &m, const int8_t *x_dev, int K, const double *betas, gdca_ais_plan plan)
+{
+    bool in_lds = false;
+    CHK(walk_placement(ctx, m.N, m.q, &in_lds));  // (before anything is enqueued; table_stage asks again)
+    hipStream_t s = ctx->stream;
+    CHK(ensure(ctx, ctx->AISb, ((size_t)plan.L + 1) * sizeof(double)));
+    CHK(ensure(ctx, ctx->AISx, (size_t)m.N * (size_t)K));
+    CHK(ensure(ctx, ctx->AISst, gdca_ais_state_bytes(m.N, K)));
+    void *state = ctx->AISst.p;
+    int8_t *Xst = (int8_t *)ctx->AISx.p;
+    HIPCHK(hipMemcpyAsync(ctx->AISb.p, betas, ((size_t)plan.L + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // (the caller's array is free once the call returns, whatever fails below)
+    plan.betas = (const double *)ctx->AISb.p;
+    gdca_launch_ais_start(s, x_dev, m.N, m.q, K, plan, Xst, state);
+    CHK(energy_stage(ctx, m, Xst, K, gdca_ais_E0(state, K)));
+    double *V = nullptr;  // (ctx->DMd: q N K doubles)
+    CHK(table_stage(ctx, m, Xst, K, &V, &in_lds));
+    const int n_steps = plan.chain.n_steps();
+    for (int t0 = 0; t0 < n_steps;) {
+        const int t1 = chunk_end(ctx, t0, n_steps);
+        HIPCHK(gdca_launch_ais(s, m.A, m.ld, m.sign, (const uint32_t *)ctx->Xg.p, m.N, m.q - 1, K, plan, t0, t1, V, in_lds, state));
+        t0 = t1;
+    }
+    gdca_launch_ais_reduce(s, K, (plan.chain.flags & GDCA_SAMPLE_GAPS) != 0 ? m.q : m.q - 1, plan, state);
+    return check_launch(ctx, "annealed importance sampling");
 }
 
 // -mJ in ctx->A (ld = n_pad) -> what `t` asks for
@@ -3760,6 +3794,35 @@ gdca_status gdca_run_sample_dev(gdca_ctx *ctx, const int8_t *Z_dev, int32_t N, i
     return run_target(ctx, Z_dev, N, M, q, p, sample_target(Z_dev, M, X_dev, K, r), st);
 }
 
+// the argument checks of the two log-partition entry points (nothing has run when one fails)
+static gdca_status check_log_partition(gdca_ctx *ctx, const void *mJ, const void *Pi, int N, int q, const void *x, const void *mask, int flags,
+                                       const double *betas, int L, int sweep, int K, const void *out4, const void *logw)
+{
+    if (L < 1 || sweep < 1) return fail(ctx, GDCA_EINVAL, "invalid L or sweep: each must be at least 1");
+    if ((long long)L * (long long)sweep > INT32_MAX) return fail(ctx, GDCA_EINVAL, "L * sweep is larger than INT32_MAX");
+    if (!betas || !out4 || !logw) return fail(ctx, GDCA_EINVAL, "null pointer");
+    CHK(validate_sample(ctx, N, q, K, flags, 0.0, 0, sweep, L, out4, logw));
+    if (betas[0] != 0.0) return fail(ctx, GDCA_EINVAL, "invalid betas: betas[0] must be 0 (the base distribution is the uniform one)");
+    for (int l = 0; l <= L; ++l)
+        if (!(betas[l] >= 0.0) || !std::isfinite(betas[l])) return fail(ctx, GDCA_EINVAL, "invalid betas: every beta must be finite and >= 0");
+    if (!mJ || !Pi) return fail(ctx, GDCA_EINVAL, "null pointer");
+    if (!x && mask) return fail(ctx, GDCA_EINVAL, "a mask needs a template x");
+    return GDCA_OK;
+}
+
+gdca_status gdca_log_partition_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *x_dev,
+                                   const int8_t *mask_dev, int32_t flags, const double *betas, int32_t L, int32_t sweep, int32_t K,
+                                   uint64_t seed, uint64_t stream0, double *out4_dev, double *logw_dev, double *E_end_dev, int8_t *X0_dev,
+                                   int8_t *Xout_dev, int32_t *accepted_dev, double *thr_dev, int32_t *moves_dev)
+{
+    CHK(check_log_partition(ctx, mJ_dev, Pi_dev, N, q, x_dev, mask_dev, flags, betas, L, sweep, K, out4_dev, logw_dev));
+    CHK(begin(ctx));
+    const gdca_ais_plan plan{{mask_dev, flags, seed, stream0, 0, sweep, L, thr_dev, moves_dev}, L, sweep, nullptr, out4_dev, logw_dev, E_end_dev,
+                             X0_dev, Xout_dev, accepted_dev};
+    CHK(ais_stage(ctx, operator_model(mJ_dev, Pi_dev, N, q), x_dev, K, betas, plan));
+    return sequences_checked(ctx);
+}
+
 // the argument checks the four replica-exchange entry points share (nothing has run when one fails); K chains as they will be used
 static gdca_status validate_temper(gdca_ctx *ctx, int N, int q, long long K, int R, const double *betas, int flags, int swap_every, int burn,
                                    int stride, int n_samples, const void *Xs, const void *accepted, const void *swaps, const void *Xr_out,
@@ -4777,6 +4840,32 @@ gdca_status gdca_run_sample(gdca_ctx *ctx, const int8_t *Z_host, int32_t N, int3
     CHK(sg.status());
     return sg.finish(gdca_run_sample_dev(ctx, Z_dev, N, M, q, p, X_dev, K, mask_dev, flags, beta, seed, stream0, burn, stride, n_samples,
                                          Xs_dev, dE_s_dev, accepted_dev, thr_dev, moves_dev, V_dev, st));
+}
+
+/* Log partition function with host pointers */
+gdca_status gdca_log_partition(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *x, const int8_t *mask,
+                               int32_t flags, const double *betas, int32_t L, int32_t sweep, int32_t K, uint64_t seed, uint64_t stream0,
+                               double *out4, double *logw, double *E_end, int8_t *X0, int8_t *Xout, int32_t *accepted, double *thr,
+                               int32_t *moves)
+{
+    CHK(check_log_partition(ctx, mJ, Pi, N, q, x, mask, flags, betas, L, sweep, K, out4, logw));
+    const size_t n = (size_t)N * (q - 1), k = (size_t)K, rows = (size_t)L * (size_t)sweep * k;
+    host_stage sg(ctx);
+    const double *mJ_dev = sg.in(mJ, n * n * sizeof(double));
+    const double *Pi_dev = sg.in(Pi, n * sizeof(double));
+    const int8_t *x_dev = sg.in(x, (size_t)N);
+    const int8_t *mask_dev = sg.in(mask, (size_t)N);
+    double *out4_dev = sg.out(out4, 4 * sizeof(double));
+    double *logw_dev = sg.out(logw, k * sizeof(double));
+    double *E_end_dev = sg.out(E_end, k * sizeof(double));
+    int8_t *X0_dev = sg.out(X0, (size_t)N * k);
+    int8_t *Xout_dev = sg.out(Xout, (size_t)N * k);
+    int32_t *accepted_dev = sg.out(accepted, k * sizeof(int32_t));
+    double *thr_dev = sg.out(thr, rows * sizeof(double));
+    int32_t *moves_dev = sg.out(moves, rows * sizeof(int32_t));
+    CHK(sg.status());
+    return sg.finish(gdca_log_partition_dev(ctx, mJ_dev, Pi_dev, N, q, x_dev, mask_dev, flags, betas, L, sweep, K, seed, stream0, out4_dev, logw_dev,
+                                            E_end_dev, X0_dev, Xout_dev, accepted_dev, thr_dev, moves_dev));
 }
 
 /* Replica-exchange chains with host pointers (fifteen arrays at the most: the pool has sixteen) */

@@ -1,6 +1,7 @@
-// What the greedy walk (k_walk.hip), the Metropolis chains (k_sample.hip) and the replica-exchange chains (k_temper.hip) share, each
-// stated once: the counter-based generator, the two-column update of the table of site potentials, and -- the two chain kernels' --
-// the LDS layout and the chain body (with, for their two launchers, the fill of its arguments).  The rule in full is include/gdca.h's ("greedy walk", "Metropolis chains").
+// What the greedy walk (k_walk.hip), the Metropolis chains (k_sample.hip), the replica-exchange chains (k_temper.hip) and the annealed
+// chains of the log partition function (k_ais.hip) share, each stated once: the counter-based generator, the two-column update of the
+// table of site potentials, and -- the chain kernels' -- the LDS layout and the chain body (with, for their launchers, the fill of its
+// arguments).  The rule in full is include/gdca.h's ("greedy walk", "Metropolis chains").
 //
 // The state is the symbols x (bytes, k_energy_pack's: 0 .. s, s = the gap) and the table V[i][c], with
 //
@@ -147,10 +148,22 @@ struct chain_args {
     int N, sdim, G, gaps, n_steps, t0, t1;  // G: the chains of the launch, one workgroup each
 };
 
-// The proposals t0 .. t1 - 1 of chain g at the inverse temperature beta; after(tt, x, sum) behind proposal tt.  -> the proposals this
-// launch accepted (every thread's count is the same)
-template <bool TL, class After>
-__device__ __forceinline__ int chain_run(const chain_args &p, double *lds, size_t g, double beta, After after)
+// the inverse temperature of proposal tt: a chain's one beta, or a workgroup-uniform function of tt (k_ais.hip: a ladder's stage)
+__device__ __forceinline__ double beta_at(double beta, int)
+{
+    return beta;
+}
+
+template <class F>
+__device__ __forceinline__ double beta_at(const F &beta, int tt)
+{
+    return beta(tt);
+}
+
+// The proposals t0 .. t1 - 1 of chain g at the inverse temperature beta_at(beta, tt); after(tt, x, sum) behind proposal tt.  -> the
+// proposals this launch accepted (every thread's count is the same)
+template <bool TL, class Beta, class After>
+__device__ __forceinline__ int chain_run(const chain_args &p, double *lds, size_t g, Beta beta, After after)
 {
     const int N = p.N, sdim = p.sdim, q = sdim + 1, n = N * sdim;
     const int t = threadIdx.x, lane = t & 63;
@@ -214,7 +227,7 @@ __device__ __forceinline__ int chain_run(const chain_args &p, double *lds, size_
             a = x[i];
             b = v + (v >= a);
             dE = ent(i, b) - ent(i, a);
-            go = beta * dE <= thr;  // (false for a NaN on the left)
+            go = beta_at(beta, tt) * dE <= thr;  // (false for a NaN on the left)
             code = i * q + b;
         }
         const int acc = __builtin_amdgcn_readfirstlane(go ? 1 : 0);

@@ -458,6 +458,28 @@ hipError_t gdca_launch_temper_chain(hipStream_t s, const double *A, size_t ld, d
 void gdca_launch_temper_round(hipStream_t s, int N, int K, const gdca_temper_plan &plan, int e, int js, void *state);
 void gdca_launch_temper_finish(hipStream_t s, int N, int K, const gdca_temper_plan &plan, void *state);
 
+// ---- k_ais.hip: log partition function by annealed importance sampling -- one workgroup a chain along a ladder of inverse temperatures --
+// (include/gdca.h, Log partition function).  Xg, V, A, ld, sign and the table's placement as k_sample's.
+struct gdca_ais_plan {
+    gdca_chain_plan chain;  // burn 0, stride = sweep, n_samples = L; thr, moves: [K][n_steps]
+    int L, sweep;
+    const double *betas;    // [L + 1], DEVICE
+    double *out4, *logw;    // [4], [K]
+    double *E_end;          // [K] or nullptr
+    int8_t *X0, *Xout;      // [K][N] or nullptr each
+    int32_t *accepted;      // [K] or nullptr
+};
+// what the chains keep in HBM beside their tables: the running sums, the log-weights, E0, the counts, the length of the site list, the symbols
+size_t gdca_ais_state_bytes(int N, int K);
+double *gdca_ais_E0(void *state, int K);  // where the stage writes the start energies (K doubles)
+// the uniform starts of the K chains from the template x (nullptr: every site is free) into Xst (N x K) and, where asked, plan.X0
+void gdca_launch_ais_start(hipStream_t s, const int8_t *x, int N, int q, int K, const gdca_ais_plan &plan, int8_t *Xst, void *state);
+// The proposals t0 .. t1 - 1 of every chain, each at the beta of its stage; the last launch writes the outputs; errors as gdca_launch_sample's
+hipError_t gdca_launch_ais(hipStream_t s, const double *A, size_t ld, double sign, const uint32_t *Xg, int N, int sdim, int K,
+                           const gdca_ais_plan &plan, int t0, int t1, double *V, bool table_in_lds, void *state);
+// plan.out4 from plan.logw; T: the target symbols of a site
+void gdca_launch_ais_reduce(hipStream_t s, int K, int T, const gdca_ais_plan &plan, void *state);
+
 // ---- k_bm.hip: Boltzmann-machine refinement -- the warm start, the parameter update and the fit read-out of the Potts model (W, 0) ------
 // (include/gdca.h, Boltzmann-machine refinement).  Every matrix is n x n column-major with ld = n, n = N sdim.
 // W from the lower triangle of mJ and g = mJ Pi (gdca_launch_energy_g); W may not alias mJ

@@ -789,6 +789,123 @@ def sample_tempered(mJ, Pi, X, q: int = 21, betas=(1.0,), swap_every=None, burn=
     return tuple(a for a in out if a is not None)
 
 
+def _ladder_arg(betas, n_stages, beta):
+    """the ladder of annealed importance sampling, checked: f64 (L + 1,), betas[0] == 0; betas None: np.linspace(0, beta, n_stages + 1)"""
+    if betas is None:
+        if not isinstance(n_stages, (int, np.integer)) or n_stages < 1:
+            raise ArgumentError(f"invalid n_stages value: {n_stages} (must be an integer >= 1)")
+        try:
+            beta = float(beta)
+        except (TypeError, ValueError):
+            raise ArgumentError(f"invalid beta value: {beta} (must be a finite number >= 0)") from None
+        if not (beta >= 0.0 and np.isfinite(beta)):
+            raise ArgumentError(f"invalid beta value: {beta} (must be a finite number >= 0)")
+        return np.linspace(0.0, beta, int(n_stages) + 1)
+    try:
+        b = np.asarray(betas, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ArgumentError(f"invalid betas: {betas} (must be at least two finite numbers >= 0, the first 0)") from None
+    if b.size < 2:
+        raise ArgumentError(f"invalid betas: {b.size} values (must be at least two finite numbers >= 0, the first 0)")
+    if not np.all(np.isfinite(b) & (b >= 0.0)):
+        raise ArgumentError(f"invalid betas: {betas} (every beta must be a finite number >= 0)")
+    if b[0] != 0.0:
+        raise ArgumentError(f"invalid betas: betas[0] = {b[0]} (must be 0: the chains start from the uniform distribution)")
+    return np.ascontiguousarray(b)
+
+
+def _state_space(N, q, x, mask, gaps):
+    """the state space of annealed importance sampling, checked: (x int8 (N,) or None, mask int8 (N,) or None, free (N,) bool)"""
+    if x is None:
+        if mask is not None:
+            raise ArgumentError("mask needs a template x (the symbols of the sites that do not move)")
+        return None, None, np.ones(N, dtype=bool)
+    xa = np.asarray(x)
+    if xa.shape != (N,) or not np.issubdtype(xa.dtype, np.integer) or (xa.size and (xa.min() < 1 or xa.max() > q)):
+        raise ArgumentError(f"x must be a vector of {N} integer symbols between 1 and q = {q}")
+    xa = np.ascontiguousarray(xa, dtype=np.int8)
+    free = np.ones(N, dtype=bool) if gaps else xa != q
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.shape != (N,) or not (m.dtype == np.bool_ or np.issubdtype(m.dtype, np.integer)):
+            raise ArgumentError(f"mask must be a vector of {N} booleans or integers, one per site")
+        mask = np.ascontiguousarray(m != 0, dtype=np.int8)
+        free &= mask != 0
+    return xa, mask, free
+
+
+def log_partition(mJ, Pi, q: int = 21, betas=None, n_stages: int = 100, beta: float = 1.0, sweep=None, K: int = 1024, x=None, mask=None,
+                  gaps: bool = False, seed: int = 0, stream0: int = 0, trace: bool = False, ctx=None):
+    """log Z(beta) = log sum_x exp(-beta E(x)) of the model (mJ, Pi) read as a Potts model -- a fit of ``gDCA_bm`` or ``gDCA_plm`` as
+    (W, zeros), or the Gaussian fit as the chains read it -- by annealed importance sampling (Neal 2001).  The sum runs over the state
+    space of the template ``x`` (N symbols 1..q): the sites ``mask`` lets change (default all) take every residue, or with ``gaps=True``
+    every symbol; without it the template's gaps stay gaps; every other site keeps the template's symbol.  ``x=None`` (no mask then):
+    every site is free.  K chains start at uniform draws from that space and run ``sweep`` Metropolis proposals (default one sweep,
+    the number of free sites) at each of the inverse temperatures ``betas[1:]``, ``betas[0] == 0`` (default
+    ``np.linspace(0, beta, n_stages + 1)``); chain k's weight is the product of exp(-(betas[l] - betas[l-1]) E) over the states it
+    stood in ahead of every stage, and |Omega| mean(w) estimates Z(betas[-1]) without bias for any ladder and any sweep.
+
+    Returns ``(logZ, ess, logw (K,))``: the estimate, the effective sample size (sum w)^2 / sum w^2 in [1, K] -- an ess far below K
+    says the ladder is too coarse or the sweeps too short -- and the chains' log-weights; with ``trace=True`` also ``E_end (K,)``,
+    ``X0 (N, K)`` and ``Xout (N, K)`` int8 (the starts and the final states: with logw a weighted sample of the target),
+    ``accepted (K,)`` int32, ``thr`` and ``moves (K, n_steps)`` as ``sample`` returns them.  mJ must be symmetric (its lower triangle
+    is read)."""
+    mJ = np.ascontiguousarray(mJ, dtype=np.float64)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    if not isinstance(q, (int, np.integer)) or q < 2:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if q >= 32:
+        raise ArgumentError(f"parameter q={q} is too big (max 31 is allowed)")
+    n = Pi.shape[0] if Pi.ndim == 1 else -1
+    if n < 1 or n % (int(q) - 1) or mJ.shape != (n, n):
+        raise ArgumentError(f"incompatible sizes: q = {q}, mJ {mJ.shape}, Pi {Pi.shape} (mJ must be n x n, Pi have n = N (q - 1) entries)")
+    N = n // (int(q) - 1)
+    b = _ladder_arg(betas, n_stages, beta)
+    if not isinstance(K, (int, np.integer)) or K < 1:
+        raise ArgumentError(f"invalid K value: {K} (must be an integer >= 1)")
+    xa, m, free = _state_space(N, int(q), x, mask, gaps)
+    sweep = max(int(free.sum()), 1) if sweep is None else sweep
+    if not isinstance(sweep, (int, np.integer)) or sweep < 1:
+        raise ArgumentError(f"invalid sweep value: {sweep} (must be an integer >= 1)")
+    L = b.size - 1
+    if L * int(sweep) > 2**31 - 1:
+        raise ArgumentError(f"invalid sweep value: {L} stages of {sweep} proposals are more than 2^31 - 1")
+    _, _, _, _, seed, stream0, _, flags = _sample_args(N, q, 1.0, 0, 1, 1, seed, stream0, None, gaps)
+    ctx = ctx or default_context()
+    out = ctx.log_partition_outputs(N, int(K), L * int(sweep), trace)
+    opt = lambda a: None if a is None else _lib._p(a)  # noqa: E731
+    ctx.check(ctx.lib.gdca_log_partition(ctx.h, _lib._p(mJ), _lib._p(Pi), N, int(q), opt(xa), opt(m), flags, _lib._p(b), L, int(sweep), int(K),
+                                         seed, stream0, *[opt(a) for a in out]))
+    return (float(out[0][0]), float(out[0][1]), out[1]) + tuple(a for a in out[2:] if a is not None)
+
+
+def potts_loglik(mJ, Pi, X, q: int = 21, **kw):
+    """The log-likelihood of the K columns of X (shape (N, K), symbols 1..q) under the Potts reading of (mJ, Pi):
+    ``L[k] = -beta E(x_k) - logZ`` with E from ``sequence_energies`` and (logZ, ess) from ``log_partition(mJ, Pi, q, **kw)`` at its
+    target temperature (default beta = 1: ``L = -E - logZ``) -- what makes a held-out score of a ``gDCA_plm`` or a ``gDCA_bm`` fit
+    comparable across fits.  Every sequence must lie in the state space logZ sums over: no gap without ``gaps=True`` (or outside the
+    template's gaps), and the template's symbol at every site that does not move.  Returns ``(L (K,), logZ, ess)``."""
+    if kw.get("trace"):
+        raise ArgumentError("trace is not an argument of potts_loglik (log_partition returns the traces)")
+    Xf = _symbols(X, "X")
+    N, K = Xf.shape
+    if not isinstance(q, (int, np.integer)) or not 2 <= q <= 31:
+        raise ArgumentError(f"invalid q value: {q} (must be an integer between 2 and 31)")
+    if K < 1:
+        raise ArgumentError("X holds no sequence")
+    if Xf.min() < 1 or Xf.max() > q:
+        raise ArgumentError("X must hold integer symbols between 1 and q")
+    b = _ladder_arg(kw.get("betas"), kw.get("n_stages", 100), kw.get("beta", 1.0))
+    xa, _, free = _state_space(N, int(q), kw.get("x"), kw.get("mask"), bool(kw.get("gaps", False)))
+    if not kw.get("gaps", False) and np.any(Xf[free] == q):
+        raise ArgumentError("X holds a sequence outside the state space: a gap at a free site (gaps=True makes the gap a symbol)")
+    if xa is not None and np.any(Xf[~free] != xa[~free, None]):
+        raise ArgumentError("X holds a sequence outside the state space: it differs from the template x at a site that does not move")
+    logZ, ess, _ = log_partition(mJ, Pi, q, **kw)
+    E = sequence_energies(mJ, Pi, Xf, q, ctx=kw.get("ctx"))
+    return -(b[-1] * E) - logZ, logZ, ess
+
+
 def potts_independent(Pi, N: int, q: int = 21):
     """The independent-site Potts model (W, zeros) of the single-site frequencies Pi (n = N (q - 1) entries, all and every site's gap
     frequency 1 - sum positive): couplings zero, W[r, r] = -2 log(Pi[r] / Pi_gap(site)) -- the start of ``gDCA_bm(init="independent")``."""

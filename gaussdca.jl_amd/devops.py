@@ -242,6 +242,36 @@ def sample_tempered_dev(ctx: Context, dmJ, dPi, N: int, q: int, dXr, K: int, bet
     return dXs, daccepted, dswaps, dXr_out, dslot_out, dE_s, dthr, dmoves, dswap_thr, dslot_path
 
 
+def log_partition_dev(ctx: Context, dmJ, dPi, N: int, q: int, betas, sweep: int, K: int, dx=None, dmask=None, flags: int = 0, seed: int = 0,
+                      stream0: int = 0, dout=None, dlogw=None, dE_end=None, dX0=None, dXout=None, daccepted=None, dthr=None, dmoves=None,
+                      want=()):
+    """log Z(betas[-1]) of the Potts reading of (mJ, Pi) by annealed importance sampling with every array in HBM
+    (gdca_log_partition_dev): K chains from uniform starts over the state space of the template dx (N int8; None: every site is free,
+    and then no mask), L = len(betas) - 1 stages of ``sweep`` proposals, betas[0] == 0.  out4 (log Z, effective sample size, max logw,
+    log |Omega|) and logw (K f64) are always made; ``want`` names the optional outputs a buffer is made for where none is given: "E_end"
+    (K f64), "X0", "Xout" (N x K int8), "accepted" (K int32), "thr" (n_steps x K f64), "moves" (n_steps x K int32).  Returns (dout,
+    dlogw, dE_end, dX0, dXout, daccepted, dthr, dmoves), None for what was not wanted."""
+    K, T = int(K), (len(betas) - 1) * int(sweep)
+    dout = dout or DeviceBuffer(ctx, 32)
+    dlogw = dlogw or DeviceBuffer(ctx, 8 * max(K, 1))
+    if "E_end" in want:
+        dE_end = dE_end or DeviceBuffer(ctx, 8 * max(K, 1))
+    if "X0" in want:
+        dX0 = dX0 or DeviceBuffer(ctx, max(N * K, 1))
+    if "Xout" in want:
+        dXout = dXout or DeviceBuffer(ctx, max(N * K, 1))
+    if "accepted" in want:
+        daccepted = daccepted or DeviceBuffer(ctx, 4 * max(K, 1))
+    if "thr" in want:
+        dthr = dthr or DeviceBuffer(ctx, 8 * max(T * K, 1))
+    if "moves" in want:
+        dmoves = dmoves or DeviceBuffer(ctx, 4 * max(T * K, 1))
+    opt = lambda b: None if b is None else _ptr(b).value  # noqa: E731
+    ctx.log_partition_dev(_ptr(dmJ).value, _ptr(dPi).value, N, int(q), opt(dx), opt(dmask), int(flags), betas, int(sweep), K, int(seed),
+                          int(stream0), opt(dout), opt(dlogw), opt(dE_end), opt(dX0), opt(dXout), opt(daccepted), opt(dthr), opt(dmoves))
+    return dout, dlogw, dE_end, dX0, dXout, daccepted, dthr, dmoves
+
+
 def potts_from_gaussian_dev(ctx: Context, dmJ, dPi, N: int, q: int, dW=None):
     """The Gaussian model (mJ, Pi) as a Potts model (W, zeros) in mJ's layout, every array in HBM (gdca_potts_from_gaussian_dev):
     off-diagonal blocks the bits of mJ, W[r, r] = mJ[r, r] - 2 (mJ Pi)[r], the rest of a diagonal block +0.0.  W may not be mJ."""

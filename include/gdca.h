@@ -806,6 +806,61 @@ gdca_status gdca_run_sample_tempered_dev(gdca_ctx *ctx, const int8_t *Z_dev, int
                                          int8_t *Xr_out_dev, int32_t *slot_out_dev, double *thr_dev, int32_t *moves_dev,
                                          double *swap_thr_dev, int32_t *slot_path_dev, gdca_stats *st);
 
+/* ---- Log partition function (annealed importance sampling) ---------------------------------------------------------------------------
+ * The discrete models -- (W, zeros) of gdca_bm_learn* and gdca_plm_learn*, and (mJ, Pi) read as a Potts model by the chains -- have
+ * energies without a normaliser.  Annealed importance sampling (Neal 2001) estimates log Z(beta) = log sum_{x in Omega} exp(-beta E(x)):
+ * K chains start at uniform draws from Omega, run the Metropolis chain along a ladder of inverse temperatures from 0 to beta, and
+ * carry the product of the ratios exp(-(betas[l] - betas[l-1]) E) met on the way; |Omega| mean_k(w_k) is an unbiased estimate of Z
+ * for any ladder and any number of proposals a stage.  With it -E(x) - log Z is a log-likelihood, and S = log Z + <E> the
+ * model's entropy.  Conventions, flags, mask, `sites`, T, proposal, `beta * dE <= thr`, table update and generator (mix64, key, draw)
+ * are the Metropolis-chain section's.
+ * STATE SPACE Omega.  A template x (N int8) fixes what does not move: sites = the template's site list (mask, and without
+ * GDCA_SAMPLE_GAPS the template's gaps stay gaps), |Omega| = T^n_sites.  x == NULL is allowed only with mask == NULL and means that
+ * every site is free.
+ * LADDER.  betas: a HOST array of L + 1 f64, L >= 1; betas[0] must be exactly 0 (the base distribution is the uniform one); every
+ * entry finite and >= 0; monotonicity is not required; betas[L] is the temperature whose Z is estimated.  The array is uploaded into a
+ * grow-only context buffer (a ladder may be far longer than GDCA_TEMPER_MAX).
+ * START of chain k (K chains, stream stream0 + k).  ikey = mix64(~key(seed, stream0 + k)) (the replica-exchange section's skey: no
+ * swaps exist here).  The site at list position m gets the 0-based symbol ((draw(ikey, m) >> 32) * T) >> 32; every other site keeps the
+ * template's symbol.  Known answers: (seed, stream) = (0, 0) has ikey = 0x1c44fab6a246bae2; m = 0 draws 0x3dc548297666b4b4: 0-based
+ * symbol 0 at T = 3, 0 at T = 4, 4 at T = 20, 5 at T = 21; m = 4 draws 0xace4d333b149e3d1: 2, 2, 13, 14; m = 69 draws
+ * 0x8537d76ccb32cd7e: 1, 2, 10, 10.
+ * START TABLE AND ENERGY.  V0 = the bits gdca_mutation_scan(.., GDCA_MUT_POTENTIAL) returns for the start, E0 = the bits
+ * gdca_energies_dev returns for it (the replica-exchange section's pairing).
+ * STAGES l = 1 .. L, each of sweep >= 1 proposals; all arithmetic f64, one rounding an operation, no contraction.
+ *     weight step   E = E0 + S, S the running sum of the accepted dE at that moment (+0.0 ahead of stage 1);
+ *                   logw = logw + (betas[l-1] - betas[l]) * E: one subtraction, one multiplication, one addition; logw starts at +0.0;
+ *     proposals     t = (l - 1) sweep .. l sweep - 1, exactly the Metropolis section's proposal t, at beta = betas[l].
+ * n_steps = L * sweep <= INT32_MAX.  E_end = E0 + S after the last proposal.  One thread keeps logw, as one thread keeps S.
+ * REDUCTION (out4), on the device in a fixed order, no floating-point atomics:  m = max_k logw[k];  e_k = exp(logw[k] - m);
+ * S1 = sum e_k and S2 = sum e_k * e_k, each summed as gdca_bm_readout_dev sums (256 strided partials, partial t the terms
+ * k = t, t + 256, .. ascending added to +0.0, folded by the halving tree t and t + 128, t and t + 64, ..);
+ * log_omega = (double)n_sites * log((double)T);
+ *     out[0] = log_omega + (m + log(S1 / (double)K))     the estimate of log Z(betas[L]) over Omega
+ *     out[1] = S1 * S1 / S2                              the effective sample size, in [1, K]
+ *     out[2] = m                                         out[3] = log_omega
+ * Any non-finite logw[k] makes out[0] and out[1] NaN.  exp and log are the device library's: their bits are not pinned.
+ * OUTPUTS (column-major).  Required: out4 (4 f64), logw (K f64).  Optional, each may be NULL: E_end (K f64); X0 (N x K int8, the
+ * starts); Xout (N x K int8, the final states: with logw a weighted sample of the target); accepted (K int32); thr, moves (n_steps x K,
+ * gdca_sample_dev's meaning).
+ * ORDER: the bits depend on the model, the template, mask, flags, betas, sweep, seed, the chain's stream number and the values of thr
+ * -- not on where the chain stands in the batch, on WALK_TABLE or on SAMPLE_CHUNK (a cut may fall inside a stage).  logw[k] and the
+ * traces do not depend on K; out4 depends on K by definition and is the same bits from run to run.
+ * GDCA_EINVAL, nothing run: whatever gdca_sample_dev refuses for K, q, flags, N and the table's placement, and T < 2; L < 1 or
+ * sweep < 1; L * sweep > INT32_MAX; betas[0] != 0, or a beta negative, NaN or infinite; a null betas, out4 or logw; x == NULL together
+ * with a mask.  A template byte outside 1..q is detected on the device as in the chains (such a site is never free).  The tables live
+ * in the context's workspace of q N K doubles.  Synchronous.  New symbols only: gdca_stats and gdca_params are unchanged.  There is no
+ * fused gdca_run_* form (as with gdca_bm_learn_dev the users are fitted Potts models). */
+gdca_status gdca_log_partition_dev(gdca_ctx *ctx, const double *mJ_dev, const double *Pi_dev, int32_t N, int32_t q, const int8_t *x_dev,
+                                   const int8_t *mask_dev, int32_t flags, const double *betas, int32_t L, int32_t sweep, int32_t K,
+                                   uint64_t seed, uint64_t stream0, double *out4_dev, double *logw_dev, double *E_end_dev, int8_t *X0_dev,
+                                   int8_t *Xout_dev, int32_t *accepted_dev, double *thr_dev, int32_t *moves_dev);
+/* ... with host pointers: upload, the _dev form, download */
+gdca_status gdca_log_partition(gdca_ctx *ctx, const double *mJ, const double *Pi, int32_t N, int32_t q, const int8_t *x, const int8_t *mask,
+                               int32_t flags, const double *betas, int32_t L, int32_t sweep, int32_t K, uint64_t seed, uint64_t stream0,
+                               double *out4, double *logw, double *E_end, int8_t *X0, int8_t *Xout, int32_t *accepted, double *thr,
+                               int32_t *moves);
+
 /* ---- Boltzmann-machine refinement: fit the Potts model the Metropolis chains draw from ----------------------------------------------
  * The chains sample exp(-beta E) with E(x) = 1/2 (x - Pi)' mJ (x - Pi): read that way (mJ, Pi) IS a Potts model -- couplings the
  * off-diagonal blocks of mJ, fields g - 1/2 diag(mJ), g = mJ Pi.  These entry points fit that model to a family's one- and two-site
